@@ -14,13 +14,17 @@ scaling).  Rank 0 prints ONE JSON line.
 
 How the timed region is taken: an untimed clock-settle loop (64-launch blocks until three consecutive block times agree within
 1 %, at most --prewarm seconds; config.clock_prewarm_s), the W warm-up steps, barrier + synchronise, then EXACTLY K timed steps,
-synchronise + barrier: `value` / `ms_per_step` / `roofline` are that FIRST region.  --regions (9) identical regions follow it and
-are reported beside it (headline_regions_ms, official_over_median): how representative the one graded sample was.
-
-Extra objects on that line:
+synchronise + barrier: `value` / `ms_per_step` / `roofline` are that FIRST region.
   roofline      dominant kernel vs the HBM roofline: algorithmic bytes per launch
                 (2*hop + 4*N per frame) / average launch duration measured with HIP events on
                 the launch stream over the timed region.
+That is all a plain run does, besides --dump-outputs DIR: the rows the last timed step computed, as DIR/mag_rows.npy,
+float32, a seeded sample of them where they exceed 32 MiB; the inputs are seeded, so two builds can be compared output for
+output.
+
+With --full, --regions (9) identical regions follow it and are reported beside it (headline_regions_ms,
+official_over_median): how representative the one graded sample was; the first rows are checked against numpy
+(parity_rel_l2_first_rows); and these objects join the line:
   cpu_baseline  the reference-shaped CPU loop (oracle/fsea_oracle.c, kind "port") timed on this
                 host's cores on a bounded sample of the same workload; the transform inside it is
                 an FFTW3-API library's when the host has one (libfftw3 is not installed in this
@@ -58,6 +62,24 @@ WORKLOADS = {
 
 
 EXTRA_REGIONS = 5   # timed regions per informational figure (median reported)
+DUMP_BYTES = 32 << 20   # --dump-outputs: at most this many bytes of rows per array (a seeded sample of the rows beyond it)
+DUMP_SEED = 20261015
+
+
+def dump_rows(total, row_bytes):
+    """Indices of the rows --dump-outputs writes: all `total` when they fit in DUMP_BYTES, else a fixed, seeded, sorted sample
+    of as many as do -- the same rows for the same arguments in every run and every build."""
+    keep = max(1, min(total, DUMP_BYTES // row_bytes))
+    if keep == total:
+        return np.arange(total)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(total, keep, replace=False))
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: every array as float32 DIR/<name>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def numpy_rows(raw_u8, n_frames, n, hop, mode="mag", window=None):
@@ -126,12 +148,14 @@ def settle_clock(torch, step, limit_s, block=64, agree=0.01, need=3, floor_s=0.2
     return time.perf_counter() - t_pre, len(times)
 
 
-def run_gpu(args, workload, rank, world, dist, torch, steps, warmup, sets, repeats=1, window=None, official_first=False):
+def run_gpu(args, workload, rank, world, dist, torch, steps, warmup, sets, repeats=1, window=None, official_first=False,
+            dump=False):
     """K = `steps` timed steps of `workload` behind `warmup` untimed ones.  repeats > 1: the timed region is measured that
     many times back to back.  official_first (the headline): the FIRST region is the reported one -- the contract's W warm-ups
     + exactly K timed steps -- and the later, identical regions are reported beside it (`regions`); otherwise (the
     informational `extra` runs) the MEDIAN region is reported, so that a 20-step region of a side workload is not one
-    sample.  window: a taper name for fsea_plan_set_window, or None."""
+    sample.  window: a taper name for fsea_plan_set_window, or None.  dump: return the rows of the last timed step
+    (dump_rows' sample of them) as `dumped`, {name: float32 array}."""
     from frequensea_amd import fsea
 
     n, frames, hop = WORKLOADS[workload]
@@ -197,6 +221,16 @@ def run_gpu(args, workload, rank, world, dist, torch, steps, warmup, sets, repea
     if dist is not None:
         dist.barrier()
         torch.cuda.synchronize()
+    dumped = None
+    if dump:
+        # the buffer set the last timed step wrote (step() was last called with warmup + repeats * steps - 1); nothing has
+        # been launched since, so it holds what that step returned to its caller
+        last = (warmup + max(1, repeats) * steps - 1) % sets
+        idx = dump_rows(frames, 4 * n)
+        rows = outs[last].view(frames, n)
+        if len(idx) < frames:
+            rows = rows.index_select(0, torch.from_numpy(idx).to(dev))
+        dumped = {"mag_rows": rows.cpu().numpy()}
     if official_first:
         # the headline: `value` is the FIRST K-step region (the bench contract: W warm-ups, then exactly K timed steps);
         # the identical regions behind it only say how representative that one sample was
@@ -212,7 +246,7 @@ def run_gpu(args, workload, rank, world, dist, torch, steps, warmup, sets, repea
     # Informational only (never `value`): the same steps issued alternately on two streams, so that
     # one launch's drain overlaps the next one's ramp -- what a double-buffered consumer would see.
     two_stream = None
-    if world == 1 and (args.two_stream or not args.no_extra) and workload.startswith("batch"):
+    if world == 1 and args.full and (args.two_stream or not args.no_extra) and workload.startswith("batch"):
         streams = [torch.cuda.Stream(), torch.cuda.Stream()]
         torch.cuda.synchronize()
         # the same clock pre-warm as the one-stream figure gets, on the two streams: 20 launches from a chip that has
@@ -243,7 +277,7 @@ def run_gpu(args, workload, rank, world, dist, torch, steps, warmup, sets, repea
     plan.close()
     return dict(n=n, frames=frames, hop=hop, wall=wall, kernel_ms=kernel_ms, kernel=kname, grid=grid, two_stream=two_stream,
                 sample=sample, host_head=np.roll(host, 0)[: 2 * 4 * hop + 2 * n], steps=steps, regions=regions,
-                prewarm_s=prewarm_s, settle_blocks=settle_blocks)
+                prewarm_s=prewarm_s, settle_blocks=settle_blocks, dumped=dumped)
 
 
 def pinned_checksums():
@@ -1035,7 +1069,19 @@ def main():
                     help="skip the sharded sweep + stream (RCCL gather) that follow the headline steps in `extra`")
     ap.add_argument("--multi-gpu-timeout", type=float, default=240.0,
                     help="seconds the multi-GPU leg may take before the line is printed without it (extra.multi_gpu_error)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the --regions regions behind the official one, the numpy "
+                         "guard on its rows, `extra` (other sizes, workloads and tapers, two streams, host path, nrf API, energy, "
+                         "ceilings, the multi-GPU leg) and the CPU baseline.  Without it a run sets up, warms up, times the K "
+                         "steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32: "
+                         "a fixed, seeded sample of its rows when the whole output exceeds %d MiB" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     # Kernel arguments in device memory instead of host-coherent memory: the first s_load of a launch
     # otherwise crosses PCIe (about 0.5 us per 54 us launch here).  A HIP runtime knob, read when HIP
@@ -1071,15 +1117,29 @@ def main():
 
     if args.workload in ("broad", "stft16384stream"):
         fn = run_broad if args.workload == "broad" else run_stft_stream
-        line = fn(args, rank, world, dist, torch, max(1, args.steps), max(1, args.warmup))
+        keep = {} if args.dump_outputs else None
+        line = fn(args, rank, world, dist, torch, max(1, args.steps), max(1, args.warmup), keep=keep)
         if rank == 0:
+            if keep and args.workload == "broad":               # the stitched u8 image: a seeded sample of its tiles
+                n = keep["n"]
+                tiles = dump_rows(keep["tiles"], 4 * keep["rows"] * n)
+                img = keep["image"]
+                write_outputs(args.dump_outputs, {"stitched_tiles": torch.stack(
+                    [img[:, t * n:(t + 1) * n] for t in tiles.tolist()]).cpu().numpy()})
+            elif keep:                                          # the gathered f32 rows of the stream
+                idx = dump_rows(keep["frames"], 4 * keep["n"])
+                rows = keep["rows"].index_select(0, torch.from_numpy(idx).to(keep["rows"].device))
+                write_outputs(args.dump_outputs, {"mag_rows": rows.cpu().numpy()})
             print(json.dumps(line))
         if dist is not None:
             dist.destroy_process_group()
         return
 
     res = run_gpu(args, args.workload, rank, world, dist, torch, args.steps, args.warmup, args.sets, window=args.window,
-                  repeats=1 + max(0, args.regions), official_first=True)
+                  repeats=1 + (max(0, args.regions) if args.full else 0), official_first=True,
+                  dump=bool(args.dump_outputs) and rank == 0)
+    if res["dumped"] is not None:
+        write_outputs(args.dump_outputs, res["dumped"])
     n, frames, hop = res["n"], res["frames"], res["hop"]
     # The timed region is the K steps between the opening and the closing barrier + device synchronise; `value` and
     # `ms_per_step` are the HOST WALL CLOCK of that region (MAX over ranks), as the bench contract defines them and as every
@@ -1165,7 +1225,7 @@ def main():
         except Exception:
             pass
 
-    if rank == 0:
+    if args.full and rank == 0:
         # correctness guard on what was just timed
         want = numpy_rows(res["host_head"], 4, n, hop, window=args.window)
         rel = float(np.linalg.norm(res["sample"] - want) / np.linalg.norm(want))
@@ -1174,13 +1234,13 @@ def main():
             raise SystemExit("bench: GPU rows differ from the numpy guard (rel %.3e)" % rel)
 
     br = None
-    if args.workload == "batch8192x4096" and not args.window and not args.no_extra:
+    if args.full and args.workload == "batch8192x4096" and not args.window and not args.no_extra:
         start_guardian(line, rank)                                # from here on a hard failure still leaves the headline's line
-    if world > 1 and args.workload == "batch8192x4096" and not args.window and not args.no_multi_gpu_leg and not args.no_extra:
+    if args.full and world > 1 and args.workload == "batch8192x4096" and not args.window and not args.no_multi_gpu_leg and not args.no_extra:
         # The driver's N > 1 command line: after the headline's steps, the workloads north_star actually scales over a node
         mg_flat, mg_lines = guarded_multi_gpu_leg(args, rank, world, dist, torch, line)
         line["extra"] = mg_flat
-    if world == 1 and not args.no_extra and args.workload == "batch8192x4096" and not args.window:
+    if args.full and world == 1 and not args.no_extra and args.workload == "batch8192x4096" and not args.window:
         # Everything in `extra` is informational.  Each figure: the same clock pre-warm as the headline, then the MEDIAN of
         # EXTRA_REGIONS timed regions of K' steps (HIP events per region) -- not one sample of a 20-step region.
         R = EXTRA_REGIONS
@@ -1243,7 +1303,7 @@ def main():
         mg_flat, mg_lines = guarded_multi_gpu_leg(args, rank, world, dist, torch, line)
         line["extra"].update(mg_flat)
         br = mg_lines.get("broad_resident")
-    if world == 1 and not args.no_extra and args.workload == "batch8192x4096" and not args.window and br is not None:
+    if args.full and world == 1 and not args.no_extra and args.workload == "batch8192x4096" and not args.window and br is not None:
         line["extra"].update({"broad_sweep_1gpu_frames_per_sec": br["value"], "broad_sweep_1gpu_ms": br["ms_per_step"],
                               "broad_sweep_1gpu_kernel_ms": br["ms_per_step_kernel_events"],
                               "broad_sweep_1gpu_host_issue_ms": br["host_issue_ms_per_step"],
@@ -1254,7 +1314,7 @@ def main():
                                                   "kernel_ms = the tiled FFT launch by HIP events; the difference is the first "
                                                   "submission + last synchronise of a 20-step region (a few tens of us) spread "
                                                   "over its steps, plus Python's per-step issue time where that exceeds the kernel"})
-    if world == 1 and not args.no_extra and args.workload == "batch8192x4096" and not args.window:
+    if args.full and world == 1 and not args.no_extra and args.workload == "batch8192x4096" and not args.window:
         line["extra"].update(host_path_rate(n, frames))
         line["extra"].update(nrf_stream_rate())
         # what bounds the headline kernel from above on THIS box, same launch shape and buffer rotation: its I/O skeleton
@@ -1273,7 +1333,7 @@ def main():
                                                      "0.25 s pre-warm, median of 5 rounds of 120 launches): compare the kernel with "
                                                      "them through kernel_over_*, not through `frac`"})
 
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cores, quota_note = effective_cpus()
         cb = cpu_baseline(n, hop, cores, args.cpu_budget,
                           nrf_stream=not args.no_extra and args.workload == "batch8192x4096")

@@ -9,7 +9,7 @@
 #   2. bench.py at 1, 2, 4 ... N ranks: the headline (frames sharded, no collective), the fft-batch-broad sweep with
 #      resident and with ingested captures (its chunks alternate on two streams per rank), the halo-sharded 16384-point
 #      stream, rectangular and with the fused Hann taper -- every line carries its regime and window in `config`
-#   3. the driver's own line, `bench.py --gpus n --steps 20 --warmup 5`, at 1, 2, 4 ... N ranks: headline + the multi-GPU leg in
+#   3. the driver's line with --full, `bench.py --gpus n --steps 20 --warmup 5 --full`, at 1, 2, 4 ... N ranks: headline + the multi-GPU leg in
 #      `extra` (census, checksums of what arrived, gather rate) -- what the round-end SCALE record will contain
 # Every step runs under `timeout`; nothing can hang the node.
 # Usage: bash scripts/multi_gpu_check.sh [N] [--dry-run] [--log FILE]
@@ -154,7 +154,7 @@ PY
   done
   n=$((n * 2))
 done
-# ---- 3. the driver's OWN command line: bench.py --gpus n --steps 20 --warmup 5 (what SCALE_rNN.json is made from) --------------
+# ---- 3. the driver's command line with --full: bench.py --gpus n --steps 20 --warmup 5 --full --------------------------------
 # Since round 5 this one line runs, behind the headline's timed steps, the sharded sweep in both regimes and the halo-sharded
 # stream with the chunked RCCL gather, and reports the communicator's census, the checksums of what arrived against what the
 # members computed and the gather's rate per link in `extra` (bench.py: multi_gpu_leg).  The checksums must be the same at every n.
@@ -162,9 +162,9 @@ n=1
 while [ $n -le "$N" ]; do
   port=$((port + 1))
   if [ $n -eq 1 ]; then
-    run "driver line x1" python bench.py --gpus 1 --steps 20 --warmup 5
+    run "driver line x1" python bench.py --gpus 1 --steps 20 --warmup 5 --full
   else
-    run "driver line x$n" python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n --steps 20 --warmup 5
+    run "driver line x$n" python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n --steps 20 --warmup 5 --full
   fi
   if [ $DRY = 0 ]; then
     python - "$LOG.step" "$n" <<'PY' 2>&1 | tee -a "$LOG"

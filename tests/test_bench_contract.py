@@ -128,7 +128,8 @@ def test_bench_with_two_ranks_runs_the_sharded_sweep_and_stream_with_a_gather():
     env = dict(os.environ, FSEA_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-                        "--warmup", "5", "--stream-frames", "4095"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
+                        "--warmup", "5", "--stream-frames", "4095", "--full"],
+                       capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -165,7 +166,7 @@ def _same_image_at_every_world_size(world, checksum):
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                        "--cpu-budget", "1.0"], capture_output=True, text=True, cwd=ROOT, timeout=900)
+                        "--cpu-budget", "1.0", "--full"], capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -243,3 +244,37 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert cb["unit"] == "frames/s" and cb["kind"] in ("port", "reference") and cb["cores"] >= 1 and cb["value"] > 0
     assert isinstance(cb["sample"], str) and cb["sample"]
     assert cb["host_cpus_visible"] >= cb["cores"] and cb["nrf_stream"]["process_get_buffer_us"] > 0
+
+
+@pytest.mark.gpu
+def test_a_plain_bench_run_is_the_headline_alone_and_dumps_what_its_last_step_computed(tmp_path):
+    """Without --full the run is set-up, warm-up, exactly K timed steps and the line; --dump-outputs writes the rows the last
+    timed step computed (a seeded sample of them), float32, within 64 MB, and they are the numpy transform of that step's
+    input (seeded: the same in every run)."""
+    import numpy as np
+    import bench
+    steps, warmup, n, frames = 7, 3, 8192, 4096
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                        str(warmup), "--dump-outputs", str(dump)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "fft_frames_per_sec_n8192" and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == steps and d["warmup"] == warmup
+    assert abs(d["value"] - frames * 1e3 / d["ms_per_step"]) / d["value"] < 1e-6
+    for key in ("extra", "cpu_baseline", "headline_regions_ms", "parity_rel_l2_first_rows"):
+        assert key not in d, key                          # measured and checked with --full only
+    assert sorted(os.listdir(dump)) == ["mag_rows.npy"]
+    rows = np.load(dump / "mag_rows.npy")
+    idx = bench.dump_rows(frames, 4 * n)
+    assert rows.dtype == np.float32 and rows.shape == (len(idx), n) and rows.nbytes <= 64e6
+    # the last timed step is step warmup + steps - 1: buffer set (warmup + steps - 1) % 6, whose input is the seeded batch
+    # rolled by 16 bytes per set (bench.run_gpu)
+    host = np.roll(bench.synth_batch(3, 2 * n * frames), 2 * 8 * ((warmup + steps - 1) % 6))
+    for j in (0, len(idx) // 2, len(idx) - 1):
+        f = int(idx[j])
+        want = bench.numpy_rows(host[2 * n * f: 2 * n * (f + 1)], 1, n, n)[0]
+        rel = float(np.linalg.norm(rows[j] - want) / np.linalg.norm(want))
+        assert rel <= 1e-6, (f, rel)

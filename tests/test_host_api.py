@@ -3,6 +3,7 @@ symbol the headers declare; nut_buffer semantics are checked against the referen
 src/nut.c (oracle/_ref/libnut_ref.so) when that build exists; the file-replay device needs no
 GPU.  No GPU compute is called here."""
 import ctypes
+import json
 import os
 import re
 
@@ -171,9 +172,12 @@ def test_nut_buffer_matches_reference_build():
     mine = _drive_nut(ours)
     # self-evident conventions (src/nut.c:121-151)
     assert mine[3][:3] == [0.0, 9 / 256.0, 18 / 256.0]
-    if ref is None:
-        pytest.skip("oracle/_ref/libnut_ref.so not built (reference absent)")
-    assert mine == _drive_nut(ref)
+    # what the reference's own src/nut.c returned for the same script (tests/golden/make_reference_nut.py), and that build
+    # itself where it exists
+    with open(os.path.join(ROOT, "tests", "golden", "reference_nut.json")) as fp:
+        assert json.loads(json.dumps(mine)) == json.load(fp)["drive_nut"]
+    if ref is not None:
+        assert mine == _drive_nut(ref)
 
 
 def test_nut_buffer_save_roundtrip(tmp_path):
