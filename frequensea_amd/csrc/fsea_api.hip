@@ -112,24 +112,47 @@ size_t mode_elem_bytes(int mode) {
 
 namespace {
 
-// the windowed twin of a u8 kind (a plan with a taper window; fsea_plan_set_window)
-int windowed_kind(int kind) {
-    switch (kind) {
-    case fsea::K_U8_MAG: return fsea::K_U8_MAG_WIN;
-    case fsea::K_U8_DB5: return fsea::K_U8_DB5_WIN;
-    case fsea::K_U8_DB10: return fsea::K_U8_DB10_WIN;
-    default: return fsea::K_U8_WIN;
+// Which __global__ entry point of the plan's configuration serves (input kind, epilogue mode, byte convention); -1, with
+// the error set, where the variant has none.
+int select_kind(const fsea_plan *p, int in_kind, int mode, int flip) {
+    const fsea::KernelEntry *e = p->entry;
+    int kind = fsea::K_U8;
+    if (in_kind == fsea::IN_F32) kind = fsea::K_F32;
+    else if (in_kind == fsea::IN_U8_ROT) kind = fsea::K_U8_ROT;
+    else if (flip && mode == FSEA_MODE_MAG_F32) kind = fsea::K_U8_MAG;
+    else if (flip && mode == FSEA_MODE_DB5_U8_DCFIX) kind = fsea::K_U8_DB5;
+    else if (flip && mode == FSEA_MODE_DB10_U8) kind = fsea::K_U8_DB10;
+    if (p->window_form != 0) {
+        // a plan with a taper launches the windowed twin; for the frequency-shifted and f32 inputs that is the
+        // nrf_freq_shifter -> nrf_fft chain and the F64 branch of nrf_fft_process (src/nrf.c:607-612) with the taper
+        static const int twin[] = {fsea::K_U8_MAG_WIN, fsea::K_U8_DB5_WIN, fsea::K_U8_DB10_WIN,
+                                   fsea::K_U8_WIN,     fsea::K_U8_ROT_WIN, fsea::K_F32_WIN};
+        kind = twin[kind];
     }
+    // tuning variants carry the u8 MAG and run-time-mode kernels only: their pixel modes run the latter
+    if (!e->fn[kind] && in_kind == fsea::IN_U8) kind = p->window_form != 0 ? fsea::K_U8_WIN : fsea::K_U8;
+    if (!e->fn[kind]) {
+        fail(FSEA_EINVAL, "kernel variant '%s' has no entry point for this input kind", e->variant);
+        return -1;
+    }
+    return kind;
 }
 
-// which __global__ entry point serves (input kind, epilogue mode, byte convention)
-int pick_kind(int in_kind, int mode, int flip) {
-    if (in_kind == fsea::IN_F32) return fsea::K_F32;
-    if (in_kind == fsea::IN_U8_ROT) return fsea::K_U8_ROT;
-    if (flip && mode == FSEA_MODE_MAG_F32) return fsea::K_U8_MAG;
-    if (flip && mode == FSEA_MODE_DB5_U8_DCFIX) return fsea::K_U8_DB5;
-    if (flip && mode == FSEA_MODE_DB10_U8) return fsea::K_U8_DB10;
-    return fsea::K_U8;
+// The half-overlap twin of MAG kind `kind` when this launch runs it, else -1: 50 %-overlapped frames of the
+// nrf_fft_process kind (raw int8, MAG rows) at the sizes with one frame per workgroup, not tiled, two frames or more.
+int half_overlap_kind(const fsea_plan *p, int kind, size_t n_frames, bool tiled) {
+    const int half = kind == fsea::K_U8_MAG ? fsea::K_U8_MAG_HALF : kind == fsea::K_U8_MAG_WIN ? fsea::K_U8_MAG_HALF_WIN : -1;
+    if (half < 0 || !p->entry->fn[half] || tiled || n_frames < 2 || 2 * (size_t)p->hop != (size_t)p->n || p->no_half_overlap) {
+        return -1;
+    }
+    return half;
+}
+
+// Every kind of every configuration takes one FftArgs by value (FSEA_KERNEL_FN_); the caller reads the launch's status
+// with hipGetLastError.
+void launch_kind(const fsea::KernelEntry *e, int kind, fsea::FftArgs &a, unsigned grid, hipStream_t s) {
+    void *args[] = {&a};
+    (void)hipLaunchKernel(e->fn[kind], dim3(grid), dim3(e->wg), args, 0, s);
 }
 
 __global__ void fsea_composite_max_kernel(uint8_t *dst, const uint8_t *src, uint32_t dst_x, uint32_t dst_y,
@@ -228,21 +251,13 @@ __global__ void fsea_f64_to_f32_kernel(const double *in, float *out, size_t n) {
 
 namespace {
 
-// the kernel raw int8 input (flip) launches on a plan of a size with kernels of its own
+// the kernel raw int8 input (flip) launches on a plan of a size with kernels of its own; whether that is the half-overlap
+// kernel is decided as for a typical launch (two frames or more, not tiled)
 std::string pow2_kernel_name(const fsea_plan *p) {
-    const fsea::KernelEntry *e = p->entry;
-    const bool windowed = p->window_form != 0;
-    int k = pick_kind(fsea::IN_U8, p->mode, 1);
-    if (windowed) {
-        k = windowed_kind(k);
-        if (!e->fn[k]) k = fsea::K_U8_WIN;
-    }
-    if (!e->fn[k]) k = fsea::K_U8;
-    const int half = windowed ? fsea::K_U8_MAG_HALF_WIN : fsea::K_U8_MAG_HALF;
-    if ((k == fsea::K_U8_MAG || k == fsea::K_U8_MAG_WIN) && e->fn[half] && 2 * (size_t)p->hop == (size_t)p->n && !p->no_half_overlap) {
-        k = half;  // 50 %-overlapped frames run the half-overlap kernel
-    }
-    return e->name[k] ? e->name[k] : "";
+    const int k = select_kind(p, fsea::IN_U8, p->mode, 1);
+    if (k < 0) return "";
+    const int half = half_overlap_kind(p, k, 2, false);
+    return p->entry->name[half >= 0 ? half : k];
 }
 
 int ensure(void **ptr, size_t *cap, size_t need) {
@@ -393,23 +408,9 @@ namespace {
 int launch_pow2(fsea_plan *p, int in_kind, const void *d_in, size_t n_frames, int flip, int mode, void *d_out,
                 hipStream_t s, double rot_delta, double rot_phase0, const TileLayout *tiles) {
     if (n_frames == 0) return FSEA_OK;
-    int kind = pick_kind(in_kind, mode, flip);
+    const int kind = select_kind(p, in_kind, mode, flip);
+    if (kind < 0) return FSEA_EINVAL;
     const fsea::KernelEntry *e = p->entry;
-    const bool windowed = p->window_form != 0;
-    if (windowed) {
-        if (in_kind == fsea::IN_U8) {
-            kind = windowed_kind(kind);
-            if (!e->fn[kind]) kind = fsea::K_U8_WIN;
-        } else {
-            // the nrf_freq_shifter -> nrf_fft chain and the F64 branch of nrf_fft_process (src/nrf.c:607-612) with the taper
-            kind = in_kind == fsea::IN_F32 ? fsea::K_F32_WIN : fsea::K_U8_ROT_WIN;
-        }
-    }
-    // tuning variants carry the u8 MAG and run-time-mode kernels only: their pixel modes run the latter
-    if (!e->fn[kind] && (kind == fsea::K_U8_DB5 || kind == fsea::K_U8_DB10)) kind = fsea::K_U8;
-    if (!e->fn[kind]) {
-        return fail(FSEA_EINVAL, "kernel variant '%s' has no entry point for this input kind", e->variant);
-    }
     fsea::FftArgs a;
     a.win = p->d_win;
     a.win_dc = p->d_win_dc;
@@ -445,11 +446,9 @@ int launch_pow2(fsea_plan *p, int in_kind, const void *d_in, size_t n_frames, in
         a.pitch_tile = tiles->pitch_tile;
         a.out_span = tiles->span;
     }
-    // 50 %-overlapped frames of the nrf_fft_process kind (raw int8, MAG rows) at the sizes with one frame per workgroup:
-    // the half-overlap kernel, runs of consecutive frames per workgroup (every sample loaded once), static units
-    const int half_kind = windowed ? fsea::K_U8_MAG_HALF_WIN : fsea::K_U8_MAG_HALF;
-    if ((kind == fsea::K_U8_MAG || kind == fsea::K_U8_MAG_WIN) && e->fn[half_kind] && !tiles &&
-        2 * (size_t)p->hop == (size_t)p->n && n_frames >= 2 && !p->no_half_overlap) {
+    // the half-overlap kernel: runs of consecutive frames per workgroup (every sample loaded once), static units
+    const int half_kind = half_overlap_kind(p, kind, n_frames, tiles != nullptr);
+    if (half_kind >= 0) {
         const size_t wgs = (size_t)p->num_cu * (size_t)(p->occ[half_kind] > 0 ? p->occ[half_kind] : 1);
         size_t run = (n_frames + wgs - 1) / wgs;  // frames per run: long enough to reuse most halves, short enough that every workgroup gets some
         if (run > (size_t)p->half_run_max) run = (size_t)p->half_run_max;
@@ -460,8 +459,7 @@ int launch_pow2(fsea_plan *p, int in_kind, const void *d_in, size_t n_frames, in
         const size_t units = (n_frames + run - 1) / run;
         size_t g = wgs < units ? wgs : units;
         if (g >= 8) g &= ~(size_t)7;
-        if (windowed) e->launch_win(half_kind, a, (unsigned)g, s);
-        else e->launch_half(a, (unsigned)g, s);
+        launch_kind(e, half_kind, a, (unsigned)g, s);
         FSEA_HIP(hipGetLastError());
         return FSEA_OK;
     }
@@ -478,8 +476,7 @@ int launch_pow2(fsea_plan *p, int in_kind, const void *d_in, size_t n_frames, in
                                    "event could not be created", FSEA_CTR_SLOTS);
         }
     }
-    if (kind >= fsea::K_U8_MAG_WIN) e->launch_win(kind, a, grid_for(p, e, p->occ[kind], n_frames), s);
-    else e->launch(kind, a, grid_for(p, e, p->occ[kind], n_frames), s);
+    launch_kind(e, kind, a, grid_for(p, e, p->occ[kind], n_frames), s);
     const hipError_t launched = hipGetLastError();
     if (slot >= 0) {
         std::lock_guard<std::mutex> lock(p->slot_mu);
@@ -812,18 +809,14 @@ int fsea_plan_set_window(fsea_plan *p, const float *w) {
 
 int fsea_plan_grid(const fsea_plan *p, size_t n_frames, unsigned *grid, unsigned *block, size_t *lds_bytes) {
     if (!p) return fail(FSEA_EINVAL, "plan is NULL");
-    int k = pick_kind(fsea::IN_U8, p->mode, 1);
-    if (p->window_form) k = windowed_kind(k);
-    if (!p->entry->fn[k]) k = p->window_form ? fsea::K_U8_WIN : fsea::K_U8;
+    // the kernel raw int8 input (flip) launches -- for a hop == N/2 plan the ordinary MAG kernel's geometry, not the
+    // half-overlap kernel's, as this call has always reported
+    const int k = select_kind(p, fsea::IN_U8, p->mode, 1);
+    if (k < 0) return FSEA_EINVAL;
     if (grid) *grid = grid_for(p, p->entry, p->occ[k], n_frames);
     if (block) *block = (unsigned)p->entry->wg;
     // a plan with a taper launches the *_WIN kernels, whose static LDS carries the DC table on top
-    if (lds_bytes) {
-        *lds_bytes = p->entry->lds_bytes;
-        if (p->window_form != 0 && p->entry->lds_bytes_win) {
-            *lds_bytes = (k == fsea::K_U8_MAG_WIN || k == fsea::K_U8_MAG_HALF_WIN) ? p->entry->lds_bytes_win : p->entry->lds_bytes_win_other;
-        }
-    }
+    if (lds_bytes) *lds_bytes = p->entry->lds_bytes[k];
     return FSEA_OK;
 }
 

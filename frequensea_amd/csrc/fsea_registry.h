@@ -29,18 +29,21 @@ struct KernelEntry {
     const char *variant;   // "" = the product configuration of this n
     int t, fpw, wg, np;
     int radix[4];
-    size_t lds_bytes;
-    size_t lds_bytes_win;  // static LDS of the windowed compile-time MAG kernels (*_u8_mag_win, *_u8_mag_half_win); 0 = no windowed kernels
-    size_t lds_bytes_win_other;  // ... of the other windowed u8 kinds (where the DC table sits in LDS it comes on top)
     int c0;                // samples per pass-0 load (hop must be a multiple)
     int counters;          // ticket counters: 0 = never used (single-wave frames), 1 = by launches with FftArgs::dynamic_units,
                            // 2 = by every launch (the V2 schedule and the progress-word experiments of the tuning library)
-    const void *fn[K_COUNT];    // __global__ function addresses (occupancy queries); null = not compiled
-    const char *name[K_COUNT];  // symbol names as rocprof shows them
-    void (*launch)(int kind, const FftArgs &args, unsigned grid, hipStream_t stream);
-    void (*launch_half)(const FftArgs &args, unsigned grid, hipStream_t stream);  // K_U8_MAG_HALF, or null
-    void (*launch_win)(int kind, const FftArgs &args, unsigned grid, hipStream_t stream);  // the *_WIN kinds, or null
+    const void *fn[K_COUNT];     // __global__ functions (launches, occupancy queries); null = not compiled
+    const char *name[K_COUNT];   // symbol names as rocprof shows them
+    size_t lds_bytes[K_COUNT];   // static LDS of each kind (the windowed u8 kinds that keep the DC table in LDS have it on top)
 };
+
+// Records one kind of `e`; returns true so that it can initialise a file-scope constant (FSEA_KIND_).
+inline bool add_kind(KernelEntry &e, int kind, const void *fn, const char *name, size_t lds_bytes) {
+    e.fn[kind] = fn;
+    e.name[kind] = name;
+    e.lds_bytes[kind] = lds_bytes;
+    return true;
+}
 
 // Each k_*.hip translation unit exports `int fsea_kernels_<tag>(KernelEntry *out, int cap)`
 // which fills `out` with its configurations and returns how many it has.
@@ -54,162 +57,76 @@ struct KernelEntry {
         fsea::FftKernel<NAME##_cfg, __VA_ARGS__>::run(a, lds);                                        \
     }
 
-#define FSEA_KERNEL_ENTRY_HEAD_(NAME, VARIANT)                                                        \
-    NAME##_cfg::N, VARIANT, NAME##_cfg::T, NAME##_cfg::FPW, NAME##_cfg::WG, NAME##_cfg::NP,           \
-        {NAME##_cfg::R(0), NAME##_cfg::R(1), NAME##_cfg::R(2), NAME##_cfg::R(3)},                     \
-        sizeof(fsea::cf) * NAME##_cfg::LDS_ALLOC, 0, 0, NAME##_cfg::C(0),                                 \
-        fsea::FftKernel<NAME##_cfg, fsea::IN_U8>::counters_used()
+// One kind of configuration NAME: the __global__ function NAME##SUFFIX (FftKernel<NAME_cfg, __VA_ARGS__>), recorded in
+// NAME_entry with its symbol name and static LDS.  The records are dynamic initialisers of this translation unit, run in
+// order when the library is loaded, after NAME_entry's constant initialisation and before any fsea_kernels_<tag> call.
+#define FSEA_KIND_(NAME, KIND, SUFFIX, ...)                                                           \
+    FSEA_KERNEL_FN_(NAME, SUFFIX, __VA_ARGS__)                                                        \
+    [[maybe_unused]] static const bool NAME##SUFFIX##_added = fsea::add_kind(                         \
+        NAME##_entry, fsea::KIND, reinterpret_cast<const void *>(&NAME##SUFFIX), #NAME #SUFFIX,       \
+        sizeof(fsea::cf) * fsea::FftKernel<NAME##_cfg, __VA_ARGS__>::LDS_CF);
 
-// Defines the six __global__ entry points of one configuration, with plain C names so that
-// profiles are easy to read, and the launch trampoline + KernelEntry for it.
-#define FSEA_DEFINE_KERNEL(NAME, VARIANT, ...)  /* NAME: C symbol stem; VARIANT: registry key */     \
+// The kinds, each spelled once:                    kind               suffix            FftKernel<Cfg, IN, MODE_T, ROT, RUNS, WIN>
+#define FSEA_K_U8_MAG_(N)             FSEA_KIND_(N, K_U8_MAG,          _u8_mag,          fsea::IN_U8,  fsea::MODE_MAG,          false, false, 0)
+#define FSEA_K_U8_DB5_(N)             FSEA_KIND_(N, K_U8_DB5,          _u8_db5,          fsea::IN_U8,  fsea::MODE_DB5_U8_DCFIX, false, false, 0)
+#define FSEA_K_U8_DB10_(N)            FSEA_KIND_(N, K_U8_DB10,         _u8_db10,         fsea::IN_U8,  fsea::MODE_DB10_U8,      false, false, 0)
+#define FSEA_K_U8_(N)                 FSEA_KIND_(N, K_U8,              _u8,              fsea::IN_U8,  -1,                      false, false, 0)
+#define FSEA_K_U8_ROT_(N)             FSEA_KIND_(N, K_U8_ROT,          _u8_rot,          fsea::IN_U8,  -1,                      true,  false, 0)
+#define FSEA_K_F32_(N)                FSEA_KIND_(N, K_F32,             _f32,             fsea::IN_F32, -1,                      false, false, 0)
+#define FSEA_K_U8_MAG_HALF_(N)        FSEA_KIND_(N, K_U8_MAG_HALF,     _u8_mag_half,     fsea::IN_U8,  fsea::MODE_MAG,          false, true,  0)
+#define FSEA_K_U8_MAG_WIN_(N, W)      FSEA_KIND_(N, K_U8_MAG_WIN,      _u8_mag_win,      fsea::IN_U8,  fsea::MODE_MAG,          false, false, W)
+#define FSEA_K_U8_DB5_WIN_(N, W)      FSEA_KIND_(N, K_U8_DB5_WIN,      _u8_db5_win,      fsea::IN_U8,  fsea::MODE_DB5_U8_DCFIX, false, false, W)
+#define FSEA_K_U8_DB10_WIN_(N, W)     FSEA_KIND_(N, K_U8_DB10_WIN,     _u8_db10_win,     fsea::IN_U8,  fsea::MODE_DB10_U8,      false, false, W)
+#define FSEA_K_U8_WIN_(N, W)          FSEA_KIND_(N, K_U8_WIN,          _u8_win,          fsea::IN_U8,  -1,                      false, false, W)
+#define FSEA_K_U8_ROT_WIN_(N, W)      FSEA_KIND_(N, K_U8_ROT_WIN,      _u8_rot_win,      fsea::IN_U8,  -1,                      true,  false, W)
+#define FSEA_K_F32_WIN_(N, W)         FSEA_KIND_(N, K_F32_WIN,         _f32_win,         fsea::IN_F32, -1,                      false, false, W)
+#define FSEA_K_U8_MAG_HALF_WIN_(N, W) FSEA_KIND_(N, K_U8_MAG_HALF_WIN, _u8_mag_half_win, fsea::IN_U8,  fsea::MODE_MAG,          false, true,  W)
+
+// The configuration NAME (FftCfg<...>) and its registry entry, which the kind lists below fill.
+#define FSEA_CONFIG_(NAME, VARIANT, ...)                                                              \
     using NAME##_cfg = fsea::FftCfg<__VA_ARGS__>;                                                     \
-    FSEA_KERNEL_FN_(NAME, _u8_mag, fsea::IN_U8, fsea::MODE_MAG)                                       \
-    FSEA_KERNEL_FN_(NAME, _u8_db5, fsea::IN_U8, fsea::MODE_DB5_U8_DCFIX)                              \
-    FSEA_KERNEL_FN_(NAME, _u8_db10, fsea::IN_U8, fsea::MODE_DB10_U8)                                  \
-    FSEA_KERNEL_FN_(NAME, _u8, fsea::IN_U8)                                                           \
-    FSEA_KERNEL_FN_(NAME, _u8_rot, fsea::IN_U8, -1, true)                                             \
-    FSEA_KERNEL_FN_(NAME, _f32, fsea::IN_F32)                                                         \
-    static void NAME##_launch(int kind, const fsea::FftArgs &a, unsigned grid, hipStream_t s) {       \
-        const dim3 g(grid), b(NAME##_cfg::WG);                                                        \
-        switch (kind) {                                                                               \
-        case fsea::K_U8_MAG: hipLaunchKernelGGL(NAME##_u8_mag, g, b, 0, s, a); break;                 \
-        case fsea::K_U8_DB5: hipLaunchKernelGGL(NAME##_u8_db5, g, b, 0, s, a); break;                 \
-        case fsea::K_U8_DB10: hipLaunchKernelGGL(NAME##_u8_db10, g, b, 0, s, a); break;               \
-        case fsea::K_U8_ROT: hipLaunchKernelGGL(NAME##_u8_rot, g, b, 0, s, a); break;                 \
-        case fsea::K_F32: hipLaunchKernelGGL(NAME##_f32, g, b, 0, s, a); break;                       \
-        default: hipLaunchKernelGGL(NAME##_u8, g, b, 0, s, a); break;                                 \
-        }                                                                                             \
-    }                                                                                                 \
-    static fsea::KernelEntry NAME##_entry() {                                                         \
-        return fsea::KernelEntry{                                                                     \
-            FSEA_KERNEL_ENTRY_HEAD_(NAME, VARIANT),                                                   \
-            {reinterpret_cast<const void *>(&NAME##_u8_mag), reinterpret_cast<const void *>(&NAME##_u8_db5), \
-             reinterpret_cast<const void *>(&NAME##_u8_db10), reinterpret_cast<const void *>(&NAME##_u8),    \
-             reinterpret_cast<const void *>(&NAME##_u8_rot), reinterpret_cast<const void *>(&NAME##_f32)},   \
-            {#NAME "_u8_mag", #NAME "_u8_db5", #NAME "_u8_db10", #NAME "_u8", #NAME "_u8_rot", #NAME "_f32"}, \
-            &NAME##_launch};                                                                          \
-    }
+    static fsea::KernelEntry NAME##_entry = {                                                         \
+        NAME##_cfg::N, VARIANT, NAME##_cfg::T, NAME##_cfg::FPW, NAME##_cfg::WG, NAME##_cfg::NP,       \
+        {NAME##_cfg::R(0), NAME##_cfg::R(1), NAME##_cfg::R(2), NAME##_cfg::R(3)}, NAME##_cfg::C(0),   \
+        fsea::FftKernel<NAME##_cfg, fsea::IN_U8>::counters_used()};
+
+// A configuration with the six kernels, with plain C names so that profiles are easy to read.  NAME: C symbol stem;
+// VARIANT: registry key.
+#define FSEA_DEFINE_KERNEL(NAME, VARIANT, ...)                                                        \
+    FSEA_CONFIG_(NAME, VARIANT, __VA_ARGS__)                                                          \
+    FSEA_K_U8_MAG_(NAME) FSEA_K_U8_DB5_(NAME) FSEA_K_U8_DB10_(NAME) FSEA_K_U8_(NAME) FSEA_K_U8_ROT_(NAME) FSEA_K_F32_(NAME)
 
 // Tuning variants (libfsea_hip_tune.so only): the MAG kernel and the run-time-mode kernel.  The pixel modes of such a
-// plan run the run-time-mode kernel; its f32-input and frequency-shifted kinds do not exist (launch() fails with
+// plan run the run-time-mode kernel; its f32-input and frequency-shifted kinds do not exist (a launch fails with
 // FSEA_EINVAL).  The V2 schedule (opt::V2) always hands its frames out by the ticket pools: fsea_plan_set_unit_distribution
 // has no effect on a V2 variant.
 #define FSEA_DEFINE_KERNEL_LITE(NAME, VARIANT, ...)                                                   \
-    using NAME##_cfg = fsea::FftCfg<__VA_ARGS__>;                                                     \
-    FSEA_KERNEL_FN_(NAME, _u8_mag, fsea::IN_U8, fsea::MODE_MAG)                                       \
-    FSEA_KERNEL_FN_(NAME, _u8, fsea::IN_U8)                                                           \
-    static void NAME##_launch(int kind, const fsea::FftArgs &a, unsigned grid, hipStream_t s) {       \
-        const dim3 g(grid), b(NAME##_cfg::WG);                                                        \
-        if (kind == fsea::K_U8_MAG) hipLaunchKernelGGL(NAME##_u8_mag, g, b, 0, s, a);                 \
-        else hipLaunchKernelGGL(NAME##_u8, g, b, 0, s, a);                                            \
-    }                                                                                                 \
-    static fsea::KernelEntry NAME##_entry() {                                                         \
-        return fsea::KernelEntry{                                                                     \
-            FSEA_KERNEL_ENTRY_HEAD_(NAME, VARIANT),                                                   \
-            {reinterpret_cast<const void *>(&NAME##_u8_mag), nullptr, nullptr,                        \
-             reinterpret_cast<const void *>(&NAME##_u8), nullptr, nullptr},                           \
-            {#NAME "_u8_mag", "", "", #NAME "_u8", "", ""},                                           \
-            &NAME##_launch};                                                                          \
-    }
+    FSEA_CONFIG_(NAME, VARIANT, __VA_ARGS__)                                                          \
+    FSEA_K_U8_MAG_(NAME) FSEA_K_U8_(NAME)
 
 // The u8 kernels only (MAG, DB5, DB10 with the mode fixed, and the run-time-mode kernel): configurations that have no
 // f32-input or frequency-shifted form (the single-wave 64 x 64 schedule).
 #define FSEA_DEFINE_KERNEL_U8(NAME, VARIANT, ...)                                                     \
-    using NAME##_cfg = fsea::FftCfg<__VA_ARGS__>;                                                     \
-    FSEA_KERNEL_FN_(NAME, _u8_mag, fsea::IN_U8, fsea::MODE_MAG)                                       \
-    FSEA_KERNEL_FN_(NAME, _u8_db5, fsea::IN_U8, fsea::MODE_DB5_U8_DCFIX)                              \
-    FSEA_KERNEL_FN_(NAME, _u8_db10, fsea::IN_U8, fsea::MODE_DB10_U8)                                  \
-    FSEA_KERNEL_FN_(NAME, _u8, fsea::IN_U8)                                                           \
-    static void NAME##_launch(int kind, const fsea::FftArgs &a, unsigned grid, hipStream_t s) {       \
-        const dim3 g(grid), b(NAME##_cfg::WG);                                                        \
-        switch (kind) {                                                                               \
-        case fsea::K_U8_MAG: hipLaunchKernelGGL(NAME##_u8_mag, g, b, 0, s, a); break;                 \
-        case fsea::K_U8_DB5: hipLaunchKernelGGL(NAME##_u8_db5, g, b, 0, s, a); break;                 \
-        case fsea::K_U8_DB10: hipLaunchKernelGGL(NAME##_u8_db10, g, b, 0, s, a); break;               \
-        default: hipLaunchKernelGGL(NAME##_u8, g, b, 0, s, a); break;                                 \
-        }                                                                                             \
-    }                                                                                                 \
-    static fsea::KernelEntry NAME##_entry() {                                                         \
-        return fsea::KernelEntry{                                                                     \
-            FSEA_KERNEL_ENTRY_HEAD_(NAME, VARIANT),                                                   \
-            {reinterpret_cast<const void *>(&NAME##_u8_mag), reinterpret_cast<const void *>(&NAME##_u8_db5), \
-             reinterpret_cast<const void *>(&NAME##_u8_db10), reinterpret_cast<const void *>(&NAME##_u8),    \
-             nullptr, nullptr},                                                                       \
-            {#NAME "_u8_mag", #NAME "_u8_db5", #NAME "_u8_db10", #NAME "_u8", "", ""},                \
-            &NAME##_launch};                                                                          \
-    }
+    FSEA_CONFIG_(NAME, VARIANT, __VA_ARGS__)                                                          \
+    FSEA_K_U8_MAG_(NAME) FSEA_K_U8_DB5_(NAME) FSEA_K_U8_DB10_(NAME) FSEA_K_U8_(NAME)
 
-// The half-overlap MAG kernel of a configuration defined above (one frame per workgroup), and the entry that carries it.
-#define FSEA_DEFINE_HALF_OVERLAP(NAME)                                                                \
-    FSEA_KERNEL_FN_(NAME, _u8_mag_half, fsea::IN_U8, fsea::MODE_MAG, false, true)                     \
-    static void NAME##_launch_half(const fsea::FftArgs &a, unsigned grid, hipStream_t s) {            \
-        hipLaunchKernelGGL(NAME##_u8_mag_half, dim3(grid), dim3(NAME##_cfg::WG), 0, s, a);            \
-    }                                                                                                 \
-    static fsea::KernelEntry NAME##_entry_half() {                                                    \
-        fsea::KernelEntry e = NAME##_entry();                                                         \
-        e.fn[fsea::K_U8_MAG_HALF] = reinterpret_cast<const void *>(&NAME##_u8_mag_half);              \
-        e.name[fsea::K_U8_MAG_HALF] = #NAME "_u8_mag_half";                                           \
-        e.launch_half = &NAME##_launch_half;                                                          \
-        return e;                                                                                     \
-    }
-#define FSEA_REGISTER_HALF(NAME) if (n < cap) out[n++] = NAME##_entry_half();
+// The half-overlap MAG kernel of a configuration defined above (one frame per workgroup).
+#define FSEA_DEFINE_HALF_OVERLAP(NAME) FSEA_K_U8_MAG_HALF_(NAME)
 
 // The windowed kernels of a configuration defined above: NAME_u8_mag_win, NAME_u8_db5_win, NAME_u8_db10_win (epilogue and
-// byte convention fixed at compile time, as their un-windowed twins), NAME_u8_win (and NAME_u8_mag_half_win with HALF = 1).  WMODE: FftKernel's WIN (1 = weights fetched per frame, 2 = register-resident).  FSEA_REGISTER_WIN /
-// FSEA_REGISTER_HALF_WIN register the entry with them.
+// byte convention fixed at compile time, as their un-windowed twins), NAME_u8_win, NAME_u8_rot_win, NAME_f32_win, and with
+// FSEA_DEFINE_HALF_OVERLAP_WIN NAME_u8_mag_half_win.  WMODE: FftKernel's WIN (1 = weights fetched per frame,
+// 2 = register-resident).
 #define FSEA_DEFINE_WINDOWED(NAME, WMODE)                                                             \
-    FSEA_KERNEL_FN_(NAME, _u8_mag_win, fsea::IN_U8, fsea::MODE_MAG, false, false, WMODE)              \
-    FSEA_KERNEL_FN_(NAME, _u8_db5_win, fsea::IN_U8, fsea::MODE_DB5_U8_DCFIX, false, false, WMODE)     \
-    FSEA_KERNEL_FN_(NAME, _u8_db10_win, fsea::IN_U8, fsea::MODE_DB10_U8, false, false, WMODE)         \
-    FSEA_KERNEL_FN_(NAME, _u8_win, fsea::IN_U8, -1, false, false, WMODE)                              \
-    FSEA_KERNEL_FN_(NAME, _u8_rot_win, fsea::IN_U8, -1, true, false, WMODE)                           \
-    FSEA_KERNEL_FN_(NAME, _f32_win, fsea::IN_F32, -1, false, false, WMODE)                            \
-    static void NAME##_launch_win(int kind, const fsea::FftArgs &a, unsigned grid, hipStream_t s) {   \
-        const dim3 g(grid), b(NAME##_cfg::WG);                                                        \
-        if (kind == fsea::K_U8_MAG_WIN) hipLaunchKernelGGL(NAME##_u8_mag_win, g, b, 0, s, a);         \
-        else if (kind == fsea::K_U8_DB5_WIN) hipLaunchKernelGGL(NAME##_u8_db5_win, g, b, 0, s, a);    \
-        else if (kind == fsea::K_U8_DB10_WIN) hipLaunchKernelGGL(NAME##_u8_db10_win, g, b, 0, s, a);  \
-        else if (kind == fsea::K_U8_ROT_WIN) hipLaunchKernelGGL(NAME##_u8_rot_win, g, b, 0, s, a);    \
-        else if (kind == fsea::K_F32_WIN) hipLaunchKernelGGL(NAME##_f32_win, g, b, 0, s, a);          \
-        else hipLaunchKernelGGL(NAME##_u8_win, g, b, 0, s, a);                                        \
-    }                                                                                                 \
-    static void NAME##_add_win(fsea::KernelEntry &e) {                                                \
-        e.fn[fsea::K_U8_ROT_WIN] = reinterpret_cast<const void *>(&NAME##_u8_rot_win);                \
-        e.fn[fsea::K_F32_WIN] = reinterpret_cast<const void *>(&NAME##_f32_win);                      \
-        e.name[fsea::K_U8_ROT_WIN] = #NAME "_u8_rot_win";                                             \
-        e.name[fsea::K_F32_WIN] = #NAME "_f32_win";                                                   \
-        e.lds_bytes_win = sizeof(fsea::cf) * fsea::FftKernel<NAME##_cfg, fsea::IN_U8, fsea::MODE_MAG, false, false, WMODE>::LDS_CF; \
-        e.lds_bytes_win_other = sizeof(fsea::cf) * fsea::FftKernel<NAME##_cfg, fsea::IN_U8, -1, false, false, WMODE>::LDS_CF; \
-        e.fn[fsea::K_U8_MAG_WIN] = reinterpret_cast<const void *>(&NAME##_u8_mag_win);                \
-        e.fn[fsea::K_U8_DB5_WIN] = reinterpret_cast<const void *>(&NAME##_u8_db5_win);                \
-        e.fn[fsea::K_U8_DB10_WIN] = reinterpret_cast<const void *>(&NAME##_u8_db10_win);              \
-        e.fn[fsea::K_U8_WIN] = reinterpret_cast<const void *>(&NAME##_u8_win);                        \
-        e.name[fsea::K_U8_MAG_WIN] = #NAME "_u8_mag_win";                                             \
-        e.name[fsea::K_U8_DB5_WIN] = #NAME "_u8_db5_win";                                             \
-        e.name[fsea::K_U8_DB10_WIN] = #NAME "_u8_db10_win";                                           \
-        e.name[fsea::K_U8_WIN] = #NAME "_u8_win";                                                     \
-        e.launch_win = &NAME##_launch_win;                                                            \
-    }
-#define FSEA_DEFINE_HALF_OVERLAP_WIN(NAME, WMODE)                                                     \
-    FSEA_KERNEL_FN_(NAME, _u8_mag_half_win, fsea::IN_U8, fsea::MODE_MAG, false, true, WMODE)          \
-    static void NAME##_launch_win_all(int kind, const fsea::FftArgs &a, unsigned grid, hipStream_t s) { \
-        if (kind == fsea::K_U8_MAG_HALF_WIN) hipLaunchKernelGGL(NAME##_u8_mag_half_win, dim3(grid), dim3(NAME##_cfg::WG), 0, s, a); \
-        else NAME##_launch_win(kind, a, grid, s);                                                     \
-    }                                                                                                 \
-    static void NAME##_add_half_win(fsea::KernelEntry &e) {                                           \
-        NAME##_add_win(e);                                                                            \
-        e.fn[fsea::K_U8_MAG_HALF_WIN] = reinterpret_cast<const void *>(&NAME##_u8_mag_half_win);      \
-        e.name[fsea::K_U8_MAG_HALF_WIN] = #NAME "_u8_mag_half_win";                                   \
-        e.launch_win = &NAME##_launch_win_all;                                                        \
-    }
-#define FSEA_REGISTER_WIN(NAME) if (n < cap) { out[n] = NAME##_entry(); NAME##_add_win(out[n]); ++n; }
-#define FSEA_REGISTER_HALF_WIN(NAME) if (n < cap) { out[n] = NAME##_entry_half(); NAME##_add_half_win(out[n]); ++n; }
+    FSEA_K_U8_MAG_WIN_(NAME, WMODE) FSEA_K_U8_DB5_WIN_(NAME, WMODE) FSEA_K_U8_DB10_WIN_(NAME, WMODE)  \
+    FSEA_K_U8_WIN_(NAME, WMODE) FSEA_K_U8_ROT_WIN_(NAME, WMODE) FSEA_K_F32_WIN_(NAME, WMODE)
+#define FSEA_DEFINE_HALF_OVERLAP_WIN(NAME, WMODE) FSEA_K_U8_MAG_HALF_WIN_(NAME, WMODE)
 
+// The registry list of a translation unit: FSEA_REGISTER(NAME) adds NAME_entry with every kind defined for NAME.
 #define FSEA_REGISTER_BEGIN(TAG)                                                                      \
     extern "C" int fsea_kernels_##TAG(fsea::KernelEntry *out, int cap) {                              \
         int n = 0;
-#define FSEA_REGISTER(NAME) if (n < cap) out[n++] = NAME##_entry();
+#define FSEA_REGISTER(NAME) if (n < cap) out[n++] = NAME##_entry;
 #define FSEA_REGISTER_END                                                                             \
         return n;                                                                                     \
     }

@@ -4,5 +4,5 @@
 FSEA_DEFINE_KERNEL(fsea_fft1024, "", FSEA_CFG_1024)
 FSEA_DEFINE_WINDOWED(fsea_fft1024, FSEA_WIN)
 FSEA_REGISTER_BEGIN(1024)
-FSEA_REGISTER_WIN(fsea_fft1024)
+FSEA_REGISTER(fsea_fft1024)
 FSEA_REGISTER_END

@@ -6,5 +6,5 @@ FSEA_DEFINE_HALF_OVERLAP(fsea_fft16384)
 FSEA_DEFINE_WINDOWED(fsea_fft16384, FSEA_WIN)
 FSEA_DEFINE_HALF_OVERLAP_WIN(fsea_fft16384, FSEA_WIN)
 FSEA_REGISTER_BEGIN(16384)
-FSEA_REGISTER_HALF_WIN(fsea_fft16384)
+FSEA_REGISTER(fsea_fft16384)
 FSEA_REGISTER_END

@@ -4,5 +4,5 @@
 FSEA_DEFINE_KERNEL(fsea_fft4096, "", FSEA_CFG_4096)
 FSEA_DEFINE_WINDOWED(fsea_fft4096, FSEA_WIN)
 FSEA_REGISTER_BEGIN(4096)
-FSEA_REGISTER_WIN(fsea_fft4096)
+FSEA_REGISTER(fsea_fft4096)
 FSEA_REGISTER_END

@@ -6,5 +6,5 @@ FSEA_DEFINE_HALF_OVERLAP(fsea_fft8192)
 FSEA_DEFINE_WINDOWED(fsea_fft8192, FSEA_WIN)
 FSEA_DEFINE_HALF_OVERLAP_WIN(fsea_fft8192, FSEA_WIN)
 FSEA_REGISTER_BEGIN(8192)
-FSEA_REGISTER_HALF_WIN(fsea_fft8192)
+FSEA_REGISTER(fsea_fft8192)
 FSEA_REGISTER_END

@@ -9,7 +9,7 @@ FSEA_DEFINE_WINDOWED(fsea_fft256rows, FSEA_WIN)
 FSEA_DEFINE_WINDOWED(fsea_fft512px, FSEA_WIN)
 FSEA_DEFINE_WINDOWED(fsea_fft1024rt, FSEA_WIN)
 FSEA_REGISTER_BEGIN(alt)
-FSEA_REGISTER_WIN(fsea_fft256rows)
-FSEA_REGISTER_WIN(fsea_fft512px)
-FSEA_REGISTER_WIN(fsea_fft1024rt)
+FSEA_REGISTER(fsea_fft256rows)
+FSEA_REGISTER(fsea_fft512px)
+FSEA_REGISTER(fsea_fft1024rt)
 FSEA_REGISTER_END

@@ -22,16 +22,16 @@ FSEA_DEFINE_HALF_OVERLAP_WIN(fsea_fft16384_w1, 1)
 FSEA_DEFINE_HALF_OVERLAP(fsea_fft16384_w2)
 FSEA_DEFINE_HALF_OVERLAP_WIN(fsea_fft16384_w2, 2)
 FSEA_REGISTER_BEGIN(tune_win)
-FSEA_REGISTER_WIN(fsea_fft256_w1)
-FSEA_REGISTER_WIN(fsea_fft256_w2)
-FSEA_REGISTER_WIN(fsea_fft1024_w1)
-FSEA_REGISTER_WIN(fsea_fft1024_w2)
-FSEA_REGISTER_WIN(fsea_fft2048_w1)
-FSEA_REGISTER_WIN(fsea_fft2048_w2)
-FSEA_REGISTER_WIN(fsea_fft4096_w1)
-FSEA_REGISTER_WIN(fsea_fft4096_w2)
-FSEA_REGISTER_HALF_WIN(fsea_fft8192_w1)
-FSEA_REGISTER_HALF_WIN(fsea_fft8192_w2)
-FSEA_REGISTER_HALF_WIN(fsea_fft16384_w1)
-FSEA_REGISTER_HALF_WIN(fsea_fft16384_w2)
+FSEA_REGISTER(fsea_fft256_w1)
+FSEA_REGISTER(fsea_fft256_w2)
+FSEA_REGISTER(fsea_fft1024_w1)
+FSEA_REGISTER(fsea_fft1024_w2)
+FSEA_REGISTER(fsea_fft2048_w1)
+FSEA_REGISTER(fsea_fft2048_w2)
+FSEA_REGISTER(fsea_fft4096_w1)
+FSEA_REGISTER(fsea_fft4096_w2)
+FSEA_REGISTER(fsea_fft8192_w1)
+FSEA_REGISTER(fsea_fft8192_w2)
+FSEA_REGISTER(fsea_fft16384_w1)
+FSEA_REGISTER(fsea_fft16384_w2)
 FSEA_REGISTER_END
