@@ -1,0 +1,406 @@
+// fsea_fir.hip -- streaming complex FIR filter with real f32 taps (include/fsea.h: fsea_fir_*), the batched form of the
+// reference's nrf_iq_filter: I and Q filtered independently by the same taps, the last L - 1 input samples carried from call
+// to call.  Output i of a call is
+//   y[i] = sum_{k < L} c[k] x_ext[i + k],   x_ext = tail ++ x,
+// and the tail becomes the last L - 1 values of x_ext.
+//
+// Kernel ("The IQ low-pass filter"): one workgroup of 256 lanes per tile of FIR_T = 2048 outputs.  The tile's
+// FIR_T + L - 1 inputs are converted once (u8 / 256 or f64 -> f32 complex) and staged in LDS as rows of FIR_R = 8
+// samples, padded to 80 bytes so that the ds_read_b128 row reads of 64 lanes hit every bank once.  Lane l owns the
+// FIR_R consecutive outputs l*FIR_R .. l*FIR_R + 7 and slides a register window of two rows along the taps: one row
+// (four ds_read_b128) feeds 64 v_pk_fma_f32, each an (I, Q) pair times a tap broadcast from an SGPR pair.  The outputs
+// go back through the same LDS rows so that the stores are coalesced.  The taps are
+// zero-padded to whole rows on the device; they arrive by scalar loads.  The tail lives in two device buffers used in
+// turn: a launch reads one and workgroup 0 writes the next one, so no workgroup can overwrite the old tail while the
+// first tile still reads it.
+#include "fsea_internal.h"
+
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "fsea_pk_asm.h"
+
+using fsea::cf;
+using fsea::cf2;
+using fsea_detail::DeviceGuard;
+using fsea_detail::fail;
+
+namespace {
+
+constexpr int FIR_WG = 256;                   // lanes per workgroup
+constexpr int FIR_R = 8;                      // outputs per lane = samples per LDS row
+constexpr int FIR_T = FIR_WG * FIR_R;         // outputs per workgroup
+constexpr int FIR_ROW = FIR_R + 2;            // LDS row pitch in complex samples: 80 bytes, conflict-free b128 reads
+constexpr int FIR_MAX_BLOCKS = FSEA_FIR_MAX_TAPS / FIR_R;
+constexpr int FIR_ROWS = FIR_WG + FIR_MAX_BLOCKS;         // rows staged per tile at the largest L
+constexpr int FIR_TAPS_ALLOC = FSEA_FIR_MAX_TAPS + 2 * FIR_R;  // padded taps on the device (zeros past L)
+static_assert(FSEA_FIR_MAX_TAPS % FIR_R == 0, "the tap cap is a whole number of rows");
+
+enum { FIR_IN_U8 = 0, FIR_IN_F64 = 1 };
+
+// acc + w * tap, the tap broadcast from the low (even k) or the high (odd k) half of an SGPR pair
+__device__ __forceinline__ cf pk_tap_fma_lo(cf w, cf taps, cf acc) {
+    cf t;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(t) : "v"(w), "s"(taps), "v"(acc));
+    return t;
+}
+__device__ __forceinline__ cf pk_tap_fma_hi(cf w, cf taps, cf acc) {
+    cf t;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(t) : "v"(w), "s"(taps), "v"(acc));
+    return t;
+}
+
+template <int KIND>
+__device__ __forceinline__ cf load_sample(const void *__restrict__ in, long long s, uint32_t flip) {
+    if (KIND == FIR_IN_U8) {
+        const uint32_t b = ((uint32_t)(static_cast<const uint16_t *>(in))[s] ^ flip) & 0xffffu;
+        return cf{(float)(b & 0xffu) * (1.0f / 256.0f), (float)(b >> 8) * (1.0f / 256.0f)};
+    } else {
+        const double2 d = (static_cast<const double2 *>(in))[s];
+        return cf{(float)d.x, (float)d.y};
+    }
+}
+
+// eight consecutive samples from s (a multiple of 8, all inside the input)
+template <int KIND>
+__device__ __forceinline__ void load_group(const void *__restrict__ in, long long s, uint32_t flip, cf v[8]) {
+    if (KIND == FIR_IN_U8) {
+        const uint4 q = (static_cast<const uint4 *>(in))[s >> 3];
+        const uint32_t w[4] = {q.x ^ flip, q.y ^ flip, q.z ^ flip, q.w ^ flip};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[2 * j] = cf{(float)(w[j] & 0xffu), (float)((w[j] >> 8) & 0xffu)} * (1.0f / 256.0f);
+            v[2 * j + 1] = cf{(float)((w[j] >> 16) & 0xffu), (float)(w[j] >> 24)} * (1.0f / 256.0f);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = load_sample<KIND>(in, s + j, flip);
+    }
+}
+
+__device__ __forceinline__ void read_row(const cf *row, cf v[FIR_R]) {
+#pragma unroll
+    for (int j = 0; j < FIR_R; j += 2) {
+        const cf2 q = *reinterpret_cast<const cf2 *>(row + j);
+        v[j] = cf{q[0], q[1]};
+        v[j + 1] = cf{q[2], q[3]};
+    }
+}
+
+// acc[r] += sum_{i < FIR_R} t[i] * win[r + i], win = a ++ b (two consecutive rows), t = taps kb*FIR_R .. + FIR_R - 1
+__device__ __forceinline__ void fma_block(cf acc[FIR_R], const cf a[FIR_R], const cf b[FIR_R], const cf *__restrict__ taps2,
+                                          int kb) {
+    cf t[FIR_R / 2];
+#pragma unroll
+    for (int j = 0; j < FIR_R / 2; ++j) t[j] = taps2[kb * (FIR_R / 2) + j];
+#pragma unroll
+    for (int i = 0; i < FIR_R; ++i) {
+#pragma unroll
+        for (int r = 0; r < FIR_R; ++r) {
+            const cf w = (r + i < FIR_R) ? a[r + i] : b[r + i - FIR_R];
+            acc[r] = (i & 1) ? pk_tap_fma_hi(w, t[i >> 1], acc[r]) : pk_tap_fma_lo(w, t[i >> 1], acc[r]);
+        }
+    }
+}
+
+template <int KIND>
+__device__ __forceinline__ void fir_body(const void *__restrict__ in, long long n, uint32_t flip, const cf *__restrict__ tail_in,
+                                         cf *__restrict__ tail_out, const float *__restrict__ taps, int L, cf *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) cf lds[FIR_ROWS * FIR_ROW];
+    const int tid = threadIdx.x;
+    const int nb = (L + FIR_R - 1) / FIR_R;      // tap rows (zero-padded past L)
+    const int span = (FIR_WG + nb) * FIR_R;      // x_ext entries the tile reads
+    const long long i0 = (long long)blockIdx.x * FIR_T;  // first output = first x_ext index of the tile
+    const long long s_first = i0 - (L - 1);      // input sample of x_ext[i0] (negative: the tail)
+    const long long s_al = s_first & ~7LL;       // the 8-sample group it lies in
+    const int groups = (int)((s_first - s_al + span + 7) >> 3);
+
+    // stage: x_ext[i0 + i], i < span, converted to f32 complex; past the end of the input: zeros (they meet zero taps or
+    // feed outputs that are not stored)
+    for (int g = tid; g < groups; g += FIR_WG) {
+        const long long s = s_al + 8LL * g;
+        cf v[8];
+        if (s >= 0 && s + 8 <= n) {
+            load_group<KIND>(in, s, flip, v);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const long long ss = s + j;
+                v[j] = ss < 0 ? (ss + (L - 1) >= 0 ? tail_in[ss + (L - 1)] : cf{0.0f, 0.0f})
+                              : (ss < n ? load_sample<KIND>(in, ss, flip) : cf{0.0f, 0.0f});
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const long long i = s + j - s_first;
+            if (i >= 0 && i < span) lds[(int)(i >> 3) * FIR_ROW + (int)(i & 7)] = v[j];
+        }
+    }
+    __syncthreads();
+
+    const cf *taps2 = reinterpret_cast<const cf *>(taps);   // tap pairs, one SGPR pair each
+    const cf *row = lds + tid * FIR_ROW;
+    cf acc[FIR_R], lo[FIR_R], hi[FIR_R];
+#pragma unroll
+    for (int r = 0; r < FIR_R; ++r) acc[r] = cf{0.0f, 0.0f};
+    read_row(row, lo);
+    int b = 0;
+    for (; b + 2 <= nb; b += 2) {
+        read_row(row + (b + 1) * FIR_ROW, hi);
+        fma_block(acc, lo, hi, taps2, b);
+        read_row(row + (b + 2) * FIR_ROW, lo);
+        fma_block(acc, hi, lo, taps2, b + 1);
+    }
+    if (b < nb) {
+        read_row(row + (b + 1) * FIR_ROW, hi);
+        fma_block(acc, lo, hi, taps2, b);
+    }
+
+    // store through LDS: lane l's eight outputs go to padded row l, then every wave writes 1 KiB runs of the tile
+    // (16 contiguous bytes per lane) instead of 64-byte-strided pieces
+    __syncthreads();  // every lane is done with the staged input
+#pragma unroll
+    for (int r = 0; r < FIR_R; r += 2) {
+        *reinterpret_cast<cf2 *>(lds + tid * FIR_ROW + r) = cf2{acc[r][0], acc[r][1], acc[r + 1][0], acc[r + 1][1]};
+    }
+    __syncthreads();
+    const long long left = n - i0;  // outputs of this tile still inside the call
+#pragma unroll
+    for (int q = 0; q < FIR_T / (2 * FIR_WG); ++q) {
+        const int p = 2 * tid + 2 * FIR_WG * q;  // tile position of this lane's pair
+        const cf2 v = *reinterpret_cast<const cf2 *>(lds + (p >> 3) * FIR_ROW + (p & 7));
+        if (p + 2 <= left) {
+            *reinterpret_cast<cf2 *>(out + i0 + p) = v;
+        } else if (p < left) {
+            out[i0 + p] = cf{v[0], v[1]};
+        }
+    }
+
+    // the next call's tail: x_ext[n + m], m < L - 1 -- from the old tail while n + m < L - 1 (a call shorter than the tail)
+    if (blockIdx.x == 0) {
+        for (int m = tid; m < L - 1; m += FIR_WG) {
+            const long long e = n + m;
+            tail_out[m] = e < L - 1 ? tail_in[e] : load_sample<KIND>(in, e - (L - 1), flip);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(FIR_WG) void fsea_fir_u8(const void *__restrict__ in, long long n, uint32_t flip,
+                                                                  const cf *__restrict__ tail_in, cf *__restrict__ tail_out,
+                                                                  const float *__restrict__ taps, int L, cf *__restrict__ out) {
+    fir_body<FIR_IN_U8>(in, n, flip, tail_in, tail_out, taps, L, out);
+}
+
+extern "C" __global__ __launch_bounds__(FIR_WG) void fsea_fir_f64(const void *__restrict__ in, long long n, uint32_t flip,
+                                                                   const cf *__restrict__ tail_in, cf *__restrict__ tail_out,
+                                                                   const float *__restrict__ taps, int L, cf *__restrict__ out) {
+    fir_body<FIR_IN_F64>(in, n, flip, tail_in, tail_out, taps, L, out);
+}
+
+struct fsea_fir {
+    int n_taps = 0;
+    int device = 0;
+    float *d_taps = nullptr;       // FIR_TAPS_ALLOC floats, zeros past n_taps
+    cf *d_tail[2] = {nullptr, nullptr};  // FSEA_FIR_MAX_TAPS samples each; d_tail[cur] is the current tail
+    int cur = 0;
+    hipStream_t stream = nullptr;  // the host-buffer forms
+    std::mutex mu;
+    void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
+    size_t d_in_bytes = 0, d_out_bytes = 0, h_in_bytes = 0, h_out_bytes = 0;
+};
+
+namespace {
+
+int grow_device(void **ptr, size_t *cap, size_t need) {
+    if (*cap >= need) return FSEA_OK;
+    if (*ptr) FSEA_HIP(hipFree(*ptr));
+    *ptr = nullptr;
+    *cap = 0;
+    const size_t want = need + need / 4 + 4096;
+    FSEA_HIP(hipMalloc(ptr, want));
+    *cap = want;
+    return FSEA_OK;
+}
+
+int grow_pinned(void **ptr, size_t *cap, size_t need) {
+    if (*cap >= need) return FSEA_OK;
+    if (*ptr) FSEA_HIP(hipHostFree(*ptr));
+    *ptr = nullptr;
+    *cap = 0;
+    const size_t want = need + need / 4 + 4096;
+    FSEA_HIP(hipHostMalloc(ptr, want, hipHostMallocDefault));
+    *cap = want;
+    return FSEA_OK;
+}
+
+// one launch; the caller holds f->mu and is on f's device
+int fir_launch(fsea_fir *f, int kind, const void *d_in, size_t n, int flip, void *d_out, hipStream_t s) {
+    const unsigned grid = (unsigned)((n + FIR_T - 1) / FIR_T);
+    const cf *tin = f->d_tail[f->cur];
+    cf *tout = f->d_tail[f->cur ^ 1];
+    const long long nn = (long long)n;
+    const uint32_t fm = (kind == FIR_IN_U8 && flip) ? 0x80808080u : 0u;
+    if (kind == FIR_IN_U8) {
+        hipLaunchKernelGGL(fsea_fir_u8, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, f->d_taps, f->n_taps,
+                           static_cast<cf *>(d_out));
+    } else {
+        hipLaunchKernelGGL(fsea_fir_f64, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, f->d_taps, f->n_taps,
+                           static_cast<cf *>(d_out));
+    }
+    FSEA_HIP(hipGetLastError());
+    f->cur ^= 1;
+    return FSEA_OK;
+}
+
+// the host-buffer forms: pinned staging, copy in, one launch, copy out, on the object's own stream
+int fir_host(fsea_fir *f, int kind, const void *in, size_t n, int flip, float *out) {
+    if (!f) return fail(FSEA_EINVAL, "fir is NULL");
+    if (n == 0) return FSEA_OK;
+    if (!in || !out) return fail(FSEA_EINVAL, "NULL buffer");
+    if (n > ((size_t)1 << 40)) return fail(FSEA_EINVAL, "n_samples %zu too large", n);
+    std::lock_guard<std::mutex> lock(f->mu);
+    FSEA_ON_DEVICE(f->device);
+    const size_t in_bytes = n * (kind == FIR_IN_U8 ? 2 : 16);
+    const size_t out_bytes = n * sizeof(cf);
+    int rc = grow_pinned(&f->h_in, &f->h_in_bytes, in_bytes);
+    if (!rc) rc = grow_pinned(&f->h_out, &f->h_out_bytes, out_bytes);
+    if (!rc) rc = grow_device(&f->d_in, &f->d_in_bytes, in_bytes);
+    if (!rc) rc = grow_device(&f->d_out, &f->d_out_bytes, out_bytes);
+    if (rc) return rc;
+    std::memcpy(f->h_in, in, in_bytes);
+    FSEA_HIP(hipMemcpyAsync(f->d_in, f->h_in, in_bytes, hipMemcpyHostToDevice, f->stream));
+    rc = fir_launch(f, kind, f->d_in, n, flip, f->d_out, f->stream);
+    if (rc) return rc;
+    FSEA_HIP(hipMemcpyAsync(f->h_out, f->d_out, out_bytes, hipMemcpyDeviceToHost, f->stream));
+    FSEA_HIP(hipStreamSynchronize(f->stream));
+    std::memcpy(out, f->h_out, out_bytes);
+    return FSEA_OK;
+}
+
+void release(fsea_fir *f) {
+    if (f->d_taps) (void)hipFree(f->d_taps);
+    for (int i = 0; i < 2; ++i)
+        if (f->d_tail[i]) (void)hipFree(f->d_tail[i]);
+    if (f->d_in) (void)hipFree(f->d_in);
+    if (f->d_out) (void)hipFree(f->d_out);
+    if (f->h_in) (void)hipHostFree(f->h_in);
+    if (f->h_out) (void)hipHostFree(f->h_out);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fsea_fir_lowpass_taps(double sample_rate, double half_ampl_freq, int length, double *taps) {
+#pragma clang fp contract(off)
+    // the reference's window-method design, operation for operation (no fused multiply-adds): bit-exact in double
+    if (!taps) return fail(FSEA_EINVAL, "taps is NULL");
+    if (length < 1) return fail(FSEA_EINVAL, "length must be >= 1, got %d", length);
+    if (!(sample_rate > 0.0) || !std::isfinite(sample_rate) || !std::isfinite(half_ampl_freq)) {
+        return fail(FSEA_EINVAL, "sample_rate must be positive and finite, half_ampl_freq finite");
+    }
+    const double two_pi = M_PI * 2;
+    const int m = length + (length + 1) % 2;     // an even length is designed one tap longer
+    const double f = half_ampl_freq / sample_rate;
+    const int c = m / 2;
+    double *v = new (std::nothrow) double[m];
+    if (!v) return fail(FSEA_ENOMEM, "out of host memory");
+    double sum = 0.0;
+    for (int i = 0; i < m; ++i) {
+        double x;
+        if (i == c) {
+            x = two_pi * f;
+        } else {
+            const double a = two_pi * (i + 1) / (double)(m + 1);
+            x = sin(two_pi * f * (i - c)) / (double)(i - c);
+            x *= 0.42 - 0.5 * cos(a) + 0.08 * cos(2 * a);
+        }
+        sum += x;
+        v[i] = x;
+    }
+    for (int i = 0; i < length; ++i) taps[i] = v[i] / sum;   // the first `length` of the m taps
+    delete[] v;
+    return FSEA_OK;
+}
+
+int fsea_fir_create(fsea_fir **out, const double *taps, int n_taps, int device) {
+    if (!out) return fail(FSEA_EINVAL, "fir out-pointer is NULL");
+    *out = nullptr;
+    if (!taps) return fail(FSEA_EINVAL, "taps is NULL");
+    if (n_taps < 1 || n_taps > FSEA_FIR_MAX_TAPS) {
+        return fail(FSEA_EINVAL, "n_taps must be in [1, %d], got %d", FSEA_FIR_MAX_TAPS, n_taps);
+    }
+    for (int k = 0; k < n_taps; ++k) {
+        if (!std::isfinite(taps[k])) return fail(FSEA_EINVAL, "tap %d is not finite", k);
+    }
+    int count = 0;
+    hipError_t ce = hipGetDeviceCount(&count);
+    if (ce != hipSuccess || count <= 0) {
+        return fail(FSEA_ENODEVICE, "no HIP device available (%s); libfsea_hip has no CPU fallback", hipGetErrorString(ce));
+    }
+    if (device < 0 || device >= count) return fail(FSEA_EINVAL, "device %d out of range [0,%d)", device, count);
+    FSEA_ON_DEVICE(device);
+    fsea_fir *f = new (std::nothrow) fsea_fir();
+    if (!f) return fail(FSEA_ENOMEM, "out of host memory");
+    f->n_taps = n_taps;
+    f->device = device;
+    float tf[FIR_TAPS_ALLOC] = {};
+    for (int k = 0; k < n_taps; ++k) tf[k] = (float)taps[k];
+    hipError_t e = hipMalloc(&f->d_taps, sizeof(tf));
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc(&f->d_tail[i], FSEA_FIR_MAX_TAPS * sizeof(cf));
+    if (e == hipSuccess) e = hipMemcpy(f->d_taps, tf, sizeof(tf), hipMemcpyHostToDevice);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMemset(f->d_tail[i], 0, FSEA_FIR_MAX_TAPS * sizeof(cf));
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        release(f);
+        return fail(FSEA_EHIP, "fsea_fir_create: %s", hipGetErrorString(e));
+    }
+    *out = f;
+    return FSEA_OK;
+}
+
+int fsea_fir_destroy(fsea_fir *f) {
+    if (!f) return FSEA_OK;
+    FSEA_ON_DEVICE(f->device);
+    FSEA_HIP(hipDeviceSynchronize());   // launches of the object on any stream may still read its taps and tails
+    release(f);
+    return FSEA_OK;
+}
+
+int fsea_fir_reset(fsea_fir *f) {
+    if (!f) return fail(FSEA_EINVAL, "fir is NULL");
+    std::lock_guard<std::mutex> lock(f->mu);
+    FSEA_ON_DEVICE(f->device);
+    FSEA_HIP(hipDeviceSynchronize());
+    FSEA_HIP(hipMemset(f->d_tail[f->cur], 0, FSEA_FIR_MAX_TAPS * sizeof(cf)));
+    FSEA_HIP(hipDeviceSynchronize());
+    return FSEA_OK;
+}
+
+int fsea_fir_n_taps(const fsea_fir *f) { return f ? f->n_taps : 0; }
+
+int fsea_fir_u8_device(fsea_fir *f, const void *d_iq, size_t n_samples, int flip, void *d_out, void *stream) {
+    if (!f) return fail(FSEA_EINVAL, "fir is NULL");
+    if (n_samples == 0) return FSEA_OK;
+    if (!d_iq || !d_out) return fail(FSEA_EINVAL, "NULL buffer");
+    if (((uintptr_t)d_iq | (uintptr_t)d_out) & 15) return fail(FSEA_EINVAL, "d_iq and d_out must be 16-byte aligned");
+    if (n_samples > ((size_t)1 << 40)) return fail(FSEA_EINVAL, "n_samples %zu too large", n_samples);
+    std::lock_guard<std::mutex> lock(f->mu);
+    FSEA_ON_DEVICE(f->device);
+    return fir_launch(f, FIR_IN_U8, d_iq, n_samples, flip, d_out, static_cast<hipStream_t>(stream));
+}
+
+int fsea_fir_u8_host(fsea_fir *f, const uint8_t *iq, size_t n_samples, int flip, float *out) {
+    return fir_host(f, FIR_IN_U8, iq, n_samples, flip, out);
+}
+
+int fsea_fir_f64_host(fsea_fir *f, const double *iq, size_t n_samples, float *out) {
+    return fir_host(f, FIR_IN_F64, iq, n_samples, 0, out);
+}
+
+}  // extern "C"

@@ -34,7 +34,10 @@ EXPORTS = [
     "fsea_history_shift", "fsea_history_get_f64",
     "fsea_plan_set_window", "fsea_plan_window_form", "fsea_window_fill",
     "fsea_stream_create", "fsea_stream_destroy", "fsea_copy_to_device_async", "fsea_copy_to_host_async",
+    "fsea_fir_lowpass_taps", "fsea_fir_create", "fsea_fir_destroy", "fsea_fir_reset", "fsea_fir_n_taps",
+    "fsea_fir_u8_device", "fsea_fir_u8_host", "fsea_fir_f64_host",
 ]
+FIR_MAX_TAPS = 512          # FSEA_FIR_MAX_TAPS (include/fsea.h)
 # include/fsea_tune.h: only libfsea_hip_tune.so (scripts/tune.py and friends) has these
 TUNE_EXPORTS = ["fsea_plan_create_variant", "fsea_time_exec_u8_device", "fsea_time_exec_u8_rotating",
                 "fsea_plan_read_trace", "fsea_tune_stream_1to2"]
@@ -132,6 +135,14 @@ def hip_lib():
         L.fsea_plan_set_window.argtypes = [vp, vp]
         L.fsea_plan_window_form.argtypes = [vp]
         L.fsea_window_fill.argtypes = [ci, ci, vp]
+        L.fsea_fir_lowpass_taps.argtypes = [ctypes.c_double, ctypes.c_double, ci, vp]
+        L.fsea_fir_create.argtypes = [ctypes.POINTER(vp), vp, ci, ci]
+        L.fsea_fir_destroy.argtypes = [vp]
+        L.fsea_fir_reset.argtypes = [vp]
+        L.fsea_fir_n_taps.argtypes = [vp]
+        L.fsea_fir_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
+        L.fsea_fir_u8_host.argtypes = [vp, vp, sz, ci, vp]
+        L.fsea_fir_f64_host.argtypes = [vp, vp, sz, vp]
         _LIB = L
     return _LIB
 
@@ -312,6 +323,62 @@ class Plan:
         _check(self._L.fsea_mean_magnitude_u8_device(self._p, d_iq_ptr, n_frames, int(bool(flip)),
                                                      ctypes.byref(m), stream or None))
         return m.value
+
+
+def lowpass_taps(sample_rate, half_ampl_freq, length):
+    """fsea_fir_lowpass_taps: the reference's low-pass design (nrf_fir_get_low_pass_coefficients), its first `length` taps."""
+    taps = np.empty(max(int(length), 1), dtype=np.float64)
+    _check(hip_lib().fsea_fir_lowpass_taps(float(sample_rate), float(half_ampl_freq), int(length), taps.ctypes.data))
+    return taps[:length]
+
+
+class Fir:
+    """A streaming complex FIR filter with real taps on one device; thin wrapper over fsea_fir_*.  Each call continues
+    the signal of the previous ones (the last n_taps - 1 samples are carried over); reset() starts a new one."""
+
+    def __init__(self, taps, device=0):
+        self._L = hip_lib()
+        self._f = ctypes.c_void_p()
+        t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
+        self.n_taps = t.size
+        self.device = device
+        _check(self._L.fsea_fir_create(ctypes.byref(self._f), t.ctypes.data if t.size else None, t.size, device))
+
+    def close(self):
+        if self._f:
+            self._L.fsea_fir_destroy(self._f)
+            self._f = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(self._L.fsea_fir_reset(self._f))
+
+    def run_device(self, d_iq_ptr, n_samples, d_out_ptr, flip=False, stream=0):
+        """Device pointers (ints, 16-byte aligned): 2 * n_samples bytes in, n_samples complex64 out; asynchronous."""
+        _check(self._L.fsea_fir_u8_device(self._f, d_iq_ptr, n_samples, int(bool(flip)), d_out_ptr, stream or None))
+
+    def run_u8(self, iq_u8, flip=False):
+        """Interleaved 8-bit IQ (host) -> complex64 of len(iq_u8) // 2 filtered samples."""
+        iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
+        out = np.empty(iq.size // 2, dtype=np.complex64)
+        _check(self._L.fsea_fir_u8_host(self._f, iq.ctypes.data, out.size, int(bool(flip)), out.ctypes.data))
+        return out
+
+    def run_f64(self, iq):
+        """Complex (or interleaved float64) IQ (host) -> complex64 filtered samples."""
+        a = np.asarray(iq)
+        if np.iscomplexobj(a):
+            flat = np.ascontiguousarray(a, dtype=np.complex128).ravel().view(np.float64)
+        else:
+            flat = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        out = np.empty(flat.size // 2, dtype=np.complex64)
+        _check(self._L.fsea_fir_f64_host(self._f, flat.ctypes.data, out.size, out.ctypes.data))
+        return out
 
 
 class PinnedArray:

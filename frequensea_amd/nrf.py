@@ -27,6 +27,8 @@ NRF_EXPORTS = [
     "nrf_fft_new", "nrf_fft_shift", "nrf_fft_process", "nrf_fft_get_buffer", "nrf_fft_free",
     "nrf_freq_shifter_new", "nrf_freq_shifter_process_samples", "nrf_freq_shifter_process",
     "nrf_freq_shifter_get_buffer", "nrf_freq_shifter_free",
+    "nrf_fir_get_low_pass_coefficients", "nrf_fir_filter_new", "nrf_fir_filter_load", "nrf_fir_filter_get",
+    "nrf_fir_filter_free", "nrf_iq_filter_new", "nrf_iq_filter_process", "nrf_iq_filter_get_buffer", "nrf_iq_filter_free",
 ]
 
 
@@ -72,6 +74,28 @@ def bind_nut(L):
     L.nut_buffer_save.argtypes = [NutBufferP, ctypes.c_char_p]
     L.nut_buffer_free.restype = None
     L.nut_buffer_free.argtypes = [NutBufferP]
+    return L
+
+
+class NrfFirFilter(ctypes.Structure):
+    """nrf_fir_filter (include/nrf.h): the reference's layout."""
+    _fields_ = [("length", ctypes.c_int), ("coefficients", ctypes.POINTER(ctypes.c_double)), ("offset", ctypes.c_int),
+                ("center", ctypes.c_int), ("samples_length", ctypes.c_int), ("samples", ctypes.POINTER(ctypes.c_double))]
+
+
+def bind_fir(L):
+    """Attach the host FIR filter prototypes (nrf_fir_*) to a loaded library (ours or a build of the reference)."""
+    fp = ctypes.POINTER(NrfFirFilter)
+    L.nrf_fir_get_low_pass_coefficients.restype = ctypes.POINTER(ctypes.c_double)
+    L.nrf_fir_get_low_pass_coefficients.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.nrf_fir_filter_new.restype = fp
+    L.nrf_fir_filter_new.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.nrf_fir_filter_load.restype = None
+    L.nrf_fir_filter_load.argtypes = [fp, ctypes.c_void_p, ctypes.c_int]
+    L.nrf_fir_filter_get.restype = ctypes.c_double
+    L.nrf_fir_filter_get.argtypes = [fp, ctypes.c_int]
+    L.nrf_fir_filter_free.restype = None
+    L.nrf_fir_filter_free.argtypes = [fp]
     return L
 
 
@@ -130,6 +154,15 @@ def nrf_lib():
         L.nrf_freq_shifter_get_buffer.argtypes = [vp]
         L.nrf_freq_shifter_free.restype = None
         L.nrf_freq_shifter_free.argtypes = [vp]
+        bind_fir(L)
+        L.nrf_iq_filter_new.restype = vp
+        L.nrf_iq_filter_new.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.nrf_iq_filter_process.restype = None
+        L.nrf_iq_filter_process.argtypes = [vp, NutBufferP]
+        L.nrf_iq_filter_get_buffer.restype = NutBufferP
+        L.nrf_iq_filter_get_buffer.argtypes = [vp]
+        L.nrf_iq_filter_free.restype = None
+        L.nrf_iq_filter_free.argtypes = [vp]
         _LIB = L
     return _LIB
 

@@ -26,6 +26,9 @@
  *                         rectangular; this is the optional w[n] beside it, fused into the same conversion
  *   fsea_plan_destroy     replaces fftw_destroy_plan/fftw_free
  *                         src/nrf.c:637-642, c/fft-batch.c:147-152
+ *   fsea_fir_*            the IQ low-pass filter behind nrf_iq_filter: the tap design of
+ *                         nrf_fir_get_low_pass_coefficients and the per-sample convolution loops of
+ *                         nrf_fir_filter_get / nrf_iq_filter_get_buffer, src/nrf.c:654-775
  *
  * Plain C: pointers, sizes and ints only; no HIP or torch types.  Device
  * pointers and streams cross the boundary as void* (a hipStream_t, e.g.
@@ -46,6 +49,7 @@ extern "C" {
 
 typedef struct fsea_plan fsea_plan;
 typedef struct fsea_history fsea_history;
+typedef struct fsea_fir fsea_fir;
 
 /* Epilogue modes.  Output element type and row length are per mode. */
 enum {
@@ -305,6 +309,39 @@ int fsea_plan_release_stream(fsea_plan *plan, void *stream);
  * Kernel variants, per-workgroup traces and the timing helper live in the separate tuning
  * library (include/fsea_tune.h, libfsea_hip_tune.so); this library has one kernel set per size. */
 const char *fsea_plan_kernel_name(const fsea_plan *plan);
+
+/* Streaming complex FIR filter with real taps: the IQ low-pass filter of the reference (src/nrf.c:654-775), one kernel
+ * launch per call.  Output i of a call on n samples x is
+ *   y[i] = sum_{k < L} c[k] x_ext[i + k],   x_ext = tail ++ x,  i < n,
+ * where the tail holds the last L - 1 samples of the previous calls (zeros after create and reset); after the call the
+ * tail is the last L - 1 values of x_ext (also when n < L - 1).  I and Q are filtered independently by the same taps.
+ * f32 taps, f32 arithmetic (one packed FMA per output sample and tap); output interleaved f32 (I, Q).
+ * Inputs: interleaved 8-bit IQ read as u8 / 256 (flip != 0: raw HackRF int8 bytes, b ^ 0x80 first, as
+ * fsea_exec_u8_device), or interleaved f64 IQ read as is (narrowed to f32). */
+#define FSEA_FIR_MAX_TAPS 512
+
+/* The reference's window-method low-pass design (nrf_fir_get_low_pass_coefficients, src/nrf.c:654-676) in double,
+ * bit for bit: m = length + (length + 1) % 2 taps are designed and normalised to sum 1, and the first `length` of them are
+ * written to taps -- for an even length that is the reference's filter as nrf_fir_filter_new uses it (asymmetric, not
+ * summing to 1).  Host arithmetic; needs no device. */
+int fsea_fir_lowpass_taps(double sample_rate, double half_ampl_freq, int length, double *taps);
+
+/* n_taps in [1, FSEA_FIR_MAX_TAPS]; the taps are copied (rounded to f32).  FSEA_EINVAL for a NULL pointer, n_taps out of
+ * range or a non-finite tap (checked before any device work); FSEA_ENODEVICE without a GPU.  Destroy waits for the device. */
+int fsea_fir_create(fsea_fir **fir, const double *taps, int n_taps, int device);
+int fsea_fir_destroy(fsea_fir *fir);
+/* Zeroes the tail (a fresh object's state).  Synchronous: waits for the device first. */
+int fsea_fir_reset(fsea_fir *fir);
+int fsea_fir_n_taps(const fsea_fir *fir);
+
+/* Device-resident form: d_iq holds 2 * n_samples bytes, d_out receives n_samples (I, Q) float pairs; both 16-byte aligned.
+ * Asynchronous on `stream`.  Calls on one object take effect in stream order: successive calls on one stream continue one
+ * signal; across streams the caller orders them (the tail of call k is read by call k + 1). */
+int fsea_fir_u8_device(fsea_fir *fir, const void *d_iq, size_t n_samples, int flip, void *d_out, void *stream);
+/* Host-buffer forms; return when `out` (2 * n_samples floats) is complete.  Staged through pinned memory on the object's
+ * own stream; calls on one object from several threads are serialised. */
+int fsea_fir_u8_host(fsea_fir *fir, const uint8_t *iq, size_t n_samples, int flip, float *out);
+int fsea_fir_f64_host(fsea_fir *fir, const double *iq, size_t n_samples, float *out);
 
 const char *fsea_last_error_string(void);
 

@@ -13,6 +13,9 @@
  *                      _get_buffer / _free -- identical signatures
  *   src/nrf.h:192-207  nrf_freq_shifter, the block lua/fft-shifted.lua puts in
  *                      front of nrf_fft (host arithmetic, as in the reference)
+ *   src/nrf.h:145-175  nrf_fir_filter (host, double, as in the reference) and
+ *                      nrf_iq_filter, whose convolution runs on the GPU
+ *                      (fsea_fir_*, include/fsea.h)
  * Differences, all invisible to callers: <fftw3.h> is gone, the FFTW-typed
  * members of nrf_fft (touched by nobody outside src/nrf.c) became an opaque
  * backend handle, the history is a ring instead of an 8 MiB memmove per row,
@@ -182,5 +185,48 @@ void nrf_freq_shifter_process(nrf_freq_shifter *shifter, nut_buffer *buffer);
 /* Copy of the last output (NULL before the first process call). */
 nut_buffer *nrf_freq_shifter_get_buffer(nrf_freq_shifter *shifter);
 void nrf_freq_shifter_free(nrf_freq_shifter *shifter);
+
+/* ---- FIR filter and IQ filter (src/nrf.h:145-175, src/nrf.c:654-775) ---- */
+
+/* The per-sample pull filter, on the host in double, bit for bit the reference's.  `length` taps are used of the
+ * length + (length + 1) % 2 designed ones (an even length: an asymmetric filter that does not sum to 1, as in the
+ * reference); `samples` holds the last offset = length - 1 samples of the previous loads followed by the last load. */
+typedef struct {
+    int length;
+    double *coefficients;
+    int offset;
+    int center;
+    int samples_length;
+    double *samples;
+} nrf_fir_filter;
+
+/* malloc'd array of length + (length + 1) % 2 taps (window-method low-pass, normalised to sum 1). */
+double *nrf_fir_get_low_pass_coefficients(int sample_rate, int half_ampl_freq, int length);
+nrf_fir_filter *nrf_fir_filter_new(int sample_rate, int half_ampl_freq, int length);
+void nrf_fir_filter_load(nrf_fir_filter *filter, double *samples, int length);
+/* sum_{i < length} coefficients[i] * samples[index + i]: output `index` of the last load. */
+double nrf_fir_filter_get(nrf_fir_filter *filter, int index);
+void nrf_fir_filter_free(nrf_fir_filter *filter);
+
+/* The IQ low-pass filter: I and Q through the same taps, state carried from call to call, the convolution on the GPU in
+ * f32 (fsea_fir_*: one kernel launch per process call).  kernel_length must lie in [1, FSEA_FIR_MAX_TAPS] (512): anything
+ * else prints and exits, as does a backend failure (no GPU).  The reference keeps two nrf_fir_filter and the de-interleaved
+ * input here; this block keeps the backend object and the last call's output instead. */
+typedef struct {
+    NRF_BLOCK;
+    int length;          /* taps */
+    int samples_length;  /* IQ pairs of the last process call (the length of the next get_buffer) */
+    void *backend;       /* fsea_fir* (libfsea_hip.so) */
+    float *output;       /* the last call's samples_length filtered (I, Q) pairs */
+    int output_capacity; /* pairs */
+    pthread_mutex_t mutex;
+} nrf_iq_filter;
+
+nrf_iq_filter *nrf_iq_filter_new(int sample_rate, int half_ampl_freq, int kernel_length);
+/* Filters buffer->length IQ pairs (u8 values count as u8 / 256.0, f64 as is; 2 channels). */
+void nrf_iq_filter_process(nrf_iq_filter *filter, nut_buffer *buffer);
+/* Fresh F64 buffer of the last call's length with 2 channels, interleaved I, Q; length 0 before any process call. */
+nut_buffer *nrf_iq_filter_get_buffer(nrf_iq_filter *f);
+void nrf_iq_filter_free(nrf_iq_filter *filter);
 
 #endif /* NRF_H */
