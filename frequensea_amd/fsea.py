@@ -36,8 +36,12 @@ EXPORTS = [
     "fsea_stream_create", "fsea_stream_destroy", "fsea_copy_to_device_async", "fsea_copy_to_host_async",
     "fsea_fir_lowpass_taps", "fsea_fir_create", "fsea_fir_destroy", "fsea_fir_reset", "fsea_fir_n_taps",
     "fsea_fir_u8_device", "fsea_fir_u8_host", "fsea_fir_f64_host",
+    "fsea_iq_draw_create", "fsea_iq_draw_destroy", "fsea_iq_points_device", "fsea_iq_lines_device",
+    "fsea_iq_points_host", "fsea_iq_lines_host",
 ]
 FIR_MAX_TAPS = 512          # FSEA_FIR_MAX_TAPS (include/fsea.h)
+IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
+IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 # include/fsea_tune.h: only libfsea_hip_tune.so (scripts/tune.py and friends) has these
 TUNE_EXPORTS = ["fsea_plan_create_variant", "fsea_time_exec_u8_device", "fsea_time_exec_u8_rotating",
                 "fsea_plan_read_trace", "fsea_tune_stream_1to2"]
@@ -143,6 +147,12 @@ def hip_lib():
         L.fsea_fir_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
         L.fsea_fir_u8_host.argtypes = [vp, vp, sz, ci, vp]
         L.fsea_fir_f64_host.argtypes = [vp, vp, sz, vp]
+        L.fsea_iq_draw_create.argtypes = [ctypes.POINTER(vp), ci]
+        L.fsea_iq_draw_destroy.argtypes = [vp]
+        L.fsea_iq_points_device.argtypes = [vp, vp, ci, ci, sz, ci, vp, vp]
+        L.fsea_iq_lines_device.argtypes = [vp, vp, ci, ci, sz, ci, ci, vp, vp]
+        L.fsea_iq_points_host.argtypes = [vp, vp, ci, ci, sz, vp]
+        L.fsea_iq_lines_host.argtypes = [vp, vp, ci, ci, sz, ci, vp]
         _LIB = L
     return _LIB
 
@@ -379,6 +389,75 @@ class Fir:
         out = np.empty(flat.size // 2, dtype=np.complex64)
         _check(self._L.fsea_fir_f64_host(self._f, flat.ctypes.data, out.size, out.ctypes.data))
         return out
+
+
+def _iq_input(iq):
+    """A host IQ array -> (contiguous flat array, FSEA_IQ_* type, pairs).  uint8, float32 and float64 pass as they are;
+    complex64 / complex128 as their interleaved float parts."""
+    a = np.asarray(iq)
+    if a.dtype == np.complex64:
+        a = a.view(np.float32)
+    elif a.dtype == np.complex128:
+        a = a.view(np.float64)
+    kinds = {np.dtype(np.uint8): IQ_U8, np.dtype(np.float32): IQ_F32, np.dtype(np.float64): IQ_F64}
+    if a.dtype not in kinds:
+        raise TypeError("IQ input must be uint8, float32, float64 or complex, got %s" % a.dtype)
+    a = np.ascontiguousarray(a).ravel()
+    return a, kinds[a.dtype], a.size // 2
+
+
+class IqDraw:
+    """IQ constellation images on one device; thin wrapper over fsea_iq_*.  points(): the 256 x 256 histogram of the
+    reference's nrf_buffer_to_iq_points (bin I * 256 + Q, counts modulo 256); lines(): the (256 m)^2 image of
+    nrf_buffer_to_iq_lines (consecutive points joined by its Bresenham lines, pixel (I m, Q m) at row Q m, counts clamped to
+    255).  Coordinates as nut_buffer_get_u8: u8 as is, floats as x86-64's (uint8_t)(v * 256.0)."""
+
+    def __init__(self, device=0):
+        self._L = hip_lib()
+        self._d = ctypes.c_void_p()
+        self.device = device
+        _check(self._L.fsea_iq_draw_create(ctypes.byref(self._d), device))
+
+    def close(self):
+        if self._d:
+            self._L.fsea_iq_draw_destroy(self._d)
+            self._d = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def points(self, iq, flip=False):
+        """Host IQ (uint8, float32, float64 interleaved, or complex) -> (256, 256) uint8, row I."""
+        a, kind, n = _iq_input(iq)
+        img = np.empty((256, 256), dtype=np.uint8)
+        _check(self._L.fsea_iq_points_host(self._d, a.ctypes.data, kind, int(bool(flip)), n, img.ctypes.data))
+        return img
+
+    def lines(self, iq, m=1, n_points=None, flip=False):
+        """Host IQ -> (256 m, 256 m) uint8, row y = Q m; the first n_points points (default all) joined in order."""
+        a, kind, n = _iq_input(iq)
+        if n_points is not None:
+            if not 0 <= int(n_points) <= n:
+                raise ValueError("n_points must be in [0, %d] (the pairs of iq), got %d" % (n, int(n_points)))
+            n = int(n_points)
+        img = np.empty((256 * m, 256 * m), dtype=np.uint8)
+        _check(self._L.fsea_iq_lines_host(self._d, a.ctypes.data, kind, int(bool(flip)), n, int(m), img.ctypes.data))
+        return img
+
+    def points_device(self, d_iq_ptr, kind, n_pairs, n_frames, d_image_ptr, flip=False, stream=0):
+        """Device pointers (ints, 16-byte aligned): n_frames frames of n_pairs pairs in, n_frames 65536-byte images out;
+        asynchronous."""
+        _check(self._L.fsea_iq_points_device(self._d, d_iq_ptr, kind, int(bool(flip)), n_pairs, n_frames, d_image_ptr,
+                                             stream or None))
+
+    def lines_device(self, d_iq_ptr, kind, n_points, n_frames, m, d_image_ptr, flip=False, stream=0):
+        """Device pointers (ints, 16-byte aligned): n_frames frames of n_points points in, n_frames (256 m)^2-byte images
+        out; asynchronous."""
+        _check(self._L.fsea_iq_lines_device(self._d, d_iq_ptr, kind, int(bool(flip)), n_points, n_frames, int(m),
+                                            d_image_ptr, stream or None))
 
 
 class PinnedArray:

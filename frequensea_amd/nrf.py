@@ -29,6 +29,8 @@ NRF_EXPORTS = [
     "nrf_freq_shifter_get_buffer", "nrf_freq_shifter_free",
     "nrf_fir_get_low_pass_coefficients", "nrf_fir_filter_new", "nrf_fir_filter_load", "nrf_fir_filter_get",
     "nrf_fir_filter_free", "nrf_iq_filter_new", "nrf_iq_filter_process", "nrf_iq_filter_get_buffer", "nrf_iq_filter_free",
+    "nrf_device_get_iq_buffer", "nrf_device_get_iq_lines", "nrf_buffer_add_position_channel", "nrf_buffer_to_iq_points",
+    "nrf_buffer_to_iq_lines", "nrf_signal_detector_new", "nrf_signal_detector_process", "nrf_signal_detector_free",
 ]
 
 
@@ -99,6 +101,34 @@ def bind_fir(L):
     return L
 
 
+class NrfSignalDetector(ctypes.Structure):
+    """nrf_signal_detector (include/nrf.h): the reference's layout."""
+    _fields_ = [("mean", ctypes.c_double), ("standard_deviation", ctypes.c_double)]
+
+
+def bind_iq_draw(L):
+    """Attach the IQ drawing and signal detector prototypes to a loaded library (ours or a build of the reference)."""
+    vp = ctypes.c_void_p
+    dp = ctypes.POINTER(NrfSignalDetector)
+    L.nrf_device_get_iq_buffer.restype = NutBufferP
+    L.nrf_device_get_iq_buffer.argtypes = [vp]
+    L.nrf_device_get_iq_lines.restype = NutBufferP
+    L.nrf_device_get_iq_lines.argtypes = [vp, ctypes.c_int, ctypes.c_float]
+    L.nrf_buffer_add_position_channel.restype = NutBufferP
+    L.nrf_buffer_add_position_channel.argtypes = [NutBufferP]
+    L.nrf_buffer_to_iq_points.restype = NutBufferP
+    L.nrf_buffer_to_iq_points.argtypes = [NutBufferP]
+    L.nrf_buffer_to_iq_lines.restype = NutBufferP
+    L.nrf_buffer_to_iq_lines.argtypes = [NutBufferP, ctypes.c_int, ctypes.c_float]
+    L.nrf_signal_detector_new.restype = dp
+    L.nrf_signal_detector_new.argtypes = []
+    L.nrf_signal_detector_process.restype = None
+    L.nrf_signal_detector_process.argtypes = [dp, NutBufferP]
+    L.nrf_signal_detector_free.restype = None
+    L.nrf_signal_detector_free.argtypes = [dp]
+    return L
+
+
 _LIB = None
 
 
@@ -163,6 +193,7 @@ def nrf_lib():
         L.nrf_iq_filter_get_buffer.argtypes = [vp]
         L.nrf_iq_filter_free.restype = None
         L.nrf_iq_filter_free.argtypes = [vp]
+        bind_iq_draw(L)
         _LIB = L
     return _LIB
 

@@ -29,6 +29,9 @@
  *   fsea_fir_*            the IQ low-pass filter behind nrf_iq_filter: the tap design of
  *                         nrf_fir_get_low_pass_coefficients and the per-sample convolution loops of
  *                         nrf_fir_filter_get / nrf_iq_filter_get_buffer, src/nrf.c:654-775
+ *   fsea_iq_*             the IQ constellation images: the per-sample loops of nrf_buffer_to_iq_points /
+ *                         nrf_device_get_iq_buffer and the Bresenham rasteriser of nrf_buffer_to_iq_lines /
+ *                         nrf_device_get_iq_lines, src/nrf.c:359-421, 519-553
  *
  * Plain C: pointers, sizes and ints only; no HIP or torch types.  Device
  * pointers and streams cross the boundary as void* (a hipStream_t, e.g.
@@ -50,6 +53,7 @@ extern "C" {
 typedef struct fsea_plan fsea_plan;
 typedef struct fsea_history fsea_history;
 typedef struct fsea_fir fsea_fir;
+typedef struct fsea_iq_draw fsea_iq_draw;
 
 /* Epilogue modes.  Output element type and row length are per mode. */
 enum {
@@ -342,6 +346,40 @@ int fsea_fir_u8_device(fsea_fir *fir, const void *d_iq, size_t n_samples, int fl
  * own stream; calls on one object from several threads are serialised. */
 int fsea_fir_u8_host(fsea_fir *fir, const uint8_t *iq, size_t n_samples, int flip, float *out);
 int fsea_fir_f64_host(fsea_fir *fir, const double *iq, size_t n_samples, float *out);
+
+/* IQ constellation images (src/nrf.c:359-421, 519-553).  The input is interleaved (I, Q) pairs of one element type:
+ * FSEA_IQ_U8 bytes used as they are (flip != 0: raw HackRF int8 bytes, b ^ 0x80 first, as fsea_fir_u8_device), or
+ * FSEA_IQ_F32 / FSEA_IQ_F64 values v whose coordinate is the reference's nut_buffer_get_u8 on x86-64:
+ * (uint8_t)(v * 256.0) computed as cvttsd2si -- truncation to int32, 0x80000000 for NaN and anything whose truncation lies
+ * outside the int32 range -- then the low byte (so -0.01 -> 254, 1.0 -> 0, NaN -> 0).  An f32 value gives the
+ * coordinate of its exact f64 widening.
+ *   points: a 256 x 256 u8 image, bin I * 256 + Q (I is the row), each pair adds 1 modulo 256 (the reference's u8++ wraps).
+ *   lines:  a (256 m)^2 u8 image, m = size_multiplier in [1, FSEA_IQ_MAX_MULTIPLIER]; for consecutive points P[k-1], P[k]
+ *           (0 < k < n_points) the reference's draw_line -- Bresenham with err = (dx > dy ? dx : -dy) / 2, both endpoints
+ *           included -- adds 1 to every pixel from (I[k-1] m, Q[k-1] m) to (I[k] m, Q[k] m); pixel (x, y) is at
+ *           y * 256 m + x, transposed relative to the points image.  Each pixel is min(count, 255) (pixel_inc saturates).
+ * The order of the increments does not change either image: both are exact and deterministic.
+ * Batched device forms: frame f is the n pairs (points) or n_points points (lines) at pair f * n of d_iq, and its image
+ * is the f-th 65536-byte (points) or (256 m)^2-byte (lines) image of d_image; d_iq and d_image 16-byte aligned.
+ * Asynchronous on `stream`.  The line images are counted in a u32 buffer that the object owns: its calls on several
+ * streams follow one another on the device (each waits for an event the previous one recorded).
+ * Host forms: one frame; return when `image` is complete; staged through pinned memory on the object's own stream, calls
+ * on one object from several threads are serialised.
+ * Every form checks its arguments before any device work: FSEA_EINVAL for a NULL object or buffer, an unknown type, an m
+ * outside [1, FSEA_IQ_MAX_MULTIPLIER], n_frames < 0, or more than 2^31 pairs per frame.  Create: FSEA_ENODEVICE without a
+ * GPU.  Destroy waits for the device. */
+enum { FSEA_IQ_U8 = 0, FSEA_IQ_F32 = 1, FSEA_IQ_F64 = 2 };
+#define FSEA_IQ_MAX_MULTIPLIER 16
+
+int fsea_iq_draw_create(fsea_iq_draw **draw, int device);
+int fsea_iq_draw_destroy(fsea_iq_draw *draw);
+int fsea_iq_points_device(fsea_iq_draw *draw, const void *d_iq, int type, int flip, size_t n_pairs, int n_frames,
+                          void *d_image, void *stream);
+int fsea_iq_lines_device(fsea_iq_draw *draw, const void *d_iq, int type, int flip, size_t n_points, int n_frames,
+                         int size_multiplier, void *d_image, void *stream);
+int fsea_iq_points_host(fsea_iq_draw *draw, const void *iq, int type, int flip, size_t n_pairs, uint8_t *image);
+int fsea_iq_lines_host(fsea_iq_draw *draw, const void *iq, int type, int flip, size_t n_points, int size_multiplier,
+                       uint8_t *image);
 
 const char *fsea_last_error_string(void);
 

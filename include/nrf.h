@@ -16,6 +16,9 @@
  *   src/nrf.h:145-175  nrf_fir_filter (host, double, as in the reference) and
  *                      nrf_iq_filter, whose convolution runs on the GPU
  *                      (fsea_fir_*, include/fsea.h)
+ *   src/nrf.h:100-101, 122-124, 209-218  the IQ drawing functions, whose
+ *                      per-sample loops run on the GPU (fsea_iq_*, include/fsea.h),
+ *                      and the signal detector (host, double)
  * Differences, all invisible to callers: <fftw3.h> is gone, the FFTW-typed
  * members of nrf_fft (touched by nobody outside src/nrf.c) became an opaque
  * backend handle, the history is a ring instead of an 8 MiB memmove per row,
@@ -120,6 +123,11 @@ void nrf_device_set_paused(nrf_device *device, int paused);
 void nrf_device_step(nrf_device *device);
 /* Locked snapshot: u8, length NRF_SAMPLES_LENGTH, 2 channels (src/nrf.c:352-357). */
 nut_buffer *nrf_device_get_samples_buffer(nrf_device *device);
+/* The IQ images of the current block (src/nrf.c:359-372, 399-421): nrf_buffer_to_iq_points / _iq_lines (below) on all
+ * NRF_BUFFER_SIZE_BYTES of device->samples.  The block is copied under data_mutex, which is released before the GPU
+ * draws (the reference holds it throughout). */
+nut_buffer *nrf_device_get_iq_buffer(nrf_device *device);
+nut_buffer *nrf_device_get_iq_lines(nrf_device *device, int size_multiplier, float line_percentage);
 void nrf_device_free(nrf_device *device);
 
 /* ---- FFT analysis (src/nrf.h:128-142, src/nrf.c:557-642) ---------------- */
@@ -228,5 +236,36 @@ void nrf_iq_filter_process(nrf_iq_filter *filter, nut_buffer *buffer);
 /* Fresh F64 buffer of the last call's length with 2 channels, interleaved I, Q; length 0 before any process call. */
 nut_buffer *nrf_iq_filter_get_buffer(nrf_iq_filter *f);
 void nrf_iq_filter_free(nrf_iq_filter *filter);
+
+/* ---- IQ drawing (src/nrf.h:122-124, src/nrf.c:499-553) ---- */
+
+/* A copy of `buffer` with one channel more: after each group of `channels` elements, t = i / (double)size, i the group's
+ * first element and size = length * channels.  Host arithmetic (nut_buffer_get_f64 / _set_f64: a U8 result holds
+ * (uint8_t)(t * 256.0)). */
+nut_buffer *nrf_buffer_add_position_channel(nut_buffer *buffer);
+/* The 256 x 256 U8 point histogram (length 65536, 1 channel) of the length * channels elements of `buffer` read pairwise
+ * as (I, Q) whatever its channel count (an incomplete last pair is ignored), coordinates by nut_buffer_get_u8; bin
+ * I * 256 + Q, each pair adding 1 modulo 256 as the reference's u8++.  Drawn on the GPU (fsea_iq_points_host). */
+nut_buffer *nrf_buffer_to_iq_points(nut_buffer *buffer);
+/* The (256 m)^2 U8 line image, m = size_multiplier: line_percentage is clamped to [0, 1] (a NaN draws nothing), the
+ * points at elements i = 0, 2, ... < (int)((float)size * line_percentage) are joined by the reference's draw_line
+ * (Bresenham, both endpoints included) from each to the next, pixel (I m, Q m) at Q m * 256 m + I m (transposed relative
+ * to the points image), each pixel saturating at 255.  Drawn on the GPU (fsea_iq_lines_host).  Deliberate difference: a
+ * size_multiplier outside [1, FSEA_IQ_MAX_MULTIPLIER] (16) prints and exits; the reference would allocate an image of
+ * zero or negative size.  Both functions return a fresh buffer that the caller frees. */
+nut_buffer *nrf_buffer_to_iq_lines(nut_buffer *buffer, int size_multiplier, float line_percentage);
+
+/* ---- Signal detector (src/nrf.h:209-218, src/nrf.c:876-903): host, double, the reference's layout ---- */
+
+/* process: mean = 2 * (sum of the I elements) / size, standard_deviation = sqrt(sum over all elements of
+ * (x - mean)^2 / mean), size = length * channels, elements by nut_buffer_get_f64. */
+typedef struct {
+    double mean;
+    double standard_deviation;
+} nrf_signal_detector;
+
+nrf_signal_detector *nrf_signal_detector_new();
+void nrf_signal_detector_process(nrf_signal_detector *detector, nut_buffer *buffer);
+void nrf_signal_detector_free(nrf_signal_detector *detector);
 
 #endif /* NRF_H */
