@@ -38,10 +38,15 @@ EXPORTS = [
     "fsea_fir_u8_device", "fsea_fir_u8_host", "fsea_fir_f64_host",
     "fsea_iq_draw_create", "fsea_iq_draw_destroy", "fsea_iq_points_device", "fsea_iq_lines_device",
     "fsea_iq_points_host", "fsea_iq_lines_host",
+    "fsea_demod_create", "fsea_demod_destroy", "fsea_demod_reset", "fsea_demod_set_channel", "fsea_demod_get_channel",
+    "fsea_demod_out_length", "fsea_demod_u8_device", "fsea_demod_u8_host", "fsea_demod_f64_host",
 ]
 FIR_MAX_TAPS = 512          # FSEA_FIR_MAX_TAPS (include/fsea.h)
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
+DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
+DEMOD_MAX_CHANNELS = 256            # FSEA_DEMOD_MAX_CHANNELS
+DEMOD_MAX_SAMPLES = 1 << 24         # FSEA_DEMOD_MAX_SAMPLES
 # include/fsea_tune.h: only libfsea_hip_tune.so (scripts/tune.py and friends) has these
 TUNE_EXPORTS = ["fsea_plan_create_variant", "fsea_time_exec_u8_device", "fsea_time_exec_u8_rotating",
                 "fsea_plan_read_trace", "fsea_tune_stream_1to2"]
@@ -153,6 +158,17 @@ def hip_lib():
         L.fsea_iq_lines_device.argtypes = [vp, vp, ci, ci, sz, ci, ci, vp, vp]
         L.fsea_iq_points_host.argtypes = [vp, vp, ci, ci, sz, vp]
         L.fsea_iq_lines_host.argtypes = [vp, vp, ci, ci, sz, ci, vp]
+        L.fsea_demod_create.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci, ci]
+        L.fsea_demod_destroy.argtypes = [vp]
+        L.fsea_demod_reset.argtypes = [vp]
+        L.fsea_demod_set_channel.argtypes = [vp, ci, ci, ctypes.c_double, ctypes.c_double]
+        L.fsea_demod_get_channel.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double)]
+        L.fsea_demod_out_length.argtypes = [vp, sz]
+        L.fsea_demod_out_length.restype = sz
+        L.fsea_demod_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
+        L.fsea_demod_u8_host.argtypes = [vp, vp, sz, ci, vp]
+        L.fsea_demod_f64_host.argtypes = [vp, vp, vp, sz, vp]
         _LIB = L
     return _LIB
 
@@ -388,6 +404,66 @@ class Fir:
             flat = np.ascontiguousarray(a, dtype=np.float64).ravel()
         out = np.empty(flat.size // 2, dtype=np.complex64)
         _check(self._L.fsea_fir_f64_host(self._f, flat.ctypes.data, out.size, out.ctypes.data))
+        return out
+
+
+class Demod:
+    """The reference's audio chain (RAW or WBFM, nrf_decoder's conversion and frequency shift) on n_channels channels of
+    one input stream; thin wrapper over fsea_demod_*.  Each call continues every channel's signal; reset() starts anew."""
+
+    def __init__(self, kind, in_rate, out_rate=48000, n_channels=1, device=0):
+        self._L = hip_lib()
+        self._d = ctypes.c_void_p()
+        self.kind = {"raw": DEMOD_RAW, "wbfm": DEMOD_WBFM}.get(kind, kind)
+        self.in_rate, self.out_rate, self.n_channels, self.device = in_rate, out_rate, n_channels, device
+        _check(self._L.fsea_demod_create(ctypes.byref(self._d), self.kind, in_rate, out_rate, n_channels, device))
+
+    def close(self):
+        if self._d:
+            self._L.fsea_demod_destroy(self._d)
+            self._d = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(self._L.fsea_demod_reset(self._d))
+
+    def set_channel(self, ch, freq_offset, cosine=1.0, sine=0.0):
+        _check(self._L.fsea_demod_set_channel(self._d, ch, int(freq_offset), float(cosine), float(sine)))
+
+    def get_channel(self, ch):
+        """(freq_offset, cosine, sine) the channel starts its next call with."""
+        o, c, s = ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
+        _check(self._L.fsea_demod_get_channel(self._d, ch, ctypes.byref(o), ctypes.byref(c), ctypes.byref(s)))
+        return o.value, c.value, s.value
+
+    def out_length(self, n_samples):
+        return self._L.fsea_demod_out_length(self._d, n_samples)
+
+    def run_device(self, d_iq_ptr, n_samples, d_audio_ptr, flip=False, stream=0):
+        """Device pointers (ints): 2 * n_samples bytes in, n_channels x out_length f64 out; asynchronous."""
+        _check(self._L.fsea_demod_u8_device(self._d, d_iq_ptr, n_samples, int(bool(flip)), d_audio_ptr, stream or None))
+
+    def run_u8(self, iq_u8, flip=False):
+        """Interleaved 8-bit IQ (host) -> float64 array (n_channels, out_length)."""
+        iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
+        n = iq.size // 2
+        out = np.empty((self.n_channels, self.out_length(n)), dtype=np.float64)
+        _check(self._L.fsea_demod_u8_host(self._d, iq.ctypes.data, n, int(bool(flip)), out.ctypes.data))
+        return out
+
+    def run_f64(self, i, q):
+        """Separate I and Q float64 arrays (host), converted by nothing -> float64 array (n_channels, out_length)."""
+        i = np.ascontiguousarray(i, dtype=np.float64).ravel()
+        q = np.ascontiguousarray(q, dtype=np.float64).ravel()
+        if i.size != q.size:
+            raise ValueError("I and Q differ in length")
+        out = np.empty((self.n_channels, self.out_length(i.size)), dtype=np.float64)
+        _check(self._L.fsea_demod_f64_host(self._d, i.ctypes.data, q.ctypes.data, i.size, out.ctypes.data))
         return out
 
 

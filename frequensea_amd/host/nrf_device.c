@@ -61,7 +61,9 @@ static void ingest_block(nrf_device *device, const uint8_t *block) {
         memcpy(device->samples + i, &w, 8);
     }
     pthread_mutex_unlock(&device->data_mutex);
+    pthread_mutex_lock(&device->decode_mutex);
     if (device->decode_cb_fn != NULL) device->decode_cb_fn(device, device->decode_cb_ctx);
+    pthread_mutex_unlock(&device->decode_mutex);
     if (!device->receiving) return;
     nrf_block_process(&device->block, NULL);
 }
@@ -123,6 +125,7 @@ nrf_device *nrf_device_new_with_config(const nrf_device_config config) {
     }
     nrf_block_init(&device->block, NRF_BLOCK_SOURCE, NULL, (nrf_block_result_fn)nrf_device_get_samples_buffer);
     pthread_mutex_init(&device->data_mutex, NULL);
+    pthread_mutex_init(&device->decode_mutex, NULL);
     replay_start(device, config.data_file);
     if (config.sample_rate > 0) device->sample_rate = config.sample_rate;
     return device;
@@ -134,8 +137,11 @@ double nrf_device_set_frequency(nrf_device *device, double freq_mhz) {
 }
 
 void nrf_device_set_decode_handler(nrf_device *device, nrf_device_decode_cb_fn fn, void *ctx) {
+    /* waits for a call of the previous handler in flight (nrf_player_free frees its context right after) */
+    pthread_mutex_lock(&device->decode_mutex);
     device->decode_cb_fn = fn;
     device->decode_cb_ctx = ctx;
+    pthread_mutex_unlock(&device->decode_mutex);
 }
 
 void nrf_device_set_paused(nrf_device *device, int paused) { device->paused = paused; }
@@ -157,6 +163,7 @@ void nrf_device_free(nrf_device *device) {
     device->receiving = 0;
     pthread_join(device->receive_thread, NULL);
     pthread_mutex_destroy(&device->data_mutex);
+    pthread_mutex_destroy(&device->decode_mutex);
     free(device->receive_buffer);
     free(device);
 }

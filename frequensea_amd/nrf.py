@@ -19,7 +19,7 @@ NUT_EXPORTS = [
     "nut_buffer_convert", "nut_buffer_save", "nut_buffer_free",
 ]
 # additions beside the reference's prototypes (include/nrf.h says so at each): the reference's nrf.h has no such function
-NRF_ADDITIONS = ["nrf_fft_set_window", "nrf_fft_set_window_weights"]
+NRF_ADDITIONS = ["nrf_fft_set_window", "nrf_fft_set_window_weights", "nrf_decoder_free", "nrf_player_pop_pcm"]
 NRF_EXPORTS = [
     "nrf_block_init", "nrf_block_connect", "nrf_block_process", "nrf_device_new",
     "nrf_device_new_with_config", "nrf_device_set_frequency", "nrf_device_set_decode_handler",
@@ -31,7 +31,12 @@ NRF_EXPORTS = [
     "nrf_fir_filter_free", "nrf_iq_filter_new", "nrf_iq_filter_process", "nrf_iq_filter_get_buffer", "nrf_iq_filter_free",
     "nrf_device_get_iq_buffer", "nrf_device_get_iq_lines", "nrf_buffer_add_position_channel", "nrf_buffer_to_iq_points",
     "nrf_buffer_to_iq_lines", "nrf_signal_detector_new", "nrf_signal_detector_process", "nrf_signal_detector_free",
+    "nrf_downsampler_new", "nrf_downsampler_process", "nrf_downsampler_free", "nrf_raw_demodulator_new",
+    "nrf_raw_demodulator_process", "nrf_raw_demodulator_free", "nrf_fm_demodulator_new", "nrf_fm_demodulator_process",
+    "nrf_fm_demodulator_free", "nrf_decoder_new", "nrf_decoder_process", "nrf_player_new", "nrf_player_set_freq_offset",
+    "nrf_player_set_gain", "nrf_player_free",
 ]
+NRF_DEMODULATE_RAW, NRF_DEMODULATE_WBFM = 0, 1
 
 
 class NutData(ctypes.Union):
@@ -129,6 +134,94 @@ def bind_iq_draw(L):
     return L
 
 
+class NrfBlock(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_int), ("process_fn", ctypes.c_void_p), ("result_fn", ctypes.c_void_p),
+                ("n_outputs", ctypes.c_int), ("outputs", ctypes.c_void_p * 10)]
+
+
+class NrfFreqShifter(ctypes.Structure):
+    """nrf_freq_shifter (include/nrf.h): the reference's layout."""
+    _fields_ = [("block", NrfBlock), ("freq_offset", ctypes.c_int), ("sample_rate", ctypes.c_int),
+                ("cosine", ctypes.c_double), ("sine", ctypes.c_double), ("buffer", NutBufferP)]
+
+
+_dp = ctypes.POINTER(ctypes.c_double)
+
+
+class NrfDownsampler(ctypes.Structure):
+    """nrf_downsampler (include/nrf.h): the reference's layout."""
+    _fields_ = [("in_rate", ctypes.c_int), ("out_rate", ctypes.c_int), ("filter", ctypes.POINTER(NrfFirFilter)),
+                ("rate_mul", ctypes.c_double), ("out_length", ctypes.c_int), ("out_samples", _dp)]
+
+
+class NrfRawDemodulator(ctypes.Structure):
+    """nrf_raw_demodulator: the reference's members (this build appends a backend handle)."""
+    _fields_ = [("in_sample_rate", ctypes.c_int), ("out_sample_rate", ctypes.c_int),
+                ("downsampler_audio", ctypes.POINTER(NrfDownsampler)), ("audio_samples", _dp),
+                ("audio_samples_length", ctypes.c_int)]
+
+
+class NrfFmDemodulator(ctypes.Structure):
+    """nrf_fm_demodulator: the reference's members (this build appends a backend handle)."""
+    _fields_ = [("in_sample_rate", ctypes.c_int), ("out_sample_rate", ctypes.c_int), ("ampl_conv", ctypes.c_double),
+                ("l_i", ctypes.c_double), ("l_q", ctypes.c_double), ("deemphasis_val", ctypes.c_double),
+                ("downsampler_i", ctypes.POINTER(NrfDownsampler)), ("downsampler_q", ctypes.POINTER(NrfDownsampler)),
+                ("downsampler_audio", ctypes.POINTER(NrfDownsampler)), ("demodulated_samples", _dp),
+                ("demodulated_length", ctypes.c_int), ("audio_samples", _dp), ("audio_samples_length", ctypes.c_int)]
+
+
+class NrfDecoder(ctypes.Structure):
+    """nrf_decoder: the reference's members (this build appends a backend handle)."""
+    _fields_ = [("in_sample_rate", ctypes.c_int), ("out_sample_rate", ctypes.c_int), ("demodulate_type", ctypes.c_int),
+                ("demodulator", ctypes.c_void_p), ("freq_shifter", ctypes.POINTER(NrfFreqShifter)),
+                ("samples_i", _dp), ("samples_q", _dp), ("samples_length", ctypes.c_int), ("audio_samples", _dp),
+                ("audio_samples_length", ctypes.c_int)]
+
+
+def bind_demod(L):
+    """Attach the downsampler, demodulator, decoder and (where the library has them) player prototypes to a loaded
+    library (ours or a build of the reference)."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    dsp, rawp, fmp, decp = (ctypes.POINTER(NrfDownsampler), ctypes.POINTER(NrfRawDemodulator),
+                            ctypes.POINTER(NrfFmDemodulator), ctypes.POINTER(NrfDecoder))
+    L.nrf_downsampler_new.restype = dsp
+    L.nrf_downsampler_new.argtypes = [ci, ci, ci, ci]
+    L.nrf_downsampler_process.restype = None
+    L.nrf_downsampler_process.argtypes = [dsp, vp, ci]
+    L.nrf_downsampler_free.restype = None
+    L.nrf_downsampler_free.argtypes = [dsp]
+    L.nrf_raw_demodulator_new.restype = rawp
+    L.nrf_raw_demodulator_new.argtypes = [ci, ci]
+    L.nrf_raw_demodulator_process.restype = None
+    L.nrf_raw_demodulator_process.argtypes = [rawp, vp, vp, ci]
+    L.nrf_raw_demodulator_free.restype = None
+    L.nrf_raw_demodulator_free.argtypes = [rawp]
+    L.nrf_fm_demodulator_new.restype = fmp
+    L.nrf_fm_demodulator_new.argtypes = [ci, ci]
+    L.nrf_fm_demodulator_process.restype = None
+    L.nrf_fm_demodulator_process.argtypes = [fmp, vp, vp, ci]
+    L.nrf_fm_demodulator_free.restype = None
+    L.nrf_fm_demodulator_free.argtypes = [fmp]
+    L.nrf_decoder_new.restype = decp
+    L.nrf_decoder_new.argtypes = [ci, ci, ci, ci]
+    L.nrf_decoder_process.restype = None
+    L.nrf_decoder_process.argtypes = [decp, vp, ctypes.c_size_t]
+    L.nrf_decoder_free.restype = None
+    L.nrf_decoder_free.argtypes = [decp]
+    if hasattr(L, "nrf_player_pop_pcm"):       # this build's headless player (include/nrf.h)
+        L.nrf_player_new.restype = vp
+        L.nrf_player_new.argtypes = [vp, ci, ci]
+        L.nrf_player_set_freq_offset.restype = None
+        L.nrf_player_set_freq_offset.argtypes = [vp, ci]
+        L.nrf_player_set_gain.restype = None
+        L.nrf_player_set_gain.argtypes = [vp, ctypes.c_float]
+        L.nrf_player_free.restype = None
+        L.nrf_player_free.argtypes = [vp]
+        L.nrf_player_pop_pcm.restype = ci
+        L.nrf_player_pop_pcm.argtypes = [vp, vp, ci, ctypes.POINTER(ctypes.c_long)]
+    return L
+
+
 _LIB = None
 
 
@@ -194,6 +287,7 @@ def nrf_lib():
         L.nrf_iq_filter_free.restype = None
         L.nrf_iq_filter_free.argtypes = [vp]
         bind_iq_draw(L)
+        bind_demod(L)
         _LIB = L
     return _LIB
 

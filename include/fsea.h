@@ -54,6 +54,7 @@ typedef struct fsea_plan fsea_plan;
 typedef struct fsea_history fsea_history;
 typedef struct fsea_fir fsea_fir;
 typedef struct fsea_iq_draw fsea_iq_draw;
+typedef struct fsea_demod fsea_demod;
 
 /* Epilogue modes.  Output element type and row length are per mode. */
 enum {
@@ -380,6 +381,47 @@ int fsea_iq_lines_device(fsea_iq_draw *draw, const void *d_iq, int type, int fli
 int fsea_iq_points_host(fsea_iq_draw *draw, const void *iq, int type, int flip, size_t n_pairs, uint8_t *image);
 int fsea_iq_lines_host(fsea_iq_draw *draw, const void *iq, int type, int flip, size_t n_points, int size_multiplier,
                        uint8_t *image);
+
+/* The reference's audio chain (src/nrf.c:778-1094: nrf_downsampler, nrf_raw_demodulator, nrf_fm_demodulator,
+ * nrf_decoder) as a streaming decoder of n_channels channels over one input stream, each channel with its own frequency
+ * offset, phase and state.  f64 arithmetic on the device.  Per call on n input samples, channel ch:
+ *   x[k] = (c + i s) e^{i theta k} (I[k], Q[k]),  theta = 2 pi freq_offset / in_rate, the phase of sample k taken from the
+ *          exactly reduced cycle count (freq_offset k mod in_rate) / in_rate; u8 input: I = b[2k] / 128.0 - 0.995 (the
+ *          reference's decoder conversion; flip != 0: raw HackRF int8 bytes, b ^ 0x80 first), f64 input as is
+ *   RAW:   audio = the reference's downsampler (in_rate -> out_rate, cutoff out_rate / 2, 41 taps) on I
+ *   WBFM:  downsamplers (in_rate -> 336000, cutoff 60000, 51 taps) on I and Q, the reference's discriminator with the
+ *          previous stage-1 output carried across calls (0 after create and reset), a downsampler (336000 -> out_rate,
+ *          cutoff 10000, 41 taps), de-emphasis v += alpha (x - v), alpha = 1 / (1 + out_rate 50e-6), v carried
+ * A downsampler keeps the last L - 1 inputs across calls and computes output j of a call at x_ext[idx_j ..], idx_j the
+ * reference's accumulated floor(t), t += in / (double) out from 0 on every call; out_length = floor(n / rate_mul).  The
+ * index tables are built on the host by that accumulation and cached per call length.
+ * Channel ch of a K-channel object gives bit for bit what a 1-channel object with the same offset and phase gives.
+ * Errors: every form checks its arguments before any device work (FSEA_EINVAL: NULL object or buffer, unknown type,
+ * rates <= 0, n_channels outside [1, FSEA_DEMOD_MAX_CHANNELS], n_samples above FSEA_DEMOD_MAX_SAMPLES or giving more than
+ * FSEA_DEMOD_MAX_SAMPLES outputs of a stage, a channel out of range, a non-finite phase).  Create: FSEA_ENODEVICE without a
+ * GPU.  Destroy waits for the device. */
+enum { FSEA_DEMOD_RAW = 0, FSEA_DEMOD_WBFM = 1 };   /* = nrf_demodulate_type values */
+#define FSEA_DEMOD_MAX_CHANNELS 256
+#define FSEA_DEMOD_MAX_SAMPLES (1 << 24)
+
+int fsea_demod_create(fsea_demod **demod, int type, int in_rate, int out_rate, int n_channels, int device);
+int fsea_demod_destroy(fsea_demod *demod);
+/* Tails, carried stage-1 outputs and de-emphasis values to 0, every phase to (1, 0); offsets stay.  Waits for the device. */
+int fsea_demod_reset(fsea_demod *demod);
+/* The offset and phase (cosine, sine) channel ch starts its next call with; get returns them, after a call advanced by
+ * theta n with the same reduction (host arithmetic). */
+int fsea_demod_set_channel(fsea_demod *demod, int ch, int freq_offset, double cosine, double sine);
+int fsea_demod_get_channel(const fsea_demod *demod, int ch, int *freq_offset, double *cosine, double *sine);
+/* Audio samples per channel of a call on n_samples (0 for a NULL object or an n_samples the object rejects). */
+size_t fsea_demod_out_length(const fsea_demod *demod, size_t n_samples);
+/* Device form: d_iq holds 2 * n_samples bytes (2-byte aligned), d_audio receives n_channels rows of out_length f64,
+ * row-major (8-byte aligned).  Asynchronous on `stream`; successive calls on one stream continue one signal, across
+ * streams the caller orders them. */
+int fsea_demod_u8_device(fsea_demod *demod, const void *d_iq, size_t n_samples, int flip, double *d_audio, void *stream);
+/* Host forms; return when `audio` is complete.  Staged through pinned memory on the object's own stream; calls on one
+ * object from several threads are serialised.  The f64 form takes separate I and Q arrays and converts nothing. */
+int fsea_demod_u8_host(fsea_demod *demod, const uint8_t *iq, size_t n_samples, int flip, double *audio);
+int fsea_demod_f64_host(fsea_demod *demod, const double *i, const double *q, size_t n_samples, double *audio);
 
 const char *fsea_last_error_string(void);
 

@@ -19,6 +19,10 @@
  *   src/nrf.h:100-101, 122-124, 209-218  the IQ drawing functions, whose
  *                      per-sample loops run on the GPU (fsea_iq_*, include/fsea.h),
  *                      and the signal detector (host, double)
+ *   src/nrf.h:177-190, 220-301  the downsampler (host, double), the RAW and
+ *                      WBFM demodulators and the decoder, whose chains run on
+ *                      the GPU (fsea_demod_*, include/fsea.h), and the player
+ *                      without OpenAL (a PCM queue and an optional s16le file)
  * Differences, all invisible to callers: <fftw3.h> is gone, the FFTW-typed
  * members of nrf_fft (touched by nobody outside src/nrf.c) became an opaque
  * backend handle, the history is a ring instead of an 8 MiB memmove per row,
@@ -110,6 +114,10 @@ struct nrf_device {
     int dummy_block_index;
 
     uint8_t samples[NRF_BUFFER_SIZE_BYTES]; /* current block, offset binary */
+
+    /* this build: held while the replay thread runs the decode handler and while nrf_device_set_decode_handler swaps it,
+     * so that once set_decode_handler returns no call of the previous handler is still running */
+    pthread_mutex_t decode_mutex;
 };
 
 /* Replays `data_file` (raw int8 IQ as written by c/rfcap.c) in 262144-byte
@@ -267,5 +275,133 @@ typedef struct {
 nrf_signal_detector *nrf_signal_detector_new();
 void nrf_signal_detector_process(nrf_signal_detector *detector, nut_buffer *buffer);
 void nrf_signal_detector_free(nrf_signal_detector *detector);
+
+/* ---- Downsampler (src/nrf.h:177-190, src/nrf.c:778-811): host, double, the reference's loop bit for bit ---- */
+
+/* process: the filter (nrf_fir_filter_new(in_rate, filter_freq, kernel_length)) is loaded with the call's samples;
+ * out_length = floor(length / rate_mul), rate_mul = in_rate / (double) out_rate, and output i is
+ * nrf_fir_filter_get(filter, floor(t)) with t accumulated (t += rate_mul) from 0 on every call. */
+typedef struct {
+    int in_rate;
+    int out_rate;
+    nrf_fir_filter *filter;
+    double rate_mul;
+    int out_length;
+    double *out_samples;
+} nrf_downsampler;
+
+nrf_downsampler *nrf_downsampler_new(int in_rate, int out_rate, int filter_freq, int kernel_length);
+void nrf_downsampler_process(nrf_downsampler *d, double *samples, int length);
+void nrf_downsampler_free(nrf_downsampler *d);
+
+/* ---- Demodulators and decoder (src/nrf.h:220-276, src/nrf.c:904-1094) ---- */
+
+/* The chains run on the GPU in f64 (fsea_demod_*, include/fsea.h; one 1-channel object per demodulator or decoder):
+ *   RAW:  the downsampler (in, out, out / 2, 41) on I; Q is not used
+ *   WBFM: downsamplers (in, 336000, 60000, 51) on I and Q, the reference's discriminator against the previous stage-1
+ *         output (carried, 0 at first), the downsampler (336000, out, 10000, 41), de-emphasis val += alpha (x - val),
+ *         alpha = 1 / (1 + out * 50 / 1e6); ampl_conv = out / (2 pi 75000)
+ * The reference's members keep their order and types; the backend handle is appended.  Differences, all documented in
+ * the intermediate arrays are not kept current (the internal downsamplers are created for their
+ * configuration but never run: out_length 0, out_samples NULL; demodulated_samples NULL, demodulated_length 0);
+ * l_i, l_q and deemphasis_val live on the device (the members stay 0); a backend failure (no GPU) prints and exits. */
+typedef struct {
+    int in_sample_rate;
+    int out_sample_rate;
+    nrf_downsampler *downsampler_audio;
+    double *audio_samples;
+    int audio_samples_length;
+    void *backend; /* fsea_demod* (libfsea_hip.so); NULL inside a decoder, which owns its own */
+} nrf_raw_demodulator;
+
+nrf_raw_demodulator *nrf_raw_demodulator_new(int in_sample_rate, int out_sample_rate);
+void nrf_raw_demodulator_process(nrf_raw_demodulator *demodulator, double *samples_i, double *samples_q, int length);
+void nrf_raw_demodulator_free(nrf_raw_demodulator *demodulator);
+
+typedef struct {
+    int in_sample_rate;
+    int out_sample_rate;
+    double ampl_conv;
+    double l_i;
+    double l_q;
+    double deemphasis_val;
+    nrf_downsampler *downsampler_i;
+    nrf_downsampler *downsampler_q;
+    nrf_downsampler *downsampler_audio;
+    double *demodulated_samples;
+    int demodulated_length;
+    double *audio_samples;
+    int audio_samples_length;
+    void *backend; /* fsea_demod* (libfsea_hip.so); NULL inside a decoder, which owns its own */
+} nrf_fm_demodulator;
+
+nrf_fm_demodulator *nrf_fm_demodulator_new(int in_sample_rate, int out_sample_rate);
+void nrf_fm_demodulator_process(nrf_fm_demodulator *demodulator, double *samples_i, double *samples_q, int length);
+void nrf_fm_demodulator_free(nrf_fm_demodulator *demodulator);
+
+typedef enum {
+    NRF_DEMODULATE_RAW = 0,
+    NRF_DEMODULATE_WBFM
+} nrf_demodulate_type;
+
+/* process: offset-binary bytes (device->samples) converted as buffer[2i] / 128.0 - 0.995, rotated by the frequency
+ * shifter's phase, then RAW or WBFM.  Each call reads freq_shifter->freq_offset / cosine / sine first (callers and the
+ * player write them directly) and writes the advanced phase back; the phase of sample k is taken from the exactly reduced
+ * cycle count (freq_offset k mod in_sample_rate) / in_sample_rate instead of the reference's running product.
+ * audio_samples aliases the demodulator's buffer.  An unknown demodulate_type has no demodulator and leaves
+ * audio_samples NULL (the phase still advances).  samples_i / samples_q stay NULL and samples_length 0: nothing is
+ * allocated per call (the reference reallocates both on every call). */
+typedef struct {
+    int in_sample_rate;
+    int out_sample_rate;
+    nrf_demodulate_type demodulate_type;
+    void *demodulator;
+    nrf_freq_shifter *freq_shifter;
+    double *samples_i;
+    double *samples_q;
+    int samples_length;
+    double *audio_samples;
+    int audio_samples_length;
+    void *backend; /* fsea_demod* (libfsea_hip.so) */
+} nrf_decoder;
+
+nrf_decoder *nrf_decoder_new(nrf_demodulate_type demodulate_type, int in_sample_rate, int out_sample_rate, int freq_offset);
+void nrf_decoder_process(nrf_decoder *decoder, uint8_t *buffer, size_t length);
+/* ADDITION: defined but not declared by the reference (src/nrf.c:1086). */
+void nrf_decoder_free(nrf_decoder *decoder);
+
+/* ---- Player (src/nrf.h:278-301, src/nrf.c:1096-1280), without an audio device ---- */
+
+/* The decode handler (on the device's replay thread) copies device->samples under data_mutex, decodes
+ * NRF_SAMPLES_LENGTH pairs and converts to (int16_t)(audio * 32000), the reference's PCM.  Each chunk is queued in a
+ * bounded queue of NRF_PLAYER_QUEUE chunks (the oldest dropped when full) and, if NRF_PLAYER_PCM=<path> was set at
+ * nrf_player_new, appended to that file as s16le mono at 48 kHz.  set_gain clamps to [0, 1] and stores the gain; it does
+ * not scale the PCM (the reference hands unscaled PCM to OpenAL).  set_freq_offset applies from the next block.  free
+ * unregisters the handler, waits for a decode in flight, and does not free the device. */
+#define NRF_PLAYER_QUEUE 64
+
+typedef struct {
+    nrf_demodulate_type demodulate_type;
+    nrf_device *device;
+    nrf_decoder *decoder;
+    float gain;              /* set_gain's clamped value */
+    pthread_mutex_t mutex;   /* the queue, sequence and shutting_down */
+    int shutting_down;
+    int16_t *queue[NRF_PLAYER_QUEUE];
+    int queue_length[NRF_PLAYER_QUEUE];
+    long queue_sequence[NRF_PLAYER_QUEUE];
+    int queue_head;          /* oldest chunk */
+    int queue_size;
+    long next_sequence;      /* decode index since nrf_player_new */
+    void *pcm_file;          /* FILE* of NRF_PLAYER_PCM, or NULL */
+} nrf_player;
+
+nrf_player *nrf_player_new(nrf_device *device, nrf_demodulate_type demodulate_type, int freq_offset);
+void nrf_player_set_freq_offset(nrf_player *player, int freq_offset);
+void nrf_player_set_gain(nrf_player *player, float gain);
+void nrf_player_free(nrf_player *player);
+/* ADDITION: moves the oldest queued chunk's samples (at most `capacity`) to `out` and returns its sample count, 0 when
+ * the queue is empty; *sequence (if not NULL) receives the chunk's decode index, so dropped chunks show as gaps. */
+int nrf_player_pop_pcm(nrf_player *player, int16_t *out, int capacity, long *sequence);
 
 #endif /* NRF_H */
