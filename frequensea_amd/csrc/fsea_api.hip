@@ -61,6 +61,60 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+int grow_device(void **ptr, size_t *cap, size_t need) {
+    if (*cap >= need) return FSEA_OK;
+    if (*ptr) FSEA_HIP(hipFree(*ptr));
+    *ptr = nullptr;
+    *cap = 0;
+    const size_t want = need + need / 4 + 4096;
+    FSEA_HIP(hipMalloc(ptr, want));
+    *cap = want;
+    return FSEA_OK;
+}
+
+int grow_pinned(void **ptr, size_t *cap, size_t need) {
+    if (*cap >= need) return FSEA_OK;
+    if (*ptr) FSEA_HIP(hipHostFree(*ptr));
+    *ptr = nullptr;
+    *cap = 0;
+    const size_t want = need + need / 4 + 4096;
+    FSEA_HIP(hipHostMalloc(ptr, want, hipHostMallocDefault));
+    *cap = want;
+    return FSEA_OK;
+}
+
+int check_device(int device) {
+    int count = 0;
+    hipError_t ce = hipGetDeviceCount(&count);
+    if (ce != hipSuccess || count <= 0) {
+        return fail(FSEA_ENODEVICE, "no HIP device available (%s); libfsea_hip has no CPU fallback", hipGetErrorString(ce));
+    }
+    if (device < 0 || device >= count) return fail(FSEA_EINVAL, "device %d out of range [0,%d)", device, count);
+    return FSEA_OK;
+}
+
+void HostStaging::release() {
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (h_in) (void)hipHostFree(h_in);
+    if (h_out) (void)hipHostFree(h_out);
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
+int HostStaging::reserve(size_t in_bytes, size_t out_bytes) {
+    // a buffer is freed only once the stream is idle: in the normal path it already is, but a call that returned an error
+    // may have left a copy queued
+    if ((h_in && h_in_bytes < in_bytes) || (h_out && h_out_bytes < out_bytes) || (d_in && d_in_bytes < in_bytes) ||
+        (d_out && d_out_bytes < out_bytes)) {
+        FSEA_HIP(hipStreamSynchronize(stream));
+    }
+    int rc = grow_pinned(&h_in, &h_in_bytes, in_bytes);
+    if (!rc) rc = grow_pinned(&h_out, &h_out_bytes, out_bytes);
+    if (!rc) rc = grow_device(&d_in, &d_in_bytes, in_bytes);
+    if (!rc) rc = grow_device(&d_out, &d_out_bytes, out_bytes);
+    return rc;
+}
+
 }  // namespace fsea_detail
 
 namespace {
@@ -258,19 +312,6 @@ std::string pow2_kernel_name(const fsea_plan *p) {
     if (k < 0) return "";
     const int half = half_overlap_kind(p, k, 2, false);
     return p->entry->name[half >= 0 ? half : k];
-}
-
-int ensure(void **ptr, size_t *cap, size_t need) {
-    if (*cap >= need) return FSEA_OK;
-    if (*ptr) {
-        FSEA_HIP(hipFree(*ptr));
-        *ptr = nullptr;
-        *cap = 0;
-    }
-    size_t want = need + need / 4 + 4096;
-    FSEA_HIP(hipMalloc(ptr, want));
-    *cap = want;
-    return FSEA_OK;
 }
 
 constexpr size_t FSEA_ZERO_COPY_MAX = 256 * 1024;  // in + out bytes up to which the staging is mapped host memory
@@ -540,13 +581,8 @@ static int create_plan(fsea_plan **out, int fft_size, int hop, int mode, int dev
         return fail(FSEA_EINVAL, "hop must be a positive multiple of 8 (any positive hop for the sizes without a kernel of their "
                                  "own); got %d", hop);
     }
-    int count = 0;
-    hipError_t ce = hipGetDeviceCount(&count);
-    if (ce != hipSuccess || count <= 0) {
-        return fail(FSEA_ENODEVICE, "no HIP device available (%s); libfsea_hip has no CPU fallback",
-                    hipGetErrorString(ce));
-    }
-    if (device < 0 || device >= count) return fail(FSEA_EINVAL, "device %d out of range [0,%d)", device, count);
+    int rc = check_device(device);
+    if (rc) return rc;
     FSEA_ON_DEVICE(device);
     hipDeviceProp_t prop;
     FSEA_HIP(hipGetDeviceProperties(&prop, device));
@@ -607,12 +643,12 @@ static int create_plan(fsea_plan **out, int fft_size, int hop, int mode, int dev
         if (e->fn[k]) he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&p->occ[k], e->fn[k], e->wg, 0);
     }
     if (he != hipSuccess) {
-        int rc = fail(FSEA_EHIP, "plan setup failed: %s", hipGetErrorString(he));
+        rc = fail(FSEA_EHIP, "plan setup failed: %s", hipGetErrorString(he));
         fsea_plan_destroy(p);
         return rc;
     }
     if (blu_m) {
-        int rc = create_plan(&p->blu_inner, blu_m, blu_m, FSEA_MODE_COMPLEX_F32, device, "");
+        rc = create_plan(&p->blu_inner, blu_m, blu_m, FSEA_MODE_COMPLEX_F32, device, "");
         if (rc == FSEA_OK) rc = blu_setup(p);
         if (rc != FSEA_OK) {
             fsea_plan_destroy(p);
@@ -622,7 +658,7 @@ static int create_plan(fsea_plan **out, int fft_size, int hop, int mode, int dev
                          (p->blu_inner->fs_n1 ? p->blu_inner->kernel_name : std::string(p->blu_inner->entry->name[fsea::K_F32])) + " x2)";
     }
     if (fs_n1) {
-        int rc = create_plan(&p->fs_inner1, fs_n1, fs_n1, FSEA_MODE_COMPLEX_F32, device, "");
+        rc = create_plan(&p->fs_inner1, fs_n1, fs_n1, FSEA_MODE_COMPLEX_F32, device, "");
         if (rc == FSEA_OK) rc = create_plan(&p->fs_inner2, fs_n2, fs_n2, FSEA_MODE_COMPLEX_F32, device, "");
         if (rc == FSEA_OK) rc = fs_setup(p);
         if (rc != FSEA_OK) {
@@ -940,13 +976,13 @@ int exec_host_pipelined(fsea_plan *p, int in_kind, const void *in, size_t bytes_
     const size_t n_samples = (n_frames - 1) * hop + n;
     const size_t in_bytes = n_samples * bytes_per_sample, out_bytes = n_frames * row_bytes;
     const bool f64 = bytes_per_sample == 16;
-    int rc = ensure(f64 ? &p->d_aux : &p->d_in, f64 ? &p->d_aux_bytes : &p->d_in_bytes, in_bytes);
+    int rc = grow_device(f64 ? &p->d_aux : &p->d_in, f64 ? &p->d_aux_bytes : &p->d_in_bytes, in_bytes);
     if (rc) return rc;
     if (f64) {
-        rc = ensure(&p->d_in, &p->d_in_bytes, n_samples * 2 * sizeof(float));
+        rc = grow_device(&p->d_in, &p->d_in_bytes, n_samples * 2 * sizeof(float));
         if (rc) return rc;
     }
-    rc = ensure(&p->d_out, &p->d_out_bytes, out_bytes);
+    rc = grow_device(&p->d_out, &p->d_out_bytes, out_bytes);
     if (rc) return rc;
     // chunks of about 24 MiB (in + out): long enough for the link's full rate, short enough that the first copy-in and
     // the last copy-out (the two pieces nothing overlaps) are a small part of the call
@@ -1229,7 +1265,7 @@ int fsea_mean_magnitude_u8_device(fsea_plan *p, const void *d_iq, size_t n_frame
     FSEA_ON_DEVICE(p->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t count = n_frames * (size_t)p->n;
-    int rc = ensure(&p->d_aux, &p->d_aux_bytes, count * sizeof(float));
+    int rc = grow_device(&p->d_aux, &p->d_aux_bytes, count * sizeof(float));
     if (rc) return rc;
     rc = launch(p, fsea::IN_U8, d_iq, n_frames, flip, FSEA_MODE_MAG_NODC_F32, p->d_aux, s);
     if (rc) return rc;

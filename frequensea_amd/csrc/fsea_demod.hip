@@ -362,38 +362,13 @@ struct fsea_demod {
     int ring = 0;
     std::vector<Table> tables;
     unsigned long long use_seq = 0;
-    hipStream_t stream = nullptr;               // the host-buffer forms
     std::mutex mu;
-    void *d_y1 = nullptr, *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
-    size_t d_y1_bytes = 0, d_in_bytes = 0, d_out_bytes = 0, h_in_bytes = 0, h_out_bytes = 0;
+    void *d_y1 = nullptr;
+    size_t d_y1_bytes = 0;
+    fsea_detail::HostStaging staging;           // the host-buffer forms
 };
 
 namespace {
-
-int grow_device(void **ptr, size_t *cap, size_t need) {
-    if (*cap >= need) return FSEA_OK;
-    if (*ptr) {
-        FSEA_HIP(hipDeviceSynchronize());   // a launch on another stream may still use the old buffer
-        FSEA_HIP(hipFree(*ptr));
-    }
-    *ptr = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    FSEA_HIP(hipMalloc(ptr, want));
-    *cap = want;
-    return FSEA_OK;
-}
-
-int grow_pinned(void **ptr, size_t *cap, size_t need) {
-    if (*cap >= need) return FSEA_OK;
-    if (*ptr) FSEA_HIP(hipHostFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    FSEA_HIP(hipHostMalloc(ptr, want, hipHostMallocDefault));
-    *cap = want;
-    return FSEA_OK;
-}
 
 // the reference's out_length = floor(length / rate_mul)
 long long stage_length(long long n, double r) { return (long long)floor((double)n / r); }
@@ -494,7 +469,11 @@ int demod_launch(fsea_demod *d, int kind, const void *in0, const void *in1, size
     int rc = tables_for(d, n, &t);
     if (rc) return rc;
     if (d->type == FSEA_DEMOD_WBFM) {
-        rc = grow_device(&d->d_y1, &d->d_y1_bytes, (size_t)d->K * (size_t)(t->n1 > 0 ? t->n1 : 1) * sizeof(double2));
+        const size_t y1_bytes = (size_t)d->K * (size_t)(t->n1 > 0 ? t->n1 : 1) * sizeof(double2);
+        if (d->d_y1 && d->d_y1_bytes < y1_bytes) {
+            FSEA_HIP(hipDeviceSynchronize());   // a launch on another stream may still use the old buffer
+        }
+        rc = fsea_detail::grow_device(&d->d_y1, &d->d_y1_bytes, y1_bytes);
         if (rc) return rc;
     }
     const int slot = d->ring;
@@ -553,7 +532,8 @@ int check_call(const fsea_demod *d, size_t n) {
     return FSEA_OK;
 }
 
-// the host-buffer forms: pinned staging, copy in, the launches, copy out, on the object's own stream
+// the host-buffer forms: the launches through the object's staging (fsea_detail::HostStaging); f64 input is staged as
+// the n I values, then the n Q values
 int demod_host(fsea_demod *d, int kind, const void *in0, const void *in1, size_t n, int flip, double *audio) {
     int rc = check_call(d, n);
     if (rc) return rc;
@@ -563,27 +543,19 @@ int demod_host(fsea_demod *d, int kind, const void *in0, const void *in1, size_t
     FSEA_ON_DEVICE(d->device);
     const size_t in_bytes = n * (kind == DM_IN_U8 ? 2 : 16);
     const size_t out_bytes = (size_t)d->K * fsea_demod_out_length(d, n) * sizeof(double);
-    rc = grow_pinned(&d->h_in, &d->h_in_bytes, in_bytes);
-    if (!rc) rc = grow_pinned(&d->h_out, &d->h_out_bytes, out_bytes);
-    if (!rc) rc = grow_device(&d->d_in, &d->d_in_bytes, in_bytes);
-    if (!rc) rc = grow_device(&d->d_out, &d->d_out_bytes, out_bytes);
-    if (rc) return rc;
-    char *hin = static_cast<char *>(d->h_in);
-    if (kind == DM_IN_U8) {
-        std::memcpy(hin, in0, in_bytes);
-    } else {
-        std::memcpy(hin, in0, n * 8);
-        std::memcpy(hin + n * 8, in1, n * 8);
-    }
-    FSEA_HIP(hipMemcpyAsync(d->d_in, d->h_in, in_bytes, hipMemcpyHostToDevice, d->stream));
-    const char *din = static_cast<const char *>(d->d_in);
-    rc = demod_launch(d, kind, din, kind == DM_IN_U8 ? nullptr : din + n * 8, n, flip, static_cast<double *>(d->d_out),
-                      d->stream);
-    if (rc) return rc;
-    if (out_bytes) FSEA_HIP(hipMemcpyAsync(d->h_out, d->d_out, out_bytes, hipMemcpyDeviceToHost, d->stream));
-    FSEA_HIP(hipStreamSynchronize(d->stream));
-    std::memcpy(audio, d->h_out, out_bytes);
-    return FSEA_OK;
+    auto fill = [&](void *h_in) {
+        if (kind == DM_IN_U8) {
+            std::memcpy(h_in, in0, in_bytes);
+        } else {
+            std::memcpy(h_in, in0, n * 8);
+            std::memcpy(static_cast<char *>(h_in) + n * 8, in1, n * 8);
+        }
+    };
+    auto launch = [&](void *d_in, void *d_out, hipStream_t s) {
+        const char *din = static_cast<const char *>(d_in);
+        return demod_launch(d, kind, din, kind == DM_IN_U8 ? nullptr : din + n * 8, n, flip, static_cast<double *>(d_out), s);
+    };
+    return d->staging.run(in_bytes, out_bytes, audio, fill, launch);
 }
 
 int zero_state(fsea_demod *d) {
@@ -602,7 +574,7 @@ int zero_state(fsea_demod *d) {
 
 void release(fsea_demod *d) {
     void *dev[] = {d->d_taps1, d->d_taps3, d->d_tail1[0], d->d_tail1[1], d->d_tail3[0], d->d_tail3[1], d->d_l[0],
-                   d->d_l[1], d->d_v[0], d->d_v[1], d->d_y1, d->d_in, d->d_out};
+                   d->d_l[1], d->d_v[0], d->d_v[1], d->d_y1};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (int i = 0; i < DM_RING; ++i) {
@@ -611,9 +583,7 @@ void release(fsea_demod *d) {
         if (d->ev[i]) (void)hipEventDestroy(d->ev[i]);
     }
     for (Table &t : d->tables) free_table(t);
-    if (d->h_in) (void)hipHostFree(d->h_in);
-    if (d->h_out) (void)hipHostFree(d->h_out);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
+    d->staging.release();
     delete d;
 }
 
@@ -637,12 +607,8 @@ int fsea_demod_create(fsea_demod **out, int type, int in_rate, int out_rate, int
     if (n_channels < 1 || n_channels > FSEA_DEMOD_MAX_CHANNELS) {
         return fail(FSEA_EINVAL, "n_channels must be in [1, %d], got %d", FSEA_DEMOD_MAX_CHANNELS, n_channels);
     }
-    int count = 0;
-    hipError_t ce = hipGetDeviceCount(&count);
-    if (ce != hipSuccess || count <= 0) {
-        return fail(FSEA_ENODEVICE, "no HIP device available (%s); libfsea_hip has no CPU fallback", hipGetErrorString(ce));
-    }
-    if (device < 0 || device >= count) return fail(FSEA_EINVAL, "device %d out of range [0,%d)", device, count);
+    int rc = fsea_detail::check_device(device);
+    if (rc) return rc;
     FSEA_ON_DEVICE(device);
     fsea_demod *d = new (std::nothrow) fsea_demod();
     if (!d) return fail(FSEA_ENOMEM, "out of host memory");
@@ -679,12 +645,12 @@ int fsea_demod_create(fsea_demod **out, int type, int in_rate, int out_rate, int
         if (e == hipSuccess) e = hipHostMalloc(&d->h_par[i], (size_t)n_channels * sizeof(ChanParam), hipHostMallocDefault);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev[i], hipEventDisableTiming);
     }
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = d->staging.create();
     if (e != hipSuccess) {
         release(d);
         return fail(FSEA_EHIP, "fsea_demod_create: %s", hipGetErrorString(e));
     }
-    int rc = zero_state(d);
+    rc = zero_state(d);
     if (rc) {
         release(d);
         return rc;

@@ -206,35 +206,11 @@ struct fsea_fir {
     float *d_taps = nullptr;       // FIR_TAPS_ALLOC floats, zeros past n_taps
     cf *d_tail[2] = {nullptr, nullptr};  // FSEA_FIR_MAX_TAPS samples each; d_tail[cur] is the current tail
     int cur = 0;
-    hipStream_t stream = nullptr;  // the host-buffer forms
     std::mutex mu;
-    void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
-    size_t d_in_bytes = 0, d_out_bytes = 0, h_in_bytes = 0, h_out_bytes = 0;
+    fsea_detail::HostStaging staging;  // the host-buffer forms
 };
 
 namespace {
-
-int grow_device(void **ptr, size_t *cap, size_t need) {
-    if (*cap >= need) return FSEA_OK;
-    if (*ptr) FSEA_HIP(hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    FSEA_HIP(hipMalloc(ptr, want));
-    *cap = want;
-    return FSEA_OK;
-}
-
-int grow_pinned(void **ptr, size_t *cap, size_t need) {
-    if (*cap >= need) return FSEA_OK;
-    if (*ptr) FSEA_HIP(hipHostFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    FSEA_HIP(hipHostMalloc(ptr, want, hipHostMallocDefault));
-    *cap = want;
-    return FSEA_OK;
-}
 
 // one launch; the caller holds f->mu and is on f's device
 int fir_launch(fsea_fir *f, int kind, const void *d_in, size_t n, int flip, void *d_out, hipStream_t s) {
@@ -255,7 +231,7 @@ int fir_launch(fsea_fir *f, int kind, const void *d_in, size_t n, int flip, void
     return FSEA_OK;
 }
 
-// the host-buffer forms: pinned staging, copy in, one launch, copy out, on the object's own stream
+// the host-buffer forms: one launch through the object's staging (fsea_detail::HostStaging)
 int fir_host(fsea_fir *f, int kind, const void *in, size_t n, int flip, float *out) {
     if (!f) return fail(FSEA_EINVAL, "fir is NULL");
     if (n == 0) return FSEA_OK;
@@ -264,31 +240,16 @@ int fir_host(fsea_fir *f, int kind, const void *in, size_t n, int flip, float *o
     std::lock_guard<std::mutex> lock(f->mu);
     FSEA_ON_DEVICE(f->device);
     const size_t in_bytes = n * (kind == FIR_IN_U8 ? 2 : 16);
-    const size_t out_bytes = n * sizeof(cf);
-    int rc = grow_pinned(&f->h_in, &f->h_in_bytes, in_bytes);
-    if (!rc) rc = grow_pinned(&f->h_out, &f->h_out_bytes, out_bytes);
-    if (!rc) rc = grow_device(&f->d_in, &f->d_in_bytes, in_bytes);
-    if (!rc) rc = grow_device(&f->d_out, &f->d_out_bytes, out_bytes);
-    if (rc) return rc;
-    std::memcpy(f->h_in, in, in_bytes);
-    FSEA_HIP(hipMemcpyAsync(f->d_in, f->h_in, in_bytes, hipMemcpyHostToDevice, f->stream));
-    rc = fir_launch(f, kind, f->d_in, n, flip, f->d_out, f->stream);
-    if (rc) return rc;
-    FSEA_HIP(hipMemcpyAsync(f->h_out, f->d_out, out_bytes, hipMemcpyDeviceToHost, f->stream));
-    FSEA_HIP(hipStreamSynchronize(f->stream));
-    std::memcpy(out, f->h_out, out_bytes);
-    return FSEA_OK;
+    return f->staging.run(
+        in_bytes, n * sizeof(cf), out, [&](void *h_in) { std::memcpy(h_in, in, in_bytes); },
+        [&](void *d_in, void *d_out, hipStream_t s) { return fir_launch(f, kind, d_in, n, flip, d_out, s); });
 }
 
 void release(fsea_fir *f) {
     if (f->d_taps) (void)hipFree(f->d_taps);
     for (int i = 0; i < 2; ++i)
         if (f->d_tail[i]) (void)hipFree(f->d_tail[i]);
-    if (f->d_in) (void)hipFree(f->d_in);
-    if (f->d_out) (void)hipFree(f->d_out);
-    if (f->h_in) (void)hipHostFree(f->h_in);
-    if (f->h_out) (void)hipHostFree(f->h_out);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
+    f->staging.release();
     delete f;
 }
 
@@ -338,12 +299,8 @@ int fsea_fir_create(fsea_fir **out, const double *taps, int n_taps, int device) 
     for (int k = 0; k < n_taps; ++k) {
         if (!std::isfinite(taps[k])) return fail(FSEA_EINVAL, "tap %d is not finite", k);
     }
-    int count = 0;
-    hipError_t ce = hipGetDeviceCount(&count);
-    if (ce != hipSuccess || count <= 0) {
-        return fail(FSEA_ENODEVICE, "no HIP device available (%s); libfsea_hip has no CPU fallback", hipGetErrorString(ce));
-    }
-    if (device < 0 || device >= count) return fail(FSEA_EINVAL, "device %d out of range [0,%d)", device, count);
+    int rc = fsea_detail::check_device(device);
+    if (rc) return rc;
     FSEA_ON_DEVICE(device);
     fsea_fir *f = new (std::nothrow) fsea_fir();
     if (!f) return fail(FSEA_ENOMEM, "out of host memory");
@@ -355,7 +312,7 @@ int fsea_fir_create(fsea_fir **out, const double *taps, int n_taps, int device) 
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc(&f->d_tail[i], FSEA_FIR_MAX_TAPS * sizeof(cf));
     if (e == hipSuccess) e = hipMemcpy(f->d_taps, tf, sizeof(tf), hipMemcpyHostToDevice);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMemset(f->d_tail[i], 0, FSEA_FIR_MAX_TAPS * sizeof(cf));
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = f->staging.create();
     if (e != hipSuccess) {
         release(f);
         return fail(FSEA_EHIP, "fsea_fir_create: %s", hipGetErrorString(e));

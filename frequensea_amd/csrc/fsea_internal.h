@@ -1,5 +1,6 @@
 // fsea_internal.h -- what the translation units of libfsea_hip.so share behind the C ABI (include/fsea.h): the plan
-// object, error plumbing, and the launch dispatcher.  fsea_api.hip: plans, the power-of-two launches, every entry point;
+// object, error plumbing, the launch dispatcher, and the host scaffold of the FIR, IQ-draw and demod objects (device check,
+// growable buffers, host-form staging).  fsea_api.hip: plans, the power-of-two launches, every entry point;
 // fsea_anysize.hip: the transform sizes without a kernel of their own (Bluestein's algorithm, four-step decomposition).
 #pragma once
 
@@ -7,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <mutex>
 #include <string>
 
@@ -59,6 +61,45 @@ struct DeviceGuard {
 struct TileLayout {
     uint32_t rows = 0, pitch_row = 0, pitch_tile = 0;
     size_t span = 0;
+};
+
+// At least `need` bytes in *ptr (device memory, or pinned host memory), reallocated with headroom when *cap is short.  The
+// old buffer is freed without any wait: a caller whose buffer work may still use waits for that work first.
+int grow_device(void **ptr, size_t *cap, size_t need);
+int grow_pinned(void **ptr, size_t *cap, size_t need);
+
+// FSEA_OK, FSEA_ENODEVICE when HIP has no device at all, FSEA_EINVAL when `device` is not one of them
+int check_device(int device);
+
+// The host-buffer forms of an object (FIR, IQ draw, demod): its own non-blocking stream and pinned + device staging, grown
+// on demand.  Only those forms use the staging, on that stream, under the object's mutex.
+struct HostStaging {
+    hipStream_t stream = nullptr;
+    void *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
+    size_t h_in_bytes = 0, h_out_bytes = 0, d_in_bytes = 0, d_out_bytes = 0;
+
+    hipError_t create() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
+    void release();
+    int reserve(size_t in_bytes, size_t out_bytes);
+
+    // One host-form call: fill(h_in) writes the in_bytes of input into pinned memory, copy in, launch(d_in, d_out, stream)
+    // queues the object's work, copy out, wait, out_bytes to `out`.  Zero-byte copies are skipped.  The caller holds the
+    // object's mutex and is on its device.
+    template <class Fill, class Launch>
+    int run(size_t in_bytes, size_t out_bytes, void *out, Fill &&fill, Launch &&launch) {
+        int rc = reserve(in_bytes, out_bytes);
+        if (rc) return rc;
+        if (in_bytes) {
+            fill(h_in);
+            FSEA_HIP(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, stream));
+        }
+        rc = launch(d_in, d_out, stream);
+        if (rc) return rc;
+        if (out_bytes) FSEA_HIP(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+        FSEA_HIP(hipStreamSynchronize(stream));
+        if (out_bytes) std::memcpy(out, h_out, out_bytes);
+        return FSEA_OK;
+    }
 };
 
 

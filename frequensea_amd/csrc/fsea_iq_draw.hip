@@ -258,39 +258,16 @@ extern "C" __global__ __launch_bounds__(CLAMP_WG) void fsea_iq_clamp(const uint4
 
 struct fsea_iq_draw {
     int device = 0;
-    hipStream_t stream = nullptr;  // the host-buffer forms
     hipEvent_t counts_free = nullptr;  // recorded after the last launch that used d_counts
     std::mutex mu;
     uint32_t *d_counts = nullptr;
-    void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
-    size_t counts_bytes = 0, d_in_bytes = 0, d_out_bytes = 0, h_in_bytes = 0, h_out_bytes = 0;
+    size_t counts_bytes = 0;
+    fsea_detail::HostStaging staging;  // the host-buffer forms
 };
 
 namespace {
 
 size_t pair_bytes(int type) { return type == FSEA_IQ_U8 ? 2 : type == FSEA_IQ_F32 ? 8 : 16; }
-
-int grow_device(void **ptr, size_t *cap, size_t need) {
-    if (*cap >= need) return FSEA_OK;
-    if (*ptr) FSEA_HIP(hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    FSEA_HIP(hipMalloc(ptr, want));
-    *cap = want;
-    return FSEA_OK;
-}
-
-int grow_pinned(void **ptr, size_t *cap, size_t need) {
-    if (*cap >= need) return FSEA_OK;
-    if (*ptr) FSEA_HIP(hipHostFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    FSEA_HIP(hipHostMalloc(ptr, want, hipHostMallocDefault));
-    *cap = want;
-    return FSEA_OK;
-}
 
 int check_common(const fsea_iq_draw *d, int type, size_t n, int n_frames) {
     if (!d) return fail(FSEA_EINVAL, "iq_draw is NULL");
@@ -347,7 +324,7 @@ int lines_launch(fsea_iq_draw *d, const void *d_iq, int type, int flip, size_t n
     const size_t chunk = std::min<size_t>((size_t)n_frames, std::max<size_t>(1, LN_CHUNK_BYTES / (4 * pixels)));
     if (d->counts_bytes < chunk * pixels * 4) {
         FSEA_HIP(hipEventSynchronize(d->counts_free));  // no launch on any stream still uses the old buffer
-        int rc = grow_device(reinterpret_cast<void **>(&d->d_counts), &d->counts_bytes, chunk * pixels * 4);
+        int rc = fsea_detail::grow_device(reinterpret_cast<void **>(&d->d_counts), &d->counts_bytes, chunk * pixels * 4);
         if (rc) return rc;
     }
     // every use of the count buffer, on whatever stream, follows the previous one
@@ -378,38 +355,24 @@ int lines_launch(fsea_iq_draw *d, const void *d_iq, int type, int flip, size_t n
     return FSEA_OK;
 }
 
-// the host-buffer forms: pinned staging, copy in, the launches, copy out, on the object's own stream
+// the host-buffer forms: the launches through the object's staging (fsea_detail::HostStaging)
 int draw_host(fsea_iq_draw *d, bool lines, const void *iq, int type, int flip, size_t n, int m, uint8_t *image) {
     const size_t pixels = (size_t)IQ_RES * m * IQ_RES * m;
     const size_t in_bytes = n * pair_bytes(type);
     std::lock_guard<std::mutex> lock(d->mu);
     FSEA_ON_DEVICE(d->device);
-    int rc = grow_pinned(&d->h_in, &d->h_in_bytes, in_bytes);
-    if (!rc) rc = grow_pinned(&d->h_out, &d->h_out_bytes, pixels);
-    if (!rc) rc = grow_device(&d->d_in, &d->d_in_bytes, in_bytes);
-    if (!rc) rc = grow_device(&d->d_out, &d->d_out_bytes, pixels);
-    if (rc) return rc;
-    if (in_bytes) {
-        std::memcpy(d->h_in, iq, in_bytes);
-        FSEA_HIP(hipMemcpyAsync(d->d_in, d->h_in, in_bytes, hipMemcpyHostToDevice, d->stream));
-    }
-    rc = lines ? lines_launch(d, d->d_in, type, flip, n, 1, m, d->d_out, d->stream)
-               : points_launch(d, d->d_in, type, flip, n, 1, d->d_out, d->stream);
-    if (rc) return rc;
-    FSEA_HIP(hipMemcpyAsync(d->h_out, d->d_out, pixels, hipMemcpyDeviceToHost, d->stream));
-    FSEA_HIP(hipStreamSynchronize(d->stream));
-    std::memcpy(image, d->h_out, pixels);
-    return FSEA_OK;
+    return d->staging.run(
+        in_bytes, pixels, image, [&](void *h_in) { std::memcpy(h_in, iq, in_bytes); },
+        [&](void *d_in, void *d_out, hipStream_t s) {
+            return lines ? lines_launch(d, d_in, type, flip, n, 1, m, d_out, s)
+                         : points_launch(d, d_in, type, flip, n, 1, d_out, s);
+        });
 }
 
 void release(fsea_iq_draw *d) {
     if (d->d_counts) (void)hipFree(d->d_counts);
-    if (d->d_in) (void)hipFree(d->d_in);
-    if (d->d_out) (void)hipFree(d->d_out);
-    if (d->h_in) (void)hipHostFree(d->h_in);
-    if (d->h_out) (void)hipHostFree(d->h_out);
     if (d->counts_free) (void)hipEventDestroy(d->counts_free);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
+    d->staging.release();
     delete d;
 }
 
@@ -420,19 +383,15 @@ extern "C" {
 int fsea_iq_draw_create(fsea_iq_draw **out, int device) {
     if (!out) return fail(FSEA_EINVAL, "iq_draw out-pointer is NULL");
     *out = nullptr;
-    int count = 0;
-    hipError_t ce = hipGetDeviceCount(&count);
-    if (ce != hipSuccess || count <= 0) {
-        return fail(FSEA_ENODEVICE, "no HIP device available (%s); libfsea_hip has no CPU fallback", hipGetErrorString(ce));
-    }
-    if (device < 0 || device >= count) return fail(FSEA_EINVAL, "device %d out of range [0,%d)", device, count);
+    int rc = fsea_detail::check_device(device);
+    if (rc) return rc;
     FSEA_ON_DEVICE(device);
     fsea_iq_draw *d = new (std::nothrow) fsea_iq_draw();
     if (!d) return fail(FSEA_ENOMEM, "out of host memory");
     d->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
+    hipError_t e = d->staging.create();
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->counts_free, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(d->counts_free, d->stream);
+    if (e == hipSuccess) e = hipEventRecord(d->counts_free, d->staging.stream);
     if (e != hipSuccess) {
         release(d);
         return fail(FSEA_EHIP, "fsea_iq_draw_create: %s", hipGetErrorString(e));

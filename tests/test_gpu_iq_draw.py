@@ -241,6 +241,18 @@ def test_two_runs_are_identical(draw):
     assert np.array_equal(draw.points(iq), draw.points(iq))
 
 
+def test_host_forms_grow_their_staging_and_reuse_it():
+    """A fresh object's host forms on a small input, a larger one (more pairs in, a (256 * 4)^2 image out), then small and
+    empty ones again: the staging grows on the second call and the later calls run in the larger buffers."""
+    d = fsea.IqDraw()
+    rng = np.random.default_rng(11)
+    for n, m in ((10, 1), (20000, 4), (10, 1), (0, 2)):
+        iq = rng.integers(0, 256, 2 * n, dtype=np.uint8)
+        assert np.array_equal(d.points(iq).ravel(), points_image(iq)), n
+        assert np.array_equal(d.lines(iq, m=m).ravel(), lines_image(iq, m, n)), (n, m)
+    d.close()
+
+
 def test_two_threads_drawing_at_once_get_their_own_images():
     L = nrf.nrf_lib()
     rng = np.random.default_rng(9)
