@@ -63,6 +63,15 @@ struct TileLayout {
     size_t span = 0;
 };
 
+// x86-64's (uint8_t)(v * 256.0), the reference's nut_buffer_set_f64 / nut_buffer_get_u8 on a u8 buffer: truncate to int32,
+// 0x80000000 outside its range or for NaN, keep the low byte.  AMDGPU's v_cvt_i32_f64 saturates instead, so the range
+// check is explicit.
+__device__ __forceinline__ uint32_t coord_f64(double v) {
+    const double s = v * 256.0;
+    if (!(s > -2147483649.0 && s < 2147483648.0)) return 0u;
+    return (uint32_t)(int)s & 0xffu;
+}
+
 // At least `need` bytes in *ptr (device memory, or pinned host memory), reallocated with headroom when *cap is short.  The
 // old buffer is freed without any wait: a caller whose buffer work may still use waits for that work first.
 int grow_device(void **ptr, size_t *cap, size_t need);

@@ -24,6 +24,7 @@
 #include <cstring>
 #include <new>
 
+using fsea_detail::coord_f64;
 using fsea_detail::DeviceGuard;
 using fsea_detail::fail;
 
@@ -43,13 +44,6 @@ template <int T> struct PairBytes;
 template <> struct PairBytes<FSEA_IQ_U8> { static constexpr int v = 2; };
 template <> struct PairBytes<FSEA_IQ_F32> { static constexpr int v = 8; };
 template <> struct PairBytes<FSEA_IQ_F64> { static constexpr int v = 16; };
-
-// x86-64's (uint8_t)(double): truncate to int32, 0x80000000 outside its range or for NaN, keep the low byte
-__device__ __forceinline__ uint32_t coord_f64(double v) {
-    const double s = v * 256.0;
-    if (!(s > -2147483649.0 && s < 2147483648.0)) return 0u;
-    return (uint32_t)(int)s & 0xffu;
-}
 
 // pair k of the input: (I, Q) coordinates in [0, 255]
 template <int T>

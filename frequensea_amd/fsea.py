@@ -40,6 +40,9 @@ EXPORTS = [
     "fsea_iq_points_host", "fsea_iq_lines_host",
     "fsea_demod_create", "fsea_demod_destroy", "fsea_demod_reset", "fsea_demod_set_channel", "fsea_demod_get_channel",
     "fsea_demod_out_length", "fsea_demod_u8_device", "fsea_demod_u8_host", "fsea_demod_f64_host",
+    "fsea_interp_create", "fsea_interp_destroy", "fsea_interp_reset", "fsea_interp_n_elements", "fsea_interp_push_device",
+    "fsea_interp_push_host", "fsea_interp_frames_device", "fsea_interp_frames_host", "fsea_interp_image_tables",
+    "fsea_interp_image_frames_device", "fsea_interp_image_frames_host",
 ]
 FIR_MAX_TAPS = 512          # FSEA_FIR_MAX_TAPS (include/fsea.h)
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
@@ -50,6 +53,11 @@ DEMOD_MAX_SAMPLES = 1 << 24         # FSEA_DEMOD_MAX_SAMPLES
 # include/fsea_tune.h: only libfsea_hip_tune.so (scripts/tune.py and friends) has these
 TUNE_EXPORTS = ["fsea_plan_create_variant", "fsea_time_exec_u8_device", "fsea_time_exec_u8_rotating",
                 "fsea_plan_read_trace", "fsea_tune_stream_1to2"]
+
+
+class InterpGeometry(ctypes.Structure):
+    """fsea_interp_geometry (include/fsea.h)."""
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("iq_size", ctypes.c_int), ("flip", ctypes.c_int)]
 
 
 class FseaError(RuntimeError):
@@ -169,6 +177,18 @@ def hip_lib():
         L.fsea_demod_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
         L.fsea_demod_u8_host.argtypes = [vp, vp, sz, ci, vp]
         L.fsea_demod_f64_host.argtypes = [vp, vp, vp, sz, vp]
+        L.fsea_interp_create.argtypes = [ctypes.POINTER(vp), ci, sz, ci]
+        L.fsea_interp_destroy.argtypes = [vp]
+        L.fsea_interp_reset.argtypes = [vp]
+        L.fsea_interp_n_elements.argtypes = [vp]
+        L.fsea_interp_n_elements.restype = sz
+        L.fsea_interp_push_device.argtypes = [vp, vp, vp]
+        L.fsea_interp_push_host.argtypes = [vp, vp]
+        L.fsea_interp_frames_device.argtypes = [vp, vp, ci, vp, vp]
+        L.fsea_interp_frames_host.argtypes = [vp, vp, ci, vp]
+        L.fsea_interp_image_tables.argtypes = [ci, ci, ci, vp, vp]
+        L.fsea_interp_image_frames_device.argtypes = [vp, vp, ci, ctypes.POINTER(InterpGeometry), vp, vp]
+        L.fsea_interp_image_frames_host.argtypes = [vp, vp, ci, ctypes.POINTER(InterpGeometry), vp]
         _LIB = L
     return _LIB
 
@@ -534,6 +554,79 @@ class IqDraw:
         out; asynchronous."""
         _check(self._L.fsea_iq_lines_device(self._d, d_iq_ptr, kind, int(bool(flip)), n_points, n_frames, int(m),
                                             d_image_ptr, stream or None))
+
+
+def interp_image_tables(width, height, iq_size):
+    """fsea_interp_image_tables: (col, row) int32 arrays, the sample whose colour each pixel column / row shows (host
+    arithmetic, needs no GPU)."""
+    col, row = np.empty(max(width, 0), dtype=np.int32), np.empty(max(height, 0), dtype=np.int32)
+    _check(hip_lib().fsea_interp_image_tables(width, height, iq_size, col.ctypes.data, row.ctypes.data))
+    return col, row
+
+
+class Interp:
+    """Two resident sample blocks A and B (uint8 or float64, n_elements each, zero at first) and their blends
+    a (1 - t) + b t for arrays of weights; thin wrapper over fsea_interp_*.  frames(): the reference's
+    nrf_interpolator_get_buffer per weight; image_frames(): the frames of its gradual-noise movie tool."""
+
+    def __init__(self, dtype, n_elements, device=0):
+        self._L = hip_lib()
+        self._p = ctypes.c_void_p()
+        self.dtype = np.dtype(dtype)
+        kinds = {np.dtype(np.uint8): IQ_U8, np.dtype(np.float64): IQ_F64}
+        if self.dtype not in kinds:
+            raise TypeError("blocks must be uint8 or float64, got %s" % self.dtype)
+        self.n, self.device = int(n_elements), device
+        _check(self._L.fsea_interp_create(ctypes.byref(self._p), kinds[self.dtype], self.n, device))
+
+    def close(self):
+        if self._p:
+            self._L.fsea_interp_destroy(self._p)
+            self._p = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(self._L.fsea_interp_reset(self._p))
+
+    def push(self, block):
+        """A takes what B held, B the host array `block` (n_elements of the object's dtype)."""
+        b = np.ascontiguousarray(block, dtype=self.dtype).ravel()
+        if b.size != self.n:
+            raise ValueError("a block has %d elements, got %d" % (self.n, b.size))
+        _check(self._L.fsea_interp_push_host(self._p, b.ctypes.data))
+
+    def push_device(self, d_block_ptr, stream=0):
+        _check(self._L.fsea_interp_push_device(self._p, d_block_ptr, stream or None))
+
+    def frames(self, weights):
+        """Host float64 weights -> (len(weights), n_elements) array of the object's dtype."""
+        w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        out = np.empty((w.size, self.n), dtype=self.dtype)
+        _check(self._L.fsea_interp_frames_host(self._p, w.ctypes.data, w.size, out.ctypes.data))
+        return out
+
+    def frames_device(self, d_weights_ptr, n_frames, d_out_ptr, stream=0):
+        """Device pointers (ints; output 16-byte aligned): n_frames weights in, n_frames blocks out; asynchronous."""
+        _check(self._L.fsea_interp_frames_device(self._p, d_weights_ptr, n_frames, d_out_ptr, stream or None))
+
+    def image_frames(self, weights, width, height, iq_size, flip=True):
+        """Host float64 (already eased) weights -> (len(weights), height, width) uint8 images."""
+        w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        g = InterpGeometry(width, height, iq_size, int(bool(flip)))
+        out = np.empty((w.size, max(height, 0), max(width, 0)), dtype=np.uint8)
+        _check(self._L.fsea_interp_image_frames_host(self._p, w.ctypes.data, w.size, ctypes.byref(g), out.ctypes.data))
+        return out
+
+    def image_frames_device(self, d_weights_ptr, n_frames, width, height, iq_size, d_images_ptr, flip=True, stream=0):
+        """Device pointers (ints; images 16-byte aligned): n_frames width x height images out; asynchronous."""
+        g = InterpGeometry(width, height, iq_size, int(bool(flip)))
+        _check(self._L.fsea_interp_image_frames_device(self._p, d_weights_ptr, n_frames, ctypes.byref(g), d_images_ptr,
+                                                       stream or None))
 
 
 class PinnedArray:

@@ -35,6 +35,7 @@ NRF_EXPORTS = [
     "nrf_raw_demodulator_process", "nrf_raw_demodulator_free", "nrf_fm_demodulator_new", "nrf_fm_demodulator_process",
     "nrf_fm_demodulator_free", "nrf_decoder_new", "nrf_decoder_process", "nrf_player_new", "nrf_player_set_freq_offset",
     "nrf_player_set_gain", "nrf_player_free",
+    "nrf_interpolator_new", "nrf_interpolator_process", "nrf_interpolator_get_buffer", "nrf_interpolator_free",
 ]
 NRF_DEMODULATE_RAW, NRF_DEMODULATE_WBFM = 0, 1
 
@@ -178,6 +179,26 @@ class NrfDecoder(ctypes.Structure):
                 ("audio_samples_length", ctypes.c_int)]
 
 
+class NrfInterpolator(ctypes.Structure):
+    """nrf_interpolator: the reference's members (this build appends a backend handle)."""
+    _fields_ = [("block", NrfBlock), ("interpolate_step", ctypes.c_double), ("t", ctypes.c_double),
+                ("buffer_a", NutBufferP), ("buffer_b", NutBufferP)]
+
+
+def bind_interpolator(L):
+    """Attach the interpolator prototypes to a loaded library (ours or a build of the reference)."""
+    ip = ctypes.POINTER(NrfInterpolator)
+    L.nrf_interpolator_new.restype = ip
+    L.nrf_interpolator_new.argtypes = [ctypes.c_double]
+    L.nrf_interpolator_process.restype = None
+    L.nrf_interpolator_process.argtypes = [ip, NutBufferP]
+    L.nrf_interpolator_get_buffer.restype = NutBufferP
+    L.nrf_interpolator_get_buffer.argtypes = [ip]
+    L.nrf_interpolator_free.restype = None
+    L.nrf_interpolator_free.argtypes = [ip]
+    return L
+
+
 def bind_demod(L):
     """Attach the downsampler, demodulator, decoder and (where the library has them) player prototypes to a loaded
     library (ours or a build of the reference)."""
@@ -288,6 +309,7 @@ def nrf_lib():
         L.nrf_iq_filter_free.argtypes = [vp]
         bind_iq_draw(L)
         bind_demod(L)
+        bind_interpolator(L)
         _LIB = L
     return _LIB
 

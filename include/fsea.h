@@ -55,6 +55,7 @@ typedef struct fsea_history fsea_history;
 typedef struct fsea_fir fsea_fir;
 typedef struct fsea_iq_draw fsea_iq_draw;
 typedef struct fsea_demod fsea_demod;
+typedef struct fsea_interp fsea_interp;
 
 /* Epilogue modes.  Output element type and row length are per mode. */
 enum {
@@ -381,6 +382,54 @@ int fsea_iq_lines_device(fsea_iq_draw *draw, const void *d_iq, int type, int fli
 int fsea_iq_points_host(fsea_iq_draw *draw, const void *iq, int type, int flip, size_t n_pairs, uint8_t *image);
 int fsea_iq_lines_host(fsea_iq_draw *draw, const void *iq, int type, int flip, size_t n_points, int size_multiplier,
                        uint8_t *image);
+
+/* Blends of two resident sample blocks for an array of weights: the batched form of the reference's nrf_interpolator
+ * (src/nrf.c:442-496) and of the frame loop of its movie tool (c/gradual-noise.c:96-112).  The object owns two device
+ * blocks A and B of n_elements elements of one type, FSEA_IQ_U8 or FSEA_IQ_F64, zero after create and reset.
+ *   push:   A takes what B held, B takes the new block.  Only the new block is copied; A and B change roles by pointer.
+ *   frames: frame f, element i is the reference's nrf_interpolator_get_buffer loop with t = weights[f]:
+ *           v = a (1.0 - t) + b t in double, two products and one sum, each rounded (no fused multiply-add).  F64 blocks:
+ *           a, b and the output are the doubles themselves.  U8 blocks: a and b are byte / 256.0 and the output byte is
+ *           x86-64's (uint8_t)(v * 256.0) as for the IQ images above (so a NaN weight gives 0).  The weights are doubles
+ *           of any value; the reference's own t ends each ramp a little above 1.  Frame f is the f-th n_elements
+ *           elements of the output.
+ *   image_frames (U8 blocks of at least 2 iq_size^2 bytes): frame f is a width x height u8 image, the tool's frame for
+ *           the weight w = weights[f], which arrives already eased.  Sample (x, y) of the iq_size x iq_size grid is byte
+ *           2 (y iq_size + x) of the blocks (flip != 0: b ^ 0x80 first, the tool's (b + 128) % 256) as an integer 0...255;
+ *           pwr = a (1.0 - w) + b w in double as above, colour = (int) of pwr clamped to [0, 255] (0 for a NaN).  Pixel
+ *           (px, py) takes the colour of sample (col[px], row[py]): the last sample, in the tool's raster order, whose
+ *           put_block covers it, with BLOCK_SCALE = max(width, height) / (double) iq_size.  fsea_interp_image_tables gives
+ *           the two tables (host arithmetic, the tool's loops in one dimension each; needs no device).
+ * Device forms: asynchronous on `stream`; weights, blocks and outputs are device memory, outputs 16-byte and weights 8-byte
+ * aligned.  Calls on one object take effect in stream order (a push is seen by the frames queued behind it on that
+ * stream); across streams the caller orders them.  The first image call with a new geometry uploads its tables and
+ * waits for the object's earlier image launches.
+ * Host forms return when the output is complete (a push: when the block is on the device); staged through pinned memory
+ * on the object's own stream, calls on one object from several threads are serialised.
+ * Every form checks its arguments before any device work: FSEA_EINVAL for a NULL object or buffer, a type other than the
+ * two, more than 2^31 elements, n_frames < 0, a misaligned device buffer, a width or height outside [1, 16384], an
+ * iq_size outside [1, 4096], blocks that are not U8 or too short for the image form.  n_frames == 0 writes nothing.
+ * Create: FSEA_ENODEVICE without a GPU.  Destroy and reset wait for the device. */
+typedef struct {
+    int width, height; /* of one image */
+    int iq_size;       /* the sample grid is iq_size x iq_size */
+    int flip;          /* != 0: raw HackRF int8 bytes */
+} fsea_interp_geometry;
+
+int fsea_interp_create(fsea_interp **interp, int type, size_t n_elements, int device);
+int fsea_interp_destroy(fsea_interp *interp);
+int fsea_interp_reset(fsea_interp *interp);
+size_t fsea_interp_n_elements(const fsea_interp *interp);
+int fsea_interp_push_device(fsea_interp *interp, const void *d_block, void *stream);
+int fsea_interp_push_host(fsea_interp *interp, const void *block);
+int fsea_interp_frames_device(fsea_interp *interp, const double *d_weights, int n_frames, void *d_out, void *stream);
+int fsea_interp_frames_host(fsea_interp *interp, const double *weights, int n_frames, void *out);
+/* col: width entries, row: height entries; entry p is the sample whose colour pixel column / row p shows. */
+int fsea_interp_image_tables(int width, int height, int iq_size, int32_t *col, int32_t *row);
+int fsea_interp_image_frames_device(fsea_interp *interp, const double *d_weights, int n_frames,
+                                    const fsea_interp_geometry *geometry, void *d_images, void *stream);
+int fsea_interp_image_frames_host(fsea_interp *interp, const double *weights, int n_frames,
+                                  const fsea_interp_geometry *geometry, uint8_t *images);
 
 /* The reference's audio chain (src/nrf.c:778-1094: nrf_downsampler, nrf_raw_demodulator, nrf_fm_demodulator,
  * nrf_decoder) as a streaming decoder of n_channels channels over one input stream, each channel with its own frequency

@@ -138,6 +138,33 @@ nut_buffer *nrf_device_get_iq_buffer(nrf_device *device);
 nut_buffer *nrf_device_get_iq_lines(nrf_device *device, int size_multiplier, float line_percentage);
 void nrf_device_free(nrf_device *device);
 
+/* ---- interpolator (src/nrf.h:105-118, src/nrf.c:442-496) ----------------- */
+
+/* A linear cross-fade between consecutive blocks, t in interpolate_step steps.  The reference's members keep their order
+ * and types; the backend handle is appended.  The two blocks live on the device: buffer_a and buffer_b are kept as
+ * members and stay NULL.  The block member is zeroed and never initialised, as in the reference. */
+typedef struct {
+    NRF_BLOCK;
+    double interpolate_step;
+    double t;
+    nut_buffer *buffer_a;
+    nut_buffer *buffer_b;
+    void *backend; /* the two device blocks (fsea_interp*, libfsea_hip.so) with their type and shape; NULL before the first process */
+} nrf_interpolator;
+
+/* t = -1, no blocks yet. */
+nrf_interpolator *nrf_interpolator_new(double interpolate_step);
+/* The reference's state machine, its `else` without braces included (src/nrf.c:451-468): the first call fixes type and
+ * size, A = zeros, B = buffer, t = 0; a call with t >= 1.0 makes A what B was, B = buffer, t = 0; any other call adds
+ * interpolate_step to t AND IGNORES ITS BUFFER.  A later buffer of another type or size prints and exits (the reference
+ * asserts), as does a backend failure (no GPU). */
+void nrf_interpolator_process(nrf_interpolator *interpolator, nut_buffer *buffer);
+/* Fresh buffer of A's type, length and channels: a (1.0 - t) + b t per element in double (u8: through / 256.0 and
+ * (uint8_t)(v * 256.0), as nut_buffer_get_f64 / nut_buffer_set_f64); caller frees with nut_buffer_free.  Before the first
+ * process: prints and exits (the reference dereferences NULL). */
+nut_buffer *nrf_interpolator_get_buffer(nrf_interpolator *interpolator);
+void nrf_interpolator_free(nrf_interpolator *interpolator);
+
 /* ---- FFT analysis (src/nrf.h:128-142, src/nrf.c:557-642) ---------------- */
 
 typedef struct {
