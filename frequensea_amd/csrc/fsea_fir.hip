@@ -13,6 +13,15 @@
 // zero-padded to whole rows on the device; they arrive by scalar loads.  The tail lives in two device buffers used in
 // turn: a launch reads one and workgroup 0 writes the next one, so no workgroup can overwrite the old tail while the
 // first tile still reads it.
+//
+// fsea_shift_fir_u8 (fsea_fir_u8_shifted_*) is the u8 kernel with nrf_freq_shifter fused into the staging step: every input
+// sample is rotated once on its way into LDS, x = (u8 / 256) e^{2 pi i phase(P)} + 0.5 (1 + i), P its position in the
+// stream.  The phasor of P is base(P & ~7) * step[P & 7]: the base from the phase reduced in double (delta * P as an exact
+// two-term product) and evaluated by one sincospif, the eight steps e^{2 pi i delta j} from the kernel arguments.  A
+// staged group of eight samples needs two bases at most (one when the call starts on a multiple of eight), and every
+// rounding of the products is spelled out, so a sample's value depends on (delta, phase0, P) alone: the tail, the tiles and
+// calls cut anywhere all see the same bits.  Samples past the input (n_in <= m < n) are plain 0.0: the zero half of the
+// shifter's buffer, filtered in the same launch.
 #include "fsea_internal.h"
 
 #include <cmath>
@@ -38,6 +47,17 @@ constexpr int FIR_TAPS_ALLOC = FSEA_FIR_MAX_TAPS + 2 * FIR_R;  // padded taps on
 static_assert(FSEA_FIR_MAX_TAPS % FIR_R == 0, "the tap cap is a whole number of rows");
 
 enum { FIR_IN_U8 = 0, FIR_IN_F64 = 1 };
+constexpr double FIR_MAX_CYCLES = 1048576.0;               // |cycles_per_sample| the shifted forms accept
+constexpr uint64_t FIR_MAX_POSITION = (uint64_t)1 << 52;   // stream positions stay exact as doubles
+
+// The frequency shift of one launch (fsea_shift_fir_u8), by value in the kernel arguments.
+struct FirRot {
+    double delta;      // cycles per sample
+    double phase0;     // phase0_cycles reduced to [0, 1)
+    long long offset;  // stream position of the call's sample 0
+    long long n_in;    // samples the input holds; samples n_in .. n - 1 of the call are plain 0.0
+    cf step[8];        // e^{2 pi i delta j}, j < 8, rounded from double
+};
 
 // acc + w * tap, the tap broadcast from the low (even k) or the high (odd k) half of an SGPR pair
 __device__ __forceinline__ cf pk_tap_fma_lo(cf w, cf taps, cf acc) {
@@ -49,6 +69,38 @@ __device__ __forceinline__ cf pk_tap_fma_hi(cf w, cf taps, cf acc) {
     cf t;
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(t) : "v"(w), "s"(taps), "v"(acc));
     return t;
+}
+
+// e^{2 pi i (phase0 + delta P)} for a stream position P: delta * P is the exact sum of the rounded product and its fma
+// residual, so the reduced phase is good to ~2^-50 turns whatever P (P < 2^52 is exact as a double); float only then
+__device__ __forceinline__ cf rot_base(const FirRot &r, long long P) {
+    const double k = (double)P;
+    const double hi = __dmul_rn(r.delta, k);
+    const double lo = fma(r.delta, k, -hi);
+    double t = (hi - floor(hi)) + (lo + r.phase0);
+    t -= floor(t);
+    float s, c;
+    sincospif(2.0f * (float)t, &s, &c);
+    return cf{c, s};
+}
+
+// r.step[j] without indexing the kernel arguments by a lane's value (that would move them to scratch)
+__device__ __forceinline__ cf rot_step(const FirRot &r, int j) {
+    cf w = r.step[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) w = (j == i) ? r.step[i] : w;
+    return w;
+}
+
+// a * b with every rounding spelled out: the same bits wherever it is inlined
+__device__ __forceinline__ cf rot_mul(cf a, cf b) {
+    return cf{__fmaf_rn(a[0], b[0], -__fmul_rn(a[1], b[1])), __fmaf_rn(a[0], b[1], __fmul_rn(a[1], b[0]))};
+}
+
+// the shifter's output for the sample u = u8 / 256 at a position whose phasor is ph
+__device__ __forceinline__ cf rot_sample(cf u, cf ph) {
+    const cf p = rot_mul(u, ph);
+    return cf{__fadd_rn(p[0], 0.5f), __fadd_rn(p[1], 0.5f)};
 }
 
 template <int KIND>
@@ -104,9 +156,23 @@ __device__ __forceinline__ void fma_block(cf acc[FIR_R], const cf a[FIR_R], cons
     }
 }
 
-template <int KIND>
+// sample s of the call (0 <= s < n) as the filter sees it
+template <int KIND, bool ROT>
+__device__ __forceinline__ cf load_input(const void *__restrict__ in, long long s, uint32_t flip, const FirRot &rot) {
+    if constexpr (ROT) {
+        if (s >= rot.n_in) return cf{0.0f, 0.0f};
+        const long long P = rot.offset + s;
+        return rot_sample(load_sample<KIND>(in, s, flip), rot_mul(rot_base(rot, P & ~7LL), rot_step(rot, (int)(P & 7))));
+    } else {
+        return load_sample<KIND>(in, s, flip);
+    }
+}
+
+template <int KIND, bool ROT = false>
 __device__ __forceinline__ void fir_body(const void *__restrict__ in, long long n, uint32_t flip, const cf *__restrict__ tail_in,
-                                         cf *__restrict__ tail_out, const float *__restrict__ taps, int L, cf *__restrict__ out) {
+                                         cf *__restrict__ tail_out, const float *__restrict__ taps, int L, cf *__restrict__ out,
+                                         const FirRot &rot = FirRot{}) {
+    const long long n_in = ROT ? rot.n_in : n;   // input samples behind `in`
     __shared__ __attribute__((aligned(16))) cf lds[FIR_ROWS * FIR_ROW];
     const int tid = threadIdx.x;
     const int nb = (L + FIR_R - 1) / FIR_R;      // tap rows (zero-padded past L)
@@ -121,14 +187,29 @@ __device__ __forceinline__ void fir_body(const void *__restrict__ in, long long 
     for (int g = tid; g < groups; g += FIR_WG) {
         const long long s = s_al + 8LL * g;
         cf v[8];
-        if (s >= 0 && s + 8 <= n) {
+        if (s >= 0 && s + 8 <= n_in) {
             load_group<KIND>(in, s, flip, v);
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const long long ss = s + j;
                 v[j] = ss < 0 ? (ss + (L - 1) >= 0 ? tail_in[ss + (L - 1)] : cf{0.0f, 0.0f})
-                              : (ss < n ? load_sample<KIND>(in, ss, flip) : cf{0.0f, 0.0f});
+                              : (ss < n_in ? load_sample<KIND>(in, ss, flip) : cf{0.0f, 0.0f});
+            }
+        }
+        if constexpr (ROT) {
+            // the group's input samples (the tail is rotated already, zeros stay zeros): stream positions P0 + j, in one
+            // block of eight or two
+            if (s >= 0 && s < n_in) {
+                const long long P0 = rot.offset + s;
+                const int o = (int)(rot.offset & 7);   // == P0 & 7: s is a multiple of 8
+                const cf b0 = rot_base(rot, P0 - o);
+                const cf b1 = o ? rot_base(rot, P0 - o + 8) : b0;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const cf ph = rot_mul(o + j < 8 ? b0 : b1, rot_step(rot, (o + j) & 7));
+                    if (s + j < n_in) v[j] = rot_sample(v[j], ph);
+                }
             }
         }
 #pragma unroll
@@ -181,7 +262,7 @@ __device__ __forceinline__ void fir_body(const void *__restrict__ in, long long 
     if (blockIdx.x == 0) {
         for (int m = tid; m < L - 1; m += FIR_WG) {
             const long long e = n + m;
-            tail_out[m] = e < L - 1 ? tail_in[e] : load_sample<KIND>(in, e - (L - 1), flip);
+            tail_out[m] = e < L - 1 ? tail_in[e] : load_input<KIND, ROT>(in, e - (L - 1), flip, rot);
         }
     }
 }
@@ -200,6 +281,14 @@ extern "C" __global__ __launch_bounds__(FIR_WG) void fsea_fir_f64(const void *__
     fir_body<FIR_IN_F64>(in, n, flip, tail_in, tail_out, taps, L, out);
 }
 
+// the u8 kernel with the frequency shift in its staging step
+extern "C" __global__ __launch_bounds__(FIR_WG) void fsea_shift_fir_u8(const void *__restrict__ in, long long n, uint32_t flip,
+                                                                        const cf *__restrict__ tail_in, cf *__restrict__ tail_out,
+                                                                        const float *__restrict__ taps, int L, cf *__restrict__ out,
+                                                                        FirRot rot) {
+    fir_body<FIR_IN_U8, true>(in, n, flip, tail_in, tail_out, taps, L, out, rot);
+}
+
 struct fsea_fir {
     int n_taps = 0;
     int device = 0;
@@ -212,14 +301,44 @@ struct fsea_fir {
 
 namespace {
 
-// one launch; the caller holds f->mu and is on f's device
-int fir_launch(fsea_fir *f, int kind, const void *d_in, size_t n, int flip, void *d_out, hipStream_t s) {
+// What the shifted kernel needs for a call whose sample 0 is at stream position `offset`, n_in samples behind its input.
+FirRot make_rot(double cycles_per_sample, double phase0_cycles, uint64_t offset, size_t n_in) {
+    FirRot r;
+    r.delta = cycles_per_sample;
+    r.phase0 = phase0_cycles - std::floor(phase0_cycles);
+    r.offset = (long long)offset;
+    r.n_in = (long long)n_in;
+    for (int j = 0; j < 8; ++j) {
+        double t = cycles_per_sample * j;
+        t -= std::floor(t);
+        r.step[j] = cf{(float)std::cos(2.0 * M_PI * t), (float)std::sin(2.0 * M_PI * t)};
+    }
+    return r;
+}
+
+int check_shift(double cycles_per_sample, double phase0_cycles, uint64_t offset, size_t n) {
+    if (!(std::fabs(cycles_per_sample) <= FIR_MAX_CYCLES) || !std::isfinite(phase0_cycles)) {
+        return fail(FSEA_EINVAL, "cycles_per_sample must be finite and within +-%g, phase0_cycles finite", FIR_MAX_CYCLES);
+    }
+    if (offset > FIR_MAX_POSITION || n > FIR_MAX_POSITION - offset) {
+        return fail(FSEA_EINVAL, "sample_offset + n_samples must not exceed 2^52");
+    }
+    return FSEA_OK;
+}
+
+// one launch; the caller holds f->mu and is on f's device.  rot != nullptr: the shifted u8 kernel, n includes the zero
+// samples past rot->n_in
+int fir_launch(fsea_fir *f, int kind, const void *d_in, size_t n, int flip, void *d_out, hipStream_t s,
+               const FirRot *rot = nullptr) {
     const unsigned grid = (unsigned)((n + FIR_T - 1) / FIR_T);
     const cf *tin = f->d_tail[f->cur];
     cf *tout = f->d_tail[f->cur ^ 1];
     const long long nn = (long long)n;
     const uint32_t fm = (kind == FIR_IN_U8 && flip) ? 0x80808080u : 0u;
-    if (kind == FIR_IN_U8) {
+    if (rot) {
+        hipLaunchKernelGGL(fsea_shift_fir_u8, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, f->d_taps, f->n_taps,
+                           static_cast<cf *>(d_out), *rot);
+    } else if (kind == FIR_IN_U8) {
         hipLaunchKernelGGL(fsea_fir_u8, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, f->d_taps, f->n_taps,
                            static_cast<cf *>(d_out));
     } else {
@@ -232,7 +351,7 @@ int fir_launch(fsea_fir *f, int kind, const void *d_in, size_t n, int flip, void
 }
 
 // the host-buffer forms: one launch through the object's staging (fsea_detail::HostStaging)
-int fir_host(fsea_fir *f, int kind, const void *in, size_t n, int flip, float *out) {
+int fir_host(fsea_fir *f, int kind, const void *in, size_t n, int flip, float *out, const FirRot *rot = nullptr) {
     if (!f) return fail(FSEA_EINVAL, "fir is NULL");
     if (n == 0) return FSEA_OK;
     if (!in || !out) return fail(FSEA_EINVAL, "NULL buffer");
@@ -242,7 +361,7 @@ int fir_host(fsea_fir *f, int kind, const void *in, size_t n, int flip, float *o
     const size_t in_bytes = n * (kind == FIR_IN_U8 ? 2 : 16);
     return f->staging.run(
         in_bytes, n * sizeof(cf), out, [&](void *h_in) { std::memcpy(h_in, in, in_bytes); },
-        [&](void *d_in, void *d_out, hipStream_t s) { return fir_launch(f, kind, d_in, n, flip, d_out, s); });
+        [&](void *d_in, void *d_out, hipStream_t s) { return fir_launch(f, kind, d_in, n, flip, d_out, s, rot); });
 }
 
 void release(fsea_fir *f) {
@@ -356,8 +475,44 @@ int fsea_fir_u8_host(fsea_fir *f, const uint8_t *iq, size_t n_samples, int flip,
     return fir_host(f, FIR_IN_U8, iq, n_samples, flip, out);
 }
 
+int fsea_fir_u8_shifted_device(fsea_fir *f, const void *d_iq, size_t n_samples, int flip, double cycles_per_sample,
+                               double phase0_cycles, uint64_t sample_offset, void *d_out, void *stream) {
+    const fsea_detail::FirShift shift = {cycles_per_sample, phase0_cycles, sample_offset};
+    return fsea_detail::fir_launch_device(f, 0, d_iq, n_samples, 0, flip, &shift, d_out, static_cast<hipStream_t>(stream));
+}
+
+int fsea_fir_u8_shifted_host(fsea_fir *f, const uint8_t *iq, size_t n_samples, int flip, double cycles_per_sample,
+                             double phase0_cycles, uint64_t sample_offset, float *out) {
+    if (!f) return fail(FSEA_EINVAL, "fir is NULL");
+    int rc = check_shift(cycles_per_sample, phase0_cycles, sample_offset, n_samples);
+    if (rc) return rc;
+    const FirRot rot = make_rot(cycles_per_sample, phase0_cycles, sample_offset, n_samples);
+    return fir_host(f, FIR_IN_U8, iq, n_samples, flip, out, &rot);
+}
+
 int fsea_fir_f64_host(fsea_fir *f, const double *iq, size_t n_samples, float *out) {
     return fir_host(f, FIR_IN_F64, iq, n_samples, 0, out);
 }
 
 }  // extern "C"
+
+int fsea_detail::fir_launch_device(fsea_fir *f, int f64, const void *d_in, size_t n_in, size_t n_zero, int flip,
+                                   const FirShift *shift, void *d_out, hipStream_t s) {
+    if (!f) return fail(FSEA_EINVAL, "fir is NULL");
+    if (shift && f64) return fail(FSEA_EINVAL, "the frequency shift takes 8-bit input");
+    if (n_zero && !shift) return fail(FSEA_EINVAL, "zero samples follow a shifted block only");
+    if (n_in > ((size_t)1 << 40) || n_zero > ((size_t)1 << 40)) return fail(FSEA_EINVAL, "n_samples %zu too large", n_in);
+    const size_t n = n_in + n_zero;
+    if (shift) {
+        int rc = check_shift(shift->cycles_per_sample, shift->phase0_cycles, shift->sample_offset, n);
+        if (rc) return rc;
+    }
+    if (n == 0) return FSEA_OK;
+    if ((n_in && !d_in) || !d_out) return fail(FSEA_EINVAL, "NULL buffer");
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(FSEA_EINVAL, "d_iq and d_out must be 16-byte aligned");
+    std::lock_guard<std::mutex> lock(f->mu);
+    FSEA_ON_DEVICE(f->device);
+    if (!shift) return fir_launch(f, f64 ? FIR_IN_F64 : FIR_IN_U8, d_in, n, flip, d_out, s);
+    const FirRot rot = make_rot(shift->cycles_per_sample, shift->phase0_cycles, shift->sample_offset, n_in);
+    return fir_launch(f, FIR_IN_U8, d_in, n, flip, d_out, s, &rot);
+}

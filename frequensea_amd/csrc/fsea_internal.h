@@ -111,6 +111,18 @@ struct HostStaging {
     }
 };
 
+// The frequency shift of fsea_fir_u8_shifted_* (include/fsea.h).
+struct FirShift {
+    double cycles_per_sample, phase0_cycles;
+    uint64_t sample_offset;
+};
+
+// One launch of a FIR object on device buffers, asynchronous on `s`, arguments checked first: n_in samples of 8-bit
+// (f64 == 0) or f64 IQ behind d_in, shifted when `shift` is not null, followed by n_zero samples of plain 0.0 (only with a
+// shift: the back half of nrf_freq_shifter's buffer); n_in + n_zero pairs to d_out.  What fsea_fir_u8_device and
+// fsea_fir_u8_shifted_device call, and fsea_chain for the forms the C ABI has no name for.
+int fir_launch_device(fsea_fir *f, int f64, const void *d_in, size_t n_in, size_t n_zero, int flip, const FirShift *shift,
+                      void *d_out, hipStream_t s);
 
 }  // namespace fsea_detail
 

@@ -35,7 +35,9 @@ EXPORTS = [
     "fsea_plan_set_window", "fsea_plan_window_form", "fsea_window_fill",
     "fsea_stream_create", "fsea_stream_destroy", "fsea_copy_to_device_async", "fsea_copy_to_host_async",
     "fsea_fir_lowpass_taps", "fsea_fir_create", "fsea_fir_destroy", "fsea_fir_reset", "fsea_fir_n_taps",
-    "fsea_fir_u8_device", "fsea_fir_u8_host", "fsea_fir_f64_host",
+    "fsea_fir_u8_device", "fsea_fir_u8_host", "fsea_fir_f64_host", "fsea_fir_u8_shifted_device", "fsea_fir_u8_shifted_host",
+    "fsea_chain_create", "fsea_chain_destroy", "fsea_chain_reset", "fsea_chain_n_pairs", "fsea_chain_run_host",
+    "fsea_chain_run_f64_host", "fsea_chain_fetch_host", "fsea_chain_run_device",
     "fsea_iq_draw_create", "fsea_iq_draw_destroy", "fsea_iq_points_device", "fsea_iq_lines_device",
     "fsea_iq_points_host", "fsea_iq_lines_host",
     "fsea_demod_create", "fsea_demod_destroy", "fsea_demod_reset", "fsea_demod_set_channel", "fsea_demod_get_channel",
@@ -58,6 +60,18 @@ TUNE_EXPORTS = ["fsea_plan_create_variant", "fsea_time_exec_u8_device", "fsea_ti
 class InterpGeometry(ctypes.Structure):
     """fsea_interp_geometry (include/fsea.h)."""
     _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("iq_size", ctypes.c_int), ("flip", ctypes.c_int)]
+
+
+class ChainStage(ctypes.Structure):
+    """fsea_chain_stage (include/fsea.h)."""
+    _fields_ = [("flip", ctypes.c_int), ("shift", ctypes.c_int), ("cycles_per_sample", ctypes.c_double),
+                ("phase0_cycles", ctypes.c_double), ("sample_offset", ctypes.c_uint64), ("n_zero", ctypes.c_size_t)]
+
+
+class ChainOutputs(ctypes.Structure):
+    """fsea_chain_outputs (include/fsea.h)."""
+    _fields_ = [("points", ctypes.c_void_p), ("lines", ctypes.c_void_p), ("size_multiplier", ctypes.c_int),
+                ("n_line_points", ctypes.c_size_t), ("pairs", ctypes.c_void_p)]
 
 
 class FseaError(RuntimeError):
@@ -160,6 +174,18 @@ def hip_lib():
         L.fsea_fir_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
         L.fsea_fir_u8_host.argtypes = [vp, vp, sz, ci, vp]
         L.fsea_fir_f64_host.argtypes = [vp, vp, sz, vp]
+        L.fsea_fir_u8_shifted_device.argtypes = [vp, vp, sz, ci, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, vp, vp]
+        L.fsea_fir_u8_shifted_host.argtypes = [vp, vp, sz, ci, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, vp]
+        stp, outp = ctypes.POINTER(ChainStage), ctypes.POINTER(ChainOutputs)
+        L.fsea_chain_create.argtypes = [ctypes.POINTER(vp), vp, ci, ci]
+        L.fsea_chain_destroy.argtypes = [vp]
+        L.fsea_chain_reset.argtypes = [vp]
+        L.fsea_chain_n_pairs.argtypes = [vp]
+        L.fsea_chain_n_pairs.restype = sz
+        L.fsea_chain_run_host.argtypes = [vp, vp, sz, stp, outp]
+        L.fsea_chain_run_f64_host.argtypes = [vp, vp, sz, outp]
+        L.fsea_chain_fetch_host.argtypes = [vp, outp]
+        L.fsea_chain_run_device.argtypes = [vp, vp, sz, ci, stp, outp, vp]
         L.fsea_iq_draw_create.argtypes = [ctypes.POINTER(vp), ci]
         L.fsea_iq_draw_destroy.argtypes = [vp]
         L.fsea_iq_points_device.argtypes = [vp, vp, ci, ci, sz, ci, vp, vp]
@@ -415,6 +441,21 @@ class Fir:
         _check(self._L.fsea_fir_u8_host(self._f, iq.ctypes.data, out.size, int(bool(flip)), out.ctypes.data))
         return out
 
+    def run_shifted_device(self, d_iq_ptr, n_samples, d_out_ptr, cycles_per_sample, phase0_cycles=0.0, sample_offset=0,
+                           flip=False, stream=0):
+        """fsea_fir_u8_shifted_device: run_device with the frequency shifter fused into the load; sample_offset is the
+        number of samples the stream's earlier calls consumed."""
+        _check(self._L.fsea_fir_u8_shifted_device(self._f, d_iq_ptr, n_samples, int(bool(flip)), cycles_per_sample,
+                                                  phase0_cycles, sample_offset, d_out_ptr, stream or None))
+
+    def run_u8_shifted(self, iq_u8, cycles_per_sample, phase0_cycles=0.0, sample_offset=0, flip=False):
+        """fsea_fir_u8_shifted_host: run_u8 with the frequency shifter fused into the load."""
+        iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
+        out = np.empty(iq.size // 2, dtype=np.complex64)
+        _check(self._L.fsea_fir_u8_shifted_host(self._f, iq.ctypes.data, out.size, int(bool(flip)), cycles_per_sample,
+                                                phase0_cycles, sample_offset, out.ctypes.data))
+        return out
+
     def run_f64(self, iq):
         """Complex (or interleaved float64) IQ (host) -> complex64 filtered samples."""
         a = np.asarray(iq)
@@ -425,6 +466,86 @@ class Fir:
         out = np.empty(flat.size // 2, dtype=np.complex64)
         _check(self._L.fsea_fir_f64_host(self._f, flat.ctypes.data, out.size, out.ctypes.data))
         return out
+
+
+class Chain:
+    """Shift -> low-pass filter -> constellation images per block, the filtered block resident on the device; thin wrapper
+    over fsea_chain_*.  run() takes one 8-bit block from the host and returns what was asked for as a dict with the keys
+    "points", "lines", "pairs"; fetch() draws more from the block of the last run."""
+
+    def __init__(self, taps, device=0):
+        self._L = hip_lib()
+        self._c = ctypes.c_void_p()
+        t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
+        self.n_taps, self.device = t.size, device
+        _check(self._L.fsea_chain_create(ctypes.byref(self._c), t.ctypes.data if t.size else None, t.size, device))
+
+    def close(self):
+        if self._c:
+            self._L.fsea_chain_destroy(self._c)
+            self._c = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(self._L.fsea_chain_reset(self._c))
+
+    @property
+    def n_pairs(self):
+        return self._L.fsea_chain_n_pairs(self._c)
+
+    @staticmethod
+    def stage(flip=False, cycles_per_sample=None, phase0_cycles=0.0, sample_offset=0, n_zero=0):
+        """A ChainStage; cycles_per_sample None = no shift."""
+        return ChainStage(int(bool(flip)), int(cycles_per_sample is not None), float(cycles_per_sample or 0.0),
+                          float(phase0_cycles), int(sample_offset), int(n_zero))
+
+    def _outputs(self, n_pairs, points, lines_m, n_line_points, pairs):
+        res, o = {}, ChainOutputs(None, None, 1, 0, None)
+        if points:
+            res["points"] = np.empty((256, 256), dtype=np.uint8)
+            o.points = res["points"].ctypes.data
+        if lines_m:
+            res["lines"] = np.empty((256 * lines_m, 256 * lines_m), dtype=np.uint8)
+            o.lines, o.size_multiplier = res["lines"].ctypes.data, int(lines_m)
+            o.n_line_points = n_pairs if n_line_points is None else int(n_line_points)
+        if pairs:
+            res["pairs"] = np.empty(n_pairs, dtype=np.complex64)
+            o.pairs = res["pairs"].ctypes.data
+        return res, o
+
+    def run(self, iq_u8, stage=None, points=False, lines_m=0, n_line_points=None, pairs=False):
+        iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
+        n = iq.size // 2
+        res, o = self._outputs(n + (stage.n_zero if stage is not None else 0), points, lines_m, n_line_points, pairs)
+        _check(self._L.fsea_chain_run_host(self._c, iq.ctypes.data, n, ctypes.byref(stage) if stage is not None else None,
+                                           ctypes.byref(o)))
+        return res
+
+    def run_f64(self, iq, points=False, lines_m=0, n_line_points=None, pairs=False):
+        flat = np.ascontiguousarray(np.asarray(iq, dtype=np.complex128)).ravel().view(np.float64)
+        res, o = self._outputs(flat.size // 2, points, lines_m, n_line_points, pairs)
+        _check(self._L.fsea_chain_run_f64_host(self._c, flat.ctypes.data, flat.size // 2, ctypes.byref(o)))
+        return res
+
+    def fetch(self, points=False, lines_m=0, n_line_points=None, pairs=False):
+        res, o = self._outputs(self.n_pairs, points, lines_m, n_line_points, pairs)
+        _check(self._L.fsea_chain_fetch_host(self._c, ctypes.byref(o)))
+        return res
+
+    def run_device(self, d_iq_ptr, n_samples, n_frames, stage=None, d_points=None, d_lines=None, lines_m=1,
+                   n_line_points=None, d_pairs=None, stream=0):
+        """Device pointers (ints, 16-byte aligned): n_frames blocks of n_samples pairs in, per frame a points image, a
+        lines image and / or the filtered pairs out; asynchronous."""
+        per_frame = n_samples + (stage.n_zero if stage is not None else 0)
+        o = ChainOutputs(d_points, d_lines, int(lines_m), per_frame if n_line_points is None else int(n_line_points), d_pairs)
+        _check(self._L.fsea_chain_run_device(self._c, d_iq_ptr, n_samples, n_frames,
+                                             ctypes.byref(stage) if stage is not None else None, ctypes.byref(o),
+                                             stream or None))
 
 
 class Demod:

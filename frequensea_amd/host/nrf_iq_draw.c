@@ -19,6 +19,7 @@
 
 #include "fsea.h"
 #include "nrf.h"
+#include "nut_private.h"
 
 static pthread_mutex_t draw_mutex = PTHREAD_MUTEX_INITIALIZER;
 static fsea_iq_draw *draw_backend = NULL; /* created on first use, never freed (one per process) */
@@ -29,7 +30,7 @@ static void draw_fatal(const char *what, int rc) {
     exit(EXIT_FAILURE);
 }
 
-static void check_multiplier(int size_multiplier) {
+void nrf_private_check_iq_multiplier(int size_multiplier) {
     if (size_multiplier < 1 || size_multiplier > FSEA_IQ_MAX_MULTIPLIER) {
         fprintf(stderr, "NRF IQ draw fatal error: size_multiplier %d is outside [1, %d]\n", size_multiplier,
                 FSEA_IQ_MAX_MULTIPLIER);
@@ -73,7 +74,7 @@ static void draw_lines(const void *iq, int type, int n_points, int size_multipli
 
 /* The points the reference's loop `for (i = 0; i < max; i += 2)` visits, max = (int)((float)size * clamped percentage),
  * without an incomplete last pair.  x86-64 turns a NaN or a product of 2^31 or more into INT_MIN: no point. */
-static int line_points(int size, float line_percentage) {
+int nrf_private_iq_line_points(int size, float line_percentage) {
     const float p = line_percentage < 0 ? 0 : line_percentage > 1 ? 1 : line_percentage; /* _nrf_clampf */
     const float product = (float)size * p;
     if (!(product < 2147483648.0f)) return 0;
@@ -93,11 +94,11 @@ nut_buffer *nrf_buffer_to_iq_points(nut_buffer *buffer) {
 }
 
 nut_buffer *nrf_buffer_to_iq_lines(nut_buffer *buffer, int size_multiplier, float line_percentage) {
-    check_multiplier(size_multiplier);
+    nrf_private_check_iq_multiplier(size_multiplier);
     nut_buffer *image = new_image(NRF_IQ_RESOLUTION * size_multiplier);
     int type;
     const void *iq = payload(buffer, &type);
-    draw_lines(iq, type, line_points(elements(buffer), line_percentage), size_multiplier, image);
+    draw_lines(iq, type, nrf_private_iq_line_points(elements(buffer), line_percentage), size_multiplier, image);
     return image;
 }
 
@@ -123,10 +124,10 @@ nut_buffer *nrf_device_get_iq_buffer(nrf_device *device) {
 }
 
 nut_buffer *nrf_device_get_iq_lines(nrf_device *device, int size_multiplier, float line_percentage) {
-    check_multiplier(size_multiplier);
+    nrf_private_check_iq_multiplier(size_multiplier);
     uint8_t *block = block_copy(device);
     nut_buffer *image = new_image(NRF_IQ_RESOLUTION * size_multiplier);
-    draw_lines(block, FSEA_IQ_U8, line_points(NRF_BUFFER_SIZE_BYTES, line_percentage), size_multiplier, image);
+    draw_lines(block, FSEA_IQ_U8, nrf_private_iq_line_points(NRF_BUFFER_SIZE_BYTES, line_percentage), size_multiplier, image);
     free(block);
     return image;
 }

@@ -19,7 +19,9 @@ NUT_EXPORTS = [
     "nut_buffer_convert", "nut_buffer_save", "nut_buffer_free",
 ]
 # additions beside the reference's prototypes (include/nrf.h says so at each): the reference's nrf.h has no such function
-NRF_ADDITIONS = ["nrf_fft_set_window", "nrf_fft_set_window_weights", "nrf_decoder_free", "nrf_player_pop_pcm"]
+NRF_ADDITIONS = ["nrf_fft_set_window", "nrf_fft_set_window_weights", "nrf_decoder_free", "nrf_player_pop_pcm",
+                 "nrf_iq_chain_new", "nrf_iq_chain_set_shifter", "nrf_iq_chain_process", "nrf_iq_chain_get_iq_points",
+                 "nrf_iq_chain_get_iq_lines", "nrf_iq_chain_get_buffer", "nrf_iq_chain_free"]
 NRF_EXPORTS = [
     "nrf_block_init", "nrf_block_connect", "nrf_block_process", "nrf_device_new",
     "nrf_device_new_with_config", "nrf_device_set_frequency", "nrf_device_set_decode_handler",
@@ -307,6 +309,20 @@ def nrf_lib():
         L.nrf_iq_filter_get_buffer.argtypes = [vp]
         L.nrf_iq_filter_free.restype = None
         L.nrf_iq_filter_free.argtypes = [vp]
+        L.nrf_iq_chain_new.restype = vp
+        L.nrf_iq_chain_new.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.nrf_iq_chain_set_shifter.restype = None
+        L.nrf_iq_chain_set_shifter.argtypes = [vp, ctypes.c_int]
+        L.nrf_iq_chain_process.restype = None
+        L.nrf_iq_chain_process.argtypes = [vp, NutBufferP]
+        L.nrf_iq_chain_get_iq_points.restype = NutBufferP
+        L.nrf_iq_chain_get_iq_points.argtypes = [vp]
+        L.nrf_iq_chain_get_iq_lines.restype = NutBufferP
+        L.nrf_iq_chain_get_iq_lines.argtypes = [vp, ctypes.c_int, ctypes.c_float]
+        L.nrf_iq_chain_get_buffer.restype = NutBufferP
+        L.nrf_iq_chain_get_buffer.argtypes = [vp]
+        L.nrf_iq_chain_free.restype = None
+        L.nrf_iq_chain_free.argtypes = [vp]
         bind_iq_draw(L)
         bind_demod(L)
         bind_interpolator(L)

@@ -29,6 +29,7 @@
  *   fsea_fir_*            the IQ low-pass filter behind nrf_iq_filter: the tap design of
  *                         nrf_fir_get_low_pass_coefficients and the per-sample convolution loops of
  *                         nrf_fir_filter_get / nrf_iq_filter_get_buffer, src/nrf.c:654-775
+ *   fsea_chain_*          shift -> filter -> images per block with the filtered block resident on the device
  *   fsea_iq_*             the IQ constellation images: the per-sample loops of nrf_buffer_to_iq_points /
  *                         nrf_device_get_iq_buffer and the Bresenham rasteriser of nrf_buffer_to_iq_lines /
  *                         nrf_device_get_iq_lines, src/nrf.c:359-421, 519-553
@@ -54,6 +55,7 @@ typedef struct fsea_plan fsea_plan;
 typedef struct fsea_history fsea_history;
 typedef struct fsea_fir fsea_fir;
 typedef struct fsea_iq_draw fsea_iq_draw;
+typedef struct fsea_chain fsea_chain;
 typedef struct fsea_demod fsea_demod;
 typedef struct fsea_interp fsea_interp;
 
@@ -349,6 +351,25 @@ int fsea_fir_u8_device(fsea_fir *fir, const void *d_iq, size_t n_samples, int fl
 int fsea_fir_u8_host(fsea_fir *fir, const uint8_t *iq, size_t n_samples, int flip, float *out);
 int fsea_fir_f64_host(fsea_fir *fir, const double *iq, size_t n_samples, float *out);
 
+/* The filter with nrf_freq_shifter_process (src/nrf.c:843-866) fused into its load: kernel fsea_shift_fir_u8.  Sample m of
+ * the call stands at position P = sample_offset + m of the stream and becomes
+ *   x[m] = (u8[m] / 256) * e^{+2 pi i (phase0_cycles + P * cycles_per_sample)} + 0.5 (1 + i)
+ * (the offset-binary value itself is rotated, then 0.5 is added to both parts), and the filter runs on tail ++ x as above;
+ * the tail holds rotated samples.  cycles_per_sample = freq_offset / sample_rate.
+ * Continuing a stream: keep cycles_per_sample and phase0_cycles as they are and pass the number of samples the earlier
+ * calls consumed as sample_offset (0 for the first call) -- do NOT add m * cycles_per_sample into phase0_cycles, the sum
+ * would round differently from call to call.  The phasor of a sample is a function of (cycles_per_sample, phase0_cycles, P)
+ * alone: P * cycles_per_sample is formed as an exact two-term product, reduced modulo 1 together with phase0_cycles in
+ * double (good to ~2^-50 cycles for every P) and only then evaluated in float.  So a stream cut into calls of any lengths
+ * gives the one-call result bit for bit, as for the unshifted forms.
+ * FSEA_EINVAL (before any device work) for a NULL pointer, a misaligned device buffer, a non-finite phase0_cycles, a
+ * cycles_per_sample that is not finite or beyond +-2^20, or sample_offset + n_samples > 2^52.  Other arguments as
+ * fsea_fir_u8_device / fsea_fir_u8_host. */
+int fsea_fir_u8_shifted_device(fsea_fir *fir, const void *d_iq, size_t n_samples, int flip, double cycles_per_sample,
+                               double phase0_cycles, uint64_t sample_offset, void *d_out, void *stream);
+int fsea_fir_u8_shifted_host(fsea_fir *fir, const uint8_t *iq, size_t n_samples, int flip, double cycles_per_sample,
+                             double phase0_cycles, uint64_t sample_offset, float *out);
+
 /* IQ constellation images (src/nrf.c:359-421, 519-553).  The input is interleaved (I, Q) pairs of one element type:
  * FSEA_IQ_U8 bytes used as they are (flip != 0: raw HackRF int8 bytes, b ^ 0x80 first, as fsea_fir_u8_device), or
  * FSEA_IQ_F32 / FSEA_IQ_F64 values v whose coordinate is the reference's nut_buffer_get_u8 on x86-64:
@@ -382,6 +403,58 @@ int fsea_iq_lines_device(fsea_iq_draw *draw, const void *d_iq, int type, int fli
 int fsea_iq_points_host(fsea_iq_draw *draw, const void *iq, int type, int flip, size_t n_pairs, uint8_t *image);
 int fsea_iq_lines_host(fsea_iq_draw *draw, const void *iq, int type, int flip, size_t n_points, int size_multiplier,
                        uint8_t *image);
+
+/* The chain the reference's IQ scenes run per block (lua/dvbt.lua:46-51, lua/iq-tex-filtered.lua:44-47): optional frequency
+ * shift -> low-pass filter -> constellation images, with the filtered block resident on the device between the steps.
+ * The object owns a filter (fsea_fir: the stream's tail is carried from run to run), a draw object (fsea_iq_draw), the
+ * device buffer of the filtered f32 pairs and pinned staging.  Nothing here computes: the kernels are those of
+ * fsea_fir_u8_device / fsea_fir_u8_shifted_device and fsea_iq_points_device / fsea_iq_lines_device (FSEA_IQ_F32), so every
+ * output is what those calls give, bit for bit.
+ *   stage (NULL: no flip, no shift): how the bytes enter the filter.  shift != 0: rotated as fsea_fir_u8_shifted_device
+ *       does, and n_zero samples of plain 0.0 follow each block through the filter in the same launch -- nrf_freq_shifter's
+ *       buffer has twice the pairs of its input, the back half zero (src/nrf.c:851), and nrf_iq_filter follows its length.
+ *       A frame of the result has n_samples + n_zero pairs.  n_zero needs shift != 0.
+ *   outputs (NULL: none): any of a points image (65536 bytes), a lines image ((256 m)^2 bytes, the first n_line_points
+ *       pairs of the frame joined, n_line_points <= its pairs) and the f32 pairs themselves, per frame.
+ *   run_host:   one block of n_samples 8-bit pairs from host memory (2 n_samples bytes up), the outputs into host memory;
+ *               one stream, one synchronisation at the end.  run_f64_host: the same for f64 pairs (no flip, no shift).
+ *   fetch_host: more outputs of the resident block of the last host run (another m or n_line_points), nothing uploaded.
+ *   run_device: n_frames consecutive blocks of one stream behind d_iq -> n_frames images and frames of pairs in device
+ *               memory, asynchronous on `stream`; the same bytes as n_frames single runs.  Without zero samples it is one
+ *               filter launch; with them one per block, which then needs n_samples a multiple of 8 and n_zero even
+ *               (16-byte-aligned pieces).  The filtered pairs pass through the object's buffer: runs on several streams
+ *               are the caller's to order.  d_iq and every output 16-byte aligned.
+ * Every form checks its arguments before any device work (FSEA_EINVAL as the calls it is made of; more than 2^31 pairs per
+ * frame).  Create: as fsea_fir_create, FSEA_ENODEVICE without a GPU.  Destroy and reset (a zero tail) wait for the device.
+ * Calls on one object from several threads are serialised. */
+typedef struct {
+    int flip;                 /* != 0: raw HackRF int8 bytes */
+    int shift;                /* != 0: frequency shift in front of the filter */
+    double cycles_per_sample; /* as fsea_fir_u8_shifted_device; sample_offset is the position of the call's first sample */
+    double phase0_cycles;
+    uint64_t sample_offset;
+    size_t n_zero;            /* zero samples behind each block (shift != 0 only) */
+} fsea_chain_stage;
+
+typedef struct {
+    void *points;             /* NULL, or 65536 bytes per frame */
+    void *lines;              /* NULL, or (256 size_multiplier)^2 bytes per frame */
+    int size_multiplier;      /* of the lines image, in [1, FSEA_IQ_MAX_MULTIPLIER] */
+    size_t n_line_points;
+    void *pairs;              /* NULL, or 2 (n_samples + n_zero) floats per frame */
+} fsea_chain_outputs;
+
+int fsea_chain_create(fsea_chain **chain, const double *taps, int n_taps, int device);
+int fsea_chain_destroy(fsea_chain *chain);
+int fsea_chain_reset(fsea_chain *chain);
+/* pairs per frame of the resident block (0 before the first run) */
+size_t fsea_chain_n_pairs(const fsea_chain *chain);
+int fsea_chain_run_host(fsea_chain *chain, const uint8_t *iq, size_t n_samples, const fsea_chain_stage *stage,
+                        const fsea_chain_outputs *outputs);
+int fsea_chain_run_f64_host(fsea_chain *chain, const double *iq, size_t n_samples, const fsea_chain_outputs *outputs);
+int fsea_chain_fetch_host(fsea_chain *chain, const fsea_chain_outputs *outputs);
+int fsea_chain_run_device(fsea_chain *chain, const void *d_iq, size_t n_samples, int n_frames, const fsea_chain_stage *stage,
+                          const fsea_chain_outputs *d_outputs, void *stream);
 
 /* Blends of two resident sample blocks for an array of weights: the batched form of the reference's nrf_interpolator
  * (src/nrf.c:442-496) and of the frame loop of its movie tool (c/gradual-noise.c:96-112).  The object owns two device

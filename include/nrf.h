@@ -290,6 +290,48 @@ nut_buffer *nrf_buffer_to_iq_points(nut_buffer *buffer);
  * zero or negative size.  Both functions return a fresh buffer that the caller frees. */
 nut_buffer *nrf_buffer_to_iq_lines(nut_buffer *buffer, int size_multiplier, float line_percentage);
 
+/* ---- ADDITIONS (not in the reference): the IQ chain ---- */
+
+/* What the reference's IQ scenes do per block with three blocks and two drawing calls, as one block whose data stays on
+ * the GPU: [nrf_freq_shifter ->] nrf_iq_filter -> nrf_buffer_to_iq_points / nrf_buffer_to_iq_lines (lua/dvbt.lua:46-51,
+ * lua/iq-tex-filtered.lua:44-47).  process uploads the 8-bit block (2 bytes per pair), rotates it in the filter kernel's
+ * load and filters it into a device buffer (fsea_chain_*, include/fsea.h); each getter draws from that buffer and brings
+ * back its image alone.  The contract is drop-in equivalence with the block sequence, quirks included:
+ *   - without a shifter: nrf_iq_filter_process + nrf_iq_filter_get_buffer bit for bit, and the images of
+ *     nrf_buffer_to_iq_points / _lines applied to that buffer byte for byte;
+ *   - with a shifter: nrf_freq_shifter_process + nrf_freq_shifter_get_buffer in front.  The shifter's buffer has twice the
+ *     pairs of its input with the back half 0.0 (src/nrf.c:851) and the filter follows its length, so a call on N pairs
+ *     filters N rotated pairs and N zero pairs, get_buffer has 2N pairs and the images are drawn over all of them.  The
+ *     phase after M consumed samples is M * freq_offset / sample_rate cycles, M an integer kept here (the reference steps a
+ *     (cos, sin) pair; the two agree to ~1e-12 over a scene's run, the filter's f32 arithmetic is ~1e-7).
+ * F64 input takes a host-staged path (rotated here in double when a shifter is set).  A kernel length outside
+ * [1, FSEA_FIR_MAX_TAPS] prints and exits, as does a size_multiplier outside [1, FSEA_IQ_MAX_MULTIPLIER] and a backend
+ * failure (no GPU).  The getters return NULL before the first process call; their buffers are the caller's to free. */
+typedef struct {
+    NRF_BLOCK;
+    int sample_rate;          /* Hz */
+    int length;               /* taps */
+    int shifting;             /* != 0 once nrf_iq_chain_set_shifter was called */
+    int freq_offset;          /* Hz */
+    unsigned long long consumed; /* samples the current shifter has rotated */
+    int samples_length;       /* IQ pairs of the last process call's result; -1 before the first */
+    void *backend;            /* fsea_chain* (libfsea_hip.so) */
+    pthread_mutex_t mutex;
+} nrf_iq_chain;
+
+/* The filter of nrf_iq_filter_new(sample_rate, half_ampl_freq, kernel_length), no shifter. */
+nrf_iq_chain *nrf_iq_chain_new(int sample_rate, int half_ampl_freq, int kernel_length);
+/* Installs a FRESH shifter at phase (1, 0), as dvbt.lua:65-69 does on a key press; the filter keeps its state. */
+void nrf_iq_chain_set_shifter(nrf_iq_chain *chain, int freq_offset);
+/* One block: buffer->length IQ pairs, 2 channels (u8 values count as u8 / 256.0, f64 as is). */
+void nrf_iq_chain_process(nrf_iq_chain *chain, nut_buffer *samples);
+/* = nrf_buffer_to_iq_points / nrf_buffer_to_iq_lines of nrf_iq_chain_get_buffer's result */
+nut_buffer *nrf_iq_chain_get_iq_points(nrf_iq_chain *chain);
+nut_buffer *nrf_iq_chain_get_iq_lines(nrf_iq_chain *chain, int size_multiplier, float line_percentage);
+/* The filtered block, F64 with 2 channels, as nrf_iq_filter_get_buffer. */
+nut_buffer *nrf_iq_chain_get_buffer(nrf_iq_chain *chain);
+void nrf_iq_chain_free(nrf_iq_chain *chain);
+
 /* ---- Signal detector (src/nrf.h:209-218, src/nrf.c:876-903): host, double, the reference's layout ---- */
 
 /* process: mean = 2 * (sum of the I elements) / size, standard_deviation = sqrt(sum over all elements of
