@@ -15,10 +15,11 @@
 //
 // fsea_iq_lines: one lane per segment computes its endpoints and pixel count max(dx, dy) + 1; a wave-wide prefix sum then
 // deals the wave's pixels out to its lanes 64 at a time, so a long segment is drawn by many lanes and the wave never waits
-// on its longest segment.  Pixel t of a segment comes from the closed form of the reference's draw_line (below; proved
-// equal to the loop for every (dx, dy) in tests/test_iq_draw_host.py) and is counted with a u32 global atomic; a second
+// on its longest segment.  Pixel t of a segment comes from the closed form of the reference's draw_line (fsea_iq_raster.h,
+// shared with fsea_trace.hip; proved equal to the loop for every (dx, dy) in tests/test_iq_draw_host.py) and is counted with a u32 global atomic; a second
 // kernel clamps the counts to 255 (the reference's saturating pixel_inc).
 #include "fsea_internal.h"
+#include "fsea_iq_raster.h"
 
 #include <algorithm>
 #include <cstring>
@@ -143,22 +144,6 @@ __device__ __forceinline__ void points_body(const void *__restrict__ in, long lo
     }
 }
 
-// Pixel t (0 <= t <= max(dx, dy)) of the reference's draw_line from (x1, y1) to (x2, y2), dx = |x2 - x1|, dy = |y2 - y1|:
-// with err0 = (dx > dy ? dx : -dy) / 2 the major axis (x if dx > dy, else y) moves at every step, and the minor
-// coordinate after t steps is the unique integer k with 0 <= h - t*d + L*k < L (L the major, d the minor delta,
-// h = L / 2), i.e. k = (t*d - h + L - 1) / L.
-__device__ __forceinline__ uint32_t line_pixel(uint32_t A, uint32_t B, uint32_t t, uint32_t stride) {
-    const int x1 = (int)(A & 0xffffu), y1 = (int)(A >> 16), x2 = (int)(B & 0xffffu), y2 = (int)(B >> 16);
-    const int dx = abs(x2 - x1), dy = abs(y2 - y1);
-    const int sx = x1 < x2 ? 1 : -1, sy = y1 < y2 ? 1 : -1;
-    const bool xmajor = dx > dy;
-    const uint32_t L = (uint32_t)(xmajor ? dx : dy), d = (uint32_t)(xmajor ? dy : dx);
-    const uint32_t k = L ? (t * d - L / 2 + L - 1) / L : 0u;
-    const int x = x1 + sx * (int)(xmajor ? t : k);
-    const int y = y1 + sy * (int)(xmajor ? k : t);
-    return (uint32_t)y * stride + (uint32_t)x;
-}
-
 // grid (ceil(segments / LN_WG), frames of this launch); counts: one (256 m)^2 u32 image per frame of the launch
 template <int T>
 __device__ __forceinline__ void lines_body(const void *__restrict__ in, long long n_points, uint32_t flip, int m,
@@ -179,27 +164,10 @@ __device__ __forceinline__ void lines_body(const void *__restrict__ in, long lon
         const int dx = abs((int)(I2 - I1)) * m, dy = abs((int)(Q2 - Q1)) * m;
         len = (uint32_t)max(dx, dy) + 1u;
     }
-    // inclusive prefix sum of the pixel counts across the wave; every lane stays active through the loop below (the
-    // shuffles read other lanes' registers), only the atomic is predicated
-    uint32_t incl = len;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    const uint32_t total = __shfl(incl, 63, 64);
-    for (uint32_t base = 0; base < total; base += 64) {
-        const uint32_t p = base + lane;
-        // the lane whose segment holds pixel p: the first with incl > p
-        int lo = 0;
-#pragma unroll
-        for (int step = 32; step >= 1; step >>= 1) {
-            if (__shfl(incl, lo + step - 1, 64) <= p) lo += step;
-        }
-        const uint32_t sA = __shfl(A, lo, 64), sB = __shfl(B, lo, 64);
-        const uint32_t start = __shfl(incl, lo, 64) - __shfl(len, lo, 64);
-        if (p < total) atomicAdd(img + line_pixel(sA, sB, p - start, stride), 1u);
-    }
+    // every lane stays active through the deal of the wave's pixels (fsea_iq_raster.h); only the atomic is predicated
+    fsea_detail::wave_lines(A, B, len, lane, [&](uint32_t sA, uint32_t sB, uint32_t t) {
+        atomicAdd(img + fsea_detail::line_pixel(sA, sB, t, stride), 1u);
+    });
 }
 
 }  // namespace

@@ -45,6 +45,8 @@ EXPORTS = [
     "fsea_interp_create", "fsea_interp_destroy", "fsea_interp_reset", "fsea_interp_n_elements", "fsea_interp_push_device",
     "fsea_interp_push_host", "fsea_interp_frames_device", "fsea_interp_frames_host", "fsea_interp_image_tables",
     "fsea_interp_image_frames_device", "fsea_interp_image_frames_host",
+    "fsea_trace_create", "fsea_trace_destroy", "fsea_trace_reset", "fsea_trace_frames_device", "fsea_trace_frames_host",
+    "fsea_trace_canvas_host",
 ]
 FIR_MAX_TAPS = 512          # FSEA_FIR_MAX_TAPS (include/fsea.h)
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
@@ -60,6 +62,12 @@ TUNE_EXPORTS = ["fsea_plan_create_variant", "fsea_time_exec_u8_device", "fsea_ti
 class InterpGeometry(ctypes.Structure):
     """fsea_interp_geometry (include/fsea.h)."""
     _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("iq_size", ctypes.c_int), ("flip", ctypes.c_int)]
+
+
+class TraceConfig(ctypes.Structure):
+    """fsea_trace_config (include/fsea.h)."""
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("size_multiplier", ctypes.c_int),
+                ("pixel_inc", ctypes.c_int), ("fade", ctypes.c_int)]
 
 
 class ChainStage(ctypes.Structure):
@@ -215,6 +223,12 @@ def hip_lib():
         L.fsea_interp_image_tables.argtypes = [ci, ci, ci, vp, vp]
         L.fsea_interp_image_frames_device.argtypes = [vp, vp, ci, ctypes.POINTER(InterpGeometry), vp, vp]
         L.fsea_interp_image_frames_host.argtypes = [vp, vp, ci, ctypes.POINTER(InterpGeometry), vp]
+        L.fsea_trace_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(TraceConfig), ci]
+        L.fsea_trace_destroy.argtypes = [vp]
+        L.fsea_trace_reset.argtypes = [vp]
+        L.fsea_trace_frames_device.argtypes = [vp, vp, sz, ci, sz, ci, vp, vp]
+        L.fsea_trace_frames_host.argtypes = [vp, vp, sz, ci, sz, ci, vp]
+        L.fsea_trace_canvas_host.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -748,6 +762,56 @@ class Interp:
         g = InterpGeometry(width, height, iq_size, int(bool(flip)))
         _check(self._L.fsea_interp_image_frames_device(self._p, d_weights_ptr, n_frames, ctypes.byref(g), d_images_ptr,
                                                        stream or None))
+
+
+class Trace:
+    """The IQ trace movie of the reference's single-sample tool on one device; thin wrapper over fsea_trace_*.  A
+    width x height canvas (zero at first) with the (256 m)^2 IQ square at its centre; every frame fades it by `fade`, joins
+    the points of its frame_bytes bytes with lines, each hit adding pixel_inc unless that reaches 255, and is one image."""
+
+    def __init__(self, width=1920, height=1080, m=4, pixel_inc=4, fade=0, device=0):
+        self._L = hip_lib()
+        self._t = ctypes.c_void_p()
+        self.width, self.height, self.m, self.device = int(width), int(height), int(m), device
+        cfg = TraceConfig(self.width, self.height, self.m, int(pixel_inc), int(fade))
+        _check(self._L.fsea_trace_create(ctypes.byref(self._t), ctypes.byref(cfg), device))
+
+    def close(self):
+        if self._t:
+            self._L.fsea_trace_destroy(self._t)
+            self._t = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(self._L.fsea_trace_reset(self._t))
+
+    def frames(self, data, frame_bytes, n_frames=None, flip=True, images=True):
+        """Host uint8 bytes -> (n_frames, height, width) uint8, frame f from byte f * frame_bytes on (n_frames defaults to
+        every frame that starts inside `data`); images=False advances the canvas and returns None."""
+        b = np.ascontiguousarray(data, dtype=np.uint8).ravel()
+        if n_frames is None:
+            n_frames = -(-b.size // int(frame_bytes)) if int(frame_bytes) > 0 else 0
+        out = np.empty((max(n_frames, 0), self.height, self.width), dtype=np.uint8) if images else None
+        _check(self._L.fsea_trace_frames_host(self._t, b.ctypes.data if b.size else None, b.size, int(bool(flip)),
+                                              frame_bytes, n_frames, out.ctypes.data if images else None))
+        return out
+
+    def frames_device(self, d_bytes_ptr, n_bytes, frame_bytes, n_frames, d_images_ptr, flip=True, stream=0):
+        """Device pointers (ints; images 16-byte aligned or 0 for none): n_bytes readable bytes in, n_frames images out;
+        asynchronous."""
+        _check(self._L.fsea_trace_frames_device(self._t, d_bytes_ptr, n_bytes, int(bool(flip)), frame_bytes, n_frames,
+                                                d_images_ptr or None, stream or None))
+
+    def canvas(self):
+        """The canvas as it stands, (height, width) uint8."""
+        out = np.empty((self.height, self.width), dtype=np.uint8)
+        _check(self._L.fsea_trace_canvas_host(self._t, out.ctypes.data))
+        return out
 
 
 class PinnedArray:

@@ -58,6 +58,7 @@ typedef struct fsea_iq_draw fsea_iq_draw;
 typedef struct fsea_chain fsea_chain;
 typedef struct fsea_demod fsea_demod;
 typedef struct fsea_interp fsea_interp;
+typedef struct fsea_trace fsea_trace;
 
 /* Epilogue modes.  Output element type and row length are per mode. */
 enum {
@@ -503,6 +504,49 @@ int fsea_interp_image_frames_device(fsea_interp *interp, const double *d_weights
                                     const fsea_interp_geometry *geometry, void *d_images, void *stream);
 int fsea_interp_image_frames_host(fsea_interp *interp, const double *weights, int n_frames,
                                   const fsea_interp_geometry *geometry, uint8_t *images);
+
+/* The IQ trace movie: the frame loop of the reference's c/single-sample.c ("slowly show a single sample, frame by frame")
+ * on a canvas that stays on the device.  The object owns a width x height u8 canvas, zero after create and reset, with the
+ * (256 m) x (256 m) IQ square at OX = (width - 256 m) / 2, OY = (height - 256 m) / 2, m = size_multiplier.
+ *   frames: frame f of a call takes the bytes from f * frame_bytes on.  Its points are P[k] = (b[2k], b[2k + 1]) for
+ *           2k < frame_bytes (flip != 0: b ^ 0x80 first, the tool's (b + 128) % 256), as far as both bytes of a point lie
+ *           inside the n_bytes readable bytes of the call: with an odd frame_bytes the Q byte of a frame's last point is the
+ *           first byte of the next frame, as in the tool, and a caller whose data goes on passes at least
+ *           n_frames * frame_bytes + 1 bytes; where the data ends earlier the rest of the frame is not drawn (the tool
+ *           reads past its buffer there), and a frame wholly behind the data only fades.
+ *           1. every canvas pixel v becomes max(v - fade, 0);
+ *           2. the reference's draw_line (as fsea_iq_lines_*) runs from m P[k-1] to m P[k] for k >= 1; the last point of
+ *              the previous frame is not joined to P[0].  A hit on (x, y) is skipped when x == 0, y == 0, x == width - 1 or
+ *              y == height - 1 (the tool compares IQ-square coordinates with the canvas size); otherwise canvas pixel
+ *              (x + OX, y + OY), of value v, becomes v + pixel_inc unless v + pixel_inc >= 255;
+ *           3. the canvas is image f of the output (width x height bytes, rows top to bottom).
+ *           d_images / images NULL: the canvas advances and no frame is written (the tool's -v).
+ * The frames are exact: h hits of a frame on a pixel of faded value v leave v + pixel_inc min(h, (254 - v) / pixel_inc),
+ * whatever their order.  The same bytes fed in one call or in calls of any numbers of frames give the same frames and the
+ * same canvas.
+ * Device form: asynchronous on `stream`; d_images 16-byte aligned.  The canvas and the count planes are the object's: its
+ * calls on several streams follow one another on the device (each waits for an event the previous one recorded).
+ * Host forms return when the output is complete; staged through pinned memory on the object's own stream, calls on one
+ * object from several threads are serialised.  canvas_host: the canvas as it stands after the calls made so far.
+ * Every form checks its arguments before any device work: FSEA_EINVAL for a NULL object, config or buffer, 256 m above the
+ * width or the height, a width or height above 16384, an m outside [1, FSEA_IQ_MAX_MULTIPLIER], a pixel_inc outside
+ * [1, 254], a fade outside [0, 255], frame_bytes == 0 or above 2^31, n_frames < 0, a misaligned d_images.  n_frames == 0
+ * does nothing.  Create: FSEA_ENODEVICE without a GPU.  Destroy and reset wait for the device. */
+typedef struct {
+    int width, height;   /* of the canvas and of every frame */
+    int size_multiplier; /* the IQ square is 256 m x 256 m */
+    int pixel_inc;       /* the tool's -p */
+    int fade;            /* the tool's -f, per frame */
+} fsea_trace_config;
+
+int fsea_trace_create(fsea_trace **trace, const fsea_trace_config *config, int device);
+int fsea_trace_destroy(fsea_trace *trace);
+int fsea_trace_reset(fsea_trace *trace);
+int fsea_trace_frames_device(fsea_trace *trace, const void *d_bytes, size_t n_bytes, int flip, size_t frame_bytes,
+                             int n_frames, uint8_t *d_images, void *stream);
+int fsea_trace_frames_host(fsea_trace *trace, const void *bytes, size_t n_bytes, int flip, size_t frame_bytes, int n_frames,
+                           uint8_t *images);
+int fsea_trace_canvas_host(fsea_trace *trace, uint8_t *image);
 
 /* The reference's audio chain (src/nrf.c:778-1094: nrf_downsampler, nrf_raw_demodulator, nrf_fm_demodulator,
  * nrf_decoder) as a streaming decoder of n_channels channels over one input stream, each channel with its own frequency
