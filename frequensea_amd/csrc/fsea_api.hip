@@ -93,7 +93,28 @@ int check_device(int device) {
     return FSEA_OK;
 }
 
-void HostStaging::release() {
+int check_multiplier(int size_multiplier) {
+    if (size_multiplier < 1 || size_multiplier > FSEA_IQ_MAX_MULTIPLIER) {
+        return fail(FSEA_EINVAL, "size_multiplier must be in [1, %d], got %d", FSEA_IQ_MAX_MULTIPLIER, size_multiplier);
+    }
+    return FSEA_OK;
+}
+
+int check_n_frames(int n_frames) {
+    if (n_frames < 0) return fail(FSEA_EINVAL, "n_frames must be >= 0, got %d", n_frames);
+    return FSEA_OK;
+}
+
+int check_aligned16(const char *names, const void *a, const void *b, const void *c) {
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) return fail(FSEA_EINVAL, "%s must be 16-byte aligned", names);
+    return FSEA_OK;
+}
+
+int init_code(const char *what, hipError_t e) {
+    return e == hipSuccess ? (int)FSEA_OK : fail(FSEA_EHIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+HostStaging::~HostStaging() {
     if (d_in) (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);
     if (h_in) (void)hipHostFree(h_in);
@@ -113,6 +134,31 @@ int HostStaging::reserve(size_t in_bytes, size_t out_bytes) {
     if (!rc) rc = grow_device(&d_in, &d_in_bytes, in_bytes);
     if (!rc) rc = grow_device(&d_out, &d_out_bytes, out_bytes);
     return rc;
+}
+
+hipError_t SharedScratch::create(hipStream_t first) {
+    hipError_t e = hipEventCreateWithFlags(&used, hipEventDisableTiming);
+    return e == hipSuccess ? hipEventRecord(used, first) : e;
+}
+
+SharedScratch::~SharedScratch() {
+    if (ptr) (void)hipFree(ptr);
+    if (used) (void)hipEventDestroy(used);
+}
+
+int SharedScratch::reserve(size_t need) {
+    FSEA_HIP(hipEventSynchronize(used));  // no launch on any stream still uses the old buffer
+    return grow_device(&ptr, &bytes, need);
+}
+
+int SharedScratch::acquire(hipStream_t s) {
+    FSEA_HIP(hipStreamWaitEvent(s, used, 0));
+    return FSEA_OK;
+}
+
+int SharedScratch::release(hipStream_t s) {
+    FSEA_HIP(hipEventRecord(used, s));
+    return FSEA_OK;
 }
 
 }  // namespace fsea_detail

@@ -10,7 +10,6 @@
 #include "fsea_internal.h"
 
 #include <cstring>
-#include <new>
 
 using fsea_detail::DeviceGuard;
 using fsea_detail::fail;
@@ -25,6 +24,12 @@ struct fsea_chain {
     size_t n_pairs = 0;       // pairs per frame of the resident block
     std::mutex mu;
     fsea_detail::HostStaging staging;  // the host forms: input, images and their pinned twins
+
+    ~fsea_chain() {
+        if (fir) (void)fsea_fir_destroy(fir);
+        if (draw) (void)fsea_iq_draw_destroy(draw);
+        if (d_pairs) (void)hipFree(d_pairs);
+    }
 };
 
 namespace {
@@ -39,7 +44,7 @@ const fsea_chain_outputs NO_OUTPUTS = {nullptr, nullptr, 1, 0, nullptr};
 size_t line_pixels(const fsea_chain_outputs &o) { return o.lines ? IMAGE_BYTES * o.size_multiplier * o.size_multiplier : 0; }
 
 int check_stage(const fsea_chain_stage &st, size_t n, int n_frames) {
-    if (n_frames < 0) return fail(FSEA_EINVAL, "n_frames must be >= 0, got %d", n_frames);
+    if (int rc = fsea_detail::check_n_frames(n_frames)) return rc;
     if (st.n_zero && !st.shift) return fail(FSEA_EINVAL, "n_zero needs a frequency shift");
     if (n > MAX_PAIRS || st.n_zero > MAX_PAIRS || n + st.n_zero > MAX_PAIRS ||
         (n_frames && n + st.n_zero > MAX_TOTAL / (size_t)n_frames)) {
@@ -53,9 +58,7 @@ int check_stage(const fsea_chain_stage &st, size_t n, int n_frames) {
 
 int check_outputs(const fsea_chain_outputs &o, size_t n_pairs, int n_frames, bool device) {
     if (o.lines) {
-        if (o.size_multiplier < 1 || o.size_multiplier > FSEA_IQ_MAX_MULTIPLIER) {
-            return fail(FSEA_EINVAL, "size_multiplier must be in [1, %d], got %d", FSEA_IQ_MAX_MULTIPLIER, o.size_multiplier);
-        }
+        if (int rc = fsea_detail::check_multiplier(o.size_multiplier)) return rc;
         if (o.n_line_points > n_pairs) {
             return fail(FSEA_EINVAL, "n_line_points %zu exceeds the %zu pairs of a frame", o.n_line_points, n_pairs);
         }
@@ -63,10 +66,7 @@ int check_outputs(const fsea_chain_outputs &o, size_t n_pairs, int n_frames, boo
             return fail(FSEA_EINVAL, "lines over a part of each frame need an even number of pairs per frame");
         }
     }
-    if (device && (((uintptr_t)o.points | (uintptr_t)o.lines | (uintptr_t)o.pairs) & 15)) {
-        return fail(FSEA_EINVAL, "the outputs must be 16-byte aligned");
-    }
-    return FSEA_OK;
+    return device ? fsea_detail::check_aligned16("the outputs", o.points, o.lines, o.pairs) : (int)FSEA_OK;
 }
 
 // the caller holds c->mu and is on c's device; stream work that may still read the old buffer is the caller's to order
@@ -160,18 +160,12 @@ int run_host(fsea_chain *c, const void *iq, int f64, size_t n, const fsea_chain_
     return host_call(c, true, iq, f64, n, st, o);
 }
 
-void release(fsea_chain *c) {
-    if (c->fir) (void)fsea_fir_destroy(c->fir);
-    if (c->draw) (void)fsea_iq_draw_destroy(c->draw);
-    if (c->d_pairs) (void)hipFree(c->d_pairs);
-    c->staging.release();
-    delete c;
-}
-
 }  // namespace
 
 extern "C" {
 
+// Not through fsea_detail::create_object: the taps are checked by fsea_fir_create, and bad taps are reported before a
+// missing device, so the object exists before the device is looked at.
 int fsea_chain_create(fsea_chain **out, const double *taps, int n_taps, int device) {
     if (!out) return fail(FSEA_EINVAL, "chain out-pointer is NULL");
     *out = nullptr;
@@ -187,20 +181,14 @@ int fsea_chain_create(fsea_chain **out, const double *taps, int n_taps, int devi
         if (e != hipSuccess) rc = fail(FSEA_EHIP, "fsea_chain_create: %s", hipGetErrorString(e));
     }
     if (rc) {
-        release(c);
+        delete c;   // no device memory of its own yet; the two objects restore the device themselves
         return rc;
     }
     *out = c;
     return FSEA_OK;
 }
 
-int fsea_chain_destroy(fsea_chain *c) {
-    if (!c) return FSEA_OK;
-    FSEA_ON_DEVICE(c->device);
-    FSEA_HIP(hipDeviceSynchronize());   // launches of the object on any stream may still use its buffers
-    release(c);
-    return FSEA_OK;
-}
+int fsea_chain_destroy(fsea_chain *c) { return fsea_detail::destroy_object(c); }
 
 int fsea_chain_reset(fsea_chain *c) {
     if (!c) return fail(FSEA_EINVAL, "chain is NULL");
@@ -238,7 +226,8 @@ int fsea_chain_run_device(fsea_chain *c, const void *d_iq, size_t n_samples, int
     if (rc) return rc;
     if (n_frames == 0) return FSEA_OK;
     if (n_samples && !d_iq) return fail(FSEA_EINVAL, "NULL buffer");
-    if ((uintptr_t)d_iq & 15) return fail(FSEA_EINVAL, "d_iq must be 16-byte aligned");
+    rc = fsea_detail::check_aligned16("d_iq", d_iq);
+    if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t total = n_samples + st.n_zero;
     std::lock_guard<std::mutex> lock(c->mu);

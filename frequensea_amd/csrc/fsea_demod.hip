@@ -26,7 +26,6 @@
 
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
 using fsea_detail::DeviceGuard;
@@ -366,6 +365,8 @@ struct fsea_demod {
     void *d_y1 = nullptr;
     size_t d_y1_bytes = 0;
     fsea_detail::HostStaging staging;           // the host-buffer forms
+
+    ~fsea_demod();
 };
 
 namespace {
@@ -572,21 +573,6 @@ int zero_state(fsea_demod *d) {
     return FSEA_OK;
 }
 
-void release(fsea_demod *d) {
-    void *dev[] = {d->d_taps1, d->d_taps3, d->d_tail1[0], d->d_tail1[1], d->d_tail3[0], d->d_tail3[1], d->d_l[0],
-                   d->d_l[1], d->d_v[0], d->d_v[1], d->d_y1};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    for (int i = 0; i < DM_RING; ++i) {
-        if (d->d_par[i]) (void)hipFree(d->d_par[i]);
-        if (d->h_par[i]) (void)hipHostFree(d->h_par[i]);
-        if (d->ev[i]) (void)hipEventDestroy(d->ev[i]);
-    }
-    for (Table &t : d->tables) free_table(t);
-    d->staging.release();
-    delete d;
-}
-
 hipError_t upload_taps(double **dst, double rate, double cutoff, int L) {
     double taps[DM_TAIL] = {};
     if (fsea_fir_lowpass_taps(rate, cutoff, L, taps) != FSEA_OK) return hipErrorInvalidValue;
@@ -596,6 +582,18 @@ hipError_t upload_taps(double **dst, double rate, double cutoff, int L) {
 }
 
 }  // namespace
+
+fsea_demod::~fsea_demod() {
+    void *dev[] = {d_taps1, d_taps3, d_tail1[0], d_tail1[1], d_tail3[0], d_tail3[1], d_l[0], d_l[1], d_v[0], d_v[1], d_y1};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    for (int i = 0; i < DM_RING; ++i) {
+        if (d_par[i]) (void)hipFree(d_par[i]);
+        if (h_par[i]) (void)hipHostFree(h_par[i]);
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    }
+    for (Table &t : tables) free_table(t);
+}
 
 extern "C" {
 
@@ -607,65 +605,45 @@ int fsea_demod_create(fsea_demod **out, int type, int in_rate, int out_rate, int
     if (n_channels < 1 || n_channels > FSEA_DEMOD_MAX_CHANNELS) {
         return fail(FSEA_EINVAL, "n_channels must be in [1, %d], got %d", FSEA_DEMOD_MAX_CHANNELS, n_channels);
     }
-    int rc = fsea_detail::check_device(device);
-    if (rc) return rc;
-    FSEA_ON_DEVICE(device);
-    fsea_demod *d = new (std::nothrow) fsea_demod();
-    if (!d) return fail(FSEA_ENOMEM, "out of host memory");
-    d->type = type;
-    d->in_rate = in_rate;
-    d->out_rate = out_rate;
-    d->K = n_channels;
-    d->device = device;
-    d->chan.resize(n_channels);
-    // the reference's constructors: nrf_raw_demodulator_new, nrf_fm_demodulator_new (src/nrf.c:904-941)
-    hipError_t e;
-    if (type == FSEA_DEMOD_RAW) {
-        d->L1 = L_RAW;
-        d->r1 = in_rate / (double)out_rate;
-        e = upload_taps(&d->d_taps1, in_rate, out_rate / 2, L_RAW);
-    } else {
-        d->L1 = L_FM1;
-        d->L3 = L_FM3;
-        d->r1 = in_rate / (double)FM_INTER_RATE;
-        d->r3 = FM_INTER_RATE / (double)out_rate;
-        d->ampl_conv = out_rate / (TAU * FM_MAX_F);
-        d->alpha = 1.0 / (1.0 + out_rate * 50.0 / 1e6);
-        e = upload_taps(&d->d_taps1, in_rate, (int)(FM_MAX_F * 0.8), L_FM1);
-        if (e == hipSuccess) e = upload_taps(&d->d_taps3, FM_INTER_RATE, 10000, L_FM3);
-    }
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(&d->d_tail1[i], (size_t)n_channels * DM_TAIL * sizeof(double2));
-        if (e == hipSuccess) e = hipMalloc(&d->d_tail3[i], (size_t)n_channels * DM_TAIL * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&d->d_l[i], (size_t)n_channels * sizeof(double2));
-        if (e == hipSuccess) e = hipMalloc(&d->d_v[i], (size_t)n_channels * sizeof(double));
-    }
-    for (int i = 0; i < DM_RING && e == hipSuccess; ++i) {
-        e = hipMalloc(&d->d_par[i], (size_t)n_channels * sizeof(ChanParam));
-        if (e == hipSuccess) e = hipHostMalloc(&d->h_par[i], (size_t)n_channels * sizeof(ChanParam), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev[i], hipEventDisableTiming);
-    }
-    if (e == hipSuccess) e = d->staging.create();
-    if (e != hipSuccess) {
-        release(d);
-        return fail(FSEA_EHIP, "fsea_demod_create: %s", hipGetErrorString(e));
-    }
-    rc = zero_state(d);
-    if (rc) {
-        release(d);
-        return rc;
-    }
-    *out = d;
-    return FSEA_OK;
+    return fsea_detail::create_object(out, device, "fsea_demod_create", [&](fsea_demod *d) {
+        d->type = type;
+        d->in_rate = in_rate;
+        d->out_rate = out_rate;
+        d->K = n_channels;
+        d->chan.resize(n_channels);
+        // the reference's constructors: nrf_raw_demodulator_new, nrf_fm_demodulator_new (src/nrf.c:904-941)
+        hipError_t e;
+        if (type == FSEA_DEMOD_RAW) {
+            d->L1 = L_RAW;
+            d->r1 = in_rate / (double)out_rate;
+            e = upload_taps(&d->d_taps1, in_rate, out_rate / 2, L_RAW);
+        } else {
+            d->L1 = L_FM1;
+            d->L3 = L_FM3;
+            d->r1 = in_rate / (double)FM_INTER_RATE;
+            d->r3 = FM_INTER_RATE / (double)out_rate;
+            d->ampl_conv = out_rate / (TAU * FM_MAX_F);
+            d->alpha = 1.0 / (1.0 + out_rate * 50.0 / 1e6);
+            e = upload_taps(&d->d_taps1, in_rate, (int)(FM_MAX_F * 0.8), L_FM1);
+            if (e == hipSuccess) e = upload_taps(&d->d_taps3, FM_INTER_RATE, 10000, L_FM3);
+        }
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+            e = hipMalloc(&d->d_tail1[i], (size_t)n_channels * DM_TAIL * sizeof(double2));
+            if (e == hipSuccess) e = hipMalloc(&d->d_tail3[i], (size_t)n_channels * DM_TAIL * sizeof(double));
+            if (e == hipSuccess) e = hipMalloc(&d->d_l[i], (size_t)n_channels * sizeof(double2));
+            if (e == hipSuccess) e = hipMalloc(&d->d_v[i], (size_t)n_channels * sizeof(double));
+        }
+        for (int i = 0; i < DM_RING && e == hipSuccess; ++i) {
+            e = hipMalloc(&d->d_par[i], (size_t)n_channels * sizeof(ChanParam));
+            if (e == hipSuccess) e = hipHostMalloc(&d->h_par[i], (size_t)n_channels * sizeof(ChanParam), hipHostMallocDefault);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev[i], hipEventDisableTiming);
+        }
+        const int rc = fsea_detail::init_code("fsea_demod_create", e);
+        return rc ? rc : zero_state(d);
+    });
 }
 
-int fsea_demod_destroy(fsea_demod *d) {
-    if (!d) return FSEA_OK;
-    FSEA_ON_DEVICE(d->device);
-    FSEA_HIP(hipDeviceSynchronize());   // launches of the object on any stream may still read its state
-    release(d);
-    return FSEA_OK;
-}
+int fsea_demod_destroy(fsea_demod *d) { return fsea_detail::destroy_object(d); }
 
 int fsea_demod_reset(fsea_demod *d) {
     if (!d) return fail(FSEA_EINVAL, "demod is NULL");

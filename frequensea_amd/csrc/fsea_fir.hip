@@ -297,6 +297,12 @@ struct fsea_fir {
     int cur = 0;
     std::mutex mu;
     fsea_detail::HostStaging staging;  // the host-buffer forms
+
+    ~fsea_fir() {
+        if (d_taps) (void)hipFree(d_taps);
+        for (cf *tail : d_tail)
+            if (tail) (void)hipFree(tail);
+    }
 };
 
 namespace {
@@ -364,14 +370,6 @@ int fir_host(fsea_fir *f, int kind, const void *in, size_t n, int flip, float *o
         [&](void *d_in, void *d_out, hipStream_t s) { return fir_launch(f, kind, d_in, n, flip, d_out, s, rot); });
 }
 
-void release(fsea_fir *f) {
-    if (f->d_taps) (void)hipFree(f->d_taps);
-    for (int i = 0; i < 2; ++i)
-        if (f->d_tail[i]) (void)hipFree(f->d_tail[i]);
-    f->staging.release();
-    delete f;
-}
-
 }  // namespace
 
 extern "C" {
@@ -418,35 +416,19 @@ int fsea_fir_create(fsea_fir **out, const double *taps, int n_taps, int device) 
     for (int k = 0; k < n_taps; ++k) {
         if (!std::isfinite(taps[k])) return fail(FSEA_EINVAL, "tap %d is not finite", k);
     }
-    int rc = fsea_detail::check_device(device);
-    if (rc) return rc;
-    FSEA_ON_DEVICE(device);
-    fsea_fir *f = new (std::nothrow) fsea_fir();
-    if (!f) return fail(FSEA_ENOMEM, "out of host memory");
-    f->n_taps = n_taps;
-    f->device = device;
-    float tf[FIR_TAPS_ALLOC] = {};
-    for (int k = 0; k < n_taps; ++k) tf[k] = (float)taps[k];
-    hipError_t e = hipMalloc(&f->d_taps, sizeof(tf));
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc(&f->d_tail[i], FSEA_FIR_MAX_TAPS * sizeof(cf));
-    if (e == hipSuccess) e = hipMemcpy(f->d_taps, tf, sizeof(tf), hipMemcpyHostToDevice);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMemset(f->d_tail[i], 0, FSEA_FIR_MAX_TAPS * sizeof(cf));
-    if (e == hipSuccess) e = f->staging.create();
-    if (e != hipSuccess) {
-        release(f);
-        return fail(FSEA_EHIP, "fsea_fir_create: %s", hipGetErrorString(e));
-    }
-    *out = f;
-    return FSEA_OK;
+    return fsea_detail::create_object(out, device, "fsea_fir_create", [&](fsea_fir *f) {
+        f->n_taps = n_taps;
+        float tf[FIR_TAPS_ALLOC] = {};
+        for (int k = 0; k < n_taps; ++k) tf[k] = (float)taps[k];
+        hipError_t e = hipMalloc(&f->d_taps, sizeof(tf));
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc(&f->d_tail[i], FSEA_FIR_MAX_TAPS * sizeof(cf));
+        if (e == hipSuccess) e = hipMemcpy(f->d_taps, tf, sizeof(tf), hipMemcpyHostToDevice);
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMemset(f->d_tail[i], 0, FSEA_FIR_MAX_TAPS * sizeof(cf));
+        return e;
+    });
 }
 
-int fsea_fir_destroy(fsea_fir *f) {
-    if (!f) return FSEA_OK;
-    FSEA_ON_DEVICE(f->device);
-    FSEA_HIP(hipDeviceSynchronize());   // launches of the object on any stream may still read its taps and tails
-    release(f);
-    return FSEA_OK;
-}
+int fsea_fir_destroy(fsea_fir *f) { return fsea_detail::destroy_object(f); }
 
 int fsea_fir_reset(fsea_fir *f) {
     if (!f) return fail(FSEA_EINVAL, "fir is NULL");
@@ -464,7 +446,7 @@ int fsea_fir_u8_device(fsea_fir *f, const void *d_iq, size_t n_samples, int flip
     if (!f) return fail(FSEA_EINVAL, "fir is NULL");
     if (n_samples == 0) return FSEA_OK;
     if (!d_iq || !d_out) return fail(FSEA_EINVAL, "NULL buffer");
-    if (((uintptr_t)d_iq | (uintptr_t)d_out) & 15) return fail(FSEA_EINVAL, "d_iq and d_out must be 16-byte aligned");
+    if (int rc = fsea_detail::check_aligned16("d_iq and d_out", d_iq, d_out)) return rc;
     if (n_samples > ((size_t)1 << 40)) return fail(FSEA_EINVAL, "n_samples %zu too large", n_samples);
     std::lock_guard<std::mutex> lock(f->mu);
     FSEA_ON_DEVICE(f->device);
@@ -509,7 +491,7 @@ int fsea_detail::fir_launch_device(fsea_fir *f, int f64, const void *d_in, size_
     }
     if (n == 0) return FSEA_OK;
     if ((n_in && !d_in) || !d_out) return fail(FSEA_EINVAL, "NULL buffer");
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(FSEA_EINVAL, "d_iq and d_out must be 16-byte aligned");
+    if (int rc = fsea_detail::check_aligned16("d_iq and d_out", d_in, d_out)) return rc;
     std::lock_guard<std::mutex> lock(f->mu);
     FSEA_ON_DEVICE(f->device);
     if (!shift) return fir_launch(f, f64 ? FIR_IN_F64 : FIR_IN_U8, d_in, n, flip, d_out, s);

@@ -1,6 +1,7 @@
 // fsea_internal.h -- what the translation units of libfsea_hip.so share behind the C ABI (include/fsea.h): the plan
-// object, error plumbing, the launch dispatcher, and the host scaffold of the FIR, IQ-draw and demod objects (device check,
-// growable buffers, host-form staging).  fsea_api.hip: plans, the power-of-two launches, every entry point;
+// object, error plumbing, the launch dispatcher, and the scaffold of the six device objects (FIR, IQ draw, demod, interp,
+// chain, trace): shared argument checks, create / destroy, growable buffers, the event-ordered scratch buffer, host-form
+// staging.  fsea_api.hip: plans, the power-of-two launches, every entry point, the scaffold's bodies;
 // fsea_anysize.hip: the transform sizes without a kernel of their own (Bluestein's algorithm, four-step decomposition).
 #pragma once
 
@@ -10,6 +11,7 @@
 
 #include <cstring>
 #include <mutex>
+#include <new>
 #include <string>
 
 #include "fsea_registry.h"
@@ -80,15 +82,21 @@ int grow_pinned(void **ptr, size_t *cap, size_t need);
 // FSEA_OK, FSEA_ENODEVICE when HIP has no device at all, FSEA_EINVAL when `device` is not one of them
 int check_device(int device);
 
-// The host-buffer forms of an object (FIR, IQ draw, demod): its own non-blocking stream and pinned + device staging, grown
-// on demand.  Only those forms use the staging, on that stream, under the object's mutex.
+// Argument checks that several objects share, with the one message each has.  `names` is what the caller's message says
+// must be 16-byte aligned ("d_iq and d_out", "the outputs", ...).
+int check_multiplier(int size_multiplier);
+int check_n_frames(int n_frames);
+int check_aligned16(const char *names, const void *a, const void *b = nullptr, const void *c = nullptr);
+
+// The host-buffer forms of a device object: its own non-blocking stream and pinned + device staging, grown on demand.
+// Only those forms use the staging, on that stream, under the object's mutex.
 struct HostStaging {
     hipStream_t stream = nullptr;
     void *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
     size_t h_in_bytes = 0, h_out_bytes = 0, d_in_bytes = 0, d_out_bytes = 0;
 
     hipError_t create() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
-    void release();
+    ~HostStaging();
     int reserve(size_t in_bytes, size_t out_bytes);
 
     // One host-form call: fill(h_in) writes the in_bytes of input into pinned memory, copy in, launch(d_in, d_out, stream)
@@ -110,6 +118,58 @@ struct HostStaging {
         return FSEA_OK;
     }
 };
+
+// A growable device buffer that an object's launches use on whatever stream the caller names.  One event keeps them in
+// order: acquire(s) makes s wait for the previous use, release(s) records the end of this one, and reserve() waits on the
+// host for the last use before the buffer is reallocated (or, by the caller, overwritten).  The caller holds the object's
+// mutex and is on its device.
+struct SharedScratch {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    hipEvent_t used = nullptr;  // recorded after the last work that used the buffer
+
+    hipError_t create(hipStream_t first);  // the event starts recorded on `first`, so it can be waited for at once
+    ~SharedScratch();
+    int reserve(size_t need);
+    int acquire(hipStream_t s);
+    int release(hipStream_t s);
+};
+
+// FSEA_OK, or FSEA_EHIP with "<what>: <HIP's text>"; an int code passes through (what an object's initialiser returns)
+int init_code(const char *what, hipError_t e);
+inline int init_code(const char *, int rc) { return rc; }
+
+// What every fsea_X_create does once its own arguments are checked: device check, `new`, the staging stream, then
+// init(obj) -> hipError_t or an FSEA_* code, on the object's device.  T has `device`, `staging` and a destructor that frees
+// whatever init got as far as allocating.  `what` is the entry point's name, for the failure text.
+template <class T, class Init>
+int create_object(T **out, int device, const char *what, Init &&init) {
+    int rc = check_device(device);
+    if (rc) return rc;
+    FSEA_ON_DEVICE(device);
+    T *obj = new (std::nothrow) T();
+    if (!obj) return fail(FSEA_ENOMEM, "out of host memory");
+    obj->device = device;
+    rc = init_code(what, obj->staging.create());
+    if (!rc) rc = init_code(what, init(obj));
+    if (rc) {
+        delete obj;
+        return rc;
+    }
+    *out = obj;
+    return FSEA_OK;
+}
+
+// fsea_X_destroy: NULL is fine; launches of the object on any stream may still use what it owns, so the device is idle
+// before the destructor frees it
+template <class T>
+int destroy_object(T *obj) {
+    if (!obj) return FSEA_OK;
+    FSEA_ON_DEVICE(obj->device);
+    FSEA_HIP(hipDeviceSynchronize());
+    delete obj;
+    return FSEA_OK;
+}
 
 // The frequency shift of fsea_fir_u8_shifted_* (include/fsea.h).
 struct FirShift {

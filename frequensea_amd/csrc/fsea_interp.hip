@@ -22,7 +22,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <vector>
 
 using fsea_detail::coord_f64;
@@ -257,11 +256,14 @@ struct fsea_interp {
     std::mutex mu;
     void *d_a = nullptr, *d_b = nullptr;  // the blocks; a push copies into d_a's memory and swaps the two
     // the image form's tables on the device, for the geometry of the last call
-    uint16_t *d_tab = nullptr;
-    size_t tab_bytes = 0;
+    fsea_detail::SharedScratch tab;
     int tab_w = 0, tab_h = 0, tab_iq = 0, tile_rows = 0, max_slots = 0;
-    hipEvent_t tab_free = nullptr;     // recorded after the last launch that read d_tab
     fsea_detail::HostStaging staging;  // the host-buffer forms
+
+    ~fsea_interp() {
+        if (d_a) (void)hipFree(d_a);
+        if (d_b) (void)hipFree(d_b);
+    }
 };
 
 namespace {
@@ -300,8 +302,7 @@ size_t image_lds_bytes(int width, int iq_size, int max_slots) {
 
 int check_frames(const fsea_interp *p, int n_frames) {
     if (!p) return fail(FSEA_EINVAL, "interp is NULL");
-    if (n_frames < 0) return fail(FSEA_EINVAL, "n_frames must be >= 0, got %d", n_frames);
-    return FSEA_OK;
+    return fsea_detail::check_n_frames(n_frames);
 }
 
 int check_image(const fsea_interp *p, int n_frames, const fsea_interp_geometry *g) {
@@ -345,7 +346,7 @@ int frames_launch(fsea_interp *p, const double *d_w, int n_frames, void *d_out, 
 
 // the tables of geometry g on the device (kept from the last call with the same geometry)
 int image_tables(fsea_interp *p, const fsea_interp_geometry *g) {
-    if (p->d_tab && p->tab_w == g->width && p->tab_h == g->height && p->tab_iq == g->iq_size) return FSEA_OK;
+    if (p->tab.ptr && p->tab_w == g->width && p->tab_h == g->height && p->tab_iq == g->iq_size) return FSEA_OK;
     const int w16 = (g->width + 15) & ~15;
     std::vector<int32_t> col((size_t)g->width), row((size_t)g->height);
     const double scale = block_scale(g->width, g->height, g->iq_size);
@@ -372,11 +373,10 @@ int image_tables(fsea_interp *p, const fsea_interp_geometry *g) {
         return fail(FSEA_EINVAL, "%d x %d images of %d x %d samples need more LDS than a workgroup has", g->width, g->height,
                     g->iq_size, g->iq_size);
     }
-    FSEA_HIP(hipEventSynchronize(p->tab_free));  // no launch on any stream still reads the old tables
-    int rc = fsea_detail::grow_device(reinterpret_cast<void **>(&p->d_tab), &p->tab_bytes, tab.size() * 2);
+    int rc = p->tab.reserve(tab.size() * 2);  // no launch on any stream still reads the old tables
     if (rc) return rc;
     p->tab_w = 0;
-    FSEA_HIP(hipMemcpy(p->d_tab, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
+    FSEA_HIP(hipMemcpy(p->tab.ptr, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
     p->tab_w = g->width;
     p->tab_h = g->height;
     p->tab_iq = g->iq_size;
@@ -398,12 +398,11 @@ int image_launch(fsea_interp *p, const double *d_w, int n_frames, const fsea_int
         const dim3 grid(gx, (unsigned)((nf + IM_RUN - 1) / IM_RUN));
         hipLaunchKernelGGL(fsea_interp_image_u8, grid, dim3(IT_WG), lds, s, static_cast<const uint8_t *>(p->d_a),
                            static_cast<const uint8_t *>(p->d_b), g->flip ? 0x80u : 0u, d_w + f0, nf, g->width, g->height,
-                           g->iq_size, p->tile_rows, p->max_slots, p->d_tab,
+                           g->iq_size, p->tile_rows, p->max_slots, static_cast<const uint16_t *>(p->tab.ptr),
                            static_cast<uint8_t *>(d_images) + (size_t)f0 * frame_bytes);
         FSEA_HIP(hipGetLastError());
     }
-    FSEA_HIP(hipEventRecord(p->tab_free, s));
-    return FSEA_OK;
+    return p->tab.release(s);
 }
 
 // B's old memory becomes A, the new block lands in A's old memory and becomes B
@@ -412,15 +411,6 @@ int push_launch(fsea_interp *p, const void *d_block, hipStream_t s) {
     if (nb) FSEA_HIP(hipMemcpyAsync(p->d_a, d_block, nb, hipMemcpyDeviceToDevice, s));
     std::swap(p->d_a, p->d_b);
     return FSEA_OK;
-}
-
-void release(fsea_interp *p) {
-    if (p->d_a) (void)hipFree(p->d_a);
-    if (p->d_b) (void)hipFree(p->d_b);
-    if (p->d_tab) (void)hipFree(p->d_tab);
-    if (p->tab_free) (void)hipEventDestroy(p->tab_free);
-    p->staging.release();
-    delete p;
 }
 
 }  // namespace
@@ -442,38 +432,21 @@ int fsea_interp_create(fsea_interp **out, int type, size_t n_elements, int devic
     *out = nullptr;
     if (type != FSEA_IQ_U8 && type != FSEA_IQ_F64) return fail(FSEA_EINVAL, "element type must be FSEA_IQ_U8 or FSEA_IQ_F64, got %d", type);
     if (n_elements > MAX_ELEMS) return fail(FSEA_EINVAL, "%zu elements are too many", n_elements);
-    int rc = fsea_detail::check_device(device);
-    if (rc) return rc;
-    FSEA_ON_DEVICE(device);
-    fsea_interp *p = new (std::nothrow) fsea_interp();
-    if (!p) return fail(FSEA_ENOMEM, "out of host memory");
-    p->device = device;
-    p->type = type;
-    p->n = n_elements;
-    const size_t nb = std::max<size_t>(16, n_elements * elem_bytes(type));
-    hipError_t e = p->staging.create();
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->tab_free, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(p->tab_free, p->staging.stream);
-    if (e == hipSuccess) e = hipMalloc(&p->d_a, nb);
-    if (e == hipSuccess) e = hipMalloc(&p->d_b, nb);
-    if (e == hipSuccess) e = hipMemset(p->d_a, 0, nb);
-    if (e == hipSuccess) e = hipMemset(p->d_b, 0, nb);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        release(p);
-        return fail(FSEA_EHIP, "fsea_interp_create: %s", hipGetErrorString(e));
-    }
-    *out = p;
-    return FSEA_OK;
+    return fsea_detail::create_object(out, device, "fsea_interp_create", [&](fsea_interp *p) {
+        p->type = type;
+        p->n = n_elements;
+        const size_t nb = std::max<size_t>(16, n_elements * elem_bytes(type));
+        hipError_t e = p->tab.create(p->staging.stream);
+        if (e == hipSuccess) e = hipMalloc(&p->d_a, nb);
+        if (e == hipSuccess) e = hipMalloc(&p->d_b, nb);
+        if (e == hipSuccess) e = hipMemset(p->d_a, 0, nb);
+        if (e == hipSuccess) e = hipMemset(p->d_b, 0, nb);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        return e;
+    });
 }
 
-int fsea_interp_destroy(fsea_interp *p) {
-    if (!p) return FSEA_OK;
-    FSEA_ON_DEVICE(p->device);
-    FSEA_HIP(hipDeviceSynchronize());  // launches of the object on any stream may still read its blocks and tables
-    release(p);
-    return FSEA_OK;
-}
+int fsea_interp_destroy(fsea_interp *p) { return fsea_detail::destroy_object(p); }
 
 int fsea_interp_reset(fsea_interp *p) {
     if (!p) return fail(FSEA_EINVAL, "interp is NULL");
@@ -515,7 +488,8 @@ int fsea_interp_frames_device(fsea_interp *p, const double *d_weights, int n_fra
     if (rc) return rc;
     if (n_frames == 0 || p->n == 0) return FSEA_OK;
     if (!d_weights || !d_out) return fail(FSEA_EINVAL, "NULL buffer");
-    if ((uintptr_t)d_out & 15) return fail(FSEA_EINVAL, "d_out must be 16-byte aligned");
+    rc = fsea_detail::check_aligned16("d_out", d_out);
+    if (rc) return rc;
     if ((uintptr_t)d_weights & 7) return fail(FSEA_EINVAL, "d_weights must be 8-byte aligned");
     if ((size_t)n_frames > MAX_OUT / (p->n * elem_bytes(p->type))) return fail(FSEA_EINVAL, "%d frames are too many", n_frames);
     std::lock_guard<std::mutex> lock(p->mu);
@@ -543,7 +517,8 @@ int fsea_interp_image_frames_device(fsea_interp *p, const double *d_weights, int
     if (rc) return rc;
     if (n_frames == 0) return FSEA_OK;
     if (!d_weights || !d_images) return fail(FSEA_EINVAL, "NULL buffer");
-    if ((uintptr_t)d_images & 15) return fail(FSEA_EINVAL, "d_images must be 16-byte aligned");
+    rc = fsea_detail::check_aligned16("d_images", d_images);
+    if (rc) return rc;
     if ((uintptr_t)d_weights & 7) return fail(FSEA_EINVAL, "d_weights must be 8-byte aligned");
     std::lock_guard<std::mutex> lock(p->mu);
     FSEA_ON_DEVICE(p->device);

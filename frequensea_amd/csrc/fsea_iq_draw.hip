@@ -23,7 +23,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 
 using fsea_detail::coord_f64;
 using fsea_detail::DeviceGuard;
@@ -220,11 +219,9 @@ extern "C" __global__ __launch_bounds__(CLAMP_WG) void fsea_iq_clamp(const uint4
 
 struct fsea_iq_draw {
     int device = 0;
-    hipEvent_t counts_free = nullptr;  // recorded after the last launch that used d_counts
     std::mutex mu;
-    uint32_t *d_counts = nullptr;
-    size_t counts_bytes = 0;
-    fsea_detail::HostStaging staging;  // the host-buffer forms
+    fsea_detail::SharedScratch counts;  // u32 counts of the frames one rasteriser launch draws
+    fsea_detail::HostStaging staging;   // the host-buffer forms
 };
 
 namespace {
@@ -234,16 +231,9 @@ size_t pair_bytes(int type) { return type == FSEA_IQ_U8 ? 2 : type == FSEA_IQ_F3
 int check_common(const fsea_iq_draw *d, int type, size_t n, int n_frames) {
     if (!d) return fail(FSEA_EINVAL, "iq_draw is NULL");
     if (type != FSEA_IQ_U8 && type != FSEA_IQ_F32 && type != FSEA_IQ_F64) return fail(FSEA_EINVAL, "unknown input type %d", type);
-    if (n_frames < 0) return fail(FSEA_EINVAL, "n_frames must be >= 0, got %d", n_frames);
+    if (int rc = fsea_detail::check_n_frames(n_frames)) return rc;
     if (n > ((size_t)1 << 31) || (n_frames && n > MAX_ELEMS / (size_t)n_frames)) {
         return fail(FSEA_EINVAL, "%zu pairs x %d frames is too large", n, n_frames);
-    }
-    return FSEA_OK;
-}
-
-int check_multiplier(int m) {
-    if (m < 1 || m > FSEA_IQ_MAX_MULTIPLIER) {
-        return fail(FSEA_EINVAL, "size_multiplier must be in [1, %d], got %d", FSEA_IQ_MAX_MULTIPLIER, m);
     }
     return FSEA_OK;
 }
@@ -284,37 +274,33 @@ int lines_launch(fsea_iq_draw *d, const void *d_iq, int type, int flip, size_t n
         return FSEA_OK;
     }
     const size_t chunk = std::min<size_t>((size_t)n_frames, std::max<size_t>(1, LN_CHUNK_BYTES / (4 * pixels)));
-    if (d->counts_bytes < chunk * pixels * 4) {
-        FSEA_HIP(hipEventSynchronize(d->counts_free));  // no launch on any stream still uses the old buffer
-        int rc = fsea_detail::grow_device(reinterpret_cast<void **>(&d->d_counts), &d->counts_bytes, chunk * pixels * 4);
-        if (rc) return rc;
-    }
-    // every use of the count buffer, on whatever stream, follows the previous one
-    FSEA_HIP(hipStreamWaitEvent(s, d->counts_free, 0));
+    int rc = d->counts.bytes < chunk * pixels * 4 ? d->counts.reserve(chunk * pixels * 4) : FSEA_OK;
+    if (!rc) rc = d->counts.acquire(s);  // every use of the count buffer, on whatever stream, follows the previous one
+    if (rc) return rc;
+    uint32_t *d_counts = static_cast<uint32_t *>(d->counts.ptr);
     const uint32_t fm = (type == FSEA_IQ_U8 && flip) ? 0x80808080u : 0u;
     const long long n = (long long)n_points;
     const unsigned gx = (unsigned)((n_points - 1 + LN_WG - 1) / LN_WG);
     for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += chunk) {
         const size_t nf = std::min(chunk, (size_t)n_frames - f0);
-        FSEA_HIP(hipMemsetAsync(d->d_counts, 0, nf * pixels * 4, s));
+        FSEA_HIP(hipMemsetAsync(d_counts, 0, nf * pixels * 4, s));
         const dim3 grid(gx, (unsigned)nf);
         const long long fr = (long long)f0;
         if (type == FSEA_IQ_U8) {
-            hipLaunchKernelGGL(fsea_iq_lines_u8, grid, dim3(LN_WG), 0, s, d_iq, n, fm, m, fr, d->d_counts);
+            hipLaunchKernelGGL(fsea_iq_lines_u8, grid, dim3(LN_WG), 0, s, d_iq, n, fm, m, fr, d_counts);
         } else if (type == FSEA_IQ_F32) {
-            hipLaunchKernelGGL(fsea_iq_lines_f32, grid, dim3(LN_WG), 0, s, d_iq, n, fm, m, fr, d->d_counts);
+            hipLaunchKernelGGL(fsea_iq_lines_f32, grid, dim3(LN_WG), 0, s, d_iq, n, fm, m, fr, d_counts);
         } else {
-            hipLaunchKernelGGL(fsea_iq_lines_f64, grid, dim3(LN_WG), 0, s, d_iq, n, fm, m, fr, d->d_counts);
+            hipLaunchKernelGGL(fsea_iq_lines_f64, grid, dim3(LN_WG), 0, s, d_iq, n, fm, m, fr, d_counts);
         }
         FSEA_HIP(hipGetLastError());
         const long long n16 = (long long)(nf * pixels / 16);
         hipLaunchKernelGGL(fsea_iq_clamp, dim3((unsigned)((n16 + CLAMP_WG - 1) / CLAMP_WG)), dim3(CLAMP_WG), 0, s,
-                           reinterpret_cast<const uint4 *>(d->d_counts), n16,
+                           reinterpret_cast<const uint4 *>(d_counts), n16,
                            reinterpret_cast<uint4 *>(static_cast<uint8_t *>(d_image) + f0 * pixels));
         FSEA_HIP(hipGetLastError());
     }
-    FSEA_HIP(hipEventRecord(d->counts_free, s));
-    return FSEA_OK;
+    return d->counts.release(s);
 }
 
 // the host-buffer forms: the launches through the object's staging (fsea_detail::HostStaging)
@@ -331,13 +317,6 @@ int draw_host(fsea_iq_draw *d, bool lines, const void *iq, int type, int flip, s
         });
 }
 
-void release(fsea_iq_draw *d) {
-    if (d->d_counts) (void)hipFree(d->d_counts);
-    if (d->counts_free) (void)hipEventDestroy(d->counts_free);
-    d->staging.release();
-    delete d;
-}
-
 }  // namespace
 
 extern "C" {
@@ -345,30 +324,11 @@ extern "C" {
 int fsea_iq_draw_create(fsea_iq_draw **out, int device) {
     if (!out) return fail(FSEA_EINVAL, "iq_draw out-pointer is NULL");
     *out = nullptr;
-    int rc = fsea_detail::check_device(device);
-    if (rc) return rc;
-    FSEA_ON_DEVICE(device);
-    fsea_iq_draw *d = new (std::nothrow) fsea_iq_draw();
-    if (!d) return fail(FSEA_ENOMEM, "out of host memory");
-    d->device = device;
-    hipError_t e = d->staging.create();
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->counts_free, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(d->counts_free, d->staging.stream);
-    if (e != hipSuccess) {
-        release(d);
-        return fail(FSEA_EHIP, "fsea_iq_draw_create: %s", hipGetErrorString(e));
-    }
-    *out = d;
-    return FSEA_OK;
+    return fsea_detail::create_object(out, device, "fsea_iq_draw_create",
+                                      [](fsea_iq_draw *d) { return d->counts.create(d->staging.stream); });
 }
 
-int fsea_iq_draw_destroy(fsea_iq_draw *d) {
-    if (!d) return FSEA_OK;
-    FSEA_ON_DEVICE(d->device);
-    FSEA_HIP(hipDeviceSynchronize());  // launches of the object on any stream may still use its count buffer
-    release(d);
-    return FSEA_OK;
-}
+int fsea_iq_draw_destroy(fsea_iq_draw *d) { return fsea_detail::destroy_object(d); }
 
 int fsea_iq_points_device(fsea_iq_draw *d, const void *d_iq, int type, int flip, size_t n_pairs, int n_frames,
                           void *d_image, void *stream) {
@@ -376,7 +336,8 @@ int fsea_iq_points_device(fsea_iq_draw *d, const void *d_iq, int type, int flip,
     if (rc) return rc;
     if (n_frames == 0) return FSEA_OK;
     if ((n_pairs && !d_iq) || !d_image) return fail(FSEA_EINVAL, "NULL buffer");
-    if (((uintptr_t)d_iq | (uintptr_t)d_image) & 15) return fail(FSEA_EINVAL, "d_iq and d_image must be 16-byte aligned");
+    rc = fsea_detail::check_aligned16("d_iq and d_image", d_iq, d_image);
+    if (rc) return rc;
     std::lock_guard<std::mutex> lock(d->mu);
     FSEA_ON_DEVICE(d->device);
     return points_launch(d, d_iq, type, flip, n_pairs, n_frames, d_image, static_cast<hipStream_t>(stream));
@@ -385,11 +346,12 @@ int fsea_iq_points_device(fsea_iq_draw *d, const void *d_iq, int type, int flip,
 int fsea_iq_lines_device(fsea_iq_draw *d, const void *d_iq, int type, int flip, size_t n_points, int n_frames,
                          int size_multiplier, void *d_image, void *stream) {
     int rc = check_common(d, type, n_points, n_frames);
-    if (!rc) rc = check_multiplier(size_multiplier);
+    if (!rc) rc = fsea_detail::check_multiplier(size_multiplier);
     if (rc) return rc;
     if (n_frames == 0) return FSEA_OK;
     if ((n_points && !d_iq) || !d_image) return fail(FSEA_EINVAL, "NULL buffer");
-    if (((uintptr_t)d_iq | (uintptr_t)d_image) & 15) return fail(FSEA_EINVAL, "d_iq and d_image must be 16-byte aligned");
+    rc = fsea_detail::check_aligned16("d_iq and d_image", d_iq, d_image);
+    if (rc) return rc;
     std::lock_guard<std::mutex> lock(d->mu);
     FSEA_ON_DEVICE(d->device);
     return lines_launch(d, d_iq, type, flip, n_points, n_frames, size_multiplier, d_image, static_cast<hipStream_t>(stream));
@@ -405,7 +367,7 @@ int fsea_iq_points_host(fsea_iq_draw *d, const void *iq, int type, int flip, siz
 int fsea_iq_lines_host(fsea_iq_draw *d, const void *iq, int type, int flip, size_t n_points, int size_multiplier,
                        uint8_t *image) {
     int rc = check_common(d, type, n_points, 1);
-    if (!rc) rc = check_multiplier(size_multiplier);
+    if (!rc) rc = fsea_detail::check_multiplier(size_multiplier);
     if (rc) return rc;
     if ((n_points && !iq) || !image) return fail(FSEA_EINVAL, "NULL buffer");
     return draw_host(d, true, iq, type, flip, n_points, size_multiplier, image);

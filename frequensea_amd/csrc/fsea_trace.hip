@@ -25,7 +25,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 
 using fsea_detail::DeviceGuard;
 using fsea_detail::fail;
@@ -235,10 +234,12 @@ struct fsea_trace {
     std::mutex mu;
     uint8_t *d_canvas = nullptr;       // width x height bytes, padded to a whole 16-byte group
     size_t canvas_bytes = 0;
-    uint8_t *d_counts = nullptr;       // the count planes of one chunk
-    size_t counts_bytes = 0;
-    hipEvent_t busy = nullptr;         // recorded after the last work that used the canvas and the count planes
-    fsea_detail::HostStaging staging;  // the host-buffer forms
+    fsea_detail::SharedScratch counts;  // the count planes of one chunk; its event orders the uses of the canvas too
+    fsea_detail::HostStaging staging;   // the host-buffer forms
+
+    ~fsea_trace() {
+        if (d_canvas) (void)hipFree(d_canvas);
+    }
 };
 
 namespace {
@@ -251,7 +252,7 @@ int check_frames(const fsea_trace *t, const void *bytes, size_t n_bytes, size_t 
     if (frame_bytes == 0 || frame_bytes > TR_MAX_FRAME_BYTES) {
         return fail(FSEA_EINVAL, "frame_bytes must be in [1, 2^31], got %zu", frame_bytes);
     }
-    if (n_frames < 0) return fail(FSEA_EINVAL, "n_frames must be >= 0, got %d", n_frames);
+    if (int rc = fsea_detail::check_n_frames(n_frames)) return rc;
     if (n_bytes && !bytes) return fail(FSEA_EINVAL, "NULL buffer");
     return FSEA_OK;
 }
@@ -270,13 +271,10 @@ int frames_launch(fsea_trace *t, const uint8_t *d_bytes, size_t n_bytes, int fli
     const int cb = segments <= 255 ? 1 : 4;
     const size_t plane = (size_t)g.side * g.side * cb;
     const size_t chunk = std::min<size_t>({(size_t)n_frames, (size_t)TR_MAX_CHUNK, std::max<size_t>(1, TR_COUNT_BYTES / plane)});
-    if (t->counts_bytes < chunk * plane) {
-        FSEA_HIP(hipEventSynchronize(t->busy));  // no launch on any stream still uses the old planes
-        int rc = fsea_detail::grow_device(reinterpret_cast<void **>(&t->d_counts), &t->counts_bytes, chunk * plane);
-        if (rc) return rc;
-    }
-    // every use of the canvas and the planes, on whatever stream, follows the previous one
-    FSEA_HIP(hipStreamWaitEvent(s, t->busy, 0));
+    int rc = t->counts.bytes < chunk * plane ? t->counts.reserve(chunk * plane) : FSEA_OK;
+    if (!rc) rc = t->counts.acquire(s);  // every use of the canvas and the planes, on whatever stream, follows the previous one
+    if (rc) return rc;
+    uint8_t *d_counts = static_cast<uint8_t *>(t->counts.ptr);
     const size_t pixels = frame_pixels(t);
     const unsigned gx_hits = (unsigned)((segments + TR_WG - 1) / TR_WG);
     const unsigned gx_compose = (unsigned)(((pixels + 15) / 16 + TR_WG - 1) / TR_WG);
@@ -284,18 +282,18 @@ int frames_launch(fsea_trace *t, const uint8_t *d_bytes, size_t n_bytes, int fli
     const uint32_t fm = flip ? 0x80u : 0u;
     for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += chunk) {
         const int nf = (int)std::min(chunk, (size_t)n_frames - f0);
-        FSEA_HIP(hipMemsetAsync(t->d_counts, 0, (size_t)nf * plane, s));
+        FSEA_HIP(hipMemsetAsync(d_counts, 0, (size_t)nf * plane, s));
         const size_t first = f0 * frame_bytes;
         if (segments && first < n_bytes) {
             const dim3 grid(gx_hits, (unsigned)nf);
             const long long left = (long long)(n_bytes - first), fb = (long long)frame_bytes;
-            uint32_t *counts = reinterpret_cast<uint32_t *>(t->d_counts);
+            uint32_t *counts = reinterpret_cast<uint32_t *>(d_counts);
             if (cb == 1) hipLaunchKernelGGL(fsea_trace_hits_b8, grid, dim3(TR_WG), 0, s, d_bytes + first, left, fb, fm, g, counts);
             else hipLaunchKernelGGL(fsea_trace_hits_b32, grid, dim3(TR_WG), 0, s, d_bytes + first, left, fb, fm, g, counts);
             FSEA_HIP(hipGetLastError());
         }
         uint8_t *images = d_images ? d_images + f0 * pixels : nullptr;
-        const uint8_t *counts = t->d_counts;
+        const uint8_t *counts = d_counts;
         const dim3 grid(gx_compose);
         if (aligned && cb == 1) hipLaunchKernelGGL(fsea_trace_compose_b8, grid, dim3(TR_WG), 0, s, counts, nf, g, t->d_canvas, images);
         else if (aligned) hipLaunchKernelGGL(fsea_trace_compose_b32, grid, dim3(TR_WG), 0, s, counts, nf, g, t->d_canvas, images);
@@ -303,16 +301,7 @@ int frames_launch(fsea_trace *t, const uint8_t *d_bytes, size_t n_bytes, int fli
         else hipLaunchKernelGGL(fsea_trace_compose_b32_any, grid, dim3(TR_WG), 0, s, counts, nf, g, t->d_canvas, images);
         FSEA_HIP(hipGetLastError());
     }
-    FSEA_HIP(hipEventRecord(t->busy, s));
-    return FSEA_OK;
-}
-
-void release(fsea_trace *t) {
-    if (t->d_canvas) (void)hipFree(t->d_canvas);
-    if (t->d_counts) (void)hipFree(t->d_counts);
-    if (t->busy) (void)hipEventDestroy(t->busy);
-    t->staging.release();
-    delete t;
+    return t->counts.release(s);
 }
 
 }  // namespace
@@ -324,53 +313,35 @@ int fsea_trace_create(fsea_trace **out, const fsea_trace_config *cfg, int device
     *out = nullptr;
     if (!cfg) return fail(FSEA_EINVAL, "trace config is NULL");
     const int m = cfg->size_multiplier;
-    if (m < 1 || m > FSEA_IQ_MAX_MULTIPLIER) {
-        return fail(FSEA_EINVAL, "size_multiplier must be in [1, %d], got %d", FSEA_IQ_MAX_MULTIPLIER, m);
-    }
+    int rc = fsea_detail::check_multiplier(m);
+    if (rc) return rc;
     if (cfg->width > TR_MAX_SIDE || cfg->height > TR_MAX_SIDE || IQ_RES * m > cfg->width || IQ_RES * m > cfg->height) {
         return fail(FSEA_EINVAL, "a %d x %d canvas does not hold the %d x %d IQ square (or is larger than %d)", cfg->width,
                     cfg->height, IQ_RES * m, IQ_RES * m, TR_MAX_SIDE);
     }
     if (cfg->pixel_inc < 1 || cfg->pixel_inc > 254) return fail(FSEA_EINVAL, "pixel_inc must be in [1, 254], got %d", cfg->pixel_inc);
     if (cfg->fade < 0 || cfg->fade > 255) return fail(FSEA_EINVAL, "fade must be in [0, 255], got %d", cfg->fade);
-    int rc = fsea_detail::check_device(device);
-    if (rc) return rc;
-    FSEA_ON_DEVICE(device);
-    fsea_trace *t = new (std::nothrow) fsea_trace();
-    if (!t) return fail(FSEA_ENOMEM, "out of host memory");
-    t->device = device;
-    TraceGeo &g = t->g;
-    g.width = cfg->width;
-    g.height = cfg->height;
-    g.m = m;
-    g.side = IQ_RES * m;
-    g.ox = (g.width - g.side) / 2;
-    g.oy = (g.height - g.side) / 2;
-    g.inc = cfg->pixel_inc;
-    g.fade = cfg->fade;
-    g.magic = (65536u + (uint32_t)g.inc - 1u) / (uint32_t)g.inc;
-    t->canvas_bytes = (frame_pixels(t) + 15) & ~(size_t)15;
-    hipError_t e = t->staging.create();
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->busy, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(t->busy, t->staging.stream);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_canvas), t->canvas_bytes);
-    if (e == hipSuccess) e = hipMemset(t->d_canvas, 0, t->canvas_bytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        release(t);
-        return fail(FSEA_EHIP, "fsea_trace_create: %s", hipGetErrorString(e));
-    }
-    *out = t;
-    return FSEA_OK;
+    return fsea_detail::create_object(out, device, "fsea_trace_create", [&](fsea_trace *t) {
+        TraceGeo &g = t->g;
+        g.width = cfg->width;
+        g.height = cfg->height;
+        g.m = m;
+        g.side = IQ_RES * m;
+        g.ox = (g.width - g.side) / 2;
+        g.oy = (g.height - g.side) / 2;
+        g.inc = cfg->pixel_inc;
+        g.fade = cfg->fade;
+        g.magic = (65536u + (uint32_t)g.inc - 1u) / (uint32_t)g.inc;
+        t->canvas_bytes = (frame_pixels(t) + 15) & ~(size_t)15;
+        hipError_t e = t->counts.create(t->staging.stream);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_canvas), t->canvas_bytes);
+        if (e == hipSuccess) e = hipMemset(t->d_canvas, 0, t->canvas_bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        return e;
+    });
 }
 
-int fsea_trace_destroy(fsea_trace *t) {
-    if (!t) return FSEA_OK;
-    FSEA_ON_DEVICE(t->device);
-    FSEA_HIP(hipDeviceSynchronize());  // launches of the object on any stream may still use its canvas and planes
-    release(t);
-    return FSEA_OK;
-}
+int fsea_trace_destroy(fsea_trace *t) { return fsea_detail::destroy_object(t); }
 
 int fsea_trace_reset(fsea_trace *t) {
     if (!t) return fail(FSEA_EINVAL, "trace is NULL");
@@ -385,9 +356,8 @@ int fsea_trace_reset(fsea_trace *t) {
 int fsea_trace_frames_device(fsea_trace *t, const void *d_bytes, size_t n_bytes, int flip, size_t frame_bytes, int n_frames,
                              uint8_t *d_images, void *stream) {
     int rc = check_frames(t, d_bytes, n_bytes, frame_bytes, n_frames);
-    if (rc) return rc;
-    if ((uintptr_t)d_images & 15) return fail(FSEA_EINVAL, "d_images must be 16-byte aligned");
-    rc = check_output(t, n_frames);
+    if (!rc) rc = fsea_detail::check_aligned16("d_images", d_images);
+    if (!rc) rc = check_output(t, n_frames);
     if (rc) return rc;
     if (n_frames == 0) return FSEA_OK;
     std::lock_guard<std::mutex> lock(t->mu);
@@ -423,10 +393,10 @@ int fsea_trace_canvas_host(fsea_trace *t, uint8_t *image) {
     return t->staging.run(
         0, pixels, image, [](void *) {},
         [&](void *, void *d_out, hipStream_t s) {
-            FSEA_HIP(hipStreamWaitEvent(s, t->busy, 0));
+            int rc = t->counts.acquire(s);
+            if (rc) return rc;
             FSEA_HIP(hipMemcpyAsync(d_out, t->d_canvas, pixels, hipMemcpyDeviceToDevice, s));
-            FSEA_HIP(hipEventRecord(t->busy, s));
-            return (int)FSEA_OK;
+            return t->counts.release(s);
         });
 }
 

@@ -22,42 +22,12 @@ _MODE_DTYPE = {
     MODE_COMPLEX_F32: np.complex64, MODE_MAG_NODC_F32: np.float32, MODE_DB_F32: np.float32,
 }
 
-# Every symbol include/fsea.h declares; tests check the built library exports all of them.
-EXPORTS = [
-    "fsea_device_count", "fsea_plan_create", "fsea_plan_destroy", "fsea_plan_reset", "fsea_plan_release_stream",
-    "fsea_plan_grid", "fsea_plan_row_bytes", "fsea_plan_fft_size", "fsea_exec_u8_device", "fsea_exec_u8_tiled_device", "fsea_plan_set_unit_distribution",
-    "fsea_exec_u8_host", "fsea_exec_f64_host", "fsea_exec_u8_shifted_device", "fsea_exec_u8_shifted_host", "fsea_mean_magnitude_u8_device",
-    "fsea_composite_max_device", "fsea_stitch_tiles_device", "fsea_device_alloc", "fsea_device_free", "fsea_copy_to_device",
-    "fsea_copy_to_host", "fsea_stream_synchronize", "fsea_host_alloc", "fsea_host_free",
-    "fsea_plan_kernel_name", "fsea_last_error_string",
-    "fsea_history_create", "fsea_history_destroy", "fsea_history_push_u8_host", "fsea_history_push_f64_host",
-    "fsea_history_shift", "fsea_history_get_f64",
-    "fsea_plan_set_window", "fsea_plan_window_form", "fsea_window_fill",
-    "fsea_stream_create", "fsea_stream_destroy", "fsea_copy_to_device_async", "fsea_copy_to_host_async",
-    "fsea_fir_lowpass_taps", "fsea_fir_create", "fsea_fir_destroy", "fsea_fir_reset", "fsea_fir_n_taps",
-    "fsea_fir_u8_device", "fsea_fir_u8_host", "fsea_fir_f64_host", "fsea_fir_u8_shifted_device", "fsea_fir_u8_shifted_host",
-    "fsea_chain_create", "fsea_chain_destroy", "fsea_chain_reset", "fsea_chain_n_pairs", "fsea_chain_run_host",
-    "fsea_chain_run_f64_host", "fsea_chain_fetch_host", "fsea_chain_run_device",
-    "fsea_iq_draw_create", "fsea_iq_draw_destroy", "fsea_iq_points_device", "fsea_iq_lines_device",
-    "fsea_iq_points_host", "fsea_iq_lines_host",
-    "fsea_demod_create", "fsea_demod_destroy", "fsea_demod_reset", "fsea_demod_set_channel", "fsea_demod_get_channel",
-    "fsea_demod_out_length", "fsea_demod_u8_device", "fsea_demod_u8_host", "fsea_demod_f64_host",
-    "fsea_interp_create", "fsea_interp_destroy", "fsea_interp_reset", "fsea_interp_n_elements", "fsea_interp_push_device",
-    "fsea_interp_push_host", "fsea_interp_frames_device", "fsea_interp_frames_host", "fsea_interp_image_tables",
-    "fsea_interp_image_frames_device", "fsea_interp_image_frames_host",
-    "fsea_trace_create", "fsea_trace_destroy", "fsea_trace_reset", "fsea_trace_frames_device", "fsea_trace_frames_host",
-    "fsea_trace_canvas_host",
-]
 FIR_MAX_TAPS = 512          # FSEA_FIR_MAX_TAPS (include/fsea.h)
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
 DEMOD_MAX_CHANNELS = 256            # FSEA_DEMOD_MAX_CHANNELS
 DEMOD_MAX_SAMPLES = 1 << 24         # FSEA_DEMOD_MAX_SAMPLES
-# include/fsea_tune.h: only libfsea_hip_tune.so (scripts/tune.py and friends) has these
-TUNE_EXPORTS = ["fsea_plan_create_variant", "fsea_time_exec_u8_device", "fsea_time_exec_u8_rotating",
-                "fsea_plan_read_trace", "fsea_tune_stream_1to2"]
-
 
 class InterpGeometry(ctypes.Structure):
     """fsea_interp_geometry (include/fsea.h)."""
@@ -80,6 +50,128 @@ class ChainOutputs(ctypes.Structure):
     """fsea_chain_outputs (include/fsea.h)."""
     _fields_ = [("points", ctypes.c_void_p), ("lines", ctypes.c_void_p), ("size_multiplier", ctypes.c_int),
                 ("n_line_points", ctypes.c_size_t), ("pairs", ctypes.c_void_p)]
+
+
+# Every function include/fsea.h declares, once: name -> (restype, argtypes).  hip_lib() applies the table, EXPORTS is its
+# names; tests check both against the header and the built library.
+_vp, _sz, _ci, _f64, _u32, _u64, _str = (ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double, ctypes.c_uint32,
+                                         ctypes.c_uint64, ctypes.c_char_p)
+_out = ctypes.POINTER(_vp)        # where a create / alloc function puts its handle
+_f32p, _uip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint)
+_stage, _outputs, _geo = ctypes.POINTER(ChainStage), ctypes.POINTER(ChainOutputs), ctypes.POINTER(InterpGeometry)
+API = {
+    "fsea_device_count": (_ci, [ctypes.POINTER(_ci)]),
+    "fsea_last_error_string": (_str, []),
+    "fsea_plan_create": (_ci, [_out, _ci, _ci, _ci, _ci]),
+    "fsea_plan_destroy": (_ci, [_vp]),
+    "fsea_plan_reset": (_ci, [_vp]),
+    "fsea_plan_release_stream": (_ci, [_vp, _vp]),
+    "fsea_plan_grid": (_ci, [_vp, _sz, _uip, _uip, ctypes.POINTER(_sz)]),
+    "fsea_plan_row_bytes": (_sz, [_vp]),
+    "fsea_plan_fft_size": (_ci, [_vp]),
+    "fsea_plan_kernel_name": (_str, [_vp]),
+    "fsea_plan_set_unit_distribution": (_ci, [_vp, _ci]),
+    "fsea_plan_set_window": (_ci, [_vp, _vp]),
+    "fsea_plan_window_form": (_ci, [_vp]),
+    "fsea_window_fill": (_ci, [_ci, _ci, _vp]),
+    "fsea_exec_u8_device": (_ci, [_vp, _vp, _sz, _ci, _vp, _vp]),
+    "fsea_exec_u8_tiled_device": (_ci, [_vp, _vp, _sz, _ci, _vp, _sz, _sz, _sz, _sz, _sz, _vp]),
+    "fsea_exec_u8_host": (_ci, [_vp, _vp, _sz, _ci, _vp]),
+    "fsea_exec_f64_host": (_ci, [_vp, _vp, _sz, _vp]),
+    "fsea_exec_u8_shifted_device": (_ci, [_vp, _vp, _sz, _ci, _f64, _f64, _vp, _vp]),
+    "fsea_exec_u8_shifted_host": (_ci, [_vp, _vp, _sz, _ci, _f64, _f64, _vp]),
+    "fsea_mean_magnitude_u8_device": (_ci, [_vp, _vp, _sz, _ci, ctypes.POINTER(_f64), _vp]),
+    "fsea_composite_max_device": (_ci, [_vp, _vp] + [_u32] * 7 + [_ci, _vp]),
+    "fsea_stitch_tiles_device": (_ci, [_vp, _vp] + [_u32] * 6 + [_ci, _vp]),
+    "fsea_device_alloc": (_ci, [_ci, _sz, _out]),
+    "fsea_device_free": (_ci, [_ci, _vp]),
+    "fsea_copy_to_device": (_ci, [_ci, _vp, _vp, _sz]),
+    "fsea_copy_to_host": (_ci, [_ci, _vp, _vp, _sz]),
+    "fsea_stream_create": (_ci, [_ci, _out]),
+    "fsea_stream_destroy": (_ci, [_ci, _vp]),
+    "fsea_stream_synchronize": (_ci, [_vp, _vp]),
+    "fsea_copy_to_device_async": (_ci, [_ci, _vp, _vp, _sz, _vp]),
+    "fsea_copy_to_host_async": (_ci, [_ci, _vp, _vp, _sz, _vp]),
+    "fsea_host_alloc": (_ci, [_sz, _out]),
+    "fsea_host_free": (_ci, [_vp]),
+    "fsea_history_create": (_ci, [_vp, _ci, _out]),
+    "fsea_history_destroy": (_ci, [_vp]),
+    "fsea_history_push_u8_host": (_ci, [_vp, _vp, _ci]),
+    "fsea_history_push_f64_host": (_ci, [_vp, _vp]),
+    "fsea_history_shift": (_ci, [_vp, _ci]),
+    "fsea_history_get_f64": (_ci, [_vp, _vp]),
+    "fsea_fir_lowpass_taps": (_ci, [_f64, _f64, _ci, _vp]),
+    "fsea_fir_create": (_ci, [_out, _vp, _ci, _ci]),
+    "fsea_fir_destroy": (_ci, [_vp]),
+    "fsea_fir_reset": (_ci, [_vp]),
+    "fsea_fir_n_taps": (_ci, [_vp]),
+    "fsea_fir_u8_device": (_ci, [_vp, _vp, _sz, _ci, _vp, _vp]),
+    "fsea_fir_u8_host": (_ci, [_vp, _vp, _sz, _ci, _vp]),
+    "fsea_fir_f64_host": (_ci, [_vp, _vp, _sz, _vp]),
+    "fsea_fir_u8_shifted_device": (_ci, [_vp, _vp, _sz, _ci, _f64, _f64, _u64, _vp, _vp]),
+    "fsea_fir_u8_shifted_host": (_ci, [_vp, _vp, _sz, _ci, _f64, _f64, _u64, _vp]),
+    "fsea_chain_create": (_ci, [_out, _vp, _ci, _ci]),
+    "fsea_chain_destroy": (_ci, [_vp]),
+    "fsea_chain_reset": (_ci, [_vp]),
+    "fsea_chain_n_pairs": (_sz, [_vp]),
+    "fsea_chain_run_host": (_ci, [_vp, _vp, _sz, _stage, _outputs]),
+    "fsea_chain_run_f64_host": (_ci, [_vp, _vp, _sz, _outputs]),
+    "fsea_chain_fetch_host": (_ci, [_vp, _outputs]),
+    "fsea_chain_run_device": (_ci, [_vp, _vp, _sz, _ci, _stage, _outputs, _vp]),
+    "fsea_iq_draw_create": (_ci, [_out, _ci]),
+    "fsea_iq_draw_destroy": (_ci, [_vp]),
+    "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
+    "fsea_iq_lines_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _ci, _vp, _vp]),
+    "fsea_iq_points_host": (_ci, [_vp, _vp, _ci, _ci, _sz, _vp]),
+    "fsea_iq_lines_host": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp]),
+    "fsea_demod_create": (_ci, [_out, _ci, _ci, _ci, _ci, _ci]),
+    "fsea_demod_destroy": (_ci, [_vp]),
+    "fsea_demod_reset": (_ci, [_vp]),
+    "fsea_demod_set_channel": (_ci, [_vp, _ci, _ci, _f64, _f64]),
+    "fsea_demod_get_channel": (_ci, [_vp, _ci, ctypes.POINTER(_ci), ctypes.POINTER(_f64), ctypes.POINTER(_f64)]),
+    "fsea_demod_out_length": (_sz, [_vp, _sz]),
+    "fsea_demod_u8_device": (_ci, [_vp, _vp, _sz, _ci, _vp, _vp]),
+    "fsea_demod_u8_host": (_ci, [_vp, _vp, _sz, _ci, _vp]),
+    "fsea_demod_f64_host": (_ci, [_vp, _vp, _vp, _sz, _vp]),
+    "fsea_interp_create": (_ci, [_out, _ci, _sz, _ci]),
+    "fsea_interp_destroy": (_ci, [_vp]),
+    "fsea_interp_reset": (_ci, [_vp]),
+    "fsea_interp_n_elements": (_sz, [_vp]),
+    "fsea_interp_push_device": (_ci, [_vp, _vp, _vp]),
+    "fsea_interp_push_host": (_ci, [_vp, _vp]),
+    "fsea_interp_frames_device": (_ci, [_vp, _vp, _ci, _vp, _vp]),
+    "fsea_interp_frames_host": (_ci, [_vp, _vp, _ci, _vp]),
+    "fsea_interp_image_tables": (_ci, [_ci, _ci, _ci, _vp, _vp]),
+    "fsea_interp_image_frames_device": (_ci, [_vp, _vp, _ci, _geo, _vp, _vp]),
+    "fsea_interp_image_frames_host": (_ci, [_vp, _vp, _ci, _geo, _vp]),
+    "fsea_trace_create": (_ci, [_out, ctypes.POINTER(TraceConfig), _ci]),
+    "fsea_trace_destroy": (_ci, [_vp]),
+    "fsea_trace_reset": (_ci, [_vp]),
+    "fsea_trace_frames_device": (_ci, [_vp, _vp, _sz, _ci, _sz, _ci, _vp, _vp]),
+    "fsea_trace_frames_host": (_ci, [_vp, _vp, _sz, _ci, _sz, _ci, _vp]),
+    "fsea_trace_canvas_host": (_ci, [_vp, _vp]),
+}
+# include/fsea_tune.h: only libfsea_hip_tune.so (scripts/tune.py and friends) has these
+TUNE_API = {
+    "fsea_plan_create_variant": (_ci, [_out, _ci, _ci, _ci, _ci, _str]),
+    "fsea_time_exec_u8_device": (_ci, [_vp, _vp, _sz, _ci, _vp, _vp, _ci, _f32p]),
+    "fsea_time_exec_u8_rotating": (_ci, [_vp, _out, _out, _ci, _sz, _ci, _vp, _ci, _f32p]),
+    "fsea_plan_read_trace": (_ci, [_vp, _vp, ctypes.c_uint]),
+    "fsea_tune_stream_1to2": (_ci, [_out, _out, _ci, _sz, _ci, _vp, _ci, _f32p]),
+}
+EXPORTS, TUNE_EXPORTS = list(API), list(TUNE_API)
+
+
+def declare(L, names=None):
+    """Attach restype and argtypes to the functions of a loaded build of the library: the one place they are assigned.
+    Without names: all of include/fsea.h, and of include/fsea_tune.h where the build is the tuning library.  With names:
+    those only (a script that loads another build of the library, which may not have every function)."""
+    if names is None:
+        names = EXPORTS + (TUNE_EXPORTS if hasattr(L, "fsea_plan_create_variant") else [])
+    for name in names:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = API[name] if name in API else TUNE_API[name]
+    return L
 
 
 class FseaError(RuntimeError):
@@ -125,111 +217,7 @@ def hip_lib():
         path = lib_path()
         if not os.path.exists(path):
             raise FseaError("libfsea_hip.so is missing: run frequensea_amd.build() / __graft_entry__.build()")
-        L = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-        vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-        L.fsea_last_error_string.restype = ctypes.c_char_p
-        L.fsea_device_count.argtypes = [ctypes.POINTER(ci)]
-        L.fsea_plan_create.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci]
-        L.fsea_plan_reset.argtypes = [vp]
-        L.fsea_plan_release_stream.argtypes = [vp, vp]
-        L.fsea_history_create.argtypes = [vp, ci, ctypes.POINTER(vp)]
-        L.fsea_history_destroy.argtypes = [vp]
-        L.fsea_history_push_u8_host.argtypes = [vp, vp, ci]
-        L.fsea_history_push_f64_host.argtypes = [vp, vp]
-        L.fsea_history_shift.argtypes = [vp, ci]
-        L.fsea_history_get_f64.argtypes = [vp, vp]
-        if hasattr(L, "fsea_plan_create_variant"):     # the tuning library
-            L.fsea_plan_create_variant.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci, ctypes.c_char_p]
-            L.fsea_time_exec_u8_device.argtypes = [vp, vp, sz, ci, vp, vp, ci, ctypes.POINTER(ctypes.c_float)]
-            L.fsea_plan_read_trace.argtypes = [vp, vp, ctypes.c_uint]
-            L.fsea_tune_stream_1to2.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ci, sz, ci, vp, ci,
-                                                ctypes.POINTER(ctypes.c_float)]
-            L.fsea_time_exec_u8_rotating.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ci, sz, ci, vp, ci,
-                                                     ctypes.POINTER(ctypes.c_float)]
-        L.fsea_plan_destroy.argtypes = [vp]
-        L.fsea_plan_grid.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
-                                     ctypes.POINTER(sz)]
-        L.fsea_plan_row_bytes.argtypes = [vp]
-        L.fsea_plan_row_bytes.restype = sz
-        L.fsea_plan_fft_size.argtypes = [vp]
-        L.fsea_plan_kernel_name.argtypes = [vp]
-        L.fsea_plan_kernel_name.restype = ctypes.c_char_p
-        L.fsea_exec_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
-        L.fsea_exec_u8_tiled_device.argtypes = [vp, vp, sz, ci, vp, sz, sz, sz, sz, sz, vp]
-        L.fsea_plan_set_unit_distribution.argtypes = [vp, ci]
-        L.fsea_exec_u8_host.argtypes = [vp, vp, sz, ci, vp]
-        L.fsea_exec_f64_host.argtypes = [vp, vp, sz, vp]
-        L.fsea_exec_u8_shifted_device.argtypes = [vp, vp, sz, ci, ctypes.c_double, ctypes.c_double, vp, vp]
-        L.fsea_exec_u8_shifted_host.argtypes = [vp, vp, sz, ci, ctypes.c_double, ctypes.c_double, vp]
-        L.fsea_mean_magnitude_u8_device.argtypes = [vp, vp, sz, ci, ctypes.POINTER(ctypes.c_double), vp]
-        L.fsea_composite_max_device.argtypes = [vp, vp] + [ctypes.c_uint32] * 7 + [ci, vp]
-        L.fsea_stitch_tiles_device.argtypes = [vp, vp] + [ctypes.c_uint32] * 6 + [ci, vp]
-        L.fsea_device_alloc.argtypes = [ci, sz, ctypes.POINTER(vp)]
-        L.fsea_device_free.argtypes = [ci, vp]
-        L.fsea_copy_to_device.argtypes = [ci, vp, vp, sz]
-        L.fsea_copy_to_host.argtypes = [ci, vp, vp, sz]
-        L.fsea_stream_synchronize.argtypes = [vp, vp]
-        L.fsea_host_alloc.argtypes = [sz, ctypes.POINTER(vp)]
-        L.fsea_host_free.argtypes = [vp]
-        L.fsea_plan_set_window.argtypes = [vp, vp]
-        L.fsea_plan_window_form.argtypes = [vp]
-        L.fsea_window_fill.argtypes = [ci, ci, vp]
-        L.fsea_fir_lowpass_taps.argtypes = [ctypes.c_double, ctypes.c_double, ci, vp]
-        L.fsea_fir_create.argtypes = [ctypes.POINTER(vp), vp, ci, ci]
-        L.fsea_fir_destroy.argtypes = [vp]
-        L.fsea_fir_reset.argtypes = [vp]
-        L.fsea_fir_n_taps.argtypes = [vp]
-        L.fsea_fir_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
-        L.fsea_fir_u8_host.argtypes = [vp, vp, sz, ci, vp]
-        L.fsea_fir_f64_host.argtypes = [vp, vp, sz, vp]
-        L.fsea_fir_u8_shifted_device.argtypes = [vp, vp, sz, ci, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, vp, vp]
-        L.fsea_fir_u8_shifted_host.argtypes = [vp, vp, sz, ci, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, vp]
-        stp, outp = ctypes.POINTER(ChainStage), ctypes.POINTER(ChainOutputs)
-        L.fsea_chain_create.argtypes = [ctypes.POINTER(vp), vp, ci, ci]
-        L.fsea_chain_destroy.argtypes = [vp]
-        L.fsea_chain_reset.argtypes = [vp]
-        L.fsea_chain_n_pairs.argtypes = [vp]
-        L.fsea_chain_n_pairs.restype = sz
-        L.fsea_chain_run_host.argtypes = [vp, vp, sz, stp, outp]
-        L.fsea_chain_run_f64_host.argtypes = [vp, vp, sz, outp]
-        L.fsea_chain_fetch_host.argtypes = [vp, outp]
-        L.fsea_chain_run_device.argtypes = [vp, vp, sz, ci, stp, outp, vp]
-        L.fsea_iq_draw_create.argtypes = [ctypes.POINTER(vp), ci]
-        L.fsea_iq_draw_destroy.argtypes = [vp]
-        L.fsea_iq_points_device.argtypes = [vp, vp, ci, ci, sz, ci, vp, vp]
-        L.fsea_iq_lines_device.argtypes = [vp, vp, ci, ci, sz, ci, ci, vp, vp]
-        L.fsea_iq_points_host.argtypes = [vp, vp, ci, ci, sz, vp]
-        L.fsea_iq_lines_host.argtypes = [vp, vp, ci, ci, sz, ci, vp]
-        L.fsea_demod_create.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci, ci]
-        L.fsea_demod_destroy.argtypes = [vp]
-        L.fsea_demod_reset.argtypes = [vp]
-        L.fsea_demod_set_channel.argtypes = [vp, ci, ci, ctypes.c_double, ctypes.c_double]
-        L.fsea_demod_get_channel.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double),
-                                             ctypes.POINTER(ctypes.c_double)]
-        L.fsea_demod_out_length.argtypes = [vp, sz]
-        L.fsea_demod_out_length.restype = sz
-        L.fsea_demod_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
-        L.fsea_demod_u8_host.argtypes = [vp, vp, sz, ci, vp]
-        L.fsea_demod_f64_host.argtypes = [vp, vp, vp, sz, vp]
-        L.fsea_interp_create.argtypes = [ctypes.POINTER(vp), ci, sz, ci]
-        L.fsea_interp_destroy.argtypes = [vp]
-        L.fsea_interp_reset.argtypes = [vp]
-        L.fsea_interp_n_elements.argtypes = [vp]
-        L.fsea_interp_n_elements.restype = sz
-        L.fsea_interp_push_device.argtypes = [vp, vp, vp]
-        L.fsea_interp_push_host.argtypes = [vp, vp]
-        L.fsea_interp_frames_device.argtypes = [vp, vp, ci, vp, vp]
-        L.fsea_interp_frames_host.argtypes = [vp, vp, ci, vp]
-        L.fsea_interp_image_tables.argtypes = [ci, ci, ci, vp, vp]
-        L.fsea_interp_image_frames_device.argtypes = [vp, vp, ci, ctypes.POINTER(InterpGeometry), vp, vp]
-        L.fsea_interp_image_frames_host.argtypes = [vp, vp, ci, ctypes.POINTER(InterpGeometry), vp]
-        L.fsea_trace_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(TraceConfig), ci]
-        L.fsea_trace_destroy.argtypes = [vp]
-        L.fsea_trace_reset.argtypes = [vp]
-        L.fsea_trace_frames_device.argtypes = [vp, vp, sz, ci, sz, ci, vp, vp]
-        L.fsea_trace_frames_host.argtypes = [vp, vp, sz, ci, sz, ci, vp]
-        L.fsea_trace_canvas_host.argtypes = [vp, vp]
-        _LIB = L
+        _LIB = declare(ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL))
     return _LIB
 
 
@@ -251,29 +239,19 @@ def device_count():
     return n.value
 
 
-class Plan:
-    """One (fft_size, hop, mode) plan on one device; thin wrapper over fsea_plan_*."""
+class _Handle:
+    """An object behind the C ABI: the library (self._L), the handle fsea_<kind>_create gave (self._p), and its destroy."""
+    _kind = None    # "plan", "fir", ...: the X of fsea_X_destroy and fsea_X_reset
+    _p = None
 
-    def __init__(self, fft_size, hop=None, mode=MODE_MAG_F32, device=0, variant=None):
+    def _create(self, create, *args):
         self._L = hip_lib()
         self._p = ctypes.c_void_p()
-        self.fft_size = fft_size
-        self.hop = fft_size if hop is None else hop
-        self.mode = mode
-        self.device = device
-        # variant None: the product plan (its mode's configuration of the size); "" (tuning library): the size's first
-        # configuration whatever the mode; a name: that tuning / per-mode configuration
-        if variant is None or (variant == "" and not hasattr(self._L, "fsea_plan_create_variant")):
-            _check(self._L.fsea_plan_create(ctypes.byref(self._p), fft_size, self.hop, mode, device))
-        elif not hasattr(self._L, "fsea_plan_create_variant"):
-            raise FseaError("kernel variants live in libfsea_hip_tune.so: call fsea.use_tune_library() first")
-        else:
-            _check(self._L.fsea_plan_create_variant(ctypes.byref(self._p), fft_size, self.hop, mode, device,
-                                                    variant.encode()))
+        _check(getattr(self._L, create)(ctypes.byref(self._p), *args))
 
     def close(self):
         if self._p:
-            self._L.fsea_plan_destroy(self._p)
+            getattr(self._L, "fsea_%s_destroy" % self._kind)(self._p)
             self._p = ctypes.c_void_p()
 
     def __del__(self):
@@ -281,6 +259,33 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+class _ResettableHandle(_Handle):
+    """A _Handle whose kind has an fsea_<kind>_reset."""
+
+    def reset(self):
+        _check(getattr(self._L, "fsea_%s_reset" % self._kind)(self._p))
+
+
+class Plan(_ResettableHandle):
+    """One (fft_size, hop, mode) plan on one device; thin wrapper over fsea_plan_*."""
+    _kind = "plan"
+
+    def __init__(self, fft_size, hop=None, mode=MODE_MAG_F32, device=0, variant=None):
+        self.fft_size = fft_size
+        self.hop = fft_size if hop is None else hop
+        self.mode = mode
+        self.device = device
+        # variant None: the product plan (its mode's configuration of the size); "" (tuning library): the size's first
+        # configuration whatever the mode; a name: that tuning / per-mode configuration
+        tuning = hasattr(hip_lib(), "fsea_plan_create_variant")
+        if variant is None or (variant == "" and not tuning):
+            self._create("fsea_plan_create", fft_size, self.hop, mode, device)
+        elif not tuning:
+            raise FseaError("kernel variants live in libfsea_hip_tune.so: call fsea.use_tune_library() first")
+        else:
+            self._create("fsea_plan_create_variant", fft_size, self.hop, mode, device, variant.encode())
 
     @property
     def row_bytes(self):
@@ -334,9 +339,6 @@ class Plan:
     def set_unit_distribution(self, policy):
         """UNITS_AUTO (default), UNITS_STATIC or UNITS_TICKETS: fsea_plan_set_unit_distribution."""
         _check(self._L.fsea_plan_set_unit_distribution(self._p, policy))
-
-    def reset(self):
-        _check(self._L.fsea_plan_reset(self._p))
 
     def release_stream(self, stream):
         """fsea_plan_release_stream: give back the counter slot `stream` holds (after its captured graphs are destroyed)."""
@@ -418,55 +420,40 @@ def lowpass_taps(sample_rate, half_ampl_freq, length):
     return taps[:length]
 
 
-class Fir:
+class Fir(_ResettableHandle):
     """A streaming complex FIR filter with real taps on one device; thin wrapper over fsea_fir_*.  Each call continues
     the signal of the previous ones (the last n_taps - 1 samples are carried over); reset() starts a new one."""
+    _kind = "fir"
 
     def __init__(self, taps, device=0):
-        self._L = hip_lib()
-        self._f = ctypes.c_void_p()
         t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
         self.n_taps = t.size
         self.device = device
-        _check(self._L.fsea_fir_create(ctypes.byref(self._f), t.ctypes.data if t.size else None, t.size, device))
-
-    def close(self):
-        if self._f:
-            self._L.fsea_fir_destroy(self._f)
-            self._f = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        _check(self._L.fsea_fir_reset(self._f))
+        self._create("fsea_fir_create", t.ctypes.data if t.size else None, t.size, device)
 
     def run_device(self, d_iq_ptr, n_samples, d_out_ptr, flip=False, stream=0):
         """Device pointers (ints, 16-byte aligned): 2 * n_samples bytes in, n_samples complex64 out; asynchronous."""
-        _check(self._L.fsea_fir_u8_device(self._f, d_iq_ptr, n_samples, int(bool(flip)), d_out_ptr, stream or None))
+        _check(self._L.fsea_fir_u8_device(self._p, d_iq_ptr, n_samples, int(bool(flip)), d_out_ptr, stream or None))
 
     def run_u8(self, iq_u8, flip=False):
         """Interleaved 8-bit IQ (host) -> complex64 of len(iq_u8) // 2 filtered samples."""
         iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
         out = np.empty(iq.size // 2, dtype=np.complex64)
-        _check(self._L.fsea_fir_u8_host(self._f, iq.ctypes.data, out.size, int(bool(flip)), out.ctypes.data))
+        _check(self._L.fsea_fir_u8_host(self._p, iq.ctypes.data, out.size, int(bool(flip)), out.ctypes.data))
         return out
 
     def run_shifted_device(self, d_iq_ptr, n_samples, d_out_ptr, cycles_per_sample, phase0_cycles=0.0, sample_offset=0,
                            flip=False, stream=0):
         """fsea_fir_u8_shifted_device: run_device with the frequency shifter fused into the load; sample_offset is the
         number of samples the stream's earlier calls consumed."""
-        _check(self._L.fsea_fir_u8_shifted_device(self._f, d_iq_ptr, n_samples, int(bool(flip)), cycles_per_sample,
+        _check(self._L.fsea_fir_u8_shifted_device(self._p, d_iq_ptr, n_samples, int(bool(flip)), cycles_per_sample,
                                                   phase0_cycles, sample_offset, d_out_ptr, stream or None))
 
     def run_u8_shifted(self, iq_u8, cycles_per_sample, phase0_cycles=0.0, sample_offset=0, flip=False):
         """fsea_fir_u8_shifted_host: run_u8 with the frequency shifter fused into the load."""
         iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
         out = np.empty(iq.size // 2, dtype=np.complex64)
-        _check(self._L.fsea_fir_u8_shifted_host(self._f, iq.ctypes.data, out.size, int(bool(flip)), cycles_per_sample,
+        _check(self._L.fsea_fir_u8_shifted_host(self._p, iq.ctypes.data, out.size, int(bool(flip)), cycles_per_sample,
                                                 phase0_cycles, sample_offset, out.ctypes.data))
         return out
 
@@ -478,39 +465,24 @@ class Fir:
         else:
             flat = np.ascontiguousarray(a, dtype=np.float64).ravel()
         out = np.empty(flat.size // 2, dtype=np.complex64)
-        _check(self._L.fsea_fir_f64_host(self._f, flat.ctypes.data, out.size, out.ctypes.data))
+        _check(self._L.fsea_fir_f64_host(self._p, flat.ctypes.data, out.size, out.ctypes.data))
         return out
 
 
-class Chain:
+class Chain(_ResettableHandle):
     """Shift -> low-pass filter -> constellation images per block, the filtered block resident on the device; thin wrapper
     over fsea_chain_*.  run() takes one 8-bit block from the host and returns what was asked for as a dict with the keys
     "points", "lines", "pairs"; fetch() draws more from the block of the last run."""
+    _kind = "chain"
 
     def __init__(self, taps, device=0):
-        self._L = hip_lib()
-        self._c = ctypes.c_void_p()
         t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
         self.n_taps, self.device = t.size, device
-        _check(self._L.fsea_chain_create(ctypes.byref(self._c), t.ctypes.data if t.size else None, t.size, device))
-
-    def close(self):
-        if self._c:
-            self._L.fsea_chain_destroy(self._c)
-            self._c = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        _check(self._L.fsea_chain_reset(self._c))
+        self._create("fsea_chain_create", t.ctypes.data if t.size else None, t.size, device)
 
     @property
     def n_pairs(self):
-        return self._L.fsea_chain_n_pairs(self._c)
+        return self._L.fsea_chain_n_pairs(self._p)
 
     @staticmethod
     def stage(flip=False, cycles_per_sample=None, phase0_cycles=0.0, sample_offset=0, n_zero=0):
@@ -536,19 +508,19 @@ class Chain:
         iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
         n = iq.size // 2
         res, o = self._outputs(n + (stage.n_zero if stage is not None else 0), points, lines_m, n_line_points, pairs)
-        _check(self._L.fsea_chain_run_host(self._c, iq.ctypes.data, n, ctypes.byref(stage) if stage is not None else None,
+        _check(self._L.fsea_chain_run_host(self._p, iq.ctypes.data, n, ctypes.byref(stage) if stage is not None else None,
                                            ctypes.byref(o)))
         return res
 
     def run_f64(self, iq, points=False, lines_m=0, n_line_points=None, pairs=False):
         flat = np.ascontiguousarray(np.asarray(iq, dtype=np.complex128)).ravel().view(np.float64)
         res, o = self._outputs(flat.size // 2, points, lines_m, n_line_points, pairs)
-        _check(self._L.fsea_chain_run_f64_host(self._c, flat.ctypes.data, flat.size // 2, ctypes.byref(o)))
+        _check(self._L.fsea_chain_run_f64_host(self._p, flat.ctypes.data, flat.size // 2, ctypes.byref(o)))
         return res
 
     def fetch(self, points=False, lines_m=0, n_line_points=None, pairs=False):
         res, o = self._outputs(self.n_pairs, points, lines_m, n_line_points, pairs)
-        _check(self._L.fsea_chain_fetch_host(self._c, ctypes.byref(o)))
+        _check(self._L.fsea_chain_fetch_host(self._p, ctypes.byref(o)))
         return res
 
     def run_device(self, d_iq_ptr, n_samples, n_frames, stage=None, d_points=None, d_lines=None, lines_m=1,
@@ -557,58 +529,43 @@ class Chain:
         lines image and / or the filtered pairs out; asynchronous."""
         per_frame = n_samples + (stage.n_zero if stage is not None else 0)
         o = ChainOutputs(d_points, d_lines, int(lines_m), per_frame if n_line_points is None else int(n_line_points), d_pairs)
-        _check(self._L.fsea_chain_run_device(self._c, d_iq_ptr, n_samples, n_frames,
+        _check(self._L.fsea_chain_run_device(self._p, d_iq_ptr, n_samples, n_frames,
                                              ctypes.byref(stage) if stage is not None else None, ctypes.byref(o),
                                              stream or None))
 
 
-class Demod:
+class Demod(_ResettableHandle):
     """The reference's audio chain (RAW or WBFM, nrf_decoder's conversion and frequency shift) on n_channels channels of
     one input stream; thin wrapper over fsea_demod_*.  Each call continues every channel's signal; reset() starts anew."""
+    _kind = "demod"
 
     def __init__(self, kind, in_rate, out_rate=48000, n_channels=1, device=0):
-        self._L = hip_lib()
-        self._d = ctypes.c_void_p()
         self.kind = {"raw": DEMOD_RAW, "wbfm": DEMOD_WBFM}.get(kind, kind)
         self.in_rate, self.out_rate, self.n_channels, self.device = in_rate, out_rate, n_channels, device
-        _check(self._L.fsea_demod_create(ctypes.byref(self._d), self.kind, in_rate, out_rate, n_channels, device))
-
-    def close(self):
-        if self._d:
-            self._L.fsea_demod_destroy(self._d)
-            self._d = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        _check(self._L.fsea_demod_reset(self._d))
+        self._create("fsea_demod_create", self.kind, in_rate, out_rate, n_channels, device)
 
     def set_channel(self, ch, freq_offset, cosine=1.0, sine=0.0):
-        _check(self._L.fsea_demod_set_channel(self._d, ch, int(freq_offset), float(cosine), float(sine)))
+        _check(self._L.fsea_demod_set_channel(self._p, ch, int(freq_offset), float(cosine), float(sine)))
 
     def get_channel(self, ch):
         """(freq_offset, cosine, sine) the channel starts its next call with."""
         o, c, s = ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
-        _check(self._L.fsea_demod_get_channel(self._d, ch, ctypes.byref(o), ctypes.byref(c), ctypes.byref(s)))
+        _check(self._L.fsea_demod_get_channel(self._p, ch, ctypes.byref(o), ctypes.byref(c), ctypes.byref(s)))
         return o.value, c.value, s.value
 
     def out_length(self, n_samples):
-        return self._L.fsea_demod_out_length(self._d, n_samples)
+        return self._L.fsea_demod_out_length(self._p, n_samples)
 
     def run_device(self, d_iq_ptr, n_samples, d_audio_ptr, flip=False, stream=0):
         """Device pointers (ints): 2 * n_samples bytes in, n_channels x out_length f64 out; asynchronous."""
-        _check(self._L.fsea_demod_u8_device(self._d, d_iq_ptr, n_samples, int(bool(flip)), d_audio_ptr, stream or None))
+        _check(self._L.fsea_demod_u8_device(self._p, d_iq_ptr, n_samples, int(bool(flip)), d_audio_ptr, stream or None))
 
     def run_u8(self, iq_u8, flip=False):
         """Interleaved 8-bit IQ (host) -> float64 array (n_channels, out_length)."""
         iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
         n = iq.size // 2
         out = np.empty((self.n_channels, self.out_length(n)), dtype=np.float64)
-        _check(self._L.fsea_demod_u8_host(self._d, iq.ctypes.data, n, int(bool(flip)), out.ctypes.data))
+        _check(self._L.fsea_demod_u8_host(self._p, iq.ctypes.data, n, int(bool(flip)), out.ctypes.data))
         return out
 
     def run_f64(self, i, q):
@@ -618,7 +575,7 @@ class Demod:
         if i.size != q.size:
             raise ValueError("I and Q differ in length")
         out = np.empty((self.n_channels, self.out_length(i.size)), dtype=np.float64)
-        _check(self._L.fsea_demod_f64_host(self._d, i.ctypes.data, q.ctypes.data, i.size, out.ctypes.data))
+        _check(self._L.fsea_demod_f64_host(self._p, i.ctypes.data, q.ctypes.data, i.size, out.ctypes.data))
         return out
 
 
@@ -637,34 +594,22 @@ def _iq_input(iq):
     return a, kinds[a.dtype], a.size // 2
 
 
-class IqDraw:
+class IqDraw(_Handle):
     """IQ constellation images on one device; thin wrapper over fsea_iq_*.  points(): the 256 x 256 histogram of the
     reference's nrf_buffer_to_iq_points (bin I * 256 + Q, counts modulo 256); lines(): the (256 m)^2 image of
     nrf_buffer_to_iq_lines (consecutive points joined by its Bresenham lines, pixel (I m, Q m) at row Q m, counts clamped to
     255).  Coordinates as nut_buffer_get_u8: u8 as is, floats as x86-64's (uint8_t)(v * 256.0)."""
+    _kind = "iq_draw"
 
     def __init__(self, device=0):
-        self._L = hip_lib()
-        self._d = ctypes.c_void_p()
         self.device = device
-        _check(self._L.fsea_iq_draw_create(ctypes.byref(self._d), device))
-
-    def close(self):
-        if self._d:
-            self._L.fsea_iq_draw_destroy(self._d)
-            self._d = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("fsea_iq_draw_create", device)
 
     def points(self, iq, flip=False):
         """Host IQ (uint8, float32, float64 interleaved, or complex) -> (256, 256) uint8, row I."""
         a, kind, n = _iq_input(iq)
         img = np.empty((256, 256), dtype=np.uint8)
-        _check(self._L.fsea_iq_points_host(self._d, a.ctypes.data, kind, int(bool(flip)), n, img.ctypes.data))
+        _check(self._L.fsea_iq_points_host(self._p, a.ctypes.data, kind, int(bool(flip)), n, img.ctypes.data))
         return img
 
     def lines(self, iq, m=1, n_points=None, flip=False):
@@ -675,19 +620,19 @@ class IqDraw:
                 raise ValueError("n_points must be in [0, %d] (the pairs of iq), got %d" % (n, int(n_points)))
             n = int(n_points)
         img = np.empty((256 * m, 256 * m), dtype=np.uint8)
-        _check(self._L.fsea_iq_lines_host(self._d, a.ctypes.data, kind, int(bool(flip)), n, int(m), img.ctypes.data))
+        _check(self._L.fsea_iq_lines_host(self._p, a.ctypes.data, kind, int(bool(flip)), n, int(m), img.ctypes.data))
         return img
 
     def points_device(self, d_iq_ptr, kind, n_pairs, n_frames, d_image_ptr, flip=False, stream=0):
         """Device pointers (ints, 16-byte aligned): n_frames frames of n_pairs pairs in, n_frames 65536-byte images out;
         asynchronous."""
-        _check(self._L.fsea_iq_points_device(self._d, d_iq_ptr, kind, int(bool(flip)), n_pairs, n_frames, d_image_ptr,
+        _check(self._L.fsea_iq_points_device(self._p, d_iq_ptr, kind, int(bool(flip)), n_pairs, n_frames, d_image_ptr,
                                              stream or None))
 
     def lines_device(self, d_iq_ptr, kind, n_points, n_frames, m, d_image_ptr, flip=False, stream=0):
         """Device pointers (ints, 16-byte aligned): n_frames frames of n_points points in, n_frames (256 m)^2-byte images
         out; asynchronous."""
-        _check(self._L.fsea_iq_lines_device(self._d, d_iq_ptr, kind, int(bool(flip)), n_points, n_frames, int(m),
+        _check(self._L.fsea_iq_lines_device(self._p, d_iq_ptr, kind, int(bool(flip)), n_points, n_frames, int(m),
                                             d_image_ptr, stream or None))
 
 
@@ -699,34 +644,19 @@ def interp_image_tables(width, height, iq_size):
     return col, row
 
 
-class Interp:
+class Interp(_ResettableHandle):
     """Two resident sample blocks A and B (uint8 or float64, n_elements each, zero at first) and their blends
     a (1 - t) + b t for arrays of weights; thin wrapper over fsea_interp_*.  frames(): the reference's
     nrf_interpolator_get_buffer per weight; image_frames(): the frames of its gradual-noise movie tool."""
+    _kind = "interp"
 
     def __init__(self, dtype, n_elements, device=0):
-        self._L = hip_lib()
-        self._p = ctypes.c_void_p()
         self.dtype = np.dtype(dtype)
         kinds = {np.dtype(np.uint8): IQ_U8, np.dtype(np.float64): IQ_F64}
         if self.dtype not in kinds:
             raise TypeError("blocks must be uint8 or float64, got %s" % self.dtype)
         self.n, self.device = int(n_elements), device
-        _check(self._L.fsea_interp_create(ctypes.byref(self._p), kinds[self.dtype], self.n, device))
-
-    def close(self):
-        if self._p:
-            self._L.fsea_interp_destroy(self._p)
-            self._p = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        _check(self._L.fsea_interp_reset(self._p))
+        self._create("fsea_interp_create", kinds[self.dtype], self.n, device)
 
     def push(self, block):
         """A takes what B held, B the host array `block` (n_elements of the object's dtype)."""
@@ -764,31 +694,16 @@ class Interp:
                                                        stream or None))
 
 
-class Trace:
+class Trace(_ResettableHandle):
     """The IQ trace movie of the reference's single-sample tool on one device; thin wrapper over fsea_trace_*.  A
     width x height canvas (zero at first) with the (256 m)^2 IQ square at its centre; every frame fades it by `fade`, joins
     the points of its frame_bytes bytes with lines, each hit adding pixel_inc unless that reaches 255, and is one image."""
+    _kind = "trace"
 
     def __init__(self, width=1920, height=1080, m=4, pixel_inc=4, fade=0, device=0):
-        self._L = hip_lib()
-        self._t = ctypes.c_void_p()
         self.width, self.height, self.m, self.device = int(width), int(height), int(m), device
         cfg = TraceConfig(self.width, self.height, self.m, int(pixel_inc), int(fade))
-        _check(self._L.fsea_trace_create(ctypes.byref(self._t), ctypes.byref(cfg), device))
-
-    def close(self):
-        if self._t:
-            self._L.fsea_trace_destroy(self._t)
-            self._t = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        _check(self._L.fsea_trace_reset(self._t))
+        self._create("fsea_trace_create", ctypes.byref(cfg), device)
 
     def frames(self, data, frame_bytes, n_frames=None, flip=True, images=True):
         """Host uint8 bytes -> (n_frames, height, width) uint8, frame f from byte f * frame_bytes on (n_frames defaults to
@@ -797,20 +712,20 @@ class Trace:
         if n_frames is None:
             n_frames = -(-b.size // int(frame_bytes)) if int(frame_bytes) > 0 else 0
         out = np.empty((max(n_frames, 0), self.height, self.width), dtype=np.uint8) if images else None
-        _check(self._L.fsea_trace_frames_host(self._t, b.ctypes.data if b.size else None, b.size, int(bool(flip)),
+        _check(self._L.fsea_trace_frames_host(self._p, b.ctypes.data if b.size else None, b.size, int(bool(flip)),
                                               frame_bytes, n_frames, out.ctypes.data if images else None))
         return out
 
     def frames_device(self, d_bytes_ptr, n_bytes, frame_bytes, n_frames, d_images_ptr, flip=True, stream=0):
         """Device pointers (ints; images 16-byte aligned or 0 for none): n_bytes readable bytes in, n_frames images out;
         asynchronous."""
-        _check(self._L.fsea_trace_frames_device(self._t, d_bytes_ptr, n_bytes, int(bool(flip)), frame_bytes, n_frames,
+        _check(self._L.fsea_trace_frames_device(self._p, d_bytes_ptr, n_bytes, int(bool(flip)), frame_bytes, n_frames,
                                                 d_images_ptr or None, stream or None))
 
     def canvas(self):
         """The canvas as it stands, (height, width) uint8."""
         out = np.empty((self.height, self.width), dtype=np.uint8)
-        _check(self._L.fsea_trace_canvas_host(self._t, out.ctypes.data))
+        _check(self._L.fsea_trace_canvas_host(self._p, out.ctypes.data))
         return out
 
 
@@ -829,6 +744,47 @@ class PinnedArray:
             self.array = None
             hip_lib().fsea_host_free(self._ptr)
             self._ptr = ctypes.c_void_p()
+
+
+class DeviceBuffer:
+    """nbytes of device memory (fsea_device_alloc; at least 16, so that an empty buffer has an address too).  .ptr is a
+    ctypes.c_void_p: pass it, or an int made of .ptr.value plus an offset, wherever a device pointer is taken."""
+
+    def __init__(self, nbytes, device=0):
+        self.ptr, self.nbytes, self.device = ctypes.c_void_p(), nbytes, device
+        _check(hip_lib().fsea_device_alloc(device, max(nbytes, 16), ctypes.byref(self.ptr)))
+
+    def upload(self, arr):
+        """The bytes of a host array to the start of the buffer (fsea_copy_to_device); returns the buffer."""
+        arr = np.ascontiguousarray(arr)
+        _check(hip_lib().fsea_copy_to_device(self.device, self.ptr, arr.ctypes.data, arr.nbytes))
+        return self
+
+    def download(self, dtype, shape, byte_offset=0):
+        """A new host array of `shape` and `dtype` from byte_offset on (fsea_copy_to_host)."""
+        out = np.empty(shape, dtype=dtype)
+        _check(hip_lib().fsea_copy_to_host(self.device, out.ctypes.data, self.ptr.value + byte_offset, out.nbytes))
+        return out
+
+    def free(self):
+        if self.ptr:
+            hip_lib().fsea_device_free(self.device, self.ptr)
+            self.ptr = ctypes.c_void_p()
+
+
+class Stream:
+    """A non-blocking stream on one device (fsea_stream_create); pass it wherever a `stream=` argument is taken, or to the
+    library's functions themselves.  .handle is the hipStream_t as a ctypes.c_void_p."""
+
+    def __init__(self, device=0):
+        self.device, self.handle = device, ctypes.c_void_p()
+        _check(hip_lib().fsea_stream_create(device, ctypes.byref(self.handle)))
+        self._as_parameter_ = self.handle
+
+    def close(self):
+        if self.handle:
+            _check(hip_lib().fsea_stream_destroy(self.device, self.handle))
+            self.handle = self._as_parameter_ = ctypes.c_void_p()
 
 
 def composite_max_device(d_dst, d_src, dst_x, dst_y, width, height, dst_stride, dst_height, src_stride, device=0,

@@ -11,34 +11,6 @@ NUT_BUFFER_U8 = 1
 NUT_BUFFER_F64 = 2
 NRF_BUFFER_SIZE_BYTES = 16 * 16384
 NRF_SAMPLES_LENGTH = 131072
-
-NUT_EXPORTS = [
-    "nut_sleep_milliseconds", "nut_buffer_new_u8", "nut_buffer_new_f64", "nut_buffer_copy",
-    "nut_buffer_reduce", "nut_buffer_clip", "nut_buffer_set_data", "nut_buffer_append",
-    "nut_buffer_get_u8", "nut_buffer_get_f64", "nut_buffer_set_u8", "nut_buffer_set_f64",
-    "nut_buffer_convert", "nut_buffer_save", "nut_buffer_free",
-]
-# additions beside the reference's prototypes (include/nrf.h says so at each): the reference's nrf.h has no such function
-NRF_ADDITIONS = ["nrf_fft_set_window", "nrf_fft_set_window_weights", "nrf_decoder_free", "nrf_player_pop_pcm",
-                 "nrf_iq_chain_new", "nrf_iq_chain_set_shifter", "nrf_iq_chain_process", "nrf_iq_chain_get_iq_points",
-                 "nrf_iq_chain_get_iq_lines", "nrf_iq_chain_get_buffer", "nrf_iq_chain_free"]
-NRF_EXPORTS = [
-    "nrf_block_init", "nrf_block_connect", "nrf_block_process", "nrf_device_new",
-    "nrf_device_new_with_config", "nrf_device_set_frequency", "nrf_device_set_decode_handler",
-    "nrf_device_set_paused", "nrf_device_step", "nrf_device_get_samples_buffer", "nrf_device_free",
-    "nrf_fft_new", "nrf_fft_shift", "nrf_fft_process", "nrf_fft_get_buffer", "nrf_fft_free",
-    "nrf_freq_shifter_new", "nrf_freq_shifter_process_samples", "nrf_freq_shifter_process",
-    "nrf_freq_shifter_get_buffer", "nrf_freq_shifter_free",
-    "nrf_fir_get_low_pass_coefficients", "nrf_fir_filter_new", "nrf_fir_filter_load", "nrf_fir_filter_get",
-    "nrf_fir_filter_free", "nrf_iq_filter_new", "nrf_iq_filter_process", "nrf_iq_filter_get_buffer", "nrf_iq_filter_free",
-    "nrf_device_get_iq_buffer", "nrf_device_get_iq_lines", "nrf_buffer_add_position_channel", "nrf_buffer_to_iq_points",
-    "nrf_buffer_to_iq_lines", "nrf_signal_detector_new", "nrf_signal_detector_process", "nrf_signal_detector_free",
-    "nrf_downsampler_new", "nrf_downsampler_process", "nrf_downsampler_free", "nrf_raw_demodulator_new",
-    "nrf_raw_demodulator_process", "nrf_raw_demodulator_free", "nrf_fm_demodulator_new", "nrf_fm_demodulator_process",
-    "nrf_fm_demodulator_free", "nrf_decoder_new", "nrf_decoder_process", "nrf_player_new", "nrf_player_set_freq_offset",
-    "nrf_player_set_gain", "nrf_player_free",
-    "nrf_interpolator_new", "nrf_interpolator_process", "nrf_interpolator_get_buffer", "nrf_interpolator_free",
-]
 NRF_DEMODULATE_RAW, NRF_DEMODULATE_WBFM = 0, 1
 
 
@@ -54,87 +26,15 @@ class NutBuffer(ctypes.Structure):
 NutBufferP = ctypes.POINTER(NutBuffer)
 
 
-def bind_nut(L):
-    """Attach nut_buffer_* prototypes to a loaded library (ours or the reference build)."""
-    L.nut_buffer_new_u8.restype = NutBufferP
-    L.nut_buffer_new_u8.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    L.nut_buffer_new_f64.restype = NutBufferP
-    L.nut_buffer_new_f64.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    L.nut_buffer_copy.restype = NutBufferP
-    L.nut_buffer_copy.argtypes = [NutBufferP]
-    L.nut_buffer_reduce.restype = NutBufferP
-    L.nut_buffer_reduce.argtypes = [NutBufferP, ctypes.c_double]
-    L.nut_buffer_clip.restype = NutBufferP
-    L.nut_buffer_clip.argtypes = [NutBufferP, ctypes.c_int, ctypes.c_int]
-    L.nut_buffer_set_data.restype = None
-    L.nut_buffer_set_data.argtypes = [NutBufferP, NutBufferP]
-    L.nut_buffer_append.restype = None
-    L.nut_buffer_append.argtypes = [NutBufferP, NutBufferP]
-    L.nut_buffer_get_u8.restype = ctypes.c_uint8
-    L.nut_buffer_get_u8.argtypes = [NutBufferP, ctypes.c_int]
-    L.nut_buffer_get_f64.restype = ctypes.c_double
-    L.nut_buffer_get_f64.argtypes = [NutBufferP, ctypes.c_int]
-    L.nut_buffer_set_u8.restype = None
-    L.nut_buffer_set_u8.argtypes = [NutBufferP, ctypes.c_int, ctypes.c_uint8]
-    L.nut_buffer_set_f64.restype = None
-    L.nut_buffer_set_f64.argtypes = [NutBufferP, ctypes.c_int, ctypes.c_double]
-    L.nut_buffer_convert.restype = NutBufferP
-    L.nut_buffer_convert.argtypes = [NutBufferP, ctypes.c_int]
-    L.nut_buffer_save.restype = None
-    L.nut_buffer_save.argtypes = [NutBufferP, ctypes.c_char_p]
-    L.nut_buffer_free.restype = None
-    L.nut_buffer_free.argtypes = [NutBufferP]
-    return L
-
-
 class NrfFirFilter(ctypes.Structure):
     """nrf_fir_filter (include/nrf.h): the reference's layout."""
     _fields_ = [("length", ctypes.c_int), ("coefficients", ctypes.POINTER(ctypes.c_double)), ("offset", ctypes.c_int),
                 ("center", ctypes.c_int), ("samples_length", ctypes.c_int), ("samples", ctypes.POINTER(ctypes.c_double))]
 
 
-def bind_fir(L):
-    """Attach the host FIR filter prototypes (nrf_fir_*) to a loaded library (ours or a build of the reference)."""
-    fp = ctypes.POINTER(NrfFirFilter)
-    L.nrf_fir_get_low_pass_coefficients.restype = ctypes.POINTER(ctypes.c_double)
-    L.nrf_fir_get_low_pass_coefficients.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.nrf_fir_filter_new.restype = fp
-    L.nrf_fir_filter_new.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.nrf_fir_filter_load.restype = None
-    L.nrf_fir_filter_load.argtypes = [fp, ctypes.c_void_p, ctypes.c_int]
-    L.nrf_fir_filter_get.restype = ctypes.c_double
-    L.nrf_fir_filter_get.argtypes = [fp, ctypes.c_int]
-    L.nrf_fir_filter_free.restype = None
-    L.nrf_fir_filter_free.argtypes = [fp]
-    return L
-
-
 class NrfSignalDetector(ctypes.Structure):
     """nrf_signal_detector (include/nrf.h): the reference's layout."""
     _fields_ = [("mean", ctypes.c_double), ("standard_deviation", ctypes.c_double)]
-
-
-def bind_iq_draw(L):
-    """Attach the IQ drawing and signal detector prototypes to a loaded library (ours or a build of the reference)."""
-    vp = ctypes.c_void_p
-    dp = ctypes.POINTER(NrfSignalDetector)
-    L.nrf_device_get_iq_buffer.restype = NutBufferP
-    L.nrf_device_get_iq_buffer.argtypes = [vp]
-    L.nrf_device_get_iq_lines.restype = NutBufferP
-    L.nrf_device_get_iq_lines.argtypes = [vp, ctypes.c_int, ctypes.c_float]
-    L.nrf_buffer_add_position_channel.restype = NutBufferP
-    L.nrf_buffer_add_position_channel.argtypes = [NutBufferP]
-    L.nrf_buffer_to_iq_points.restype = NutBufferP
-    L.nrf_buffer_to_iq_points.argtypes = [NutBufferP]
-    L.nrf_buffer_to_iq_lines.restype = NutBufferP
-    L.nrf_buffer_to_iq_lines.argtypes = [NutBufferP, ctypes.c_int, ctypes.c_float]
-    L.nrf_signal_detector_new.restype = dp
-    L.nrf_signal_detector_new.argtypes = []
-    L.nrf_signal_detector_process.restype = None
-    L.nrf_signal_detector_process.argtypes = [dp, NutBufferP]
-    L.nrf_signal_detector_free.restype = None
-    L.nrf_signal_detector_free.argtypes = [dp]
-    return L
 
 
 class NrfBlock(ctypes.Structure):
@@ -187,62 +87,158 @@ class NrfInterpolator(ctypes.Structure):
                 ("buffer_a", NutBufferP), ("buffer_b", NutBufferP)]
 
 
+class NrfDeviceConfig(ctypes.Structure):
+    """nrf_device_config (include/nrf.h)."""
+    _fields_ = [("sample_rate", ctypes.c_int), ("freq_mhz", ctypes.c_double), ("data_file", ctypes.c_char_p)]
+
+
+# Every function of include/nut.h and include/nrf.h once: name -> (restype, argtypes).  Grouped as the bind_* functions
+# below apply them, because those also serve builds of the reference, which have only some of the groups.
+_vp, _ci, _f64, _f32, _buf = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_float, NutBufferP
+_firp, _detp, _ipp = ctypes.POINTER(NrfFirFilter), ctypes.POINTER(NrfSignalDetector), ctypes.POINTER(NrfInterpolator)
+_dsp, _rawp, _fmp, _decp = (ctypes.POINTER(NrfDownsampler), ctypes.POINTER(NrfRawDemodulator),
+                            ctypes.POINTER(NrfFmDemodulator), ctypes.POINTER(NrfDecoder))
+NUT_TABLE = {
+    "nut_sleep_milliseconds": (None, [_ci]),
+    "nut_buffer_new_u8": (_buf, [_ci, _ci, _vp]),
+    "nut_buffer_new_f64": (_buf, [_ci, _ci, _vp]),
+    "nut_buffer_copy": (_buf, [_buf]),
+    "nut_buffer_reduce": (_buf, [_buf, _f64]),
+    "nut_buffer_clip": (_buf, [_buf, _ci, _ci]),
+    "nut_buffer_set_data": (None, [_buf, _buf]),
+    "nut_buffer_append": (None, [_buf, _buf]),
+    "nut_buffer_get_u8": (ctypes.c_uint8, [_buf, _ci]),
+    "nut_buffer_get_f64": (_f64, [_buf, _ci]),
+    "nut_buffer_set_u8": (None, [_buf, _ci, ctypes.c_uint8]),
+    "nut_buffer_set_f64": (None, [_buf, _ci, _f64]),
+    "nut_buffer_convert": (_buf, [_buf, _ci]),
+    "nut_buffer_save": (None, [_buf, ctypes.c_char_p]),
+    "nut_buffer_free": (None, [_buf]),
+}
+_FIR = {
+    "nrf_fir_get_low_pass_coefficients": (_dp, [_ci, _ci, _ci]),
+    "nrf_fir_filter_new": (_firp, [_ci, _ci, _ci]),
+    "nrf_fir_filter_load": (None, [_firp, _vp, _ci]),
+    "nrf_fir_filter_get": (_f64, [_firp, _ci]),
+    "nrf_fir_filter_free": (None, [_firp]),
+}
+_IQ_DRAW = {
+    "nrf_device_get_iq_buffer": (_buf, [_vp]),
+    "nrf_device_get_iq_lines": (_buf, [_vp, _ci, _f32]),
+    "nrf_buffer_add_position_channel": (_buf, [_buf]),
+    "nrf_buffer_to_iq_points": (_buf, [_buf]),
+    "nrf_buffer_to_iq_lines": (_buf, [_buf, _ci, _f32]),
+    "nrf_signal_detector_new": (_detp, []),
+    "nrf_signal_detector_process": (None, [_detp, _buf]),
+    "nrf_signal_detector_free": (None, [_detp]),
+}
+_DEMOD = {
+    "nrf_downsampler_new": (_dsp, [_ci, _ci, _ci, _ci]),
+    "nrf_downsampler_process": (None, [_dsp, _vp, _ci]),
+    "nrf_downsampler_free": (None, [_dsp]),
+    "nrf_raw_demodulator_new": (_rawp, [_ci, _ci]),
+    "nrf_raw_demodulator_process": (None, [_rawp, _vp, _vp, _ci]),
+    "nrf_raw_demodulator_free": (None, [_rawp]),
+    "nrf_fm_demodulator_new": (_fmp, [_ci, _ci]),
+    "nrf_fm_demodulator_process": (None, [_fmp, _vp, _vp, _ci]),
+    "nrf_fm_demodulator_free": (None, [_fmp]),
+    "nrf_decoder_new": (_decp, [_ci, _ci, _ci, _ci]),
+    "nrf_decoder_process": (None, [_decp, _vp, ctypes.c_size_t]),
+    "nrf_decoder_free": (None, [_decp]),
+}
+_PLAYER = {   # this build's headless player (include/nrf.h); a build of the reference has none
+    "nrf_player_new": (_vp, [_vp, _ci, _ci]),
+    "nrf_player_set_freq_offset": (None, [_vp, _ci]),
+    "nrf_player_set_gain": (None, [_vp, _f32]),
+    "nrf_player_free": (None, [_vp]),
+    "nrf_player_pop_pcm": (_ci, [_vp, _vp, _ci, ctypes.POINTER(ctypes.c_long)]),
+}
+_INTERPOLATOR = {
+    "nrf_interpolator_new": (_ipp, [_f64]),
+    "nrf_interpolator_process": (None, [_ipp, _buf]),
+    "nrf_interpolator_get_buffer": (_buf, [_ipp]),
+    "nrf_interpolator_free": (None, [_ipp]),
+}
+_REST = {     # what only nrf_lib() binds: blocks, the sample source, the FFT, the shifter, the IQ filter and chain
+    "nrf_block_init": (None, [_vp, _ci, _vp, _vp]),
+    "nrf_block_connect": (None, [_vp, _vp]),
+    "nrf_block_process": (None, [_vp, _buf]),
+    "nrf_device_new": (_vp, [_f64, ctypes.c_char_p]),
+    "nrf_device_new_with_config": (_vp, [NrfDeviceConfig]),
+    "nrf_device_set_frequency": (_f64, [_vp, _f64]),
+    "nrf_device_set_decode_handler": (None, [_vp, _vp, _vp]),
+    "nrf_device_set_paused": (None, [_vp, _ci]),
+    "nrf_device_step": (None, [_vp]),
+    "nrf_device_get_samples_buffer": (_buf, [_vp]),
+    "nrf_device_free": (None, [_vp]),
+    "nrf_fft_new": (_vp, [_ci, _ci]),
+    "nrf_fft_shift": (None, [_vp, _f64]),
+    "nrf_fft_process": (None, [_vp, _buf]),
+    "nrf_fft_get_buffer": (_buf, [_vp]),
+    "nrf_fft_free": (None, [_vp]),
+    "nrf_fft_set_window": (None, [_vp, ctypes.c_char_p]),
+    "nrf_fft_set_window_weights": (None, [_vp, _vp]),
+    "nrf_freq_shifter_new": (_vp, [_ci, _ci]),
+    "nrf_freq_shifter_process_samples": (None, [_vp, _vp, _vp, _ci]),
+    "nrf_freq_shifter_process": (None, [_vp, _buf]),
+    "nrf_freq_shifter_get_buffer": (_buf, [_vp]),
+    "nrf_freq_shifter_free": (None, [_vp]),
+    "nrf_iq_filter_new": (_vp, [_ci, _ci, _ci]),
+    "nrf_iq_filter_process": (None, [_vp, _buf]),
+    "nrf_iq_filter_get_buffer": (_buf, [_vp]),
+    "nrf_iq_filter_free": (None, [_vp]),
+    "nrf_iq_chain_new": (_vp, [_ci, _ci, _ci]),
+    "nrf_iq_chain_set_shifter": (None, [_vp, _ci]),
+    "nrf_iq_chain_process": (None, [_vp, _buf]),
+    "nrf_iq_chain_get_iq_points": (_buf, [_vp]),
+    "nrf_iq_chain_get_iq_lines": (_buf, [_vp, _ci, _f32]),
+    "nrf_iq_chain_get_buffer": (_buf, [_vp]),
+    "nrf_iq_chain_free": (None, [_vp]),
+}
+NRF_TABLES = (_FIR, _IQ_DRAW, _DEMOD, _PLAYER, _INTERPOLATOR, _REST)
+API = {name: proto for table in (NUT_TABLE,) + NRF_TABLES for name, proto in table.items()}
+
+NUT_EXPORTS = list(NUT_TABLE)
+# additions beside the reference's prototypes (include/nrf.h says so at each): the reference's nrf.h has no such function
+NRF_ADDITIONS = ["nrf_fft_set_window", "nrf_fft_set_window_weights", "nrf_decoder_free", "nrf_player_pop_pcm",
+                 "nrf_iq_chain_new", "nrf_iq_chain_set_shifter", "nrf_iq_chain_process", "nrf_iq_chain_get_iq_points",
+                 "nrf_iq_chain_get_iq_lines", "nrf_iq_chain_get_buffer", "nrf_iq_chain_free"]
+NRF_EXPORTS = [name for table in NRF_TABLES for name in table if name not in NRF_ADDITIONS]
+
+
+def bind(L, *tables):
+    """Attach the prototypes of `tables` to a loaded library: the one place restype / argtypes are assigned."""
+    for table in tables:
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
+def bind_nut(L):
+    """Attach nut_buffer_* prototypes to a loaded library (ours or the reference build)."""
+    return bind(L, NUT_TABLE)
+
+
+def bind_fir(L):
+    """Attach the host FIR filter prototypes (nrf_fir_*) to a loaded library (ours or a build of the reference)."""
+    return bind(L, _FIR)
+
+
+def bind_iq_draw(L):
+    """Attach the IQ drawing and signal detector prototypes to a loaded library (ours or a build of the reference)."""
+    return bind(L, _IQ_DRAW)
+
+
 def bind_interpolator(L):
     """Attach the interpolator prototypes to a loaded library (ours or a build of the reference)."""
-    ip = ctypes.POINTER(NrfInterpolator)
-    L.nrf_interpolator_new.restype = ip
-    L.nrf_interpolator_new.argtypes = [ctypes.c_double]
-    L.nrf_interpolator_process.restype = None
-    L.nrf_interpolator_process.argtypes = [ip, NutBufferP]
-    L.nrf_interpolator_get_buffer.restype = NutBufferP
-    L.nrf_interpolator_get_buffer.argtypes = [ip]
-    L.nrf_interpolator_free.restype = None
-    L.nrf_interpolator_free.argtypes = [ip]
-    return L
+    return bind(L, _INTERPOLATOR)
 
 
 def bind_demod(L):
     """Attach the downsampler, demodulator, decoder and (where the library has them) player prototypes to a loaded
     library (ours or a build of the reference)."""
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    dsp, rawp, fmp, decp = (ctypes.POINTER(NrfDownsampler), ctypes.POINTER(NrfRawDemodulator),
-                            ctypes.POINTER(NrfFmDemodulator), ctypes.POINTER(NrfDecoder))
-    L.nrf_downsampler_new.restype = dsp
-    L.nrf_downsampler_new.argtypes = [ci, ci, ci, ci]
-    L.nrf_downsampler_process.restype = None
-    L.nrf_downsampler_process.argtypes = [dsp, vp, ci]
-    L.nrf_downsampler_free.restype = None
-    L.nrf_downsampler_free.argtypes = [dsp]
-    L.nrf_raw_demodulator_new.restype = rawp
-    L.nrf_raw_demodulator_new.argtypes = [ci, ci]
-    L.nrf_raw_demodulator_process.restype = None
-    L.nrf_raw_demodulator_process.argtypes = [rawp, vp, vp, ci]
-    L.nrf_raw_demodulator_free.restype = None
-    L.nrf_raw_demodulator_free.argtypes = [rawp]
-    L.nrf_fm_demodulator_new.restype = fmp
-    L.nrf_fm_demodulator_new.argtypes = [ci, ci]
-    L.nrf_fm_demodulator_process.restype = None
-    L.nrf_fm_demodulator_process.argtypes = [fmp, vp, vp, ci]
-    L.nrf_fm_demodulator_free.restype = None
-    L.nrf_fm_demodulator_free.argtypes = [fmp]
-    L.nrf_decoder_new.restype = decp
-    L.nrf_decoder_new.argtypes = [ci, ci, ci, ci]
-    L.nrf_decoder_process.restype = None
-    L.nrf_decoder_process.argtypes = [decp, vp, ctypes.c_size_t]
-    L.nrf_decoder_free.restype = None
-    L.nrf_decoder_free.argtypes = [decp]
-    if hasattr(L, "nrf_player_pop_pcm"):       # this build's headless player (include/nrf.h)
-        L.nrf_player_new.restype = vp
-        L.nrf_player_new.argtypes = [vp, ci, ci]
-        L.nrf_player_set_freq_offset.restype = None
-        L.nrf_player_set_freq_offset.argtypes = [vp, ci]
-        L.nrf_player_set_gain.restype = None
-        L.nrf_player_set_gain.argtypes = [vp, ctypes.c_float]
-        L.nrf_player_free.restype = None
-        L.nrf_player_free.argtypes = [vp]
-        L.nrf_player_pop_pcm.restype = ci
-        L.nrf_player_pop_pcm.argtypes = [vp, vp, ci, ctypes.POINTER(ctypes.c_long)]
-    return L
+    return bind(L, _DEMOD, *([_PLAYER] if hasattr(L, "nrf_player_pop_pcm") else []))
 
 
 _LIB = None
@@ -258,75 +254,7 @@ def nrf_lib():
         path = lib_path()
         if not os.path.exists(path):
             raise RuntimeError("libfsea_nrf.so is missing: run frequensea_amd.build()")
-        L = bind_nut(ctypes.CDLL(path))
-        vp = ctypes.c_void_p
-        L.nrf_device_new.restype = vp
-        L.nrf_device_new.argtypes = [ctypes.c_double, ctypes.c_char_p]
-        L.nrf_device_set_frequency.restype = ctypes.c_double
-        L.nrf_device_set_frequency.argtypes = [vp, ctypes.c_double]
-        L.nrf_device_set_paused.restype = None
-        L.nrf_device_set_paused.argtypes = [vp, ctypes.c_int]
-        L.nrf_device_step.restype = None
-        L.nrf_device_step.argtypes = [vp]
-        L.nrf_device_get_samples_buffer.restype = NutBufferP
-        L.nrf_device_get_samples_buffer.argtypes = [vp]
-        L.nrf_device_free.restype = None
-        L.nrf_device_free.argtypes = [vp]
-        L.nrf_block_connect.restype = None
-        L.nrf_block_connect.argtypes = [vp, vp]
-        L.nrf_block_process.restype = None
-        L.nrf_block_process.argtypes = [vp, NutBufferP]
-        L.nrf_fft_new.restype = vp
-        L.nrf_fft_new.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.nrf_fft_shift.restype = None
-        L.nrf_fft_shift.argtypes = [vp, ctypes.c_double]
-        L.nrf_fft_process.restype = None
-        L.nrf_fft_process.argtypes = [vp, NutBufferP]
-        L.nrf_fft_get_buffer.restype = NutBufferP
-        L.nrf_fft_get_buffer.argtypes = [vp]
-        L.nrf_fft_free.restype = None
-        L.nrf_fft_free.argtypes = [vp]
-        L.nrf_fft_set_window.restype = None
-        L.nrf_fft_set_window.argtypes = [vp, ctypes.c_char_p]
-        L.nrf_fft_set_window_weights.restype = None
-        L.nrf_fft_set_window_weights.argtypes = [vp, ctypes.c_void_p]
-        L.nrf_freq_shifter_new.restype = vp
-        L.nrf_freq_shifter_new.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.nrf_freq_shifter_process_samples.restype = None
-        L.nrf_freq_shifter_process_samples.argtypes = [vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        L.nrf_freq_shifter_process.restype = None
-        L.nrf_freq_shifter_process.argtypes = [vp, NutBufferP]
-        L.nrf_freq_shifter_get_buffer.restype = NutBufferP
-        L.nrf_freq_shifter_get_buffer.argtypes = [vp]
-        L.nrf_freq_shifter_free.restype = None
-        L.nrf_freq_shifter_free.argtypes = [vp]
-        bind_fir(L)
-        L.nrf_iq_filter_new.restype = vp
-        L.nrf_iq_filter_new.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.nrf_iq_filter_process.restype = None
-        L.nrf_iq_filter_process.argtypes = [vp, NutBufferP]
-        L.nrf_iq_filter_get_buffer.restype = NutBufferP
-        L.nrf_iq_filter_get_buffer.argtypes = [vp]
-        L.nrf_iq_filter_free.restype = None
-        L.nrf_iq_filter_free.argtypes = [vp]
-        L.nrf_iq_chain_new.restype = vp
-        L.nrf_iq_chain_new.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.nrf_iq_chain_set_shifter.restype = None
-        L.nrf_iq_chain_set_shifter.argtypes = [vp, ctypes.c_int]
-        L.nrf_iq_chain_process.restype = None
-        L.nrf_iq_chain_process.argtypes = [vp, NutBufferP]
-        L.nrf_iq_chain_get_iq_points.restype = NutBufferP
-        L.nrf_iq_chain_get_iq_points.argtypes = [vp]
-        L.nrf_iq_chain_get_iq_lines.restype = NutBufferP
-        L.nrf_iq_chain_get_iq_lines.argtypes = [vp, ctypes.c_int, ctypes.c_float]
-        L.nrf_iq_chain_get_buffer.restype = NutBufferP
-        L.nrf_iq_chain_get_buffer.argtypes = [vp]
-        L.nrf_iq_chain_free.restype = None
-        L.nrf_iq_chain_free.argtypes = [vp]
-        bind_iq_draw(L)
-        bind_demod(L)
-        bind_interpolator(L)
-        _LIB = L
+        _LIB = bind(ctypes.CDLL(path), NUT_TABLE, *NRF_TABLES)
     return _LIB
 
 

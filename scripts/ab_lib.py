@@ -9,6 +9,9 @@ import sys
 import numpy as np
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from frequensea_amd import fsea  # noqa: E402  (fsea.API: the prototypes)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 old = sys.argv[1]
 new = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "frequensea_amd", "libfsea_hip.so")
@@ -19,8 +22,7 @@ sets, launches, rounds = 6, 200, 12
 libs = []
 for path in (old, new):
     L = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-    L.fsea_plan_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.fsea_exec_u8_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    fsea.declare(L, ("fsea_plan_create", "fsea_exec_u8_device"))
     p = ctypes.c_void_p()
     assert L.fsea_plan_create(ctypes.byref(p), n, n, 0, 0) == 0
     libs.append((os.path.basename(path), L, p))

@@ -11,6 +11,9 @@ import time
 import numpy as np
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from frequensea_amd import fsea  # noqa: E402  (fsea.API: the prototypes)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 args = sys.argv[1:]
 sizes = [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384]
@@ -27,11 +30,7 @@ stream = torch.cuda.current_stream().cuda_stream
 libs = []
 for path in paths:
     L = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-    L.fsea_plan_create.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci]
-    L.fsea_plan_destroy.argtypes = [vp]
-    L.fsea_exec_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
-    L.fsea_plan_kernel_name.argtypes = [vp]
-    L.fsea_plan_kernel_name.restype = ctypes.c_char_p
+    fsea.declare(L, ("fsea_plan_create", "fsea_plan_destroy", "fsea_exec_u8_device", "fsea_plan_kernel_name"))
     libs.append((os.path.basename(path), L))
 host = np.random.default_rng(1).integers(-70, 70, 2 * TOTAL, dtype=np.int8)
 d_in = torch.from_numpy(host).to(dev)

@@ -13,6 +13,9 @@ import time
 import numpy as np
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from frequensea_amd import fsea  # noqa: E402  (fsea.API: the prototypes)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 paths = sys.argv[1:] + [os.path.join(ROOT, "frequensea_amd", "libfsea_hip.so")]
 vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
@@ -22,9 +25,7 @@ stream = torch.cuda.current_stream().cuda_stream
 
 def load(path):
     L = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-    L.fsea_plan_create.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci]
-    L.fsea_exec_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
-    L.fsea_exec_u8_tiled_device.argtypes = [vp, vp, sz, ci, vp, sz, sz, sz, sz, sz, vp]
+    fsea.declare(L, ("fsea_plan_create", "fsea_exec_u8_device", "fsea_exec_u8_tiled_device"))
     return L
 
 

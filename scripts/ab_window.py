@@ -10,6 +10,9 @@ import time
 import numpy as np
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from frequensea_amd import fsea  # noqa: E402  (fsea.API: the prototypes)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 paths = sys.argv[1:] + [os.path.join(ROOT, "frequensea_amd", "libfsea_hip.so")]
 vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
@@ -25,9 +28,7 @@ w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(n) / n)).astype(np.float32)
 plans = []
 for path in paths:
     L = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-    L.fsea_plan_create.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci]
-    L.fsea_exec_u8_device.argtypes = [vp, vp, sz, ci, vp, vp]
-    L.fsea_plan_set_window.argtypes = [vp, vp]
+    fsea.declare(L, ("fsea_plan_create", "fsea_exec_u8_device", "fsea_plan_set_window"))
     for tag in ("rect", "hann"):
         p = vp()
         assert L.fsea_plan_create(ctypes.byref(p), n, hop, 0, 0) == 0

@@ -11,7 +11,6 @@ fsea.use_tune_library()
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
 frames = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 L = fsea.hip_lib()
-L.fsea_plan_read_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
 def dev_alloc(nbytes):
     p = ctypes.c_void_p(); fsea._check(L.fsea_device_alloc(0, nbytes, ctypes.byref(p))); return p
 sets = 8

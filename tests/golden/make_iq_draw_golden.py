@@ -136,13 +136,9 @@ def main():
         L = build_reference(gen, tmp)
         nrf.bind_iq_draw(nrf.bind_nut(L))
         vp = ctypes.c_void_p
-        L.nrf_device_new.restype = vp
-        L.nrf_device_new.argtypes = [ctypes.c_double, ctypes.c_char_p]
-        L.nrf_device_set_paused.argtypes = [vp, ctypes.c_int]
-        L.nrf_device_step.argtypes = [vp]
-        L.nrf_device_get_samples_buffer.restype = nrf.NutBufferP
-        L.nrf_device_get_samples_buffer.argtypes = [vp]
-        L.nrf_device_free.argtypes = [vp]
+        nrf.bind(L, {name: nrf.API[name] for name in (
+                    "nrf_device_new", "nrf_device_set_paused", "nrf_device_step",
+                    "nrf_device_get_samples_buffer", "nrf_device_free")})
 
         def take(buf):
             out = nrf.buffer_to_numpy(L, buf)

@@ -136,17 +136,10 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         L = nrf.bind_fir(nrf.bind_nut(build_reference(tmp)))
         vp = ctypes.c_void_p
-        L.nrf_iq_filter_new.restype = vp
-        L.nrf_iq_filter_new.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.nrf_iq_filter_process.argtypes = [vp, nrf.NutBufferP]
-        L.nrf_iq_filter_get_buffer.restype = nrf.NutBufferP
-        L.nrf_iq_filter_get_buffer.argtypes = [vp]
-        L.nrf_iq_filter_free.argtypes = [vp]
-        L.nrf_freq_shifter_new.restype = vp
-        L.nrf_freq_shifter_new.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.nrf_freq_shifter_process.argtypes = [vp, nrf.NutBufferP]
-        L.nrf_freq_shifter_get_buffer.restype = nrf.NutBufferP
-        L.nrf_freq_shifter_get_buffer.argtypes = [vp]
+        nrf.bind(L, {name: nrf.API[name] for name in (
+                    "nrf_iq_filter_new", "nrf_iq_filter_process", "nrf_iq_filter_get_buffer",
+                    "nrf_iq_filter_free", "nrf_freq_shifter_new", "nrf_freq_shifter_process",
+                    "nrf_freq_shifter_get_buffer")})
 
         def taps(rate, cutoff, length):
             m = length + (length + 1) % 2

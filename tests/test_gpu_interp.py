@@ -10,7 +10,6 @@ import pytest
 
 from frequensea_amd import fsea, nrf
 from tests import interp_ref as R
-from tests.test_gpu_iq_draw import DeviceBuffer
 from tests.test_interp_host import GOLDEN, TOOL, generator, sha
 
 pytestmark = pytest.mark.gpu
@@ -105,10 +104,10 @@ def test_sample_form_host_and_device(kind):
             assert same(ip.frames(w[f:f + 1])[0], got[f])
         assert ip.frames([]).shape == (0, n)
         # device form, on a stream, into a buffer with guard bytes behind it
-        d_w, d_out = DeviceBuffer(w.nbytes, w), DeviceBuffer(want.nbytes + 64, np.full(want.nbytes + 64, 0xA5, np.uint8))
+        d_w, d_out = fsea.DeviceBuffer(w.nbytes).upload(w), fsea.DeviceBuffer(want.nbytes + 64).upload(np.full(want.nbytes + 64, 0xA5, np.uint8))
         ip.frames_device(d_w.ptr, len(w), d_out.ptr)
         fsea._check(ip._L.fsea_interp_frames_device(ip._p, d_w.ptr, 0, None, None))   # n_frames 0: nothing happens
-        raw = d_out.get()
+        raw = d_out.download(np.uint8, d_out.nbytes)
         assert raw[:want.nbytes].tobytes() == want.tobytes() and np.all(raw[want.nbytes:] == 0xA5), (kind, n)
         ip.reset()
         assert same(ip.frames([0.7]), np.zeros((1, n), a.dtype))
@@ -124,9 +123,9 @@ def test_push_order_on_one_stream_and_two_objects_on_two_streams():
     for s in streams:
         fsea._check(L.fsea_stream_create(0, ctypes.byref(s)))
     objs = [fsea.Interp(np.uint8, n), fsea.Interp(np.uint8, n)]
-    d_w = DeviceBuffer(w.nbytes, w)
-    d_blocks = [DeviceBuffer(n, b) for b in blocks]
-    outs = [[DeviceBuffer(len(w) * n) for _ in blocks] for _ in objs]
+    d_w = fsea.DeviceBuffer(w.nbytes).upload(w)
+    d_blocks = [fsea.DeviceBuffer(n).upload(b) for b in blocks]
+    outs = [[fsea.DeviceBuffer(len(w) * n) for _ in blocks] for _ in objs]
     # object 0 takes the blocks in order, object 1 in reverse; pushes and frames alternate without any wait
     order = [list(range(5)), list(range(4, -1, -1))]
     for k in range(5):
@@ -138,7 +137,7 @@ def test_push_order_on_one_stream_and_two_objects_on_two_streams():
     for o in range(2):
         for k in range(5):
             a = blocks[order[o][k - 1]] if k else np.zeros(n, np.uint8)
-            assert same(outs[o][k].get().reshape(len(w), n), R.blend_frames(a, blocks[order[o][k]], w)), (o, k)
+            assert same(outs[o][k].download(np.uint8, outs[o][k].nbytes).reshape(len(w), n), R.blend_frames(a, blocks[order[o][k]], w)), (o, k)
     for b in [d_w] + d_blocks + outs[0] + outs[1]:
         b.free()
     for s in streams:
@@ -155,9 +154,9 @@ def test_image_form_at_the_tools_geometry(gold):
     for pair in range(2):
         ip.push(caps[pair + 1])
         w = np.array(eased + extra)
-        d_w, d_img = DeviceBuffer(w.nbytes, w), DeviceBuffer(len(w) * 1920 * 1080)
+        d_w, d_img = fsea.DeviceBuffer(w.nbytes).upload(w), fsea.DeviceBuffer(len(w) * 1920 * 1080)
         ip.image_frames_device(d_w.ptr, len(w), 1920, 1080, 256, d_img.ptr)
-        got = d_img.get().reshape(len(w), 1080, 1920)
+        got = d_img.download(np.uint8, d_img.nbytes).reshape(len(w), 1080, 1920)
         d_w.free(), d_img.free()
         for k in range(100):                                   # the reference binary's own frames
             assert np.array_equal(sha(got[k]), gold["movie__sha256"][100 * pair + k]), (pair, k)
@@ -183,10 +182,10 @@ def test_image_form_odd_geometries(width, height, iq_size):
     w = np.concatenate([np.linspace(-0.2, 1.2, 19), [np.nan]])
     want = R.image_frames(a, b, w, width, height, iq_size)
     assert same(ip.image_frames(w, width, height, iq_size), want)
-    d_w = DeviceBuffer(w.nbytes, w)
-    d_img = DeviceBuffer(want.nbytes + 64, np.full(want.nbytes + 64, 0xA5, np.uint8))
+    d_w = fsea.DeviceBuffer(w.nbytes).upload(w)
+    d_img = fsea.DeviceBuffer(want.nbytes + 64).upload(np.full(want.nbytes + 64, 0xA5, np.uint8))
     ip.image_frames_device(d_w.ptr, len(w), width, height, iq_size, d_img.ptr)
-    raw = d_img.get()
+    raw = d_img.download(np.uint8, d_img.nbytes)
     assert raw[:want.nbytes].tobytes() == want.tobytes() and np.all(raw[want.nbytes:] == 0xA5)
     d_w.free(), d_img.free(), ip.close()
 
@@ -258,7 +257,7 @@ def test_argument_errors_come_before_device_work():
     ip, f64 = fsea.Interp(np.uint8, 2 * 16 * 16), fsea.Interp(np.float64, 2 * 16 * 16)
     w = np.zeros(4)
     out = np.zeros(4 * 512 + 4096, dtype=np.uint8)
-    d = DeviceBuffer(8192)
+    d = fsea.DeviceBuffer(8192)
     g = fsea.InterpGeometry(32, 32, 16, 1)
     gp = ctypes.byref(g)
     assert L.fsea_interp_push_host(ip._p, None) == EINVAL

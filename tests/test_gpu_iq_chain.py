@@ -42,28 +42,6 @@ def block():
         return np.ascontiguousarray(z["block__raw"] ^ 0x80)
 
 
-class DeviceBuffers:
-    """Device memory for n_bytes_in of input and n_bytes_out of output (fsea_device_alloc)."""
-
-    def __init__(self, n_bytes_in, n_bytes_out):
-        self.L = fsea.hip_lib()
-        self.d_in, self.d_out = ctypes.c_void_p(), ctypes.c_void_p()
-        fsea._check(self.L.fsea_device_alloc(0, max(n_bytes_in, 16), ctypes.byref(self.d_in)))
-        fsea._check(self.L.fsea_device_alloc(0, max(n_bytes_out, 16), ctypes.byref(self.d_out)))
-
-    def put(self, a):
-        fsea._check(self.L.fsea_copy_to_device(0, self.d_in, a.ctypes.data, a.nbytes))
-
-    def get(self, dtype, count, byte_offset=0):
-        out = np.empty(count, dtype=dtype)
-        fsea._check(self.L.fsea_copy_to_host(0, out.ctypes.data, ctypes.c_void_p(self.d_out.value + byte_offset), out.nbytes))
-        return out
-
-    def close(self):
-        fsea._check(self.L.fsea_device_free(0, self.d_in))
-        fsea._check(self.L.fsea_device_free(0, self.d_out))
-
-
 def bits(y):
     return np.ascontiguousarray(y).view(np.uint64)
 
@@ -80,10 +58,10 @@ def test_shifted_sizes_against_the_restatement(L, flip):
     c = random_taps(L, L)
     fir = fsea.Fir(c)
     rng = np.random.default_rng(2000 + L)
-    dev = DeviceBuffers(2 * max(COUNTS), 8 * max(COUNTS))
+    d_in, d_out = fsea.DeviceBuffer(2 * max(COUNTS)), fsea.DeviceBuffer(8 * max(COUNTS))
     for n in COUNTS:
         iq = rng.integers(0, 256, 2 * n, dtype=np.uint8)
-        dev.put(iq)
+        d_in.upload(iq)
         for cps in CYCLES:
             for phase0 in PHASES:
                 want, _ = shifted_fir_reference(iq, flip, cps, phase0, c)
@@ -91,11 +69,12 @@ def test_shifted_sizes_against_the_restatement(L, flip):
                 got = fir.run_u8_shifted(iq, cps, phase0, flip=bool(flip))
                 check(got, want, ("host", L, n, flip, cps, phase0))
                 fir.reset()
-                fir.run_shifted_device(dev.d_in.value, n, dev.d_out.value, cps, phase0, flip=bool(flip))
-                got_d = dev.get(np.complex64, n)
+                fir.run_shifted_device(d_in.ptr.value, n, d_out.ptr.value, cps, phase0, flip=bool(flip))
+                got_d = d_out.download(np.complex64, n)
                 check(got_d, want, ("device", L, n, flip, cps, phase0))
                 assert np.array_equal(bits(got), bits(got_d)), (L, n, flip, cps, phase0)
-    dev.close()
+    d_in.free()
+    d_out.free()
     fir.close()
 
 
@@ -124,24 +103,25 @@ def test_a_stream_cut_anywhere_is_the_one_call_result_bit_for_bit(L):
     assert np.array_equal(bits(np.concatenate(got)), bits(want))
     # the device form: pieces that start on 8-sample boundaries of the input buffer (16-byte alignment), each written at its
     # own place in the output
-    dev = DeviceBuffers(2 * n, 8 * n)
-    dev.put(iq)
+    d_in, d_out = fsea.DeviceBuffer(2 * n), fsea.DeviceBuffer(8 * n)
+    d_in.upload(iq)
     runs = []
     for _ in range(2):
         whole.reset()
-        whole.run_shifted_device(dev.d_in.value, n, dev.d_out.value, cps, phase0, flip=True)
-        runs.append(dev.get(np.complex64, n))
+        whole.run_shifted_device(d_in.ptr.value, n, d_out.ptr.value, cps, phase0, flip=True)
+        runs.append(d_out.download(np.complex64, n))
     assert np.array_equal(bits(runs[0]), bits(runs[1])) and np.array_equal(bits(runs[0]), bits(want))
     parts.reset()
     pos = 0
     for k in [8, 4096, 70000, 8 * 12345, 2048 + 8]:
-        parts.run_shifted_device(dev.d_in.value + 2 * pos, k, dev.d_out.value + 8 * pos, cps, phase0, sample_offset=pos,
+        parts.run_shifted_device(d_in.ptr.value + 2 * pos, k, d_out.ptr.value + 8 * pos, cps, phase0, sample_offset=pos,
                                  flip=True)
         pos += k
-    parts.run_shifted_device(dev.d_in.value + 2 * pos, n - pos, dev.d_out.value + 8 * pos, cps, phase0, sample_offset=pos,
+    parts.run_shifted_device(d_in.ptr.value + 2 * pos, n - pos, d_out.ptr.value + 8 * pos, cps, phase0, sample_offset=pos,
                              flip=True)
-    assert np.array_equal(bits(dev.get(np.complex64, n)), bits(want))
-    dev.close()
+    assert np.array_equal(bits(d_out.download(np.complex64, n)), bits(want))
+    d_in.free()
+    d_out.free()
     whole.close()
     parts.close()
 
@@ -362,20 +342,21 @@ def test_batched_device_form_equals_single_calls_byte_for_byte(block, shifted, n
         want.append(single.run(stream[2 * n * f:2 * n * (f + 1)], st, points=True, lines_m=m, n_line_points=n_line, pairs=True))
     single.close()
     pts, lns, prs = frames * 65536, frames * (256 * m) ** 2, frames * per * 8
-    dev = DeviceBuffers(stream.nbytes, pts + lns + prs)
-    dev.put(stream)
+    d_in, d_out = fsea.DeviceBuffer(stream.nbytes), fsea.DeviceBuffer(pts + lns + prs)
+    d_in.upload(stream)
     batched = fsea.Chain(c)
     st = fsea.Chain.stage(cycles_per_sample=cps, n_zero=n_zero) if shifted else None
-    base = dev.d_out.value
-    batched.run_device(dev.d_in.value, n, frames, st, d_points=base, d_lines=base + pts, lines_m=m, n_line_points=n_line,
+    base = d_out.ptr.value
+    batched.run_device(d_in.ptr.value, n, frames, st, d_points=base, d_lines=base + pts, lines_m=m, n_line_points=n_line,
                        d_pairs=base + pts + lns)
-    got_p = dev.get(np.uint8, pts).reshape(frames, 256, 256)
-    got_l = dev.get(np.uint8, lns, pts).reshape(frames, 256 * m, 256 * m)
-    got_y = dev.get(np.complex64, frames * per, pts + lns).reshape(frames, per)
+    got_p = d_out.download(np.uint8, pts).reshape(frames, 256, 256)
+    got_l = d_out.download(np.uint8, lns, pts).reshape(frames, 256 * m, 256 * m)
+    got_y = d_out.download(np.complex64, frames * per, pts + lns).reshape(frames, per)
     for f in range(frames):
         assert np.array_equal(bits(got_y[f]), bits(want[f]["pairs"])), f
         assert np.array_equal(got_p[f], want[f]["points"]) and np.array_equal(got_l[f], want[f]["lines"]), f
         assert int(got_l[f].max()) > 0
     assert batched.n_pairs == per
     batched.close()
-    dev.close()
+    d_in.free()
+    d_out.free()

@@ -42,23 +42,7 @@ def take(L, buf):
     return out, meta
 
 
-class DeviceBuffer:
-    def __init__(self, nbytes, host=None):
-        self.L = fsea.hip_lib()
-        self.nbytes = nbytes
-        self.ptr = ctypes.c_void_p()
-        fsea._check(self.L.fsea_device_alloc(0, max(nbytes, 16), ctypes.byref(self.ptr)))
-        if host is not None:
-            h = np.ascontiguousarray(host)
-            fsea._check(self.L.fsea_copy_to_device(0, self.ptr, h.ctypes.data, h.nbytes))
-
-    def get(self, dtype=np.uint8):
-        out = np.empty(self.nbytes // np.dtype(dtype).itemsize, dtype=dtype)
-        fsea._check(self.L.fsea_copy_to_host(0, out.ctypes.data, self.ptr, self.nbytes))
-        return out
-
-    def free(self):
-        fsea._check(self.L.fsea_device_free(0, self.ptr))
+DeviceBuffer = fsea.DeviceBuffer
 
 
 @pytest.mark.parametrize("name", INPUTS)
@@ -193,10 +177,10 @@ def test_device_chain_fir_into_lines_equals_the_nrf_chain(length):
 
     fir = fsea.Fir(fsea.lowpass_taps(5000000, 200000, length))
     draw = fsea.IqDraw()
-    d_in, d_f, d_img = DeviceBuffer(block.nbytes, block), DeviceBuffer(8 * n), DeviceBuffer((256 * m) ** 2)
+    d_in, d_f, d_img = DeviceBuffer(block.nbytes).upload(block), DeviceBuffer(8 * n), DeviceBuffer((256 * m) ** 2)
     fir.run_device(d_in.ptr.value, n, d_f.ptr.value, flip=True)
     draw.lines_device(d_f.ptr.value, fsea.IQ_F32, line_points(2 * n, pct), 1, m, d_img.ptr.value)
-    got = d_img.get()
+    got = d_img.download(np.uint8, d_img.nbytes)
     for b in (d_in, d_f, d_img):
         b.free()
     fir.close()
@@ -214,16 +198,16 @@ def test_batched_device_forms_equal_per_frame_calls(draw, kind):
         else:
             iq = rng.uniform(-0.2, 1.2, 2 * n * n_frames).astype(dtype)
         frames = iq.reshape(n_frames, -1)
-        d_in = DeviceBuffer(iq.nbytes, iq)
+        d_in = DeviceBuffer(iq.nbytes).upload(iq)
         d_pts = DeviceBuffer(65536 * n_frames)
         draw.points_device(d_in.ptr.value, kind, n, n_frames, d_pts.ptr.value)
-        got = d_pts.get().reshape(n_frames, 256, 256)
+        got = d_pts.download(np.uint8, (n_frames, 256, 256))
         for f in range(n_frames):
             assert np.array_equal(got[f], draw.points(frames[f])), (n_frames, n, f)
         m = 2
         d_lines = DeviceBuffer((256 * m) ** 2 * n_frames)
         draw.lines_device(d_in.ptr.value, kind, n, n_frames, m, d_lines.ptr.value)
-        got = d_lines.get().reshape(n_frames, 256 * m, 256 * m)
+        got = d_lines.download(np.uint8, (n_frames, 256 * m, 256 * m))
         for f in range(n_frames):
             assert np.array_equal(got[f], draw.lines(frames[f], m=m)), (n_frames, n, f)
         for b in (d_in, d_pts, d_lines):

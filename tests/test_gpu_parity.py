@@ -18,27 +18,7 @@ pytestmark = pytest.mark.gpu
 SIZES = [32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384]
 
 
-class DeviceBuffer:
-    def __init__(self, nbytes, device=0):
-        self.ptr = ctypes.c_void_p()
-        self.nbytes = nbytes
-        self.device = device
-        fsea._check(fsea.hip_lib().fsea_device_alloc(device, nbytes, ctypes.byref(self.ptr)))
-
-    def upload(self, arr):
-        arr = np.ascontiguousarray(arr)
-        fsea._check(fsea.hip_lib().fsea_copy_to_device(self.device, self.ptr, arr.ctypes.data, arr.nbytes))
-        return self
-
-    def download(self, dtype, shape):
-        out = np.empty(shape, dtype=dtype)
-        fsea._check(fsea.hip_lib().fsea_copy_to_host(self.device, out.ctypes.data, self.ptr, out.nbytes))
-        return out
-
-    def free(self):
-        if self.ptr:
-            fsea.hip_lib().fsea_device_free(self.device, self.ptr)
-            self.ptr = ctypes.c_void_p()
+DeviceBuffer = fsea.DeviceBuffer
 
 
 @pytest.fixture(params=["auto", "tickets", "static"])
@@ -1593,14 +1573,10 @@ def test_captured_streams_give_their_counter_slot_back():
     fsea_stream_create: torch.cuda.Stream() hands out 32 pooled handles round-robin.)"""
     torch = pytest.importorskip("torch")
     dev = torch.device("cuda", 0)
-    L = fsea.hip_lib()
-    L.fsea_stream_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-    L.fsea_stream_destroy.argtypes = [ctypes.c_int, ctypes.c_void_p]
 
     def new_stream():
-        h = ctypes.c_void_p()
-        fsea._check(L.fsea_stream_create(0, ctypes.byref(h)))
-        return h.value, torch.cuda.ExternalStream(h.value, device=dev)
+        s = fsea.Stream(0)
+        return s, torch.cuda.ExternalStream(s.handle.value, device=dev)
 
     n, nf = 8192, 96
     iq = torch.from_numpy(synth_iq(83, 2 * nf * n).copy()).to(dev)
@@ -1613,7 +1589,7 @@ def test_captured_streams_give_their_counter_slot_back():
     seen = set()
     for rnd in range(80):
         handle, side = new_stream()
-        seen.add(handle)
+        seen.add(handle.handle.value)
         side.wait_stream(torch.cuda.current_stream())
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
@@ -1625,7 +1601,7 @@ def test_captured_streams_give_their_counter_slot_back():
         del graph
         plan.release_stream(handle)
         del side
-        fsea._check(L.fsea_stream_destroy(0, handle))
+        handle.close()
     plan.release_stream(0)                                  # a stream without a slot: nothing to do, FSEA_OK
     plan.close()
     plan = fsea.Plan(n)
@@ -1651,7 +1627,7 @@ def test_captured_streams_give_their_counter_slot_back():
     plan.reset()
     plan.close()
     for h in handles:
-        fsea._check(L.fsea_stream_destroy(0, h))
+        h.close()
 
 
 def test_windowed_launches_capture_too_and_the_anysize_paths_refuse_a_capturing_stream():
@@ -1698,16 +1674,9 @@ def test_streams_and_asynchronous_copies_of_the_c_abi():
     L = fsea.hip_lib()
     n, nf, batches = 2048, 300, 6
     plan = fsea.Plan(n, mode=fsea.MODE_DB10_U8)
-    vp = ctypes.c_void_p
-    L.fsea_stream_create.argtypes = [ctypes.c_int, ctypes.POINTER(vp)]
-    L.fsea_stream_destroy.argtypes = [ctypes.c_int, vp]
-    L.fsea_copy_to_device_async.argtypes = [ctypes.c_int, vp, vp, ctypes.c_size_t, vp]
-    L.fsea_copy_to_host_async.argtypes = [ctypes.c_int, vp, vp, ctypes.c_size_t, vp]
     slots = []
     for k in range(2):
-        st = vp()
-        fsea._check(L.fsea_stream_create(0, ctypes.byref(st)))
-        slots.append((st, DeviceBuffer(2 * nf * n), DeviceBuffer(nf * n), fsea.PinnedArray((2 * nf * n,), np.uint8),
+        slots.append((fsea.Stream(0), DeviceBuffer(2 * nf * n), DeviceBuffer(nf * n), fsea.PinnedArray((2 * nf * n,), np.uint8),
                       fsea.PinnedArray((nf, n), np.uint8)))
     iqs = [synth_iq(90 + b, 2 * nf * n) for b in range(batches)]
     got = []
@@ -1719,7 +1688,7 @@ def test_streams_and_asynchronous_copies_of_the_c_abi():
         if b < batches:
             h_in.array[:] = iqs[b]
             fsea._check(L.fsea_copy_to_device_async(0, d_in.ptr, h_in.array.ctypes.data, h_in.array.nbytes, st))
-            plan.exec_device(d_in.ptr, nf, d_out.ptr, stream=st.value)
+            plan.exec_device(d_in.ptr, nf, d_out.ptr, stream=st)
             fsea._check(L.fsea_copy_to_host_async(0, h_out.array.ctypes.data, d_out.ptr, nf * n, st))
     for b in range(batches):
         parity.check_mode(got[b], iqs[b], n, nf, n, True, fsea.MODE_DB10_U8)
@@ -1728,7 +1697,7 @@ def test_streams_and_asynchronous_copies_of_the_c_abi():
         d_out.free()
         h_in.close()
         h_out.close()
-        fsea._check(L.fsea_stream_destroy(0, st))
+        st.close()
     plan.close()
 
 

@@ -10,7 +10,6 @@ import pytest
 from frequensea_amd import fsea
 from tests import trace_ref as R
 from tests.test_gpu_interp import read_png
-from tests.test_gpu_iq_draw import DeviceBuffer
 from tests.test_trace_host import GOLDEN, TOOL, check_case, generator, sha
 
 pytestmark = pytest.mark.gpu
@@ -30,15 +29,15 @@ def same(got, want):
 
 def device_frames(tr, data, s, n, images=True, guard=64, stream=0):
     """n frames through the device form in one call: (frames, guard bytes behind them)."""
-    d_in = DeviceBuffer(data.size, data)
+    d_in = fsea.DeviceBuffer(data.size).upload(data)
     size = n * tr.width * tr.height
-    d_out = DeviceBuffer(size + guard, np.full(size + guard, 0xA5, np.uint8)) if images else None
+    d_out = fsea.DeviceBuffer(size + guard).upload(np.full(size + guard, 0xA5, np.uint8)) if images else None
     tr.frames_device(d_in.ptr, data.size, s, n, d_out.ptr if images else 0, stream=stream)
     if not images:
         tr.canvas()                                        # waits for the launches
         d_in.free()
         return None, None
-    raw = d_out.get()
+    raw = d_out.download(np.uint8, d_out.nbytes)
     d_in.free(), d_out.free()
     return raw[:size].reshape(n, tr.height, tr.width), raw[size:]
 
@@ -141,9 +140,9 @@ def test_two_objects_on_two_streams():
         fsea._check(L.fsea_stream_create(0, ctypes.byref(st)))
     cfg = [(40, 3, 1024), (100, 0, 4096)]
     objs = [fsea.Trace(pixel_inc=p, fade=f) for p, f, _ in cfg]
-    d_in = DeviceBuffer(data.size, data)
+    d_in = fsea.DeviceBuffer(data.size).upload(data)
     calls = 4
-    outs = [[DeviceBuffer((16384 // s // calls) * W * H) for _ in range(calls)] for _, _, s in cfg]
+    outs = [[fsea.DeviceBuffer((16384 // s // calls) * W * H) for _ in range(calls)] for _, _, s in cfg]
     # every object takes its capture in four calls, the two alternating without any wait
     for c in range(calls):
         for o, (_, _, s) in enumerate(cfg):
@@ -156,7 +155,7 @@ def test_two_objects_on_two_streams():
         nf = 16384 // s // calls
         want = R.frames(data, s, 16384 // s, p=p, f=f)[0]
         for c in range(calls):
-            assert same(outs[o][c].get().reshape(nf, H, W), want[c * nf:(c + 1) * nf]), (o, c)
+            assert same(outs[o][c].download(np.uint8, outs[o][c].nbytes).reshape(nf, H, W), want[c * nf:(c + 1) * nf]), (o, c)
     for b in [d_in] + outs[0] + outs[1]:
         b.free()
     for st in streams:

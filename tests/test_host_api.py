@@ -16,10 +16,40 @@ from oracle import oracle as O
 from tests.conftest import ROOT, synth_iq
 
 
-def declared_functions(header):
+def declared_functions(header, parameters=False):
+    """The functions a header declares; with parameters=True a dict name -> number of parameters of the prototype."""
     text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b((?:fsea|nut|nrf)_[a-z0-9_]+)\s*\(", text))
+    names = set(re.findall(r"\b((?:fsea|nut|nrf)_[a-z0-9_]+)\s*\(", text))
+    if not parameters:
+        return names
+    counts = {}
+    for name, params in re.findall(r"\b((?:fsea|nut|nrf)_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        counts[name] = 0 if params.strip() in ("", "void") else params.count(",") + 1
+    return counts
+
+
+def test_every_entry_point_is_declared_once_with_the_headers_parameter_count():
+    """Each exported function has argtypes once its library is loaded, as many as its prototype has parameters: a 64-bit
+    handle passed as a plain int to a function without argtypes is converted as a C int."""
+    import json
+    import subprocess
+    import sys
+    # the tuning library replaces the product library for a whole process (fsea.use_tune_library): ask a fresh one
+    code = ("import json; from frequensea_amd import fsea; fsea.use_tune_library(); L = fsea.hip_lib(); "
+            "print(json.dumps({n: None if getattr(L, n).argtypes is None else len(getattr(L, n).argtypes) "
+            "for n in fsea.EXPORTS + fsea.TUNE_EXPORTS}))")
+    tune = json.loads(subprocess.check_output([sys.executable, "-c", code], cwd=ROOT).decode())
+
+    def bound(L, names):
+        return {n: None if getattr(L, n).argtypes is None else len(getattr(L, n).argtypes) for n in names}
+
+    for got, headers in ((bound(fsea.hip_lib(), fsea.EXPORTS), ("fsea.h",)), (tune, ("fsea.h", "fsea_tune.h")),
+                         (bound(nrf.nrf_lib(), nrf.NUT_EXPORTS + nrf.NRF_EXPORTS + nrf.NRF_ADDITIONS), ("nut.h", "nrf.h"))):
+        want = {}
+        for header in headers:
+            want.update(declared_functions(header, parameters=True))
+        assert got == {name: want[name] for name in got}, {n: (got[n], want[n]) for n in got if got[n] != want[n]}
 
 
 def test_fsea_exports_every_declared_symbol():

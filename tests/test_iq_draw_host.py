@@ -263,7 +263,7 @@ def test_iq_draw_create_needs_a_device():
 
 def test_iq_draw_python_wrapper_rejects_more_points_than_given():
     draw = fsea.IqDraw.__new__(fsea.IqDraw)                # no device: the check comes before the library call
-    draw._d = ctypes.c_void_p()
+    draw._p = ctypes.c_void_p()
     with pytest.raises(ValueError, match="n_points"):
         draw.lines(np.zeros(8, np.uint8), m=1, n_points=5)
     with pytest.raises(ValueError, match="n_points"):

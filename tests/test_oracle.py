@@ -230,12 +230,8 @@ def test_reference_nut_conventions():
     path = os.path.join(ROOT, "oracle", "_ref", "libnut_ref.so")
     if not os.path.exists(path):
         return
-    L = ctypes.CDLL(path)
-    L.nut_buffer_new_u8.restype = ctypes.c_void_p
-    L.nut_buffer_new_u8.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    L.nut_buffer_get_f64.restype = ctypes.c_double
-    L.nut_buffer_get_f64.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.nut_buffer_free.argtypes = [ctypes.c_void_p]
+    from frequensea_amd import nrf
+    L = nrf.bind_nut(ctypes.CDLL(path))
     data = np.arange(256, dtype=np.uint8)
     buf = L.nut_buffer_new_u8(128, 2, data.ctypes.data)
     for k in (0, 1, 128, 255):
