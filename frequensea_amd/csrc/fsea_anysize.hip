@@ -164,71 +164,7 @@ __global__ void fsea_fs_epilogue_kernel(const fsea::cf *B, int add_dc, int n1, i
     }
 }
 
-void host_fft(std::vector<double> &re, std::vector<double> &im);
-
-}  // namespace
-
-namespace fsea_detail {
-
-// One Bluestein pass over n_frames frames (in chunks that fit the work buffers): prep -> FFT_m -> x chirp spectrum -> FFT_m ->
-// epilogue, all on stream `s`.  d_in: u8 IQ or f32 complex (device, or device-mapped host memory), frame f at sample f * hop.
-int blu_launch(fsea_plan *p, int in_kind, const void *d_in, size_t n_frames, int flip, int mode, void *d_out, hipStream_t s) {
-    if (n_frames == 0) return FSEA_OK;
-    const int n = p->n, m = p->blu_m;
-    const size_t esz = mode_elem_bytes(mode);
-    const size_t in_bps = (in_kind == fsea::IN_F32) ? 8 : 2;
-    for (size_t f0 = 0; f0 < n_frames; f0 += p->blu_work_frames) {
-        const size_t nf = (n_frames - f0 < p->blu_work_frames) ? n_frames - f0 : p->blu_work_frames;
-        const size_t total = nf * (size_t)m;
-        unsigned blocks = (unsigned)((total + 255) / 256);
-        if (blocks > 8192) blocks = 8192;
-        const char *src = static_cast<const char *>(d_in) + f0 * (size_t)p->hop * in_bps;
-        hipLaunchKernelGGL(fsea_blu_prep_kernel, dim3(blocks), dim3(256), 0, s, static_cast<const void *>(src),
-                           in_kind == fsea::IN_F32 ? 1 : 0, flip ? 0u : 0x80u, (size_t)p->hop, n, m, p->d_blu_chirp, p->d_blu_work[0], nf);
-        int rc = launch(p->blu_inner, fsea::IN_F32, p->d_blu_work[0], nf, 0, FSEA_MODE_COMPLEX_F32, p->d_blu_work[1], s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(fsea_blu_mul_kernel, dim3(blocks), dim3(256), 0, s, p->d_blu_work[1], p->d_blu_bfft, p->d_blu_work[0], m, nf);
-        rc = launch(p->blu_inner, fsea::IN_F32, p->d_blu_work[0], nf, 0, FSEA_MODE_COMPLEX_F32, p->d_blu_work[1], s);
-        if (rc) return rc;
-        unsigned eblocks = (unsigned)((nf * (size_t)n + 255) / 256);
-        if (eblocks > 8192) eblocks = 8192;
-        hipLaunchKernelGGL(fsea_blu_epilogue_kernel, dim3(eblocks), dim3(256), 0, s, p->d_blu_work[1], p->d_blu_chirp,
-                           in_kind == fsea::IN_F32 ? nullptr : p->d_blu_dc, n, m, mode,
-                           static_cast<void *>(static_cast<char *>(d_out) + f0 * (size_t)n * esz), nf);
-        FSEA_HIP(hipGetLastError());
-    }
-    return FSEA_OK;
-}
-
-// One four-step pass over n_frames frames (in chunks that fit the work buffers, shared with the Bluestein fields).
-int fs_launch(fsea_plan *p, int in_kind, const void *d_in, size_t n_frames, int flip, int mode, void *d_out, hipStream_t s) {
-    if (n_frames == 0) return FSEA_OK;
-    const int n1 = p->fs_n1, n2 = p->fs_n2;
-    const size_t n = (size_t)p->n, esz = mode_elem_bytes(mode);
-    const size_t in_bps = (in_kind == fsea::IN_F32) ? 8 : 2;
-    for (size_t f0 = 0; f0 < n_frames; f0 += p->blu_work_frames) {
-        const size_t nf = (n_frames - f0 < p->blu_work_frames) ? n_frames - f0 : p->blu_work_frames;
-        unsigned blocks = (unsigned)((nf * n + 255) / 256);
-        if (blocks > 16384) blocks = 16384;
-        const char *src = static_cast<const char *>(d_in) + f0 * (size_t)p->hop * in_bps;
-        hipLaunchKernelGGL(fsea_fs_prep_kernel, dim3(blocks), dim3(256), 0, s, static_cast<const void *>(src),
-                           in_kind == fsea::IN_F32 ? 1 : 0, flip ? 0u : 0x80u, (size_t)p->hop, n1, n2, p->d_blu_work[0], nf);
-        int rc = launch(p->fs_inner1, fsea::IN_F32, p->d_blu_work[0], nf * (size_t)n2, 0, FSEA_MODE_COMPLEX_F32, p->d_blu_work[1], s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(fsea_fs_twiddle_kernel, dim3(blocks), dim3(256), 0, s, p->d_blu_work[1], p->d_fs_tw, p->d_blu_work[0], n1, n2, nf);
-        rc = launch(p->fs_inner2, fsea::IN_F32, p->d_blu_work[0], nf * (size_t)n1, 0, FSEA_MODE_COMPLEX_F32, p->d_blu_work[1], s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(fsea_fs_epilogue_kernel, dim3(blocks), dim3(256), 0, s, p->d_blu_work[1], in_kind == fsea::IN_F32 ? 0 : 1, n1, n2,
-                           mode, static_cast<void *>(static_cast<char *>(d_out) + f0 * n * esz), nf);
-        FSEA_HIP(hipGetLastError());
-    }
-    return FSEA_OK;
-}
-
 // host-side double FFT (radix 2, in place) for the chirp's spectrum: plan creation only
-}  // namespace fsea_detail
-
-namespace {
 void host_fft(std::vector<double> &re, std::vector<double> &im) {
     const size_t m = re.size();
     for (size_t i = 1, j = 0; i < m; ++i) {
@@ -256,10 +192,65 @@ void host_fft(std::vector<double> &re, std::vector<double> &im) {
     }
 }
 
-
 }  // namespace
 
 namespace fsea_detail {
+
+// One Bluestein pass over n_frames frames (in chunks that fit the work buffers): prep -> FFT_m -> x chirp spectrum -> FFT_m ->
+// epilogue, all on stream `s`.  d_in: u8 IQ or f32 complex (device, or device-mapped host memory), frame f at sample f * hop.
+int blu_launch(fsea_plan *p, int in_kind, const void *d_in, size_t n_frames, int flip, int mode, void *d_out, hipStream_t s) {
+    if (n_frames == 0) return FSEA_OK;
+    const int n = p->n, m = p->blu.m;
+    const size_t esz = mode_elem_bytes(mode);
+    const size_t in_bps = (in_kind == fsea::IN_F32) ? 8 : 2;
+    for (size_t f0 = 0; f0 < n_frames; f0 += p->work.frames) {
+        const size_t nf = (n_frames - f0 < p->work.frames) ? n_frames - f0 : p->work.frames;
+        const size_t total = nf * (size_t)m;
+        unsigned blocks = (unsigned)((total + 255) / 256);
+        if (blocks > 8192) blocks = 8192;
+        const char *src = static_cast<const char *>(d_in) + f0 * (size_t)p->hop * in_bps;
+        hipLaunchKernelGGL(fsea_blu_prep_kernel, dim3(blocks), dim3(256), 0, s, static_cast<const void *>(src),
+                           in_kind == fsea::IN_F32 ? 1 : 0, flip ? 0u : 0x80u, (size_t)p->hop, n, m, p->blu.chirp.ptr, p->work.buf[0].ptr, nf);
+        int rc = launch(p->blu.inner, fsea::IN_F32, p->work.buf[0].ptr, nf, 0, FSEA_MODE_COMPLEX_F32, p->work.buf[1].ptr, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(fsea_blu_mul_kernel, dim3(blocks), dim3(256), 0, s, p->work.buf[1].ptr, p->blu.bfft.ptr, p->work.buf[0].ptr, m, nf);
+        rc = launch(p->blu.inner, fsea::IN_F32, p->work.buf[0].ptr, nf, 0, FSEA_MODE_COMPLEX_F32, p->work.buf[1].ptr, s);
+        if (rc) return rc;
+        unsigned eblocks = (unsigned)((nf * (size_t)n + 255) / 256);
+        if (eblocks > 8192) eblocks = 8192;
+        hipLaunchKernelGGL(fsea_blu_epilogue_kernel, dim3(eblocks), dim3(256), 0, s, p->work.buf[1].ptr, p->blu.chirp.ptr,
+                           in_kind == fsea::IN_F32 ? nullptr : p->blu.dc.ptr, n, m, mode,
+                           static_cast<void *>(static_cast<char *>(d_out) + f0 * (size_t)n * esz), nf);
+        FSEA_HIP(hipGetLastError());
+    }
+    return FSEA_OK;
+}
+
+// One four-step pass over n_frames frames (in chunks that fit the work buffers).
+int fs_launch(fsea_plan *p, int in_kind, const void *d_in, size_t n_frames, int flip, int mode, void *d_out, hipStream_t s) {
+    if (n_frames == 0) return FSEA_OK;
+    const int n1 = p->fs.n1, n2 = p->fs.n2;
+    const size_t n = (size_t)p->n, esz = mode_elem_bytes(mode);
+    const size_t in_bps = (in_kind == fsea::IN_F32) ? 8 : 2;
+    for (size_t f0 = 0; f0 < n_frames; f0 += p->work.frames) {
+        const size_t nf = (n_frames - f0 < p->work.frames) ? n_frames - f0 : p->work.frames;
+        unsigned blocks = (unsigned)((nf * n + 255) / 256);
+        if (blocks > 16384) blocks = 16384;
+        const char *src = static_cast<const char *>(d_in) + f0 * (size_t)p->hop * in_bps;
+        hipLaunchKernelGGL(fsea_fs_prep_kernel, dim3(blocks), dim3(256), 0, s, static_cast<const void *>(src),
+                           in_kind == fsea::IN_F32 ? 1 : 0, flip ? 0u : 0x80u, (size_t)p->hop, n1, n2, p->work.buf[0].ptr, nf);
+        int rc = launch(p->fs.inner1, fsea::IN_F32, p->work.buf[0].ptr, nf * (size_t)n2, 0, FSEA_MODE_COMPLEX_F32, p->work.buf[1].ptr, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(fsea_fs_twiddle_kernel, dim3(blocks), dim3(256), 0, s, p->work.buf[1].ptr, p->fs.tw.ptr, p->work.buf[0].ptr, n1, n2, nf);
+        rc = launch(p->fs.inner2, fsea::IN_F32, p->work.buf[0].ptr, nf * (size_t)n1, 0, FSEA_MODE_COMPLEX_F32, p->work.buf[1].ptr, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(fsea_fs_epilogue_kernel, dim3(blocks), dim3(256), 0, s, p->work.buf[1].ptr, in_kind == fsea::IN_F32 ? 0 : 1, n1, n2,
+                           mode, static_cast<void *>(static_cast<char *>(d_out) + f0 * n * esz), nf);
+        FSEA_HIP(hipGetLastError());
+    }
+    return FSEA_OK;
+}
+
 
 // powers of two above 16384 up to FSEA_MAX_FFT_SIZE: n = n1 * n2, both kernel sizes; n1 >= n2
 bool fourstep_split(int n, int *n1, int *n2) {
@@ -281,9 +272,9 @@ int bluestein_m(int n) {
     return m;
 }
 
-// twiddles W_n^{j2 k1} and work buffers of a four-step plan (p->n = fs_n1 * fs_n2)
+// twiddles W_n^{j2 k1} and work buffers of a four-step plan (p->n = fs.n1 * fs.n2)
 int fs_setup(fsea_plan *p) {
-    const size_t n = (size_t)p->n, n1 = (size_t)p->fs_n1, n2 = (size_t)p->fs_n2;
+    const size_t n = (size_t)p->n, n1 = (size_t)p->fs.n1, n2 = (size_t)p->fs.n2;
     std::vector<fsea::TwPair> tw(n);
     const double two_pi = 6.283185307179586476925286766559;
     for (size_t j2 = 0; j2 < n2; ++j2) {
@@ -294,17 +285,17 @@ int fs_setup(fsea_plan *p) {
     }
     size_t frames = ((size_t)64 << 20) / (n * sizeof(fsea::cf));
     if (frames < 1) frames = 1;
-    p->blu_work_frames = frames;
-    FSEA_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_fs_tw), n * sizeof(fsea::cf)));
-    FSEA_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_blu_work[0]), frames * n * sizeof(fsea::cf)));
-    FSEA_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_blu_work[1]), frames * n * sizeof(fsea::cf)));
-    FSEA_HIP(hipMemcpy(p->d_fs_tw, tw.data(), n * sizeof(fsea::cf), hipMemcpyHostToDevice));
+    p->work.frames = frames;
+    FSEA_HIP(p->fs.tw.alloc(n));
+    FSEA_HIP(p->work.buf[0].alloc(frames * n));
+    FSEA_HIP(p->work.buf[1].alloc(frames * n));
+    FSEA_HIP(hipMemcpy(p->fs.tw.ptr, tw.data(), n * sizeof(fsea::cf), hipMemcpyHostToDevice));
     return FSEA_OK;
 }
 
-// tables and work buffers of a Bluestein plan (p->n, p->blu_m set, device current)
+// tables and work buffers of a Bluestein plan (p->n, p->blu.m set, device current)
 int blu_setup(fsea_plan *p) {
-    const int n = p->n, m = p->blu_m;
+    const int n = p->n, m = p->blu.m;
     const double pi = 3.14159265358979323846264338327950288;
     std::vector<fsea::TwPair> chirp((size_t)n), dc((size_t)n), bf((size_t)m);
     std::vector<double> br((size_t)m, 0.0), bi((size_t)m, 0.0);
@@ -341,15 +332,15 @@ int blu_setup(fsea_plan *p) {
     size_t frames = ((size_t)64 << 20) / ((size_t)m * sizeof(fsea::cf));
     if (frames < 1) frames = 1;
     if (frames > 65536) frames = 65536;
-    p->blu_work_frames = frames;
-    FSEA_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_blu_chirp), (size_t)n * sizeof(fsea::cf)));
-    FSEA_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_blu_dc), (size_t)n * sizeof(fsea::cf)));
-    FSEA_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_blu_bfft), (size_t)m * sizeof(fsea::cf)));
-    FSEA_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_blu_work[0]), frames * (size_t)m * sizeof(fsea::cf)));
-    FSEA_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_blu_work[1]), frames * (size_t)m * sizeof(fsea::cf)));
-    FSEA_HIP(hipMemcpy(p->d_blu_chirp, chirp.data(), (size_t)n * sizeof(fsea::cf), hipMemcpyHostToDevice));
-    FSEA_HIP(hipMemcpy(p->d_blu_dc, dc.data(), (size_t)n * sizeof(fsea::cf), hipMemcpyHostToDevice));
-    FSEA_HIP(hipMemcpy(p->d_blu_bfft, bf.data(), (size_t)m * sizeof(fsea::cf), hipMemcpyHostToDevice));
+    p->work.frames = frames;
+    FSEA_HIP(p->blu.chirp.alloc((size_t)n));
+    FSEA_HIP(p->blu.dc.alloc((size_t)n));
+    FSEA_HIP(p->blu.bfft.alloc((size_t)m));
+    FSEA_HIP(p->work.buf[0].alloc(frames * (size_t)m));
+    FSEA_HIP(p->work.buf[1].alloc(frames * (size_t)m));
+    FSEA_HIP(hipMemcpy(p->blu.chirp.ptr, chirp.data(), (size_t)n * sizeof(fsea::cf), hipMemcpyHostToDevice));
+    FSEA_HIP(hipMemcpy(p->blu.dc.ptr, dc.data(), (size_t)n * sizeof(fsea::cf), hipMemcpyHostToDevice));
+    FSEA_HIP(hipMemcpy(p->blu.bfft.ptr, bf.data(), (size_t)m * sizeof(fsea::cf), hipMemcpyHostToDevice));
     return FSEA_OK;
 }
 

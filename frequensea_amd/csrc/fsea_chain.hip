@@ -19,8 +19,7 @@ struct fsea_chain {
     int device = 0;
     fsea_fir *fir = nullptr;
     fsea_iq_draw *draw = nullptr;
-    void *d_pairs = nullptr;  // the filtered (I, Q) f32 pairs of the last run, frame after frame
-    size_t pairs_bytes = 0;
+    fsea_detail::DeviceBuffer pairs;  // the filtered (I, Q) f32 pairs of the last run, frame after frame
     size_t n_pairs = 0;       // pairs per frame of the resident block
     std::mutex mu;
     fsea_detail::HostStaging staging;  // the host forms: input, images and their pinned twins
@@ -28,7 +27,6 @@ struct fsea_chain {
     ~fsea_chain() {
         if (fir) (void)fsea_fir_destroy(fir);
         if (draw) (void)fsea_iq_draw_destroy(draw);
-        if (d_pairs) (void)hipFree(d_pairs);
     }
 };
 
@@ -71,20 +69,20 @@ int check_outputs(const fsea_chain_outputs &o, size_t n_pairs, int n_frames, boo
 
 // the caller holds c->mu and is on c's device; stream work that may still read the old buffer is the caller's to order
 int reserve_pairs(fsea_chain *c, size_t bytes) {
-    return fsea_detail::grow_device(&c->d_pairs, &c->pairs_bytes, bytes ? bytes : 16);
+    return c->pairs.grow(bytes ? bytes : 16);
 }
 
-// the filter launches of n_frames blocks into c->d_pairs
+// the filter launches of n_frames blocks into c->pairs.ptr
 int queue_filter(fsea_chain *c, int f64, const void *d_in, size_t n, int n_frames, const fsea_chain_stage &st, hipStream_t s) {
     FirShift shift = {st.cycles_per_sample, st.phase0_cycles, st.sample_offset};
     if (!st.n_zero) {   // the blocks are one piece of the stream: one launch
         return fsea_detail::fir_launch_device(c->fir, f64, d_in, n * (size_t)n_frames, 0, st.flip, st.shift ? &shift : nullptr,
-                                              c->d_pairs, s);
+                                              c->pairs.ptr, s);
     }
     for (int f = 0; f < n_frames; ++f) {
         shift.sample_offset = st.sample_offset + (uint64_t)f * n;   // the zeros are not the shifter's samples
         int rc = fsea_detail::fir_launch_device(c->fir, 0, static_cast<const uint8_t *>(d_in) + 2 * n * f, n, st.n_zero, st.flip,
-                                                &shift, static_cast<float *>(c->d_pairs) + 2 * (n + st.n_zero) * f, s);
+                                                &shift, static_cast<float *>(c->pairs.ptr) + 2 * (n + st.n_zero) * f, s);
         if (rc) return rc;
     }
     return FSEA_OK;
@@ -94,16 +92,16 @@ int queue_filter(fsea_chain *c, int f64, const void *d_in, size_t n, int n_frame
 int queue_images(fsea_chain *c, int n_frames, const fsea_chain_outputs &o, void *d_points, void *d_lines, hipStream_t s) {
     const size_t n = c->n_pairs;
     if (o.points) {
-        int rc = fsea_iq_points_device(c->draw, c->d_pairs, FSEA_IQ_F32, 0, n, n_frames, d_points, s);
+        int rc = fsea_iq_points_device(c->draw, c->pairs.ptr, FSEA_IQ_F32, 0, n, n_frames, d_points, s);
         if (rc) return rc;
     }
     if (o.lines) {
         if (o.n_line_points == n || n_frames <= 1) {
-            return fsea_iq_lines_device(c->draw, c->d_pairs, FSEA_IQ_F32, 0, o.n_line_points, n_frames, o.size_multiplier,
+            return fsea_iq_lines_device(c->draw, c->pairs.ptr, FSEA_IQ_F32, 0, o.n_line_points, n_frames, o.size_multiplier,
                                         d_lines, s);
         }
         for (int f = 0; f < n_frames; ++f) {   // the frames' first points are not consecutive in the buffer
-            int rc = fsea_iq_lines_device(c->draw, static_cast<const float *>(c->d_pairs) + 2 * n * f, FSEA_IQ_F32, 0,
+            int rc = fsea_iq_lines_device(c->draw, static_cast<const float *>(c->pairs.ptr) + 2 * n * f, FSEA_IQ_F32, 0,
                                           o.n_line_points, 1, o.size_multiplier,
                                           static_cast<uint8_t *>(d_lines) + line_pixels(o) * f, s);
             if (rc) return rc;
@@ -129,18 +127,18 @@ int host_call(fsea_chain *c, bool run, const void *in, int f64, size_t n, const 
         rc = reserve_pairs(c, total * 8);
         if (rc) return rc;
         if (in_bytes) {
-            std::memcpy(g.h_in, in, in_bytes);
-            FSEA_HIP(hipMemcpyAsync(g.d_in, g.h_in, in_bytes, hipMemcpyHostToDevice, g.stream));
+            std::memcpy(g.h_in.ptr, in, in_bytes);
+            FSEA_HIP(hipMemcpyAsync(g.d_in.ptr, g.h_in.ptr, in_bytes, hipMemcpyHostToDevice, g.stream));
         }
-        rc = queue_filter(c, f64, g.d_in, n, 1, st, g.stream);
+        rc = queue_filter(c, f64, g.d_in.ptr, n, 1, st, g.stream);
         if (rc) return rc;
         c->n_pairs = total;
     }
-    uint8_t *h = static_cast<uint8_t *>(g.h_out), *d = static_cast<uint8_t *>(g.d_out);
+    uint8_t *h = static_cast<uint8_t *>(g.h_out.ptr), *d = static_cast<uint8_t *>(g.d_out.ptr);
     rc = queue_images(c, 1, o, d, d + lines_at, g.stream);
     if (rc) return rc;
     if (pairs_at) FSEA_HIP(hipMemcpyAsync(h, d, pairs_at, hipMemcpyDeviceToHost, g.stream));
-    if (o.pairs && total) FSEA_HIP(hipMemcpyAsync(h + pairs_at, c->d_pairs, total * 8, hipMemcpyDeviceToHost, g.stream));
+    if (o.pairs && total) FSEA_HIP(hipMemcpyAsync(h + pairs_at, c->pairs.ptr, total * 8, hipMemcpyDeviceToHost, g.stream));
     FSEA_HIP(hipStreamSynchronize(g.stream));
     if (o.points) std::memcpy(o.points, h, IMAGE_BYTES);
     if (o.lines) std::memcpy(o.lines, h + lines_at, line_pixels(o));
@@ -240,7 +238,7 @@ int fsea_chain_run_device(fsea_chain *c, const void *d_iq, size_t n_samples, int
     rc = queue_images(c, n_frames, o, o.points, o.lines, s);
     if (rc) return rc;
     if (o.pairs && total) {
-        FSEA_HIP(hipMemcpyAsync(o.pairs, c->d_pairs, total * 8 * (size_t)n_frames, hipMemcpyDeviceToDevice, s));
+        FSEA_HIP(hipMemcpyAsync(o.pairs, c->pairs.ptr, total * 8 * (size_t)n_frames, hipMemcpyDeviceToDevice, s));
     }
     return FSEA_OK;
 }

@@ -31,7 +31,7 @@
 #define FSEA_CFG_16384 16384, 512, 1, 2, 3, 16, 32, 32, 1, true, true, 0, fo::STREAMING_PIXELS | fo::WIN_DC_REGS_MAG | fo::LD_NT | fo::DEFER | fo::TW_FUSE
 
 // Per-(size, mode) configurations: where the modes of one size prefer different radix orders, a plan takes the one its
-// mode prefers (fsea_api.hip: preferred_variant; registry variants "rows" / "px" / "rt", full kernel sets).  Measured in one
+// mode prefers (fsea_plan.hip: preferred_variant; registry variants "rows" / "px" / "rt", full kernel sets).  Measured in one
 // process against the size's first configuration (profiles/r03_layouts_other_sizes.txt, r03_1024_three_pass.txt,
 // r04_mode_rates.txt):
 //   256 points, f32 rows (MAG, MAG_NODC, DB_F32): 4 x 8 x 8 -- dwordx4 pass-0 loads, four adjacent bins per lane: +4 %

@@ -362,8 +362,7 @@ struct fsea_demod {
     std::vector<Table> tables;
     unsigned long long use_seq = 0;
     std::mutex mu;
-    void *d_y1 = nullptr;
-    size_t d_y1_bytes = 0;
+    fsea_detail::DeviceBuffer y1;               // stage 1's outputs of a WBFM call
     fsea_detail::HostStaging staging;           // the host-buffer forms
 
     ~fsea_demod();
@@ -471,10 +470,10 @@ int demod_launch(fsea_demod *d, int kind, const void *in0, const void *in1, size
     if (rc) return rc;
     if (d->type == FSEA_DEMOD_WBFM) {
         const size_t y1_bytes = (size_t)d->K * (size_t)(t->n1 > 0 ? t->n1 : 1) * sizeof(double2);
-        if (d->d_y1 && d->d_y1_bytes < y1_bytes) {
+        if (d->y1.ptr && d->y1.cap < y1_bytes) {
             FSEA_HIP(hipDeviceSynchronize());   // a launch on another stream may still use the old buffer
         }
-        rc = fsea_detail::grow_device(&d->d_y1, &d->d_y1_bytes, y1_bytes);
+        rc = d->y1.grow(y1_bytes);
         if (rc) return rc;
     }
     const int slot = d->ring;
@@ -489,7 +488,7 @@ int demod_launch(fsea_demod *d, int kind, const void *in0, const void *in1, size
     const long long nn = (long long)n;
     const unsigned g1 = (unsigned)(t->n1 > 0 ? (t->n1 + t->T1 - 1) / t->T1 : 1);
     const bool fm_chain = d->type == FSEA_DEMOD_WBFM;
-    double *out1 = fm_chain ? static_cast<double *>(d->d_y1) : d_audio;
+    double *out1 = fm_chain ? static_cast<double *>(d->y1.ptr) : d_audio;
     const long long ld1 = fm_chain ? (t->n1 > 0 ? t->n1 : 1) : t->n1;
     auto k1 = kind == DM_IN_U8 ? (fm_chain ? fsea_demod_stage1_u8 : fsea_demod_stage1_u8_i)
                                : (fm_chain ? fsea_demod_stage1_f64 : fsea_demod_stage1_f64_i);
@@ -498,7 +497,7 @@ int demod_launch(fsea_demod *d, int kind, const void *in0, const void *in1, size
     FSEA_HIP(hipGetLastError());
     if (fm_chain) {
         const unsigned g3 = (unsigned)(t->n2 > 0 ? (t->n2 + t->T3 - 1) / t->T3 : 1);
-        hipLaunchKernelGGL(fsea_demod_fm, dim3(g3, d->K), dim3(DM_WG), 0, s, static_cast<const double2 *>(d->d_y1),
+        hipLaunchKernelGGL(fsea_demod_fm, dim3(g3, d->K), dim3(DM_WG), 0, s, static_cast<const double2 *>(d->y1.ptr),
                            (long long)t->n1, ld1, d->d_l[cur], d->d_l[nxt], d->d_tail3[cur], d->d_tail3[nxt], d->L3,
                            d->d_taps3, t->d_idx3, t->n2, t->T3, d->ampl_conv, d_audio, (long long)t->n2);
         FSEA_HIP(hipGetLastError());
@@ -584,7 +583,7 @@ hipError_t upload_taps(double **dst, double rate, double cutoff, int L) {
 }  // namespace
 
 fsea_demod::~fsea_demod() {
-    void *dev[] = {d_taps1, d_taps3, d_tail1[0], d_tail1[1], d_tail3[0], d_tail3[1], d_l[0], d_l[1], d_v[0], d_v[1], d_y1};
+    void *dev[] = {d_taps1, d_taps3, d_tail1[0], d_tail1[1], d_tail3[0], d_tail3[1], d_l[0], d_l[1], d_v[0], d_v[1]};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (int i = 0; i < DM_RING; ++i) {

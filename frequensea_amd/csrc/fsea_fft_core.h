@@ -1033,7 +1033,7 @@ struct FftKernel {
     static constexpr bool V2 = false, W64 = false;
     static_assert((Cfg::OPT & opt::TUNE_ONLY) == 0 && Cfg::ABL == 0, "tuning-only option or ablation in a product build");
 #endif
-    // what a launch does with FftArgs::ctr (host side: which launches need a ticket-counter slot, fsea_api.hip):
+    // what a launch does with FftArgs::ctr (host side: which launches need a ticket-counter slot, fsea_plan.hip):
     // 0 = nothing, 1 = ticket pools when FftArgs::dynamic_units, 2 = ticket pools always (V2)
     static constexpr int counters_used() { return W64 ? 0 : (V2 ? 2 : (DYNAMIC ? 1 : 0)); }
 

@@ -1,8 +1,10 @@
 // fsea_internal.h -- what the translation units of libfsea_hip.so share behind the C ABI (include/fsea.h): the plan
-// object, error plumbing, the launch dispatcher, and the scaffold of the six device objects (FIR, IQ draw, demod, interp,
-// chain, trace): shared argument checks, create / destroy, growable buffers, the event-ordered scratch buffer, host-form
-// staging.  fsea_api.hip: plans, the power-of-two launches, every entry point, the scaffold's bodies;
-// fsea_anysize.hip: the transform sizes without a kernel of their own (Bluestein's algorithm, four-step decomposition).
+// object, error plumbing, the launch dispatcher, owning buffers, and the scaffold of the six device objects (FIR, IQ draw,
+// demod, interp, chain, trace): shared argument checks, create / destroy, the event-ordered scratch buffer, host-form
+// staging.  fsea_api.hip: the error plumbing, the scaffold's bodies and the entry points that take no plan;
+// fsea_plan.hip: the kernel registry, a plan's life cycle, the launch path and the device-buffer entry points;
+// fsea_plan_host.hip: the host-buffer entry points and the history ring; fsea_anysize.hip: the transform sizes without a
+// kernel of their own (Bluestein's algorithm, four-step decomposition).
 #pragma once
 
 #include "../../include/fsea.h"
@@ -74,10 +76,50 @@ __device__ __forceinline__ uint32_t coord_f64(double v) {
     return (uint32_t)(int)s & 0xffu;
 }
 
-// At least `need` bytes in *ptr (device memory, or pinned host memory), reallocated with headroom when *cap is short.  The
-// old buffer is freed without any wait: a caller whose buffer work may still use waits for that work first.
-int grow_device(void **ptr, size_t *cap, size_t need);
-int grow_pinned(void **ptr, size_t *cap, size_t need);
+// A buffer that grows on demand and frees itself, one type per memory kind: device memory and default pinned host memory
+// (the source and target of copies) with a quarter of headroom, mapped host memory (a kernel reads and writes it itself)
+// with a 64 KiB floor and none.  grow(need): at least `need` bytes behind `ptr`, reallocated when `cap` is short.  The old
+// memory is freed without any wait: a caller whose buffer work may still use waits for that work first.
+enum class Mem { Device, Pinned, Mapped };
+template <Mem K>
+struct Buffer {
+    void *ptr = nullptr;
+    size_t cap = 0;
+
+    Buffer() = default;
+    Buffer(const Buffer &) = delete;
+    Buffer &operator=(const Buffer &) = delete;
+    ~Buffer() { if (ptr) (void)release(ptr); }
+    static hipError_t alloc(void **p, size_t n) {
+        return K == Mem::Device ? hipMalloc(p, n) : hipHostMalloc(p, n, K == Mem::Mapped ? hipHostMallocMapped : hipHostMallocDefault);
+    }
+    static hipError_t release(void *p) { return K == Mem::Device ? hipFree(p) : hipHostFree(p); }
+    int grow(size_t need) {
+        if (cap >= need) return FSEA_OK;
+        if (ptr) FSEA_HIP(release(ptr));
+        ptr = nullptr;
+        cap = 0;
+        const size_t want = K == Mem::Mapped ? (need < 65536 ? 65536 : need) : need + need / 4 + 4096;
+        FSEA_HIP(alloc(&ptr, want));
+        cap = want;
+        return FSEA_OK;
+    }
+};
+using DeviceBuffer = Buffer<Mem::Device>;
+using PinnedBuffer = Buffer<Mem::Pinned>;
+using MappedBuffer = Buffer<Mem::Mapped>;
+
+// `count` elements of device memory, allocated once at exactly that size and freed with their owner
+template <class T>
+struct DeviceArray {
+    T *ptr = nullptr;
+
+    DeviceArray() = default;
+    DeviceArray(const DeviceArray &) = delete;
+    DeviceArray &operator=(const DeviceArray &) = delete;
+    ~DeviceArray() { if (ptr) (void)hipFree(ptr); }
+    hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void **>(&ptr), count * sizeof(T)); }
+};
 
 // FSEA_OK, FSEA_ENODEVICE when HIP has no device at all, FSEA_EINVAL when `device` is not one of them
 int check_device(int device);
@@ -92,11 +134,11 @@ int check_aligned16(const char *names, const void *a, const void *b = nullptr, c
 // Only those forms use the staging, on that stream, under the object's mutex.
 struct HostStaging {
     hipStream_t stream = nullptr;
-    void *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
-    size_t h_in_bytes = 0, h_out_bytes = 0, d_in_bytes = 0, d_out_bytes = 0;
+    PinnedBuffer h_in, h_out;
+    DeviceBuffer d_in, d_out;
 
     hipError_t create() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
-    ~HostStaging();
+    ~HostStaging() { if (stream) (void)hipStreamDestroy(stream); }
     int reserve(size_t in_bytes, size_t out_bytes);
 
     // One host-form call: fill(h_in) writes the in_bytes of input into pinned memory, copy in, launch(d_in, d_out, stream)
@@ -107,14 +149,14 @@ struct HostStaging {
         int rc = reserve(in_bytes, out_bytes);
         if (rc) return rc;
         if (in_bytes) {
-            fill(h_in);
-            FSEA_HIP(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, stream));
+            fill(h_in.ptr);
+            FSEA_HIP(hipMemcpyAsync(d_in.ptr, h_in.ptr, in_bytes, hipMemcpyHostToDevice, stream));
         }
-        rc = launch(d_in, d_out, stream);
+        rc = launch(d_in.ptr, d_out.ptr, stream);
         if (rc) return rc;
-        if (out_bytes) FSEA_HIP(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+        if (out_bytes) FSEA_HIP(hipMemcpyAsync(h_out.ptr, d_out.ptr, out_bytes, hipMemcpyDeviceToHost, stream));
         FSEA_HIP(hipStreamSynchronize(stream));
-        if (out_bytes) std::memcpy(out, h_out, out_bytes);
+        if (out_bytes) std::memcpy(out, h_out.ptr, out_bytes);
         return FSEA_OK;
     }
 };
@@ -124,12 +166,11 @@ struct HostStaging {
 // host for the last use before the buffer is reallocated (or, by the caller, overwritten).  The caller holds the object's
 // mutex and is on its device.
 struct SharedScratch {
-    void *ptr = nullptr;
-    size_t bytes = 0;
+    DeviceBuffer buf;
     hipEvent_t used = nullptr;  // recorded after the last work that used the buffer
 
     hipError_t create(hipStream_t first);  // the event starts recorded on `first`, so it can be waited for at once
-    ~SharedScratch();
+    ~SharedScratch() { if (used) (void)hipEventDestroy(used); }
     int reserve(size_t need);
     int acquire(hipStream_t s);
     int release(hipStream_t s);
@@ -186,6 +227,8 @@ int fir_launch_device(fsea_fir *f, int f64, const void *d_in, size_t n_in, size_
 
 }  // namespace fsea_detail
 
+// A plan is made of parts that own what they hold: each frees its memory, events and streams in its destructor, so
+// fsea_plan_destroy is a `delete` and a failed fsea_plan_create frees whatever it got as far as allocating.
 struct fsea_plan {
     int n = 0;
     int hop = 0;
@@ -193,77 +236,121 @@ struct fsea_plan {
     int device = 0;
     const fsea::KernelEntry *entry = nullptr;
     hipStream_t stream = nullptr;
-    fsea::cf *d_tw = nullptr;      // passes 1..np-1 concatenated
+    fsea_detail::DeviceArray<fsea::cf> d_tw;  // passes 1..np-1 concatenated
     size_t tw_off[5] = {0, 0, 0, 0, 0};  // passes 0..3, then the HI/LO factor tables (fsea_tables.h)
     size_t tw_def_off = 0;               // deferred middle-pass table (fo::DEFER / fo::V2), 16-byte aligned
     int num_cu = 0;
-    // Ticket counters of the multi-wave sizes: one slot per stream the plan is launched on.  Launches
-    // on one stream run in order and the last workgroup of a launch zeroes its slot, so a stream
-    // needs exactly one; launches on different streams may overlap and never share one.
-    unsigned *d_ctr = nullptr;  // FSEA_CTR_SLOTS x FSEA_CTR_WORDS
-    std::mutex slot_mu;
-    struct CtrSlot {
-        hipStream_t stream = nullptr;   // the stream the slot serves (meaningful while `used` and not `anonymous`)
-        hipEvent_t ev = nullptr;        // recorded behind the slot's last launch (not while the stream is being captured)
-        bool used = false, pending = false, anonymous = false, captured = false;
-        bool launching = false;         // claimed by a host thread between counter_slot() and the record of `ev`: not to be recycled
-        unsigned long long seq = 0;     // launch order, for least-recently-used recycling
-    } slots[FSEA_CTR_SLOTS];
-    unsigned long long slot_seq = 0;
-    unsigned long long *d_trace = nullptr;  // FSEA_TRACE diagnostics (tuning library)
+    fsea_detail::DeviceArray<unsigned long long> d_trace;  // FSEA_TRACE diagnostics (tuning library)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the launches fsea_time_exec_* time (tuning library; created by every build)
     int occ[fsea::K_COUNT] = {};
     // FSEA_UNITS_AUTO: launches with at most FSEA_STATIC_UNITS_PER_WG units per workgroup use the static interleave,
     // longer ones the ticket pools; fsea_plan_set_unit_distribution pins one of the two
     int units_policy = FSEA_UNITS_AUTO;
     int half_run_max = 32;         // frames per run of the half-overlap kernels at most (FSEA_HALF_RUN_MAX at plan creation; 8, 16 and 32 equal in rate, fetch 1.127x / 1.064x / 1.033x the distinct bytes: profiles/r04_stft_run_length.txt)
     bool no_half_overlap = false;  // FSEA_NO_HALF_OVERLAP=1 at plan creation: hop == N/2 runs the ordinary kernel (A/B measurements)
-    // staging for the host-buffer entry points
-    std::mutex mu;
-    void *d_in = nullptr;
-    size_t d_in_bytes = 0;
-    void *d_out = nullptr;
-    size_t d_out_bytes = 0;
-    void *d_aux = nullptr;
-    size_t d_aux_bytes = 0;
-    double *d_acc = nullptr;
-    // small host batches (the nrf_fft_process pattern: one 2 KiB frame in, one row out) go through
-    // pinned, device-mapped staging: the kernel reads and writes host memory itself, so a call is
-    // one launch and one synchronisation instead of copy + launch + copy
-    void *h_in = nullptr;
-    void *h_out = nullptr;
-    size_t h_in_bytes = 0, h_out_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // the pipelined host-buffer path (exec_host_pipelined): copy-in and copy-out streams beside `stream`, and one
-    // "chunk arrived" / "chunk transformed" event pair per chunk in flight
+
+    // Ticket counters of the multi-wave sizes: one slot per stream the plan is launched on.  Launches
+    // on one stream run in order and the last workgroup of a launch zeroes its slot, so a stream
+    // needs exactly one; launches on different streams may overlap and never share one.
+    struct Counters {
+        fsea_detail::DeviceArray<unsigned> d_ctr;  // FSEA_CTR_SLOTS x FSEA_CTR_WORDS
+        std::mutex slot_mu;
+        struct Slot {
+            hipStream_t stream = nullptr;   // the stream the slot serves (meaningful while `used` and not `anonymous`)
+            hipEvent_t ev = nullptr;        // recorded behind the slot's last launch (not while the stream is being captured)
+            bool used = false, pending = false, anonymous = false, captured = false;
+            bool launching = false;         // claimed by a host thread between counter_slot() and the record of `ev`: not to be recycled
+            unsigned long long seq = 0;     // launch order, for least-recently-used recycling
+        } slots[FSEA_CTR_SLOTS];
+        unsigned long long slot_seq = 0;
+
+        hipError_t create();  // the counters, zeroed on the null stream: the caller waits for the device before a launch
+        ~Counters() { for (auto &c : slots) if (c.ev) (void)hipEventDestroy(c.ev); }
+    } ctr;
+
+    // The host-buffer entry points (fsea_plan_host.hip), one call at a time under `mu`.
+    struct HostPath {
+        std::mutex mu;
+        // device staging of the large batches; d_aux also holds the rows that fsea_mean_magnitude_u8_device sums into d_acc
+        fsea_detail::DeviceBuffer d_in, d_out, d_aux;
+        fsea_detail::DeviceArray<double> d_acc;
+        // small host batches (the nrf_fft_process pattern: one 2 KiB frame in, one row out) go through
+        // pinned, device-mapped staging: the kernel reads and writes host memory itself, so a call is
+        // one launch and one synchronisation instead of copy + launch + copy
+        fsea_detail::MappedBuffer h_in, h_out;
+        // the pipelined host-buffer path (exec_host_pipelined): copy-in and copy-out streams beside the plan's stream, and
+        // one "chunk arrived" / "chunk transformed" event pair per chunk in flight
+        hipStream_t s_h2d = nullptr, s_d2h = nullptr;
+        hipEvent_t ev_in[FSEA_HOST_CHUNKS_MAX] = {}, ev_done[FSEA_HOST_CHUNKS_MAX] = {};
+
+        hipError_t create();  // the two streams and the events
+        ~HostPath();
+
+        // One small batch through the mapped staging: fill(h_in) writes the in_bytes of input, launch(d_in, d_out) queues the
+        // transform on `stream` with the staging's device addresses, wait, out_bytes to `out`.  `out` null: the launch writes
+        // device memory of its own, no output staging.  The caller holds `mu` and is on the plan's device.
+        template <class Fill, class Launch>
+        int zero_copy(hipStream_t stream, size_t in_bytes, size_t out_bytes, void *out, Fill &&fill, Launch &&launch) {
+            int rc = h_in.grow(in_bytes);
+            if (!rc && out) rc = h_out.grow(out_bytes);
+            if (rc) return rc;
+            void *d_src = nullptr, *d_dst = nullptr;
+            FSEA_HIP(hipHostGetDevicePointer(&d_src, h_in.ptr, 0));
+            if (out) FSEA_HIP(hipHostGetDevicePointer(&d_dst, h_out.ptr, 0));
+            fill(h_in.ptr);
+            rc = launch(d_src, d_dst);
+            if (rc) return rc;
+            FSEA_HIP(hipStreamSynchronize(stream));
+            if (out) std::memcpy(out, h_out.ptr, out_bytes);
+            return FSEA_OK;
+        }
+    } host;
+
     // Bluestein plans (transform sizes without a kernel of their own): `n` is the logical size, `entry` the power-of-two
-    // kernel set of size blu_m the convolution runs on
-    int blu_m = 0;
-    fsea_plan *blu_inner = nullptr;          // size blu_m, COMPLEX_F32
-    fsea::cf *d_blu_chirp = nullptr;         // conj(w[j]), j < n
-    fsea::cf *d_blu_bfft = nullptr;          // FFT_m of the wrapped chirp
-    fsea::cf *d_blu_dc = nullptr;            // spectrum of the offset-binary DC term, n entries
-    fsea::cf *d_blu_work[2] = {nullptr, nullptr};
-    size_t blu_work_frames = 0;
-    // the work buffers are the plan's, not the launch's: launches of such a plan on different streams are put in order
-    // behind one another (an event recorded behind each launch, waited for by the next one's stream)
-    std::mutex work_mu;
-    hipEvent_t work_ev = nullptr;
-    bool work_pending = false;
-    // four-step plans (powers of two above 16384): n = fs_n1 * fs_n2, two inner plans, the twiddles W_n^{j2 k1}
-    int fs_n1 = 0, fs_n2 = 0;
-    fsea_plan *fs_inner1 = nullptr, *fs_inner2 = nullptr;
-    fsea::cf *d_fs_tw = nullptr;
-    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-    hipEvent_t ev_in[FSEA_HOST_CHUNKS_MAX] = {}, ev_done[FSEA_HOST_CHUNKS_MAX] = {};
+    // kernel set of size blu.m the convolution runs on
+    struct Bluestein {
+        int m = 0;
+        fsea_plan *inner = nullptr;                 // size m, COMPLEX_F32
+        fsea_detail::DeviceArray<fsea::cf> chirp;   // conj(w[j]), j < n
+        fsea_detail::DeviceArray<fsea::cf> bfft;    // FFT_m of the wrapped chirp
+        fsea_detail::DeviceArray<fsea::cf> dc;      // spectrum of the offset-binary DC term, n entries
+        ~Bluestein() { if (inner) (void)fsea_plan_destroy(inner); }
+    } blu;
+
+    // four-step plans (powers of two above 16384): n = fs.n1 * fs.n2, two inner plans, the twiddles W_n^{j2 k1}
+    struct FourStep {
+        int n1 = 0, n2 = 0;
+        fsea_plan *inner1 = nullptr, *inner2 = nullptr;
+        fsea_detail::DeviceArray<fsea::cf> tw;
+        ~FourStep() { if (inner1) (void)fsea_plan_destroy(inner1); if (inner2) (void)fsea_plan_destroy(inner2); }
+    } fs;
+
+    // What a Bluestein and a four-step plan share: two work buffers of `frames` frames each.  They are the plan's, not the
+    // launch's: launches of such a plan on different streams are put in order behind one another (an event recorded
+    // behind each launch, waited for by the next one's stream)
+    struct Work {
+        fsea_detail::DeviceArray<fsea::cf> buf[2];
+        size_t frames = 0;
+        std::mutex mu;
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+        ~Work() { if (ev) (void)hipEventDestroy(ev); }
+    } work;
+
     // taper window (fsea_plan_set_window): weights in the pass-0 lane order with (-1)^n folded in, and the DC term's
-    // spectrum around bin n/2 (FftArgs::win, win_dc); window_form 0 = none, 1 = centred, 2 = offset-binary
-    float *d_win = nullptr;
-    fsea::cf *d_win_dc = nullptr;
-    int window_form = 0;
+    // spectrum around bin n/2 (FftArgs::win, win_dc); form 0 = none, 1 = centred, 2 = offset-binary
+    struct Window {
+        fsea_detail::DeviceArray<float> d_win;
+        fsea_detail::DeviceArray<fsea::cf> d_win_dc;
+        int form = 0;
+    } window;
+
     // both strings live as long as the plan: fsea_plan_kernel_name hands out a pointer into the one in use, and a pointer a
     // caller got earlier stays valid across fsea_plan_set_window (the windowed name depends on the plan's constants only)
     std::string kernel_name;        // while no window is set
     std::string kernel_name_win;    // while one is (filled by the first fsea_plan_set_window)
+
+    ~fsea_plan();
 };
 
 

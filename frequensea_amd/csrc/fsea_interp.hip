@@ -346,7 +346,7 @@ int frames_launch(fsea_interp *p, const double *d_w, int n_frames, void *d_out, 
 
 // the tables of geometry g on the device (kept from the last call with the same geometry)
 int image_tables(fsea_interp *p, const fsea_interp_geometry *g) {
-    if (p->tab.ptr && p->tab_w == g->width && p->tab_h == g->height && p->tab_iq == g->iq_size) return FSEA_OK;
+    if (p->tab.buf.ptr && p->tab_w == g->width && p->tab_h == g->height && p->tab_iq == g->iq_size) return FSEA_OK;
     const int w16 = (g->width + 15) & ~15;
     std::vector<int32_t> col((size_t)g->width), row((size_t)g->height);
     const double scale = block_scale(g->width, g->height, g->iq_size);
@@ -376,7 +376,7 @@ int image_tables(fsea_interp *p, const fsea_interp_geometry *g) {
     int rc = p->tab.reserve(tab.size() * 2);  // no launch on any stream still reads the old tables
     if (rc) return rc;
     p->tab_w = 0;
-    FSEA_HIP(hipMemcpy(p->tab.ptr, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
+    FSEA_HIP(hipMemcpy(p->tab.buf.ptr, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
     p->tab_w = g->width;
     p->tab_h = g->height;
     p->tab_iq = g->iq_size;
@@ -398,7 +398,7 @@ int image_launch(fsea_interp *p, const double *d_w, int n_frames, const fsea_int
         const dim3 grid(gx, (unsigned)((nf + IM_RUN - 1) / IM_RUN));
         hipLaunchKernelGGL(fsea_interp_image_u8, grid, dim3(IT_WG), lds, s, static_cast<const uint8_t *>(p->d_a),
                            static_cast<const uint8_t *>(p->d_b), g->flip ? 0x80u : 0u, d_w + f0, nf, g->width, g->height,
-                           g->iq_size, p->tile_rows, p->max_slots, static_cast<const uint16_t *>(p->tab.ptr),
+                           g->iq_size, p->tile_rows, p->max_slots, static_cast<const uint16_t *>(p->tab.buf.ptr),
                            static_cast<uint8_t *>(d_images) + (size_t)f0 * frame_bytes);
         FSEA_HIP(hipGetLastError());
     }

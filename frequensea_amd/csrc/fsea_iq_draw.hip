@@ -274,10 +274,10 @@ int lines_launch(fsea_iq_draw *d, const void *d_iq, int type, int flip, size_t n
         return FSEA_OK;
     }
     const size_t chunk = std::min<size_t>((size_t)n_frames, std::max<size_t>(1, LN_CHUNK_BYTES / (4 * pixels)));
-    int rc = d->counts.bytes < chunk * pixels * 4 ? d->counts.reserve(chunk * pixels * 4) : FSEA_OK;
+    int rc = d->counts.buf.cap < chunk * pixels * 4 ? d->counts.reserve(chunk * pixels * 4) : FSEA_OK;
     if (!rc) rc = d->counts.acquire(s);  // every use of the count buffer, on whatever stream, follows the previous one
     if (rc) return rc;
-    uint32_t *d_counts = static_cast<uint32_t *>(d->counts.ptr);
+    uint32_t *d_counts = static_cast<uint32_t *>(d->counts.buf.ptr);
     const uint32_t fm = (type == FSEA_IQ_U8 && flip) ? 0x80808080u : 0u;
     const long long n = (long long)n_points;
     const unsigned gx = (unsigned)((n_points - 1 + LN_WG - 1) / LN_WG);

@@ -244,8 +244,8 @@ def _store_hazard_findings(lib, tmp_path, tag):
 def test_every_16_byte_store_is_followed_by_its_wait_states(tmp_path):
     """DESIGN.md section 3, the store-data hazard: a VALU write to a data register of a 16-byte store too soon behind it
     changes what the store writes.  Checked in the disassembly of EVERY shipped code object (the product library incl. the
-    plain HIP kernels of fsea_api.hip, the gather library, and the tuning library), so that a 12- or 16-byte store added
-    past bst128() fails here without a GPU.  FSEA_ARTIFACT_LIB=<path> checks another build of libfsea_hip.so instead
+    plain HIP kernels of fsea_api.hip, fsea_plan.hip and fsea_plan_host.hip, the gather library, and the tuning library), so
+    that a 12- or 16-byte store added past bst128() fails here without a GPU.  FSEA_ARTIFACT_LIB=<path> checks another build of libfsea_hip.so instead
     (a -DFSEA_STORE_GUARD=0 build must fail: scripts/store_guard_regression.sh)."""
     objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
     lib = os.environ.get("FSEA_ARTIFACT_LIB", LIB)
