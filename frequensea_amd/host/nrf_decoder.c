@@ -16,30 +16,18 @@
 
 #include "fsea.h"
 #include "nrf.h"
+#include "nrf_private.h"
+
+#define BLOCK "decoder"
 
 static const double TAU = 6.28318530717958647692;
 static const int FM_INTER_RATE = 336000;
 static const int FM_MAX_F = 75000;
 
-static void demod_fatal(const char *what, int rc) {
-    /* same convention as src/nrf.c:54-78: print and exit */
-    fprintf(stderr, "NRF decoder fatal error: %s failed (%d): %s\n", what, rc, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
-
-static void *checked_calloc(size_t count, size_t size) {
-    void *p = calloc(count > 0 ? count : 1, size);
-    if (p == NULL) {
-        fprintf(stderr, "NRF decoder fatal error: out of memory\n");
-        exit(EXIT_FAILURE);
-    }
-    return p;
-}
-
 /* ---- Downsampler (host, double) ------------------------------------------------ */
 
 nrf_downsampler *nrf_downsampler_new(int in_rate, int out_rate, int filter_freq, int kernel_length) {
-    nrf_downsampler *d = (nrf_downsampler *)checked_calloc(1, sizeof(nrf_downsampler));
+    nrf_downsampler *d = (nrf_downsampler *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_downsampler));
     d->in_rate = in_rate;
     d->out_rate = out_rate;
     d->filter = nrf_fir_filter_new(in_rate, filter_freq, kernel_length);
@@ -53,7 +41,7 @@ void nrf_downsampler_process(nrf_downsampler *d, double *samples, int length) {
     nrf_fir_filter_load(d->filter, samples, length);
     free(d->out_samples);
     d->out_length = (int)floor(length / d->rate_mul);
-    d->out_samples = (double *)checked_calloc((size_t)d->out_length, sizeof(double));
+    d->out_samples = (double *)nrf_private_calloc(BLOCK, (size_t)d->out_length, sizeof(double));
     double t = 0;
     for (int i = 0; i < d->out_length; i++) {
         d->out_samples[i] = nrf_fir_filter_get(d->filter, (int)floor(t));
@@ -72,16 +60,15 @@ void nrf_downsampler_free(nrf_downsampler *d) {
 
 static fsea_demod *backend_new(int type, int in_rate, int out_rate) {
     fsea_demod *b = NULL;
-    const char *dev_env = getenv("NRF_FFT_DEVICE"); /* the GPU the nrf blocks use */
-    const int rc = fsea_demod_create(&b, type, in_rate, out_rate, 1, dev_env ? atoi(dev_env) : 0);
-    if (rc != FSEA_OK) demod_fatal("fsea_demod_create", rc);
+    const int rc = fsea_demod_create(&b, type, in_rate, out_rate, 1, nrf_private_device());
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_demod_create", rc);
     return b;
 }
 
 static void backend_free(void *b) {
     if (b == NULL) return;
     const int rc = fsea_demod_destroy((fsea_demod *)b);
-    if (rc != FSEA_OK) demod_fatal("fsea_demod_destroy", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_demod_destroy", rc);
 }
 
 /* the demodulator's audio buffer sized for a call on `length` samples (reallocated when the length changes, as upstream) */
@@ -89,15 +76,24 @@ static double *audio_buffer(fsea_demod *b, double **audio, int *audio_length, in
     const int n = (int)fsea_demod_out_length(b, (size_t)length);
     if (n != *audio_length || *audio == NULL) {
         free(*audio);
-        *audio = (double *)checked_calloc((size_t)n, sizeof(double));
+        *audio = (double *)nrf_private_calloc(BLOCK, (size_t)n, sizeof(double));
         *audio_length = n;
     }
     return *audio;
 }
 
+/* nrf_raw_demodulator_process and nrf_fm_demodulator_process: `who` is the name in the message */
+static void demodulate_f64(const char *who, void *backend, double **audio, int *audio_length, double *samples_i,
+                           double *samples_q, int length) {
+    fsea_demod *b = (fsea_demod *)backend;
+    audio_buffer(b, audio, audio_length, length);
+    const int rc = fsea_demod_f64_host(b, samples_i, samples_q, (size_t)length, *audio);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, who, rc);
+}
+
 /* the reference's constructors without the backend: nrf_decoder_new owns one of its own */
 static nrf_raw_demodulator *raw_shell(int in_sample_rate, int out_sample_rate) {
-    nrf_raw_demodulator *d = (nrf_raw_demodulator *)checked_calloc(1, sizeof(nrf_raw_demodulator));
+    nrf_raw_demodulator *d = (nrf_raw_demodulator *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_raw_demodulator));
     d->in_sample_rate = in_sample_rate;
     d->out_sample_rate = out_sample_rate;
     d->downsampler_audio = nrf_downsampler_new(in_sample_rate, out_sample_rate, out_sample_rate / 2, 41);
@@ -105,7 +101,7 @@ static nrf_raw_demodulator *raw_shell(int in_sample_rate, int out_sample_rate) {
 }
 
 static nrf_fm_demodulator *fm_shell(int in_sample_rate, int out_sample_rate) {
-    nrf_fm_demodulator *d = (nrf_fm_demodulator *)checked_calloc(1, sizeof(nrf_fm_demodulator));
+    nrf_fm_demodulator *d = (nrf_fm_demodulator *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_fm_demodulator));
     const double filter_freq = FM_MAX_F * 0.8;
     d->in_sample_rate = in_sample_rate;
     d->out_sample_rate = out_sample_rate;
@@ -125,10 +121,8 @@ nrf_raw_demodulator *nrf_raw_demodulator_new(int in_sample_rate, int out_sample_
 }
 
 void nrf_raw_demodulator_process(nrf_raw_demodulator *demodulator, double *samples_i, double *samples_q, int length) {
-    fsea_demod *b = (fsea_demod *)demodulator->backend;
-    double *audio = audio_buffer(b, &demodulator->audio_samples, &demodulator->audio_samples_length, length);
-    const int rc = fsea_demod_f64_host(b, samples_i, samples_q, (size_t)length, audio);
-    if (rc != FSEA_OK) demod_fatal("nrf_raw_demodulator_process", rc);
+    demodulate_f64("nrf_raw_demodulator_process", demodulator->backend, &demodulator->audio_samples,
+                   &demodulator->audio_samples_length, samples_i, samples_q, length);
 }
 
 void nrf_raw_demodulator_free(nrf_raw_demodulator *demodulator) {
@@ -148,10 +142,8 @@ nrf_fm_demodulator *nrf_fm_demodulator_new(int in_sample_rate, int out_sample_ra
 }
 
 void nrf_fm_demodulator_process(nrf_fm_demodulator *demodulator, double *samples_i, double *samples_q, int length) {
-    fsea_demod *b = (fsea_demod *)demodulator->backend;
-    double *audio = audio_buffer(b, &demodulator->audio_samples, &demodulator->audio_samples_length, length);
-    const int rc = fsea_demod_f64_host(b, samples_i, samples_q, (size_t)length, audio);
-    if (rc != FSEA_OK) demod_fatal("nrf_fm_demodulator_process", rc);
+    demodulate_f64("nrf_fm_demodulator_process", demodulator->backend, &demodulator->audio_samples,
+                   &demodulator->audio_samples_length, samples_i, samples_q, length);
 }
 
 void nrf_fm_demodulator_free(nrf_fm_demodulator *demodulator) {
@@ -168,7 +160,7 @@ void nrf_fm_demodulator_free(nrf_fm_demodulator *demodulator) {
 /* ---- Decoder ----------------------------------------------------------------------- */
 
 nrf_decoder *nrf_decoder_new(nrf_demodulate_type demodulate_type, int in_sample_rate, int out_sample_rate, int freq_offset) {
-    nrf_decoder *decoder = (nrf_decoder *)checked_calloc(1, sizeof(nrf_decoder));
+    nrf_decoder *decoder = (nrf_decoder *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_decoder));
     decoder->in_sample_rate = in_sample_rate;
     decoder->out_sample_rate = out_sample_rate;
     decoder->demodulate_type = demodulate_type;
@@ -180,11 +172,21 @@ nrf_decoder *nrf_decoder_new(nrf_demodulate_type demodulate_type, int in_sample_
         decoder->backend = backend_new(FSEA_DEMOD_WBFM, in_sample_rate, out_sample_rate);
     }
     decoder->freq_shifter = nrf_freq_shifter_new(freq_offset, in_sample_rate);
-    if (decoder->freq_shifter == NULL) {
-        fprintf(stderr, "NRF decoder fatal error: out of memory\n");
-        exit(EXIT_FAILURE);
-    }
+    if (decoder->freq_shifter == NULL) nrf_private_oom(BLOCK);
     return decoder;
+}
+
+/* the (audio_samples, audio_samples_length) pair of the decoder's demodulator, of either type */
+static void decoder_audio(nrf_decoder *decoder, double ***audio, int **audio_length) {
+    if (decoder->demodulate_type == NRF_DEMODULATE_RAW) {
+        nrf_raw_demodulator *d = (nrf_raw_demodulator *)decoder->demodulator;
+        *audio = &d->audio_samples;
+        *audio_length = &d->audio_samples_length;
+    } else {
+        nrf_fm_demodulator *d = (nrf_fm_demodulator *)decoder->demodulator;
+        *audio = &d->audio_samples;
+        *audio_length = &d->audio_samples_length;
+    }
 }
 
 /* no demodulator: the phase advances as the reference's nrf_freq_shifter_process_samples would advance it */
@@ -210,23 +212,15 @@ void nrf_decoder_process(nrf_decoder *decoder, uint8_t *buffer, size_t length) {
         return;
     }
     int rc = fsea_demod_set_channel(b, 0, fs->freq_offset, fs->cosine, fs->sine);
-    if (rc != FSEA_OK) demod_fatal("fsea_demod_set_channel", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_demod_set_channel", rc);
     double **audio;
     int *audio_length;
-    if (decoder->demodulate_type == NRF_DEMODULATE_RAW) {
-        nrf_raw_demodulator *d = (nrf_raw_demodulator *)decoder->demodulator;
-        audio = &d->audio_samples;
-        audio_length = &d->audio_samples_length;
-    } else {
-        nrf_fm_demodulator *d = (nrf_fm_demodulator *)decoder->demodulator;
-        audio = &d->audio_samples;
-        audio_length = &d->audio_samples_length;
-    }
+    decoder_audio(decoder, &audio, &audio_length);
     audio_buffer(b, audio, audio_length, (int)length);
     rc = fsea_demod_u8_host(b, buffer, length, 0, *audio);
-    if (rc != FSEA_OK) demod_fatal("nrf_decoder_process", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "nrf_decoder_process", rc);
     rc = fsea_demod_get_channel(b, 0, NULL, &fs->cosine, &fs->sine);
-    if (rc != FSEA_OK) demod_fatal("fsea_demod_get_channel", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_demod_get_channel", rc);
     decoder->audio_samples = *audio;
     decoder->audio_samples_length = *audio_length;
 }

@@ -39,19 +39,9 @@
 
 #include "fsea.h"
 #include "nrf.h"
-#ifdef FSEA_NRF_FFT_ONLY
-/* libfsea_nrf_fft.so: only the five nrf_fft_* functions, to be linked next to the application's own
- * nut.c / nrf.c; then only the public nut.h interface is available. */
-#define nut_private_new_f64_unfilled(n_elements, n_channels) nut_buffer_new_f64((n_elements), (n_channels), NULL)
-#else
-#include "nut_private.h"
-#endif
+#include "nrf_private.h" /* also in libfsea_nrf_fft.so (-DFSEA_NRF_FFT_ONLY): the five nrf_fft_* functions alone */
 
-static void fsea_fatal(const char *what, int rc) {
-    /* same convention as src/nrf.c:54-78: print and exit */
-    fprintf(stderr, "NRF FFT fatal error: %s failed (%d): %s\n", what, rc, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
+#define BLOCK "FFT"
 
 /* taper names of nrf_fft_set_window / NRF_FFT_WINDOW -> fsea_window_fill kinds; -1 = rectangular (no taper), -2 = unknown */
 static int fsea_window_kind(const char *name) {
@@ -70,21 +60,17 @@ static void set_window_by_name(fsea_plan *plan, int fft_size, const char *name, 
     int rc;
     if (kind == -1) {
         rc = fsea_plan_set_window(plan, NULL);
-        if (rc != FSEA_OK) fsea_fatal("fsea_plan_set_window", rc);
+        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_plan_set_window", rc);
         return;
     }
-    float *w = (float *)malloc(sizeof(float) * (size_t)fft_size);
-    if (w == NULL) {
-        fprintf(stderr, "NRF FFT fatal error: out of memory\n");
-        exit(EXIT_FAILURE);
-    }
+    float *w = (float *)nrf_private_malloc(BLOCK, sizeof(float) * (size_t)fft_size);
     rc = fsea_window_fill(kind, fft_size, w);
-    if (rc != FSEA_OK) fsea_fatal("fsea_window_fill", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_window_fill", rc);
     rc = fsea_plan_set_window(plan, w); /* fails for a size without a kernel of its own: said loudly, not ignored */
     if (rc != FSEA_OK) {
         char what[96];
         snprintf(what, sizeof(what), "fsea_plan_set_window (%s)", who);
-        fsea_fatal(what, rc);
+        nrf_private_fatal(BLOCK, what, rc);
     }
     free(w);
 }
@@ -106,24 +92,19 @@ void nrf_fft_set_window(nrf_fft *fft, const char *name) {
 void nrf_fft_set_window_weights(nrf_fft *fft, const float *weights) {
     pthread_mutex_lock(&fft->mutex);
     const int rc = fsea_plan_set_window((fsea_plan *)fft->backend, weights); /* NULL: back to the reference's rectangular frames */
-    if (rc != FSEA_OK) fsea_fatal("fsea_plan_set_window (nrf_fft_set_window_weights)", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_plan_set_window (nrf_fft_set_window_weights)", rc);
     pthread_mutex_unlock(&fft->mutex);
 }
 
 nrf_fft *nrf_fft_new(int fft_size, int fft_history_size) {
-    nrf_fft *fft = (nrf_fft *)calloc(1, sizeof(nrf_fft));
-    if (fft == NULL) {
-        fprintf(stderr, "NRF FFT fatal error: out of memory\n");
-        exit(EXIT_FAILURE);
-    }
+    nrf_fft *fft = (nrf_fft *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_fft));
     nrf_block_init(&fft->block, NRF_BLOCK_GENERIC, (nrf_block_process_fn)nrf_fft_process,
                    (nrf_block_result_fn)nrf_fft_get_buffer);
     fft->fft_size = fft_size;
     fft->fft_history_size = fft_history_size;
     fsea_plan *plan = NULL;
-    const char *dev_env = getenv("NRF_FFT_DEVICE"); /* which GPU; the reference has no such notion */
-    int rc = fsea_plan_create(&plan, fft_size, fft_size, FSEA_MODE_MAG_F32, dev_env ? atoi(dev_env) : 0);
-    if (rc != FSEA_OK) fsea_fatal("fsea_plan_create", rc);
+    int rc = fsea_plan_create(&plan, fft_size, fft_size, FSEA_MODE_MAG_F32, nrf_private_device());
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_plan_create", rc);
     fft->backend = plan;
     /* the process-wide default for scenes that do not ask (an unmodified fft-sea.lua gets a taper this way); a scene or a
      * C caller that wants its own calls nrf_fft_set_window afterwards */
@@ -140,18 +121,14 @@ nrf_fft *nrf_fft_new(int fft_size, int fft_history_size) {
     if (hist_env != NULL && strcmp(hist_env, "device") == 0) {
         fsea_history *hist = NULL;
         rc = fsea_history_create(plan, fft_history_size, &hist);
-        if (rc != FSEA_OK) fsea_fatal("fsea_history_create", rc);
+        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_history_create", rc);
         fft->device_history = hist;
     }
-    fft->buffer = fft->device_history != NULL
-                      ? NULL
-                      : (double *)calloc((size_t)fft_size * (size_t)fft_history_size, sizeof(double));
-    fft->row_f32 = (float *)calloc((size_t)fft_size, sizeof(float));
-    fft->scratch = calloc((size_t)fft_size * 2, sizeof(double));
-    if ((fft->buffer == NULL && fft->device_history == NULL) || fft->row_f32 == NULL || fft->scratch == NULL) {
-        fprintf(stderr, "NRF FFT fatal error: out of memory\n");
-        exit(EXIT_FAILURE);
+    if (fft->device_history == NULL) {
+        fft->buffer = (double *)nrf_private_calloc(BLOCK, (size_t)fft_size * (size_t)fft_history_size, sizeof(double));
     }
+    fft->row_f32 = (float *)nrf_private_calloc(BLOCK, (size_t)fft_size, sizeof(float));
+    fft->scratch = nrf_private_calloc(BLOCK, (size_t)fft_size * 2, sizeof(double));
     fft->ring_head = 0;
     pthread_mutex_init(&fft->mutex, NULL);
     return fft;
@@ -164,7 +141,7 @@ void nrf_fft_shift(nrf_fft *fft, double d) {
     pthread_mutex_lock(&fft->mutex);
     if (fft->device_history != NULL) {
         const int rc = fsea_history_shift((fsea_history *)fft->device_history, shift);
-        if (rc != FSEA_OK) fsea_fatal("fsea_history_shift", rc);
+        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_history_shift", rc);
     } else if (abs(shift) >= n) {
         /* shifted out of range: start over */
         memset(fft->buffer, 0, sizeof(double) * (size_t)n * (size_t)fft->fft_history_size);
@@ -209,7 +186,7 @@ void nrf_fft_process(nrf_fft *fft, nut_buffer *buffer) {
         } else {
             rc = fsea_exec_u8_host(plan, iq, 1, 0, fft->row_f32);
         }
-        if (rc != FSEA_OK) fsea_fatal("fsea_exec_u8_host", rc);
+        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_exec_u8_host", rc);
     } else {
         const double *iq = buffer->data.f64;
         if (have < n) {
@@ -223,13 +200,12 @@ void nrf_fft_process(nrf_fft *fft, nut_buffer *buffer) {
         } else {
             rc = fsea_exec_f64_host(plan, iq, 1, fft->row_f32);
         }
-        if (rc != FSEA_OK) fsea_fatal("fsea_exec_f64_host", rc);
+        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_exec_f64_host", rc);
     }
     if (fft->device_history == NULL) {
         /* push as the newest row: the ring head moves back by one */
         fft->ring_head = (fft->ring_head + fft->fft_history_size - 1) % fft->fft_history_size;
-        double *row = fft->buffer + (size_t)fft->ring_head * (size_t)n;
-        for (int i = 0; i < n; i++) row[i] = (double)fft->row_f32[i];
+        nrf_private_widen(fft->buffer + (size_t)fft->ring_head * (size_t)n, fft->row_f32, n);
     }
     pthread_mutex_unlock(&fft->mutex);
 }
@@ -240,7 +216,7 @@ nut_buffer *nrf_fft_get_buffer(nrf_fft *fft) {
     pthread_mutex_lock(&fft->mutex);
     if (fft->device_history != NULL) {
         const int rc = fsea_history_get_f64((fsea_history *)fft->device_history, out->data.f64);
-        if (rc != FSEA_OK) fsea_fatal("fsea_history_get_f64", rc);
+        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_history_get_f64", rc);
         pthread_mutex_unlock(&fft->mutex);
         return out;
     }

@@ -17,6 +17,9 @@
 
 #include "fsea.h"
 #include "nrf.h"
+#include "nrf_private.h"
+
+#define BLOCK "interpolator"
 
 typedef struct {
     fsea_interp *interp;
@@ -24,32 +27,18 @@ typedef struct {
     int length, channels;
 } interp_backend;
 
-static void interp_fatal(const char *what, int rc) {
-    /* same convention as src/nrf.c:54-78: print and exit */
-    fprintf(stderr, "NRF interpolator fatal error: %s failed (%d): %s\n", what, rc, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
-
-static const void *payload(const nut_buffer *buffer) {
-    return buffer->type == NUT_BUFFER_U8 ? (const void *)buffer->data.u8 : (const void *)buffer->data.f64;
-}
-
 static void push(interp_backend *b, const nut_buffer *buffer) {
     if (buffer->type != b->type || buffer->length * buffer->channels != b->length * b->channels) {
         fprintf(stderr, "NRF interpolator fatal error: a buffer of type %d with %d elements follows type %d with %d\n",
                 (int)buffer->type, buffer->length * buffer->channels, (int)b->type, b->length * b->channels);
         exit(EXIT_FAILURE);
     }
-    const int rc = fsea_interp_push_host(b->interp, payload(buffer));
-    if (rc != FSEA_OK) interp_fatal("fsea_interp_push_host", rc);
+    const int rc = fsea_interp_push_host(b->interp, nrf_private_payload(buffer));
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_interp_push_host", rc);
 }
 
 nrf_interpolator *nrf_interpolator_new(double interpolate_step) {
-    nrf_interpolator *interpolator = (nrf_interpolator *)calloc(1, sizeof(nrf_interpolator));
-    if (interpolator == NULL) {
-        fprintf(stderr, "NRF interpolator fatal error: out of memory\n");
-        exit(EXIT_FAILURE);
-    }
+    nrf_interpolator *interpolator = (nrf_interpolator *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_interpolator));
     interpolator->interpolate_step = interpolate_step;
     interpolator->t = -1;
     return interpolator;
@@ -58,19 +47,18 @@ nrf_interpolator *nrf_interpolator_new(double interpolate_step) {
 void nrf_interpolator_process(nrf_interpolator *interpolator, nut_buffer *buffer) {
     if (interpolator->t < 0.0) {
         /* start: A is zeros (a fresh backend), B the buffer */
-        interp_backend *b = (interp_backend *)calloc(1, sizeof(interp_backend));
+        interp_backend *b = (interp_backend *)nrf_private_calloc(BLOCK, 1, sizeof(interp_backend));
         const int size = buffer->length * buffer->channels;
-        if (b == NULL || size < 0) {
-            fprintf(stderr, "NRF interpolator fatal error: %s\n", b == NULL ? "out of memory" : "negative buffer size");
+        if (size < 0) {
+            fprintf(stderr, "NRF interpolator fatal error: negative buffer size\n");
             exit(EXIT_FAILURE);
         }
         b->type = buffer->type;
         b->length = buffer->length;
         b->channels = buffer->channels;
-        const char *dev_env = getenv("NRF_FFT_DEVICE"); /* the GPU the nrf blocks use */
         const int rc = fsea_interp_create(&b->interp, buffer->type == NUT_BUFFER_U8 ? FSEA_IQ_U8 : FSEA_IQ_F64, (size_t)size,
-                                          dev_env ? atoi(dev_env) : 0);
-        if (rc != FSEA_OK) interp_fatal("fsea_interp_create", rc);
+                                          nrf_private_device());
+        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_interp_create", rc);
         interpolator->backend = b;
         push(b, buffer);
         interpolator->t = 0.0;
@@ -93,8 +81,8 @@ nut_buffer *nrf_interpolator_get_buffer(nrf_interpolator *interpolator) {
     nut_buffer *dst = b->type == NUT_BUFFER_U8 ? nut_buffer_new_u8(b->length, b->channels, NULL)
                                                 : nut_buffer_new_f64(b->length, b->channels, NULL);
     const double t = interpolator->t;
-    const int rc = fsea_interp_frames_host(b->interp, &t, 1, b->type == NUT_BUFFER_U8 ? (void *)dst->data.u8 : (void *)dst->data.f64);
-    if (rc != FSEA_OK) interp_fatal("fsea_interp_frames_host", rc);
+    const int rc = fsea_interp_frames_host(b->interp, &t, 1, nrf_private_payload(dst));
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_interp_frames_host", rc);
     return dst;
 }
 

@@ -19,40 +19,27 @@
 
 #include "fsea.h"
 #include "nrf.h"
-#include "nut_private.h"
+#include "nrf_private.h"
+
+#define BLOCK "IQ chain"
 
 static const double TWO_PI = 6.28318530717958647692;
-
-static void chain_fatal(const char *what, int rc) {
-    /* same convention as src/nrf.c:54-78: print and exit */
-    fprintf(stderr, "NRF IQ chain fatal error: %s failed (%d): %s\n", what, rc, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
-
-static void out_of_memory(void) {
-    fprintf(stderr, "NRF IQ chain fatal error: out of memory\n");
-    exit(EXIT_FAILURE);
-}
 
 nrf_iq_chain *nrf_iq_chain_new(int sample_rate, int half_ampl_freq, int kernel_length) {
     if (kernel_length < 1 || kernel_length > FSEA_FIR_MAX_TAPS) {
         fprintf(stderr, "NRF IQ chain fatal error: kernel length %d is outside [1, %d]\n", kernel_length, FSEA_FIR_MAX_TAPS);
         exit(EXIT_FAILURE);
     }
-    nrf_iq_chain *c = (nrf_iq_chain *)calloc(1, sizeof(nrf_iq_chain));
-    double *taps = (double *)malloc(sizeof(double) * (size_t)kernel_length);
-    if (c == NULL || taps == NULL) out_of_memory();
+    nrf_iq_chain *c = (nrf_iq_chain *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_iq_chain));
     nrf_block_init(&c->block, NRF_BLOCK_GENERIC, (nrf_block_process_fn)nrf_iq_chain_process,
                    (nrf_block_result_fn)nrf_iq_chain_get_buffer);
     c->sample_rate = sample_rate;
     c->length = kernel_length;
     c->samples_length = -1;
-    int rc = fsea_fir_lowpass_taps((double)sample_rate, (double)half_ampl_freq, kernel_length, taps);
-    if (rc != FSEA_OK) chain_fatal("fsea_fir_lowpass_taps", rc);
+    double *taps = nrf_private_lowpass_taps(BLOCK, sample_rate, half_ampl_freq, kernel_length);
     fsea_chain *backend = NULL;
-    const char *dev_env = getenv("NRF_FFT_DEVICE"); /* the GPU the nrf blocks use */
-    rc = fsea_chain_create(&backend, taps, kernel_length, dev_env ? atoi(dev_env) : 0);
-    if (rc != FSEA_OK) chain_fatal("fsea_chain_create", rc);
+    const int rc = fsea_chain_create(&backend, taps, kernel_length, nrf_private_device());
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_chain_create", rc);
     free(taps);
     c->backend = backend;
     pthread_mutex_init(&c->mutex, NULL);
@@ -70,8 +57,7 @@ void nrf_iq_chain_set_shifter(nrf_iq_chain *chain, int freq_offset) {
 /* nrf_freq_shifter_process on an F64 buffer: 2 * length pairs, the first `length` rotated + 0.5, the rest 0.0 */
 static double *shifted_f64(const nrf_iq_chain *chain, const nut_buffer *buffer, double cycles_per_sample) {
     const int length = buffer->length;
-    double *out = (double *)calloc((size_t)(length > 0 ? length : 1) * 4, sizeof(double));
-    if (out == NULL) out_of_memory();
+    double *out = (double *)nrf_private_calloc(BLOCK, (size_t)(length > 0 ? length : 1) * 4, sizeof(double));
     for (int k = 0; k < length; k++) {
         double turns = (double)(chain->consumed + (unsigned long long)k) * cycles_per_sample;
         turns -= floor(turns);
@@ -107,7 +93,7 @@ void nrf_iq_chain_process(nrf_iq_chain *chain, nut_buffer *buffer) {
     } else {
         rc = fsea_chain_run_f64_host(backend, buffer->data.f64, (size_t)length, NULL);
     }
-    if (rc != FSEA_OK) chain_fatal("nrf_iq_chain_process", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "nrf_iq_chain_process", rc);
     if (chain->shifting) chain->consumed += (unsigned long long)length;
     chain->samples_length = out_length;
     pthread_mutex_unlock(&chain->mutex);
@@ -116,7 +102,7 @@ void nrf_iq_chain_process(nrf_iq_chain *chain, nut_buffer *buffer) {
 /* one output of the resident block; the caller holds the mutex */
 static void fetch(nrf_iq_chain *chain, const fsea_chain_outputs *outputs) {
     const int rc = fsea_chain_fetch_host((fsea_chain *)chain->backend, outputs);
-    if (rc != FSEA_OK) chain_fatal("fsea_chain_fetch_host", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_chain_fetch_host", rc);
 }
 
 nut_buffer *nrf_iq_chain_get_iq_points(nrf_iq_chain *chain) {
@@ -158,13 +144,12 @@ nut_buffer *nrf_iq_chain_get_buffer(nrf_iq_chain *chain) {
     if (chain->samples_length >= 0) {
         const int length = chain->samples_length;
         result = nut_private_new_f64_unfilled(length, 2);
-        float *pairs = (float *)malloc(sizeof(float) * 2 * (size_t)(length > 0 ? length : 1));
-        if (pairs == NULL) out_of_memory();
+        float *pairs = (float *)nrf_private_malloc(BLOCK, sizeof(float) * 2 * (size_t)length);
         fsea_chain_outputs outputs;
         memset(&outputs, 0, sizeof(outputs));
         outputs.pairs = pairs;
         fetch(chain, &outputs);
-        for (int k = 0; k < 2 * length; k++) result->data.f64[k] = (double)pairs[k];
+        nrf_private_widen(result->data.f64, pairs, 2 * length);
         free(pairs);
     }
     pthread_mutex_unlock(&chain->mutex);
@@ -174,7 +159,7 @@ nut_buffer *nrf_iq_chain_get_buffer(nrf_iq_chain *chain) {
 void nrf_iq_chain_free(nrf_iq_chain *chain) {
     if (chain == NULL) return;
     const int rc = fsea_chain_destroy((fsea_chain *)chain->backend);
-    if (rc != FSEA_OK) chain_fatal("fsea_chain_destroy", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_chain_destroy", rc);
     pthread_mutex_destroy(&chain->mutex);
     free(chain);
 }

@@ -19,16 +19,12 @@
 
 #include "fsea.h"
 #include "nrf.h"
-#include "nut_private.h"
+#include "nrf_private.h"
+
+#define BLOCK "IQ draw"
 
 static pthread_mutex_t draw_mutex = PTHREAD_MUTEX_INITIALIZER;
 static fsea_iq_draw *draw_backend = NULL; /* created on first use, never freed (one per process) */
-
-static void draw_fatal(const char *what, int rc) {
-    /* same convention as src/nrf.c:54-78: print and exit */
-    fprintf(stderr, "NRF IQ draw fatal error: %s failed (%d): %s\n", what, rc, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
 
 void nrf_private_check_iq_multiplier(int size_multiplier) {
     if (size_multiplier < 1 || size_multiplier > FSEA_IQ_MAX_MULTIPLIER) {
@@ -41,9 +37,8 @@ void nrf_private_check_iq_multiplier(int size_multiplier) {
 /* the caller holds draw_mutex */
 static fsea_iq_draw *backend(void) {
     if (draw_backend == NULL) {
-        const char *dev_env = getenv("NRF_FFT_DEVICE"); /* the GPU the nrf blocks use */
-        const int rc = fsea_iq_draw_create(&draw_backend, dev_env ? atoi(dev_env) : 0);
-        if (rc != FSEA_OK) draw_fatal("fsea_iq_draw_create", rc);
+        const int rc = fsea_iq_draw_create(&draw_backend, nrf_private_device());
+        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_iq_draw_create", rc);
     }
     return draw_backend;
 }
@@ -53,23 +48,20 @@ static int elements(const nut_buffer *buffer) {
     return size > 0 ? size : 0;
 }
 
-static const void *payload(const nut_buffer *buffer, int *type) {
-    *type = buffer->type == NUT_BUFFER_U8 ? FSEA_IQ_U8 : FSEA_IQ_F64;
-    return buffer->type == NUT_BUFFER_U8 ? (const void *)buffer->data.u8 : (const void *)buffer->data.f64;
-}
+static int iq_type(const nut_buffer *buffer) { return buffer->type == NUT_BUFFER_U8 ? FSEA_IQ_U8 : FSEA_IQ_F64; }
 
 static void draw_points(const void *iq, int type, int n_pairs, nut_buffer *image) {
     pthread_mutex_lock(&draw_mutex);
     const int rc = fsea_iq_points_host(backend(), iq, type, 0, (size_t)n_pairs, image->data.u8);
     pthread_mutex_unlock(&draw_mutex);
-    if (rc != FSEA_OK) draw_fatal("fsea_iq_points_host", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_iq_points_host", rc);
 }
 
 static void draw_lines(const void *iq, int type, int n_points, int size_multiplier, nut_buffer *image) {
     pthread_mutex_lock(&draw_mutex);
     const int rc = fsea_iq_lines_host(backend(), iq, type, 0, (size_t)n_points, size_multiplier, image->data.u8);
     pthread_mutex_unlock(&draw_mutex);
-    if (rc != FSEA_OK) draw_fatal("fsea_iq_lines_host", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_iq_lines_host", rc);
 }
 
 /* The points the reference's loop `for (i = 0; i < max; i += 2)` visits, max = (int)((float)size * clamped percentage),
@@ -87,28 +79,21 @@ static nut_buffer *new_image(int side) { return nut_buffer_new_u8(side * side, 1
 
 nut_buffer *nrf_buffer_to_iq_points(nut_buffer *buffer) {
     nut_buffer *image = new_image(NRF_IQ_RESOLUTION);
-    int type;
-    const void *iq = payload(buffer, &type);
-    draw_points(iq, type, elements(buffer) / 2, image);
+    draw_points(nrf_private_payload(buffer), iq_type(buffer), elements(buffer) / 2, image);
     return image;
 }
 
 nut_buffer *nrf_buffer_to_iq_lines(nut_buffer *buffer, int size_multiplier, float line_percentage) {
     nrf_private_check_iq_multiplier(size_multiplier);
     nut_buffer *image = new_image(NRF_IQ_RESOLUTION * size_multiplier);
-    int type;
-    const void *iq = payload(buffer, &type);
-    draw_lines(iq, type, nrf_private_iq_line_points(elements(buffer), line_percentage), size_multiplier, image);
+    draw_lines(nrf_private_payload(buffer), iq_type(buffer), nrf_private_iq_line_points(elements(buffer), line_percentage),
+               size_multiplier, image);
     return image;
 }
 
 /* a copy of the device's current block, taken under its lock */
 static uint8_t *block_copy(nrf_device *device) {
-    uint8_t *copy = (uint8_t *)malloc(NRF_BUFFER_SIZE_BYTES);
-    if (copy == NULL) {
-        fprintf(stderr, "NRF IQ draw fatal error: out of memory\n");
-        exit(EXIT_FAILURE);
-    }
+    uint8_t *copy = (uint8_t *)nrf_private_malloc(BLOCK, NRF_BUFFER_SIZE_BYTES);
     pthread_mutex_lock(&device->data_mutex);
     memcpy(copy, device->samples, NRF_BUFFER_SIZE_BYTES);
     pthread_mutex_unlock(&device->data_mutex);
@@ -147,12 +132,7 @@ nut_buffer *nrf_buffer_add_position_channel(nut_buffer *buffer) {
 /* ---- Signal detector (host, double) -------------------------------------------- */
 
 nrf_signal_detector *nrf_signal_detector_new() {
-    nrf_signal_detector *detector = (nrf_signal_detector *)calloc(1, sizeof(nrf_signal_detector));
-    if (detector == NULL) {
-        fprintf(stderr, "NRF signal detector fatal error: out of memory\n");
-        exit(EXIT_FAILURE);
-    }
-    return detector;
+    return (nrf_signal_detector *)nrf_private_calloc("signal detector", 1, sizeof(nrf_signal_detector));
 }
 
 void nrf_signal_detector_process(nrf_signal_detector *detector, nut_buffer *buffer) {

@@ -17,18 +17,9 @@
 
 #include "fsea.h"
 #include "nrf.h"
-#include "nut_private.h"
+#include "nrf_private.h"
 
-static void iq_fatal(const char *what, int rc) {
-    /* same convention as src/nrf.c:54-78: print and exit */
-    fprintf(stderr, "NRF IQ filter fatal error: %s failed (%d): %s\n", what, rc, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
-
-static void out_of_memory(void) {
-    fprintf(stderr, "NRF IQ filter fatal error: out of memory\n");
-    exit(EXIT_FAILURE);
-}
+#define BLOCK "IQ filter"
 
 /* ---- FIR filter (host, double) ---------------------------------------------- */
 
@@ -38,12 +29,8 @@ double *nrf_fir_get_low_pass_coefficients(int sample_rate, int half_ampl_freq, i
         fprintf(stderr, "NRF FIR fatal error: filter length %d\n", length);
         exit(EXIT_FAILURE);
     }
-    double *taps = (double *)malloc(sizeof(double) * (size_t)m);
-    if (taps == NULL) out_of_memory();
     /* m is odd, so the design of length m is all m taps */
-    const int rc = fsea_fir_lowpass_taps((double)sample_rate, (double)half_ampl_freq, m, taps);
-    if (rc != FSEA_OK) iq_fatal("fsea_fir_lowpass_taps", rc);
-    return taps;
+    return nrf_private_lowpass_taps(BLOCK, sample_rate, half_ampl_freq, m);
 }
 
 nrf_fir_filter *nrf_fir_filter_new(int sample_rate, int half_ampl_freq, int length) {
@@ -51,15 +38,13 @@ nrf_fir_filter *nrf_fir_filter_new(int sample_rate, int half_ampl_freq, int leng
         fprintf(stderr, "NRF FIR fatal error: filter length %d is not >= 1\n", length);
         exit(EXIT_FAILURE);
     }
-    nrf_fir_filter *filter = (nrf_fir_filter *)calloc(1, sizeof(nrf_fir_filter));
-    if (filter == NULL) out_of_memory();
+    nrf_fir_filter *filter = (nrf_fir_filter *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_fir_filter));
     filter->length = length;
     filter->coefficients = nrf_fir_get_low_pass_coefficients(sample_rate, half_ampl_freq, length);
     filter->offset = length - 1;
     filter->center = length / 2;
     filter->samples_length = filter->offset;
-    filter->samples = (double *)calloc((size_t)(filter->offset > 0 ? filter->offset : 1), sizeof(double));
-    if (filter->samples == NULL) out_of_memory();
+    filter->samples = (double *)nrf_private_calloc(BLOCK, (size_t)filter->offset, sizeof(double));
     return filter;
 }
 
@@ -71,8 +56,7 @@ void nrf_fir_filter_load(nrf_fir_filter *filter, double *samples, int length) {
     if (new_length == filter->samples_length) {
         memmove(filter->samples, tail, sizeof(double) * (size_t)offset); /* regions overlap when length < offset */
     } else {
-        double *next = (double *)malloc(sizeof(double) * (size_t)(new_length > 0 ? new_length : 1));
-        if (next == NULL) out_of_memory();
+        double *next = (double *)nrf_private_malloc(BLOCK, sizeof(double) * (size_t)new_length);
         memcpy(next, tail, sizeof(double) * (size_t)offset);
         free(filter->samples);
         filter->samples = next;
@@ -101,18 +85,14 @@ nrf_iq_filter *nrf_iq_filter_new(int sample_rate, int half_ampl_freq, int kernel
         fprintf(stderr, "NRF IQ filter fatal error: kernel length %d is outside [1, %d]\n", kernel_length, FSEA_FIR_MAX_TAPS);
         exit(EXIT_FAILURE);
     }
-    nrf_iq_filter *f = (nrf_iq_filter *)calloc(1, sizeof(nrf_iq_filter));
-    double *taps = (double *)malloc(sizeof(double) * (size_t)kernel_length);
-    if (f == NULL || taps == NULL) out_of_memory();
+    nrf_iq_filter *f = (nrf_iq_filter *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_iq_filter));
     nrf_block_init(&f->block, NRF_BLOCK_GENERIC, (nrf_block_process_fn)nrf_iq_filter_process,
                    (nrf_block_result_fn)nrf_iq_filter_get_buffer);
     f->length = kernel_length;
-    int rc = fsea_fir_lowpass_taps((double)sample_rate, (double)half_ampl_freq, kernel_length, taps);
-    if (rc != FSEA_OK) iq_fatal("fsea_fir_lowpass_taps", rc);
+    double *taps = nrf_private_lowpass_taps(BLOCK, sample_rate, half_ampl_freq, kernel_length);
     fsea_fir *fir = NULL;
-    const char *dev_env = getenv("NRF_FFT_DEVICE"); /* the GPU the nrf blocks use */
-    rc = fsea_fir_create(&fir, taps, kernel_length, dev_env ? atoi(dev_env) : 0);
-    if (rc != FSEA_OK) iq_fatal("fsea_fir_create", rc);
+    const int rc = fsea_fir_create(&fir, taps, kernel_length, nrf_private_device());
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_fir_create", rc);
     free(taps);
     f->backend = fir;
     pthread_mutex_init(&f->mutex, NULL);
@@ -125,8 +105,7 @@ void nrf_iq_filter_process(nrf_iq_filter *filter, nut_buffer *buffer) {
     pthread_mutex_lock(&filter->mutex);
     if (length > filter->output_capacity) {
         free(filter->output);
-        filter->output = (float *)malloc(sizeof(float) * 2 * (size_t)length);
-        if (filter->output == NULL) out_of_memory();
+        filter->output = (float *)nrf_private_malloc(BLOCK, sizeof(float) * 2 * (size_t)length);
         filter->output_capacity = length;
     }
     int rc = FSEA_OK;
@@ -136,7 +115,7 @@ void nrf_iq_filter_process(nrf_iq_filter *filter, nut_buffer *buffer) {
     } else {
         rc = fsea_fir_f64_host((fsea_fir *)filter->backend, buffer->data.f64, (size_t)length, filter->output);
     }
-    if (rc != FSEA_OK) iq_fatal("nrf_iq_filter_process", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "nrf_iq_filter_process", rc);
     filter->samples_length = length;
     pthread_mutex_unlock(&filter->mutex);
 }
@@ -145,7 +124,7 @@ nut_buffer *nrf_iq_filter_get_buffer(nrf_iq_filter *f) {
     pthread_mutex_lock(&f->mutex);
     const int length = f->samples_length;
     nut_buffer *result = nut_private_new_f64_unfilled(length, 2);
-    for (int k = 0; k < 2 * length; k++) result->data.f64[k] = (double)f->output[k];
+    nrf_private_widen(result->data.f64, f->output, 2 * length);
     pthread_mutex_unlock(&f->mutex);
     return result;
 }
@@ -153,7 +132,7 @@ nut_buffer *nrf_iq_filter_get_buffer(nrf_iq_filter *f) {
 void nrf_iq_filter_free(nrf_iq_filter *filter) {
     if (filter == NULL) return;
     const int rc = fsea_fir_destroy((fsea_fir *)filter->backend);
-    if (rc != FSEA_OK) iq_fatal("fsea_fir_destroy", rc);
+    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_fir_destroy", rc);
     pthread_mutex_destroy(&filter->mutex);
     free(filter->output);
     free(filter);

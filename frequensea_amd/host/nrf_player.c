@@ -13,21 +13,18 @@
 #include <string.h>
 
 #include "nrf.h"
+#include "nrf_private.h"
+
+#define BLOCK "player"
 
 static const int AUDIO_SAMPLE_RATE = 48000;
-
-static void player_oom(void) {
-    fprintf(stderr, "NRF player fatal error: out of memory\n");
-    exit(EXIT_FAILURE);
-}
 
 static float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 static void player_decode(nrf_device *device, void *ctx) {
     nrf_player *player = (nrf_player *)ctx;
     if (player->shutting_down) return;
-    uint8_t *block = (uint8_t *)malloc(NRF_BUFFER_SIZE_BYTES);
-    if (block == NULL) player_oom();
+    uint8_t *block = (uint8_t *)nrf_private_malloc(BLOCK, NRF_BUFFER_SIZE_BYTES);
     pthread_mutex_lock(&device->data_mutex);
     memcpy(block, device->samples, NRF_BUFFER_SIZE_BYTES);
     pthread_mutex_unlock(&device->data_mutex);
@@ -36,8 +33,7 @@ static void player_decode(nrf_device *device, void *ctx) {
     free(block);
     const double *audio = player->decoder->audio_samples;
     const int length = audio ? player->decoder->audio_samples_length : 0;
-    int16_t *pcm = (int16_t *)malloc(sizeof(int16_t) * (size_t)(length > 0 ? length : 1));
-    if (pcm == NULL) player_oom();
+    int16_t *pcm = (int16_t *)nrf_private_malloc(BLOCK, sizeof(int16_t) * (size_t)(length > 0 ? length : 1));
     for (int i = 0; i < length; i++) pcm[i] = (int16_t)(audio[i] * 32000);
 
     if (player->pcm_file != NULL && length > 0) {
@@ -59,8 +55,7 @@ static void player_decode(nrf_device *device, void *ctx) {
 }
 
 nrf_player *nrf_player_new(nrf_device *device, nrf_demodulate_type demodulate_type, int freq_offset) {
-    nrf_player *player = (nrf_player *)calloc(1, sizeof(nrf_player));
-    if (player == NULL) player_oom();
+    nrf_player *player = (nrf_player *)nrf_private_calloc(BLOCK, 1, sizeof(nrf_player));
     player->demodulate_type = demodulate_type;
     player->device = device;
     player->decoder = nrf_decoder_new(demodulate_type, device->sample_rate, AUDIO_SAMPLE_RATE, freq_offset);

@@ -8,7 +8,7 @@
  */
 #define _POSIX_C_SOURCE 200809L
 #include "nut.h"
-#include "nut_private.h"
+#include "nrf_private.h"
 
 #include <assert.h>
 #include <math.h>
@@ -26,10 +26,6 @@ void nut_sleep_milliseconds(int duration_ms) {
 
 static size_t elem_size(nut_buffer_type type) {
     return type == NUT_BUFFER_U8 ? sizeof(uint8_t) : sizeof(double);
-}
-
-static void *payload(const nut_buffer *b) {
-    return b->type == NUT_BUFFER_U8 ? (void *)b->data.u8 : (void *)b->data.f64;
 }
 
 static void set_payload(nut_buffer *b, void *p) {
@@ -68,7 +64,7 @@ static nut_buffer *nut_alloc(nut_buffer_type type, int length, int channels, con
     return nut_alloc_mode(type, length, channels, init, 1);
 }
 
-/* Library-internal (nut_private.h): F64 buffer whose contents the caller is about to write in full. */
+/* Library-internal (nrf_private.h): F64 buffer whose contents the caller is about to write in full. */
 nut_buffer *nut_private_new_f64_unfilled(int n_elements, int n_channels) {
     return nut_alloc_mode(NUT_BUFFER_F64, n_elements, n_channels, NULL, 0);
 }
@@ -83,13 +79,13 @@ nut_buffer *nut_buffer_new_f64(int n_elements, int n_channels, const double *ini
 
 nut_buffer *nut_buffer_copy(nut_buffer *source) {
     assert(source != NULL);
-    return nut_alloc(source->type, source->length, source->channels, payload(source));
+    return nut_alloc(source->type, source->length, source->channels, nrf_private_payload(source));
 }
 
 nut_buffer *nut_buffer_reduce(nut_buffer *source, double fraction) {
     assert(source != NULL);
     const double f = fraction < 0.0 ? 0.0 : (fraction > 1.0 ? 1.0 : fraction);
-    return nut_alloc(source->type, (int)round(source->length * f), source->channels, payload(source));
+    return nut_alloc(source->type, (int)round(source->length * f), source->channels, nrf_private_payload(source));
 }
 
 nut_buffer *nut_buffer_clip(nut_buffer *source, int first, int count) {
@@ -98,14 +94,14 @@ nut_buffer *nut_buffer_clip(nut_buffer *source, int first, int count) {
     assert(count < 0 || available >= count);
     const int keep = (count < 0 || count > available) ? available : count;
     /* the reference advances the data pointer by `first` elements, not frames */
-    const uint8_t *from = (const uint8_t *)payload(source) + (size_t)first * elem_size(source->type);
+    const uint8_t *from = (const uint8_t *)nrf_private_payload(source) + (size_t)first * elem_size(source->type);
     return nut_alloc(source->type, keep, source->channels, from);
 }
 
 void nut_buffer_set_data(nut_buffer *target, nut_buffer *origin) {
     assert(target != NULL && origin != NULL);
     assert(target->type == origin->type && target->size_bytes == origin->size_bytes);
-    memcpy(payload(target), payload(origin), (size_t)target->size_bytes);
+    memcpy(nrf_private_payload(target), nrf_private_payload(origin), (size_t)target->size_bytes);
 }
 
 void nut_buffer_append(nut_buffer *target, nut_buffer *origin) {
@@ -119,9 +115,9 @@ void nut_buffer_append(nut_buffer *target, nut_buffer *origin) {
         fprintf(stderr, "nut_buffer_append: out of memory\n");
         exit(EXIT_FAILURE);
     }
-    memcpy(grown, payload(target), (size_t)target->size_bytes);
-    memcpy(grown + target_elems * es, payload(origin), (size_t)origin->size_bytes);
-    free(payload(target));
+    memcpy(grown, nrf_private_payload(target), (size_t)target->size_bytes);
+    memcpy(grown + target_elems * es, nrf_private_payload(origin), (size_t)origin->size_bytes);
+    free(nrf_private_payload(target));
     set_payload(target, grown);
     target->size_bytes = (int)((target_elems + origin_elems) * es);
     target->length += origin->length;
@@ -169,13 +165,13 @@ void nut_buffer_save(nut_buffer *source, const char *path) {
     assert(source != NULL);
     FILE *out = fopen(path, "wb");
     if (out == NULL) return;
-    fwrite(payload(source), (size_t)source->size_bytes, 1, out);
+    fwrite(nrf_private_payload(source), (size_t)source->size_bytes, 1, out);
     fclose(out);
     printf("Written %s.\n", path);
 }
 
 void nut_buffer_free(nut_buffer *victim) {
     if (victim == NULL) return;
-    free(payload(victim));
+    free(nrf_private_payload(victim));
     free(victim);
 }

@@ -21,93 +21,28 @@
  *             kernel (fsea_plan_set_window; the reference's tools are rectangular, c/fft-batch.c:65-66 -- the default)
  *   --timing  print, at the end, the seconds each of the three stages was busy and the wall time of the loop
  */
-#include <fcntl.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/stat.h>
-#include <sys/types.h>
-#include <unistd.h>
 
 #include "easypng.h"
 #include "fsea.h"
 #include "pipeline.h"
+#include "tool_common.h"
 
-#define TRANSFER_BYTES 262144 /* one HackRF transfer: 131072 IQ samples */
-#define EVALUATE_ROWS 100     /* c/fft-batch-broad.c:22 */
-
-static void die(const char *what) {
-    fprintf(stderr, "fsea-fft-batch: %s: %s\n", what, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
-
-/* --window NAME: the periodic cosine-sum taper of that name on the plan (include/fsea.h: fsea_window_fill) */
-static int set_named_window(fsea_plan *plan, const char *name, int n) {
-    static const char *names[] = {"rect", "hann", "hamming", "blackman", "blackmanharris", "flattop"};
-    for (int k = 0; k < 6; k++) {
-        if (strcmp(name, names[k]) != 0) continue;
-        float *w = (float *)malloc(sizeof(float) * (size_t)n);
-        if (!w) return -1;
-        int rc = fsea_window_fill(k, n, w);
-        if (rc == 0 && k != 0) rc = fsea_plan_set_window(plan, w);
-        free(w);
-        return rc;
-    }
-    fprintf(stderr, "fsea-fft-batch: unknown window '%s' (hann, hamming, blackman, blackmanharris, flattop)\n", name);
-    return -1;
-}
+static void die(const char *what) { tool_die("fsea-fft-batch", what); }
 
 typedef struct {
     char **args;          /* FREQ_MHZ=capture.raw, one per item */
-    int rows_wanted, skip;
-    size_t row_in;
+    int fft_size, rows_wanted, skip;
 } batch_ctx;
 
-/* reader thread: rows of one capture, newest first: row y <- first 2N bytes of transfer skip + rows - 1 - y
- * (c/fft-batch.c:62-74).  0 = loaded, > 0 = fatal (cannot open, short read), < 0 = too few transfers (skip it). */
+/* reader thread: the rows of one capture (tool_load_rows), a capture with too few transfers being one to skip */
 static int load_capture(void *vctx, int item, uint8_t *packed, int *rows_out) {
     const batch_ctx *ctx = (const batch_ctx *)vctx;
     const char *path = strchr(ctx->args[item], '=') + 1;
-    /* one pread per row (a row is the first 2N bytes of a 262144-byte transfer): stdio's fseek + fread pair refills its
-     * buffer for every row, twice the system calls for the 4.9 million rows of the reference's narrow sweep */
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) {
-        fprintf(stderr, "fsea-fft-batch: cannot open %s\n", path);
-        return 1;
-    }
-    struct stat st;
-    if (fstat(fd, &st) != 0) {
-        fprintf(stderr, "fsea-fft-batch: cannot stat %s\n", path);
-        close(fd);
-        return 1;
-    }
-    const long transfers = (long)(st.st_size / TRANSFER_BYTES);
-    int rows = (int)(transfers - ctx->skip);
-    if (rows > ctx->rows_wanted) rows = ctx->rows_wanted;
-    if (rows <= 0) {
-        fprintf(stderr, "fsea-fft-batch: %s holds %ld transfers, need more than %d\n", path, transfers, ctx->skip);
-        close(fd);
-        return -1;
-    }
-    for (int y = 0; y < rows; y++) {
-        const off_t tr = (off_t)ctx->skip + rows - 1 - y;
-        uint8_t *dst = packed + (size_t)y * ctx->row_in;
-        size_t got = 0;
-        while (got < ctx->row_in) {
-            const ssize_t r = pread(fd, dst + got, ctx->row_in - got, tr * (off_t)TRANSFER_BYTES + (off_t)got);
-            if (r <= 0) break;
-            got += (size_t)r;
-        }
-        if (got != ctx->row_in) {
-            fprintf(stderr, "Short read, samples lost, exiting!\n");
-            close(fd);
-            return 1;
-        }
-    }
-    close(fd);
-    *rows_out = rows;
-    return 0;
+    return tool_load_rows("fsea-fft-batch", path, ctx->fft_size, ctx->skip, ctx->rows_wanted, 0, packed, rows_out);
 }
 
 int main(int argc, char **argv) {
@@ -138,7 +73,13 @@ int main(int argc, char **argv) {
     if (fsea_plan_create(&plan, fft_size, fft_size, broad ? FSEA_MODE_DB5_U8_DCFIX : FSEA_MODE_DB10_U8, device) != 0) {
         die("fsea_plan_create");
     }
-    if (window && set_named_window(plan, window, fft_size) != 0) die("--window");
+    if (window) {
+        const int rc = tool_set_named_window(plan, window, fft_size);
+        if (rc == TOOL_WINDOW_UNKNOWN) {
+            fprintf(stderr, "fsea-fft-batch: unknown window '%s' (hann, hamming, blackman, blackmanharris, flattop)\n", window);
+        }
+        if (rc != 0) die("--window");
+    }
     /* two GPU slots: stream + device buffers each; capture k uses slot (number of captures sent to the GPU so far) % 2 */
     typedef struct {
         void *stream, *d_iq, *d_px;
@@ -163,7 +104,7 @@ int main(int argc, char **argv) {
             return EXIT_FAILURE;
         }
     }
-    batch_ctx ctx = {argv + first_capture, rows_wanted, skip, row_in};
+    batch_ctx ctx = {argv + first_capture, fft_size, rows_wanted, skip};
     capture_reader reader;
     png_writer writer;
     if (capture_reader_start(&reader, argc - first_capture, load_capture, &ctx, (uint8_t *)packed[0], (uint8_t *)packed[1]) != 0 ||

@@ -22,6 +22,7 @@
 #include "easypng.h"
 #include "fsea.h"
 #include "imgaxis.h"
+#include "tool_common.h"
 
 /* Tile PNGs are decoded ahead of the composite loop by a few threads: at the reference's own geometry (c/fft-stitch.c:16-27:
  * 300 tiles of 1024 x 16384) the inflate of one tile takes longer than its upload + max-composite on the GPU, and 300 of
@@ -71,10 +72,7 @@ static void *decoder_main(void *p) {
     return NULL;
 }
 
-static void die(const char *what) {
-    fprintf(stderr, "fsea-fft-stitch: %s: %s\n", what, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
+static void die(const char *what) { tool_die("fsea-fft-stitch", what); }
 
 int main(int argc, char **argv) {
     int broad = 0, device = 0, rows = -1, footer = 0;

@@ -26,23 +26,18 @@
  *             position k is placed at x = k * FFT_SIZE / (SAMPLE_RATE / FREQUENCY_STEP)
  *   --chunk   tiles per gather (default 4)
  */
-#include <fcntl.h>
 #include <math.h>
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/stat.h>
-#include <sys/types.h>
-#include <unistd.h>
 
 #include "easypng.h"
 #include "fsea.h"
 #include "fsea_comm.h"
 #include "pipeline.h"
+#include "tool_common.h"
 
-#define TRANSFER_BYTES 262144 /* one HackRF transfer: 131072 IQ samples */
-#define EVALUATE_ROWS 100     /* c/fft-batch-broad.c:22 */
 #define MAX_MEMBERS 64
 
 typedef struct {
@@ -130,58 +125,18 @@ static int parse_devices(const char *text, int *devices) {
     return n;
 }
 
-/* rows of one capture, newest first: row y <- first 2N bytes of transfer skip + rows - 1 - y (c/fft-batch.c:62-74) */
-static int load_capture(const sweep_config *cfg, const capture *cap, uint8_t *packed, int *rows_out) {
-    const size_t row_in = (size_t)2 * (size_t)cfg->fft_size;
-    /* one pread per row, as fsea-fft-batch reads (a row is the first 2N bytes of a 262144-byte transfer) */
-    const int fd = open(cap->path, O_RDONLY);
-    if (fd < 0) {
-        fprintf(stderr, "fsea-fft-sweep: cannot open %s\n", cap->path);
-        return -1;
-    }
-    struct stat st;
-    if (fstat(fd, &st) != 0) {
-        fprintf(stderr, "fsea-fft-sweep: cannot stat %s\n", cap->path);
-        close(fd);
-        return -1;
-    }
-    const long transfers = (long)(st.st_size / TRANSFER_BYTES);
-    int rows = (int)(transfers - cfg->skip);
-    if (rows > cfg->rows_wanted) rows = cfg->rows_wanted;
-    if (rows < cfg->rows_wanted) {
-        fprintf(stderr, "fsea-fft-sweep: %s holds %ld transfers, need %d after skipping %d\n", cap->path, transfers,
-                cfg->rows_wanted, cfg->skip);
-        close(fd);
-        return -1;
-    }
-    for (int y = 0; y < rows; y++) {
-        const off_t tr = (off_t)cfg->skip + rows - 1 - y;
-        uint8_t *dst = packed + (size_t)y * row_in;
-        size_t got = 0;
-        while (got < row_in) {
-            const ssize_t r = pread(fd, dst + got, row_in - got, tr * (off_t)TRANSFER_BYTES + (off_t)got);
-            if (r <= 0) break;
-            got += (size_t)r;
-        }
-        if (got != row_in) {
-            fprintf(stderr, "Short read, samples lost, exiting!\n");
-            close(fd);
-            return -1;
-        }
-    }
-    close(fd);
-    *rows_out = rows;
-    return 0;
-}
-
 typedef struct {
     const sweep_config *cfg;
     int first; /* index of the member's first capture */
 } member_reader_ctx;
 
+/* reader thread: the rows of one capture, as fsea-fft-batch reads them (tool_load_rows); a tile needs all its rows */
 static int member_loader(void *vctx, int item, uint8_t *packed, int *rows_out) {
     const member_reader_ctx *c = (const member_reader_ctx *)vctx;
-    return load_capture(c->cfg, &c->cfg->captures[c->first + item], packed, rows_out);
+    const sweep_config *cfg = c->cfg;
+    const int rc = tool_load_rows("fsea-fft-sweep", cfg->captures[c->first + item].path, cfg->fft_size, cfg->skip,
+                                  cfg->rows_wanted, 1, packed, rows_out);
+    return rc == 0 ? 0 : -1;
 }
 
 static void *member_main(void *argp) {
@@ -216,15 +171,9 @@ static void *member_main(void *argp) {
     CHECK(fsea_plan_create(&plan, n, n, cfg->broad ? FSEA_MODE_DB5_U8_DCFIX : FSEA_MODE_DB10_U8, device) == 0,
           "member %d: fsea_plan_create", me);
     if (cfg->window) {
-        static const char *names[] = {"rect", "hann", "hamming", "blackman", "blackmanharris", "flattop"};
-        int kind = -1;
-        for (int k = 0; k < 6; k++) {
-            if (strcmp(cfg->window, names[k]) == 0) kind = k;
-        }
-        CHECK(kind >= 0, "unknown window '%s' (hann, hamming, blackman, blackmanharris, flattop)", cfg->window);
-        float *w = (float *)malloc(sizeof(float) * (size_t)n);
-        CHECK(w && fsea_window_fill(kind, n, w) == 0 && (kind == 0 || fsea_plan_set_window(plan, w) == 0), "member %d: --window", me);
-        free(w);
+        const int rc = tool_set_named_window(plan, cfg->window, n);
+        CHECK(rc != TOOL_WINDOW_UNKNOWN, "unknown window '%s' (hann, hamming, blackman, blackmanharris, flattop)", cfg->window);
+        CHECK(rc == 0, "member %d: --window", me);
     }
     CHECK(fsea_comm_stream_create(device, &stream) == 0 && fsea_comm_stream_create(device, &stream2) == 0, "member %d: stream", me);
     CHECK(fsea_device_alloc(device, (size_t)rows * row_in, &d_iq2[0]) == 0 &&

@@ -23,20 +23,15 @@
 
 #include "easypng.h"
 #include "fsea.h"
+#include "tool_common.h"
 
 #define PI 3.14159265358979323846 /* glibc's M_PI */
 #define CHUNK_FRAMES 16           /* frames per fsea_interp_image_frames_host call */
 #define MAX_PAIR_FRAMES (1 << 20)
 
-static void usage_error(const char *msg) {
-    fprintf(stderr, "fsea-gradual-noise: %s\n", msg);
-    exit(EXIT_FAILURE);
-}
+static void usage_error(const char *msg) { tool_usage_error("fsea-gradual-noise", msg); }
 
-static void die(const char *what) {
-    fprintf(stderr, "fsea-gradual-noise: %s: %s\n", what, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
+static void die(const char *what) { tool_die("fsea-gradual-noise", what); }
 
 static double sine_ease_in_out(double p) { return 0.5 * (1 - cos(p * PI)); }
 

@@ -23,18 +23,13 @@
 
 #include "easypng.h"
 #include "fsea.h"
+#include "tool_common.h"
 
 #define CHUNK_FRAMES 16 /* frames per fsea_trace_frames_host call */
 
-static void usage_error(const char *msg) {
-    fprintf(stderr, "fsea-single-sample: %s\n", msg);
-    exit(EXIT_FAILURE);
-}
+static void usage_error(const char *msg) { tool_usage_error("fsea-single-sample", msg); }
 
-static void die(const char *what) {
-    fprintf(stderr, "fsea-single-sample: %s: %s\n", what, fsea_last_error_string());
-    exit(EXIT_FAILURE);
-}
+static void die(const char *what) { tool_die("fsea-single-sample", what); }
 
 static int write_frame(const char *out_dir, int raw, long index, int width, int height, const uint8_t *image) {
     char fname[1100];
