@@ -52,6 +52,18 @@ class ChainOutputs(ctypes.Structure):
                 ("n_line_points", ctypes.c_size_t), ("pairs", ctypes.c_void_p)]
 
 
+class CaptureRun(ctypes.Structure):
+    """fsea_capture_run (include/fsea.h)."""
+    _fields_ = [("first_block", ctypes.c_size_t), ("n_blocks", ctypes.c_size_t), ("continues", ctypes.c_int),
+                ("open", ctypes.c_int)]
+
+
+class CaptureBurstInfo(ctypes.Structure):
+    """fsea_capture_burst_info (include/fsea.h)."""
+    _fields_ = [("first_block", ctypes.c_size_t), ("n_blocks", ctypes.c_size_t), ("n_pairs", ctypes.c_size_t),
+                ("open", ctypes.c_int), ("d_pairs", ctypes.c_void_p)]
+
+
 # Every function include/fsea.h declares, once: name -> (restype, argtypes).  hip_lib() applies the table, EXPORTS is its
 # names; tests check both against the header and the built library.
 _vp, _sz, _ci, _f64, _u32, _u64, _str = (ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double, ctypes.c_uint32,
@@ -59,6 +71,7 @@ _vp, _sz, _ci, _f64, _u32, _u64, _str = (ctypes.c_void_p, ctypes.c_size_t, ctype
 _out = ctypes.POINTER(_vp)        # where a create / alloc function puts its handle
 _f32p, _uip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint)
 _stage, _outputs, _geo = ctypes.POINTER(ChainStage), ctypes.POINTER(ChainOutputs), ctypes.POINTER(InterpGeometry)
+_f64p, _szp = ctypes.POINTER(_f64), ctypes.POINTER(_sz)
 API = {
     "fsea_device_count": (_ci, [ctypes.POINTER(_ci)]),
     "fsea_last_error_string": (_str, []),
@@ -150,6 +163,25 @@ API = {
     "fsea_trace_frames_device": (_ci, [_vp, _vp, _sz, _ci, _sz, _ci, _vp, _vp]),
     "fsea_trace_frames_host": (_ci, [_vp, _vp, _sz, _ci, _sz, _ci, _vp]),
     "fsea_trace_canvas_host": (_ci, [_vp, _vp]),
+    "fsea_detect_create": (_ci, [_out, _ci]),
+    "fsea_detect_destroy": (_ci, [_vp]),
+    "fsea_detect_u8_device": (_ci, [_vp, _vp, _sz, _sz, _ci, _vp, _vp]),
+    "fsea_detect_u8_host": (_ci, [_vp, _vp, _sz, _sz, _ci, _vp, _vp]),
+    "fsea_detect_moments": (_ci, [_vp, _sz, _f64p, _f64p]),
+    "fsea_detect_finish": (_ci, [_vp, _sz, _f64p, _f64p]),
+    "fsea_capture_create": (_ci, [_out, _vp, _ci, _ci]),
+    "fsea_capture_destroy": (_ci, [_vp]),
+    "fsea_capture_reset": (_ci, [_vp]),
+    "fsea_capture_scan_device": (_ci, [_vp, _vp, _sz, _sz, _ci, _f64, _vp]),
+    "fsea_capture_scan_host": (_ci, [_vp, _vp, _sz, _sz, _ci, _f64]),
+    "fsea_capture_segment": (_ci, [_vp, _sz, _f64, _ci, ctypes.POINTER(CaptureRun), _szp]),
+    "fsea_capture_n_blocks": (_sz, [_vp]),
+    "fsea_capture_stats": (_ci, [_vp, _sz, _f64p, _f64p]),
+    "fsea_capture_n_bursts": (_sz, [_vp]),
+    "fsea_capture_burst": (_ci, [_vp, _sz, ctypes.POINTER(CaptureBurstInfo)]),
+    "fsea_capture_burst_pairs_host": (_ci, [_vp, _sz, _vp]),
+    "fsea_capture_burst_lines_device": (_ci, [_vp, _sz, _ci, _sz, _vp, _vp]),
+    "fsea_capture_burst_lines_host": (_ci, [_vp, _sz, _ci, _sz, _vp]),
 }
 # include/fsea_tune.h: only libfsea_hip_tune.so (scripts/tune.py and friends) has these
 TUNE_API = {
@@ -727,6 +759,107 @@ class Trace(_ResettableHandle):
         out = np.empty((self.height, self.width), dtype=np.uint8)
         _check(self._L.fsea_trace_canvas_host(self._p, out.ctypes.data))
         return out
+
+
+def detect_finish(sums, n_elements):
+    """fsea_detect_finish: (mean, sd) of a block of n_elements bytes from its three integer sums (host arithmetic, needs no
+    GPU)."""
+    a = np.ascontiguousarray(sums, dtype=np.uint64).ravel()
+    mean, sd = ctypes.c_double(), ctypes.c_double()
+    _check(hip_lib().fsea_detect_finish(a.ctypes.data, n_elements, ctypes.byref(mean), ctypes.byref(sd)))
+    return mean.value, sd.value
+
+
+def capture_segment(sd, threshold, capturing=False):
+    """fsea_capture_segment: the scene's state machine over the standard deviations of a scan's blocks -> a list of
+    (first_block, n_blocks, continues, open) (host arithmetic, needs no GPU)."""
+    a = np.ascontiguousarray(sd, dtype=np.float64).ravel()
+    runs, n = (CaptureRun * (a.size // 2 + 1))(), ctypes.c_size_t(0)
+    _check(hip_lib().fsea_capture_segment(a.ctypes.data if a.size else None, a.size, float(threshold), int(bool(capturing)),
+                                          runs, ctypes.byref(n)))
+    return [(r.first_block, r.n_blocks, bool(r.continues), bool(r.open)) for r in runs[:n.value]]
+
+
+class Detect(_Handle):
+    """The burst detector of the reference's signal scene on one device; thin wrapper over fsea_detect_*: per block of
+    8-bit samples the three integer sums of nrf_signal_detector_process, or its mean and standard deviation."""
+    _kind = "detect"
+
+    def __init__(self, device=0):
+        self.device = device
+        self._create("fsea_detect_create", device)
+
+    def sums_device(self, d_iq_ptr, block_bytes, n_blocks, d_sums_ptr, flip=False, stream=0):
+        """Device pointers (ints, 16-byte aligned): n_blocks blocks in, three uint64 per block out; asynchronous."""
+        _check(self._L.fsea_detect_u8_device(self._p, d_iq_ptr, block_bytes, n_blocks, int(bool(flip)), d_sums_ptr,
+                                             stream or None))
+
+    def run(self, iq_u8, block_bytes, flip=False):
+        """Host uint8 bytes -> (mean, sd), one float64 each per whole block of block_bytes."""
+        iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
+        n = iq.size // int(block_bytes) if int(block_bytes) > 0 else 0
+        mean, sd = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+        _check(self._L.fsea_detect_u8_host(self._p, iq.ctypes.data, block_bytes, n, int(bool(flip)), mean.ctypes.data,
+                                           sd.ctypes.data))
+        return mean, sd
+
+
+class Capture(_ResettableHandle):
+    """The signal scene on a recording that stays on the device; thin wrapper over fsea_capture_*.  scan() finds the
+    bursts and filters their blocks; the bursts accumulate until reset()."""
+    _kind = "capture"
+
+    def __init__(self, taps, device=0):
+        t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
+        self.n_taps, self.device = t.size, device
+        self._create("fsea_capture_create", t.ctypes.data if t.size else None, t.size, device)
+
+    def scan(self, iq_u8, block_bytes, threshold, flip=False):
+        """Host uint8 bytes, every whole block of block_bytes; returns the number of bursts so far."""
+        iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
+        n = iq.size // int(block_bytes) if int(block_bytes) > 0 else 0
+        _check(self._L.fsea_capture_scan_host(self._p, iq.ctypes.data, block_bytes, n, int(bool(flip)), float(threshold)))
+        return self.n_bursts
+
+    def scan_device(self, d_iq_ptr, block_bytes, n_blocks, threshold, flip=False, stream=0):
+        _check(self._L.fsea_capture_scan_device(self._p, d_iq_ptr, block_bytes, n_blocks, int(bool(flip)), float(threshold),
+                                                stream or None))
+        return self.n_bursts
+
+    def stats(self):
+        """(mean, sd) of the last scan's blocks."""
+        n = self._L.fsea_capture_n_blocks(self._p)
+        out = np.empty((2, n), dtype=np.float64)
+        m, s = ctypes.c_double(), ctypes.c_double()
+        for b in range(n):
+            _check(self._L.fsea_capture_stats(self._p, b, ctypes.byref(m), ctypes.byref(s)))
+            out[:, b] = m.value, s.value
+        return out[0], out[1]
+
+    @property
+    def n_bursts(self):
+        return self._L.fsea_capture_n_bursts(self._p)
+
+    def burst(self, k):
+        """CaptureBurstInfo of burst k."""
+        info = CaptureBurstInfo()
+        _check(self._L.fsea_capture_burst(self._p, k, ctypes.byref(info)))
+        return info
+
+    def burst_pairs(self, k):
+        out = np.empty(self.burst(k).n_pairs, dtype=np.complex64)
+        _check(self._L.fsea_capture_burst_pairs_host(self._p, k, out.ctypes.data))
+        return out
+
+    def burst_lines(self, k, m=1, n_points=None):
+        """(256 m, 256 m) uint8: the burst's first n_points points (default all) joined in order."""
+        n = self.burst(k).n_pairs if n_points is None else int(n_points)
+        img = np.empty((256 * m, 256 * m), dtype=np.uint8)
+        _check(self._L.fsea_capture_burst_lines_host(self._p, k, int(m), n, img.ctypes.data))
+        return img
+
+    def burst_lines_device(self, k, m, n_points, d_image_ptr, stream=0):
+        _check(self._L.fsea_capture_burst_lines_device(self._p, k, int(m), n_points, d_image_ptr, stream or None))
 
 
 class PinnedArray:

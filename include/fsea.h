@@ -30,6 +30,9 @@
  *                         nrf_fir_get_low_pass_coefficients and the per-sample convolution loops of
  *                         nrf_fir_filter_get / nrf_iq_filter_get_buffer, src/nrf.c:654-775
  *   fsea_chain_*          shift -> filter -> images per block with the filtered block resident on the device
+ *   fsea_detect_*         the burst detector of lua/signal-detector.lua: the two loops of nrf_signal_detector_process,
+ *                         src/nrf.c:883-898, as integer sums over many blocks per launch
+ *   fsea_capture_*        that scene on a resident recording: detect -> gate -> filter the bursts -> line images
  *   fsea_iq_*             the IQ constellation images: the per-sample loops of nrf_buffer_to_iq_points /
  *                         nrf_device_get_iq_buffer and the Bresenham rasteriser of nrf_buffer_to_iq_lines /
  *                         nrf_device_get_iq_lines, src/nrf.c:359-421, 519-553
@@ -59,6 +62,8 @@ typedef struct fsea_chain fsea_chain;
 typedef struct fsea_demod fsea_demod;
 typedef struct fsea_interp fsea_interp;
 typedef struct fsea_trace fsea_trace;
+typedef struct fsea_detect fsea_detect;
+typedef struct fsea_capture fsea_capture;
 
 /* Epilogue modes.  Output element type and row length are per mode. */
 enum {
@@ -456,6 +461,98 @@ int fsea_chain_run_f64_host(fsea_chain *chain, const double *iq, size_t n_sample
 int fsea_chain_fetch_host(fsea_chain *chain, const fsea_chain_outputs *outputs);
 int fsea_chain_run_device(fsea_chain *chain, const void *d_iq, size_t n_samples, int n_frames, const fsea_chain_stage *stage,
                           const fsea_chain_outputs *d_outputs, void *stream);
+
+/* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
+ * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With
+ * x_i = byte_i / 256.0 and n = block_bytes the reference computes
+ *     mean = (sum of x_i over even i) / n * 2,    standard_deviation = sqrt(sum over all i of (x_i - mean)^2 / mean)
+ * -- it divides by the mean, not by n; an all-zero block gives NaN.  The device part is three exact unsigned 64-bit sums per
+ * block over the bytes as the detector sees them (flip != 0: b ^ 0x80 first, as in the other entry points): sums[3 b] the
+ * bytes at even offsets of block b, sums[3 b + 1] all bytes, sums[3 b + 2] their squares.  Integer sums: the same bits
+ * whatever the launch geometry, one launch of n_blocks blocks or n_blocks launches of one.
+ *   u8_device: asynchronous on `stream`; d_iq and d_sums 16-byte aligned; only the n_blocks * block_bytes bytes are read.
+ *   u8_host:   upload, launch, finish: mean[b] and sd[b] per block.  Staged through pinned memory on the object's own
+ *              stream; calls on one object from several threads are serialised.
+ *   moments, finish: host arithmetic, callable in a process without a GPU.  mean is the reference's value bit for bit (its
+ *              first loop adds multiples of 1/256 below 2^53: exact).  diffs_total, the reference's sum of (x_i - mean)^2,
+ *              comes from the sums centred on the integer nearest to 256 mean in exact 64-bit arithmetic, so a quiet block
+ *              loses nothing to cancellation (within 8 * 2^-53 relative of the exact value, exactly 0 where that is 0);
+ *              sd = sqrt(diffs_total / mean) with the reference's division and root, NaN for a zero mean.
+ * Every form checks its arguments before any device work: FSEA_EINVAL for a NULL object or buffer, a block_bytes that is
+ * odd, below 2 or above 2^31, n_blocks == 0, more than 2^40 bytes in all, a misaligned device pointer, sums no block of
+ * n_elements bytes can have.  Create: FSEA_ENODEVICE without a GPU.  Destroy waits for the device. */
+int fsea_detect_create(fsea_detect **detect, int device);
+int fsea_detect_destroy(fsea_detect *detect);
+int fsea_detect_u8_device(fsea_detect *detect, const void *d_iq, size_t block_bytes, size_t n_blocks, int flip,
+                          uint64_t *d_sums, void *stream);
+int fsea_detect_u8_host(fsea_detect *detect, const uint8_t *iq, size_t block_bytes, size_t n_blocks, int flip, double *mean,
+                        double *sd);
+int fsea_detect_moments(const uint64_t sums[3], size_t n_elements, double *mean, double *diffs_total);
+int fsea_detect_finish(const uint64_t sums[3], size_t n_elements, double *mean, double *sd);
+
+/* The signal scene on a recording that stays on the device (lua/signal-detector.lua:89-133): detect the bursts, low-pass
+ * the blocks of each burst, keep them appended, draw a burst as a growing line image.  The object owns a detector
+ * (fsea_detect), a chain (fsea_chain: the filter taps are given at create, the stream's tail is carried), a draw object and
+ * a growing device buffer of the bursts' filtered f32 pairs.  Nothing here computes beyond the detector: the filter launches
+ * are fsea_chain_run_device on runs of consecutive blocks of the resident recording and the images are
+ * fsea_iq_lines_device (FSEA_IQ_F32) on a resident burst, so every pair and every pixel is what those calls give, bit for
+ * bit.
+ *   scan: one detector launch over all blocks, one copy of 24 n_blocks bytes to the host, the scene's state machine there
+ *       (fsea_capture_segment), then per burst one filter run over its blocks, n_frames = its block count, appended to the
+ *       burst buffer: what nut_buffer_append builds in the scene's draw_buffer.  Returns when the bursts are complete.
+ *       The filter's tail carries across bursts and across scans, and so does the state machine: a burst still open at the
+ *       end of a scan is reported with open != 0 and continued by the next scan.  Bursts accumulate, numbered from 0, until
+ *       reset, which also zeroes the tail.  block_bytes is a multiple of 16 here (every run of blocks is then a 16-byte
+ *       aligned piece of the recording); d_iq 16-byte aligned.  scan_host uploads the recording into device memory of the
+ *       object first.
+ *       A scan that fails after the detector (a filter launch, an allocation) leaves the bursts, the statistics and the
+ *       filter's tail partly advanced: call reset before the object is used again.
+ *   segment: the state machine alone, host arithmetic.  DETECTING: a block with sd > threshold starts a burst.  CAPTURING:
+ *       blocks with sd > threshold join it; the first block at or below the threshold ends it and is dropped.  A NaN is
+ *       not above the threshold.  capturing != 0: a burst is open from an earlier scan; runs[0] then continues it
+ *       (continues != 0) and may have no block at all, when the first block ends it.  `runs` has room for
+ *       n_blocks / 2 + 1 entries.
+ *   stats: mean and standard deviation of block `block` of the last scan.
+ *   burst: first_block counts the blocks of all scans since create or reset; d_pairs is valid until the next scan, reset
+ *       or destroy.  burst_pairs_host: 2 n_pairs floats.  burst_lines_*: fsea_iq_lines_* over the burst's first
+ *       n_line_points pairs; the device form is asynchronous on `stream`, d_image 16-byte aligned.
+ * Every form checks its arguments before any device work (FSEA_EINVAL: as fsea_detect_u8_device, a block_bytes that is no
+ * multiple of 16, a block or burst index out of range, n_line_points above the burst's pairs, a size_multiplier outside
+ * [1, FSEA_IQ_MAX_MULTIPLIER]).  Create: as fsea_fir_create, FSEA_ENODEVICE without a GPU.  Destroy and reset wait for the
+ * device.  Calls on one object from several threads are serialised. */
+typedef struct {
+    size_t first_block;   /* in the scan's blocks (fsea_capture_segment) or in all blocks since reset (fsea_capture_burst) */
+    size_t n_blocks;
+    int continues;        /* the run belongs to the burst that was open before the scan */
+    int open;             /* the scan ended inside the run */
+} fsea_capture_run;
+
+typedef struct {
+    size_t first_block;
+    size_t n_blocks;
+    size_t n_pairs;
+    int open;
+    const float *d_pairs; /* device memory: n_pairs (I, Q) pairs */
+} fsea_capture_burst_info;
+
+int fsea_capture_create(fsea_capture **capture, const double *taps, int n_taps, int device);
+int fsea_capture_destroy(fsea_capture *capture);
+int fsea_capture_reset(fsea_capture *capture);
+int fsea_capture_scan_device(fsea_capture *capture, const void *d_iq, size_t block_bytes, size_t n_blocks, int flip,
+                             double threshold, void *stream);
+int fsea_capture_scan_host(fsea_capture *capture, const uint8_t *iq, size_t block_bytes, size_t n_blocks, int flip,
+                           double threshold);
+int fsea_capture_segment(const double *sd, size_t n_blocks, double threshold, int capturing, fsea_capture_run *runs,
+                         size_t *n_runs);
+size_t fsea_capture_n_blocks(const fsea_capture *capture);
+int fsea_capture_stats(const fsea_capture *capture, size_t block, double *mean, double *sd);
+size_t fsea_capture_n_bursts(const fsea_capture *capture);
+int fsea_capture_burst(const fsea_capture *capture, size_t burst, fsea_capture_burst_info *info);
+int fsea_capture_burst_pairs_host(fsea_capture *capture, size_t burst, float *pairs);
+int fsea_capture_burst_lines_device(fsea_capture *capture, size_t burst, int size_multiplier, size_t n_line_points,
+                                    void *d_image, void *stream);
+int fsea_capture_burst_lines_host(fsea_capture *capture, size_t burst, int size_multiplier, size_t n_line_points,
+                                  uint8_t *image);
 
 /* Blends of two resident sample blocks for an array of weights: the batched form of the reference's nrf_interpolator
  * (src/nrf.c:442-496) and of the frame loop of its movie tool (c/gradual-noise.c:96-112).  The object owns two device

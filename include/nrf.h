@@ -332,6 +332,44 @@ nut_buffer *nrf_iq_chain_get_iq_lines(nrf_iq_chain *chain, int size_multiplier, 
 nut_buffer *nrf_iq_chain_get_buffer(nrf_iq_chain *chain);
 void nrf_iq_chain_free(nrf_iq_chain *chain);
 
+/* ---- ADDITIONS (not in the reference): the signal capture ---- */
+
+/* The reference's signal scene (lua/signal-detector.lua:89-133) over a whole recording that stays on the GPU: the detector
+ * of nrf_signal_detector_process on every block in one launch, the scene's state machine over the statistics, the blocks of
+ * each burst through the filter of nrf_iq_filter_new(sample_rate, half_ampl_freq, kernel_length) and appended, a burst
+ * drawn as nrf_buffer_to_iq_lines draws the scene's draw_buffer (fsea_capture_*, include/fsea.h).  The contract is
+ * equivalence with the block sequence:
+ *   - get_mean is nrf_signal_detector_process's mean bit for bit, get_standard_deviation its standard deviation to within
+ *     (n / 2 + 16) 2^-53 relative, n the elements of a block (the reference's own sequential sum is no closer to the exact
+ *     value);
+ *   - a block with standard deviation > threshold starts or continues a burst; the first block at or below it ends the
+ *     burst and is dropped; a NaN is not above the threshold;
+ *   - get_burst is nrf_iq_filter_process + nrf_iq_filter_get_buffer over the gated blocks in order, joined by
+ *     nut_buffer_append, bit for bit: one filter for the whole life of the object, its tail carried across bursts and scans;
+ *   - get_iq_lines is nrf_buffer_to_iq_lines of get_burst's buffer byte for byte.
+ * scan takes a U8 buffer with 2 channels; block_length is in IQ pairs and a multiple of 8; a trailing partial block is
+ * ignored.  Bursts are numbered from 0 and accumulate over the scans of one object; a burst still open at the end of a scan
+ * is continued by the next one.  scan returns the number of bursts so far.  The scene's shader gain and alpha fade are
+ * rendering and not part of this.  A kernel length outside [1, FSEA_FIR_MAX_TAPS], a block or burst index out of range, a
+ * size_multiplier outside [1, FSEA_IQ_MAX_MULTIPLIER] and a backend failure (no GPU) print and exit.  The buffers returned
+ * are the caller's to free. */
+typedef struct {
+    int sample_rate;   /* Hz */
+    int length;        /* taps */
+    double threshold;  /* the scene's signal_threshold */
+    void *backend;     /* fsea_capture* (libfsea_hip.so) */
+    pthread_mutex_t mutex;
+} nrf_signal_capture;
+
+nrf_signal_capture *nrf_signal_capture_new(int sample_rate, int half_ampl_freq, int kernel_length, double threshold);
+int nrf_signal_capture_scan(nrf_signal_capture *capture, nut_buffer *recording, int block_length);
+double nrf_signal_capture_get_mean(nrf_signal_capture *capture, int block);
+double nrf_signal_capture_get_standard_deviation(nrf_signal_capture *capture, int block);
+/* The burst's filtered pairs, F64 with 2 channels: what the scene's draw_buffer holds. */
+nut_buffer *nrf_signal_capture_get_burst(nrf_signal_capture *capture, int burst);
+nut_buffer *nrf_signal_capture_get_iq_lines(nrf_signal_capture *capture, int burst, int size_multiplier, float line_percentage);
+void nrf_signal_capture_free(nrf_signal_capture *capture);
+
 /* ---- Signal detector (src/nrf.h:209-218, src/nrf.c:876-903): host, double, the reference's layout ---- */
 
 /* process: mean = 2 * (sum of the I elements) / size, standard_deviation = sqrt(sum over all elements of
