@@ -58,6 +58,49 @@ def check_mode(got, iq, n, n_frames, hop, flip, mode):
     return check_float(got, want)
 
 
+def any_size_spectra(iq, n, nf, hop, flip, exact=None):
+    """f64 spectra of nf frames for a transform size the oracle's power-of-two FFT does not take: the oracle's own unpack
+    loop in front of its O(n^2) long-double DFT (`exact`, by default for n <= 1001) or of numpy's f64 FFT (an O(n^2)
+    check of a large n would take minutes)."""
+    exact = n <= 1001 if exact is None else exact
+    iq = np.ascontiguousarray(iq, dtype=np.uint8).ravel()
+    spectra = np.empty((nf, n), dtype=np.complex128)
+    for f in range(nf):
+        raw = iq[2 * f * hop: 2 * (f * hop + n)]
+        x = O.unpack_center_u8(O.flip_u8(raw) if flip else raw)
+        spectra[f] = O.dft_naive(x) if exact else np.fft.fft(x)
+    return spectra
+
+
+def rows_of_spectra(spectra, mode):
+    """The oracle's magnitude / pixel loops over f64 spectra (modes 4 and 5, for which it exports no row function: the
+    expressions of its orc_epilogue)."""
+    if mode == 0:
+        return np.stack([O.mag_row(s) for s in spectra])
+    if mode in (1, 2):
+        return np.stack([O.db_u8_row(s, 10.0 if mode == 1 else 5.0, int(mode == 2)) for s in spectra])
+    if mode == 3:
+        return spectra
+    if mode == 4:
+        return np.abs(spectra)
+    return 10.0 * np.log10(spectra.real ** 2 + spectra.imag ** 2 + 1.0e-20)
+
+
+def check_spectra(got, spectra, mode):
+    """check_mode against f64 spectra that the caller computed (and may share between modes)."""
+    want = rows_of_spectra(spectra, mode)
+    if mode in (1, 2):
+        return check_u8(got, want)
+    if mode == 5:
+        return check_db(got, want, np.abs(spectra))
+    return check_float(got, want)
+
+
+def check_any_size(got, iq, n, nf, hop, flip, mode, exact=None):
+    """check_mode for the sizes without a kernel of their own (Bluestein, four-step): same bounds, reference any_size_spectra."""
+    return check_spectra(got, any_size_spectra(iq, n, nf, hop, flip, exact), mode)
+
+
 def check_mode_shifted(got, iq, n, n_frames, hop, flip, mode, cycles_per_sample, phase0_cycles=0.0):
     """check_mode for the frequency-shifted path (oracle: orc_rows_shifted)."""
     kw = dict(hop=hop, flip=flip)

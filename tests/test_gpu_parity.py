@@ -756,19 +756,6 @@ def test_nrf_fft_lua_sizes_and_f64_input(golden, history_mode):
         L.nrf_fft_free(fft)
 
 
-def _expected_rows_any_size(iq, n, nf, hop, flip, mode, exact):
-    """Rows for a transform size the oracle's power-of-two FFT does not take: the oracle's own loops around its O(n^2)
-    long-double DFT (`exact`, small n) or around numpy's f64 FFT (large n: an O(n^2) check there would take minutes)."""
-    rows = []
-    for f in range(nf):
-        raw = iq[2 * f * hop: 2 * (f * hop + n)]
-        x = O.unpack_center_u8(O.flip_u8(raw) if flip else raw)
-        spec = O.dft_naive(x) if exact else np.fft.fft(x)
-        rows.append({0: lambda: O.mag_row(spec), 1: lambda: O.db_u8_row(spec, 10.0, 0), 2: lambda: O.db_u8_row(spec, 5.0, 1),
-                     3: lambda: spec, 4: lambda: np.abs(spec)}[mode]())
-    return np.stack(rows)
-
-
 @pytest.mark.parametrize("n", [1000, 1001, 96, 17, 16, 2, 3000, 8191])
 def test_transform_sizes_fftw_takes_and_the_kernels_do_not(n):
     """`fftw_plan_dft_1d` (src/nrf.c:564) takes any size; the gfx950 kernels are powers of two from 32 to 16384.  Every
@@ -784,11 +771,7 @@ def test_transform_sizes_fftw_takes_and_the_kernels_do_not(n):
                 assert plan.kernel_name.startswith("bluestein(fsea_fft")
                 got = plan.exec_host(iq, nf, flip=flip)
                 plan.close()
-                want = _expected_rows_any_size(iq, n, nf, hop, flip, mode, exact)
-                if mode in (1, 2):
-                    parity.check_u8(got, want)
-                else:
-                    parity.check_float(got, want)
+                parity.check_any_size(got, iq, n, nf, hop, flip, mode, exact)
                 if mode in (0, 2) and n >= 4:
                     assert np.array_equal(got[:, n // 2], got[:, n // 2 - 1])
     # resident data, a batch larger than the work buffers' chunk, f64 input, and the entry points that do not exist
@@ -801,7 +784,7 @@ def test_transform_sizes_fftw_takes_and_the_kernels_do_not(n):
     plan.synchronize()
     got = d_out.download(np.float32, (nf, n))
     for f in (0, nf // 2, nf - 1):
-        parity.check_float(got[f:f + 1], _expected_rows_any_size(iq[2 * f * n:], n, 1, n, True, 0, exact))
+        parity.check_any_size(got[f:f + 1], iq[2 * f * n:], n, 1, n, True, 0, exact)
     x = np.random.default_rng(n).normal(0, 0.3, 2 * 2 * n)
     got = plan.exec_host_f64(x, 2)
     for f in range(2):
@@ -827,16 +810,13 @@ def test_transform_sizes_above_the_largest_kernel(n):
         assert plan.kernel_name.startswith(("fourstep(", "bluestein(fourstep("))
         got = plan.exec_host(iq, nf)
         plan.close()
-        want = _expected_rows_any_size(iq, n, nf, n, True, mode, False)
+        parity.check_any_size(got, iq, n, nf, n, True, mode, False)
         if mode == 2:
-            parity.check_u8(got, want)
             assert np.array_equal(got[:, n // 2], got[:, n // 2 - 1])
-        else:
-            parity.check_float(got, want)
     if n == 32768:                       # offset-binary bytes, f64 input, resident data
         plan = fsea.Plan(n, mode=3)
         got = plan.exec_host(iq ^ np.uint8(0x80), nf, flip=False)
-        parity.check_float(got, _expected_rows_any_size(iq, n, nf, n, True, 3, False))
+        parity.check_any_size(got, iq, n, nf, n, True, 3, False)
         x = np.random.default_rng(1).normal(0, 0.3, 2 * n)
         parity.check_float(plan.exec_host_f64(x, 1)[0], np.fft.fft(O.unpack_center_f64(x)))
         plan.close()
@@ -856,8 +836,8 @@ def test_nrf_fft_with_a_size_that_is_not_a_power_of_two(history_mode):
     out = L.nrf_fft_get_buffer(fft)
     hist = nrf.buffer_to_numpy(L, out).reshape(h, n)
     L.nut_buffer_free(out)
-    want = np.stack([O.mag_row(O.dft_naive(O.unpack_center_u8(raw[: 2 * n]))) for raw in reversed(raws)])
-    parity.check_float(hist[:3], want)
+    spectra = np.concatenate([parity.any_size_spectra(raw, n, 1, n, False, exact=True) for raw in reversed(raws)])
+    parity.check_spectra(hist[:3], spectra, 0)
     assert not hist[3].any()
     ref = hist.copy()
     O.fft_shift(ref, n, h, 7.0)
