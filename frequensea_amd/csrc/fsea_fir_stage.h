@@ -1,0 +1,174 @@
+// fsea_fir_stage.h -- how an input sample becomes the f32 complex value a FIR kernel stages in LDS, shared by the kernels of
+// fsea_fir.hip (fsea_fir_u8, fsea_fir_f64, fsea_shift_fir_u8) and fsea_zoom.hip (fsea_shift_decim_u8): the byte and f64
+// conversions, the frequency shift of fsea_fir_u8_shifted_* (include/fsea.h) with every rounding spelled out, the packed
+// tap FMA, and the host side of the shift (FirRot from the caller's arguments, the argument limits).  A sample's value is a
+// function of (cycles_per_sample, phase0_cycles, stream position) alone, so every kernel that stages through these
+// helpers sees the same bits.
+#pragma once
+
+#include "fsea_internal.h"
+
+#include <cmath>
+
+#include "fsea_pk_asm.h"
+
+namespace fsea_stage {
+
+using fsea::cf;
+using fsea::cf2;
+
+enum { FIR_IN_U8 = 0, FIR_IN_F64 = 1 };
+constexpr double FIR_MAX_CYCLES = 1048576.0;               // |cycles_per_sample| the shifted forms accept
+constexpr uint64_t FIR_MAX_POSITION = (uint64_t)1 << 52;   // stream positions stay exact as doubles
+
+// The frequency shift of one launch (fsea_shift_fir_u8), by value in the kernel arguments.
+struct FirRot {
+    double delta;      // cycles per sample
+    double phase0;     // phase0_cycles reduced to [0, 1)
+    long long offset;  // stream position of the call's sample 0
+    long long n_in;    // samples the input holds; samples n_in .. n - 1 of the call are plain 0.0
+    cf step[8];        // e^{2 pi i delta j}, j < 8, rounded from double
+};
+
+// acc + w * tap, the tap broadcast from the low (even k) or the high (odd k) half of an SGPR pair
+__device__ __forceinline__ cf pk_tap_fma_lo(cf w, cf taps, cf acc) {
+    cf t;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(t) : "v"(w), "s"(taps), "v"(acc));
+    return t;
+}
+__device__ __forceinline__ cf pk_tap_fma_hi(cf w, cf taps, cf acc) {
+    cf t;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(t) : "v"(w), "s"(taps), "v"(acc));
+    return t;
+}
+
+// e^{2 pi i (phase0 + delta P)} for a stream position P: delta * P is the exact sum of the rounded product and its fma
+// residual, so the reduced phase is good to ~2^-50 turns whatever P (P < 2^52 is exact as a double); float only then
+__device__ __forceinline__ cf rot_base(const FirRot &r, long long P) {
+    const double k = (double)P;
+    const double hi = __dmul_rn(r.delta, k);
+    const double lo = fma(r.delta, k, -hi);
+    double t = (hi - floor(hi)) + (lo + r.phase0);
+    t -= floor(t);
+    float s, c;
+    sincospif(2.0f * (float)t, &s, &c);
+    return cf{c, s};
+}
+
+// r.step[j] without indexing the kernel arguments by a lane's value (that would move them to scratch)
+__device__ __forceinline__ cf rot_step(const FirRot &r, int j) {
+    cf w = r.step[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) w = (j == i) ? r.step[i] : w;
+    return w;
+}
+
+// a * b with every rounding spelled out: the same bits wherever it is inlined
+__device__ __forceinline__ cf rot_mul(cf a, cf b) {
+    return cf{__fmaf_rn(a[0], b[0], -__fmul_rn(a[1], b[1])), __fmaf_rn(a[0], b[1], __fmul_rn(a[1], b[0]))};
+}
+
+// the shifter's output for the sample u = u8 / 256 at a position whose phasor is ph
+__device__ __forceinline__ cf rot_sample(cf u, cf ph) {
+    const cf p = rot_mul(u, ph);
+    return cf{__fadd_rn(p[0], 0.5f), __fadd_rn(p[1], 0.5f)};
+}
+
+template <int KIND>
+__device__ __forceinline__ cf load_sample(const void *__restrict__ in, long long s, uint32_t flip) {
+    if (KIND == FIR_IN_U8) {
+        const uint32_t b = ((uint32_t)(static_cast<const uint16_t *>(in))[s] ^ flip) & 0xffffu;
+        return cf{(float)(b & 0xffu) * (1.0f / 256.0f), (float)(b >> 8) * (1.0f / 256.0f)};
+    } else {
+        const double2 d = (static_cast<const double2 *>(in))[s];
+        return cf{(float)d.x, (float)d.y};
+    }
+}
+
+// eight consecutive samples from s (a multiple of 8, all inside the input)
+template <int KIND>
+__device__ __forceinline__ void load_group(const void *__restrict__ in, long long s, uint32_t flip, cf v[8]) {
+    if (KIND == FIR_IN_U8) {
+        const uint4 q = (static_cast<const uint4 *>(in))[s >> 3];
+        const uint32_t w[4] = {q.x ^ flip, q.y ^ flip, q.z ^ flip, q.w ^ flip};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[2 * j] = cf{(float)(w[j] & 0xffu), (float)((w[j] >> 8) & 0xffu)} * (1.0f / 256.0f);
+            v[2 * j + 1] = cf{(float)((w[j] >> 16) & 0xffu), (float)(w[j] >> 24)} * (1.0f / 256.0f);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = load_sample<KIND>(in, s + j, flip);
+    }
+}
+
+// sample s of the call (0 <= s < n) as the filter sees it
+template <int KIND, bool ROT>
+__device__ __forceinline__ cf load_input(const void *__restrict__ in, long long s, uint32_t flip, const FirRot &rot) {
+    if constexpr (ROT) {
+        if (s >= rot.n_in) return cf{0.0f, 0.0f};
+        const long long P = rot.offset + s;
+        return rot_sample(load_sample<KIND>(in, s, flip), rot_mul(rot_base(rot, P & ~7LL), rot_step(rot, (int)(P & 7))));
+    } else {
+        return load_sample<KIND>(in, s, flip);
+    }
+}
+
+// One staged group: the eight samples s .. s + 7 of a call (s a multiple of 8, negative in the tail) as the filter sees
+// them.  tail_in holds the L - 1 samples in front of the call (rotated already); past the n_in samples of the input: 0.0.
+template <int KIND, bool ROT>
+__device__ __forceinline__ void stage_group(const void *in, long long s, long long n_in, uint32_t flip, const cf *tail_in, int L,
+                                            const FirRot &rot, cf v[8]) {
+    if (s >= 0 && s + 8 <= n_in) {
+        load_group<KIND>(in, s, flip, v);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const long long ss = s + j;
+            v[j] = ss < 0 ? (ss + (L - 1) >= 0 ? tail_in[ss + (L - 1)] : cf{0.0f, 0.0f})
+                          : (ss < n_in ? load_sample<KIND>(in, ss, flip) : cf{0.0f, 0.0f});
+        }
+    }
+    if constexpr (ROT) {
+        // the group's input samples (the tail is rotated already, zeros stay zeros): stream positions P0 + j, in one
+        // block of eight or two
+        if (s >= 0 && s < n_in) {
+            const long long P0 = rot.offset + s;
+            const int o = (int)(rot.offset & 7);   // == P0 & 7: s is a multiple of 8
+            const cf b0 = rot_base(rot, P0 - o);
+            const cf b1 = o ? rot_base(rot, P0 - o + 8) : b0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const cf ph = rot_mul(o + j < 8 ? b0 : b1, rot_step(rot, (o + j) & 7));
+                if (s + j < n_in) v[j] = rot_sample(v[j], ph);
+            }
+        }
+    }
+}
+
+// What the shifted kernel needs for a call whose sample 0 is at stream position `offset`, n_in samples behind its input.
+inline FirRot make_rot(double cycles_per_sample, double phase0_cycles, uint64_t offset, size_t n_in) {
+    FirRot r;
+    r.delta = cycles_per_sample;
+    r.phase0 = phase0_cycles - std::floor(phase0_cycles);
+    r.offset = (long long)offset;
+    r.n_in = (long long)n_in;
+    for (int j = 0; j < 8; ++j) {
+        double t = cycles_per_sample * j;
+        t -= std::floor(t);
+        r.step[j] = cf{(float)std::cos(2.0 * M_PI * t), (float)std::sin(2.0 * M_PI * t)};
+    }
+    return r;
+}
+
+inline int check_shift(double cycles_per_sample, double phase0_cycles, uint64_t offset, size_t n) {
+    if (!(std::fabs(cycles_per_sample) <= FIR_MAX_CYCLES) || !std::isfinite(phase0_cycles)) {
+        return fsea_detail::fail(FSEA_EINVAL, "cycles_per_sample must be finite and within +-%g, phase0_cycles finite", FIR_MAX_CYCLES);
+    }
+    if (offset > FIR_MAX_POSITION || n > FIR_MAX_POSITION - offset) {
+        return fsea_detail::fail(FSEA_EINVAL, "sample_offset + n_samples must not exceed 2^52");
+    }
+    return FSEA_OK;
+}
+
+}  // namespace fsea_stage

@@ -1,6 +1,6 @@
 // fsea_internal.h -- what the translation units of libfsea_hip.so share behind the C ABI (include/fsea.h): the plan
-// object, error plumbing, the launch dispatcher, owning buffers, and the scaffold of the eight device objects (FIR, IQ draw,
-// demod, interp, chain, trace, detect, capture): shared argument checks, create / destroy, the event-ordered scratch buffer, host-form
+// object, error plumbing, the launch dispatcher, owning buffers, and the scaffold of the nine device objects (FIR, IQ draw,
+// demod, interp, chain, zoom, trace, detect, capture): shared argument checks, create / destroy, the event-ordered scratch buffer, host-form
 // staging.  fsea_api.hip: the error plumbing, the scaffold's bodies and the entry points that take no plan;
 // fsea_plan.hip: the kernel registry, a plan's life cycle, the launch path and the device-buffer entry points;
 // fsea_plan_host.hip: the host-buffer entry points and the history ring; fsea_anysize.hip: the transform sizes without a

@@ -23,6 +23,8 @@ _MODE_DTYPE = {
 }
 
 FIR_MAX_TAPS = 512          # FSEA_FIR_MAX_TAPS (include/fsea.h)
+ZOOM_MAX_DECIMATION = 64    # FSEA_ZOOM_MAX_DECIMATION
+ZOOM_TILE_OUTPUTS = 128     # FSEA_ZOOM_TILE_OUTPUTS: outputs per workgroup of fsea_shift_decim_u8
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
@@ -131,6 +133,15 @@ API = {
     "fsea_chain_run_f64_host": (_ci, [_vp, _vp, _sz, _outputs]),
     "fsea_chain_fetch_host": (_ci, [_vp, _outputs]),
     "fsea_chain_run_device": (_ci, [_vp, _vp, _sz, _ci, _stage, _outputs, _vp]),
+    "fsea_zoom_create": (_ci, [_out, _vp, _ci, _ci, _ci, _ci, _ci, _ci]),
+    "fsea_zoom_destroy": (_ci, [_vp]),
+    "fsea_zoom_reset": (_ci, [_vp]),
+    "fsea_zoom_set_window": (_ci, [_vp, _vp]),
+    "fsea_zoom_out_pairs": (_sz, [_vp, _sz]),
+    "fsea_zoom_out_rows": (_sz, [_vp, _sz]),
+    "fsea_zoom_row_bytes": (_sz, [_vp]),
+    "fsea_zoom_run_device": (_ci, [_vp, _vp, _sz, _ci, _f64, _f64, _u64, _vp, _vp, _vp]),
+    "fsea_zoom_run_host": (_ci, [_vp, _vp, _sz, _ci, _f64, _f64, _u64, _vp, _vp]),
     "fsea_iq_draw_create": (_ci, [_out, _ci]),
     "fsea_iq_draw_destroy": (_ci, [_vp]),
     "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
@@ -564,6 +575,58 @@ class Chain(_ResettableHandle):
         _check(self._L.fsea_chain_run_device(self._p, d_iq_ptr, n_samples, n_frames,
                                              ctypes.byref(stage) if stage is not None else None, ctypes.byref(o),
                                              stream or None))
+
+
+class Zoom(_ResettableHandle):
+    """Shift -> decimating low-pass -> FFT on one device, the decimated pairs resident between the two; thin wrapper over
+    fsea_zoom_*.  run() takes 8-bit IQ from the host and returns (rows, pairs): the rows of the inner (fft_size, hop, mode)
+    plan on the len // decimation decimated pairs of this call, and those pairs where asked for.  Each call continues the
+    filter of the previous ones; sample_offset is the number of samples they consumed."""
+    _kind = "zoom"
+
+    def __init__(self, taps, decimation, fft_size, hop=None, mode=MODE_MAG_F32, device=0):
+        t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
+        self.n_taps, self.decimation, self.device = t.size, decimation, device
+        self.fft_size, self.hop, self.mode = fft_size, fft_size if hop is None else hop, mode
+        self._create("fsea_zoom_create", t.ctypes.data if t.size else None, t.size, decimation, fft_size, self.hop, mode, device)
+
+    def set_window(self, w):
+        """fsea_zoom_set_window: Plan.set_window on the inner plan."""
+        if w is None:
+            _check(self._L.fsea_zoom_set_window(self._p, None))
+            return
+        if isinstance(w, str):
+            w = window(w, self.fft_size)
+        wf = np.ascontiguousarray(w, dtype=np.float32).ravel()
+        if wf.size != self.fft_size:
+            raise ValueError("a window has fft_size weights")
+        _check(self._L.fsea_zoom_set_window(self._p, wf.ctypes.data))
+
+    def out_pairs(self, n_samples):
+        return self._L.fsea_zoom_out_pairs(self._p, n_samples)
+
+    def out_rows(self, n_samples):
+        return self._L.fsea_zoom_out_rows(self._p, n_samples)
+
+    @property
+    def row_bytes(self):
+        return self._L.fsea_zoom_row_bytes(self._p)
+
+    def run(self, iq_u8, cycles_per_sample, phase0_cycles=0.0, sample_offset=0, flip=False, pairs=False):
+        iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
+        n = iq.size // 2
+        rows = np.empty((self.out_rows(n), self.fft_size), dtype=_MODE_DTYPE[self.mode])
+        out = np.empty(self.out_pairs(n), dtype=np.complex64) if pairs else None
+        _check(self._L.fsea_zoom_run_host(self._p, iq.ctypes.data, n, int(bool(flip)), cycles_per_sample, phase0_cycles,
+                                          sample_offset, rows.ctypes.data, out.ctypes.data if pairs else None))
+        return rows, out
+
+    def run_device(self, d_iq_ptr, n_samples, d_rows_ptr, cycles_per_sample, phase0_cycles=0.0, sample_offset=0, flip=False,
+                   d_pairs_ptr=None, stream=0):
+        """Device pointers (ints, 16-byte aligned): 2 * n_samples bytes in, out_rows(n_samples) rows and, where asked for,
+        out_pairs(n_samples) complex64 out; asynchronous."""
+        _check(self._L.fsea_zoom_run_device(self._p, d_iq_ptr, n_samples, int(bool(flip)), cycles_per_sample, phase0_cycles,
+                                            sample_offset, d_rows_ptr, d_pairs_ptr, stream or None))
 
 
 class Demod(_ResettableHandle):

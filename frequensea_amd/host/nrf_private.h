@@ -58,8 +58,8 @@ static inline void nrf_private_widen(double *f64, const float *f32, int n) {
     for (int k = 0; k < n; k++) f64[k] = (double)f32[k];
 }
 
-/* The low-pass design of nrf_iq_filter_new / nrf_iq_chain_new / nrf_fir_get_low_pass_coefficients: `length` taps the caller
- * frees.  The caller has checked the length. */
+/* The low-pass design of nrf_iq_filter_new / nrf_iq_chain_new / nrf_zoom_fft_new / nrf_fir_get_low_pass_coefficients:
+ * `length` taps the caller frees.  The caller has checked the length. */
 static inline double *nrf_private_lowpass_taps(const char *block, int sample_rate, int half_ampl_freq, int length) {
     double *taps = (double *)nrf_private_malloc(block, sizeof(double) * (size_t)length);
     const int rc = fsea_fir_lowpass_taps((double)sample_rate, (double)half_ampl_freq, length, taps);

@@ -30,6 +30,7 @@
  *                         nrf_fir_get_low_pass_coefficients and the per-sample convolution loops of
  *                         nrf_fir_filter_get / nrf_iq_filter_get_buffer, src/nrf.c:654-775
  *   fsea_chain_*          shift -> filter -> images per block with the filtered block resident on the device
+ *   fsea_zoom_*           shift -> decimating filter -> FFT: a spectrum of 1 / D of the bandwidth (nrf_decoder's chain)
  *   fsea_detect_*         the burst detector of lua/signal-detector.lua: the two loops of nrf_signal_detector_process,
  *                         src/nrf.c:883-898, as integer sums over many blocks per launch
  *   fsea_capture_*        that scene on a resident recording: detect -> gate -> filter the bursts -> line images
@@ -59,6 +60,7 @@ typedef struct fsea_history fsea_history;
 typedef struct fsea_fir fsea_fir;
 typedef struct fsea_iq_draw fsea_iq_draw;
 typedef struct fsea_chain fsea_chain;
+typedef struct fsea_zoom fsea_zoom;
 typedef struct fsea_demod fsea_demod;
 typedef struct fsea_interp fsea_interp;
 typedef struct fsea_trace fsea_trace;
@@ -461,6 +463,50 @@ int fsea_chain_run_f64_host(fsea_chain *chain, const double *iq, size_t n_sample
 int fsea_chain_fetch_host(fsea_chain *chain, const fsea_chain_outputs *outputs);
 int fsea_chain_run_device(fsea_chain *chain, const void *d_iq, size_t n_samples, int n_frames, const fsea_chain_stage *stage,
                           const fsea_chain_outputs *d_outputs, void *stream);
+
+/* The zoom spectrum: frequency shift -> low-pass -> keep every D-th sample -> FFT, the chain the reference runs inside
+ * nrf_decoder (nrf_freq_shifter, nrf_downsampler at rate_mul = D, nrf_fft) as one object.  A call hands in n_samples
+ * interleaved 8-bit IQ samples at stream position sample_offset.  With x the rotated samples of fsea_fir_u8_shifted_*
+ * above (same flip, cycles_per_sample, phase0_cycles and sample_offset; no zero half) and x_ext = tail ++ x,
+ *   pairs[i] = sum_{k < L} c[k] x_ext[i D + k],   i < n_out = n_samples / D (rounded down),
+ * and afterwards the tail is the last L - 1 values of x_ext (also when n_samples < L - 1, and when n_samples < D: no
+ * output, the tail still advances).  Kernel fsea_shift_decim_u8: the staging arithmetic of fsea_shift_fir_u8, one FMA chain
+ * per output with the taps ascending, so pairs[i] is output i D of fsea_fir_u8_shifted_device with the same taps, state and
+ * arguments, bit for bit; a stream cut into calls at multiples of D gives the one-call result bit for bit.  The decimation
+ * phase restarts with every call (the reference's nrf_downsampler_process restarts t = 0 per block): a call whose length is
+ * not a multiple of D drops its last n_samples mod D samples from the decimated sequence (they still enter the tail), and
+ * the next call's output 0 stands at its own sample 0.
+ * The object owns an ordinary plan (fft_size, hop, mode; hop counted in decimated samples) and the device buffer of the
+ * pairs.  Behind the decimating launch the plan transforms the pairs on the same stream: row r covers the decimated
+ * samples [r hop, r hop + fft_size) of THIS call, n_out >= fft_size ? (n_out - fft_size) / hop + 1 : 0 rows.  Decimated
+ * samples that do not fill a row are not carried to the next call; the filter's tail is, and the stream position is the
+ * caller's sample_offset.  The rows are those of fsea_exec_f64_host of such a plan on the pairs, bit for bit.
+ *   create:     decimation in [1, FSEA_ZOOM_MAX_DECIMATION], n_taps in [1, FSEA_FIR_MAX_TAPS] (the taps are copied, rounded to
+ *               f32); fft_size, hop and mode as fsea_plan_create, with its statuses.  FSEA_EINVAL for a NULL pointer, n_taps or
+ *               decimation out of range or a non-finite tap, checked before any device work; FSEA_ENODEVICE without a GPU.
+ *   reset:      a zero tail; synchronous.  set_window: fsea_plan_set_window of the inner plan.
+ *   run_device: d_iq (2 n_samples bytes), d_rows (out_rows x row_bytes) and d_pairs (NULL, or 2 n_out floats), 16-byte
+ *               aligned; asynchronous on `stream`.  The pairs pass through the object's buffer: a call on any stream waits for
+ *               the previous call of the object (an event), so successive calls continue one signal.
+ *   run_host:   the same from and to host memory through pinned staging on the object's own stream; returns when rows and
+ *               pairs are complete.  Calls on one object from several threads are serialised.
+ * Both check before any device work: FSEA_EINVAL for a NULL object or buffer (d_rows / rows only where the call yields a row),
+ * a misaligned device buffer, more than 2^31 samples, and the cycles_per_sample, phase0_cycles and sample_offset limits of
+ * fsea_fir_u8_shifted_*.  Destroy waits for the device. */
+#define FSEA_ZOOM_MAX_DECIMATION 64
+#define FSEA_ZOOM_TILE_OUTPUTS 128   /* outputs per workgroup of fsea_shift_decim_u8 */
+int fsea_zoom_create(fsea_zoom **zoom, const double *taps, int n_taps, int decimation, int fft_size, int hop, int mode,
+                     int device);
+int fsea_zoom_destroy(fsea_zoom *zoom);
+int fsea_zoom_reset(fsea_zoom *zoom);
+int fsea_zoom_set_window(fsea_zoom *zoom, const float *w);
+size_t fsea_zoom_out_pairs(const fsea_zoom *zoom, size_t n_samples);
+size_t fsea_zoom_out_rows(const fsea_zoom *zoom, size_t n_samples);
+size_t fsea_zoom_row_bytes(const fsea_zoom *zoom);
+int fsea_zoom_run_device(fsea_zoom *zoom, const void *d_iq, size_t n_samples, int flip, double cycles_per_sample,
+                         double phase0_cycles, uint64_t sample_offset, void *d_rows, void *d_pairs, void *stream);
+int fsea_zoom_run_host(fsea_zoom *zoom, const uint8_t *iq, size_t n_samples, int flip, double cycles_per_sample,
+                       double phase0_cycles, uint64_t sample_offset, void *rows, float *pairs);
 
 /* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
  * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With

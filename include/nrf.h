@@ -332,6 +332,46 @@ nut_buffer *nrf_iq_chain_get_iq_lines(nrf_iq_chain *chain, int size_multiplier, 
 nut_buffer *nrf_iq_chain_get_buffer(nrf_iq_chain *chain);
 void nrf_iq_chain_free(nrf_iq_chain *chain);
 
+/* ---- ADDITIONS (not in the reference): the zoom spectrum ---- */
+
+/* A spectrum of 1 / decimation of the device's bandwidth around freq_offset: what nrf_decoder chains for its audio --
+ * nrf_freq_shifter -> nrf_downsampler (rate_mul = decimation, on I and on Q) -> nrf_fft -- as one block whose samples stay on
+ * the GPU from the 8-bit upload to the rows (fsea_zoom_*, include/fsea.h).  One bin is sample_rate / (decimation * fft_size)
+ * wide: lua/fft-sea.lua's 128 points over 10 MHz are 78 kHz per bin, at decimation 16 they are 4.9 kHz.
+ *   - The low-pass is nrf_fir_get_low_pass_coefficients(sample_rate, half_ampl_freq, kernel_length) at the input rate.
+ *   - The spectrum moves up by freq_offset, the sign convention of nrf_freq_shifter_new: a signal at +f is centred by
+ *     passing -f.  The phase after M consumed samples is M * freq_offset / sample_rate cycles, M an integer kept here.
+ *   - Rows are nrf_fft's: magnitudes, the DC bin replaced, bin fft_size / 2 the centre.  A block of `length` pairs gives
+ *     length / decimation decimated pairs and (that - fft_size) / fft_size + 1 gapless rows (131072 pairs at decimation 16
+ *     and 128 points: 64 rows); decimated pairs that do not fill a row are dropped, the filter's state and the phase carry on
+ *     to the next block.  A block whose length is not a multiple of decimation restarts the decimation phase, as the
+ *     reference's downsampler does with every block.
+ *   - get_buffer is the history: fft_history_size rows of fft_size F64 values, one channel, row 0 the newest (all 0.0 at
+ *     the start); when a block yields fft_history_size rows or more its newest fft_history_size remain.
+ * process takes a U8 buffer with 2 channels.  An F64 buffer, a kernel length outside [1, FSEA_FIR_MAX_TAPS], a decimation
+ * outside [1, FSEA_ZOOM_MAX_DECIMATION], a history size below 1 and a backend failure (no GPU, an fft_size no plan serves)
+ * print "NRF zoom FFT fatal error: ..." and exit.  The buffer returned is the caller's to free. */
+typedef struct {
+    NRF_BLOCK;
+    int sample_rate;          /* Hz */
+    int freq_offset;          /* Hz */
+    int decimation;
+    int fft_size;
+    int fft_history_size;     /* rows */
+    unsigned long long consumed; /* samples rotated since the offset was set */
+    double *history;          /* fft_history_size x fft_size, row 0 the newest */
+    void *backend;            /* fsea_zoom* (libfsea_hip.so) */
+    pthread_mutex_t mutex;
+} nrf_zoom_fft;
+
+nrf_zoom_fft *nrf_zoom_fft_new(int sample_rate, int freq_offset, int decimation, int half_ampl_freq, int kernel_length,
+                               int fft_size, int fft_history_size);
+/* Another centre: the phase restarts at 0 and the filter at a zero tail; the history stays. */
+void nrf_zoom_fft_set_freq_offset(nrf_zoom_fft *zoom, int freq_offset);
+void nrf_zoom_fft_process(nrf_zoom_fft *zoom, nut_buffer *samples);
+nut_buffer *nrf_zoom_fft_get_buffer(nrf_zoom_fft *zoom);
+void nrf_zoom_fft_free(nrf_zoom_fft *zoom);
+
 /* ---- ADDITIONS (not in the reference): the signal capture ---- */
 
 /* The reference's signal scene (lua/signal-detector.lua:89-133) over a whole recording that stays on the GPU: the detector
