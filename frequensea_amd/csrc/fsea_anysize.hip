@@ -286,10 +286,9 @@ int fs_setup(fsea_plan *p) {
     size_t frames = ((size_t)64 << 20) / (n * sizeof(fsea::cf));
     if (frames < 1) frames = 1;
     p->work.frames = frames;
-    FSEA_HIP(p->fs.tw.alloc(n));
+    FSEA_HIP(p->fs.tw.upload(tw.data(), n));
     FSEA_HIP(p->work.buf[0].alloc(frames * n));
     FSEA_HIP(p->work.buf[1].alloc(frames * n));
-    FSEA_HIP(hipMemcpy(p->fs.tw.ptr, tw.data(), n * sizeof(fsea::cf), hipMemcpyHostToDevice));
     return FSEA_OK;
 }
 
@@ -333,14 +332,11 @@ int blu_setup(fsea_plan *p) {
     if (frames < 1) frames = 1;
     if (frames > 65536) frames = 65536;
     p->work.frames = frames;
-    FSEA_HIP(p->blu.chirp.alloc((size_t)n));
-    FSEA_HIP(p->blu.dc.alloc((size_t)n));
-    FSEA_HIP(p->blu.bfft.alloc((size_t)m));
+    FSEA_HIP(p->blu.chirp.upload(chirp.data(), (size_t)n));
+    FSEA_HIP(p->blu.dc.upload(dc.data(), (size_t)n));
+    FSEA_HIP(p->blu.bfft.upload(bf.data(), (size_t)m));
     FSEA_HIP(p->work.buf[0].alloc(frames * (size_t)m));
     FSEA_HIP(p->work.buf[1].alloc(frames * (size_t)m));
-    FSEA_HIP(hipMemcpy(p->blu.chirp.ptr, chirp.data(), (size_t)n * sizeof(fsea::cf), hipMemcpyHostToDevice));
-    FSEA_HIP(hipMemcpy(p->blu.dc.ptr, dc.data(), (size_t)n * sizeof(fsea::cf), hipMemcpyHostToDevice));
-    FSEA_HIP(hipMemcpy(p->blu.bfft.ptr, bf.data(), (size_t)m * sizeof(fsea::cf), hipMemcpyHostToDevice));
     return FSEA_OK;
 }
 

@@ -135,7 +135,7 @@ int HostStaging::reserve(size_t in_bytes, size_t out_bytes) {
 }
 
 hipError_t SharedScratch::create(hipStream_t first) {
-    hipError_t e = hipEventCreateWithFlags(&used, hipEventDisableTiming);
+    const hipError_t e = used.create();
     return e == hipSuccess ? hipEventRecord(used, first) : e;
 }
 

@@ -17,9 +17,6 @@ using fsea_detail::fail;
 
 struct fsea_capture {
     int device = 0;
-    fsea_detect *detect = nullptr;
-    fsea_chain *chain = nullptr;
-    fsea_iq_draw *draw = nullptr;
     mutable std::mutex mu;                  // the accessors lock it too
     fsea_detail::HostStaging staging;       // the host forms' stream and the images' way back
     fsea_detail::DeviceBuffer recording;    // scan_host's upload
@@ -31,16 +28,15 @@ struct fsea_capture {
         bool open;
     };
     std::vector<Burst> bursts;
-    float *d_pairs = nullptr;               // the bursts' pairs, one after the other
-    size_t pairs_cap = 0, pairs_used = 0;   // in pairs
+    fsea_detail::DeviceBuffer pairs;        // the bursts' pairs, one after the other
+    size_t pairs_used = 0;                  // in pairs
     size_t blocks_seen = 0;                 // of all scans since reset
+    // the inner objects are the first to go: the detector, the chain, the drawer
+    fsea_detail::Owned<fsea_iq_draw, fsea_iq_draw_destroy> draw;
+    fsea_detail::Owned<fsea_chain, fsea_chain_destroy> chain;
+    fsea_detail::Owned<fsea_detect, fsea_detect_destroy> detect;
 
-    ~fsea_capture() {
-        if (detect) (void)fsea_detect_destroy(detect);
-        if (chain) (void)fsea_chain_destroy(chain);
-        if (draw) (void)fsea_iq_draw_destroy(draw);
-        if (d_pairs) (void)hipFree(d_pairs);
-    }
+    float *d_pairs() const { return static_cast<float *>(pairs.ptr); }
 };
 
 namespace {
@@ -60,25 +56,8 @@ int check_scan(const fsea_capture *c, const void *iq, size_t block_bytes, size_t
     return FSEA_OK;
 }
 
-// room for `more` pairs behind the ones in use; the device is idle (every scan ends with a wait)
-int reserve_pairs(fsea_capture *c, size_t more) {
-    const size_t need = c->pairs_used + more;
-    if (need <= c->pairs_cap) return FSEA_OK;
-    const size_t want = need + need / 4 + 512;
-    float *grown = nullptr;
-    FSEA_HIP(hipMalloc(reinterpret_cast<void **>(&grown), want * 8));
-    if (c->pairs_used) {
-        hipError_t e = hipMemcpy(grown, c->d_pairs, c->pairs_used * 8, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(grown);
-            return fail(FSEA_EHIP, "hipMemcpy failed: %s", hipGetErrorString(e));
-        }
-    }
-    if (c->d_pairs) FSEA_HIP(hipFree(c->d_pairs));
-    c->d_pairs = grown;
-    c->pairs_cap = want;
-    return FSEA_OK;
-}
+// room for `more` pairs behind the ones in use, which move along; the device is idle (every scan ends with a wait)
+int reserve_pairs(fsea_capture *c, size_t more) { return c->pairs.grow((c->pairs_used + more) * 8, c->pairs_used * 8); }
 
 // The caller holds c->mu and is on c's device.
 int scan(fsea_capture *c, const uint8_t *d_iq, size_t block_bytes, size_t n_blocks, int flip, double threshold, hipStream_t s) {
@@ -125,7 +104,7 @@ int scan(fsea_capture *c, const uint8_t *d_iq, size_t block_bytes, size_t n_bloc
             fsea_chain_outputs out;
             std::memset(&out, 0, sizeof(out));
             out.size_multiplier = 1;
-            out.pairs = c->d_pairs + 2 * c->pairs_used;
+            out.pairs = c->d_pairs() + 2 * c->pairs_used;
             rc = fsea_chain_run_device(c->chain, d_iq + (run.first_block + f0) * block_bytes, n_samples, (int)nf, &stage, &out, s);
             if (rc) return rc;
             c->pairs_used += nf * n_samples;
@@ -157,7 +136,7 @@ int lines_launch(fsea_capture *c, size_t burst, int m, size_t n_line_points, voi
     if (n_line_points > b.n_pairs) {
         return fail(FSEA_EINVAL, "n_line_points %zu exceeds the %zu pairs of the burst", n_line_points, b.n_pairs);
     }
-    return fsea_iq_lines_device(c->draw, c->d_pairs + 2 * b.at, FSEA_IQ_F32, 0, n_line_points, 1, m, d_image, s);
+    return fsea_iq_lines_device(c->draw, c->d_pairs() + 2 * b.at, FSEA_IQ_F32, 0, n_line_points, 1, m, d_image, s);
 }
 
 }  // namespace
@@ -172,9 +151,9 @@ int fsea_capture_create(fsea_capture **out, const double *taps, int n_taps, int 
     fsea_capture *c = new (std::nothrow) fsea_capture();
     if (!c) return fail(FSEA_ENOMEM, "out of host memory");
     c->device = device;
-    int rc = fsea_chain_create(&c->chain, taps, n_taps, device);   // checks the taps, then the device
-    if (!rc) rc = fsea_detect_create(&c->detect, device);
-    if (!rc) rc = fsea_iq_draw_create(&c->draw, device);
+    int rc = fsea_chain_create(&c->chain.ptr, taps, n_taps, device);   // checks the taps, then the device
+    if (!rc) rc = fsea_detect_create(&c->detect.ptr, device);
+    if (!rc) rc = fsea_iq_draw_create(&c->draw.ptr, device);
     if (!rc) {
         DeviceGuard guard(device);
         hipError_t e = guard.err;
@@ -275,7 +254,7 @@ int fsea_capture_burst(const fsea_capture *c, size_t burst, fsea_capture_burst_i
     int rc = check_burst(c, burst);
     if (rc) return rc;
     const fsea_capture::Burst &b = c->bursts[burst];
-    *info = fsea_capture_burst_info{b.first_block, b.n_blocks, b.n_pairs, b.open ? 1 : 0, c->d_pairs + 2 * b.at};
+    *info = fsea_capture_burst_info{b.first_block, b.n_blocks, b.n_pairs, b.open ? 1 : 0, c->d_pairs() + 2 * b.at};
     return FSEA_OK;
 }
 
@@ -288,7 +267,7 @@ int fsea_capture_burst_pairs_host(fsea_capture *c, size_t burst, float *pairs) {
     const fsea_capture::Burst &b = c->bursts[burst];
     if (!b.n_pairs) return FSEA_OK;
     FSEA_ON_DEVICE(c->device);
-    FSEA_HIP(hipMemcpyAsync(pairs, c->d_pairs + 2 * b.at, b.n_pairs * 8, hipMemcpyDeviceToHost, c->staging.stream));
+    FSEA_HIP(hipMemcpyAsync(pairs, c->d_pairs() + 2 * b.at, b.n_pairs * 8, hipMemcpyDeviceToHost, c->staging.stream));
     FSEA_HIP(hipStreamSynchronize(c->staging.stream));
     return FSEA_OK;
 }

@@ -17,17 +17,13 @@ using fsea_detail::FirShift;
 
 struct fsea_chain {
     int device = 0;
-    fsea_fir *fir = nullptr;
-    fsea_iq_draw *draw = nullptr;
     fsea_detail::DeviceBuffer pairs;  // the filtered (I, Q) f32 pairs of the last run, frame after frame
     size_t n_pairs = 0;       // pairs per frame of the resident block
     std::mutex mu;
     fsea_detail::HostStaging staging;  // the host forms: input, images and their pinned twins
-
-    ~fsea_chain() {
-        if (fir) (void)fsea_fir_destroy(fir);
-        if (draw) (void)fsea_iq_draw_destroy(draw);
-    }
+    // the inner objects are the first to go: the filter, then the drawer
+    fsea_detail::Owned<fsea_iq_draw, fsea_iq_draw_destroy> draw;
+    fsea_detail::Owned<fsea_fir, fsea_fir_destroy> fir;
 };
 
 namespace {
@@ -170,8 +166,8 @@ int fsea_chain_create(fsea_chain **out, const double *taps, int n_taps, int devi
     fsea_chain *c = new (std::nothrow) fsea_chain();
     if (!c) return fail(FSEA_ENOMEM, "out of host memory");
     c->device = device;
-    int rc = fsea_fir_create(&c->fir, taps, n_taps, device);   // checks the taps, then the device
-    if (!rc) rc = fsea_iq_draw_create(&c->draw, device);
+    int rc = fsea_fir_create(&c->fir.ptr, taps, n_taps, device);   // checks the taps, then the device
+    if (!rc) rc = fsea_iq_draw_create(&c->draw.ptr, device);
     if (!rc) {
         DeviceGuard guard(device);
         hipError_t e = guard.err;

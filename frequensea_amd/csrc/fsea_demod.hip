@@ -28,6 +28,7 @@
 #include <cstring>
 #include <vector>
 
+using fsea_detail::DeviceArray;
 using fsea_detail::DeviceGuard;
 using fsea_detail::fail;
 
@@ -334,7 +335,7 @@ namespace {
 struct Table {
     size_t n = 0;                 // input samples of the call
     int n1 = 0, n2 = 0, T1 = 0, T3 = 0;
-    int *d_idx1 = nullptr, *d_idx3 = nullptr;
+    DeviceArray<int> d_idx1, d_idx3;
     unsigned long long use = 0;
 };
 
@@ -344,28 +345,29 @@ struct fsea_demod {
     int type = 0, in_rate = 0, out_rate = 0, K = 0, device = 0;
     int L1 = 0, L3 = 0;
     double r1 = 0.0, r3 = 0.0, ampl_conv = 0.0, alpha = 0.0;
-    double *d_taps1 = nullptr, *d_taps3 = nullptr;
-    double2 *d_tail1[2] = {nullptr, nullptr};   // K rows of DM_TAIL rotated samples
-    double *d_tail3[2] = {nullptr, nullptr};    // K rows of DM_TAIL discriminator outputs
-    double2 *d_l[2] = {nullptr, nullptr};       // K carried stage-1 outputs
-    double *d_v[2] = {nullptr, nullptr};        // K de-emphasis values
+    DeviceArray<double> d_taps1, d_taps3;       // DM_TAIL taps each, zeros past L
+    DeviceArray<double2> d_tail1[2];            // K rows of DM_TAIL rotated samples
+    DeviceArray<double> d_tail3[2];             // K rows of DM_TAIL discriminator outputs
+    DeviceArray<double2> d_l[2];                // K carried stage-1 outputs
+    DeviceArray<double> d_v[2];                 // K de-emphasis values
     int cur = 0;
     struct Chan {
         int offset = 0;
         double c = 1.0, s = 0.0;
     };
     std::vector<Chan> chan;
-    ChanParam *h_par[DM_RING] = {}, *d_par[DM_RING] = {};
-    hipEvent_t ev[DM_RING] = {};
-    bool ev_used[DM_RING] = {};
+    struct Slot {                               // the K channel parameters of one call, on their way to the device
+        DeviceArray<ChanParam> d_par;
+        fsea_detail::PinnedArray<ChanParam> h_par;
+        fsea_detail::Event ev;                  // recorded behind the call that read d_par
+        bool used = false;
+    } slots[DM_RING];
     int ring = 0;
     std::vector<Table> tables;
     unsigned long long use_seq = 0;
     std::mutex mu;
     fsea_detail::DeviceBuffer y1;               // stage 1's outputs of a WBFM call
     fsea_detail::HostStaging staging;           // the host-buffer forms
-
-    ~fsea_demod();
 };
 
 namespace {
@@ -401,20 +403,6 @@ void index_table(int count, double r, int L, std::vector<int> &idx, int *T) {
     *T = tt;
 }
 
-int upload_ints(const std::vector<int> &v, int **d) {
-    *d = nullptr;
-    if (v.empty()) return FSEA_OK;
-    FSEA_HIP(hipMalloc(d, v.size() * sizeof(int)));
-    FSEA_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-    return FSEA_OK;
-}
-
-void free_table(Table &t) {
-    if (t.d_idx1) (void)hipFree(t.d_idx1);
-    if (t.d_idx3) (void)hipFree(t.d_idx3);
-    t.d_idx1 = t.d_idx3 = nullptr;
-}
-
 // the cached tables for calls of n samples; the caller holds d->mu and is on d's device
 int tables_for(fsea_demod *d, size_t n, const Table **out) {
     for (Table &t : d->tables) {
@@ -437,22 +425,17 @@ int tables_for(fsea_demod *d, size_t n, const Table **out) {
         index_table(t.n2, d->r3, d->L3, idx3, &t.T3);
         if (t.n2 > 0 && idx3.back() > n1 - 1) return fail(FSEA_EINVAL, "rate %g does not fit %lld samples", d->r3, n1);
     }
-    int rc = upload_ints(idx1, &t.d_idx1);
-    if (!rc) rc = upload_ints(idx3, &t.d_idx3);
-    if (rc) {
-        free_table(t);
-        return rc;
-    }
+    FSEA_HIP(t.d_idx1.upload(idx1.data(), idx1.size()));
+    FSEA_HIP(t.d_idx3.upload(idx3.data(), idx3.size()));
     if ((int)d->tables.size() >= DM_CACHE) {
         size_t lru = 0;
         for (size_t i = 1; i < d->tables.size(); ++i)
             if (d->tables[i].use < d->tables[lru].use) lru = i;
         FSEA_HIP(hipDeviceSynchronize());   // launches on any stream may still read it
-        free_table(d->tables[lru]);
-        d->tables.erase(d->tables.begin() + (long)lru);
+        d->tables.erase(d->tables.begin() + (long)lru);   // the tables behind it move down; the evicted arrays are freed
     }
     t.use = ++d->use_seq;
-    d->tables.push_back(t);
+    d->tables.push_back(std::move(t));
     *out = &d->tables.back();
     return FSEA_OK;
 }
@@ -476,12 +459,12 @@ int demod_launch(fsea_demod *d, int kind, const void *in0, const void *in1, size
         rc = d->y1.grow(y1_bytes);
         if (rc) return rc;
     }
-    const int slot = d->ring;
-    if (d->ev_used[slot]) FSEA_HIP(hipEventSynchronize(d->ev[slot]));   // the slot's last copy has been read
+    fsea_demod::Slot &slot = d->slots[d->ring];
+    if (slot.used) FSEA_HIP(hipEventSynchronize(slot.ev));   // the slot's last copy has been read
     for (int ch = 0; ch < d->K; ++ch) {
-        d->h_par[slot][ch] = ChanParam{offset_mod(d->chan[ch].offset, d->in_rate), d->chan[ch].c, d->chan[ch].s};
+        slot.h_par.ptr[ch] = ChanParam{offset_mod(d->chan[ch].offset, d->in_rate), d->chan[ch].c, d->chan[ch].s};
     }
-    FSEA_HIP(hipMemcpyAsync(d->d_par[slot], d->h_par[slot], (size_t)d->K * sizeof(ChanParam), hipMemcpyHostToDevice, s));
+    FSEA_HIP(hipMemcpyAsync(slot.d_par.ptr, slot.h_par.ptr, (size_t)d->K * sizeof(ChanParam), hipMemcpyHostToDevice, s));
 
     const int cur = d->cur, nxt = d->cur ^ 1;
     const uint32_t fm = (kind == DM_IN_U8 && flip) ? 0x8080u : 0u;
@@ -492,22 +475,22 @@ int demod_launch(fsea_demod *d, int kind, const void *in0, const void *in1, size
     const long long ld1 = fm_chain ? (t->n1 > 0 ? t->n1 : 1) : t->n1;
     auto k1 = kind == DM_IN_U8 ? (fm_chain ? fsea_demod_stage1_u8 : fsea_demod_stage1_u8_i)
                                : (fm_chain ? fsea_demod_stage1_f64 : fsea_demod_stage1_f64_i);
-    hipLaunchKernelGGL(k1, dim3(g1, d->K), dim3(DM_WG), 0, s, in0, in1, nn, fm, d->in_rate, d->d_par[slot],
-                       d->d_tail1[cur], d->d_tail1[nxt], d->L1, d->d_taps1, t->d_idx1, t->n1, t->T1, out1, ld1);
+    hipLaunchKernelGGL(k1, dim3(g1, d->K), dim3(DM_WG), 0, s, in0, in1, nn, fm, d->in_rate, slot.d_par.ptr,
+                       d->d_tail1[cur].ptr, d->d_tail1[nxt].ptr, d->L1, d->d_taps1.ptr, t->d_idx1.ptr, t->n1, t->T1, out1, ld1);
     FSEA_HIP(hipGetLastError());
     if (fm_chain) {
         const unsigned g3 = (unsigned)(t->n2 > 0 ? (t->n2 + t->T3 - 1) / t->T3 : 1);
         hipLaunchKernelGGL(fsea_demod_fm, dim3(g3, d->K), dim3(DM_WG), 0, s, static_cast<const double2 *>(d->y1.ptr),
-                           (long long)t->n1, ld1, d->d_l[cur], d->d_l[nxt], d->d_tail3[cur], d->d_tail3[nxt], d->L3,
-                           d->d_taps3, t->d_idx3, t->n2, t->T3, d->ampl_conv, d_audio, (long long)t->n2);
+                           (long long)t->n1, ld1, d->d_l[cur].ptr, d->d_l[nxt].ptr, d->d_tail3[cur].ptr, d->d_tail3[nxt].ptr,
+                           d->L3, d->d_taps3.ptr, t->d_idx3.ptr, t->n2, t->T3, d->ampl_conv, d_audio, (long long)t->n2);
         FSEA_HIP(hipGetLastError());
         hipLaunchKernelGGL(fsea_demod_deemph, dim3(d->K), dim3(DM_WG), 0, s, d_audio, t->n2, (long long)t->n2, d->alpha,
-                           d->d_v[cur], d->d_v[nxt]);
+                           d->d_v[cur].ptr, d->d_v[nxt].ptr);
         FSEA_HIP(hipGetLastError());
     }
-    FSEA_HIP(hipEventRecord(d->ev[slot], s));
-    d->ev_used[slot] = true;
-    d->ring = (slot + 1) % DM_RING;
+    FSEA_HIP(hipEventRecord(slot.ev, s));
+    slot.used = true;
+    d->ring = (d->ring + 1) % DM_RING;
     d->cur = nxt;
 
     // the phase each channel starts its next call with: (c, s) e^{2 pi i (offset n mod in_rate) / in_rate}
@@ -560,10 +543,10 @@ int demod_host(fsea_demod *d, int kind, const void *in0, const void *in1, size_t
 
 int zero_state(fsea_demod *d) {
     for (int i = 0; i < 2; ++i) {
-        FSEA_HIP(hipMemset(d->d_tail1[i], 0, (size_t)d->K * DM_TAIL * sizeof(double2)));
-        FSEA_HIP(hipMemset(d->d_tail3[i], 0, (size_t)d->K * DM_TAIL * sizeof(double)));
-        FSEA_HIP(hipMemset(d->d_l[i], 0, (size_t)d->K * sizeof(double2)));
-        FSEA_HIP(hipMemset(d->d_v[i], 0, (size_t)d->K * sizeof(double)));
+        FSEA_HIP(d->d_tail1[i].zero((size_t)d->K * DM_TAIL));
+        FSEA_HIP(d->d_tail3[i].zero((size_t)d->K * DM_TAIL));
+        FSEA_HIP(d->d_l[i].zero((size_t)d->K));
+        FSEA_HIP(d->d_v[i].zero((size_t)d->K));
     }
     for (fsea_demod::Chan &c : d->chan) {
         c.c = 1.0;
@@ -572,27 +555,13 @@ int zero_state(fsea_demod *d) {
     return FSEA_OK;
 }
 
-hipError_t upload_taps(double **dst, double rate, double cutoff, int L) {
+hipError_t upload_taps(DeviceArray<double> &dst, double rate, double cutoff, int L) {
     double taps[DM_TAIL] = {};
     if (fsea_fir_lowpass_taps(rate, cutoff, L, taps) != FSEA_OK) return hipErrorInvalidValue;
-    hipError_t e = hipMalloc(dst, sizeof(taps));
-    if (e == hipSuccess) e = hipMemcpy(*dst, taps, sizeof(taps), hipMemcpyHostToDevice);
-    return e;
+    return dst.upload(taps, DM_TAIL);
 }
 
 }  // namespace
-
-fsea_demod::~fsea_demod() {
-    void *dev[] = {d_taps1, d_taps3, d_tail1[0], d_tail1[1], d_tail3[0], d_tail3[1], d_l[0], d_l[1], d_v[0], d_v[1]};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    for (int i = 0; i < DM_RING; ++i) {
-        if (d_par[i]) (void)hipFree(d_par[i]);
-        if (h_par[i]) (void)hipHostFree(h_par[i]);
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-    }
-    for (Table &t : tables) free_table(t);
-}
 
 extern "C" {
 
@@ -615,7 +584,7 @@ int fsea_demod_create(fsea_demod **out, int type, int in_rate, int out_rate, int
         if (type == FSEA_DEMOD_RAW) {
             d->L1 = L_RAW;
             d->r1 = in_rate / (double)out_rate;
-            e = upload_taps(&d->d_taps1, in_rate, out_rate / 2, L_RAW);
+            e = upload_taps(d->d_taps1, in_rate, out_rate / 2, L_RAW);
         } else {
             d->L1 = L_FM1;
             d->L3 = L_FM3;
@@ -623,19 +592,19 @@ int fsea_demod_create(fsea_demod **out, int type, int in_rate, int out_rate, int
             d->r3 = FM_INTER_RATE / (double)out_rate;
             d->ampl_conv = out_rate / (TAU * FM_MAX_F);
             d->alpha = 1.0 / (1.0 + out_rate * 50.0 / 1e6);
-            e = upload_taps(&d->d_taps1, in_rate, (int)(FM_MAX_F * 0.8), L_FM1);
-            if (e == hipSuccess) e = upload_taps(&d->d_taps3, FM_INTER_RATE, 10000, L_FM3);
+            e = upload_taps(d->d_taps1, in_rate, (int)(FM_MAX_F * 0.8), L_FM1);
+            if (e == hipSuccess) e = upload_taps(d->d_taps3, FM_INTER_RATE, 10000, L_FM3);
         }
         for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-            e = hipMalloc(&d->d_tail1[i], (size_t)n_channels * DM_TAIL * sizeof(double2));
-            if (e == hipSuccess) e = hipMalloc(&d->d_tail3[i], (size_t)n_channels * DM_TAIL * sizeof(double));
-            if (e == hipSuccess) e = hipMalloc(&d->d_l[i], (size_t)n_channels * sizeof(double2));
-            if (e == hipSuccess) e = hipMalloc(&d->d_v[i], (size_t)n_channels * sizeof(double));
+            e = d->d_tail1[i].alloc((size_t)n_channels * DM_TAIL);
+            if (e == hipSuccess) e = d->d_tail3[i].alloc((size_t)n_channels * DM_TAIL);
+            if (e == hipSuccess) e = d->d_l[i].alloc((size_t)n_channels);
+            if (e == hipSuccess) e = d->d_v[i].alloc((size_t)n_channels);
         }
         for (int i = 0; i < DM_RING && e == hipSuccess; ++i) {
-            e = hipMalloc(&d->d_par[i], (size_t)n_channels * sizeof(ChanParam));
-            if (e == hipSuccess) e = hipHostMalloc(&d->h_par[i], (size_t)n_channels * sizeof(ChanParam), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev[i], hipEventDisableTiming);
+            e = d->slots[i].d_par.alloc((size_t)n_channels);
+            if (e == hipSuccess) e = d->slots[i].h_par.alloc((size_t)n_channels);
+            if (e == hipSuccess) e = d->slots[i].ev.create();
         }
         const int rc = fsea_detail::init_code("fsea_demod_create", e);
         return rc ? rc : zero_state(d);
@@ -645,14 +614,7 @@ int fsea_demod_create(fsea_demod **out, int type, int in_rate, int out_rate, int
 int fsea_demod_destroy(fsea_demod *d) { return fsea_detail::destroy_object(d); }
 
 int fsea_demod_reset(fsea_demod *d) {
-    if (!d) return fail(FSEA_EINVAL, "demod is NULL");
-    std::lock_guard<std::mutex> lock(d->mu);
-    FSEA_ON_DEVICE(d->device);
-    FSEA_HIP(hipDeviceSynchronize());
-    int rc = zero_state(d);
-    if (rc) return rc;
-    FSEA_HIP(hipDeviceSynchronize());
-    return FSEA_OK;
+    return fsea_detail::reset_object(d, "demod is NULL", [&] { return zero_state(d); });
 }
 
 int fsea_demod_set_channel(fsea_demod *d, int ch, int freq_offset, double cosine, double sine) {

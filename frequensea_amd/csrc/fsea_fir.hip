@@ -173,17 +173,9 @@ extern "C" __global__ __launch_bounds__(FIR_WG) void fsea_shift_fir_u8(const voi
 struct fsea_fir {
     int n_taps = 0;
     int device = 0;
-    float *d_taps = nullptr;       // FIR_TAPS_ALLOC floats, zeros past n_taps
-    cf *d_tail[2] = {nullptr, nullptr};  // FSEA_FIR_MAX_TAPS samples each; d_tail[cur] is the current tail
-    int cur = 0;
+    FirState state;                    // FIR_TAPS_ALLOC floats of taps, the two tails
     std::mutex mu;
     fsea_detail::HostStaging staging;  // the host-buffer forms
-
-    ~fsea_fir() {
-        if (d_taps) (void)hipFree(d_taps);
-        for (cf *tail : d_tail)
-            if (tail) (void)hipFree(tail);
-    }
 };
 
 namespace {
@@ -193,22 +185,23 @@ namespace {
 int fir_launch(fsea_fir *f, int kind, const void *d_in, size_t n, int flip, void *d_out, hipStream_t s,
                const FirRot *rot = nullptr) {
     const unsigned grid = (unsigned)((n + FIR_T - 1) / FIR_T);
-    const cf *tin = f->d_tail[f->cur];
-    cf *tout = f->d_tail[f->cur ^ 1];
+    const cf *tin = f->state.in();
+    cf *tout = f->state.out();
+    const float *taps = f->state.taps.ptr;
     const long long nn = (long long)n;
     const uint32_t fm = (kind == FIR_IN_U8 && flip) ? 0x80808080u : 0u;
     if (rot) {
-        hipLaunchKernelGGL(fsea_shift_fir_u8, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, f->d_taps, f->n_taps,
+        hipLaunchKernelGGL(fsea_shift_fir_u8, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, taps, f->n_taps,
                            static_cast<cf *>(d_out), *rot);
     } else if (kind == FIR_IN_U8) {
-        hipLaunchKernelGGL(fsea_fir_u8, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, f->d_taps, f->n_taps,
+        hipLaunchKernelGGL(fsea_fir_u8, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, taps, f->n_taps,
                            static_cast<cf *>(d_out));
     } else {
-        hipLaunchKernelGGL(fsea_fir_f64, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, f->d_taps, f->n_taps,
+        hipLaunchKernelGGL(fsea_fir_f64, dim3(grid), dim3(FIR_WG), 0, s, d_in, nn, fm, tin, tout, taps, f->n_taps,
                            static_cast<cf *>(d_out));
     }
     FSEA_HIP(hipGetLastError());
-    f->cur ^= 1;
+    f->state.advance();
     return FSEA_OK;
 }
 
@@ -265,35 +258,17 @@ int fsea_fir_lowpass_taps(double sample_rate, double half_ampl_freq, int length,
 int fsea_fir_create(fsea_fir **out, const double *taps, int n_taps, int device) {
     if (!out) return fail(FSEA_EINVAL, "fir out-pointer is NULL");
     *out = nullptr;
-    if (!taps) return fail(FSEA_EINVAL, "taps is NULL");
-    if (n_taps < 1 || n_taps > FSEA_FIR_MAX_TAPS) {
-        return fail(FSEA_EINVAL, "n_taps must be in [1, %d], got %d", FSEA_FIR_MAX_TAPS, n_taps);
-    }
-    for (int k = 0; k < n_taps; ++k) {
-        if (!std::isfinite(taps[k])) return fail(FSEA_EINVAL, "tap %d is not finite", k);
-    }
+    if (int rc = FirState::check_taps(taps, n_taps)) return rc;
     return fsea_detail::create_object(out, device, "fsea_fir_create", [&](fsea_fir *f) {
         f->n_taps = n_taps;
-        float tf[FIR_TAPS_ALLOC] = {};
-        for (int k = 0; k < n_taps; ++k) tf[k] = (float)taps[k];
-        hipError_t e = hipMalloc(&f->d_taps, sizeof(tf));
-        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc(&f->d_tail[i], FSEA_FIR_MAX_TAPS * sizeof(cf));
-        if (e == hipSuccess) e = hipMemcpy(f->d_taps, tf, sizeof(tf), hipMemcpyHostToDevice);
-        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMemset(f->d_tail[i], 0, FSEA_FIR_MAX_TAPS * sizeof(cf));
-        return e;
+        return f->state.create(taps, n_taps, FIR_TAPS_ALLOC);
     });
 }
 
 int fsea_fir_destroy(fsea_fir *f) { return fsea_detail::destroy_object(f); }
 
 int fsea_fir_reset(fsea_fir *f) {
-    if (!f) return fail(FSEA_EINVAL, "fir is NULL");
-    std::lock_guard<std::mutex> lock(f->mu);
-    FSEA_ON_DEVICE(f->device);
-    FSEA_HIP(hipDeviceSynchronize());
-    FSEA_HIP(hipMemset(f->d_tail[f->cur], 0, FSEA_FIR_MAX_TAPS * sizeof(cf)));
-    FSEA_HIP(hipDeviceSynchronize());
-    return FSEA_OK;
+    return fsea_detail::reset_object(f, "fir is NULL", [&] { return f->state.reset(); });
 }
 
 int fsea_fir_n_taps(const fsea_fir *f) { return f ? f->n_taps : 0; }

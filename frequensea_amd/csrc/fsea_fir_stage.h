@@ -1,14 +1,15 @@
 // fsea_fir_stage.h -- how an input sample becomes the f32 complex value a FIR kernel stages in LDS, shared by the kernels of
 // fsea_fir.hip (fsea_fir_u8, fsea_fir_f64, fsea_shift_fir_u8) and fsea_zoom.hip (fsea_shift_decim_u8): the byte and f64
 // conversions, the frequency shift of fsea_fir_u8_shifted_* (include/fsea.h) with every rounding spelled out, the packed
-// tap FMA, and the host side of the shift (FirRot from the caller's arguments, the argument limits).  A sample's value is a
-// function of (cycles_per_sample, phase0_cycles, stream position) alone, so every kernel that stages through these
-// helpers sees the same bits.
+// tap FMA, the host side of the shift (FirRot from the caller's arguments, the argument limits), and the filter state both
+// objects carry from call to call (FirState).  A sample's value is a function of (cycles_per_sample, phase0_cycles, stream
+// position) alone, so every kernel that stages through these helpers sees the same bits.
 #pragma once
 
 #include "fsea_internal.h"
 
 #include <cmath>
+#include <vector>
 
 #include "fsea_pk_asm.h"
 
@@ -170,5 +171,39 @@ inline int check_shift(double cycles_per_sample, double phase0_cycles, uint64_t 
     }
     return FSEA_OK;
 }
+
+// What fsea_fir and fsea_zoom keep between calls: the taps as floats, padded with zeros to the length the object's kernel
+// reads, and two tails of FSEA_FIR_MAX_TAPS samples.  A launch reads in() and writes out(); advance() makes the written
+// tail the current one.
+struct FirState {
+    fsea_detail::DeviceArray<float> taps;
+    fsea_detail::DeviceArray<cf> tail[2];
+    int cur = 0;
+
+    static int check_taps(const double *taps, int n_taps) {
+        if (!taps) return fsea_detail::fail(FSEA_EINVAL, "taps is NULL");
+        if (n_taps < 1 || n_taps > FSEA_FIR_MAX_TAPS) {
+            return fsea_detail::fail(FSEA_EINVAL, "n_taps must be in [1, %d], got %d", FSEA_FIR_MAX_TAPS, n_taps);
+        }
+        for (int k = 0; k < n_taps; ++k) {
+            if (!std::isfinite(taps[k])) return fsea_detail::fail(FSEA_EINVAL, "tap %d is not finite", k);
+        }
+        return FSEA_OK;
+    }
+    hipError_t create(const double *t, int n_taps, int alloc_floats) {
+        std::vector<float> tf((size_t)alloc_floats, 0.0f);
+        for (int k = 0; k < n_taps; ++k) tf[k] = (float)t[k];
+        hipError_t e = taps.upload(tf.data(), tf.size());
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = tail[i].zeros(FSEA_FIR_MAX_TAPS);
+        return e;
+    }
+    const cf *in() const { return tail[cur].ptr; }
+    cf *out() const { return tail[cur ^ 1].ptr; }
+    void advance() { cur ^= 1; }
+    int reset() {   // the current tail only: the other one is written whole by the next launch
+        FSEA_HIP(tail[cur].zero(FSEA_FIR_MAX_TAPS));
+        return FSEA_OK;
+    }
+};
 
 }  // namespace fsea_stage

@@ -1,7 +1,19 @@
 // fsea_internal.h -- what the translation units of libfsea_hip.so share behind the C ABI (include/fsea.h): the plan
-// object, error plumbing, the launch dispatcher, owning buffers, and the scaffold of the nine device objects (FIR, IQ draw,
-// demod, interp, chain, zoom, trace, detect, capture): shared argument checks, create / destroy, the event-ordered scratch buffer, host-form
-// staging.  fsea_api.hip: the error plumbing, the scaffold's bodies and the entry points that take no plan;
+// object, error plumbing, the launch dispatcher, the owning types, and the scaffold of the nine device objects (FIR, IQ
+// draw, demod, interp, chain, zoom, trace, detect, capture).
+//
+// The owning types: a struct here releases HIP resources only by having members that release themselves.  Buffer<Mem>
+// (memory that grows on demand), DeviceArray<T> and PinnedArray<T> (exact size, allocated once), Stream and Event, and
+// Owned<T, destroy> (an inner object or plan, destroyed through its own C entry point).  No struct has a release list, so
+// a failed create frees whatever it got as far as making, and the order of the members is the order of release, reversed.
+//
+// The scaffold: shared argument checks, create_object / destroy_object / reset_object, the event-ordered scratch buffer
+// (SharedScratch), host-form staging (HostStaging).  What stays written out: fsea_chain_create and fsea_capture_create
+// (bad taps are reported before a missing device), fsea_plan_reset (it clears the counter slots too), fsea_interp_reset
+// (nothing to zero and no second wait without elements), and the two device-wide waits of fsea_demod (before an evicted
+// index table is released and before the stage-1 buffer grows).
+//
+// fsea_api.hip: the error plumbing, the scaffold's bodies and the entry points that take no plan;
 // fsea_plan.hip: the kernel registry, a plan's life cycle, the launch path and the device-buffer entry points;
 // fsea_plan_host.hip: the host-buffer entry points and the history ring; fsea_anysize.hip: the transform sizes without a
 // kernel of their own (Bluestein's algorithm, four-step decomposition).
@@ -15,6 +27,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 
 #include "fsea_registry.h"
 
@@ -80,6 +93,8 @@ __device__ __forceinline__ uint32_t coord_f64(double v) {
 // (the source and target of copies) with a quarter of headroom, mapped host memory (a kernel reads and writes it itself)
 // with a 64 KiB floor and none.  grow(need): at least `need` bytes behind `ptr`, reallocated when `cap` is short.  The old
 // memory is freed without any wait: a caller whose buffer work may still use waits for that work first.
+// grow(need, keep), device memory on an idle device: the same, and the first `keep` bytes move along -- new memory, a
+// device-to-device copy, then the old memory is freed; a failed copy frees the new memory and leaves the old in place.
 enum class Mem { Device, Pinned, Mapped };
 template <Mem K>
 struct Buffer {
@@ -94,14 +109,29 @@ struct Buffer {
         return K == Mem::Device ? hipMalloc(p, n) : hipHostMalloc(p, n, K == Mem::Mapped ? hipHostMallocMapped : hipHostMallocDefault);
     }
     static hipError_t release(void *p) { return K == Mem::Device ? hipFree(p) : hipHostFree(p); }
+    static size_t headroom(size_t need) { return K == Mem::Mapped ? (need < 65536 ? 65536 : need) : need + need / 4 + 4096; }
     int grow(size_t need) {
         if (cap >= need) return FSEA_OK;
         if (ptr) FSEA_HIP(release(ptr));
         ptr = nullptr;
         cap = 0;
-        const size_t want = K == Mem::Mapped ? (need < 65536 ? 65536 : need) : need + need / 4 + 4096;
-        FSEA_HIP(alloc(&ptr, want));
-        cap = want;
+        FSEA_HIP(alloc(&ptr, headroom(need)));
+        cap = headroom(need);
+        return FSEA_OK;
+    }
+    int grow(size_t need, size_t keep) {
+        static_assert(K == Mem::Device, "the copy is device to device");
+        if (cap >= need) return FSEA_OK;
+        void *grown = nullptr, *old = ptr;
+        FSEA_HIP(alloc(&grown, headroom(need)));
+        const hipError_t e = keep ? hipMemcpy(grown, old, keep, hipMemcpyDeviceToDevice) : hipSuccess;
+        if (e != hipSuccess) {
+            (void)release(grown);
+            return fail(FSEA_EHIP, "hipMemcpy failed: %s", hipGetErrorString(e));
+        }
+        ptr = grown;
+        cap = headroom(need);
+        if (old) FSEA_HIP(release(old));
         return FSEA_OK;
     }
 };
@@ -109,16 +139,74 @@ using DeviceBuffer = Buffer<Mem::Device>;
 using PinnedBuffer = Buffer<Mem::Pinned>;
 using MappedBuffer = Buffer<Mem::Mapped>;
 
-// `count` elements of device memory, allocated once at exactly that size and freed with their owner
-template <class T>
-struct DeviceArray {
+// `count` elements of device or default pinned memory, allocated once at exactly that size and freed with their owner;
+// it moves, so a struct that holds one can live in a std::vector.  upload: allocate and copy from the host (nothing to
+// allocate for a count of zero); zeros: allocate and zero; zero: zero again.  Those three are the device kind's.
+template <class T, Mem K>
+struct Array {
     T *ptr = nullptr;
 
-    DeviceArray() = default;
-    DeviceArray(const DeviceArray &) = delete;
-    DeviceArray &operator=(const DeviceArray &) = delete;
-    ~DeviceArray() { if (ptr) (void)hipFree(ptr); }
-    hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void **>(&ptr), count * sizeof(T)); }
+    Array() = default;
+    Array(Array &&o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
+    Array &operator=(Array &&o) noexcept {   // the old memory goes with `o`
+        std::swap(ptr, o.ptr);
+        return *this;
+    }
+    ~Array() { if (ptr) (void)Buffer<K>::release(ptr); }
+    hipError_t alloc(size_t count) { return Buffer<K>::alloc(reinterpret_cast<void **>(&ptr), count * sizeof(T)); }
+    hipError_t zero(size_t count) { return hipMemset(ptr, 0, count * sizeof(T)); }
+    hipError_t zeros(size_t count) {
+        const hipError_t e = alloc(count);
+        return e == hipSuccess ? zero(count) : e;
+    }
+    template <class U>   // T itself, or the host's name for the same bytes (fsea::TwPair for fsea::cf)
+    hipError_t upload(const U *host, size_t count) {
+        static_assert(sizeof(U) == sizeof(T), "one host element per device element");
+        if (!count) return hipSuccess;
+        const hipError_t e = alloc(count);
+        return e == hipSuccess ? hipMemcpy(ptr, host, count * sizeof(T), hipMemcpyHostToDevice) : e;
+    }
+};
+template <class T>
+using DeviceArray = Array<T, Mem::Device>;
+template <class T>
+using PinnedArray = Array<T, Mem::Pinned>;
+
+// A non-blocking stream and an event, destroyed with their owner.  An event takes its flag when it is created: no timing
+// unless hipEventDefault is asked for.  Both stand where the raw handle would.
+struct Stream {
+    hipStream_t s = nullptr;
+
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDisableTiming) { return hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+
+// An inner object or plan, destroyed through its own C entry point (which brings the device, or the plan's stream, to rest
+// first).  Declared after the memory and streams the inner object may use, so that it goes before them.
+template <class T, int (*Destroy)(T *)>
+struct Owned {
+    T *ptr = nullptr;
+
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() { if (ptr) (void)Destroy(ptr); }
+    T *operator->() const { return ptr; }
+    operator T *() const { return ptr; }
 };
 
 // FSEA_OK, FSEA_ENODEVICE when HIP has no device at all, FSEA_EINVAL when `device` is not one of them
@@ -133,12 +221,11 @@ int check_aligned16(const char *names, const void *a, const void *b = nullptr, c
 // The host-buffer forms of a device object: its own non-blocking stream and pinned + device staging, grown on demand.
 // Only those forms use the staging, on that stream, under the object's mutex.
 struct HostStaging {
-    hipStream_t stream = nullptr;
     PinnedBuffer h_in, h_out;
     DeviceBuffer d_in, d_out;
+    Stream stream;
 
-    hipError_t create() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
-    ~HostStaging() { if (stream) (void)hipStreamDestroy(stream); }
+    hipError_t create() { return stream.create(); }
     int reserve(size_t in_bytes, size_t out_bytes);
 
     // One host-form call: fill(h_in) writes the in_bytes of input into pinned memory, copy in, launch(d_in, d_out, stream)
@@ -167,10 +254,9 @@ struct HostStaging {
 // mutex and is on its device.
 struct SharedScratch {
     DeviceBuffer buf;
-    hipEvent_t used = nullptr;  // recorded after the last work that used the buffer
+    Event used;  // recorded after the last work that used the buffer
 
     hipError_t create(hipStream_t first);  // the event starts recorded on `first`, so it can be waited for at once
-    ~SharedScratch() { if (used) (void)hipEventDestroy(used); }
     int reserve(size_t need);
     int acquire(hipStream_t s);
     int release(hipStream_t s);
@@ -181,7 +267,7 @@ int init_code(const char *what, hipError_t e);
 inline int init_code(const char *, int rc) { return rc; }
 
 // What every fsea_X_create does once its own arguments are checked: device check, `new`, the staging stream, then
-// init(obj) -> hipError_t or an FSEA_* code, on the object's device.  T has `device`, `staging` and a destructor that frees
+// init(obj) -> hipError_t or an FSEA_* code, on the object's device.  T has `device` and `staging`; its members free
 // whatever init got as far as allocating.  `what` is the entry point's name, for the failure text.
 template <class T, class Init>
 int create_object(T **out, int device, const char *what, Init &&init) {
@@ -212,6 +298,20 @@ int destroy_object(T *obj) {
     return FSEA_OK;
 }
 
+// fsea_X_reset: `null_message` for a NULL object; under the object's mutex and on its device, body() -> FSEA_* code zeroes
+// the state between two waits for the device (launches on any stream may use the state; the zeroes are in place before
+// the next one)
+template <class T, class Body>
+int reset_object(T *obj, const char *null_message, Body &&body) {
+    if (!obj) return fail(FSEA_EINVAL, "%s", null_message);
+    std::lock_guard<std::mutex> lock(obj->mu);
+    FSEA_ON_DEVICE(obj->device);
+    FSEA_HIP(hipDeviceSynchronize());
+    if (int rc = body()) return rc;
+    FSEA_HIP(hipDeviceSynchronize());
+    return FSEA_OK;
+}
+
 // The frequency shift of fsea_fir_u8_shifted_* (include/fsea.h).
 struct FirShift {
     double cycles_per_sample, phase0_cycles;
@@ -227,21 +327,19 @@ int fir_launch_device(fsea_fir *f, int f64, const void *d_in, size_t n_in, size_
 
 }  // namespace fsea_detail
 
-// A plan is made of parts that own what they hold: each frees its memory, events and streams in its destructor, so
-// fsea_plan_destroy is a `delete` and a failed fsea_plan_create frees whatever it got as far as allocating.
+// A plan is made of parts that own what they hold (the owning types above), so fsea_plan_destroy is a `delete` and a failed
+// fsea_plan_create frees whatever it got as far as allocating.
 struct fsea_plan {
     int n = 0;
     int hop = 0;
     int mode = 0;
     int device = 0;
     const fsea::KernelEntry *entry = nullptr;
-    hipStream_t stream = nullptr;
     fsea_detail::DeviceArray<fsea::cf> d_tw;  // passes 1..np-1 concatenated
     size_t tw_off[5] = {0, 0, 0, 0, 0};  // passes 0..3, then the HI/LO factor tables (fsea_tables.h)
     size_t tw_def_off = 0;               // deferred middle-pass table (fo::DEFER / fo::V2), 16-byte aligned
     int num_cu = 0;
     fsea_detail::DeviceArray<unsigned long long> d_trace;  // FSEA_TRACE diagnostics (tuning library)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the launches fsea_time_exec_* time (tuning library; created by every build)
     int occ[fsea::K_COUNT] = {};
     // FSEA_UNITS_AUTO: launches with at most FSEA_STATIC_UNITS_PER_WG units per workgroup use the static interleave,
     // longer ones the ticket pools; fsea_plan_set_unit_distribution pins one of the two
@@ -257,7 +355,7 @@ struct fsea_plan {
         std::mutex slot_mu;
         struct Slot {
             hipStream_t stream = nullptr;   // the stream the slot serves (meaningful while `used` and not `anonymous`)
-            hipEvent_t ev = nullptr;        // recorded behind the slot's last launch (not while the stream is being captured)
+            fsea_detail::Event ev;          // recorded behind the slot's last launch (not while the stream is being captured); created on first use
             bool used = false, pending = false, anonymous = false, captured = false;
             bool launching = false;         // claimed by a host thread between counter_slot() and the record of `ev`: not to be recycled
             unsigned long long seq = 0;     // launch order, for least-recently-used recycling
@@ -265,7 +363,6 @@ struct fsea_plan {
         unsigned long long slot_seq = 0;
 
         hipError_t create();  // the counters, zeroed on the null stream: the caller waits for the device before a launch
-        ~Counters() { for (auto &c : slots) if (c.ev) (void)hipEventDestroy(c.ev); }
     } ctr;
 
     // The host-buffer entry points (fsea_plan_host.hip), one call at a time under `mu`.
@@ -280,11 +377,10 @@ struct fsea_plan {
         fsea_detail::MappedBuffer h_in, h_out;
         // the pipelined host-buffer path (exec_host_pipelined): copy-in and copy-out streams beside the plan's stream, and
         // one "chunk arrived" / "chunk transformed" event pair per chunk in flight
-        hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-        hipEvent_t ev_in[FSEA_HOST_CHUNKS_MAX] = {}, ev_done[FSEA_HOST_CHUNKS_MAX] = {};
+        fsea_detail::Stream s_h2d, s_d2h;
+        fsea_detail::Event ev_in[FSEA_HOST_CHUNKS_MAX], ev_done[FSEA_HOST_CHUNKS_MAX];
 
         hipError_t create();  // the two streams and the events
-        ~HostPath();
 
         // One small batch through the mapped staging: fill(h_in) writes the in_bytes of input, launch(d_in, d_out) queues the
         // transform on `stream` with the staging's device addresses, wait, out_bytes to `out`.  `out` null: the launch writes
@@ -310,19 +406,17 @@ struct fsea_plan {
     // kernel set of size blu.m the convolution runs on
     struct Bluestein {
         int m = 0;
-        fsea_plan *inner = nullptr;                 // size m, COMPLEX_F32
         fsea_detail::DeviceArray<fsea::cf> chirp;   // conj(w[j]), j < n
         fsea_detail::DeviceArray<fsea::cf> bfft;    // FFT_m of the wrapped chirp
         fsea_detail::DeviceArray<fsea::cf> dc;      // spectrum of the offset-binary DC term, n entries
-        ~Bluestein() { if (inner) (void)fsea_plan_destroy(inner); }
+        fsea_detail::Owned<fsea_plan, fsea_plan_destroy> inner;   // size m, COMPLEX_F32; the first to go
     } blu;
 
     // four-step plans (powers of two above 16384): n = fs.n1 * fs.n2, two inner plans, the twiddles W_n^{j2 k1}
     struct FourStep {
         int n1 = 0, n2 = 0;
-        fsea_plan *inner1 = nullptr, *inner2 = nullptr;
         fsea_detail::DeviceArray<fsea::cf> tw;
-        ~FourStep() { if (inner1) (void)fsea_plan_destroy(inner1); if (inner2) (void)fsea_plan_destroy(inner2); }
+        fsea_detail::Owned<fsea_plan, fsea_plan_destroy> inner2, inner1;   // inner1 goes first, then inner2, then tw
     } fs;
 
     // What a Bluestein and a four-step plan share: two work buffers of `frames` frames each.  They are the plan's, not the
@@ -332,9 +426,8 @@ struct fsea_plan {
         fsea_detail::DeviceArray<fsea::cf> buf[2];
         size_t frames = 0;
         std::mutex mu;
-        hipEvent_t ev = nullptr;
+        fsea_detail::Event ev;   // created by the first launch
         bool pending = false;
-        ~Work() { if (ev) (void)hipEventDestroy(ev); }
     } work;
 
     // taper window (fsea_plan_set_window): weights in the pass-0 lane order with (-1)^n folded in, and the DC term's
@@ -350,7 +443,10 @@ struct fsea_plan {
     std::string kernel_name;        // while no window is set
     std::string kernel_name_win;    // while one is (filled by the first fsea_plan_set_window)
 
-    ~fsea_plan();
+    // the last members, so the first to be released: the plan's own stream (fsea_plan_destroy has waited for it), and the
+    // events around the launches fsea_time_exec_* time (tuning library; created by every build)
+    fsea_detail::Stream stream;
+    fsea_detail::Event ev0, ev1;
 };
 
 

@@ -254,16 +254,11 @@ struct fsea_interp {
     int type = FSEA_IQ_U8;
     size_t n = 0;                      // elements per block
     std::mutex mu;
-    void *d_a = nullptr, *d_b = nullptr;  // the blocks; a push copies into d_a's memory and swaps the two
+    fsea_detail::DeviceArray<uint8_t> d_a, d_b;  // the blocks; a push copies into d_a's memory and swaps the two
     // the image form's tables on the device, for the geometry of the last call
     fsea_detail::SharedScratch tab;
     int tab_w = 0, tab_h = 0, tab_iq = 0, tile_rows = 0, max_slots = 0;
     fsea_detail::HostStaging staging;  // the host-buffer forms
-
-    ~fsea_interp() {
-        if (d_a) (void)hipFree(d_a);
-        if (d_b) (void)hipFree(d_b);
-    }
 };
 
 namespace {
@@ -335,9 +330,9 @@ int frames_launch(fsea_interp *p, const double *d_w, int n_frames, void *d_out, 
         const dim3 grid(gx, (unsigned)period * runs);
         uint8_t *out = static_cast<uint8_t *>(d_out) + (size_t)f0 * nb;
         if (p->type == FSEA_IQ_U8) {
-            hipLaunchKernelGGL(fsea_interp_frames_u8, grid, dim3(IT_WG), 0, s, p->d_a, p->d_b, n, d_w + f0, nf, period, out);
+            hipLaunchKernelGGL(fsea_interp_frames_u8, grid, dim3(IT_WG), 0, s, p->d_a.ptr, p->d_b.ptr, n, d_w + f0, nf, period, out);
         } else {
-            hipLaunchKernelGGL(fsea_interp_frames_f64, grid, dim3(IT_WG), 0, s, p->d_a, p->d_b, n, d_w + f0, nf, period, out);
+            hipLaunchKernelGGL(fsea_interp_frames_f64, grid, dim3(IT_WG), 0, s, p->d_a.ptr, p->d_b.ptr, n, d_w + f0, nf, period, out);
         }
         FSEA_HIP(hipGetLastError());
     }
@@ -396,8 +391,8 @@ int image_launch(fsea_interp *p, const double *d_w, int n_frames, const fsea_int
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         const int nf = std::min(chunk, n_frames - f0);
         const dim3 grid(gx, (unsigned)((nf + IM_RUN - 1) / IM_RUN));
-        hipLaunchKernelGGL(fsea_interp_image_u8, grid, dim3(IT_WG), lds, s, static_cast<const uint8_t *>(p->d_a),
-                           static_cast<const uint8_t *>(p->d_b), g->flip ? 0x80u : 0u, d_w + f0, nf, g->width, g->height,
+        hipLaunchKernelGGL(fsea_interp_image_u8, grid, dim3(IT_WG), lds, s, static_cast<const uint8_t *>(p->d_a.ptr),
+                           static_cast<const uint8_t *>(p->d_b.ptr), g->flip ? 0x80u : 0u, d_w + f0, nf, g->width, g->height,
                            g->iq_size, p->tile_rows, p->max_slots, static_cast<const uint16_t *>(p->tab.buf.ptr),
                            static_cast<uint8_t *>(d_images) + (size_t)f0 * frame_bytes);
         FSEA_HIP(hipGetLastError());
@@ -408,8 +403,8 @@ int image_launch(fsea_interp *p, const double *d_w, int n_frames, const fsea_int
 // B's old memory becomes A, the new block lands in A's old memory and becomes B
 int push_launch(fsea_interp *p, const void *d_block, hipStream_t s) {
     const size_t nb = p->n * elem_bytes(p->type);
-    if (nb) FSEA_HIP(hipMemcpyAsync(p->d_a, d_block, nb, hipMemcpyDeviceToDevice, s));
-    std::swap(p->d_a, p->d_b);
+    if (nb) FSEA_HIP(hipMemcpyAsync(p->d_a.ptr, d_block, nb, hipMemcpyDeviceToDevice, s));
+    std::swap(p->d_a.ptr, p->d_b.ptr);
     return FSEA_OK;
 }
 
@@ -437,10 +432,8 @@ int fsea_interp_create(fsea_interp **out, int type, size_t n_elements, int devic
         p->n = n_elements;
         const size_t nb = std::max<size_t>(16, n_elements * elem_bytes(type));
         hipError_t e = p->tab.create(p->staging.stream);
-        if (e == hipSuccess) e = hipMalloc(&p->d_a, nb);
-        if (e == hipSuccess) e = hipMalloc(&p->d_b, nb);
-        if (e == hipSuccess) e = hipMemset(p->d_a, 0, nb);
-        if (e == hipSuccess) e = hipMemset(p->d_b, 0, nb);
+        if (e == hipSuccess) e = p->d_a.zeros(nb);
+        if (e == hipSuccess) e = p->d_b.zeros(nb);
         if (e == hipSuccess) e = hipDeviceSynchronize();
         return e;
     });
@@ -448,6 +441,7 @@ int fsea_interp_create(fsea_interp **out, int type, size_t n_elements, int devic
 
 int fsea_interp_destroy(fsea_interp *p) { return fsea_detail::destroy_object(p); }
 
+// Not through fsea_detail::reset_object: without elements there is nothing to zero and no second wait.
 int fsea_interp_reset(fsea_interp *p) {
     if (!p) return fail(FSEA_EINVAL, "interp is NULL");
     std::lock_guard<std::mutex> lock(p->mu);
@@ -455,8 +449,8 @@ int fsea_interp_reset(fsea_interp *p) {
     FSEA_HIP(hipDeviceSynchronize());
     const size_t nb = p->n * elem_bytes(p->type);
     if (nb) {
-        FSEA_HIP(hipMemset(p->d_a, 0, nb));
-        FSEA_HIP(hipMemset(p->d_b, 0, nb));
+        FSEA_HIP(p->d_a.zero(nb));
+        FSEA_HIP(p->d_b.zero(nb));
         FSEA_HIP(hipDeviceSynchronize());
     }
     return FSEA_OK;

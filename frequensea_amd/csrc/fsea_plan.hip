@@ -43,34 +43,16 @@ extern "C" int fsea_kernels_tune_win(fsea::KernelEntry *out, int cap);
 #endif
 
 // ---- what the parts of a plan own (fsea_internal.h) ----
-hipError_t fsea_plan::Counters::create() {
-    hipError_t e = d_ctr.alloc(FSEA_CTR_SLOTS * FSEA_CTR_WORDS);
-    return e == hipSuccess ? hipMemset(d_ctr.ptr, 0, FSEA_CTR_SLOTS * FSEA_CTR_WORDS * sizeof(unsigned)) : e;
-}
+hipError_t fsea_plan::Counters::create() { return d_ctr.zeros(FSEA_CTR_SLOTS * FSEA_CTR_WORDS); }
 
 hipError_t fsea_plan::HostPath::create() {
-    hipError_t he = hipStreamCreateWithFlags(&s_h2d, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipStreamCreateWithFlags(&s_d2h, hipStreamNonBlocking);
+    hipError_t he = s_h2d.create();
+    if (he == hipSuccess) he = s_d2h.create();
     for (unsigned c = 0; c < FSEA_HOST_CHUNKS_MAX && he == hipSuccess; ++c) {
-        he = hipEventCreateWithFlags(&ev_in[c], hipEventDisableTiming);
-        if (he == hipSuccess) he = hipEventCreateWithFlags(&ev_done[c], hipEventDisableTiming);
+        he = ev_in[c].create();
+        if (he == hipSuccess) he = ev_done[c].create();
     }
     return he;
-}
-
-fsea_plan::HostPath::~HostPath() {
-    for (unsigned c = 0; c < FSEA_HOST_CHUNKS_MAX; ++c) {
-        if (ev_in[c]) (void)hipEventDestroy(ev_in[c]);
-        if (ev_done[c]) (void)hipEventDestroy(ev_done[c]);
-    }
-    if (s_h2d) (void)hipStreamDestroy(s_h2d);
-    if (s_d2h) (void)hipStreamDestroy(s_d2h);
-}
-
-fsea_plan::~fsea_plan() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (stream) (void)hipStreamDestroy(stream);
 }
 
 #ifdef FSEA_TUNE
@@ -273,7 +255,7 @@ unsigned *counter_slot(fsea_plan *p, hipStream_t s, int *index, bool *record) {
     // capturing stream itself keeps using it for ordinary launches, in stream order with a replay on that stream.
     if (capturing) c.captured = true;
     if (!capturing && !c.ev) {
-        if (hipEventCreateWithFlags(&c.ev, hipEventDisableTiming) != hipSuccess) return nullptr;
+        if (c.ev.create() != hipSuccess) return nullptr;
     }
     c.seq = ++p->ctr.slot_seq;
     c.launching = true;  // until launch_pow2 has enqueued the kernel and recorded the slot's event
@@ -443,17 +425,15 @@ int create_plan(fsea_plan **out, int fft_size, int hop, int mode, int device, co
         p->tw_def_off = tw.size();
         tw.insert(tw.end(), def.begin(), def.end());
     }
-    static_assert(sizeof(fsea::TwPair) == sizeof(fsea::cf), "twiddle layout");
-    hipError_t he = p->d_tw.alloc(tw.size());
-    if (he == hipSuccess) he = hipMemcpy(p->d_tw.ptr, tw.data(), tw.size() * sizeof(fsea::cf), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+    hipError_t he = p->d_tw.upload(tw.data(), tw.size());
+    if (he == hipSuccess) he = p->stream.create();
     if (he == hipSuccess) he = p->host.d_acc.alloc(1);
     if (he == hipSuccess) he = p->ctr.create();
     // the counters' memset runs on the null stream; the caller's (possibly non-blocking) streams are not ordered
     // behind it, so it is complete before the plan is handed out
     if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he == hipSuccess) he = hipEventCreate(&p->ev0);
-    if (he == hipSuccess) he = hipEventCreate(&p->ev1);
+    if (he == hipSuccess) he = p->ev0.create(hipEventDefault);
+    if (he == hipSuccess) he = p->ev1.create(hipEventDefault);
     if (he == hipSuccess) he = p->host.create();
     for (int k = 0; k < fsea::K_COUNT && he == hipSuccess; ++k) {
         if (e->fn[k]) he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&p->occ[k], e->fn[k], e->wg, 0);
@@ -464,7 +444,7 @@ int create_plan(fsea_plan **out, int fft_size, int hop, int mode, int device, co
         return rc;
     }
     if (blu_m) {
-        rc = create_plan(&p->blu.inner, blu_m, blu_m, FSEA_MODE_COMPLEX_F32, device, "");
+        rc = create_plan(&p->blu.inner.ptr, blu_m, blu_m, FSEA_MODE_COMPLEX_F32, device, "");
         if (rc == FSEA_OK) rc = blu_setup(p);
         if (rc != FSEA_OK) {
             delete p;
@@ -474,8 +454,8 @@ int create_plan(fsea_plan **out, int fft_size, int hop, int mode, int device, co
                          (p->blu.inner->fs.n1 ? p->blu.inner->kernel_name : std::string(p->blu.inner->entry->name[fsea::K_F32])) + " x2)";
     }
     if (fs_n1) {
-        rc = create_plan(&p->fs.inner1, fs_n1, fs_n1, FSEA_MODE_COMPLEX_F32, device, "");
-        if (rc == FSEA_OK) rc = create_plan(&p->fs.inner2, fs_n2, fs_n2, FSEA_MODE_COMPLEX_F32, device, "");
+        rc = create_plan(&p->fs.inner1.ptr, fs_n1, fs_n1, FSEA_MODE_COMPLEX_F32, device, "");
+        if (rc == FSEA_OK) rc = create_plan(&p->fs.inner2.ptr, fs_n2, fs_n2, FSEA_MODE_COMPLEX_F32, device, "");
         if (rc == FSEA_OK) rc = fs_setup(p);
         if (rc != FSEA_OK) {
             delete p;
@@ -551,7 +531,7 @@ int launch(fsea_plan *p, int in_kind, const void *d_in, size_t n_frames, int fli
             (void)hipGetLastError();
         }
         std::lock_guard<std::mutex> lock(p->work.mu);
-        if (!p->work.ev) FSEA_HIP(hipEventCreateWithFlags(&p->work.ev, hipEventDisableTiming));
+        if (!p->work.ev) FSEA_HIP(p->work.ev.create());
         if (p->work.pending) FSEA_HIP(hipStreamWaitEvent(s, p->work.ev, 0));
         const int rc = p->blu.m ? blu_launch(p, in_kind, d_in, n_frames, flip, mode, d_out, s)
                                 : fs_launch(p, in_kind, d_in, n_frames, flip, mode, d_out, s);
@@ -578,7 +558,7 @@ int fsea_plan_reset(fsea_plan *p) {
     if (!p) return fail(FSEA_EINVAL, "plan is NULL");
     FSEA_ON_DEVICE(p->device);
     FSEA_HIP(hipDeviceSynchronize());
-    FSEA_HIP(hipMemset(p->ctr.d_ctr.ptr, 0, FSEA_CTR_SLOTS * FSEA_CTR_WORDS * sizeof(unsigned)));
+    FSEA_HIP(p->ctr.d_ctr.zero(FSEA_CTR_SLOTS * FSEA_CTR_WORDS));
     FSEA_HIP(hipDeviceSynchronize());
     {
         std::lock_guard<std::mutex> lock(p->ctr.slot_mu);
@@ -797,19 +777,16 @@ int fsea_tune_stream_1to2(void *const *d_in, void *const *d_out, int n_sets, siz
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipDeviceProp_t prop;
     FSEA_HIP(hipGetDeviceProperties(&prop, device));
-    hipEvent_t e0, e1;
-    FSEA_HIP(hipEventCreate(&e0));
-    FSEA_HIP(hipEventCreate(&e1));
+    Event e0, e1;
+    FSEA_HIP(e0.create(hipEventDefault));
+    FSEA_HIP(e1.create(hipEventDefault));
     const char *wg_env = std::getenv("FSEA_TUNE_COPY_WG");  // workgroups per CU (default 32: two 16-byte pieces per thread; measured 0.58-0.67 of 8 TB/s at 2-16, 0.73 at 32)
     const unsigned grid = (unsigned)prop.multiProcessorCount * (unsigned)(wg_env ? std::atoi(wg_env) : 32);
-    const int rc = time_reps(e0, e1, s, reps, avg_ms, [&](int i) {
+    return time_reps(e0, e1, s, reps, avg_ms, [&](int i) {
         hipLaunchKernelGGL(fsea_tune_stream_1to2_kernel, dim3(grid), dim3(256), 0, s, static_cast<const tune_u32x4 *>(d_in[i % n_sets]),
                            static_cast<tune_u32x4 *>(d_out[i % n_sets]), in_bytes / 16);
         return (int)FSEA_OK;
     });
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
 }
 
 int fsea_plan_create_variant(fsea_plan **out, int fft_size, int hop, int mode, int device, const char *variant) {

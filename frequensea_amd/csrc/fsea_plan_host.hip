@@ -24,9 +24,7 @@ struct fsea_history {
     int head = 0;             // ring row holding the newest spectrum
     int cur = 0;              // which of the two storages is live (nrf_fft_shift works out of place)
     DeviceArray<float> d_ring[2];
-    float *h_stage = nullptr; // pinned, rows * n floats: target of the D2H in fsea_history_get_f64
-
-    ~fsea_history() { if (h_stage) (void)hipHostFree(h_stage); }
+    PinnedArray<float> h_stage;   // rows * n floats: target of the D2H in fsea_history_get_f64
 };
 
 namespace {
@@ -265,11 +263,10 @@ int fsea_history_create(fsea_plan *p, int rows, fsea_history **out) {
     h->plan = p;
     h->device = p->device;
     h->rows = rows;
-    const size_t count = (size_t)rows * (size_t)p->n, bytes = count * sizeof(float);
-    hipError_t he = h->d_ring[0].alloc(count);
+    const size_t count = (size_t)rows * (size_t)p->n;
+    hipError_t he = h->d_ring[0].zeros(count);
     if (he == hipSuccess) he = h->d_ring[1].alloc(count);
-    if (he == hipSuccess) he = hipMemset(h->d_ring[0].ptr, 0, bytes);
-    if (he == hipSuccess) he = hipHostMalloc(reinterpret_cast<void **>(&h->h_stage), bytes, hipHostMallocDefault);
+    if (he == hipSuccess) he = h->h_stage.alloc(count);
     if (he == hipSuccess) he = hipDeviceSynchronize();
     if (he != hipSuccess) {
         int rc = fail(FSEA_EHIP, "history setup failed: %s", hipGetErrorString(he));
@@ -327,15 +324,15 @@ int fsea_history_get_f64(fsea_history *h, double *out) {
     const size_t first = (size_t)(h->rows - h->head);  // rows from the head to the end of storage
     const float *ring = h->d_ring[h->cur].ptr;
     // one device-to-host transfer of rows * n f32, already in newest-first order, then one widening
-    FSEA_HIP(hipMemcpyAsync(h->h_stage, ring + (size_t)h->head * n, first * n * sizeof(float), hipMemcpyDeviceToHost,
+    FSEA_HIP(hipMemcpyAsync(h->h_stage.ptr, ring + (size_t)h->head * n, first * n * sizeof(float), hipMemcpyDeviceToHost,
                             p->stream));
     if (h->head > 0) {
-        FSEA_HIP(hipMemcpyAsync(h->h_stage + first * n, ring, (size_t)h->head * n * sizeof(float), hipMemcpyDeviceToHost,
+        FSEA_HIP(hipMemcpyAsync(h->h_stage.ptr + first * n, ring, (size_t)h->head * n * sizeof(float), hipMemcpyDeviceToHost,
                                 p->stream));
     }
     FSEA_HIP(hipStreamSynchronize(p->stream));
     const size_t total = (size_t)h->rows * n;
-    const float *src = h->h_stage;
+    const float *src = h->h_stage.ptr;
     for (size_t i = 0; i < total; ++i) out[i] = (double)src[i];
     return FSEA_OK;
 }

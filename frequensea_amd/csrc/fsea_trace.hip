@@ -232,14 +232,10 @@ struct fsea_trace {
     int device = 0;
     TraceGeo g = {};
     std::mutex mu;
-    uint8_t *d_canvas = nullptr;       // width x height bytes, padded to a whole 16-byte group
+    fsea_detail::DeviceArray<uint8_t> canvas;  // width x height bytes, padded to a whole 16-byte group
     size_t canvas_bytes = 0;
     fsea_detail::SharedScratch counts;  // the count planes of one chunk; its event orders the uses of the canvas too
     fsea_detail::HostStaging staging;   // the host-buffer forms
-
-    ~fsea_trace() {
-        if (d_canvas) (void)hipFree(d_canvas);
-    }
 };
 
 namespace {
@@ -295,10 +291,10 @@ int frames_launch(fsea_trace *t, const uint8_t *d_bytes, size_t n_bytes, int fli
         uint8_t *images = d_images ? d_images + f0 * pixels : nullptr;
         const uint8_t *counts = d_counts;
         const dim3 grid(gx_compose);
-        if (aligned && cb == 1) hipLaunchKernelGGL(fsea_trace_compose_b8, grid, dim3(TR_WG), 0, s, counts, nf, g, t->d_canvas, images);
-        else if (aligned) hipLaunchKernelGGL(fsea_trace_compose_b32, grid, dim3(TR_WG), 0, s, counts, nf, g, t->d_canvas, images);
-        else if (cb == 1) hipLaunchKernelGGL(fsea_trace_compose_b8_any, grid, dim3(TR_WG), 0, s, counts, nf, g, t->d_canvas, images);
-        else hipLaunchKernelGGL(fsea_trace_compose_b32_any, grid, dim3(TR_WG), 0, s, counts, nf, g, t->d_canvas, images);
+        if (aligned && cb == 1) hipLaunchKernelGGL(fsea_trace_compose_b8, grid, dim3(TR_WG), 0, s, counts, nf, g, t->canvas.ptr, images);
+        else if (aligned) hipLaunchKernelGGL(fsea_trace_compose_b32, grid, dim3(TR_WG), 0, s, counts, nf, g, t->canvas.ptr, images);
+        else if (cb == 1) hipLaunchKernelGGL(fsea_trace_compose_b8_any, grid, dim3(TR_WG), 0, s, counts, nf, g, t->canvas.ptr, images);
+        else hipLaunchKernelGGL(fsea_trace_compose_b32_any, grid, dim3(TR_WG), 0, s, counts, nf, g, t->canvas.ptr, images);
         FSEA_HIP(hipGetLastError());
     }
     return t->counts.release(s);
@@ -334,8 +330,7 @@ int fsea_trace_create(fsea_trace **out, const fsea_trace_config *cfg, int device
         g.magic = (65536u + (uint32_t)g.inc - 1u) / (uint32_t)g.inc;
         t->canvas_bytes = (frame_pixels(t) + 15) & ~(size_t)15;
         hipError_t e = t->counts.create(t->staging.stream);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_canvas), t->canvas_bytes);
-        if (e == hipSuccess) e = hipMemset(t->d_canvas, 0, t->canvas_bytes);
+        if (e == hipSuccess) e = t->canvas.zeros(t->canvas_bytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();
         return e;
     });
@@ -344,13 +339,10 @@ int fsea_trace_create(fsea_trace **out, const fsea_trace_config *cfg, int device
 int fsea_trace_destroy(fsea_trace *t) { return fsea_detail::destroy_object(t); }
 
 int fsea_trace_reset(fsea_trace *t) {
-    if (!t) return fail(FSEA_EINVAL, "trace is NULL");
-    std::lock_guard<std::mutex> lock(t->mu);
-    FSEA_ON_DEVICE(t->device);
-    FSEA_HIP(hipDeviceSynchronize());
-    FSEA_HIP(hipMemset(t->d_canvas, 0, t->canvas_bytes));
-    FSEA_HIP(hipDeviceSynchronize());
-    return FSEA_OK;
+    return fsea_detail::reset_object(t, "trace is NULL", [&]() -> int {
+        FSEA_HIP(t->canvas.zero(t->canvas_bytes));
+        return FSEA_OK;
+    });
 }
 
 int fsea_trace_frames_device(fsea_trace *t, const void *d_bytes, size_t n_bytes, int flip, size_t frame_bytes, int n_frames,
@@ -395,7 +387,7 @@ int fsea_trace_canvas_host(fsea_trace *t, uint8_t *image) {
         [&](void *, void *d_out, hipStream_t s) {
             int rc = t->counts.acquire(s);
             if (rc) return rc;
-            FSEA_HIP(hipMemcpyAsync(d_out, t->d_canvas, pixels, hipMemcpyDeviceToDevice, s));
+            FSEA_HIP(hipMemcpyAsync(d_out, t->canvas.ptr, pixels, hipMemcpyDeviceToDevice, s));
             return t->counts.release(s);
         });
 }

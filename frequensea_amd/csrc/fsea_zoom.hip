@@ -132,18 +132,12 @@ struct fsea_zoom {
     int n_taps = 0;
     int decimation = 1;
     int device = 0;
-    fsea_plan *plan = nullptr;                    // (fft_size, hop, mode) on the decimated pairs
-    fsea_detail::DeviceArray<float> d_taps;       // ZM_TAPS_ALLOC floats, zeros past n_taps
+    FirState state;                               // ZM_TAPS_ALLOC floats of taps, the two tails
     fsea_detail::DeviceArray<uint32_t> d_offs;    // ZM_TAPS_ALLOC byte offsets of the taps' samples in the LDS image, 0 past n_taps
-    fsea_detail::DeviceArray<cf> d_tail[2];       // FSEA_FIR_MAX_TAPS samples each; d_tail[cur] is the current tail
-    int cur = 0;
     fsea_detail::SharedScratch pairs;             // the decimated pairs of the last call; its event orders the calls
     std::mutex mu;
     fsea_detail::HostStaging staging;             // the host form
-
-    ~fsea_zoom() {
-        if (plan) (void)fsea_plan_destroy(plan);
-    }
+    fsea_detail::Owned<fsea_plan, fsea_plan_destroy> plan;   // (fft_size, hop, mode) on the decimated pairs; the first to go
 };
 
 namespace {
@@ -180,10 +174,10 @@ int queue_call(fsea_zoom *z, const void *d_iq, size_t n, int flip, const FirRot 
     const int need = zoom_lds_samples(D, L);
     auto kernel = need <= ZM_CAP_S ? fsea_shift_decim_u8_s : need <= ZM_CAP_M ? fsea_shift_decim_u8_m : fsea_shift_decim_u8;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(ZM_WG), 0, s, d_iq, (long long)n, flip ? 0x80808080u : 0u,
-                       (const cf *)z->d_tail[z->cur].ptr, z->d_tail[z->cur ^ 1].ptr, (const float *)z->d_taps.ptr,
-                       (const uint32_t *)z->d_offs.ptr, L, D, d_out, rot);
+                       z->state.in(), z->state.out(), (const float *)z->state.taps.ptr, (const uint32_t *)z->d_offs.ptr, L, D,
+                       d_out, rot);
     FSEA_HIP(hipGetLastError());
-    z->cur ^= 1;
+    z->state.advance();
     if (rows) {
         rc = fsea_detail::launch(z->plan, fsea::IN_F32, d_out, rows, 0, z->plan->mode, d_rows, s);
         if (rc) return rc;
@@ -200,33 +194,21 @@ int fsea_zoom_create(fsea_zoom **out, const double *taps, int n_taps, int decima
                      int device) {
     if (!out) return fail(FSEA_EINVAL, "zoom out-pointer is NULL");
     *out = nullptr;
-    if (!taps) return fail(FSEA_EINVAL, "taps is NULL");
-    if (n_taps < 1 || n_taps > FSEA_FIR_MAX_TAPS) {
-        return fail(FSEA_EINVAL, "n_taps must be in [1, %d], got %d", FSEA_FIR_MAX_TAPS, n_taps);
-    }
-    for (int k = 0; k < n_taps; ++k) {
-        if (!std::isfinite(taps[k])) return fail(FSEA_EINVAL, "tap %d is not finite", k);
-    }
+    if (int rc = FirState::check_taps(taps, n_taps)) return rc;
     if (decimation < 1 || decimation > FSEA_ZOOM_MAX_DECIMATION) {
         return fail(FSEA_EINVAL, "decimation must be in [1, %d], got %d", FSEA_ZOOM_MAX_DECIMATION, decimation);
     }
     return fsea_detail::create_object(out, device, "fsea_zoom_create", [&](fsea_zoom *z) -> int {
         z->n_taps = n_taps;
         z->decimation = decimation;
-        int rc = fsea_plan_create(&z->plan, fft_size, hop, mode, device);   // the sizes and modes of any plan, and its statuses
+        int rc = fsea_plan_create(&z->plan.ptr, fft_size, hop, mode, device);   // the sizes and modes of any plan, and its statuses
         if (rc) return rc;
-        float tf[ZM_TAPS_ALLOC] = {};
-        for (int k = 0; k < n_taps; ++k) tf[k] = (float)taps[k];
         uint32_t offs[ZM_TAPS_ALLOC] = {};
         for (int k = 0; k < n_taps; ++k) {
             offs[k] = (uint32_t)(((k % decimation) * zoom_pitch(decimation, n_taps) + k / decimation) * (int)sizeof(cf));
         }
-        hipError_t e = z->d_taps.alloc(ZM_TAPS_ALLOC);
-        if (e == hipSuccess) e = z->d_offs.alloc(ZM_TAPS_ALLOC);
-        if (e == hipSuccess) e = hipMemcpy(z->d_offs.ptr, offs, sizeof(offs), hipMemcpyHostToDevice);
-        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = z->d_tail[i].alloc(FSEA_FIR_MAX_TAPS);
-        if (e == hipSuccess) e = hipMemcpy(z->d_taps.ptr, tf, sizeof(tf), hipMemcpyHostToDevice);
-        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMemset(z->d_tail[i].ptr, 0, FSEA_FIR_MAX_TAPS * sizeof(cf));
+        hipError_t e = z->state.create(taps, n_taps, ZM_TAPS_ALLOC);
+        if (e == hipSuccess) e = z->d_offs.upload(offs, ZM_TAPS_ALLOC);
         if (e == hipSuccess) e = z->pairs.create(z->staging.stream);
         return fsea_detail::init_code("fsea_zoom_create", e);
     });
@@ -235,13 +217,7 @@ int fsea_zoom_create(fsea_zoom **out, const double *taps, int n_taps, int decima
 int fsea_zoom_destroy(fsea_zoom *z) { return fsea_detail::destroy_object(z); }
 
 int fsea_zoom_reset(fsea_zoom *z) {
-    if (!z) return fail(FSEA_EINVAL, "zoom is NULL");
-    std::lock_guard<std::mutex> lock(z->mu);
-    FSEA_ON_DEVICE(z->device);
-    FSEA_HIP(hipDeviceSynchronize());
-    FSEA_HIP(hipMemset(z->d_tail[z->cur].ptr, 0, FSEA_FIR_MAX_TAPS * sizeof(cf)));
-    FSEA_HIP(hipDeviceSynchronize());
-    return FSEA_OK;
+    return fsea_detail::reset_object(z, "zoom is NULL", [&] { return z->state.reset(); });
 }
 
 int fsea_zoom_set_window(fsea_zoom *z, const float *w) {
