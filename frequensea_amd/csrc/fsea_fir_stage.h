@@ -1,5 +1,6 @@
 // fsea_fir_stage.h -- how an input sample becomes the f32 complex value a FIR kernel stages in LDS, shared by the kernels of
-// fsea_fir.hip (fsea_fir_u8, fsea_fir_f64, fsea_shift_fir_u8) and fsea_zoom.hip (fsea_shift_decim_u8): the byte and f64
+// fsea_fir.hip (fsea_fir_u8, fsea_fir_f64, fsea_shift_fir_u8), fsea_zoom.hip (fsea_shift_decim_u8) and fsea_pfb.hip
+// (fsea_pfb_frames_u8): the byte and f64
 // conversions, the frequency shift of fsea_fir_u8_shifted_* (include/fsea.h) with every rounding spelled out, the packed
 // tap FMA, the host side of the shift (FirRot from the caller's arguments, the argument limits), and the filter state both
 // objects carry from call to call (FirState).  A sample's value is a function of (cycles_per_sample, phase0_cycles, stream
@@ -40,6 +41,17 @@ __device__ __forceinline__ cf pk_tap_fma_lo(cf w, cf taps, cf acc) {
 __device__ __forceinline__ cf pk_tap_fma_hi(cf w, cf taps, cf acc) {
     cf t;
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(t) : "v"(w), "s"(taps), "v"(acc));
+    return t;
+}
+// the same with a tap pair of the lane's own in a VGPR pair (fsea_pfb.hip: every column has its own branch of the prototype)
+__device__ __forceinline__ cf pk_tap_fma_lo_v(cf w, cf taps, cf acc) {
+    cf t;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(t) : "v"(w), "v"(taps), "v"(acc));
+    return t;
+}
+__device__ __forceinline__ cf pk_tap_fma_hi_v(cf w, cf taps, cf acc) {
+    cf t;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(t) : "v"(w), "v"(taps), "v"(acc));
     return t;
 }
 

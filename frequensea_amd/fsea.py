@@ -25,6 +25,8 @@ _MODE_DTYPE = {
 FIR_MAX_TAPS = 512          # FSEA_FIR_MAX_TAPS (include/fsea.h)
 ZOOM_MAX_DECIMATION = 64    # FSEA_ZOOM_MAX_DECIMATION
 ZOOM_TILE_OUTPUTS = 128     # FSEA_ZOOM_TILE_OUTPUTS: outputs per workgroup of fsea_shift_decim_u8
+PFB_MAX_CHANNELS = 16384    # FSEA_PFB_MAX_CHANNELS
+PFB_MAX_BRANCH_TAPS = 16    # FSEA_PFB_MAX_BRANCH_TAPS
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
@@ -142,6 +144,14 @@ API = {
     "fsea_zoom_row_bytes": (_sz, [_vp]),
     "fsea_zoom_run_device": (_ci, [_vp, _vp, _sz, _ci, _f64, _f64, _u64, _vp, _vp, _vp]),
     "fsea_zoom_run_host": (_ci, [_vp, _vp, _sz, _ci, _f64, _f64, _u64, _vp, _vp]),
+    "fsea_pfb_prototype": (_ci, [_ci, _ci, _vp]),
+    "fsea_pfb_create": (_ci, [_out, _vp, _ci, _ci, _ci, _ci, _ci]),
+    "fsea_pfb_destroy": (_ci, [_vp]),
+    "fsea_pfb_reset": (_ci, [_vp]),
+    "fsea_pfb_out_frames": (_sz, [_vp, _sz]),
+    "fsea_pfb_row_bytes": (_sz, [_vp]),
+    "fsea_pfb_run_device": (_ci, [_vp, _vp, _sz, _ci, _vp, _vp, _vp, _vp]),
+    "fsea_pfb_run_host": (_ci, [_vp, _vp, _sz, _ci, _vp, _vp, _vp]),
     "fsea_iq_draw_create": (_ci, [_out, _ci]),
     "fsea_iq_draw_destroy": (_ci, [_vp]),
     "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
@@ -627,6 +637,54 @@ class Zoom(_ResettableHandle):
         out_pairs(n_samples) complex64 out; asynchronous."""
         _check(self._L.fsea_zoom_run_device(self._p, d_iq_ptr, n_samples, int(bool(flip)), cycles_per_sample, phase0_cycles,
                                             sample_offset, d_rows_ptr, d_pairs_ptr, stream or None))
+
+
+def pfb_prototype(channels, branch_taps):
+    """fsea_pfb_prototype: the bank's default prototype, channels * lowpass_taps(2 channels, 1, channels * branch_taps)."""
+    taps = np.empty(max(int(channels) * int(branch_taps), 1), dtype=np.float64)
+    _check(hip_lib().fsea_pfb_prototype(int(channels), int(branch_taps), taps.ctypes.data))
+    return taps
+
+
+class Pfb(_ResettableHandle):
+    """A polyphase filter bank on one device: the band split into `channels` channels, a frame every channels /
+    oversampling samples; thin wrapper over fsea_pfb_*.  run() takes 8-bit IQ from the host and returns (rows, frames,
+    series): the rows of the inner (channels, channels, mode) plan on the len // (channels / oversampling) polyphase frames
+    of this call, and where asked for those frames and the rows transposed (one channel's outputs in a row; COMPLEX mode),
+    None otherwise.  Each call continues the stream of the previous ones; reset() starts a new one."""
+    _kind = "pfb"
+
+    def __init__(self, taps, channels, oversampling=1, mode=MODE_MAG_F32, device=0):
+        t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
+        if channels < 1 or t.size % channels:
+            raise ValueError("the prototype has channels * branch_taps taps")
+        self.channels, self.branch_taps, self.oversampling = channels, t.size // channels, oversampling
+        self.mode, self.device = mode, device
+        self._create("fsea_pfb_create", t.ctypes.data if t.size else None, channels, self.branch_taps, oversampling, mode, device)
+
+    def out_frames(self, n_samples):
+        return self._L.fsea_pfb_out_frames(self._p, n_samples)
+
+    @property
+    def row_bytes(self):
+        return self._L.fsea_pfb_row_bytes(self._p)
+
+    def run(self, iq_u8, flip=False, frames=False, series=False):
+        iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
+        n = iq.size // 2
+        F, M = self.out_frames(n), self.channels
+        rows = np.empty((F, M), dtype=_MODE_DTYPE[self.mode])
+        fr = np.empty((F, M), dtype=np.complex64) if frames else None
+        se = np.empty((M, F), dtype=np.complex64) if series else None
+        _check(self._L.fsea_pfb_run_host(self._p, iq.ctypes.data, n, int(bool(flip)), rows.ctypes.data,
+                                         fr.ctypes.data if frames else None, se.ctypes.data if series else None))
+        return rows, fr, se
+
+    def run_device(self, d_iq_ptr, n_samples, d_rows_ptr, flip=False, d_frames_ptr=None, d_series_ptr=None, stream=0):
+        """Device pointers (ints, 16-byte aligned): 2 * n_samples bytes in, out_frames(n_samples) rows and, where asked for,
+        as many frames of `channels` complex64 and the `channels` series out; asynchronous."""
+        _check(self._L.fsea_pfb_run_device(self._p, d_iq_ptr, n_samples, int(bool(flip)), d_rows_ptr, d_frames_ptr,
+                                           d_series_ptr, stream or None))
 
 
 class Demod(_ResettableHandle):

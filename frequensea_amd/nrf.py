@@ -159,7 +159,7 @@ _INTERPOLATOR = {
     "nrf_interpolator_get_buffer": (_buf, [_ipp]),
     "nrf_interpolator_free": (None, [_ipp]),
 }
-_REST = {     # what only nrf_lib() binds: blocks, the sample source, the FFT, the shifter, the IQ filter and chain, the zoom spectrum, the signal capture
+_REST = {     # what only nrf_lib() binds: blocks, the sample source, the FFT, the shifter, the IQ filter and chain, the zoom spectrum, the filter bank, the signal capture
     "nrf_block_init": (None, [_vp, _ci, _vp, _vp]),
     "nrf_block_connect": (None, [_vp, _vp]),
     "nrf_block_process": (None, [_vp, _buf]),
@@ -199,6 +199,10 @@ _REST = {     # what only nrf_lib() binds: blocks, the sample source, the FFT, t
     "nrf_zoom_fft_process": (None, [_vp, _buf]),
     "nrf_zoom_fft_get_buffer": (_buf, [_vp]),
     "nrf_zoom_fft_free": (None, [_vp]),
+    "nrf_pfb_fft_new": (_vp, [_ci] * 3),
+    "nrf_pfb_fft_process": (None, [_vp, _buf]),
+    "nrf_pfb_fft_get_buffer": (_buf, [_vp]),
+    "nrf_pfb_fft_free": (None, [_vp]),
     "nrf_signal_capture_new": (_vp, [_ci, _ci, _ci, _f64]),
     "nrf_signal_capture_scan": (_ci, [_vp, _buf, _ci]),
     "nrf_signal_capture_get_mean": (_f64, [_vp, _ci]),
@@ -217,6 +221,7 @@ NRF_ADDITIONS = ["nrf_fft_set_window", "nrf_fft_set_window_weights", "nrf_decode
                  "nrf_iq_chain_get_iq_lines", "nrf_iq_chain_get_buffer", "nrf_iq_chain_free",
                  "nrf_zoom_fft_new", "nrf_zoom_fft_set_freq_offset", "nrf_zoom_fft_process", "nrf_zoom_fft_get_buffer",
                  "nrf_zoom_fft_free",
+                 "nrf_pfb_fft_new", "nrf_pfb_fft_process", "nrf_pfb_fft_get_buffer", "nrf_pfb_fft_free",
                  "nrf_signal_capture_new", "nrf_signal_capture_scan", "nrf_signal_capture_get_mean",
                  "nrf_signal_capture_get_standard_deviation", "nrf_signal_capture_get_burst",
                  "nrf_signal_capture_get_iq_lines", "nrf_signal_capture_free"]

@@ -31,6 +31,7 @@
  *                         nrf_fir_filter_get / nrf_iq_filter_get_buffer, src/nrf.c:654-775
  *   fsea_chain_*          shift -> filter -> images per block with the filtered block resident on the device
  *   fsea_zoom_*           shift -> decimating filter -> FFT: a spectrum of 1 / D of the bandwidth (nrf_decoder's chain)
+ *   fsea_pfb_*            a polyphase filter bank (no counterpart in the reference): all M channels of the band at once
  *   fsea_detect_*         the burst detector of lua/signal-detector.lua: the two loops of nrf_signal_detector_process,
  *                         src/nrf.c:883-898, as integer sums over many blocks per launch
  *   fsea_capture_*        that scene on a resident recording: detect -> gate -> filter the bursts -> line images
@@ -61,6 +62,7 @@ typedef struct fsea_fir fsea_fir;
 typedef struct fsea_iq_draw fsea_iq_draw;
 typedef struct fsea_chain fsea_chain;
 typedef struct fsea_zoom fsea_zoom;
+typedef struct fsea_pfb fsea_pfb;
 typedef struct fsea_demod fsea_demod;
 typedef struct fsea_interp fsea_interp;
 typedef struct fsea_trace fsea_trace;
@@ -507,6 +509,60 @@ int fsea_zoom_run_device(fsea_zoom *zoom, const void *d_iq, size_t n_samples, in
                          double phase0_cycles, uint64_t sample_offset, void *d_rows, void *d_pairs, void *stream);
 int fsea_zoom_run_host(fsea_zoom *zoom, const uint8_t *iq, size_t n_samples, int flip, double cycles_per_sample,
                        double phase0_cycles, uint64_t sample_offset, void *rows, float *pairs);
+
+/* The polyphase filter bank: the whole band split into M channels, every D-th output of each, D = M / q.  A prototype
+ * low-pass c of L = M P taps (doubles, copied as f32) is folded into M branches of P taps; one M-point transform of the
+ * object's own plan follows per frame.  State between calls: the tail (the last L - 1 samples of earlier calls, zero after
+ * create and reset) and s0, the samples earlier calls consumed since create or reset.  A call reads its n_samples 8-bit
+ * pairs as the other u8 entry points do (u8 / 256; flip != 0: b ^ 0x80 first).  With x_ext = tail ++ x and
+ * F = n_samples / D (rounded down), for t < F and r < M
+ *   v_t[r] = sum_{p < P} c[p M + r] x_ext[t D + p M + r]       one f32 FMA chain per output, p ascending, from +0
+ *   frames[t][(r + s0 + t D) mod M] = v_t[r]
+ *   rows[t] = the plan (size M, hop M, the object's mode) on frames[t] as f32 input,
+ * which, M being even, is with the plan's (-1)^m centring
+ *   X_t[k] = sum_{j < L} c[j] x_ext[t D + j] e^{-2 pi i (k - M/2)(s0 + t D + j) / M}:
+ * column k of a row is the band centred at (k - M/2) rate / M, mixed to zero with a phase tied to the stream position,
+ * filtered by c, every D-th output.  Column M/2 is the centre channel and carries the offset-binary DC term; MAG and DB5
+ * rows get the plan's usual DC patch there.  Afterwards the tail is the last L - 1 values of x_ext (also when
+ * n_samples < L - 1) and s0 += n_samples: a stream cut at multiples of D gives the one-call result bit for bit; the
+ * n_samples mod D samples a call leaves over stay in the tail, and the next call's frames start at its own sample 0 (the
+ * zoom's convention).  v_t[r] is output t D of fsea_fir_u8_device with the taps c[p M + r] at p M + r and zeros elsewhere,
+ * as a value; the rows are those of fsea_exec_f64_host of such a plan on the frames, bit for bit.
+ * Kernel fsea_pfb_frames_u8: a workgroup of 256 lanes owns T frames x C columns and stages T + (2 ceil(P / 2) - 1) q rows
+ * of C samples in LDS: the smallest image of 20, 40 and 80 KiB, and in it the widest C of min(M, 256), 128 and 64, that
+ * leave T >= twice those extra rows (64 columns in 80 KiB where none does), T <= 128 a multiple of the 256 / C frames
+ * the lanes work on at a time.  Kernel fsea_pfb_transpose:
+ * series[k F + t] = rows[t][k], the F outputs of channel k in a row.
+ *   prototype:  host arithmetic, no device: taps[j] = channels * fsea_fir_lowpass_taps(2 channels, 1, channels branch_taps)[j],
+ *               the half-amplitude point at half a channel, scaled by M so that a row has the scale of the plan's M-point
+ *               rows (a constant c gives M c in column M/2) and the dB modes' pixel mapping keeps its range.
+ *   create:     channels even in [2, FSEA_PFB_MAX_CHANNELS], branch_taps in [1, FSEA_PFB_MAX_BRANCH_TAPS], oversampling q
+ *               1, 2 or 4 and a divisor of channels; mode as fsea_plan_create, with its statuses (and the plan's for a size
+ *               it does not serve).  A channel count that is no power of two, or below 32, runs on the plan's Bluestein
+ *               path and inherits its limits: no stream capture, and the object's launches on different streams follow one
+ *               another.  FSEA_EINVAL for a NULL pointer, a parameter out of range or a non-finite tap, checked before any
+ *               device work; FSEA_ENODEVICE without a GPU.
+ *   reset:      a zero tail and s0 = 0; synchronous.
+ *   run_device: d_iq (2 n_samples bytes), d_rows (out_frames x row_bytes), d_frames (NULL, or 2 F M floats) and d_series
+ *               (NULL, or 2 M F floats; FSEA_MODE_COMPLEX_F32 only), 16-byte aligned; asynchronous on `stream`.  The frames
+ *               pass through the object's buffer: a call on any stream waits for the previous call of the object (an event).
+ *   run_host:   the same from and to host memory through pinned staging on the object's own stream; returns when the
+ *               outputs are complete.  Calls on one object from several threads are serialised.
+ * Both check before any device work: FSEA_EINVAL for a NULL object or buffer (d_rows / rows only where the call yields a
+ * frame), a series outside FSEA_MODE_COMPLEX_F32, a misaligned device buffer, more than 2^31 samples, F M > 2^31.
+ * Destroy waits for the device. */
+#define FSEA_PFB_MAX_CHANNELS 16384
+#define FSEA_PFB_MAX_BRANCH_TAPS 16
+int fsea_pfb_prototype(int channels, int branch_taps, double *taps);
+int fsea_pfb_create(fsea_pfb **pfb, const double *taps, int channels, int branch_taps, int oversampling, int mode, int device);
+int fsea_pfb_destroy(fsea_pfb *pfb);
+int fsea_pfb_reset(fsea_pfb *pfb);
+size_t fsea_pfb_out_frames(const fsea_pfb *pfb, size_t n_samples);
+size_t fsea_pfb_row_bytes(const fsea_pfb *pfb);
+int fsea_pfb_run_device(fsea_pfb *pfb, const void *d_iq, size_t n_samples, int flip, void *d_rows, void *d_frames,
+                        void *d_series, void *stream);
+int fsea_pfb_run_host(fsea_pfb *pfb, const uint8_t *iq, size_t n_samples, int flip, void *rows, float *frames,
+                      float *series);
 
 /* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
  * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With

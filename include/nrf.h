@@ -372,6 +372,35 @@ void nrf_zoom_fft_process(nrf_zoom_fft *zoom, nut_buffer *samples);
 nut_buffer *nrf_zoom_fft_get_buffer(nrf_zoom_fft *zoom);
 void nrf_zoom_fft_free(nrf_zoom_fft *zoom);
 
+/* ---- ADDITIONS (not in the reference): the filter-bank spectrum ---- */
+
+/* nrf_fft with a polyphase filter bank in front of the transform (fsea_pfb_*, include/fsea.h), a drop-in for nrf_fft in the
+ * FFT scenes: fft_size channels, the prototype of fsea_pfb_prototype(fft_size, branch_taps), no oversampling.  Where a
+ * rectangular fft_size-point row leaks a tone between two bins into every other bin (-17 dB three bins away), a bin here
+ * has the prototype's stop band.
+ *   - Rows are nrf_fft's in scale and layout: magnitudes, the DC bin replaced, bin fft_size / 2 the centre.  A block of
+ *     `length` pairs gives length / fft_size rows; the last fft_size * branch_taps - 1 samples and the stream position carry
+ *     on to the next block, so a row looks back over earlier blocks.
+ *   - get_buffer is the history: fft_history_size rows of fft_size F64 values, one channel, row 0 the newest (all 0.0 at
+ *     the start); when a block yields fft_history_size rows or more its newest fft_history_size remain.
+ * process takes a U8 buffer with 2 channels.  An F64 buffer, an fft_size that is odd or outside [2, FSEA_PFB_MAX_CHANNELS],
+ * branch_taps outside [1, FSEA_PFB_MAX_BRANCH_TAPS], a history size below 1 and a backend failure (no GPU) print
+ * "NRF PFB FFT fatal error: ..." and exit.  The buffer returned is the caller's to free. */
+typedef struct {
+    NRF_BLOCK;
+    int fft_size;             /* channels */
+    int fft_history_size;     /* rows */
+    int branch_taps;
+    double *history;          /* fft_history_size x fft_size, row 0 the newest */
+    void *backend;            /* fsea_pfb* (libfsea_hip.so) */
+    pthread_mutex_t mutex;
+} nrf_pfb_fft;
+
+nrf_pfb_fft *nrf_pfb_fft_new(int fft_size, int fft_history_size, int branch_taps);
+void nrf_pfb_fft_process(nrf_pfb_fft *pfb, nut_buffer *samples);
+nut_buffer *nrf_pfb_fft_get_buffer(nrf_pfb_fft *pfb);
+void nrf_pfb_fft_free(nrf_pfb_fft *pfb);
+
 /* ---- ADDITIONS (not in the reference): the signal capture ---- */
 
 /* The reference's signal scene (lua/signal-detector.lua:89-133) over a whole recording that stays on the GPU: the detector
