@@ -149,6 +149,11 @@ int SharedScratch::acquire(hipStream_t s) {
     return FSEA_OK;
 }
 
+int SharedScratch::acquire(size_t need, hipStream_t s) {
+    const int rc = buf.cap < need ? reserve(need) : FSEA_OK;
+    return rc ? rc : acquire(s);
+}
+
 int SharedScratch::release(hipStream_t s) {
     FSEA_HIP(hipEventRecord(used, s));
     return FSEA_OK;

@@ -6,7 +6,7 @@
 // waits, runs the scene's state machine over the statistics on the host (fsea_capture_segment) and then queues one
 // fsea_chain_run_device per run of consecutive gated blocks, straight from the recording, its pairs going to the end of the
 // burst buffer.  The block sequence it replaces brings every block to the host to decide whether it is worth filtering.
-#include "fsea_internal.h"
+#include "fsea_fir_stage.h"
 
 #include <algorithm>
 #include <cstring>
@@ -143,29 +143,15 @@ int lines_launch(fsea_capture *c, size_t burst, int m, size_t n_line_points, voi
 
 extern "C" {
 
-// Not through fsea_detail::create_object, as fsea_chain_create: the taps are checked by the chain's filter, and bad taps
-// are reported before a missing device.
 int fsea_capture_create(fsea_capture **out, const double *taps, int n_taps, int device) {
     if (!out) return fail(FSEA_EINVAL, "capture out-pointer is NULL");
     *out = nullptr;
-    fsea_capture *c = new (std::nothrow) fsea_capture();
-    if (!c) return fail(FSEA_ENOMEM, "out of host memory");
-    c->device = device;
-    int rc = fsea_chain_create(&c->chain.ptr, taps, n_taps, device);   // checks the taps, then the device
-    if (!rc) rc = fsea_detect_create(&c->detect.ptr, device);
-    if (!rc) rc = fsea_iq_draw_create(&c->draw.ptr, device);
-    if (!rc) {
-        DeviceGuard guard(device);
-        hipError_t e = guard.err;
-        if (e == hipSuccess) e = c->staging.create();
-        if (e != hipSuccess) rc = fail(FSEA_EHIP, "fsea_capture_create: %s", hipGetErrorString(e));
-    }
-    if (rc) {
-        delete c;   // no device memory of its own yet; the three objects restore the device themselves
-        return rc;
-    }
-    *out = c;
-    return FSEA_OK;
+    if (int rc = fsea_stage::FirState::check_taps(taps, n_taps)) return rc;   // bad taps are reported before a missing device
+    return fsea_detail::create_object(out, device, "fsea_capture_create", [&](fsea_capture *c) -> int {
+        int rc = fsea_chain_create(&c->chain.ptr, taps, n_taps, device);
+        if (!rc) rc = fsea_detect_create(&c->detect.ptr, device);
+        return rc ? rc : fsea_iq_draw_create(&c->draw.ptr, device);
+    });
 }
 
 int fsea_capture_destroy(fsea_capture *c) { return fsea_detail::destroy_object(c); }

@@ -7,7 +7,7 @@
 // that buffer as FSEA_IQ_F32 (fsea_iq_points_device / fsea_iq_lines_device), the downloads of what was asked for, and
 // waits once.  The block sequence it replaces moves the filtered block to the host as f32, widens it to f64 there and
 // uploads it again for every image.
-#include "fsea_internal.h"
+#include "fsea_fir_stage.h"
 
 #include <cstring>
 
@@ -106,40 +106,28 @@ int queue_images(fsea_chain *c, int n_frames, const fsea_chain_outputs &o, void 
     return FSEA_OK;
 }
 
-// One host call: upload and filter n samples (run), then the outputs of the resident block.  The caller holds c->mu.
+// One host call: upload and filter n samples (run), then the outputs of the resident block: the images through the
+// staging, the pairs straight from c->pairs.  The caller holds c->mu.
 int host_call(fsea_chain *c, bool run, const void *in, int f64, size_t n, const fsea_chain_stage &st,
               const fsea_chain_outputs &o) {
     FSEA_ON_DEVICE(c->device);
-    fsea_detail::HostStaging &g = c->staging;
     const size_t in_bytes = run ? n * (f64 ? 16 : 2) : 0;
     const size_t total = run ? n + st.n_zero : c->n_pairs;
-    const size_t lines_at = o.points ? IMAGE_BYTES : 0;
-    const size_t pairs_at = lines_at + line_pixels(o);
-    const size_t out_bytes = pairs_at + (o.pairs ? total * 8 : 0);
-    int rc = g.reserve(in_bytes, out_bytes);
-    if (rc) return rc;
     if (run) {
         c->n_pairs = 0;
-        rc = reserve_pairs(c, total * 8);
-        if (rc) return rc;
-        if (in_bytes) {
-            std::memcpy(g.h_in.ptr, in, in_bytes);
-            FSEA_HIP(hipMemcpyAsync(g.d_in.ptr, g.h_in.ptr, in_bytes, hipMemcpyHostToDevice, g.stream));
-        }
-        rc = queue_filter(c, f64, g.d_in.ptr, n, 1, st, g.stream);
-        if (rc) return rc;
-        c->n_pairs = total;
+        if (int rc = reserve_pairs(c, total * 8)) return rc;
     }
-    uint8_t *h = static_cast<uint8_t *>(g.h_out.ptr), *d = static_cast<uint8_t *>(g.d_out.ptr);
-    rc = queue_images(c, 1, o, d, d + lines_at, g.stream);
-    if (rc) return rc;
-    if (pairs_at) FSEA_HIP(hipMemcpyAsync(h, d, pairs_at, hipMemcpyDeviceToHost, g.stream));
-    if (o.pairs && total) FSEA_HIP(hipMemcpyAsync(h + pairs_at, c->pairs.ptr, total * 8, hipMemcpyDeviceToHost, g.stream));
-    FSEA_HIP(hipStreamSynchronize(g.stream));
-    if (o.points) std::memcpy(o.points, h, IMAGE_BYTES);
-    if (o.lines) std::memcpy(o.lines, h + lines_at, line_pixels(o));
-    if (o.pairs && total) std::memcpy(o.pairs, h + pairs_at, total * 8);
-    return FSEA_OK;
+    const fsea_detail::HostStaging::Part parts[3] = {{o.points, IMAGE_BYTES}, {o.lines, line_pixels(o)}, {o.pairs, total * 8}};
+    return c->staging.run(
+        in_bytes, parts, [&](void *h_in) { std::memcpy(h_in, in, in_bytes); },
+        [&](void *d_in, void **d_parts, hipStream_t s) {
+            if (run) {
+                if (int rc = queue_filter(c, f64, d_in, n, 1, st, s)) return rc;
+                c->n_pairs = total;
+            }
+            if (d_parts[2]) d_parts[2] = c->pairs.ptr;
+            return queue_images(c, 1, o, d_parts[0], d_parts[1], s);
+        });
 }
 
 int run_host(fsea_chain *c, const void *iq, int f64, size_t n, const fsea_chain_stage *stage, const fsea_chain_outputs *outputs) {
@@ -158,28 +146,14 @@ int run_host(fsea_chain *c, const void *iq, int f64, size_t n, const fsea_chain_
 
 extern "C" {
 
-// Not through fsea_detail::create_object: the taps are checked by fsea_fir_create, and bad taps are reported before a
-// missing device, so the object exists before the device is looked at.
 int fsea_chain_create(fsea_chain **out, const double *taps, int n_taps, int device) {
     if (!out) return fail(FSEA_EINVAL, "chain out-pointer is NULL");
     *out = nullptr;
-    fsea_chain *c = new (std::nothrow) fsea_chain();
-    if (!c) return fail(FSEA_ENOMEM, "out of host memory");
-    c->device = device;
-    int rc = fsea_fir_create(&c->fir.ptr, taps, n_taps, device);   // checks the taps, then the device
-    if (!rc) rc = fsea_iq_draw_create(&c->draw.ptr, device);
-    if (!rc) {
-        DeviceGuard guard(device);
-        hipError_t e = guard.err;
-        if (e == hipSuccess) e = c->staging.create();
-        if (e != hipSuccess) rc = fail(FSEA_EHIP, "fsea_chain_create: %s", hipGetErrorString(e));
-    }
-    if (rc) {
-        delete c;   // no device memory of its own yet; the two objects restore the device themselves
-        return rc;
-    }
-    *out = c;
-    return FSEA_OK;
+    if (int rc = fsea_stage::FirState::check_taps(taps, n_taps)) return rc;   // bad taps are reported before a missing device
+    return fsea_detail::create_object(out, device, "fsea_chain_create", [&](fsea_chain *c) -> int {
+        int rc = fsea_fir_create(&c->fir.ptr, taps, n_taps, device);
+        return rc ? rc : fsea_iq_draw_create(&c->draw.ptr, device);
+    });
 }
 
 int fsea_chain_destroy(fsea_chain *c) { return fsea_detail::destroy_object(c); }

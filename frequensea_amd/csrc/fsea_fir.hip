@@ -261,7 +261,7 @@ int fsea_fir_create(fsea_fir **out, const double *taps, int n_taps, int device) 
     if (int rc = FirState::check_taps(taps, n_taps)) return rc;
     return fsea_detail::create_object(out, device, "fsea_fir_create", [&](fsea_fir *f) {
         f->n_taps = n_taps;
-        return f->state.create(taps, n_taps, FIR_TAPS_ALLOC);
+        return f->state.create(taps, n_taps, FIR_TAPS_ALLOC, FSEA_FIR_MAX_TAPS);
     });
 }
 

@@ -1,9 +1,9 @@
 // fsea_fir_stage.h -- how an input sample becomes the f32 complex value a FIR kernel stages in LDS, shared by the kernels of
 // fsea_fir.hip (fsea_fir_u8, fsea_fir_f64, fsea_shift_fir_u8), fsea_zoom.hip (fsea_shift_decim_u8) and fsea_pfb.hip
-// (fsea_pfb_frames_u8): the byte and f64
-// conversions, the frequency shift of fsea_fir_u8_shifted_* (include/fsea.h) with every rounding spelled out, the packed
-// tap FMA, the host side of the shift (FirRot from the caller's arguments, the argument limits), and the filter state both
-// objects carry from call to call (FirState).  A sample's value is a function of (cycles_per_sample, phase0_cycles, stream
+// (fsea_pfb_frames_u8): the byte and f64 conversions, the frequency shift of fsea_fir_u8_shifted_* (include/fsea.h) with
+// every rounding spelled out, the packed tap FMA, the host side of the shift (FirRot from the caller's arguments, the
+// argument limits), and the filter state the three objects carry from call to call (FirState: the taps and two tails of a
+// length each object gives at create).  A sample's value is a function of (cycles_per_sample, phase0_cycles, stream
 // position) alone, so every kernel that stages through these helpers sees the same bits.
 #pragma once
 
@@ -184,36 +184,41 @@ inline int check_shift(double cycles_per_sample, double phase0_cycles, uint64_t 
     return FSEA_OK;
 }
 
-// What fsea_fir and fsea_zoom keep between calls: the taps as floats, padded with zeros to the length the object's kernel
-// reads, and two tails of FSEA_FIR_MAX_TAPS samples.  A launch reads in() and writes out(); advance() makes the written
-// tail the current one.
+// What fsea_fir, fsea_zoom and fsea_pfb keep between calls: the taps as floats, padded with zeros to the length the
+// object's kernel reads, and two tails of tail_len samples, the length given at create: FSEA_FIR_MAX_TAPS for the filter
+// and the zoom, the bank's L - 1.  A launch reads in() and writes out(); advance() makes the written tail the current one.
 struct FirState {
     fsea_detail::DeviceArray<float> taps;
     fsea_detail::DeviceArray<cf> tail[2];
+    size_t tail_len = 0;
     int cur = 0;
 
-    static int check_taps(const double *taps, int n_taps) {
-        if (!taps) return fsea_detail::fail(FSEA_EINVAL, "taps is NULL");
-        if (n_taps < 1 || n_taps > FSEA_FIR_MAX_TAPS) {
-            return fsea_detail::fail(FSEA_EINVAL, "n_taps must be in [1, %d], got %d", FSEA_FIR_MAX_TAPS, n_taps);
-        }
+    static int check_finite(const double *taps, int n_taps) {
         for (int k = 0; k < n_taps; ++k) {
             if (!std::isfinite(taps[k])) return fsea_detail::fail(FSEA_EINVAL, "tap %d is not finite", k);
         }
         return FSEA_OK;
     }
-    hipError_t create(const double *t, int n_taps, int alloc_floats) {
+    static int check_taps(const double *taps, int n_taps) {
+        if (!taps) return fsea_detail::fail(FSEA_EINVAL, "taps is NULL");
+        if (n_taps < 1 || n_taps > FSEA_FIR_MAX_TAPS) {
+            return fsea_detail::fail(FSEA_EINVAL, "n_taps must be in [1, %d], got %d", FSEA_FIR_MAX_TAPS, n_taps);
+        }
+        return check_finite(taps, n_taps);
+    }
+    hipError_t create(const double *t, int n_taps, int alloc_floats, size_t tail_samples) {
         std::vector<float> tf((size_t)alloc_floats, 0.0f);
         for (int k = 0; k < n_taps; ++k) tf[k] = (float)t[k];
+        tail_len = tail_samples;
         hipError_t e = taps.upload(tf.data(), tf.size());
-        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = tail[i].zeros(FSEA_FIR_MAX_TAPS);
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = tail[i].zeros(tail_len);
         return e;
     }
     const cf *in() const { return tail[cur].ptr; }
     cf *out() const { return tail[cur ^ 1].ptr; }
     void advance() { cur ^= 1; }
     int reset() {   // the current tail only: the other one is written whole by the next launch
-        FSEA_HIP(tail[cur].zero(FSEA_FIR_MAX_TAPS));
+        FSEA_HIP(tail[cur].zero(tail_len));
         return FSEA_OK;
     }
 };

@@ -8,10 +8,13 @@
 // a failed create frees whatever it got as far as making, and the order of the members is the order of release, reversed.
 //
 // The scaffold: shared argument checks, create_object / destroy_object / reset_object, the event-ordered scratch buffer
-// (SharedScratch), host-form staging (HostStaging).  What stays written out: fsea_chain_create and fsea_capture_create
-// (bad taps are reported before a missing device), fsea_plan_reset (it clears the counter slots too), fsea_interp_reset
-// (nothing to zero and no second wait without elements), and the two device-wide waits of fsea_demod (before an evicted
-// index table is released and before the stage-1 buffer grows).
+// (SharedScratch), host-form staging (HostStaging).  A host form with several outputs (rows and pairs, two images and
+// pairs) hands HostStaging::run its parts: they lie behind one another in the staging at 16-byte boundaries and come back
+// in one copy and one wait.  The filter state of fsea_fir, fsea_zoom and fsea_pfb is FirState (fsea_fir_stage.h), whose
+// tail length each object gives at create: FSEA_FIR_MAX_TAPS samples, or the bank's L - 1.  What stays written out:
+// fsea_plan_reset (it clears the counter slots too), fsea_interp_reset (nothing to zero and no second wait without
+// elements), and the two device-wide waits of fsea_demod (before an evicted index table is released and before the
+// stage-1 buffer grows).
 //
 // fsea_api.hip: the error plumbing, the scaffold's bodies and the entry points that take no plan;
 // fsea_plan.hip: the kernel registry, a plan's life cycle, the launch path and the device-buffer entry points;
@@ -228,29 +231,66 @@ struct HostStaging {
     hipError_t create() { return stream.create(); }
     int reserve(size_t in_bytes, size_t out_bytes);
 
-    // One host-form call: fill(h_in) writes the in_bytes of input into pinned memory, copy in, launch(d_in, d_out, stream)
-    // queues the object's work, copy out, wait, out_bytes to `out`.  Zero-byte copies are skipped.  The caller holds the
-    // object's mutex and is on its device.
-    template <class Fill, class Launch>
-    int run(size_t in_bytes, size_t out_bytes, void *out, Fill &&fill, Launch &&launch) {
-        int rc = reserve(in_bytes, out_bytes);
+    // One output of a host-form call: `bytes` to `host`.  A part whose pointer is null or whose size is zero is not asked
+    // for: it takes no room and its device address is null.
+    struct Part {
+        void *host;
+        size_t bytes;
+    };
+
+    // One host-form call: fill(h_in) writes the in_bytes of input into pinned memory, copy in, launch(d_in, d_parts, stream)
+    // queues the object's work, copy out, wait, every part to its host pointer.  The parts lie behind d_out / h_out in
+    // their order, each at a 16-byte boundary; d_parts[i] is the device address of part i.  A launch may put memory of
+    // the object's own there instead: that part comes back in a copy of its own, queued behind the one copy of all that
+    // is staged.  Zero-byte copies are skipped.  The caller holds the object's mutex and is on its device.
+    template <size_t N, class Fill, class Launch>
+    int run(size_t in_bytes, const Part (&parts)[N], Fill &&fill, Launch &&launch) {
+        size_t at[N], bytes[N], end = 0;
+        for (size_t i = 0; i < N; ++i) {
+            bytes[i] = parts[i].host ? parts[i].bytes : 0;
+            at[i] = (end + 15) & ~(size_t)15;
+            if (bytes[i]) end = at[i] + bytes[i];
+        }
+        int rc = reserve(in_bytes, end);
         if (rc) return rc;
         if (in_bytes) {
             fill(h_in.ptr);
             FSEA_HIP(hipMemcpyAsync(d_in.ptr, h_in.ptr, in_bytes, hipMemcpyHostToDevice, stream));
         }
-        rc = launch(d_in.ptr, d_out.ptr, stream);
+        uint8_t *h = static_cast<uint8_t *>(h_out.ptr), *d = static_cast<uint8_t *>(d_out.ptr);
+        void *d_parts[N];
+        for (size_t i = 0; i < N; ++i) d_parts[i] = bytes[i] ? d + at[i] : nullptr;
+        rc = launch(d_in.ptr, d_parts, stream);
         if (rc) return rc;
-        if (out_bytes) FSEA_HIP(hipMemcpyAsync(h_out.ptr, d_out.ptr, out_bytes, hipMemcpyDeviceToHost, stream));
+        size_t staged = 0;
+        for (size_t i = 0; i < N; ++i) {
+            if (bytes[i] && d_parts[i] == d + at[i]) staged = at[i] + bytes[i];
+        }
+        if (staged) FSEA_HIP(hipMemcpyAsync(h, d, staged, hipMemcpyDeviceToHost, stream));
+        for (size_t i = 0; i < N; ++i) {
+            if (bytes[i] && d_parts[i] != d + at[i]) {
+                FSEA_HIP(hipMemcpyAsync(h + at[i], d_parts[i], bytes[i], hipMemcpyDeviceToHost, stream));
+            }
+        }
         FSEA_HIP(hipStreamSynchronize(stream));
-        if (out_bytes) std::memcpy(out, h_out.ptr, out_bytes);
+        for (size_t i = 0; i < N; ++i) {
+            if (bytes[i]) std::memcpy(parts[i].host, h + at[i], bytes[i]);
+        }
         return FSEA_OK;
+    }
+
+    // the same with one output: launch(d_in, d_out, stream)
+    template <class Fill, class Launch>
+    int run(size_t in_bytes, size_t out_bytes, void *out, Fill &&fill, Launch &&launch) {
+        const Part part[1] = {{out, out_bytes}};
+        return run(in_bytes, part, fill, [&](void *d_in, void **d_parts, hipStream_t s) { return launch(d_in, d_parts[0], s); });
     }
 };
 
 // A growable device buffer that an object's launches use on whatever stream the caller names.  One event keeps them in
 // order: acquire(s) makes s wait for the previous use, release(s) records the end of this one, and reserve() waits on the
-// host for the last use before the buffer is reallocated (or, by the caller, overwritten).  The caller holds the object's
+// host for the last use before the buffer is reallocated (or, by the caller, overwritten).  acquire(need, s) is how a
+// launch begins: reserve(need) where the buffer is shorter than that, then acquire(s).  The caller holds the object's
 // mutex and is on its device.
 struct SharedScratch {
     DeviceBuffer buf;
@@ -259,6 +299,7 @@ struct SharedScratch {
     hipError_t create(hipStream_t first);  // the event starts recorded on `first`, so it can be waited for at once
     int reserve(size_t need);
     int acquire(hipStream_t s);
+    int acquire(size_t need, hipStream_t s);
     int release(hipStream_t s);
 };
 

@@ -274,9 +274,8 @@ int lines_launch(fsea_iq_draw *d, const void *d_iq, int type, int flip, size_t n
         return FSEA_OK;
     }
     const size_t chunk = std::min<size_t>((size_t)n_frames, std::max<size_t>(1, LN_CHUNK_BYTES / (4 * pixels)));
-    int rc = d->counts.buf.cap < chunk * pixels * 4 ? d->counts.reserve(chunk * pixels * 4) : FSEA_OK;
-    if (!rc) rc = d->counts.acquire(s);  // every use of the count buffer, on whatever stream, follows the previous one
-    if (rc) return rc;
+    // every use of the count buffer, on whatever stream, follows the previous one
+    if (int rc = d->counts.acquire(chunk * pixels * 4, s)) return rc;
     uint32_t *d_counts = static_cast<uint32_t *>(d->counts.buf.ptr);
     const uint32_t fm = (type == FSEA_IQ_U8 && flip) ? 0x80808080u : 0u;
     const long long n = (long long)n_points;

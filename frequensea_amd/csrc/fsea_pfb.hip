@@ -22,9 +22,6 @@
 // 8-byte accesses contiguous along k on the read and along t on the write.
 #include "fsea_fir_stage.h"
 
-#include <cmath>
-#include <vector>
-
 using fsea_detail::DeviceGuard;
 using fsea_detail::fail;
 using namespace fsea_stage;
@@ -192,15 +189,11 @@ struct fsea_pfb {
     int channels = 0, branch_taps = 0, oversampling = 1, mode = 0;
     int device = 0;
     uint64_t s0 = 0;                              // samples consumed since create or reset
-    fsea_detail::DeviceArray<float> taps;         // the L taps as floats
-    fsea_detail::DeviceArray<cf> tail[2];         // L - 1 samples each: a launch reads tail[cur] and writes the other
-    int cur = 0;
+    FirState state;                               // the L taps as floats, two tails of L - 1 samples
     fsea_detail::SharedScratch frames;            // the frames of the last call; its event orders the calls
     std::mutex mu;
     fsea_detail::HostStaging staging;             // the host form
     fsea_detail::Owned<fsea_plan, fsea_plan_destroy> plan;   // (M, M, mode) on the frames; the first to go
-
-    size_t tail_len() const { return (size_t)channels * branch_taps - 1; }
 };
 
 namespace {
@@ -244,8 +237,8 @@ int queue_call(fsea_pfb *b, const void *d_iq, size_t n, int flip, void *d_rows, 
     const int M = b->channels, P = b->branch_taps, q = b->oversampling;
     const size_t F = out_frames(b, n), n_out = F * (size_t)M;
     if (n == 0) return FSEA_OK;
-    int rc = b->frames.buf.cap < n_out * sizeof(cf) + 16 ? b->frames.reserve(n_out * sizeof(cf) + 16) : FSEA_OK;
-    if (!rc) rc = b->frames.acquire(s);   // every call, on whatever stream, follows the previous user of the frames and the tails
+    // every call, on whatever stream, follows the previous user of the frames and the tails
+    int rc = b->frames.acquire(n_out * sizeof(cf) + 16, s);
     if (rc) return rc;
     cf *d_out = static_cast<cf *>(b->frames.buf.ptr);
     const PfbShape sh = pfb_shape(M, P, q);
@@ -254,10 +247,10 @@ int queue_call(fsea_pfb *b, const void *d_iq, size_t n, int flip, void *d_rows, 
     // no frame: one workgroup, the tail still advances
     const dim3 grid(F ? (unsigned)((F + sh.T - 1) / sh.T) : 1u, F ? (unsigned)((M + sh.C - 1) / sh.C) : 1u);
     hipLaunchKernelGGL(kernel, grid, dim3(PF_WG), 0, s, d_iq, (long long)n, flip ? 0x80808080u : 0u,
-                       (const cf *)b->tail[b->cur].ptr, b->tail[b->cur ^ 1].ptr, (const float *)b->taps.ptr, M, P, q, sh.C, sh.T,
+                       b->state.in(), b->state.out(), (const float *)b->state.taps.ptr, M, P, q, sh.C, sh.T,
                        (int)(b->s0 % (uint64_t)M), d_out);
     FSEA_HIP(hipGetLastError());
-    b->cur ^= 1;
+    b->state.advance();
     b->s0 += n;
     if (F) {
         rc = fsea_detail::launch(b->plan, fsea::IN_F32, d_out, F, 0, b->mode, d_rows, s);
@@ -295,9 +288,7 @@ int fsea_pfb_create(fsea_pfb **out, const double *taps, int channels, int branch
         return fail(FSEA_EINVAL, "oversampling must be 1, 2 or 4 and divide the %d channels, got %d", channels, oversampling);
     }
     const int L = channels * branch_taps;
-    for (int k = 0; k < L; ++k) {
-        if (!std::isfinite(taps[k])) return fail(FSEA_EINVAL, "tap %d is not finite", k);
-    }
+    if (int rc = FirState::check_finite(taps, L)) return rc;
     return fsea_detail::create_object(out, device, "fsea_pfb_create", [&](fsea_pfb *b) -> int {
         b->channels = channels;
         b->branch_taps = branch_taps;
@@ -305,10 +296,7 @@ int fsea_pfb_create(fsea_pfb **out, const double *taps, int channels, int branch
         b->mode = mode;
         int rc = fsea_plan_create(&b->plan.ptr, channels, channels, mode, device);   // the modes of any plan, and its statuses
         if (rc) return rc;
-        std::vector<float> tf((size_t)L);
-        for (int k = 0; k < L; ++k) tf[k] = (float)taps[k];
-        hipError_t e = b->taps.upload(tf.data(), tf.size());
-        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = b->tail[i].zeros(b->tail_len());
+        hipError_t e = b->state.create(taps, L, L, (size_t)L - 1);
         if (e == hipSuccess) e = b->frames.create(b->staging.stream);
         return fsea_detail::init_code("fsea_pfb_create", e);
     });
@@ -317,10 +305,9 @@ int fsea_pfb_create(fsea_pfb **out, const double *taps, int channels, int branch
 int fsea_pfb_destroy(fsea_pfb *b) { return fsea_detail::destroy_object(b); }
 
 int fsea_pfb_reset(fsea_pfb *b) {
-    return fsea_detail::reset_object(b, "pfb is NULL", [&]() -> int {
+    return fsea_detail::reset_object(b, "pfb is NULL", [&] {
         b->s0 = 0;
-        FSEA_HIP(b->tail[b->cur].zero(b->tail_len()));   // the current tail only: the other one is written whole by the next launch
-        return FSEA_OK;
+        return b->state.reset();
     });
 }
 
@@ -347,27 +334,14 @@ int fsea_pfb_run_host(fsea_pfb *b, const uint8_t *iq, size_t n_samples, int flip
     if (n_samples == 0) return FSEA_OK;
     std::lock_guard<std::mutex> lock(b->mu);
     FSEA_ON_DEVICE(b->device);
-    fsea_detail::HostStaging &g = b->staging;
     const size_t F = out_frames(b, n_samples), pairs_bytes = F * (size_t)b->channels * sizeof(cf);
-    const size_t in_bytes = 2 * n_samples;
-    const size_t rows_bytes = F * fsea_plan_row_bytes(b->plan);        // a multiple of 16 only by chance: pad what follows
-    const size_t rows_span = (rows_bytes + 15) & ~(size_t)15;
-    const size_t frames_bytes = frames ? pairs_bytes : 0, series_bytes = series ? pairs_bytes : 0;
-    rc = g.reserve(in_bytes, rows_span + frames_bytes + series_bytes);
-    if (rc) return rc;
-    std::memcpy(g.h_in.ptr, iq, in_bytes);
-    FSEA_HIP(hipMemcpyAsync(g.d_in.ptr, g.h_in.ptr, in_bytes, hipMemcpyHostToDevice, g.stream));
-    uint8_t *h = static_cast<uint8_t *>(g.h_out.ptr), *d = static_cast<uint8_t *>(g.d_out.ptr);
-    rc = queue_call(b, g.d_in.ptr, n_samples, flip, d, frames_bytes ? d + rows_span : nullptr,
-                    series_bytes ? d + rows_span + frames_bytes : nullptr, g.stream);
-    if (rc) return rc;
-    const size_t out_bytes = rows_span + frames_bytes + series_bytes;
-    if (F) FSEA_HIP(hipMemcpyAsync(h, d, out_bytes, hipMemcpyDeviceToHost, g.stream));
-    FSEA_HIP(hipStreamSynchronize(g.stream));
-    if (rows_bytes) std::memcpy(rows, h, rows_bytes);
-    if (frames_bytes) std::memcpy(frames, h + rows_span, frames_bytes);
-    if (series_bytes) std::memcpy(series, h + rows_span + frames_bytes, series_bytes);
-    return FSEA_OK;
+    const fsea_detail::HostStaging::Part parts[3] = {{rows, F * fsea_plan_row_bytes(b->plan)}, {frames, pairs_bytes},
+                                                     {series, pairs_bytes}};
+    return b->staging.run(
+        2 * n_samples, parts, [&](void *h_in) { std::memcpy(h_in, iq, 2 * n_samples); },
+        [&](void *d_in, void **d_parts, hipStream_t s) {
+            return queue_call(b, d_in, n_samples, flip, d_parts[0], d_parts[1], d_parts[2], s);
+        });
 }
 
 }  // extern "C"

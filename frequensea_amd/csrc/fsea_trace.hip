@@ -267,9 +267,8 @@ int frames_launch(fsea_trace *t, const uint8_t *d_bytes, size_t n_bytes, int fli
     const int cb = segments <= 255 ? 1 : 4;
     const size_t plane = (size_t)g.side * g.side * cb;
     const size_t chunk = std::min<size_t>({(size_t)n_frames, (size_t)TR_MAX_CHUNK, std::max<size_t>(1, TR_COUNT_BYTES / plane)});
-    int rc = t->counts.buf.cap < chunk * plane ? t->counts.reserve(chunk * plane) : FSEA_OK;
-    if (!rc) rc = t->counts.acquire(s);  // every use of the canvas and the planes, on whatever stream, follows the previous one
-    if (rc) return rc;
+    // every use of the canvas and the planes, on whatever stream, follows the previous one
+    if (int rc = t->counts.acquire(chunk * plane, s)) return rc;
     uint8_t *d_counts = static_cast<uint8_t *>(t->counts.buf.ptr);
     const size_t pixels = frame_pixels(t);
     const unsigned gx_hits = (unsigned)((segments + TR_WG - 1) / TR_WG);

@@ -166,8 +166,8 @@ int queue_call(fsea_zoom *z, const void *d_iq, size_t n, int flip, const FirRot 
     const int D = z->decimation, L = z->n_taps;
     const size_t n_out = n / (size_t)D, rows = out_rows(z, n);
     if (n == 0) return FSEA_OK;
-    int rc = z->pairs.buf.cap < n_out * sizeof(cf) + 16 ? z->pairs.reserve(n_out * sizeof(cf) + 16) : FSEA_OK;
-    if (!rc) rc = z->pairs.acquire(s);   // every call, on whatever stream, follows the previous user of the pairs and the tails
+    // every call, on whatever stream, follows the previous user of the pairs and the tails
+    int rc = z->pairs.acquire(n_out * sizeof(cf) + 16, s);
     if (rc) return rc;
     cf *d_out = static_cast<cf *>(z->pairs.buf.ptr);
     const unsigned grid = n_out ? (unsigned)((n_out + ZM_T - 1) / ZM_T) : 1u;   // no output: the tail still advances
@@ -207,7 +207,7 @@ int fsea_zoom_create(fsea_zoom **out, const double *taps, int n_taps, int decima
         for (int k = 0; k < n_taps; ++k) {
             offs[k] = (uint32_t)(((k % decimation) * zoom_pitch(decimation, n_taps) + k / decimation) * (int)sizeof(cf));
         }
-        hipError_t e = z->state.create(taps, n_taps, ZM_TAPS_ALLOC);
+        hipError_t e = z->state.create(taps, n_taps, ZM_TAPS_ALLOC, FSEA_FIR_MAX_TAPS);
         if (e == hipSuccess) e = z->d_offs.upload(offs, ZM_TAPS_ALLOC);
         if (e == hipSuccess) e = z->pairs.create(z->staging.stream);
         return fsea_detail::init_code("fsea_zoom_create", e);
@@ -253,22 +253,11 @@ int fsea_zoom_run_host(fsea_zoom *z, const uint8_t *iq, size_t n_samples, int fl
     const FirRot rot = make_rot(cycles_per_sample, phase0_cycles, sample_offset, n_samples);
     std::lock_guard<std::mutex> lock(z->mu);
     FSEA_ON_DEVICE(z->device);
-    fsea_detail::HostStaging &g = z->staging;
-    const size_t in_bytes = 2 * n_samples;
-    const size_t rows_bytes = out_rows(z, n_samples) * fsea_plan_row_bytes(z->plan);
-    const size_t pairs_bytes = pairs ? n_samples / (size_t)z->decimation * sizeof(cf) : 0;
-    rc = g.reserve(in_bytes, rows_bytes + pairs_bytes);
-    if (rc) return rc;
-    std::memcpy(g.h_in.ptr, iq, in_bytes);
-    FSEA_HIP(hipMemcpyAsync(g.d_in.ptr, g.h_in.ptr, in_bytes, hipMemcpyHostToDevice, g.stream));
-    uint8_t *h = static_cast<uint8_t *>(g.h_out.ptr), *d = static_cast<uint8_t *>(g.d_out.ptr);
-    rc = queue_call(z, g.d_in.ptr, n_samples, flip, rot, d, pairs_bytes ? d + rows_bytes : nullptr, g.stream);
-    if (rc) return rc;
-    if (rows_bytes + pairs_bytes) FSEA_HIP(hipMemcpyAsync(h, d, rows_bytes + pairs_bytes, hipMemcpyDeviceToHost, g.stream));
-    FSEA_HIP(hipStreamSynchronize(g.stream));
-    if (rows_bytes) std::memcpy(rows, h, rows_bytes);
-    if (pairs_bytes) std::memcpy(pairs, h + rows_bytes, pairs_bytes);
-    return FSEA_OK;
+    const fsea_detail::HostStaging::Part parts[2] = {{rows, out_rows(z, n_samples) * fsea_plan_row_bytes(z->plan)},
+                                                     {pairs, n_samples / (size_t)z->decimation * sizeof(cf)}};
+    return z->staging.run(
+        2 * n_samples, parts, [&](void *h_in) { std::memcpy(h_in, iq, 2 * n_samples); },
+        [&](void *d_in, void **d_parts, hipStream_t s) { return queue_call(z, d_in, n_samples, flip, rot, d_parts[0], d_parts[1], s); });
 }
 
 }  // extern "C"

@@ -36,6 +36,7 @@ def same(a, b):
 
 FIR_BYTES = 2 * (4096 + 3)        # two tiles and an edge
 ZOOM_BYTES = 2 * 4 * 256          # D = 4: 256 decimated pairs, two rows of 128
+PFB_BYTES = 2 * (32 * 40 + 5)     # M = 64 at oversampling 2, a frame every 32 samples: 40 frames and an edge
 DEMOD_SAMPLES = 1 << 14
 INTERP_N = 4096
 WEIGHTS = [0.0, 0.3, 1.0]
@@ -65,6 +66,14 @@ def make_zoom():
 
 def call_zoom(z, seed):
     return z.run(data(seed, ZOOM_BYTES), 0.0123, pairs=True)
+
+
+def make_pfb():
+    return fsea.Pfb(fsea.pfb_prototype(64, 16), 64, 2, fsea.MODE_COMPLEX_F32)   # L = 1024: a tail above FSEA_FIR_MAX_TAPS
+
+
+def call_pfb(b, seed):
+    return b.run(data(seed, PFB_BYTES), frames=True, series=True)
 
 
 def make_demod():
@@ -154,6 +163,7 @@ def call_plan(p, seed):
 OBJECTS = {
     "fir": (make_fir, call_fir),
     "zoom": (make_zoom, call_zoom),
+    "pfb": (make_pfb, call_pfb),
     "demod": (make_demod, call_demod),
     "interp": (make_interp, call_interp),
     "trace": (make_trace, call_trace),
@@ -181,7 +191,7 @@ def test_create_use_destroy_cycles_give_the_same_bits(kind):
         assert same(got, first), (kind, cycle)
 
 
-@pytest.mark.parametrize("kind", ["fir", "zoom", "demod", "interp", "trace"])
+@pytest.mark.parametrize("kind", ["fir", "zoom", "pfb", "chain", "demod", "interp", "trace"])
 def test_reset_equals_a_fresh_object(kind):
     make, call = OBJECTS[kind]
     used, fresh = make(), make()
@@ -205,6 +215,21 @@ def test_a_failed_zoom_create_leaves_nothing_half_made():
     z, ref = make_zoom(), make_zoom()
     assert same(call_zoom(z, 3), call_zoom(ref, 3))
     z.close()
+    ref.close()
+
+
+def test_a_failed_chain_create_leaves_nothing_half_made():
+    """A device index one past the last fails in the shared create sequence, after the taps are found good: the text is the
+    filter's for the same index, and a valid chain created right after it works."""
+    no_device = fsea.device_count()
+    with pytest.raises(fsea.FseaError) as chain_error:
+        fsea.Chain(taps(), device=no_device)
+    with pytest.raises(fsea.FseaError) as fir_error:
+        fsea.Fir(taps(), device=no_device)
+    assert str(chain_error.value) == str(fir_error.value)
+    c, ref = make_chain(), make_chain()
+    assert same(call_chain(c, 3), call_chain(ref, 3))
+    c.close()
     ref.close()
 
 

@@ -144,6 +144,15 @@ def test_rows_are_the_plans_rows_on_the_pairs(n_fft, hop_div, mode):
         print("N %d hop N/%d mode %d: max deviation %.3e (rows up to %.3e)" % (n_fft, hop_div, mode, dev.max(), want.max()))
 
 
+@pytest.mark.parametrize("n_fft,hop", [(50, 50), (6, 3)])
+def test_rows_of_a_byte_count_that_is_no_multiple_of_16_with_pairs(n_fft, hop):
+    """5 rows of 50 bytes and 10 rows of 6 bytes on Bluestein plans, the pairs asked for: the rows do not end at a 16-byte
+    boundary of the host form's staging, and the pairs that follow them come back from where they were put -- the rows
+    recomputed from pairs read at a wrong offset would differ (_rows_case's bit identity)."""
+    rows, _ = _rows_case(n_fft, hop, fsea.MODE_DB10_U8)
+    assert rows.dtype == np.uint8 and rows.nbytes % 16 != 0, rows.shape
+
+
 def test_rows_with_a_hann_window():
     rows, spectra = _rows_case(1024, 512, fsea.MODE_COMPLEX_F32, "hann")
     rel = float(np.linalg.norm(rows - spectra) / np.linalg.norm(spectra))
