@@ -27,6 +27,12 @@ ZOOM_MAX_DECIMATION = 64    # FSEA_ZOOM_MAX_DECIMATION
 ZOOM_TILE_OUTPUTS = 128     # FSEA_ZOOM_TILE_OUTPUTS: outputs per workgroup of fsea_shift_decim_u8
 PFB_MAX_CHANNELS = 16384    # FSEA_PFB_MAX_CHANNELS
 PFB_MAX_BRANCH_TAPS = 16    # FSEA_PFB_MAX_BRANCH_TAPS
+PERSIST_LEVELS = 256        # FSEA_PERSIST_LEVELS
+PERSIST_MAX_WIDTH = 65536   # FSEA_PERSIST_MAX_WIDTH
+PERSIST_RUN_ROWS = 1024     # FSEA_PERSIST_RUN_ROWS: rows per workgroup of fsea_persist_u8 / fsea_persist_f32
+PERSIST_U8, PERSIST_F32 = 0, 1                                       # FSEA_PERSIST_*: element type of a row
+PERSIST_MAP_SATURATE, PERSIST_MAP_LINEAR, PERSIST_MAP_LOG = 0, 1, 2  # FSEA_PERSIST_MAP_*
+PERSIST_TRACE_MAX, PERSIST_TRACE_MIN, PERSIST_TRACE_QUANTILE = 0, 1, 2   # FSEA_PERSIST_TRACE_*
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
@@ -152,6 +158,19 @@ API = {
     "fsea_pfb_row_bytes": (_sz, [_vp]),
     "fsea_pfb_run_device": (_ci, [_vp, _vp, _sz, _ci, _vp, _vp, _vp, _vp]),
     "fsea_pfb_run_host": (_ci, [_vp, _vp, _sz, _ci, _vp, _vp, _vp]),
+    "fsea_persist_create": (_ci, [_out, _ci, _ci]),
+    "fsea_persist_destroy": (_ci, [_vp]),
+    "fsea_persist_reset": (_ci, [_vp]),
+    "fsea_persist_set_range": (_ci, [_vp, ctypes.c_float, ctypes.c_float]),
+    "fsea_persist_width": (_ci, [_vp]),
+    "fsea_persist_rows": (_u64, [_vp]),
+    "fsea_persist_add_device": (_ci, [_vp, _vp, _ci, _sz, _sz, _vp]),
+    "fsea_persist_add_host": (_ci, [_vp, _vp, _ci, _sz, _sz]),
+    "fsea_persist_decay": (_ci, [_vp, _u32, _u32, _vp]),
+    "fsea_persist_counts_host": (_ci, [_vp, _vp]),
+    "fsea_persist_image_device": (_ci, [_vp, _ci, _u64, _vp, _vp]),
+    "fsea_persist_image_host": (_ci, [_vp, _ci, _u64, _vp]),
+    "fsea_persist_trace": (_ci, [_vp, _ci, _ci, _f64, _vp]),
     "fsea_iq_draw_create": (_ci, [_out, _ci]),
     "fsea_iq_draw_destroy": (_ci, [_vp]),
     "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
@@ -685,6 +704,73 @@ class Pfb(_ResettableHandle):
         as many frames of `channels` complex64 and the `channels` series out; asynchronous."""
         _check(self._L.fsea_pfb_run_device(self._p, d_iq_ptr, n_samples, int(bool(flip)), d_rows_ptr, d_frames_ptr,
                                            d_series_ptr, stream or None))
+
+
+def persist_trace(counts, kind, fraction=0.5):
+    """fsea_persist_trace (host arithmetic): one level per column of a (256, width) array of counts -- the highest
+    (PERSIST_TRACE_MAX) or lowest (PERSIST_TRACE_MIN) occupied level, or the level at which the cumulative count reaches
+    `fraction` of the column's total (PERSIST_TRACE_QUANTILE; 0.5: the median level)."""
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    if c.ndim != 2 or c.shape[0] != PERSIST_LEVELS:
+        raise ValueError("counts has shape (256, width)")
+    levels = np.empty(c.shape[1], dtype=np.uint8)
+    _check(hip_lib().fsea_persist_trace(c.ctypes.data, c.shape[1], int(kind), float(fraction), levels.ctypes.data))
+    return levels
+
+
+class Persist(_ResettableHandle):
+    """A persistence spectrum on one device: counts[level, column] over all the rows offered; thin wrapper over
+    fsea_persist_*.  add() takes a 2-D uint8 or float32 array from the host (any row stride), add_device() resident rows;
+    counts() and image() fetch the (256, width) counts and the (256, width) uint8 picture, strongest level on top."""
+    _kind = "persist"
+
+    def __init__(self, width, device=0):
+        self.device = device
+        self._create("fsea_persist_create", int(width), device)
+
+    @property
+    def width(self):
+        return self._L.fsea_persist_width(self._p)
+
+    @property
+    def rows(self):
+        return self._L.fsea_persist_rows(self._p)
+
+    def set_range(self, lo, hi):
+        _check(self._L.fsea_persist_set_range(self._p, lo, hi))
+
+    def add(self, rows):
+        a = np.asarray(rows)
+        if a.ndim != 2 or a.dtype not in (np.uint8, np.float32):
+            raise ValueError("rows is a 2-D uint8 or float32 array")
+        if a.shape[1] != self.width:
+            raise ValueError("a row has `width` elements")
+        if a.strides[1] != a.itemsize or (a.shape[0] > 1 and (a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize)):
+            a = np.ascontiguousarray(a)     # only rows of contiguous elements a whole number of elements apart go as they are
+        pitch = a.strides[0] // a.itemsize if a.shape[0] > 1 else a.shape[1]
+        _check(self._L.fsea_persist_add_host(self._p, a.ctypes.data, PERSIST_U8 if a.dtype == np.uint8 else PERSIST_F32,
+                                             a.shape[0], pitch))
+
+    def add_device(self, d_rows_ptr, type, n_rows, pitch=None, stream=0):
+        """d_rows_ptr (an int, 16-byte aligned): n_rows rows of `width` elements, `pitch` elements apart; asynchronous."""
+        _check(self._L.fsea_persist_add_device(self._p, d_rows_ptr, int(type), n_rows, self.width if pitch is None else pitch,
+                                               stream or None))
+
+    def decay(self, numerator, denominator, stream=0):
+        _check(self._L.fsea_persist_decay(self._p, numerator, denominator, stream or None))
+
+    def counts(self):
+        out = np.empty((PERSIST_LEVELS, self.width), dtype=np.uint32)
+        _check(self._L.fsea_persist_counts_host(self._p, out.ctypes.data))
+        return out
+
+    def image(self, map=PERSIST_MAP_LOG, full=0):
+        out = np.empty((PERSIST_LEVELS, self.width), dtype=np.uint8)
+        _check(self._L.fsea_persist_image_host(self._p, int(map), int(full), out.ctypes.data))
+        return out
+
+    def image_device(self, d_image_ptr, map=PERSIST_MAP_LOG, full=0, stream=0):
+        _check(self._L.fsea_persist_image_device(self._p, int(map), int(full), d_image_ptr, stream or None))
 
 
 class Demod(_ResettableHandle):

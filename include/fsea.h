@@ -32,6 +32,7 @@
  *   fsea_chain_*          shift -> filter -> images per block with the filtered block resident on the device
  *   fsea_zoom_*           shift -> decimating filter -> FFT: a spectrum of 1 / D of the bandwidth (nrf_decoder's chain)
  *   fsea_pfb_*            a polyphase filter bank (no counterpart in the reference): all M channels of the band at once
+ *   fsea_persist_*        a persistence spectrum (no counterpart in the reference): per-bin level histograms of resident rows
  *   fsea_detect_*         the burst detector of lua/signal-detector.lua: the two loops of nrf_signal_detector_process,
  *                         src/nrf.c:883-898, as integer sums over many blocks per launch
  *   fsea_capture_*        that scene on a resident recording: detect -> gate -> filter the bursts -> line images
@@ -63,6 +64,7 @@ typedef struct fsea_iq_draw fsea_iq_draw;
 typedef struct fsea_chain fsea_chain;
 typedef struct fsea_zoom fsea_zoom;
 typedef struct fsea_pfb fsea_pfb;
+typedef struct fsea_persist fsea_persist;
 typedef struct fsea_demod fsea_demod;
 typedef struct fsea_interp fsea_interp;
 typedef struct fsea_trace fsea_trace;
@@ -563,6 +565,59 @@ int fsea_pfb_run_device(fsea_pfb *pfb, const void *d_iq, size_t n_samples, int f
                         void *d_series, void *stream);
 int fsea_pfb_run_host(fsea_pfb *pfb, const uint8_t *iq, size_t n_samples, int flip, void *rows, float *frames,
                       float *series);
+
+/* The persistence spectrum: how often was bin k at level l over all the rows offered -- what an analyser's persistence
+ * display shows: the noise floor, the max-hold envelope and short bursts in one picture.  The frequency-domain twin of the
+ * IQ constellation image; it consumes rows that are already resident (the FSEA_MODE_DB10_U8 / FSEA_MODE_DB5_U8_DCFIX /
+ * FSEA_MODE_DB_F32 output of fsea_plan, fsea_zoom, fsea_pfb).  Integer and order-free: the counts are the same bits
+ * however the rows are cut into calls.  The object owns counts[l * width + k], 256 x width uint32_t, level-major, zero after
+ * create and reset; `rows`, the rows offered so far; and the f32 range (lo, hi), (-100, 0) after create, with
+ * scale = (float)(256.0 / ((double)hi - (double)lo)).
+ *   add:    row r starts pitch elements behind row r - 1, pitch >= width; a sub-band of wider rows is d_rows + offset with
+ *           the wide pitch.  For each of the n_rows * width elements counts[level(v)][k] += 1.  U8: level = v.  F32:
+ *           t = (v - lo) * scale in two rounded f32 operations (no fused multiply-add); a NaN is not counted, t < 0 gives 0,
+ *           t >= 256 gives 255, otherwise (int)t.  Then rows += n_rows; a call that would take rows above 2^32 - 1 is
+ *           refused, so no count can wrap.  n_rows == 0 is a successful no-op.  add_device: only the base pointer is
+ *           aligned (16 bytes); asynchronous on `stream`; calls on different streams follow one another (an event).  Rows
+ *           whose pitch is a multiple of 16 bytes are read 16 bytes per lane, others element by element.  add_host stages
+ *           through pinned memory on the object's own stream and returns when the counts are in place.
+ *           Kernels fsea_persist_u8 / fsea_persist_f32: a workgroup of 256 lanes counts a tile of 64 columns over a run of
+ *           FSEA_PERSIST_RUN_ROWS rows into a 256 x 64 u32 histogram in LDS, then adds its non-zero counters to the counts.
+ *   decay:  c <- floor(c * numerator / denominator) in 64-bit integers for every count, and for rows: the phosphor of a
+ *           running display.  1 <= denominator, numerator <= denominator.  Asynchronous on `stream`.
+ *   counts_host: the 256 * width counts, behind every add queued so far.
+ *   image:  256 x width uint8_t, image[(255 - l) * width + k]: the strongest level is the top row.  full == 0 means rows; if
+ *           that is 0 too the image is zero.  SATURATE: min(c, 255).  LINEAR: min(255, floor(c * 255 / full)).  LOG, integer
+ *           and monotone: q(0) = 0 and for c >= 1, e = floor(log2 c), m = ((c << 8) >> e) & 255, q(c) = 256 e + m + 1; the
+ *           pixel is 0 for c = 0, else min(255, 1 + floor((q(c) - 1) * 254 / max(1, q(full) - 1))): a single hit stays
+ *           visible.  image_device: d_image 16-byte aligned, asynchronous on `stream`.
+ *   trace:  host arithmetic on fetched counts, no device.  MAX / MIN: the highest / lowest level with a non-zero count, 0
+ *           for an empty column.  QUANTILE: the smallest l whose cumulative count reaches
+ *           max(1, (uint64_t)ceil(fraction * total_k)); 0.5 is the median level, the per-bin noise floor.
+ * Every check runs before any device work: FSEA_EINVAL for a NULL object or buffer, a width outside
+ * [1, FSEA_PERSIST_MAX_WIDTH], an unknown type, map or kind, pitch < width, n_rows > 2^31, a misaligned device pointer, a
+ * range that is not finite with lo < hi (or too narrow for a finite scale), a bad decay ratio, a fraction outside [0, 1].
+ * Create: FSEA_ENODEVICE without a GPU.  width and rows return 0 for NULL.  Destroy and reset wait for the device; reset
+ * zeroes counts and rows and keeps the range.  Calls on one object from several threads are serialised. */
+#define FSEA_PERSIST_LEVELS 256
+#define FSEA_PERSIST_MAX_WIDTH 65536
+#define FSEA_PERSIST_RUN_ROWS 1024   /* rows a workgroup of the add kernels counts before it adds its histogram to the counts */
+enum { FSEA_PERSIST_U8 = 0, FSEA_PERSIST_F32 = 1 };                       /* element type of a row */
+enum { FSEA_PERSIST_MAP_SATURATE = 0, FSEA_PERSIST_MAP_LINEAR = 1, FSEA_PERSIST_MAP_LOG = 2 };
+enum { FSEA_PERSIST_TRACE_MAX = 0, FSEA_PERSIST_TRACE_MIN = 1, FSEA_PERSIST_TRACE_QUANTILE = 2 };
+int fsea_persist_create(fsea_persist **persist, int width, int device);
+int fsea_persist_destroy(fsea_persist *persist);
+int fsea_persist_reset(fsea_persist *persist);
+int fsea_persist_set_range(fsea_persist *persist, float lo, float hi);
+int fsea_persist_width(const fsea_persist *persist);
+uint64_t fsea_persist_rows(const fsea_persist *persist);
+int fsea_persist_add_device(fsea_persist *persist, const void *d_rows, int type, size_t n_rows, size_t pitch, void *stream);
+int fsea_persist_add_host(fsea_persist *persist, const void *rows, int type, size_t n_rows, size_t pitch);
+int fsea_persist_decay(fsea_persist *persist, uint32_t numerator, uint32_t denominator, void *stream);
+int fsea_persist_counts_host(fsea_persist *persist, uint32_t *counts);
+int fsea_persist_image_device(fsea_persist *persist, int map, uint64_t full, uint8_t *d_image, void *stream);
+int fsea_persist_image_host(fsea_persist *persist, int map, uint64_t full, uint8_t *image);
+int fsea_persist_trace(const uint32_t *counts, int width, int kind, double fraction, uint8_t *levels);
 
 /* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
  * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With

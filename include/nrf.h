@@ -401,6 +401,42 @@ void nrf_pfb_fft_process(nrf_pfb_fft *pfb, nut_buffer *samples);
 nut_buffer *nrf_pfb_fft_get_buffer(nrf_pfb_fft *pfb);
 void nrf_pfb_fft_free(nrf_pfb_fft *pfb);
 
+/* ---- ADDITIONS (not in the reference): the persistence spectrum ---- */
+
+/* An analyser's persistence display of the device's band (fsea_persist_*, include/fsea.h): how often each of the fft_size
+ * bins was at each of 256 levels over all the blocks processed.
+ *   - process takes a U8 buffer with 2 channels.  All (length - fft_size) / hop + 1 frames of the block go through a
+ *     FSEA_MODE_DB5_U8_DCFIX plan on the device and from there into the object: the block goes up once, no row comes back.
+ *     A block shorter than fft_size adds nothing.
+ *   - set_window takes the names of nrf_fft_set_window.  set_decay(numerator, denominator): every count is scaled by
+ *     numerator / denominator (rounded down) before each block, the phosphor of a running display; none by default.
+ *   - get_buffer is the picture under the map given at new (FSEA_PERSIST_MAP_*; full scale = the rows counted): a U8 buffer of
+ *     256 * fft_size elements, one channel, the strongest level in the first row -- what
+ *     ngl_texture_update(texture, buffer, fft_size, 256) takes.  The buffer returned is the caller's to free.
+ * An F64 buffer, an fft_size outside [1, FSEA_PERSIST_MAX_WIDTH] or without a plan, a hop below 1, an unknown map or window
+ * name, a decay ratio above 1 or with a zero denominator, and a backend failure (no GPU) print
+ * "NRF PERSISTENCE fatal error: ..." and exit. */
+typedef struct {
+    NRF_BLOCK;
+    int fft_size;
+    int hop;
+    int map;                  /* FSEA_PERSIST_MAP_* */
+    unsigned decay_numerator, decay_denominator;
+    int device;
+    void *plan;               /* fsea_plan* (libfsea_hip.so): (fft_size, hop, FSEA_MODE_DB5_U8_DCFIX) */
+    void *backend;            /* fsea_persist* */
+    void *d_iq, *d_rows;      /* device memory: the block, its rows */
+    size_t iq_cap, rows_cap;
+    pthread_mutex_t mutex;
+} nrf_persistence;
+
+nrf_persistence *nrf_persistence_new(int fft_size, int hop, int map);
+void nrf_persistence_set_window(nrf_persistence *p, const char *name);
+void nrf_persistence_set_decay(nrf_persistence *p, unsigned numerator, unsigned denominator);
+void nrf_persistence_process(nrf_persistence *p, nut_buffer *buffer);
+nut_buffer *nrf_persistence_get_buffer(nrf_persistence *p);
+void nrf_persistence_free(nrf_persistence *p);
+
 /* ---- ADDITIONS (not in the reference): the signal capture ---- */
 
 /* The reference's signal scene (lua/signal-detector.lua:89-133) over a whole recording that stays on the GPU: the detector
