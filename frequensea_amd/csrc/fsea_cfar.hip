@@ -1,0 +1,488 @@
+// fsea_cfar.hip -- the CFAR spectrum detector (include/fsea.h: fsea_cfar_*): which cells of a dB row stand above the mean
+// level of their neighbours, per-column hit counts over all the rows offered (the occupancy), and the bands of occupied
+// columns.  Integer and order-free like the persistence spectrum (fsea_persist.hip): every mask byte, row count and hit
+// count is the same whatever the launch geometry or the cut of the rows into calls.
+//
+// Kernels fsea_cfar_u8 / fsea_cfar_f32 (and their _narrow forms; DESIGN.md section 4, "The CFAR detector"): a workgroup of
+// 256 lanes owns a tile of FSEA_CFAR_TILE_COLUMNS = 1024 columns and a run of FSEA_CFAR_RUN_ROWS = 64 rows; each of its four
+// waves takes every fourth row of the run.  Per row a wave
+//   1. stages the segment [a0, e1) of the row: the tile plus a halo of G + T cells each side, clipped at the row's ends, a0
+//      rounded down to a multiple of 16 cells.  A lane loads 16 bytes (16 u8 or 4 f32 cells), turns them into levels, scans
+//      them, the wave scans the lanes' totals (six __shfl_up steps) and a carry joins the chunks of 64 lanes.  The inclusive
+//      prefix sums go to LDS as u32, q[FRONT + c - a0] for cell c, behind FRONT zero dwords (the cells before the row and the
+//      cell before the segment); cells past the row's end have level 0, so the prefix stays constant there.  The tile's own
+//      levels go to x[c - c0].
+//   2. decides its 1024 cells in 16 steps of 64 consecutive columns: lane l takes column c0 + 64 j + l at step j.  A side sum
+//      is the difference of two prefix values, so the cost per cell does not depend on T: four prefix reads at the fixed
+//      offsets -G-T-1, -G-1, +G, +G+T from k (never clamped: the zeroes in front and the constant tail clip a window at the
+//      row's ends) and one level read, every one 64 consecutive dwords across the wave -- 32 lanes of a bank group on 32
+//      banks whatever G and T are.
+//   3. the 64 decisions of a step are one ballot: its population count is the step's share of the row's hits, the lane keeps
+//      its own bit in a register counter of column 64 j + l (the same 16 columns over all rows of the run), and lane m keeps
+//      the 16 bits of columns 16 m .. 16 m + 15, which it spreads into 16 mask bytes and stores at once.
+// At the end of the run the four waves add their column counters in LDS and the workgroup issues one u32 global atomic per
+// non-zero column; a row's hits are one atomic per row and tile on row_hits, which the launch zeroes first.  The prefix and
+// level arrays are a wave's own, so the four waves meet only at the kernel's first and last barrier, and a wave loads the
+// 16-byte groups of its next row before it decides the current one.
+//
+// The prefix sums are u32 and wrap: an f32 level is in [-2^20, 2^20], so a prefix value may be "negative" (two's complement)
+// or, over a long row, pass 2^32.  A side sum has at most 256 terms, |S| <= 2^28, and the difference of two u32 prefix values
+// is that sum modulo 2^32, hence exact once read as an int32_t.  (Here the prefix restarts at every segment of at most 1680
+// cells, so it stays below 2^31 in size; nothing depends on that.)
+//
+// The _narrow kernels are the same code with every cell loaded on its own (any pitch and base).  In the 16-byte kernels a
+// group that would end past the row's width is loaded cell by cell too, so no load passes the width; the mask is written 16
+// bytes per lane where the width is a multiple of 16 and byte by byte otherwise.
+#include "fsea_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <type_traits>
+
+using fsea_detail::DeviceGuard;
+using fsea_detail::fail;
+
+namespace {
+
+constexpr int CF_WG = 256;                        // lanes per workgroup
+constexpr int CF_WAVES = CF_WG / 64;
+constexpr int CF_C = FSEA_CFAR_TILE_COLUMNS;      // columns per tile
+constexpr int CF_RUN = FSEA_CFAR_RUN_ROWS;        // rows per workgroup
+constexpr int CF_HALO = FSEA_CFAR_MAX_GUARD + FSEA_CFAR_MAX_TRAIN;
+constexpr int CF_SEG = CF_C + 2 * CF_HALO + 16;   // cells of a staged segment at most (a0 is rounded down by up to 15)
+constexpr int CF_FRONT = (CF_HALO + 1 + 15) & ~15;   // zero dwords in front of a wave's prefix array: the cells before the row
+constexpr int CF_Q = CF_FRONT + CF_SEG;           // dwords of a wave's prefix array
+constexpr int CF_LIMIT = 1 << 20;                 // |level| of an f32 cell at most
+constexpr size_t CF_MAX_ROWS = (size_t)1 << 31;   // rows of one call
+constexpr size_t CF_STAGE_BYTES = (size_t)64 << 20;   // the host form's chunk
+static_assert(CF_SEG % 16 == 0, "whole 16-byte groups");
+static_assert(CF_C == 16 * 64, "a wave decides a row of the tile in 16 steps; a lane stores 16 mask bytes");
+static_assert(CF_RUN % CF_WAVES == 0 && CF_RUN / CF_WAVES <= 255, "a run is whole iterations of the four waves; a lane counts a column in a byte");
+static_assert((CF_WAVES * (CF_Q + CF_C) + CF_C) * 4 <= 80 * 1024, "two workgroups per CU");
+static_assert(FSEA_CFAR_F32_SCALE == 64 && FSEA_CFAR_MAX_OFFSET == CF_LIMIT, "the 32-bit bounds of the decision");
+
+struct Settings {
+    int guard, train, offset, method;
+};
+
+// level of an f32 element: one rounded multiplication, round half to even; the clamp for a NaN
+__device__ __forceinline__ int level_f32(float v) {
+    const float t = __fmul_rn(v, (float)FSEA_CFAR_F32_SCALE);
+    if (t != t || t <= (float)-CF_LIMIT) return -CF_LIMIT;
+    if (t >= (float)CF_LIMIT) return CF_LIMIT;
+    return (int)rintf(t);
+}
+
+template <bool F32>
+__device__ __forceinline__ int level_at(const void *__restrict__ rows, size_t i) {
+    if (F32) return level_f32(static_cast<const float *>(rows)[i]);
+    return (int)static_cast<const uint8_t *>(rows)[i];
+}
+
+// Whether the group that starts at `cell` is read with one 16-byte load: the kernel may (VEC), the group starts inside the
+// segment and ends inside the width.
+template <bool VEC, int EPG>
+__device__ __forceinline__ bool whole_group(int cell, int end, int width) {
+    return VEC && cell < end && cell + EPG <= width;
+}
+
+// The EPG levels of the group that starts at cell `cell` of the row at element offset `at`: from `w`, its 16 bytes loaded
+// ahead, where whole_group() holds; cell by cell below `end` otherwise; 0 for what is not loaded.
+template <bool F32, bool VEC, int EPG>
+__device__ __forceinline__ void levels_of(const void *__restrict__ rows, size_t at, int cell, int end, int width, bool live,
+                                          uint4 w, int (&lv)[EPG]) {
+    if (whole_group<VEC, EPG>(cell, end, width)) {
+        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int e = 0; e < EPG; ++e) {
+            if (F32) lv[e] = live ? level_f32(__uint_as_float(ws[e & 3])) : 0;
+            else lv[e] = (int)((ws[e >> 2] >> (8 * (e & 3))) & 0xffu);
+        }
+        return;
+    }
+#pragma unroll
+    for (int e = 0; e < EPG; ++e) lv[e] = live && cell + e < end ? level_at<F32>(rows, at + cell + e) : 0;
+}
+
+// bits 0..3 of n to the bytes of a word, 255 for a set bit: the four shifted copies of n do not overlap
+__device__ __forceinline__ uint32_t spread4(uint32_t n) { return (((n & 15u) * 0x00204081u) & 0x01010101u) * 255u; }
+
+template <bool F32, bool VEC>
+__device__ __forceinline__ void cfar_body(const void *__restrict__ rows, size_t n_rows, size_t pitch, int width, Settings st,
+                                          uint8_t *__restrict__ mask, int mask_vec, uint32_t *__restrict__ row_hits,
+                                          uint32_t *__restrict__ hits) {
+    constexpr int EPG = F32 ? 4 : 16;             // elements per 16-byte group
+    __shared__ __attribute__((aligned(16))) uint32_t q_all[CF_WAVES][CF_Q];
+    __shared__ __attribute__((aligned(16))) int32_t x_all[CF_WAVES][CF_C];
+    __shared__ uint32_t total[CF_C];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t *q = q_all[wave];
+    int32_t *x = x_all[wave];
+    const int c0 = (int)blockIdx.y * CF_C;
+    const int G = st.guard, T = st.train;
+    const int a0 = max(0, c0 - G - T) & ~15;                   // the segment [a0, e1) of the row ...
+    const int e1 = min(width, c0 + CF_C + G + T);
+    const int ngrp = (c0 + CF_C + G + T - a0 + EPG - 1) / EPG; // ... and the groups up to the last cell a window may name
+    const bool inner = c0 - G - T >= 0 && c0 + CF_C + G + T <= width;
+    const size_t row0 = (size_t)blockIdx.x * CF_RUN;
+    const size_t left = n_rows - row0;
+    const int run = left < (size_t)CF_RUN ? (int)left : CF_RUN;
+
+    for (int i = tid; i < CF_C; i += CF_WG) total[i] = 0u;
+    for (int i = lane; i < CF_FRONT; i += 64) q[i] = 0u;       // the cells before the row and before the segment
+    uint32_t cnt[4] = {0u, 0u, 0u, 0u};                        // the lane's 16 columns, a byte each: at most CF_RUN / 4 hits
+    __syncthreads();
+
+    // the 16-byte groups of a row are loaded one row ahead: raw[c] is the lane's group of chunk c (zero where there is none)
+    constexpr int NCH = (CF_SEG / EPG + 63) / 64;
+    uint4 raw[NCH];
+    auto fetch = [&](int rr, int zero) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int cell = a0 + (c * 64 + lane + zero) * EPG;
+            raw[c] = uint4{0u, 0u, 0u, 0u};
+            if (rr < run && whole_group<VEC, EPG>(cell, e1, width)) {
+                raw[c] = *reinterpret_cast<const uint4 *>(static_cast<const char *>(rows) +
+                                                          ((row0 + rr) * pitch + cell) * (F32 ? 4 : 1));
+            }
+        }
+    };
+    fetch(wave, 0);
+
+    // The waves do not wait for one another: q and x are a wave's own, an LDS instruction of a wave is carried out after the
+    // ones it issued before, and wave_sync() keeps the compiler from moving an access across it.
+    auto wave_sync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+
+    for (int it = 0; it < (run + CF_WAVES - 1) / CF_WAVES; ++it) {
+        const int rr = it * CF_WAVES + wave;
+        const bool live = rr < run;
+        const size_t row = row0 + (live ? rr : 0);
+        // 0, behind an asm the compiler cannot see through: what depends on the lane and the column alone (which groups are
+        // whole, which lie in the tile, the windows' counts at the row's ends, the step that holds the lane's mask bits)
+        // is worked out again in every row.  Hoisted out of the row loop for all chunks and all 16 steps at once it costs
+        // more registers than the kernel has.
+        int zero;
+        asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+
+        // 1. the segment's levels and their inclusive prefix sums
+        uint32_t carry = 0u;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            if (c * 64 >= ngrp) break;
+            const int g = c * 64 + lane + zero;
+            const int cell = a0 + g * EPG;
+            int lv[EPG];
+            levels_of<F32, VEC, EPG>(rows, row * pitch, cell, e1, width, live, raw[c], lv);
+            uint32_t p[EPG], s = 0u;
+#pragma unroll
+            for (int e = 0; e < EPG; ++e) {
+                s += (uint32_t)lv[e];
+                p[e] = s;
+            }
+            uint32_t t = s;                                    // the wave's inclusive scan of the lanes' totals
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t up = __shfl_up(t, d);
+                t += up & (uint32_t)((d - 1 - lane) >> 31);    // lanes d and up; a mask in a register, not a saved exec
+            }
+            const uint32_t base = carry + t - s;
+            carry += __shfl(t, 63);
+            if (g < ngrp) {
+                uint4 *dst = reinterpret_cast<uint4 *>(q + CF_FRONT + g * EPG);
+#pragma unroll
+                for (int e = 0; e < EPG; e += 4) dst[e >> 2] = uint4{p[e] + base, p[e + 1] + base, p[e + 2] + base, p[e + 3] + base};
+                if (cell >= c0 && cell < c0 + CF_C) {          // a0 and c0 are multiples of 16: a group is inside or outside
+                    int4 *xd = reinterpret_cast<int4 *>(x + (cell - c0));
+#pragma unroll
+                    for (int e = 0; e < EPG; e += 4) xd[e >> 2] = int4{lv[e], lv[e + 1], lv[e + 2], lv[e + 3]};
+                }
+            }
+        }
+        fetch(rr + CF_WAVES, zero);                            // the next row's loads fly while this one is decided
+        wave_sync();
+
+        // 2. the decisions: column c0 + 64 j + lane at step j
+        // No index is clamped: the zeroes in front of the segment and the constant prefix behind the row's end make a
+        // clipped window's difference the clipped sum, so the four streams are qk + a fixed offset + 64 j.
+        const uint32_t *qk = q + CF_FRONT + (c0 - a0) + lane;  // qk[i]: the prefix value of cell c0 + lane + i
+        uint32_t mybits = 0u, rh = 0u;
+        // A tile whose windows all lie inside the row (`inner`) has nL = nR = T everywhere; in the other tiles the counts
+        // depend on the column (with `zero`: see the head of the loop).
+        const int is_ca = -(int)(st.method == FSEA_CFAR_CA), is_go = -(int)(st.method == FSEA_CFAR_GO), is_so = ~(is_ca | is_go);
+        auto decide = [&](auto edge) {
+            constexpr bool EDGE = decltype(edge)::value;
+            const int own = (lane >> 2) + zero;                // the step whose ballot holds the lane's 16 mask bits
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int kk = 64 * j + lane, k = c0 + kk + (EDGE ? zero : 0);
+                const int xl = x[kk];
+                const int nL = EDGE ? min(max(k - G, 0), T) : T, nR = EDGE ? min(max(width - 1 - k - G, 0), T) : T;
+                const int SL = (int)(qk[64 * j - G - 1] - qk[64 * j - G - T - 1]);   // exact: the u32 difference is the sum
+                const int SR = (int)(qk[64 * j + G + T] - qk[64 * j + G]);           // modulo 2^32, and |sum| <= 2^28
+                const int dL = xl * nL - SL - st.offset * nL, dR = xl * nR - SR - st.offset * nR;   // 0 for an empty side
+                // GO: an empty side (d = 0) stands back for the other; both empty: 0, no hit
+                const int gL = EDGE && nL == 0 ? dR : dL, gR = EDGE && nR == 0 ? dL : dR;
+                const int v = ((dL + dR) & is_ca) | (min(gL, gR) & is_go) | (max(dL, dR) & is_so);   // one code path for the three
+                bool hit = v > 0;
+                hit = hit && live && (!EDGE || k < width);
+                if (mask && !mask_vec && live && (!EDGE || k < width)) mask[row * (size_t)width + k] = hit ? 255 : 0;
+                const unsigned long long b = __ballot(hit);
+                rh += (uint32_t)__popcll(b);
+                cnt[j >> 2] += (hit ? 1u : 0u) << (8 * (j & 3));
+                if (own == j) mybits = (uint32_t)(b >> (16 * (lane & 3))) & 0xffffu;
+            }
+        };
+        if (inner) decide(std::false_type{});
+        else decide(std::true_type{});
+        if (live) {
+            const int col = c0 + 16 * lane;
+            if (mask && mask_vec && col < width) {             // width is a multiple of 16: the group is inside
+                *reinterpret_cast<uint4 *>(mask + row * (size_t)width + col) =
+                    uint4{spread4(mybits), spread4(mybits >> 4), spread4(mybits >> 8), spread4(mybits >> 12)};
+            }
+            if (row_hits && lane == 0 && rh) atomicAdd(&row_hits[row], rh);
+        }
+        wave_sync();                                           // before the next row overwrites q and x
+    }
+
+    // 3. the run's column hits: the four waves in LDS, then one global atomic per non-zero column
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const uint32_t n = (cnt[j >> 2] >> (8 * (j & 3))) & 0xffu;
+        if (n) atomicAdd(&total[64 * j + lane], n);
+    }
+    __syncthreads();
+    for (int i = tid; i < CF_C; i += CF_WG) {
+        const uint32_t v = total[i];
+        if (v && c0 + i < width) atomicAdd(&hits[c0 + i], v);
+    }
+}
+
+}  // namespace
+
+#define FSEA_CFAR_KERNEL(name, F32, VEC)                                                                                       \
+    extern "C" __global__ __launch_bounds__(CF_WG, 3) void name(const void *__restrict__ rows, size_t n_rows, size_t pitch,      \
+                                                              int width, int guard, int train, int offset, int method,        \
+                                                              uint8_t *__restrict__ mask, int mask_vec,                        \
+                                                              uint32_t *__restrict__ row_hits, uint32_t *__restrict__ hits) { \
+        cfar_body<F32, VEC>(rows, n_rows, pitch, width, Settings{guard, train, offset, method}, mask, mask_vec, row_hits,     \
+                            hits);                                                                                             \
+    }
+FSEA_CFAR_KERNEL(fsea_cfar_u8, false, true)
+FSEA_CFAR_KERNEL(fsea_cfar_f32, true, true)
+FSEA_CFAR_KERNEL(fsea_cfar_u8_narrow, false, false)
+FSEA_CFAR_KERNEL(fsea_cfar_f32_narrow, true, false)
+#undef FSEA_CFAR_KERNEL
+
+// `width` and `rows` lead the struct: tests/test_cfar_host.py reaches the checks that read them with a fake object
+struct fsea_cfar {
+    int width = 0;
+    int device = 0;
+    uint64_t rows = 0;                            // rows offered since create or reset
+    Settings set{2, 16, 60, FSEA_CFAR_CA};
+    fsea_detail::SharedScratch hits;              // width u32; its event orders the calls
+    std::mutex mu;
+    fsea_detail::HostStaging staging;             // the host forms
+};
+
+namespace {
+
+size_t elem_bytes(int type) { return type == FSEA_CFAR_F32 ? 4 : 1; }
+
+int check_add(const fsea_cfar *c, const void *rows, int type, size_t n_rows, size_t pitch) {
+    if (!c) return fail(FSEA_EINVAL, "cfar is NULL");
+    if (type != FSEA_CFAR_U8 && type != FSEA_CFAR_F32) return fail(FSEA_EINVAL, "unknown row type %d", type);
+    if (n_rows > CF_MAX_ROWS) return fail(FSEA_EINVAL, "n_rows %zu is more than 2^31", n_rows);
+    if (n_rows == 0) return FSEA_OK;
+    if (!rows) return fail(FSEA_EINVAL, "NULL buffer for the %zu rows of the call", n_rows);
+    if (pitch < (size_t)c->width) return fail(FSEA_EINVAL, "pitch %zu is below the width %d", pitch, c->width);
+    if (pitch > ((size_t)1 << 40) / n_rows) return fail(FSEA_EINVAL, "pitch %zu x n_rows %zu is too large", pitch, n_rows);
+    return FSEA_OK;
+}
+
+// the caller holds c->mu
+int check_room(const fsea_cfar *c, size_t n_rows) {
+    if (c->rows + n_rows > 0xffffffffull) {
+        return fail(FSEA_EINVAL, "n_rows %zu would take rows past 2^32 - 1 (%llu so far)", n_rows, (unsigned long long)c->rows);
+    }
+    return FSEA_OK;
+}
+
+// One add on device rows, asynchronous on `s`.  The caller holds c->mu, is on c's device and has checked the arguments.
+int add_launch(fsea_cfar *c, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask, uint32_t *d_row_hits,
+               hipStream_t s) {
+    int rc = c->hits.acquire(s);
+    if (rc) return rc;
+    uint32_t *hits = static_cast<uint32_t *>(c->hits.buf.ptr);
+    const int width = c->width;
+    if (d_row_hits) FSEA_HIP(hipMemsetAsync(d_row_hits, 0, n_rows * sizeof(uint32_t), s));   // set, not added to
+    const dim3 grid((unsigned)((n_rows + CF_RUN - 1) / CF_RUN), (unsigned)((width + CF_C - 1) / CF_C));
+    const size_t esz = elem_bytes(type);
+    const bool vec = ((uintptr_t)d_rows & 15) == 0 && (pitch * esz) % 16 == 0;
+    const int mask_vec = width % 16 == 0;
+    const Settings st = c->set;
+    auto kernel = type == FSEA_CFAR_U8 ? (vec ? fsea_cfar_u8 : fsea_cfar_u8_narrow) : (vec ? fsea_cfar_f32 : fsea_cfar_f32_narrow);
+    hipLaunchKernelGGL(kernel, grid, dim3(CF_WG), 0, s, d_rows, n_rows, pitch, width, st.guard, st.train, st.offset, st.method,
+                       d_mask, mask_vec, d_row_hits, hits);
+    FSEA_HIP(hipGetLastError());
+    c->rows += n_rows;
+    return c->hits.release(s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fsea_cfar_create(fsea_cfar **out, int width, int device) {
+    if (!out) return fail(FSEA_EINVAL, "cfar out-pointer is NULL");
+    *out = nullptr;
+    if (width < 1 || width > FSEA_CFAR_MAX_WIDTH) {
+        return fail(FSEA_EINVAL, "width must be in [1, %d], got %d", FSEA_CFAR_MAX_WIDTH, width);
+    }
+    return fsea_detail::create_object(out, device, "fsea_cfar_create", [&](fsea_cfar *c) -> int {
+        c->width = width;
+        const size_t bytes = (size_t)width * sizeof(uint32_t);
+        hipError_t e = c->hits.create(c->staging.stream);
+        if (e != hipSuccess) return fsea_detail::init_code("fsea_cfar_create", e);
+        if (int rc = c->hits.reserve(bytes)) return rc;
+        e = hipMemset(c->hits.buf.ptr, 0, bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        return fsea_detail::init_code("fsea_cfar_create", e);
+    });
+}
+
+int fsea_cfar_destroy(fsea_cfar *c) { return fsea_detail::destroy_object(c); }
+
+int fsea_cfar_reset(fsea_cfar *c) {
+    return fsea_detail::reset_object(c, "cfar is NULL", [&] {
+        c->rows = 0;
+        FSEA_HIP(hipMemset(c->hits.buf.ptr, 0, (size_t)c->width * sizeof(uint32_t)));
+        return (int)FSEA_OK;
+    });
+}
+
+int fsea_cfar_set(fsea_cfar *c, int guard, int train, int offset, int method) {
+    if (!c) return fail(FSEA_EINVAL, "cfar is NULL");
+    if (guard < 0 || guard > FSEA_CFAR_MAX_GUARD) return fail(FSEA_EINVAL, "guard must be in [0, %d], got %d", FSEA_CFAR_MAX_GUARD, guard);
+    if (train < 1 || train > FSEA_CFAR_MAX_TRAIN) return fail(FSEA_EINVAL, "train must be in [1, %d], got %d", FSEA_CFAR_MAX_TRAIN, train);
+    if (offset < -FSEA_CFAR_MAX_OFFSET || offset > FSEA_CFAR_MAX_OFFSET) {
+        return fail(FSEA_EINVAL, "offset must be in [-%d, %d], got %d", FSEA_CFAR_MAX_OFFSET, FSEA_CFAR_MAX_OFFSET, offset);
+    }
+    if (method != FSEA_CFAR_CA && method != FSEA_CFAR_GO && method != FSEA_CFAR_SO) return fail(FSEA_EINVAL, "unknown method %d", method);
+    std::lock_guard<std::mutex> lock(c->mu);
+    c->set = Settings{guard, train, offset, method};
+    return FSEA_OK;
+}
+
+int fsea_cfar_width(const fsea_cfar *c) { return c ? c->width : 0; }
+
+uint64_t fsea_cfar_rows(const fsea_cfar *c) { return c ? c->rows : 0; }
+
+int fsea_cfar_add_device(fsea_cfar *c, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask,
+                         uint32_t *d_row_hits, void *stream) {
+    int rc = check_add(c, d_rows, type, n_rows, pitch);
+    if (!rc && n_rows) rc = fsea_detail::check_aligned16("d_rows, d_mask and d_row_hits", d_rows, d_mask, d_row_hits);
+    if (rc) return rc;
+    if (n_rows == 0) return FSEA_OK;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = check_room(c, n_rows))) return rc;
+    FSEA_ON_DEVICE(c->device);
+    return add_launch(c, d_rows, type, n_rows, pitch, d_mask, d_row_hits, static_cast<hipStream_t>(stream));
+}
+
+int fsea_cfar_add_host(fsea_cfar *c, const void *rows, int type, size_t n_rows, size_t pitch, uint8_t *mask, uint32_t *row_hits) {
+    int rc = check_add(c, rows, type, n_rows, pitch);
+    if (rc) return rc;
+    if (n_rows == 0) return FSEA_OK;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = check_room(c, n_rows))) return rc;
+    FSEA_ON_DEVICE(c->device);
+    // the rows go up packed, at a pitch of whole 16-byte groups, in chunks of at most CF_STAGE_BYTES; mask and row hits of a
+    // chunk come back behind it
+    const size_t width = (size_t)c->width;
+    const size_t esz = elem_bytes(type), row_bytes = width * esz, packed = (row_bytes + 15) & ~(size_t)15;
+    const size_t chunk = std::max<size_t>(1, CF_STAGE_BYTES / packed);
+    for (size_t r0 = 0; r0 < n_rows; r0 += chunk) {
+        const size_t nr = std::min(chunk, n_rows - r0);
+        const char *src = static_cast<const char *>(rows) + r0 * pitch * esz;
+        const fsea_detail::HostStaging::Part parts[2] = {{mask ? mask + r0 * width : nullptr, nr * width},
+                                                         {row_hits ? row_hits + r0 : nullptr, nr * sizeof(uint32_t)}};
+        rc = c->staging.run(
+            nr * packed, parts,
+            [&](void *h_in) {
+                char *dst = static_cast<char *>(h_in);
+                for (size_t r = 0; r < nr; ++r) {
+                    std::memcpy(dst + r * packed, src + r * pitch * esz, row_bytes);
+                    std::memset(dst + r * packed + row_bytes, 0, packed - row_bytes);
+                }
+            },
+            [&](void *d_in, void **d_parts, hipStream_t s) {
+                return add_launch(c, d_in, type, nr, packed / esz, static_cast<uint8_t *>(d_parts[0]),
+                                  static_cast<uint32_t *>(d_parts[1]), s);
+            });
+        if (rc) return rc;
+    }
+    return FSEA_OK;
+}
+
+int fsea_cfar_hits_host(fsea_cfar *c, uint32_t *hits) {
+    if (!c) return fail(FSEA_EINVAL, "cfar is NULL");
+    if (!hits) return fail(FSEA_EINVAL, "hits is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    FSEA_ON_DEVICE(c->device);
+    const fsea_detail::HostStaging::Part part[1] = {{hits, (size_t)c->width * sizeof(uint32_t)}};
+    return c->staging.run(0, part, [](void *) {}, [&](void *, void **d_parts, hipStream_t s) {
+        d_parts[0] = c->hits.buf.ptr;        // the object's own memory, behind every add queued so far
+        return c->hits.acquire(s);
+    });
+}
+
+int fsea_cfar_bands(const uint32_t *hits, int width, uint64_t rows, double min_fraction, int max_gap, int min_width,
+                    fsea_cfar_band *bands, size_t capacity, size_t *n_bands) {
+    if (!hits || !n_bands || (!bands && capacity)) return fail(FSEA_EINVAL, "NULL buffer");
+    if (width < 1 || width > FSEA_CFAR_MAX_WIDTH) {
+        return fail(FSEA_EINVAL, "width must be in [1, %d], got %d", FSEA_CFAR_MAX_WIDTH, width);
+    }
+    if (!(min_fraction >= 0.0 && min_fraction <= 1.0)) return fail(FSEA_EINVAL, "min_fraction must be in [0, 1], got %g", min_fraction);
+    if (max_gap < 0) return fail(FSEA_EINVAL, "max_gap must not be negative, got %d", max_gap);
+    if (min_width < 1) return fail(FSEA_EINVAL, "min_width must be at least 1, got %d", min_width);
+    size_t found = 0;
+    *n_bands = 0;
+    if (rows == 0) return FSEA_OK;
+    const uint64_t c_min = std::max<uint64_t>(1, (uint64_t)std::ceil(min_fraction * (double)rows));
+    auto close_band = [&](int first, int last) {
+        if (last - first + 1 < min_width) return;
+        if (found < capacity) {
+            fsea_cfar_band b{first, last, first, hits[first], 0};
+            for (int k = first; k <= last; ++k) {
+                b.hits_sum += hits[k];
+                if (hits[k] > b.peak_hits) {
+                    b.peak = k;
+                    b.peak_hits = hits[k];
+                }
+            }
+            bands[found] = b;
+        }
+        ++found;
+    };
+    int first = -1, last = -1;
+    for (int k = 0; k < width; ++k) {
+        if (hits[k] < c_min) continue;
+        if (first >= 0 && k - last - 1 > max_gap) {
+            close_band(first, last);
+            first = -1;
+        }
+        if (first < 0) first = k;
+        last = k;
+    }
+    if (first >= 0) close_band(first, last);
+    *n_bands = found;
+    return FSEA_OK;
+}
+
+}  // extern "C"

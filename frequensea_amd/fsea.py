@@ -33,6 +33,16 @@ PERSIST_RUN_ROWS = 1024     # FSEA_PERSIST_RUN_ROWS: rows per workgroup of fsea_
 PERSIST_U8, PERSIST_F32 = 0, 1                                       # FSEA_PERSIST_*: element type of a row
 PERSIST_MAP_SATURATE, PERSIST_MAP_LINEAR, PERSIST_MAP_LOG = 0, 1, 2  # FSEA_PERSIST_MAP_*
 PERSIST_TRACE_MAX, PERSIST_TRACE_MIN, PERSIST_TRACE_QUANTILE = 0, 1, 2   # FSEA_PERSIST_TRACE_*
+CFAR_MAX_WIDTH = 1 << 20     # FSEA_CFAR_MAX_WIDTH
+CFAR_MAX_GUARD = 64         # FSEA_CFAR_MAX_GUARD
+CFAR_MAX_TRAIN = 256        # FSEA_CFAR_MAX_TRAIN, per side
+CFAR_MAX_OFFSET = 1 << 20   # FSEA_CFAR_MAX_OFFSET
+CFAR_F32_SCALE = 64         # FSEA_CFAR_F32_SCALE: f32 dB rows are taken in 1/64 dB
+CFAR_TILE_COLUMNS = 1024    # FSEA_CFAR_TILE_COLUMNS: columns per workgroup of fsea_cfar_u8 / fsea_cfar_f32
+CFAR_RUN_ROWS = 64          # FSEA_CFAR_RUN_ROWS: rows per workgroup
+CFAR_U8, CFAR_F32 = 0, 1                # FSEA_CFAR_*: element type of a row
+CFAR_CA, CFAR_GO, CFAR_SO = 0, 1, 2     # FSEA_CFAR_*: method
+CFAR_BAND = np.dtype([("first", "<i4"), ("last", "<i4"), ("peak", "<i4"), ("peak_hits", "<u4"), ("hits_sum", "<u8")])   # fsea_cfar_band
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
@@ -171,6 +181,16 @@ API = {
     "fsea_persist_image_device": (_ci, [_vp, _ci, _u64, _vp, _vp]),
     "fsea_persist_image_host": (_ci, [_vp, _ci, _u64, _vp]),
     "fsea_persist_trace": (_ci, [_vp, _ci, _ci, _f64, _vp]),
+    "fsea_cfar_create": (_ci, [_out, _ci, _ci]),
+    "fsea_cfar_destroy": (_ci, [_vp]),
+    "fsea_cfar_reset": (_ci, [_vp]),
+    "fsea_cfar_set": (_ci, [_vp, _ci, _ci, _ci, _ci]),
+    "fsea_cfar_width": (_ci, [_vp]),
+    "fsea_cfar_rows": (_u64, [_vp]),
+    "fsea_cfar_add_device": (_ci, [_vp, _vp, _ci, _sz, _sz, _vp, _vp, _vp]),
+    "fsea_cfar_add_host": (_ci, [_vp, _vp, _ci, _sz, _sz, _vp, _vp]),
+    "fsea_cfar_hits_host": (_ci, [_vp, _vp]),
+    "fsea_cfar_bands": (_ci, [_vp, _ci, _u64, _f64, _ci, _ci, _vp, _sz, _szp]),
     "fsea_iq_draw_create": (_ci, [_out, _ci]),
     "fsea_iq_draw_destroy": (_ci, [_vp]),
     "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
@@ -771,6 +791,72 @@ class Persist(_ResettableHandle):
 
     def image_device(self, d_image_ptr, map=PERSIST_MAP_LOG, full=0, stream=0):
         _check(self._L.fsea_persist_image_device(self._p, int(map), int(full), d_image_ptr, stream or None))
+
+
+def cfar_bands(hits, rows, min_fraction, max_gap=0, min_width=1):
+    """fsea_cfar_bands (host arithmetic): the bands of occupied columns of `hits` (width uint32, a Cfar's hits()) over
+    `rows` rows as a structured array of dtype CFAR_BAND (first, last, peak, peak_hits, hits_sum).  A column is occupied
+    when hits[k] >= max(1, ceil(min_fraction * rows)); up to max_gap unoccupied columns do not end a band; a band narrower
+    than min_width is dropped."""
+    h = np.ascontiguousarray(hits, dtype=np.uint32)
+    if h.ndim != 1:
+        raise ValueError("hits is a 1-D array")
+    n = ctypes.c_size_t()
+    args = (h.ctypes.data, h.shape[0], int(rows), float(min_fraction), int(max_gap), int(min_width))
+    _check(hip_lib().fsea_cfar_bands(*args, None, 0, ctypes.byref(n)))
+    out = np.zeros(n.value, dtype=CFAR_BAND)
+    if n.value:
+        _check(hip_lib().fsea_cfar_bands(*args, out.ctypes.data, n.value, ctypes.byref(n)))
+    return out
+
+
+class Cfar(_ResettableHandle):
+    """A CFAR detector across frequency on one device: which cells of a dB row stand above the mean level of their
+    neighbours, and hits[column] over all the rows offered; thin wrapper over fsea_cfar_*.  add() takes a 2-D uint8 or
+    float32 array from the host (any row stride) and returns what was asked for; add_device() takes resident rows."""
+    _kind = "cfar"
+
+    def __init__(self, width, device=0):
+        self.device = device
+        self._create("fsea_cfar_create", int(width), device)
+
+    @property
+    def width(self):
+        return self._L.fsea_cfar_width(self._p)
+
+    @property
+    def rows(self):
+        return self._L.fsea_cfar_rows(self._p)
+
+    def set(self, guard=2, train=16, offset=60, method=CFAR_CA):
+        _check(self._L.fsea_cfar_set(self._p, int(guard), int(train), int(offset), int(method)))
+
+    def add(self, rows, mask=False, row_hits=False):
+        """None, the (n_rows, width) uint8 mask, the (n_rows,) uint32 row hits, or (mask, row_hits)."""
+        a = np.asarray(rows)
+        if a.ndim != 2 or a.dtype not in (np.uint8, np.float32):
+            raise ValueError("rows is a 2-D uint8 or float32 array")
+        if a.shape[1] != self.width:
+            raise ValueError("a row has `width` elements")
+        if a.strides[1] != a.itemsize or (a.shape[0] > 1 and (a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize)):
+            a = np.ascontiguousarray(a)     # only rows of contiguous elements a whole number of elements apart go as they are
+        pitch = a.strides[0] // a.itemsize if a.shape[0] > 1 else a.shape[1]
+        m = np.empty(a.shape, dtype=np.uint8) if mask else None
+        h = np.empty(a.shape[0], dtype=np.uint32) if row_hits else None
+        _check(self._L.fsea_cfar_add_host(self._p, a.ctypes.data, CFAR_U8 if a.dtype == np.uint8 else CFAR_F32, a.shape[0], pitch,
+                                          m.ctypes.data if mask else None, h.ctypes.data if row_hits else None))
+        return (m, h) if mask and row_hits else m if mask else h
+
+    def add_device(self, d_rows_ptr, type, n_rows, pitch=None, d_mask_ptr=None, d_row_hits_ptr=None, stream=0):
+        """d_rows_ptr (an int, 16-byte aligned): n_rows rows of `width` elements, `pitch` elements apart; d_mask_ptr
+        (n_rows * width bytes) and d_row_hits_ptr (n_rows uint32) are optional; asynchronous."""
+        _check(self._L.fsea_cfar_add_device(self._p, d_rows_ptr, int(type), n_rows, self.width if pitch is None else pitch,
+                                            d_mask_ptr or None, d_row_hits_ptr or None, stream or None))
+
+    def hits(self):
+        out = np.empty(self.width, dtype=np.uint32)
+        _check(self._L.fsea_cfar_hits_host(self._p, out.ctypes.data))
+        return out
 
 
 class Demod(_ResettableHandle):

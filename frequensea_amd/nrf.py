@@ -209,6 +209,12 @@ _REST = {     # what only nrf_lib() binds: blocks, the sample source, the FFT, t
     "nrf_persistence_process": (None, [_vp, _buf]),
     "nrf_persistence_get_buffer": (_buf, [_vp]),
     "nrf_persistence_free": (None, [_vp]),
+    "nrf_spectrum_occupancy_new": (_vp, [_ci] * 6),
+    "nrf_spectrum_occupancy_set_window": (None, [_vp, ctypes.c_char_p]),
+    "nrf_spectrum_occupancy_process": (None, [_vp, _buf]),
+    "nrf_spectrum_occupancy_get_buffer": (_buf, [_vp]),
+    "nrf_spectrum_occupancy_get_mask_buffer": (_buf, [_vp]),
+    "nrf_spectrum_occupancy_free": (None, [_vp]),
     "nrf_signal_capture_new": (_vp, [_ci, _ci, _ci, _f64]),
     "nrf_signal_capture_scan": (_ci, [_vp, _buf, _ci]),
     "nrf_signal_capture_get_mean": (_f64, [_vp, _ci]),
@@ -230,6 +236,8 @@ NRF_ADDITIONS = ["nrf_fft_set_window", "nrf_fft_set_window_weights", "nrf_decode
                  "nrf_pfb_fft_new", "nrf_pfb_fft_process", "nrf_pfb_fft_get_buffer", "nrf_pfb_fft_free",
                  "nrf_persistence_new", "nrf_persistence_set_window", "nrf_persistence_set_decay", "nrf_persistence_process",
                  "nrf_persistence_get_buffer", "nrf_persistence_free",
+                 "nrf_spectrum_occupancy_new", "nrf_spectrum_occupancy_set_window", "nrf_spectrum_occupancy_process",
+                 "nrf_spectrum_occupancy_get_buffer", "nrf_spectrum_occupancy_get_mask_buffer", "nrf_spectrum_occupancy_free",
                  "nrf_signal_capture_new", "nrf_signal_capture_scan", "nrf_signal_capture_get_mean",
                  "nrf_signal_capture_get_standard_deviation", "nrf_signal_capture_get_burst",
                  "nrf_signal_capture_get_iq_lines", "nrf_signal_capture_free"]

@@ -33,6 +33,7 @@
  *   fsea_zoom_*           shift -> decimating filter -> FFT: a spectrum of 1 / D of the bandwidth (nrf_decoder's chain)
  *   fsea_pfb_*            a polyphase filter bank (no counterpart in the reference): all M channels of the band at once
  *   fsea_persist_*        a persistence spectrum (no counterpart in the reference): per-bin level histograms of resident rows
+ *   fsea_cfar_*           a CFAR detector across frequency (no counterpart in the reference): occupied bins, bands and masks
  *   fsea_detect_*         the burst detector of lua/signal-detector.lua: the two loops of nrf_signal_detector_process,
  *                         src/nrf.c:883-898, as integer sums over many blocks per launch
  *   fsea_capture_*        that scene on a resident recording: detect -> gate -> filter the bursts -> line images
@@ -65,6 +66,7 @@ typedef struct fsea_chain fsea_chain;
 typedef struct fsea_zoom fsea_zoom;
 typedef struct fsea_pfb fsea_pfb;
 typedef struct fsea_persist fsea_persist;
+typedef struct fsea_cfar fsea_cfar;
 typedef struct fsea_demod fsea_demod;
 typedef struct fsea_interp fsea_interp;
 typedef struct fsea_trace fsea_trace;
@@ -618,6 +620,78 @@ int fsea_persist_counts_host(fsea_persist *persist, uint32_t *counts);
 int fsea_persist_image_device(fsea_persist *persist, int map, uint64_t full, uint8_t *d_image, void *stream);
 int fsea_persist_image_host(fsea_persist *persist, int map, uint64_t full, uint8_t *image);
 int fsea_persist_trace(const uint32_t *counts, int width, int kind, double fraction, uint8_t *levels);
+
+/* The CFAR spectrum detector: which cells of a dB row hold a signal, and which bands are occupied how often -- a
+ * constant-false-alarm-rate detector across frequency.  Each cell of a row is compared with the mean level of its neighbours to
+ * the left and right, a few guard cells beside it left out; the per-column count of detections over many rows is the
+ * occupancy (duty cycle) of the column, and runs of occupied columns are the bands.  It consumes rows that are already
+ * resident (the FSEA_MODE_DB10_U8 / FSEA_MODE_DB5_U8_DCFIX / FSEA_MODE_DB_F32 output of fsea_plan, fsea_zoom, fsea_pfb, or a
+ * stitched sweep image).  Integer and order-free: every result is the same bits however the rows are cut into calls.  The
+ * object owns hits[k], width uint32_t, zero after create and reset; `rows`, the rows offered so far; and the settings
+ * (guard G, train T, offset, method), (2, 16, 60, FSEA_CFAR_CA) after create.
+ *   level:  of an element.  U8: the byte.  F32: t = v * 64 in one rounded f32 multiplication (FSEA_CFAR_F32_SCALE: 1/64 dB);
+ *           a NaN gives -2^20, t <= -2^20 gives -2^20, t >= 2^20 gives 2^20, otherwise (int)rintf(t), round half to even.
+ *           `offset` is in the same units: u8 levels, or 1/64 dB for f32 rows.
+ *   windows: of cell k of a row of `width` cells.  Left training cells k-G-T .. k-G-1, right training cells k+G+1 .. k+G+T,
+ *           each side clipped to [0, width-1], no wrap-around; nL, nR are the counts of cells and SL, SR the sums of levels.
+ *   decision: for the cell's level x, all in 32-bit integers.  With ok(n, S): x*n > S + offset*n,
+ *             CA (cell averaging):  nL+nR > 0 and ok(nL+nR, SL+SR)
+ *             GO (greatest of):     nL+nR > 0 and every side with n > 0 satisfies ok(n, S) -- holds at the step between two
+ *                                   stitched tiles
+ *             SO (smallest of):     some side with n > 0 satisfies ok(n, S) -- finds the weaker of two close carriers
+ *   add:    row r starts pitch elements behind row r - 1, pitch >= width; a sub-band of wider rows is d_rows + offset with the
+ *           wide pitch.  d_mask (optional, NULL: not written) is tight, n_rows * width bytes, 255 for a hit and 0 otherwise.
+ *           d_row_hits (optional): d_row_hits[r] is set to, not added to, the number of hits in row r of this call.
+ *           hits[k] += the hits of column k; rows += n_rows; a call that would take rows above 2^32 - 1 is refused, so no
+ *           count can wrap.  n_rows == 0 is a successful no-op.  The settings used are those at the time of the call.
+ *           add_device: d_rows, d_mask and d_row_hits are 16-byte aligned, pitch (in elements) may be anything;
+ *           asynchronous on `stream`; calls on different streams follow one another (an event).  Rows whose pitch is a
+ *           multiple of 16 bytes are read 16 bytes per lane, others element by element; the mask is written 16 bytes per lane
+ *           where width is a multiple of 16.  add_host stages the rows through pinned memory in chunks on the object's own
+ *           stream and returns when mask, row hits and hits are in place.
+ *           Kernels fsea_cfar_u8 / fsea_cfar_f32: a workgroup of 256 lanes takes a tile of FSEA_CFAR_TILE_COLUMNS columns over a
+ *           run of FSEA_CFAR_RUN_ROWS rows; a row segment's prefix sums in LDS make the cost per cell independent of T.
+ *   hits_host: the width hit counts, behind every add queued so far.
+ *   bands:  host arithmetic on fetched hits, no device.  c_min = max(1, (uint64_t)ceil(min_fraction * rows)); column k is
+ *           occupied when hits[k] >= c_min.  Going up the columns, a band runs from an occupied column through every further
+ *           occupied column that has at most max_gap unoccupied columns before it; first and last are its first and last
+ *           occupied columns; a band narrower than min_width columns (last - first + 1) is dropped.  peak is the lowest
+ *           column of the band with the most hits, peak_hits its count, hits_sum the sum over first .. last.  rows == 0 gives
+ *           no band.  At most `capacity` bands are written; *n_bands is the number found, which may exceed capacity; bands may
+ *           be NULL when capacity is 0.
+ * Every check runs before any device work: FSEA_EINVAL for a NULL object or input buffer, a width outside
+ * [1, FSEA_CFAR_MAX_WIDTH], a guard outside [0, FSEA_CFAR_MAX_GUARD], a train outside [1, FSEA_CFAR_MAX_TRAIN], |offset| above
+ * FSEA_CFAR_MAX_OFFSET, an unknown type or method, pitch < width, n_rows > 2^31, a misaligned device pointer, min_fraction
+ * outside [0, 1], a negative max_gap, min_width < 1.  Create: FSEA_ENODEVICE without a GPU.  width and rows return 0 for NULL.
+ * Destroy and reset wait for the device; reset zeroes hits and rows and keeps the settings.  Calls on one object from several
+ * threads are serialised. */
+#define FSEA_CFAR_MAX_WIDTH (1 << 20)   /* a stitched sweep image fits */
+#define FSEA_CFAR_MAX_GUARD 64
+#define FSEA_CFAR_MAX_TRAIN 256         /* per side */
+#define FSEA_CFAR_MAX_OFFSET (1 << 20)  /* |offset| */
+#define FSEA_CFAR_F32_SCALE 64          /* f32 dB rows are taken in 1/64 dB */
+#define FSEA_CFAR_TILE_COLUMNS 1024     /* columns of a workgroup of the add kernels */
+#define FSEA_CFAR_RUN_ROWS 64           /* rows a workgroup of the add kernels takes before it adds its column hits to hits */
+enum { FSEA_CFAR_U8 = 0, FSEA_CFAR_F32 = 1 };                       /* element type of a row */
+enum { FSEA_CFAR_CA = 0, FSEA_CFAR_GO = 1, FSEA_CFAR_SO = 2 };      /* method */
+typedef struct {
+    int32_t first, last, peak;
+    uint32_t peak_hits;
+    uint64_t hits_sum;
+} fsea_cfar_band;
+int fsea_cfar_create(fsea_cfar **cfar, int width, int device);
+int fsea_cfar_destroy(fsea_cfar *cfar);
+int fsea_cfar_reset(fsea_cfar *cfar);
+int fsea_cfar_set(fsea_cfar *cfar, int guard, int train, int offset, int method);
+int fsea_cfar_width(const fsea_cfar *cfar);
+uint64_t fsea_cfar_rows(const fsea_cfar *cfar);
+int fsea_cfar_add_device(fsea_cfar *cfar, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask,
+                         uint32_t *d_row_hits, void *stream);
+int fsea_cfar_add_host(fsea_cfar *cfar, const void *rows, int type, size_t n_rows, size_t pitch, uint8_t *mask,
+                       uint32_t *row_hits);
+int fsea_cfar_hits_host(fsea_cfar *cfar, uint32_t *hits);
+int fsea_cfar_bands(const uint32_t *hits, int width, uint64_t rows, double min_fraction, int max_gap, int min_width,
+                    fsea_cfar_band *bands, size_t capacity, size_t *n_bands);
 
 /* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
  * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With

@@ -437,6 +437,43 @@ void nrf_persistence_process(nrf_persistence *p, nut_buffer *buffer);
 nut_buffer *nrf_persistence_get_buffer(nrf_persistence *p);
 void nrf_persistence_free(nrf_persistence *p);
 
+/* ---- ADDITIONS (not in the reference): the spectrum occupancy ---- */
+
+/* A CFAR detector across the device's band (fsea_cfar_*, include/fsea.h): which of the fft_size bins hold a signal, and how
+ * often over all the blocks processed.
+ *   - new takes the detector's settings: guard and train cells per side, the offset in levels of the DB5 rows
+ *     (FSEA_MODE_DB5_U8_DCFIX, include/fsea.h) and the method (FSEA_CFAR_CA, _GO, _SO).
+ *   - process takes a U8 buffer with 2 channels.  All (length - fft_size) / hop + 1 frames of the block go through a
+ *     FSEA_MODE_DB5_U8_DCFIX plan on the device and from there into the object: the block goes up once, nothing comes
+ *     back.  A block shorter than fft_size adds nothing.
+ *   - set_window takes the names of nrf_fft_set_window.
+ *   - get_buffer is an F64 buffer of fft_size duty cycles hits[k] / rows, one channel, all 0 before any row.
+ *   - get_mask_buffer is the last block's mask: a U8 buffer of frames * fft_size elements, one channel, 255 where frame r had
+ *     a detection in bin k; of length 0 before any block and after a block shorter than a frame.
+ *   Both buffers are the caller's to free.
+ * An F64 buffer, an fft_size outside [1, FSEA_CFAR_MAX_WIDTH] or without a plan, a hop below 1, a guard, train, offset or
+ * method that fsea_cfar_set refuses, an unknown window name, and a backend failure (no GPU) print
+ * "NRF SPECTRUM OCCUPANCY fatal error: ..." and exit. */
+typedef struct {
+    NRF_BLOCK;
+    int fft_size;
+    int hop;
+    int device;
+    void *plan;               /* fsea_plan* (libfsea_hip.so): (fft_size, hop, FSEA_MODE_DB5_U8_DCFIX) */
+    void *backend;            /* fsea_cfar* */
+    void *d_iq, *d_rows, *d_mask;   /* device memory: the block, its rows, their mask */
+    size_t iq_cap, rows_cap, mask_cap;
+    size_t mask_rows;         /* frames of the last block */
+    pthread_mutex_t mutex;
+} nrf_spectrum_occupancy;
+
+nrf_spectrum_occupancy *nrf_spectrum_occupancy_new(int fft_size, int hop, int guard, int train, int offset, int method);
+void nrf_spectrum_occupancy_set_window(nrf_spectrum_occupancy *p, const char *name);
+void nrf_spectrum_occupancy_process(nrf_spectrum_occupancy *p, nut_buffer *buffer);
+nut_buffer *nrf_spectrum_occupancy_get_buffer(nrf_spectrum_occupancy *p);
+nut_buffer *nrf_spectrum_occupancy_get_mask_buffer(nrf_spectrum_occupancy *p);
+void nrf_spectrum_occupancy_free(nrf_spectrum_occupancy *p);
+
 /* ---- ADDITIONS (not in the reference): the signal capture ---- */
 
 /* The reference's signal scene (lua/signal-detector.lua:89-133) over a whole recording that stays on the GPU: the detector
