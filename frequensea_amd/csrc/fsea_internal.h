@@ -1,6 +1,6 @@
 // fsea_internal.h -- what the translation units of libfsea_hip.so share behind the C ABI (include/fsea.h): the plan
-// object, error plumbing, the launch dispatcher, the owning types, and the scaffold of the twelve device objects (FIR, IQ
-// draw, demod, interp, chain, zoom, pfb, persist, cfar, trace, detect, capture).
+// object, error plumbing, the launch dispatcher, the owning types, and the scaffold of the thirteen device objects (FIR, IQ
+// draw, demod, interp, chain, zoom, pfb, persist, cfar, events, trace, detect, capture).
 //
 // The owning types: a struct here releases HIP resources only by having members that release themselves.  Buffer<Mem>
 // (memory that grows on demand), DeviceArray<T> and PinnedArray<T> (exact size, allocated once), Stream and Event, and

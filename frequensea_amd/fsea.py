@@ -43,6 +43,14 @@ CFAR_RUN_ROWS = 64          # FSEA_CFAR_RUN_ROWS: rows per workgroup
 CFAR_U8, CFAR_F32 = 0, 1                # FSEA_CFAR_*: element type of a row
 CFAR_CA, CFAR_GO, CFAR_SO = 0, 1, 2     # FSEA_CFAR_*: method
 CFAR_BAND = np.dtype([("first", "<i4"), ("last", "<i4"), ("peak", "<i4"), ("peak_hits", "<u4"), ("hits_sum", "<u8")])   # fsea_cfar_band
+EVENTS_MAX_WIDTH = 1 << 20      # FSEA_EVENTS_MAX_WIDTH
+EVENTS_MAX_GAP_COLS = 64        # FSEA_EVENTS_MAX_GAP_COLS
+EVENTS_MAX_GAP_ROWS = 1 << 16   # FSEA_EVENTS_MAX_GAP_ROWS
+EVENTS_NO_EVENT = 0xFFFFFFFF    # FSEA_EVENTS_NO_EVENT: event_of_run of a run whose event the filters dropped
+EVENTS_RUN = np.dtype([("row", "<u4"), ("first", "<u4"), ("last", "<u4"), ("hits", "<u4"), ("peak", "<i4"), ("peak_col", "<u4"),
+                       ("level_sum", "<i8")])   # fsea_events_run
+EVENTS_EVENT = np.dtype([("row_first", "<u4"), ("row_last", "<u4"), ("col_first", "<u4"), ("col_last", "<u4"), ("runs", "<u4"),
+                         ("peak", "<i4"), ("peak_row", "<u4"), ("peak_col", "<u4"), ("hits", "<u8"), ("level_sum", "<i8")])   # fsea_events_event
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
@@ -191,6 +199,17 @@ API = {
     "fsea_cfar_add_host": (_ci, [_vp, _vp, _ci, _sz, _sz, _vp, _vp]),
     "fsea_cfar_hits_host": (_ci, [_vp, _vp]),
     "fsea_cfar_bands": (_ci, [_vp, _ci, _u64, _f64, _ci, _ci, _vp, _sz, _szp]),
+    "fsea_events_create": (_ci, [_out, _ci, _ci]),
+    "fsea_events_destroy": (_ci, [_vp]),
+    "fsea_events_reset": (_ci, [_vp]),
+    "fsea_events_set_gap": (_ci, [_vp, _ci]),
+    "fsea_events_width": (_ci, [_vp]),
+    "fsea_events_rows": (_u64, [_vp]),
+    "fsea_events_runs_device": (_ci, [_vp, _vp, _sz, _vp, _ci, _sz, _sz, _vp, _sz, _szp, _vp]),
+    "fsea_events_runs_host": (_ci, [_vp, _vp, _sz, _vp, _ci, _sz, _sz, _vp, _sz, _szp]),
+    "fsea_events_link": (_ci, [_vp, _sz, _ci, _ci, _u32, _u32, _u64, _vp, _vp, _sz, _szp]),
+    "fsea_events_paint_device": (_ci, [_vp, _vp, _vp, _sz, _u64, _sz, _vp, _sz, _vp]),
+    "fsea_events_paint_host": (_ci, [_vp, _vp, _vp, _sz, _u64, _sz, _vp, _sz]),
     "fsea_iq_draw_create": (_ci, [_out, _ci]),
     "fsea_iq_draw_destroy": (_ci, [_vp]),
     "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
@@ -857,6 +876,105 @@ class Cfar(_ResettableHandle):
         out = np.empty(self.width, dtype=np.uint32)
         _check(self._L.fsea_cfar_hits_host(self._p, out.ctypes.data))
         return out
+
+
+def _rows_2d(a, dtypes, what):
+    """A 2-D array whose rows are contiguous and a whole number of elements apart (copied where they are not), and its pitch
+    in elements."""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype not in dtypes:
+        raise ValueError("%s is a 2-D array of %s" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
+    if a.strides[1] != a.itemsize or (a.shape[0] > 1 and (a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize)):
+        a = np.ascontiguousarray(a)
+    return a, (a.strides[0] // a.itemsize if a.shape[0] > 1 else a.shape[1])
+
+
+class Events(_ResettableHandle):
+    """Spectrum events on one device: a detection mask (and the level rows under it) as a sorted list of runs, the runs
+    linked into time-frequency events, runs painted back as an image; thin wrapper over fsea_events_*.  runs() and paint()
+    take and give host arrays, runs_device() and paint_device() work on resident memory; link() is host arithmetic."""
+    _kind = "events"
+
+    def __init__(self, width, device=0):
+        self.device = device
+        self._create("fsea_events_create", int(width), device)
+
+    @property
+    def width(self):
+        return self._L.fsea_events_width(self._p)
+
+    @property
+    def rows(self):
+        return self._L.fsea_events_rows(self._p)
+
+    def set_gap(self, gap_cols):
+        _check(self._L.fsea_events_set_gap(self._p, int(gap_cols)))
+
+    def runs(self, mask, levels=None):
+        """The runs of a 2-D uint8 mask (any row stride), with the statistics of `levels` (uint8 or float32, the mask's shape)
+        under its hits: a structured array of dtype EVENTS_RUN, sorted by (row, first)."""
+        m, mp = _rows_2d(mask, (np.uint8,), "mask")
+        if m.shape[1] != self.width:
+            raise ValueError("a row has `width` elements")
+        lp, lptr, type = m.shape[1], None, CFAR_U8
+        if levels is not None:
+            lv, lp = _rows_2d(levels, (np.uint8, np.float32), "levels")
+            if lv.shape != m.shape:
+                raise ValueError("levels has the mask's shape")
+            lptr, type = lv.ctypes.data, CFAR_U8 if lv.dtype == np.uint8 else CFAR_F32
+        # room for the records: the hits with no hit to their left are the runs at a gap of 0 and no fewer at any other
+        hit = m != 0
+        room = int(hit[:, 0].sum()) + int((hit[:, 1:] & ~hit[:, :-1]).sum())
+        out = np.zeros(room, dtype=EVENTS_RUN)
+        n = ctypes.c_size_t()
+        _check(self._L.fsea_events_runs_host(self._p, m.ctypes.data, mp, lptr, type, lp, m.shape[0],
+                                             out.ctypes.data if room else None, room, ctypes.byref(n)))
+        assert n.value <= room
+        return out[:n.value]
+
+    def runs_device(self, d_mask_ptr, n_rows, d_runs_ptr, capacity, mask_pitch=None, d_levels_ptr=None, type=CFAR_U8,
+                    level_pitch=None, stream=0):
+        """d_mask_ptr (an int, 16-byte aligned): n_rows rows of `width` bytes, mask_pitch bytes apart; d_levels_ptr (optional)
+        the level rows, level_pitch elements apart; at most `capacity` records to d_runs_ptr.  Returns the number of runs
+        found, which may exceed capacity; the records are in place when it returns."""
+        n = ctypes.c_size_t()
+        _check(self._L.fsea_events_runs_device(self._p, d_mask_ptr, self.width if mask_pitch is None else mask_pitch,
+                                               d_levels_ptr or None, int(type), self.width if level_pitch is None else level_pitch,
+                                               n_rows, d_runs_ptr or None, capacity, ctypes.byref(n), stream or None))
+        return n.value
+
+    @staticmethod
+    def link(runs, gap_cols=0, gap_rows=0, min_rows=1, min_cols=1, min_hits=1):
+        """fsea_events_link (host arithmetic): (events, event_of_run) of a sorted array of EVENTS_RUN -- a structured array
+        of dtype EVENTS_EVENT for the events that pass the filters, and per run the number of its event or EVENTS_NO_EVENT."""
+        r = np.ascontiguousarray(runs, dtype=EVENTS_RUN)
+        if r.ndim != 1:
+            raise ValueError("runs is a 1-D array")
+        of_run = np.empty(r.size, dtype=np.uint32)
+        n = ctypes.c_size_t()
+        args = (r.ctypes.data if r.size else None, r.size, int(gap_cols), int(gap_rows), int(min_rows), int(min_cols), int(min_hits))
+        _check(hip_lib().fsea_events_link(*args, None, None, 0, ctypes.byref(n)))
+        events = np.zeros(n.value, dtype=EVENTS_EVENT)
+        _check(hip_lib().fsea_events_link(*args, of_run.ctypes.data if r.size else None, events.ctypes.data if n.value else None,
+                                          n.value, ctypes.byref(n)))
+        return events, of_run
+
+    def paint(self, runs, values, n_rows, row0=0):
+        """The (n_rows, width) uint8 image of `runs` with one uint8 value per run; image row 0 is row `row0`."""
+        r = np.ascontiguousarray(runs, dtype=EVENTS_RUN)
+        v = np.ascontiguousarray(values, dtype=np.uint8)
+        if r.ndim != 1 or v.shape != r.shape:
+            raise ValueError("runs is a 1-D array and values has one uint8 per run")
+        out = np.empty((n_rows, self.width), dtype=np.uint8)
+        _check(self._L.fsea_events_paint_host(self._p, r.ctypes.data if r.size else None, v.ctypes.data if r.size else None, r.size,
+                                              int(row0), n_rows, out.ctypes.data if n_rows else None, self.width))
+        return out
+
+    def paint_device(self, d_runs_ptr, d_values_ptr, n_runs, n_rows, d_image_ptr, row0=0, pitch=None, stream=0):
+        """d_runs_ptr, d_image_ptr (ints, 16-byte aligned) and d_values_ptr: n_runs records and values, an image of n_rows rows
+        `pitch` bytes apart; asynchronous."""
+        _check(self._L.fsea_events_paint_device(self._p, d_runs_ptr or None, d_values_ptr or None, n_runs, int(row0), n_rows,
+                                                d_image_ptr or None, self.width if pitch is None else pitch, stream or None))
 
 
 class Demod(_ResettableHandle):

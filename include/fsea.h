@@ -34,6 +34,7 @@
  *   fsea_pfb_*            a polyphase filter bank (no counterpart in the reference): all M channels of the band at once
  *   fsea_persist_*        a persistence spectrum (no counterpart in the reference): per-bin level histograms of resident rows
  *   fsea_cfar_*           a CFAR detector across frequency (no counterpart in the reference): occupied bins, bands and masks
+ *   fsea_events_*         spectrum events (no counterpart in the reference): a detection mask as runs, time-frequency boxes
  *   fsea_detect_*         the burst detector of lua/signal-detector.lua: the two loops of nrf_signal_detector_process,
  *                         src/nrf.c:883-898, as integer sums over many blocks per launch
  *   fsea_capture_*        that scene on a resident recording: detect -> gate -> filter the bursts -> line images
@@ -67,6 +68,7 @@ typedef struct fsea_zoom fsea_zoom;
 typedef struct fsea_pfb fsea_pfb;
 typedef struct fsea_persist fsea_persist;
 typedef struct fsea_cfar fsea_cfar;
+typedef struct fsea_events fsea_events;
 typedef struct fsea_demod fsea_demod;
 typedef struct fsea_interp fsea_interp;
 typedef struct fsea_trace fsea_trace;
@@ -692,6 +694,93 @@ int fsea_cfar_add_host(fsea_cfar *cfar, const void *rows, int type, size_t n_row
 int fsea_cfar_hits_host(fsea_cfar *cfar, uint32_t *hits);
 int fsea_cfar_bands(const uint32_t *hits, int width, uint64_t rows, double min_fraction, int max_gap, int min_width,
                     fsea_cfar_band *bands, size_t capacity, size_t *n_bands);
+
+/* Spectrum events: which emissions a detection mask holds -- this burst, from row 812 to row 860, columns 3011 .. 3042, peak
+ * 171 at (830, 3027).  A device pass reduces a resident mask (fsea_cfar's, n_rows x width bytes) and optionally the level rows
+ * under it to a sorted list of runs, a few records per row; fsea_events_link joins the runs into events on the host; a device
+ * pass paints runs back as a cleaned mask or a label image.  Integer and bit for bit: every record is the same whatever the
+ * launch geometry or the cut of the rows into calls.  The object owns `rows`, the rows offered since create or reset, and the
+ * column gap G, 0 after create.
+ *   hit:    a mask byte that is not 0 (fsea_cfar writes 255).
+ *   level:  of a cell: fsea_cfar's, above.  FSEA_CFAR_U8: the byte.  FSEA_CFAR_F32: rint(v * 64) in one rounded f32
+ *           multiplication, clamped to +-2^20, -2^20 for a NaN.
+ *   runs:   of a row.  Going up the columns, a run starts at a hit and continues through every further hit that has at most G
+ *           non-hit columns before it (fsea_cfar_bands' wording).  One record per run: row = rows at the call + the row within
+ *           the call; first and last, its first and last hit column; hits, the hit cells in first .. last (last - first + 1
+ *           when G is 0); peak, the largest level over the hit cells, and peak_col, the lowest hit column that holds it;
+ *           level_sum, the sum of the levels over the hit cells.  Without level rows (d_levels NULL; `type` is still checked)
+ *           peak = 0, peak_col = first, level_sum = 0.  The records come out sorted by (row, first).  At most `capacity` are
+ *           written, the first ones in order; *n_runs is the number found, which may exceed capacity; capacity 0 with a NULL
+ *           buffer just counts.  Then rows += n_rows; a call that would take rows past 2^32 - 1 is refused.  n_rows == 0 is
+ *           a successful no-op with *n_runs = 0.  Row r of the mask starts mask_pitch bytes behind row r - 1, of the levels
+ *           level_pitch elements; both pitches >= width.  runs_device: d_mask, d_levels and d_runs are 16-byte aligned;
+ *           queued on `stream`, and the call waits for its own count before it returns: the records are then in place.
+ *           Rows whose pitches are multiples of 16 bytes are read 16 bytes per lane, others element by element; no load
+ *           passes the width of a row, no store the capacity.  runs_host stages mask and levels through pinned memory in
+ *           chunks of rows on the object's own stream.
+ *           Kernels fsea_events_count and fsea_events_runs / _u8 / _f32 (and their _narrow forms): one wave per row walks
+ *           it in chunks of 64 lanes x 16 cells with a carry; the first pass counts the runs of every row, a scan over the
+ *           rows gives each row's first index and the total, the second pass stores the records: sorted without a sort.
+ *   touch:  run a in row ra and run b in row rb > ra touch when rb - ra <= gap_rows + 1, first_a <= last_b + gap_cols and
+ *           first_b <= last_a + gap_cols.  With both gaps 0 this is 4-connectivity on the mask.
+ *   link:   host arithmetic, no device.  The events are the connected components of the touch relation.  An event's record:
+ *           the box row_first .. row_last, col_first .. col_last; runs; hits; peak with peak_row and peak_col, ties to the
+ *           lowest row, then the lowest column; level_sum, wrapping modulo 2^64.  The events are ordered by the position of
+ *           their first run in the list.  An event whose box is lower than min_rows or narrower than min_cols, or whose hits
+ *           are below min_hits, is dropped; the survivors are numbered 0, 1, ... in order.  event_of_run[i] (optional) is the
+ *           number of run i's event, FSEA_EVENTS_NO_EVENT for a run of a dropped one.  At most `capacity` events are written;
+ *           *n_events is the number that survive; events may be NULL when capacity is 0.  The runs must be sorted by
+ *           (row, first), disjoint within a row, first <= last.  The cost is linear in the runs and the pairs that touch.
+ *   paint:  every byte of the n_rows x width image (row r starts pitch bytes behind row r - 1, pitch >= width; the bytes
+ *           between width and pitch are left alone) is written: columns first .. last of a run with values[i] != 0 hold
+ *           values[i], closed gaps included, everything else 0.  Image row 0 is row `row0`; runs whose row lies outside
+ *           [row0, row0 + n_rows), and runs that do not lie inside the width, are ignored.  Runs that overlap are the
+ *           caller's error.  paint_device: d_runs and d_image 16-byte aligned, asynchronous on `stream`.
+ *           Kernel fsea_events_paint: a zero fill, then one wave per run, 16-byte stores in the aligned middle.
+ * Every check runs before any device work: FSEA_EINVAL for a NULL object, buffer or count, a width outside
+ * [1, FSEA_EVENTS_MAX_WIDTH], a gap_cols outside [0, FSEA_EVENTS_MAX_GAP_COLS], a gap_rows outside
+ * [0, FSEA_EVENTS_MAX_GAP_ROWS], an unknown type, a pitch < width, n_rows > 2^31, a misaligned device pointer, a filter
+ * below 1, runs that are not sorted.  Create: FSEA_ENODEVICE without a GPU.  width and rows return 0 for NULL.  Destroy and
+ * reset wait for the device; reset puts rows back to 0 and keeps the gap.  Calls on one object from several threads are
+ * serialised. */
+#define FSEA_EVENTS_MAX_WIDTH (1 << 20)
+#define FSEA_EVENTS_MAX_GAP_COLS 64
+#define FSEA_EVENTS_MAX_GAP_ROWS (1 << 16)
+#define FSEA_EVENTS_NO_EVENT 0xFFFFFFFFu
+typedef struct {            /* 32 bytes */
+    uint32_t row;
+    uint32_t first, last;
+    uint32_t hits;
+    int32_t peak;
+    uint32_t peak_col;
+    int64_t level_sum;
+} fsea_events_run;
+typedef struct {            /* 48 bytes */
+    uint32_t row_first, row_last, col_first, col_last;
+    uint32_t runs;
+    int32_t peak;
+    uint32_t peak_row, peak_col;
+    uint64_t hits;
+    int64_t level_sum;
+} fsea_events_event;
+int fsea_events_create(fsea_events **events, int width, int device);
+int fsea_events_destroy(fsea_events *events);
+int fsea_events_reset(fsea_events *events);
+int fsea_events_set_gap(fsea_events *events, int gap_cols);
+int fsea_events_width(const fsea_events *events);
+uint64_t fsea_events_rows(const fsea_events *events);
+int fsea_events_runs_device(fsea_events *events, const uint8_t *d_mask, size_t mask_pitch, const void *d_levels, int type,
+                            size_t level_pitch, size_t n_rows, fsea_events_run *d_runs, size_t capacity, size_t *n_runs,
+                            void *stream);
+int fsea_events_runs_host(fsea_events *events, const uint8_t *mask, size_t mask_pitch, const void *levels, int type,
+                          size_t level_pitch, size_t n_rows, fsea_events_run *runs, size_t capacity, size_t *n_runs);
+int fsea_events_link(const fsea_events_run *runs, size_t n_runs, int gap_cols, int gap_rows, uint32_t min_rows,
+                     uint32_t min_cols, uint64_t min_hits, uint32_t *event_of_run, fsea_events_event *events, size_t capacity,
+                     size_t *n_events);
+int fsea_events_paint_device(fsea_events *events, const fsea_events_run *d_runs, const uint8_t *d_values, size_t n_runs,
+                             uint64_t row0, size_t n_rows, uint8_t *d_image, size_t pitch, void *stream);
+int fsea_events_paint_host(fsea_events *events, const fsea_events_run *runs, const uint8_t *values, size_t n_runs, uint64_t row0,
+                           size_t n_rows, uint8_t *image, size_t pitch);
 
 /* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
  * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With
