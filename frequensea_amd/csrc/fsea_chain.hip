@@ -47,6 +47,13 @@ int check_stage(const fsea_chain_stage &st, size_t n, int n_frames) {
     if (n_frames > 1 && st.n_zero && ((n & 7) || (st.n_zero & 1))) {
         return fail(FSEA_EINVAL, "frames with zero samples need n_samples a multiple of 8 and n_zero even");
     }
+    // the shift of the whole call, here and not piece by piece: the frames stand at sample_offset + f n (the zeros are not
+    // the shifter's samples), so no launch of queue_filter can be refused once an earlier one is queued.  Without a shift
+    // the three fields are not looked at.
+    if (st.shift) {
+        const size_t span = n * (size_t)(n_frames > 0 ? n_frames : 0);   // <= MAX_TOTAL: checked above
+        return fsea_stage::check_shift(st.cycles_per_sample, st.phase0_cycles, st.sample_offset, span);
+    }
     return FSEA_OK;
 }
 
@@ -63,9 +70,12 @@ int check_outputs(const fsea_chain_outputs &o, size_t n_pairs, int n_frames, boo
     return device ? fsea_detail::check_aligned16("the outputs", o.points, o.lines, o.pairs) : (int)FSEA_OK;
 }
 
-// the caller holds c->mu and is on c's device; stream work that may still read the old buffer is the caller's to order
+// the caller holds c->mu and is on c's device; stream work that may still read the old buffer is the caller's to order.
+// The resident block goes only where the buffer has to be reallocated; otherwise it stays until a filter launch is queued.
 int reserve_pairs(fsea_chain *c, size_t bytes) {
-    return c->pairs.grow(bytes ? bytes : 16);
+    const size_t need = bytes ? bytes : 16;
+    if (c->pairs.cap < need) c->n_pairs = 0;
+    return c->pairs.grow(need);
 }
 
 // the filter launches of n_frames blocks into c->pairs.ptr
@@ -114,7 +124,6 @@ int host_call(fsea_chain *c, bool run, const void *in, int f64, size_t n, const 
     const size_t in_bytes = run ? n * (f64 ? 16 : 2) : 0;
     const size_t total = run ? n + st.n_zero : c->n_pairs;
     if (run) {
-        c->n_pairs = 0;
         if (int rc = reserve_pairs(c, total * 8)) return rc;
     }
     const fsea_detail::HostStaging::Part parts[3] = {{o.points, IMAGE_BYTES}, {o.lines, line_pixels(o)}, {o.pairs, total * 8}};
@@ -122,6 +131,7 @@ int host_call(fsea_chain *c, bool run, const void *in, int f64, size_t n, const 
         in_bytes, parts, [&](void *h_in) { std::memcpy(h_in, in, in_bytes); },
         [&](void *d_in, void **d_parts, hipStream_t s) {
             if (run) {
+                c->n_pairs = 0;   // from here on the buffer is being overwritten
                 if (int rc = queue_filter(c, f64, d_in, n, 1, st, s)) return rc;
                 c->n_pairs = total;
             }
@@ -200,9 +210,10 @@ int fsea_chain_run_device(fsea_chain *c, const void *d_iq, size_t n_samples, int
     const size_t total = n_samples + st.n_zero;
     std::lock_guard<std::mutex> lock(c->mu);
     FSEA_ON_DEVICE(c->device);
-    c->n_pairs = 0;
     rc = reserve_pairs(c, total * 8 * (size_t)n_frames);
-    if (!rc) rc = queue_filter(c, 0, d_iq, n_samples, n_frames, st, s);
+    if (rc) return rc;
+    c->n_pairs = 0;   // from here on the buffer is being overwritten
+    rc = queue_filter(c, 0, d_iq, n_samples, n_frames, st, s);
     if (rc) return rc;
     c->n_pairs = total;
     rc = queue_images(c, n_frames, o, o.points, o.lines, s);

@@ -316,8 +316,8 @@ int fsea_detail::fir_launch_device(fsea_fir *f, int f64, const void *d_in, size_
     if (n_zero && !shift) return fail(FSEA_EINVAL, "zero samples follow a shifted block only");
     if (n_in > ((size_t)1 << 40) || n_zero > ((size_t)1 << 40)) return fail(FSEA_EINVAL, "n_samples %zu too large", n_in);
     const size_t n = n_in + n_zero;
-    if (shift) {
-        int rc = check_shift(shift->cycles_per_sample, shift->phase0_cycles, shift->sample_offset, n);
+    if (shift) {   // the n_in samples of the input have stream positions; the zeros behind them have none
+        int rc = check_shift(shift->cycles_per_sample, shift->phase0_cycles, shift->sample_offset, n_in);
         if (rc) return rc;
     }
     if (n == 0) return FSEA_OK;

@@ -55,9 +55,17 @@ __device__ __forceinline__ cf pk_tap_fma_hi_v(cf w, cf taps, cf acc) {
     return t;
 }
 
-// e^{2 pi i (phase0 + delta P)} for a stream position P: delta * P is the exact sum of the rounded product and its fma
-// residual, so the reduced phase is good to ~2^-50 turns whatever P (P < 2^52 is exact as a double); float only then
+// e^{2 pi i (phase0 + delta P)} for a stream position P <= 2^52 (exact as a double): delta * P is the exact sum of the
+// rounded product hi and its fma residual lo.  hi is reduced modulo 1 exactly; lo is added to phase0 as it is, |lo| <=
+// ulp(hi) / 2.  While |delta P| < 2^53 (|delta| <= 0.5 at every P) lo is below 1 and the reduced phase is within about
+// 2^-50 turns of the exact one (measured: 2^-52).  Beyond that lo grows to 2^19 at |delta| = 2^20, P = 2^52, and the two
+// sums round at its size: no worse than 2^-35 turns by that argument, 2^-36 measured (DESIGN.md section 6,
+// tests/test_shift_ref_host.py, which holds this arithmetic to 2^-30).  The float conversion that follows rounds to 2^-25.
+// No contraction in here: device code is compiled with -ffp-contract=fast, __dmul_rn is a plain multiplication to the
+// compiler, and hi - floor(hi) was fused into fma(delta, k, -floor(hi)) -- the fraction of the EXACT product, to which lo
+// was then added a second time: an error of lo, that of one rounded product (tests/test_gpu_shift_domain.py found it).
 __device__ __forceinline__ cf rot_base(const FirRot &r, long long P) {
+#pragma clang fp contract(off)
     const double k = (double)P;
     const double hi = __dmul_rn(r.delta, k);
     const double lo = fma(r.delta, k, -hi);
@@ -175,9 +183,10 @@ inline FirRot make_rot(double cycles_per_sample, double phase0_cycles, uint64_t 
 }
 
 inline int check_shift(double cycles_per_sample, double phase0_cycles, uint64_t offset, size_t n) {
-    if (!(std::fabs(cycles_per_sample) <= FIR_MAX_CYCLES) || !std::isfinite(phase0_cycles)) {
-        return fsea_detail::fail(FSEA_EINVAL, "cycles_per_sample must be finite and within +-%g, phase0_cycles finite", FIR_MAX_CYCLES);
+    if (!(std::fabs(cycles_per_sample) <= FIR_MAX_CYCLES)) {
+        return fsea_detail::fail(FSEA_EINVAL, "cycles_per_sample must be finite and within +-%g", FIR_MAX_CYCLES);
     }
+    if (!std::isfinite(phase0_cycles)) return fsea_detail::fail(FSEA_EINVAL, "phase0_cycles must be finite");
     if (offset > FIR_MAX_POSITION || n > FIR_MAX_POSITION - offset) {
         return fsea_detail::fail(FSEA_EINVAL, "sample_offset + n_samples must not exceed 2^52");
     }

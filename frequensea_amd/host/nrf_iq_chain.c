@@ -54,13 +54,25 @@ void nrf_iq_chain_set_shifter(nrf_iq_chain *chain, int freq_offset) {
     pthread_mutex_unlock(&chain->mutex);
 }
 
+/* The phase, in [0, 1) cycles, of stream position `position` (< 2^53: exact as a double): cycles_per_sample * position as
+ * the exact sum of the rounded product and its fma residual, the product reduced modulo 1 before the residual is added --
+ * the two-term reduction of the U8 path's kernel (fsea_fir_stage.h: rot_base) with phase0 = 0, so both inputs of the block
+ * are rotated by the same phase however long the stream.  One rounded product alone is off by 1e-5 cycles at 2^40. */
+static double phase_cycles(double cycles_per_sample, unsigned long long position) {
+    const double k = (double)position;
+    const double hi = cycles_per_sample * k;
+    const double lo = fma(cycles_per_sample, k, -hi);
+    double turns = (hi - floor(hi)) + lo;
+    turns -= floor(turns);
+    return turns;
+}
+
 /* nrf_freq_shifter_process on an F64 buffer: 2 * length pairs, the first `length` rotated + 0.5, the rest 0.0 */
 static double *shifted_f64(const nrf_iq_chain *chain, const nut_buffer *buffer, double cycles_per_sample) {
     const int length = buffer->length;
     double *out = (double *)nrf_private_calloc(BLOCK, (size_t)(length > 0 ? length : 1) * 4, sizeof(double));
     for (int k = 0; k < length; k++) {
-        double turns = (double)(chain->consumed + (unsigned long long)k) * cycles_per_sample;
-        turns -= floor(turns);
+        const double turns = phase_cycles(cycles_per_sample, chain->consumed + (unsigned long long)k);
         const double c = cos(TWO_PI * turns), s = sin(TWO_PI * turns);
         const double vi = buffer->data.f64[2 * k], vq = buffer->data.f64[2 * k + 1];
         out[2 * k] = vi * c - vq * s + 0.5;

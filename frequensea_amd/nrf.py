@@ -87,6 +87,19 @@ class NrfInterpolator(ctypes.Structure):
                 ("buffer_a", NutBufferP), ("buffer_b", NutBufferP)]
 
 
+class NrfIqChain(ctypes.Structure):
+    """nrf_iq_chain (include/nrf.h): the members up to `consumed`, the stream position a test may set."""
+    _fields_ = [("block", NrfBlock), ("sample_rate", ctypes.c_int), ("length", ctypes.c_int), ("shifting", ctypes.c_int),
+                ("freq_offset", ctypes.c_int), ("consumed", ctypes.c_ulonglong)]
+
+
+class NrfZoomFft(ctypes.Structure):
+    """nrf_zoom_fft (include/nrf.h): the members up to `consumed`."""
+    _fields_ = [("block", NrfBlock), ("sample_rate", ctypes.c_int), ("freq_offset", ctypes.c_int),
+                ("decimation", ctypes.c_int), ("fft_size", ctypes.c_int), ("fft_history_size", ctypes.c_int),
+                ("consumed", ctypes.c_ulonglong)]
+
+
 class NrfDeviceConfig(ctypes.Structure):
     """nrf_device_config (include/nrf.h)."""
     _fields_ = [("sample_rate", ctypes.c_int), ("freq_mhz", ctypes.c_double), ("data_file", ctypes.c_char_p)]

@@ -376,11 +376,14 @@ int fsea_fir_f64_host(fsea_fir *fir, const double *iq, size_t n_samples, float *
  * calls consumed as sample_offset (0 for the first call) -- do NOT add m * cycles_per_sample into phase0_cycles, the sum
  * would round differently from call to call.  The phasor of a sample is a function of (cycles_per_sample, phase0_cycles, P)
  * alone: P * cycles_per_sample is formed as an exact two-term product, reduced modulo 1 together with phase0_cycles in
- * double (good to ~2^-50 cycles for every P) and only then evaluated in float.  So a stream cut into calls of any lengths
- * gives the one-call result bit for bit, as for the unshifted forms.
+ * double and only then evaluated in float.  The reduced phase is within about 2^-50 cycles of the exact one while
+ * |cycles_per_sample * P| < 2^53 (every P at |cycles_per_sample| <= 0.5); at the limits of the domain (|cycles_per_sample|
+ * near 2^20, P near 2^52) it is no worse than 2^-35 cycles, 2^-36 measured -- still a thousandth of the 2^-25 the float
+ * conversion rounds to (tests/test_shift_ref_host.py holds it to 2^-30 over the whole domain).  So a stream cut into calls
+ * of any lengths gives the one-call result bit for bit, as for the unshifted forms.
  * FSEA_EINVAL (before any device work) for a NULL pointer, a misaligned device buffer, a non-finite phase0_cycles, a
- * cycles_per_sample that is not finite or beyond +-2^20, or sample_offset + n_samples > 2^52.  Other arguments as
- * fsea_fir_u8_device / fsea_fir_u8_host. */
+ * cycles_per_sample that is not finite or beyond +-2^20, or sample_offset + n_samples > 2^52 (the last sample may stand at
+ * position 2^52 - 1).  Other arguments as fsea_fir_u8_device / fsea_fir_u8_host. */
 int fsea_fir_u8_shifted_device(fsea_fir *fir, const void *d_iq, size_t n_samples, int flip, double cycles_per_sample,
                                double phase0_cycles, uint64_t sample_offset, void *d_out, void *stream);
 int fsea_fir_u8_shifted_host(fsea_fir *fir, const uint8_t *iq, size_t n_samples, int flip, double cycles_per_sample,
@@ -440,8 +443,12 @@ int fsea_iq_lines_host(fsea_iq_draw *draw, const void *iq, int type, int flip, s
  *               filter launch; with them one per block, which then needs n_samples a multiple of 8 and n_zero even
  *               (16-byte-aligned pieces).  The filtered pairs pass through the object's buffer: runs on several streams
  *               are the caller's to order.  d_iq and every output 16-byte aligned.
- * Every form checks its arguments before any device work (FSEA_EINVAL as the calls it is made of; more than 2^31 pairs per
- * frame).  Create: as fsea_fir_create, FSEA_ENODEVICE without a GPU.  Destroy and reset (a zero tail) wait for the device.
+ * Every form checks its arguments before any device work and before it looks into the object (FSEA_EINVAL as the calls it
+ * is made of; more than 2^31 pairs per frame).  With shift != 0 that includes the limits of fsea_fir_u8_shifted_* for the
+ * whole call: frame f stands at sample_offset + f * n_samples -- the n_zero samples are no samples of the stream and do not
+ * count -- so sample_offset + n_frames * n_samples <= 2^52.  With shift == 0 cycles_per_sample, phase0_cycles and
+ * sample_offset are not looked at.  A refused call changes nothing: the resident block, fsea_chain_n_pairs, the filter's
+ * tail and the caller's outputs are as before it.  Create: as fsea_fir_create, FSEA_ENODEVICE without a GPU.  Destroy and reset (a zero tail) wait for the device.
  * Calls on one object from several threads are serialised. */
 typedef struct {
     int flip;                 /* != 0: raw HackRF int8 bytes */

@@ -304,7 +304,8 @@ nut_buffer *nrf_buffer_to_iq_lines(nut_buffer *buffer, int size_multiplier, floa
  *     filters N rotated pairs and N zero pairs, get_buffer has 2N pairs and the images are drawn over all of them.  The
  *     phase after M consumed samples is M * freq_offset / sample_rate cycles, M an integer kept here (the reference steps a
  *     (cos, sin) pair; the two agree to ~1e-12 over a scene's run, the filter's f32 arithmetic is ~1e-7).
- * F64 input takes a host-staged path (rotated here in double when a shifter is set).  A kernel length outside
+ * F64 input takes a host-staged path (rotated here in double when a shifter is set, by the phase of the U8 path: M *
+ * freq_offset / sample_rate reduced modulo 1 as an exact two-term product, not one rounded product).  A kernel length outside
  * [1, FSEA_FIR_MAX_TAPS] prints and exits, as does a size_multiplier outside [1, FSEA_IQ_MAX_MULTIPLIER] and a backend
  * failure (no GPU).  The getters return NULL before the first process call; their buffers are the caller's to free. */
 typedef struct {
