@@ -33,15 +33,15 @@
 // The _narrow kernels are the same code with every cell loaded on its own (any pitch and base).  In the 16-byte kernels a
 // group that would end past the row's width is loaded cell by cell too, so no load passes the width; the mask is written 16
 // bytes per lane where the width is a multiple of 16 and byte by byte otherwise.
-#include "fsea_internal.h"
+#include "fsea_rows.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <type_traits>
 
 using fsea_detail::DeviceGuard;
+using fsea_detail::cfar_level_f32;
 using fsea_detail::fail;
+using fsea_detail::run_of_workgroup;
 
 namespace {
 
@@ -53,30 +53,18 @@ constexpr int CF_HALO = FSEA_CFAR_MAX_GUARD + FSEA_CFAR_MAX_TRAIN;
 constexpr int CF_SEG = CF_C + 2 * CF_HALO + 16;   // cells of a staged segment at most (a0 is rounded down by up to 15)
 constexpr int CF_FRONT = (CF_HALO + 1 + 15) & ~15;   // zero dwords in front of a wave's prefix array: the cells before the row
 constexpr int CF_Q = CF_FRONT + CF_SEG;           // dwords of a wave's prefix array
-constexpr int CF_LIMIT = 1 << 20;                 // |level| of an f32 cell at most
-constexpr size_t CF_MAX_ROWS = (size_t)1 << 31;   // rows of one call
-constexpr size_t CF_STAGE_BYTES = (size_t)64 << 20;   // the host form's chunk
 static_assert(CF_SEG % 16 == 0, "whole 16-byte groups");
 static_assert(CF_C == 16 * 64, "a wave decides a row of the tile in 16 steps; a lane stores 16 mask bytes");
 static_assert(CF_RUN % CF_WAVES == 0 && CF_RUN / CF_WAVES <= 255, "a run is whole iterations of the four waves; a lane counts a column in a byte");
 static_assert((CF_WAVES * (CF_Q + CF_C) + CF_C) * 4 <= 80 * 1024, "two workgroups per CU");
-static_assert(FSEA_CFAR_F32_SCALE == 64 && FSEA_CFAR_MAX_OFFSET == CF_LIMIT, "the 32-bit bounds of the decision");
 
 struct Settings {
     int guard, train, offset, method;
 };
 
-// level of an f32 element: one rounded multiplication, round half to even; the clamp for a NaN
-__device__ __forceinline__ int level_f32(float v) {
-    const float t = __fmul_rn(v, (float)FSEA_CFAR_F32_SCALE);
-    if (t != t || t <= (float)-CF_LIMIT) return -CF_LIMIT;
-    if (t >= (float)CF_LIMIT) return CF_LIMIT;
-    return (int)rintf(t);
-}
-
 template <bool F32>
 __device__ __forceinline__ int level_at(const void *__restrict__ rows, size_t i) {
-    if (F32) return level_f32(static_cast<const float *>(rows)[i]);
+    if (F32) return cfar_level_f32(static_cast<const float *>(rows)[i]);
     return (int)static_cast<const uint8_t *>(rows)[i];
 }
 
@@ -96,7 +84,7 @@ __device__ __forceinline__ void levels_of(const void *__restrict__ rows, size_t 
         const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
         for (int e = 0; e < EPG; ++e) {
-            if (F32) lv[e] = live ? level_f32(__uint_as_float(ws[e & 3])) : 0;
+            if (F32) lv[e] = live ? cfar_level_f32(__uint_as_float(ws[e & 3])) : 0;
             else lv[e] = (int)((ws[e >> 2] >> (8 * (e & 3))) & 0xffu);
         }
         return;
@@ -126,9 +114,8 @@ __device__ __forceinline__ void cfar_body(const void *__restrict__ rows, size_t 
     const int e1 = min(width, c0 + CF_C + G + T);
     const int ngrp = (c0 + CF_C + G + T - a0 + EPG - 1) / EPG; // ... and the groups up to the last cell a window may name
     const bool inner = c0 - G - T >= 0 && c0 + CF_C + G + T <= width;
-    const size_t row0 = (size_t)blockIdx.x * CF_RUN;
-    const size_t left = n_rows - row0;
-    const int run = left < (size_t)CF_RUN ? (int)left : CF_RUN;
+    size_t row0;
+    const int run = run_of_workgroup<CF_RUN>(n_rows, &row0);
 
     for (int i = tid; i < CF_C; i += CF_WG) total[i] = 0u;
     for (int i = lane; i < CF_FRONT; i += 64) q[i] = 0u;       // the cells before the row and before the segment
@@ -279,39 +266,14 @@ FSEA_CFAR_KERNEL(fsea_cfar_u8_narrow, false, false)
 FSEA_CFAR_KERNEL(fsea_cfar_f32_narrow, true, false)
 #undef FSEA_CFAR_KERNEL
 
-// `width` and `rows` lead the struct: tests/test_cfar_host.py reaches the checks that read them with a fake object
-struct fsea_cfar {
-    int width = 0;
-    int device = 0;
-    uint64_t rows = 0;                            // rows offered since create or reset
+struct fsea_cfar : fsea_detail::RowObject {
     Settings set{2, 16, 60, FSEA_CFAR_CA};
-    fsea_detail::SharedScratch hits;              // width u32; its event orders the calls
+    fsea_detail::ZeroedScratch hits;              // width u32; its event orders the calls
     std::mutex mu;
     fsea_detail::HostStaging staging;             // the host forms
 };
 
 namespace {
-
-size_t elem_bytes(int type) { return type == FSEA_CFAR_F32 ? 4 : 1; }
-
-int check_add(const fsea_cfar *c, const void *rows, int type, size_t n_rows, size_t pitch) {
-    if (!c) return fail(FSEA_EINVAL, "cfar is NULL");
-    if (type != FSEA_CFAR_U8 && type != FSEA_CFAR_F32) return fail(FSEA_EINVAL, "unknown row type %d", type);
-    if (n_rows > CF_MAX_ROWS) return fail(FSEA_EINVAL, "n_rows %zu is more than 2^31", n_rows);
-    if (n_rows == 0) return FSEA_OK;
-    if (!rows) return fail(FSEA_EINVAL, "NULL buffer for the %zu rows of the call", n_rows);
-    if (pitch < (size_t)c->width) return fail(FSEA_EINVAL, "pitch %zu is below the width %d", pitch, c->width);
-    if (pitch > ((size_t)1 << 40) / n_rows) return fail(FSEA_EINVAL, "pitch %zu x n_rows %zu is too large", pitch, n_rows);
-    return FSEA_OK;
-}
-
-// the caller holds c->mu
-int check_room(const fsea_cfar *c, size_t n_rows) {
-    if (c->rows + n_rows > 0xffffffffull) {
-        return fail(FSEA_EINVAL, "n_rows %zu would take rows past 2^32 - 1 (%llu so far)", n_rows, (unsigned long long)c->rows);
-    }
-    return FSEA_OK;
-}
 
 // One add on device rows, asynchronous on `s`.  The caller holds c->mu, is on c's device and has checked the arguments.
 int add_launch(fsea_cfar *c, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask, uint32_t *d_row_hits,
@@ -322,8 +284,7 @@ int add_launch(fsea_cfar *c, const void *d_rows, int type, size_t n_rows, size_t
     const int width = c->width;
     if (d_row_hits) FSEA_HIP(hipMemsetAsync(d_row_hits, 0, n_rows * sizeof(uint32_t), s));   // set, not added to
     const dim3 grid((unsigned)((n_rows + CF_RUN - 1) / CF_RUN), (unsigned)((width + CF_C - 1) / CF_C));
-    const size_t esz = elem_bytes(type);
-    const bool vec = ((uintptr_t)d_rows & 15) == 0 && (pitch * esz) % 16 == 0;
+    const bool vec = fsea_detail::rows_vec16(d_rows, pitch * fsea_detail::row_elem_bytes(type));
     const int mask_vec = width % 16 == 0;
     const Settings st = c->set;
     auto kernel = type == FSEA_CFAR_U8 ? (vec ? fsea_cfar_u8 : fsea_cfar_u8_narrow) : (vec ? fsea_cfar_f32 : fsea_cfar_f32_narrow);
@@ -346,13 +307,7 @@ int fsea_cfar_create(fsea_cfar **out, int width, int device) {
     }
     return fsea_detail::create_object(out, device, "fsea_cfar_create", [&](fsea_cfar *c) -> int {
         c->width = width;
-        const size_t bytes = (size_t)width * sizeof(uint32_t);
-        hipError_t e = c->hits.create(c->staging.stream);
-        if (e != hipSuccess) return fsea_detail::init_code("fsea_cfar_create", e);
-        if (int rc = c->hits.reserve(bytes)) return rc;
-        e = hipMemset(c->hits.buf.ptr, 0, bytes);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        return fsea_detail::init_code("fsea_cfar_create", e);
+        return c->hits.create_zeroed("fsea_cfar_create", (size_t)width * sizeof(uint32_t), c->staging.stream);
     });
 }
 
@@ -361,8 +316,7 @@ int fsea_cfar_destroy(fsea_cfar *c) { return fsea_detail::destroy_object(c); }
 int fsea_cfar_reset(fsea_cfar *c) {
     return fsea_detail::reset_object(c, "cfar is NULL", [&] {
         c->rows = 0;
-        FSEA_HIP(hipMemset(c->hits.buf.ptr, 0, (size_t)c->width * sizeof(uint32_t)));
-        return (int)FSEA_OK;
+        return c->hits.zero();
     });
 }
 
@@ -385,49 +339,36 @@ uint64_t fsea_cfar_rows(const fsea_cfar *c) { return c ? c->rows : 0; }
 
 int fsea_cfar_add_device(fsea_cfar *c, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask,
                          uint32_t *d_row_hits, void *stream) {
-    int rc = check_add(c, d_rows, type, n_rows, pitch);
+    int rc = fsea_detail::check_rows_add(c, "cfar", d_rows, type, n_rows, pitch);
     if (!rc && n_rows) rc = fsea_detail::check_aligned16("d_rows, d_mask and d_row_hits", d_rows, d_mask, d_row_hits);
     if (rc) return rc;
     if (n_rows == 0) return FSEA_OK;
     std::lock_guard<std::mutex> lock(c->mu);
-    if ((rc = check_room(c, n_rows))) return rc;
+    if ((rc = fsea_detail::check_rows_room(c, n_rows))) return rc;
     FSEA_ON_DEVICE(c->device);
     return add_launch(c, d_rows, type, n_rows, pitch, d_mask, d_row_hits, static_cast<hipStream_t>(stream));
 }
 
 int fsea_cfar_add_host(fsea_cfar *c, const void *rows, int type, size_t n_rows, size_t pitch, uint8_t *mask, uint32_t *row_hits) {
-    int rc = check_add(c, rows, type, n_rows, pitch);
+    int rc = fsea_detail::check_rows_add(c, "cfar", rows, type, n_rows, pitch);
     if (rc) return rc;
     if (n_rows == 0) return FSEA_OK;
     std::lock_guard<std::mutex> lock(c->mu);
-    if ((rc = check_room(c, n_rows))) return rc;
+    if ((rc = fsea_detail::check_rows_room(c, n_rows))) return rc;
     FSEA_ON_DEVICE(c->device);
-    // the rows go up packed, at a pitch of whole 16-byte groups, in chunks of at most CF_STAGE_BYTES; mask and row hits of a
-    // chunk come back behind it
-    const size_t width = (size_t)c->width;
-    const size_t esz = elem_bytes(type), row_bytes = width * esz, packed = (row_bytes + 15) & ~(size_t)15;
-    const size_t chunk = std::max<size_t>(1, CF_STAGE_BYTES / packed);
-    for (size_t r0 = 0; r0 < n_rows; r0 += chunk) {
-        const size_t nr = std::min(chunk, n_rows - r0);
-        const char *src = static_cast<const char *>(rows) + r0 * pitch * esz;
+    // the rows go up packed, in chunks; mask and row hits of a chunk come back behind it
+    const size_t width = (size_t)c->width, esz = fsea_detail::row_elem_bytes(type);
+    const fsea_detail::PackedPlane in(rows, pitch * esz, width * esz);
+    return fsea_detail::for_row_chunks(n_rows, in.packed, [&](size_t r0, size_t nr) {
         const fsea_detail::HostStaging::Part parts[2] = {{mask ? mask + r0 * width : nullptr, nr * width},
                                                          {row_hits ? row_hits + r0 : nullptr, nr * sizeof(uint32_t)}};
-        rc = c->staging.run(
-            nr * packed, parts,
-            [&](void *h_in) {
-                char *dst = static_cast<char *>(h_in);
-                for (size_t r = 0; r < nr; ++r) {
-                    std::memcpy(dst + r * packed, src + r * pitch * esz, row_bytes);
-                    std::memset(dst + r * packed + row_bytes, 0, packed - row_bytes);
-                }
-            },
+        return c->staging.run(
+            nr * in.packed, parts, [&](void *h_in) { in.pack(h_in, r0, nr); },
             [&](void *d_in, void **d_parts, hipStream_t s) {
-                return add_launch(c, d_in, type, nr, packed / esz, static_cast<uint8_t *>(d_parts[0]),
+                return add_launch(c, d_in, type, nr, in.packed / esz, static_cast<uint8_t *>(d_parts[0]),
                                   static_cast<uint32_t *>(d_parts[1]), s);
             });
-        if (rc) return rc;
-    }
-    return FSEA_OK;
+    });
 }
 
 int fsea_cfar_hits_host(fsea_cfar *c, uint32_t *hits) {
@@ -435,11 +376,7 @@ int fsea_cfar_hits_host(fsea_cfar *c, uint32_t *hits) {
     if (!hits) return fail(FSEA_EINVAL, "hits is NULL");
     std::lock_guard<std::mutex> lock(c->mu);
     FSEA_ON_DEVICE(c->device);
-    const fsea_detail::HostStaging::Part part[1] = {{hits, (size_t)c->width * sizeof(uint32_t)}};
-    return c->staging.run(0, part, [](void *) {}, [&](void *, void **d_parts, hipStream_t s) {
-        d_parts[0] = c->hits.buf.ptr;        // the object's own memory, behind every add queued so far
-        return c->hits.acquire(s);
-    });
+    return c->hits.fetch(c->staging, hits);
 }
 
 int fsea_cfar_bands(const uint32_t *hits, int width, uint64_t rows, double min_fraction, int max_gap, int min_width,

@@ -30,15 +30,14 @@
 //
 // fsea_events_paint: one wave per run stores the run's value over first .. last of its image row, 16 bytes per lane in the
 // aligned middle and single bytes at both ends, behind a zero fill of the image rows.
-#include "fsea_internal.h"
+#include "fsea_rows.h"
 
-#include <algorithm>
 #include <climits>
-#include <cstring>
 #include <type_traits>
 #include <vector>
 
 using fsea_detail::DeviceGuard;
+using fsea_detail::cfar_level_f32;
 using fsea_detail::fail;
 
 static_assert(sizeof(fsea_events_run) == 32 && sizeof(fsea_events_event) == 48, "the records of include/fsea.h");
@@ -50,20 +49,7 @@ constexpr int EV_WAVES = EV_WG / 64;              // rows (runs, for the paint) 
 constexpr int EV_CHUNK = 64 * 16;                 // cells of a wave's step along its row
 constexpr int EV_NONE = -(1 << 29);               // "no hit so far": far enough below column 0 for any G, no overflow
 constexpr int EV_TILE = 4 * EV_WG;                // rows whose counts one workgroup of the scan adds up
-constexpr int EV_LIMIT = 1 << 20;                 // |level| of an f32 cell at most
-constexpr size_t EV_MAX_ROWS = (size_t)1 << 31;   // rows of one call
-constexpr size_t EV_STAGE_BYTES = (size_t)64 << 20;   // the host forms' chunk
-static_assert(FSEA_CFAR_F32_SCALE == 64 && FSEA_CFAR_MAX_OFFSET == EV_LIMIT, "the levels are fsea_cfar's");
 static_assert(FSEA_EVENTS_MAX_GAP_COLS < EV_CHUNK && FSEA_EVENTS_MAX_WIDTH <= (1 << 20), "positions and sums stay in range");
-
-// fsea_cfar's level of an f32 element (fsea_cfar.hip: level_f32): one rounded multiplication, round half to even, the clamp
-// for a NaN
-__device__ __forceinline__ int level_f32(float v) {
-    const float t = __fmul_rn(v, (float)FSEA_CFAR_F32_SCALE);
-    if (t != t || t <= (float)-EV_LIMIT) return -EV_LIMIT;
-    if (t >= (float)EV_LIMIT) return EV_LIMIT;
-    return (int)rintf(t);
-}
 
 // bit i of the result: byte i of w is not zero
 __device__ __forceinline__ uint32_t nonzero4(uint32_t w) {
@@ -230,10 +216,10 @@ __device__ __forceinline__ void runs_body(const uint8_t *__restrict__ mask, size
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const uint4 w = src[q];
-                        lv[4 * q] = level_f32(__uint_as_float(w.x));
-                        lv[4 * q + 1] = level_f32(__uint_as_float(w.y));
-                        lv[4 * q + 2] = level_f32(__uint_as_float(w.z));
-                        lv[4 * q + 3] = level_f32(__uint_as_float(w.w));
+                        lv[4 * q] = cfar_level_f32(__uint_as_float(w.x));
+                        lv[4 * q + 1] = cfar_level_f32(__uint_as_float(w.y));
+                        lv[4 * q + 2] = cfar_level_f32(__uint_as_float(w.z));
+                        lv[4 * q + 3] = cfar_level_f32(__uint_as_float(w.w));
                     }
                 }
             } else {
@@ -241,7 +227,7 @@ __device__ __forceinline__ void runs_body(const uint8_t *__restrict__ mask, size
                 for (int e = 0; e < 16; ++e) {
                     if ((hb >> e) & 1u) {
                         lv[e] = LV == 1 ? (int)static_cast<const uint8_t *>(levels)[lrow + cell + e]
-                                        : level_f32(static_cast<const float *>(levels)[lrow + cell + e]);
+                                        : cfar_level_f32(static_cast<const float *>(levels)[lrow + cell + e]);
                     }
                 }
             }
@@ -424,11 +410,8 @@ extern "C" __global__ __launch_bounds__(EV_WG) void fsea_events_paint(const fsea
     if (m1 + lane < b) dst[m1 + lane] = (uint8_t)v;                            // ... and behind
 }
 
-// `width`, `rows` and `gap` lead the struct: tests/test_events_host.py reaches the checks that read them with a fake object
-struct fsea_events {
-    int width = 0;
-    int device = 0;
-    uint64_t rows = 0;                            // rows offered since create or reset
+// `gap` follows the common head: tests/test_events_host.py reads it from its fake object
+struct fsea_events : fsea_detail::RowObject {
     int gap = 0;
     fsea_detail::SharedScratch scratch;           // the row counts and the tile sums of a call; its event orders the calls
     fsea_detail::MappedBuffer h_total;            // where a call's count arrives: the scan stores it into host memory itself
@@ -439,31 +422,15 @@ struct fsea_events {
 
 namespace {
 
-size_t elem_bytes(int type) { return type == FSEA_CFAR_F32 ? 4 : 1; }
-
 int check_runs(const fsea_events *ev, const uint8_t *mask, size_t mask_pitch, const void *levels, int type, size_t level_pitch,
                size_t n_rows, const fsea_events_run *runs, size_t capacity, size_t *n_runs) {
     if (!ev) return fail(FSEA_EINVAL, "events is NULL");
     if (!n_runs) return fail(FSEA_EINVAL, "n_runs is NULL");
-    if (type != FSEA_CFAR_U8 && type != FSEA_CFAR_F32) return fail(FSEA_EINVAL, "unknown level type %d", type);
-    if (n_rows > EV_MAX_ROWS) return fail(FSEA_EINVAL, "n_rows %zu is more than 2^31", n_rows);
+    if (int rc = fsea_detail::check_rows_head("level", type, n_rows)) return rc;
     if (!runs && capacity) return fail(FSEA_EINVAL, "NULL buffer for a capacity of %zu runs", capacity);
     if (n_rows == 0) return FSEA_OK;
-    if (!mask) return fail(FSEA_EINVAL, "NULL buffer for the %zu mask rows of the call", n_rows);
-    if (mask_pitch < (size_t)ev->width) return fail(FSEA_EINVAL, "mask pitch %zu is below the width %d", mask_pitch, ev->width);
-    if (levels && level_pitch < (size_t)ev->width) return fail(FSEA_EINVAL, "level pitch %zu is below the width %d", level_pitch, ev->width);
-    if (mask_pitch > ((size_t)1 << 40) / n_rows || (levels && level_pitch > ((size_t)1 << 40) / n_rows)) {
-        return fail(FSEA_EINVAL, "pitch x n_rows %zu is too large", n_rows);
-    }
-    return FSEA_OK;
-}
-
-// the caller holds ev->mu
-int check_room(const fsea_events *ev, size_t n_rows) {
-    if (ev->rows + n_rows > 0xffffffffull) {
-        return fail(FSEA_EINVAL, "n_rows %zu would take rows past 2^32 - 1 (%llu so far)", n_rows, (unsigned long long)ev->rows);
-    }
-    return FSEA_OK;
+    const fsea_detail::RowPlane m{mask, "mask pitch", mask_pitch}, l{levels, "level pitch", level_pitch};
+    return fsea_detail::check_rows_planes(ev->width, n_rows, "mask ", m, &l);
 }
 
 struct RowsArgs {
@@ -473,8 +440,8 @@ struct RowsArgs {
     int type;
     size_t level_pitch, n_rows;
     bool vec() const {
-        return ((uintptr_t)mask & 15) == 0 && mask_pitch % 16 == 0 &&
-               (!levels || (((uintptr_t)levels & 15) == 0 && (level_pitch * elem_bytes(type)) % 16 == 0));
+        return fsea_detail::rows_vec16(mask, mask_pitch) &&
+               (!levels || fsea_detail::rows_vec16(levels, level_pitch * fsea_detail::row_elem_bytes(type)));
     }
 };
 
@@ -533,14 +500,11 @@ int runs_launch(fsea_events *ev, const RowsArgs &a, fsea_events_run *d_runs, siz
 int check_paint(const fsea_events *ev, const fsea_events_run *runs, const uint8_t *values, size_t n_runs, size_t n_rows,
                 const uint8_t *image, size_t pitch) {
     if (!ev) return fail(FSEA_EINVAL, "events is NULL");
-    if (n_rows > EV_MAX_ROWS) return fail(FSEA_EINVAL, "n_rows %zu is more than 2^31", n_rows);
+    if (int rc = fsea_detail::check_rows_head(nullptr, 0, n_rows)) return rc;
     if (n_runs > ((size_t)1 << 32)) return fail(FSEA_EINVAL, "n_runs %zu is more than 2^32", n_runs);
     if (n_runs && (!runs || !values)) return fail(FSEA_EINVAL, "NULL buffer for the %zu runs of the call", n_runs);
     if (n_rows == 0) return FSEA_OK;
-    if (!image) return fail(FSEA_EINVAL, "NULL buffer for the %zu image rows of the call", n_rows);
-    if (pitch < (size_t)ev->width) return fail(FSEA_EINVAL, "pitch %zu is below the width %d", pitch, ev->width);
-    if (pitch > ((size_t)1 << 40) / n_rows) return fail(FSEA_EINVAL, "pitch %zu x n_rows %zu is too large", pitch, n_rows);
-    return FSEA_OK;
+    return fsea_detail::check_rows_planes(ev->width, n_rows, "image ", fsea_detail::RowPlane{image, "pitch", pitch});
 }
 
 // the zero fill and the runs, asynchronous on `s`
@@ -616,7 +580,7 @@ int fsea_events_runs_device(fsea_events *ev, const uint8_t *d_mask, size_t mask_
     *n_runs = 0;
     if (n_rows == 0) return FSEA_OK;
     std::lock_guard<std::mutex> lock(ev->mu);
-    if ((rc = check_room(ev, n_rows))) return rc;
+    if ((rc = fsea_detail::check_rows_room(ev, n_rows))) return rc;
     FSEA_ON_DEVICE(ev->device);
     unsigned long long found = 0;
     rc = runs_launch(ev, RowsArgs{d_mask, mask_pitch, d_levels, type, level_pitch, n_rows}, d_runs, capacity, &found,
@@ -633,28 +597,21 @@ int fsea_events_runs_host(fsea_events *ev, const uint8_t *mask, size_t mask_pitc
     *n_runs = 0;
     if (n_rows == 0) return FSEA_OK;
     std::lock_guard<std::mutex> lock(ev->mu);
-    if ((rc = check_room(ev, n_rows))) return rc;
+    if ((rc = fsea_detail::check_rows_room(ev, n_rows))) return rc;
     FSEA_ON_DEVICE(ev->device);
-    // mask and levels go up packed, at pitches of whole 16-byte groups, in chunks of rows of at most EV_STAGE_BYTES; the
-    // records of a chunk that still fit the capacity come back behind it
+    // mask and levels go up packed, the levels of a chunk behind its mask; the records of a chunk that still fit the
+    // capacity come back behind it
     fsea_detail::HostStaging &st = ev->staging;
-    const size_t width = (size_t)ev->width, esz = elem_bytes(type);
-    const size_t mrow = (width + 15) & ~(size_t)15, lrow = levels ? (width * esz + 15) & ~(size_t)15 : 0;
-    const size_t chunk = std::max<size_t>(1, EV_STAGE_BYTES / (mrow + lrow));
+    const size_t width = (size_t)ev->width, esz = fsea_detail::row_elem_bytes(type);
+    const fsea_detail::PackedPlane m(mask, mask_pitch, width), l(levels, level_pitch * esz, width * esz);
+    const size_t mrow = m.packed, lrow = l.packed;
     size_t found = 0, written = 0;
-    for (size_t r0 = 0; r0 < n_rows; r0 += chunk) {
-        const size_t nr = std::min(chunk, n_rows - r0);
-        if ((rc = st.reserve(nr * (mrow + lrow), 0))) return rc;
+    rc = fsea_detail::for_row_chunks(n_rows, mrow + lrow, [&](size_t r0, size_t nr) -> int {
+        int rc = st.reserve(nr * (mrow + lrow), 0);
+        if (rc) return rc;
         char *h = static_cast<char *>(st.h_in.ptr);
-        for (size_t r = 0; r < nr; ++r) {
-            std::memcpy(h + r * mrow, mask + (r0 + r) * mask_pitch, width);
-            std::memset(h + r * mrow + width, 0, mrow - width);
-            if (levels) {
-                char *l = h + nr * mrow + r * lrow;
-                std::memcpy(l, static_cast<const char *>(levels) + (r0 + r) * level_pitch * esz, width * esz);
-                std::memset(l + width * esz, 0, lrow - width * esz);
-            }
-        }
+        m.pack(h, r0, nr);
+        if (levels) l.pack(h + nr * mrow, r0, nr);
         FSEA_HIP(hipMemcpyAsync(st.d_in.ptr, h, nr * (mrow + lrow), hipMemcpyHostToDevice, st.stream));
         const char *d = static_cast<const char *>(st.d_in.ptr);
         const RowsArgs a{reinterpret_cast<const uint8_t *>(d), mrow, levels ? d + nr * mrow : nullptr, type, lrow / esz, nr};
@@ -671,11 +628,11 @@ int fsea_events_runs_host(fsea_events *ev, const uint8_t *mask, size_t mask_pitc
             written += take;
         }
         ev->rows += nr;
-        if ((rc = ev->scratch.release(st.stream))) return rc;
         found += (size_t)here;
-    }
-    *n_runs = found;
-    return FSEA_OK;
+        return ev->scratch.release(st.stream);
+    });
+    if (!rc) *n_runs = found;
+    return rc;
 }
 
 int fsea_events_link(const fsea_events_run *runs, size_t n_runs, int gap_cols, int gap_rows, uint32_t min_rows, uint32_t min_cols,
@@ -790,13 +747,12 @@ int fsea_events_paint_host(fsea_events *ev, const fsea_events_run *runs, const u
     if (n_rows == 0) return FSEA_OK;
     std::lock_guard<std::mutex> lock(ev->mu);
     FSEA_ON_DEVICE(ev->device);
-    // the image comes back tight, in chunks of rows of at most EV_STAGE_BYTES; the runs and their values go up with each
+    // the image comes back tight, in chunks of rows; the runs and their values go up with each
     const size_t width = (size_t)ev->width, run_bytes = n_runs * sizeof(fsea_events_run);
-    const size_t chunk = std::max<size_t>(1, EV_STAGE_BYTES / width);
     fsea_detail::HostStaging &st = ev->staging;
-    for (size_t r0 = 0; r0 < n_rows; r0 += chunk) {
-        const size_t nr = std::min(chunk, n_rows - r0);
-        if ((rc = st.reserve(run_bytes + n_runs, nr * width))) return rc;
+    return fsea_detail::for_row_chunks(n_rows, width, [&](size_t r0, size_t nr) -> int {
+        int rc = st.reserve(run_bytes + n_runs, nr * width);
+        if (rc) return rc;
         if (n_runs) {
             std::memcpy(st.h_in.ptr, runs, run_bytes);
             std::memcpy(static_cast<char *>(st.h_in.ptr) + run_bytes, values, n_runs);
@@ -809,8 +765,8 @@ int fsea_events_paint_host(fsea_events *ev, const fsea_events_run *runs, const u
         FSEA_HIP(hipMemcpyAsync(st.h_out.ptr, st.d_out.ptr, nr * width, hipMemcpyDeviceToHost, st.stream));
         FSEA_HIP(hipStreamSynchronize(st.stream));
         for (size_t r = 0; r < nr; ++r) std::memcpy(image + (r0 + r) * pitch, static_cast<const char *>(st.h_out.ptr) + r * width, width);
-    }
-    return FSEA_OK;
+        return FSEA_OK;
+    });
 }
 
 }  // extern "C"

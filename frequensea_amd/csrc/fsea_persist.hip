@@ -22,14 +22,13 @@
 //
 // fsea_persist_image and fsea_persist_decay_u32 stream over the counts: 16 pixels (four 16-byte loads, one 16-byte store) per
 // lane where the width is a multiple of 16, one pixel otherwise; four counts per lane (256 width is a multiple of 4).
-#include "fsea_internal.h"
+#include "fsea_rows.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstring>
 
 using fsea_detail::DeviceGuard;
 using fsea_detail::fail;
+using fsea_detail::run_of_workgroup;
 
 namespace {
 
@@ -37,8 +36,6 @@ constexpr int PS_WG = 256;                       // lanes per workgroup
 constexpr int PS_C = 64;                         // columns per tile
 constexpr int PS_L = FSEA_PERSIST_LEVELS;        // levels
 constexpr int PS_RUN = FSEA_PERSIST_RUN_ROWS;    // rows per workgroup
-constexpr size_t PS_MAX_ROWS = (size_t)1 << 31;  // rows of one call
-constexpr size_t PS_STAGE_BYTES = (size_t)64 << 20;   // the host form's chunk
 static_assert(PS_L * PS_C * sizeof(uint32_t) <= 80 * 1024, "two workgroups per CU");
 static_assert(PS_RUN % 64 == 0, "a run is whole iterations of the u8 kernel (64 rows) and the f32 kernel (16 rows)");
 
@@ -138,9 +135,8 @@ __device__ __forceinline__ void persist_body(const void *__restrict__ rows, size
     const uint32_t m = (uint32_t)tid % LPR;                    // the lane's group of the row
     const uint32_t s = ((uint32_t)tid / LPR) & (32 / LPR - 1);  // its row within the 32-lane bank group
     const int col = c0 + (int)m * EPG;
-    const size_t row0 = (size_t)blockIdx.x * PS_RUN;
-    const size_t left = n_rows - row0;
-    const int run = left < (size_t)PS_RUN ? (int)left : PS_RUN;
+    size_t row0;
+    const int run = run_of_workgroup<PS_RUN>(n_rows, &row0);
     const bool whole = col + EPG <= width;                     // a group that ends past the width is read by element
     const char *src = static_cast<const char *>(rows);
     const size_t esz = F32 ? 4 : 1;
@@ -185,9 +181,8 @@ __device__ __forceinline__ void persist_narrow_body(const void *__restrict__ row
     const uint32_t cm = (uint32_t)tid & ((1u << lw_log2) - 1u);
     const uint32_t c = lw_log2 == 6 ? rev6(cm) : cm;           // 64 lanes per row: lane m at position m
     const int rpi = PS_WG >> lw_log2;
-    const size_t row0 = (size_t)blockIdx.x * PS_RUN;
-    const size_t left = n_rows - row0;
-    const int run = left < (size_t)PS_RUN ? (int)left : PS_RUN;
+    size_t row0;
+    const int run = run_of_workgroup<PS_RUN>(n_rows, &row0);
     if (c0 + (int)c < width) {
         const uint32_t pos = rev6(c);
         for (int rr = tid >> lw_log2; rr < run; rr += rpi) {
@@ -275,20 +270,15 @@ extern "C" __global__ __launch_bounds__(PS_WG) void fsea_persist_decay_u32(uint4
     counts[i] = c;
 }
 
-// `width` and `rows` lead the struct: tests/test_persist_host.py reaches the checks that read them with a fake object
-struct fsea_persist {
-    int width = 0;
-    int device = 0;
-    uint64_t rows = 0;                            // rows offered since create or reset, scaled by every decay
+// `rows` is scaled by every decay
+struct fsea_persist : fsea_detail::RowObject {
     float lo = -100.0f, hi = 0.0f, scale = 2.56f;
-    fsea_detail::SharedScratch counts;            // 256 x width u32, level-major; its event orders the calls
+    fsea_detail::ZeroedScratch counts;            // 256 x width u32, level-major; its event orders the calls
     std::mutex mu;
     fsea_detail::HostStaging staging;             // the host forms
 };
 
 namespace {
-
-size_t elem_bytes(int type) { return type == FSEA_PERSIST_F32 ? 4 : 1; }
 
 uint64_t host_log_q(uint64_t c) {
     if (!c) return 0;
@@ -296,25 +286,6 @@ uint64_t host_log_q(uint64_t c) {
     while (!(c >> e)) --e;
     const uint64_t m = (e >= 8 ? c >> (e - 8) : c << (8 - e)) & 255u;
     return 256u * (uint64_t)e + m + 1u;
-}
-
-int check_add(const fsea_persist *p, const void *rows, int type, size_t n_rows, size_t pitch) {
-    if (!p) return fail(FSEA_EINVAL, "persist is NULL");
-    if (type != FSEA_PERSIST_U8 && type != FSEA_PERSIST_F32) return fail(FSEA_EINVAL, "unknown row type %d", type);
-    if (n_rows > PS_MAX_ROWS) return fail(FSEA_EINVAL, "n_rows %zu is more than 2^31", n_rows);
-    if (n_rows == 0) return FSEA_OK;
-    if (!rows) return fail(FSEA_EINVAL, "NULL buffer for the %zu rows of the call", n_rows);
-    if (pitch < (size_t)p->width) return fail(FSEA_EINVAL, "pitch %zu is below the width %d", pitch, p->width);
-    if (pitch > ((size_t)1 << 40) / n_rows) return fail(FSEA_EINVAL, "pitch %zu x n_rows %zu is too large", pitch, n_rows);
-    return FSEA_OK;
-}
-
-// the caller holds p->mu
-int check_room(const fsea_persist *p, size_t n_rows) {
-    if (p->rows + n_rows > 0xffffffffull) {
-        return fail(FSEA_EINVAL, "n_rows %zu would take rows past 2^32 - 1 (%llu so far)", n_rows, (unsigned long long)p->rows);
-    }
-    return FSEA_OK;
 }
 
 int check_image(const fsea_persist *p, int map, const void *image) {
@@ -333,8 +304,8 @@ int add_launch(fsea_persist *p, const void *d_rows, int type, size_t n_rows, siz
     uint32_t *counts = static_cast<uint32_t *>(p->counts.buf.ptr);
     const int width = p->width;
     const dim3 grid((unsigned)((n_rows + PS_RUN - 1) / PS_RUN), (unsigned)((width + PS_C - 1) / PS_C));
-    const size_t esz = elem_bytes(type);
-    const bool vec = ((uintptr_t)d_rows & 15) == 0 && (pitch * esz) % 16 == 0 && (size_t)width * esz >= 16;
+    const size_t esz = fsea_detail::row_elem_bytes(type);
+    const bool vec = fsea_detail::rows_vec16(d_rows, pitch * esz) && (size_t)width * esz >= 16;
     int lw_log2 = 0;
     while ((1 << lw_log2) < std::min(width, PS_C)) ++lw_log2;
     if (type == FSEA_PERSIST_U8) {
@@ -375,13 +346,7 @@ int fsea_persist_create(fsea_persist **out, int width, int device) {
     }
     return fsea_detail::create_object(out, device, "fsea_persist_create", [&](fsea_persist *p) -> int {
         p->width = width;
-        const size_t bytes = (size_t)PS_L * width * sizeof(uint32_t);
-        hipError_t e = p->counts.create(p->staging.stream);
-        if (e != hipSuccess) return fsea_detail::init_code("fsea_persist_create", e);
-        if (int rc = p->counts.reserve(bytes)) return rc;
-        e = hipMemset(p->counts.buf.ptr, 0, bytes);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        return fsea_detail::init_code("fsea_persist_create", e);
+        return p->counts.create_zeroed("fsea_persist_create", (size_t)PS_L * width * sizeof(uint32_t), p->staging.stream);
     });
 }
 
@@ -390,8 +355,7 @@ int fsea_persist_destroy(fsea_persist *p) { return fsea_detail::destroy_object(p
 int fsea_persist_reset(fsea_persist *p) {
     return fsea_detail::reset_object(p, "persist is NULL", [&] {
         p->rows = 0;
-        FSEA_HIP(hipMemset(p->counts.buf.ptr, 0, (size_t)PS_L * p->width * sizeof(uint32_t)));
-        return (int)FSEA_OK;
+        return p->counts.zero();
     });
 }
 
@@ -414,42 +378,31 @@ int fsea_persist_width(const fsea_persist *p) { return p ? p->width : 0; }
 uint64_t fsea_persist_rows(const fsea_persist *p) { return p ? p->rows : 0; }
 
 int fsea_persist_add_device(fsea_persist *p, const void *d_rows, int type, size_t n_rows, size_t pitch, void *stream) {
-    int rc = check_add(p, d_rows, type, n_rows, pitch);
+    int rc = fsea_detail::check_rows_add(p, "persist", d_rows, type, n_rows, pitch);
     if (!rc && n_rows) rc = fsea_detail::check_aligned16("d_rows", d_rows);
     if (rc) return rc;
     if (n_rows == 0) return FSEA_OK;
     std::lock_guard<std::mutex> lock(p->mu);
-    if ((rc = check_room(p, n_rows))) return rc;
+    if ((rc = fsea_detail::check_rows_room(p, n_rows))) return rc;
     FSEA_ON_DEVICE(p->device);
     return add_launch(p, d_rows, type, n_rows, pitch, static_cast<hipStream_t>(stream));
 }
 
 int fsea_persist_add_host(fsea_persist *p, const void *rows, int type, size_t n_rows, size_t pitch) {
-    int rc = check_add(p, rows, type, n_rows, pitch);
+    int rc = fsea_detail::check_rows_add(p, "persist", rows, type, n_rows, pitch);
     if (rc) return rc;
     if (n_rows == 0) return FSEA_OK;
     std::lock_guard<std::mutex> lock(p->mu);
-    if ((rc = check_room(p, n_rows))) return rc;
+    if ((rc = fsea_detail::check_rows_room(p, n_rows))) return rc;
     FSEA_ON_DEVICE(p->device);
-    // the rows go up packed, at a pitch of whole 16-byte groups, in chunks of at most PS_STAGE_BYTES
-    const size_t esz = elem_bytes(type), row_bytes = (size_t)p->width * esz, packed = (row_bytes + 15) & ~(size_t)15;
-    const size_t chunk = std::max<size_t>(1, PS_STAGE_BYTES / packed);
-    for (size_t r0 = 0; r0 < n_rows; r0 += chunk) {
-        const size_t nr = std::min(chunk, n_rows - r0);
-        const char *src = static_cast<const char *>(rows) + r0 * pitch * esz;
-        rc = p->staging.run(
-            nr * packed, 0, nullptr,
-            [&](void *h_in) {
-                char *dst = static_cast<char *>(h_in);
-                for (size_t r = 0; r < nr; ++r) {
-                    std::memcpy(dst + r * packed, src + r * pitch * esz, row_bytes);
-                    std::memset(dst + r * packed + row_bytes, 0, packed - row_bytes);
-                }
-            },
-            [&](void *d_in, void *, hipStream_t s) { return add_launch(p, d_in, type, nr, packed / esz, s); });
-        if (rc) return rc;
-    }
-    return FSEA_OK;
+    // the rows go up packed, in chunks
+    const size_t esz = fsea_detail::row_elem_bytes(type);
+    const fsea_detail::PackedPlane in(rows, pitch * esz, (size_t)p->width * esz);
+    return fsea_detail::for_row_chunks(n_rows, in.packed, [&](size_t r0, size_t nr) {
+        return p->staging.run(
+            nr * in.packed, 0, nullptr, [&](void *h_in) { in.pack(h_in, r0, nr); },
+            [&](void *d_in, void *, hipStream_t s) { return add_launch(p, d_in, type, nr, in.packed / esz, s); });
+    });
 }
 
 int fsea_persist_decay(fsea_persist *p, uint32_t numerator, uint32_t denominator, void *stream) {
@@ -477,11 +430,7 @@ int fsea_persist_counts_host(fsea_persist *p, uint32_t *counts) {
     if (!counts) return fail(FSEA_EINVAL, "counts is NULL");
     std::lock_guard<std::mutex> lock(p->mu);
     FSEA_ON_DEVICE(p->device);
-    const fsea_detail::HostStaging::Part part[1] = {{counts, (size_t)PS_L * p->width * sizeof(uint32_t)}};
-    return p->staging.run(0, part, [](void *) {}, [&](void *, void **d_parts, hipStream_t s) {
-        d_parts[0] = p->counts.buf.ptr;      // the object's own memory, behind every add queued so far
-        return p->counts.acquire(s);
-    });
+    return p->counts.fetch(p->staging, counts);
 }
 
 int fsea_persist_image_device(fsea_persist *p, int map, uint64_t full, uint8_t *d_image, void *stream) {

@@ -745,6 +745,40 @@ class Pfb(_ResettableHandle):
                                            d_series_ptr, stream or None))
 
 
+def _rows_2d(a, dtypes, what):
+    """A 2-D array whose rows are contiguous and a whole number of elements apart (copied where they are not: only such
+    rows go to the library as they are), and its pitch in elements."""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype not in dtypes:
+        raise ValueError("%s is a 2-D array of %s" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
+    if a.strides[1] != a.itemsize or (a.shape[0] > 1 and (a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize)):
+        a = np.ascontiguousarray(a)
+    return a, (a.strides[0] // a.itemsize if a.shape[0] > 1 else a.shape[1])
+
+
+class _RowsHandle(_ResettableHandle):
+    """What consumes rows of `width` levels (Persist, Cfar, Events): the width and the rows offered so far."""
+
+    def __init__(self, width, device=0):
+        self.device = device
+        self._create("fsea_%s_create" % self._kind, int(width), device)
+
+    @property
+    def width(self):
+        return getattr(self._L, "fsea_%s_width" % self._kind)(self._p)
+
+    @property
+    def rows(self):
+        return getattr(self._L, "fsea_%s_rows" % self._kind)(self._p)
+
+    def _host_rows(self, rows):
+        """(array, pitch, type) of a 2-D uint8 or float32 array of rows of `width` elements"""
+        a, pitch = _rows_2d(rows, (np.uint8, np.float32), "rows")
+        if a.shape[1] != self.width:
+            raise ValueError("a row has `width` elements")
+        return a, pitch, CFAR_U8 if a.dtype == np.uint8 else CFAR_F32   # PERSIST_U8 and PERSIST_F32 are the same two
+
+
 def persist_trace(counts, kind, fraction=0.5):
     """fsea_persist_trace (host arithmetic): one level per column of a (256, width) array of counts -- the highest
     (PERSIST_TRACE_MAX) or lowest (PERSIST_TRACE_MIN) occupied level, or the level at which the cumulative count reaches
@@ -757,38 +791,18 @@ def persist_trace(counts, kind, fraction=0.5):
     return levels
 
 
-class Persist(_ResettableHandle):
+class Persist(_RowsHandle):
     """A persistence spectrum on one device: counts[level, column] over all the rows offered; thin wrapper over
     fsea_persist_*.  add() takes a 2-D uint8 or float32 array from the host (any row stride), add_device() resident rows;
     counts() and image() fetch the (256, width) counts and the (256, width) uint8 picture, strongest level on top."""
     _kind = "persist"
 
-    def __init__(self, width, device=0):
-        self.device = device
-        self._create("fsea_persist_create", int(width), device)
-
-    @property
-    def width(self):
-        return self._L.fsea_persist_width(self._p)
-
-    @property
-    def rows(self):
-        return self._L.fsea_persist_rows(self._p)
-
     def set_range(self, lo, hi):
         _check(self._L.fsea_persist_set_range(self._p, lo, hi))
 
     def add(self, rows):
-        a = np.asarray(rows)
-        if a.ndim != 2 or a.dtype not in (np.uint8, np.float32):
-            raise ValueError("rows is a 2-D uint8 or float32 array")
-        if a.shape[1] != self.width:
-            raise ValueError("a row has `width` elements")
-        if a.strides[1] != a.itemsize or (a.shape[0] > 1 and (a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize)):
-            a = np.ascontiguousarray(a)     # only rows of contiguous elements a whole number of elements apart go as they are
-        pitch = a.strides[0] // a.itemsize if a.shape[0] > 1 else a.shape[1]
-        _check(self._L.fsea_persist_add_host(self._p, a.ctypes.data, PERSIST_U8 if a.dtype == np.uint8 else PERSIST_F32,
-                                             a.shape[0], pitch))
+        a, pitch, type = self._host_rows(rows)
+        _check(self._L.fsea_persist_add_host(self._p, a.ctypes.data, type, a.shape[0], pitch))
 
     def add_device(self, d_rows_ptr, type, n_rows, pitch=None, stream=0):
         """d_rows_ptr (an int, 16-byte aligned): n_rows rows of `width` elements, `pitch` elements apart; asynchronous."""
@@ -829,40 +843,21 @@ def cfar_bands(hits, rows, min_fraction, max_gap=0, min_width=1):
     return out
 
 
-class Cfar(_ResettableHandle):
+class Cfar(_RowsHandle):
     """A CFAR detector across frequency on one device: which cells of a dB row stand above the mean level of their
     neighbours, and hits[column] over all the rows offered; thin wrapper over fsea_cfar_*.  add() takes a 2-D uint8 or
     float32 array from the host (any row stride) and returns what was asked for; add_device() takes resident rows."""
     _kind = "cfar"
-
-    def __init__(self, width, device=0):
-        self.device = device
-        self._create("fsea_cfar_create", int(width), device)
-
-    @property
-    def width(self):
-        return self._L.fsea_cfar_width(self._p)
-
-    @property
-    def rows(self):
-        return self._L.fsea_cfar_rows(self._p)
 
     def set(self, guard=2, train=16, offset=60, method=CFAR_CA):
         _check(self._L.fsea_cfar_set(self._p, int(guard), int(train), int(offset), int(method)))
 
     def add(self, rows, mask=False, row_hits=False):
         """None, the (n_rows, width) uint8 mask, the (n_rows,) uint32 row hits, or (mask, row_hits)."""
-        a = np.asarray(rows)
-        if a.ndim != 2 or a.dtype not in (np.uint8, np.float32):
-            raise ValueError("rows is a 2-D uint8 or float32 array")
-        if a.shape[1] != self.width:
-            raise ValueError("a row has `width` elements")
-        if a.strides[1] != a.itemsize or (a.shape[0] > 1 and (a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize)):
-            a = np.ascontiguousarray(a)     # only rows of contiguous elements a whole number of elements apart go as they are
-        pitch = a.strides[0] // a.itemsize if a.shape[0] > 1 else a.shape[1]
+        a, pitch, type = self._host_rows(rows)
         m = np.empty(a.shape, dtype=np.uint8) if mask else None
         h = np.empty(a.shape[0], dtype=np.uint32) if row_hits else None
-        _check(self._L.fsea_cfar_add_host(self._p, a.ctypes.data, CFAR_U8 if a.dtype == np.uint8 else CFAR_F32, a.shape[0], pitch,
+        _check(self._L.fsea_cfar_add_host(self._p, a.ctypes.data, type, a.shape[0], pitch,
                                           m.ctypes.data if mask else None, h.ctypes.data if row_hits else None))
         return (m, h) if mask and row_hits else m if mask else h
 
@@ -878,34 +873,11 @@ class Cfar(_ResettableHandle):
         return out
 
 
-def _rows_2d(a, dtypes, what):
-    """A 2-D array whose rows are contiguous and a whole number of elements apart (copied where they are not), and its pitch
-    in elements."""
-    a = np.asarray(a)
-    if a.ndim != 2 or a.dtype not in dtypes:
-        raise ValueError("%s is a 2-D array of %s" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
-    if a.strides[1] != a.itemsize or (a.shape[0] > 1 and (a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize)):
-        a = np.ascontiguousarray(a)
-    return a, (a.strides[0] // a.itemsize if a.shape[0] > 1 else a.shape[1])
-
-
-class Events(_ResettableHandle):
+class Events(_RowsHandle):
     """Spectrum events on one device: a detection mask (and the level rows under it) as a sorted list of runs, the runs
     linked into time-frequency events, runs painted back as an image; thin wrapper over fsea_events_*.  runs() and paint()
     take and give host arrays, runs_device() and paint_device() work on resident memory; link() is host arithmetic."""
     _kind = "events"
-
-    def __init__(self, width, device=0):
-        self.device = device
-        self._create("fsea_events_create", int(width), device)
-
-    @property
-    def width(self):
-        return self._L.fsea_events_width(self._p)
-
-    @property
-    def rows(self):
-        return self._L.fsea_events_rows(self._p)
 
     def set_gap(self, gap_cols):
         _check(self._L.fsea_events_set_gap(self._p, int(gap_cols)))

@@ -43,49 +43,12 @@
 
 #define BLOCK "FFT"
 
-/* taper names of nrf_fft_set_window / NRF_FFT_WINDOW -> fsea_window_fill kinds; -1 = rectangular (no taper), -2 = unknown */
-static int fsea_window_kind(const char *name) {
-    static const struct { const char *name; int kind; } tapers[] = {
-        {"hann", FSEA_WINDOW_HANN},           {"hamming", FSEA_WINDOW_HAMMING}, {"blackman", FSEA_WINDOW_BLACKMAN},
-        {"blackmanharris", FSEA_WINDOW_BLACKMANHARRIS}, {"flattop", FSEA_WINDOW_FLATTOP}};
-    if (name == NULL || name[0] == '\0' || strcmp(name, "rect") == 0 || strcmp(name, "none") == 0) return -1;
-    for (size_t i = 0; i < sizeof(tapers) / sizeof(tapers[0]); i++) {
-        if (strcmp(name, tapers[i].name) == 0) return tapers[i].kind;
-    }
-    return -2;
-}
-
-static void set_window_by_name(fsea_plan *plan, int fft_size, const char *name, const char *who) {
-    const int kind = fsea_window_kind(name);
-    int rc;
-    if (kind == -1) {
-        rc = fsea_plan_set_window(plan, NULL);
-        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_plan_set_window", rc);
-        return;
-    }
-    float *w = (float *)nrf_private_malloc(BLOCK, sizeof(float) * (size_t)fft_size);
-    rc = fsea_window_fill(kind, fft_size, w);
-    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_window_fill", rc);
-    rc = fsea_plan_set_window(plan, w); /* fails for a size without a kernel of its own: said loudly, not ignored */
-    if (rc != FSEA_OK) {
-        char what[96];
-        snprintf(what, sizeof(what), "fsea_plan_set_window (%s)", who);
-        nrf_private_fatal(BLOCK, what, rc);
-    }
-    free(w);
-}
-
 void nrf_fft_set_window(nrf_fft *fft, const char *name) {
-    if (fsea_window_kind(name) == -2) {
-        /* a programming error in the scene, handled as src/main.cpp handles a wrong argument type: say it and stop */
-        fprintf(stderr, "NRF FFT fatal error: nrf_fft_set_window: \"%s\" is not one of hann, hamming, blackman, blackmanharris, "
-                        "flattop, rect\n", name);
-        exit(EXIT_FAILURE);
-    }
+    nrf_private_check_window_name(BLOCK, "nrf_fft_set_window", name);
     /* under the block's mutex: a device thread may be inside nrf_fft_process (SURVEY 8(b) threading); rows already in the
      * history stay as they were computed, the next process call uses the new taper */
     pthread_mutex_lock(&fft->mutex);
-    set_window_by_name((fsea_plan *)fft->backend, fft->fft_size, name, "nrf_fft_set_window");
+    nrf_private_set_window(BLOCK, "nrf_fft_set_window", (fsea_plan *)fft->backend, fft->fft_size, name);
     pthread_mutex_unlock(&fft->mutex);
 }
 
@@ -110,12 +73,12 @@ nrf_fft *nrf_fft_new(int fft_size, int fft_history_size) {
      * C caller that wants its own calls nrf_fft_set_window afterwards */
     const char *win_env = getenv("NRF_FFT_WINDOW");
     if (win_env != NULL && win_env[0] != '\0') {
-        if (fsea_window_kind(win_env) == -2) {
+        if (nrf_private_window_kind(win_env) == -2) {
             fprintf(stderr, "NRF FFT fatal error: NRF_FFT_WINDOW=%s is not one of hann, hamming, blackman, blackmanharris, "
                             "flattop, rect\n", win_env);
             exit(EXIT_FAILURE);
         }
-        set_window_by_name(plan, fft_size, win_env, "NRF_FFT_WINDOW");
+        nrf_private_set_window(BLOCK, "NRF_FFT_WINDOW", plan, fft_size, win_env);
     }
     const char *hist_env = getenv("NRF_FFT_HISTORY");
     if (hist_env != NULL && strcmp(hist_env, "device") == 0) {

@@ -11,24 +11,12 @@
 #include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include "fsea.h"
 #include "nrf.h"
 #include "nrf_private.h"
 
 #define BLOCK "PERSISTENCE"
-
-static void grow(int device, void **d_ptr, size_t *cap, size_t need) {
-    if (*cap >= need) return;
-    int rc = *d_ptr != NULL ? fsea_device_free(device, *d_ptr) : FSEA_OK;
-    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_device_free", rc);
-    *d_ptr = NULL;
-    *cap = 0;
-    rc = fsea_device_alloc(device, need, d_ptr);
-    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_device_alloc", rc);
-    *cap = need;
-}
 
 nrf_persistence *nrf_persistence_new(int fft_size, int hop, int map) {
     if (fft_size < 1 || fft_size > FSEA_PERSIST_MAX_WIDTH) {
@@ -64,29 +52,9 @@ nrf_persistence *nrf_persistence_new(int fft_size, int hop, int map) {
 }
 
 void nrf_persistence_set_window(nrf_persistence *p, const char *name) {
-    static const char *names[] = {"rect", "hann", "hamming", "blackman", "blackmanharris", "flattop"};   /* FSEA_WINDOW_* */
-    int kind = -1;
-    if (name == NULL || name[0] == '\0' || strcmp(name, "none") == 0) kind = 0;
-    for (int k = 0; k < 6 && kind < 0; k++) {
-        if (strcmp(name, names[k]) == 0) kind = k;
-    }
-    if (kind < 0) {
-        fprintf(stderr, "NRF PERSISTENCE fatal error: nrf_persistence_set_window: \"%s\" is not one of hann, hamming, blackman, "
-                        "blackmanharris, flattop, rect\n", name);
-        exit(EXIT_FAILURE);
-    }
+    nrf_private_check_window_name(BLOCK, "nrf_persistence_set_window", name);
     pthread_mutex_lock(&p->mutex);
-    int rc;
-    if (kind == 0) {
-        rc = fsea_plan_set_window((fsea_plan *)p->plan, NULL);
-    } else {
-        float *w = (float *)nrf_private_malloc(BLOCK, sizeof(float) * (size_t)p->fft_size);
-        rc = fsea_window_fill(kind, p->fft_size, w);
-        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_window_fill", rc);
-        rc = fsea_plan_set_window((fsea_plan *)p->plan, w);
-        free(w);
-    }
-    if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_plan_set_window", rc);
+    nrf_private_set_window(BLOCK, NULL, (fsea_plan *)p->plan, p->fft_size, name);
     pthread_mutex_unlock(&p->mutex);
 }
 
@@ -104,25 +72,15 @@ void nrf_persistence_set_decay(nrf_persistence *p, unsigned numerator, unsigned 
 
 void nrf_persistence_process(nrf_persistence *p, nut_buffer *buffer) {
     assert(buffer->channels == 2);
-    if (buffer->type != NUT_BUFFER_U8) {
-        fprintf(stderr, "NRF PERSISTENCE fatal error: the block takes 8-bit samples, not an F64 buffer\n");
-        exit(EXIT_FAILURE);
-    }
-    const size_t length = (size_t)buffer->length, n = (size_t)p->fft_size;
+    nrf_private_need_u8(BLOCK, buffer);
+    const size_t n = (size_t)p->fft_size;
     pthread_mutex_lock(&p->mutex);
     fsea_persist *persist = (fsea_persist *)p->backend;
     int rc = fsea_persist_decay(persist, p->decay_numerator, p->decay_denominator, NULL);
     if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_persist_decay", rc);
-    if (length >= n) {
-        const size_t frames = (length - n) / (size_t)p->hop + 1;
-        grow(p->device, &p->d_iq, &p->iq_cap, 2 * length);
-        grow(p->device, &p->d_rows, &p->rows_cap, frames * n);
-        /* everything on the null stream, in order; u8 / 256 with no flip: nrf_device_get_samples_buffer's bytes are offset
-         * binary already */
-        rc = fsea_copy_to_device(p->device, p->d_iq, buffer->data.u8, 2 * length);
-        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_copy_to_device", rc);
-        rc = fsea_exec_u8_device((fsea_plan *)p->plan, p->d_iq, frames, 0, p->d_rows, NULL);
-        if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_exec_u8_device", rc);
+    const size_t frames = nrf_private_rows_on_device(BLOCK, p->device, (fsea_plan *)p->plan, n, (size_t)p->hop, buffer, &p->d_iq,
+                                                     &p->iq_cap, &p->d_rows, &p->rows_cap);
+    if (frames) {
         rc = fsea_persist_add_device(persist, p->d_rows, FSEA_PERSIST_U8, frames, n, NULL);
         if (rc != FSEA_OK) nrf_private_fatal(BLOCK, "fsea_persist_add_device", rc);
     }

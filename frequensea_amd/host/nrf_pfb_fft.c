@@ -52,10 +52,7 @@ nrf_pfb_fft *nrf_pfb_fft_new(int fft_size, int fft_history_size, int branch_taps
 
 void nrf_pfb_fft_process(nrf_pfb_fft *pfb, nut_buffer *buffer) {
     assert(buffer->channels == 2);
-    if (buffer->type != NUT_BUFFER_U8) {
-        fprintf(stderr, "NRF PFB FFT fatal error: the block takes 8-bit samples, not an F64 buffer\n");
-        exit(EXIT_FAILURE);
-    }
+    nrf_private_need_u8(BLOCK, buffer);
     const size_t length = (size_t)buffer->length, n = (size_t)pfb->fft_size, history = (size_t)pfb->fft_history_size;
     pthread_mutex_lock(&pfb->mutex);
     fsea_pfb *backend = (fsea_pfb *)pfb->backend;

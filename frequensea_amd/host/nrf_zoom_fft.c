@@ -66,10 +66,7 @@ void nrf_zoom_fft_set_freq_offset(nrf_zoom_fft *zoom, int freq_offset) {
 
 void nrf_zoom_fft_process(nrf_zoom_fft *zoom, nut_buffer *buffer) {
     assert(buffer->channels == 2);
-    if (buffer->type != NUT_BUFFER_U8) {
-        fprintf(stderr, "NRF zoom FFT fatal error: the block takes 8-bit samples, not an F64 buffer\n");
-        exit(EXIT_FAILURE);
-    }
+    nrf_private_need_u8(BLOCK, buffer);
     const size_t length = (size_t)buffer->length, n = (size_t)zoom->fft_size, history = (size_t)zoom->fft_history_size;
     pthread_mutex_lock(&zoom->mutex);
     fsea_zoom *backend = (fsea_zoom *)zoom->backend;

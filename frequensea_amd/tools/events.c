@@ -28,9 +28,6 @@
 #include "fsea.h"
 #include "tool_common.h"
 
-#define CHUNK_SAMPLES ((size_t)1 << 22)        /* samples read at a time */
-#define CHUNK_ROW_BYTES ((size_t)256 << 20)    /* and the rows of a chunk at most */
-
 static const char *USAGE =
     "usage: fsea-events FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db] [--guard G] [--train T]\n"
     "                   [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R] [--min-rows R] [--min-cols B]\n"
@@ -68,11 +65,10 @@ static fsea_events_run *runs_room(size_t more) {
 }
 
 int main(int argc, char **argv) {
-    const char *path = NULL, *image_path = NULL, *paint_path = NULL, *window = "rect", *mode_name = "db5";
-    int size = 0, hop = 0, flip = 0, guard = 2, train = 16, offset = 60, method = FSEA_CFAR_CA, gap_cols = 0, gap_rows = 0;
-    int have_freq = 0;
+    const char *path = NULL, *paint_path = NULL, *window = "rect", *mode_name = "db5";
+    int size = 0, hop = 0, flip = 0, gap_cols = 0, gap_rows = 0;
     long long min_rows = 1, min_cols = 1, min_hits = 1;
-    double rate = 0.0, freq = 0.0;
+    tool_detector det = TOOL_DETECTOR_DEFAULTS;
     for (int i = 1; i < argc; i++) {
         const int more = i + 1 < argc;
         if (!strcmp(argv[i], "--help")) {
@@ -83,49 +79,32 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--window") && more) window = argv[++i];
         else if (!strcmp(argv[i], "--flip")) flip = 1;
         else if (!strcmp(argv[i], "--mode") && more) mode_name = argv[++i];
-        else if (!strcmp(argv[i], "--guard") && more) guard = atoi(argv[++i]);
-        else if (!strcmp(argv[i], "--train") && more) train = atoi(argv[++i]);
-        else if (!strcmp(argv[i], "--offset") && more) offset = atoi(argv[++i]);
-        else if (!strcmp(argv[i], "--method") && more) {
-            const char *m = argv[++i];
-            if (!strcmp(m, "ca")) method = FSEA_CFAR_CA;
-            else if (!strcmp(m, "go")) method = FSEA_CFAR_GO;
-            else if (!strcmp(m, "so")) method = FSEA_CFAR_SO;
-            else usage_error("--method must be ca, go or so");
-        } else if (!strcmp(argv[i], "--gap-cols") && more) gap_cols = atoi(argv[++i]);
+        else if (tool_detector_option("fsea-events", &det, argc, argv, &i)) continue;
+        else if (!strcmp(argv[i], "--gap-cols") && more) gap_cols = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gap-rows") && more) gap_rows = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--min-rows") && more) min_rows = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--min-cols") && more) min_cols = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--min-hits") && more) min_hits = atoll(argv[++i]);
-        else if (!strcmp(argv[i], "--rate") && more) rate = atof(argv[++i]);
-        else if (!strcmp(argv[i], "--freq") && more) {
-            freq = atof(argv[++i]);
-            have_freq = 1;
-        } else if (!strcmp(argv[i], "--image") && more) image_path = argv[++i];
         else if (!strcmp(argv[i], "--paint") && more) paint_path = argv[++i];
         else if (argv[i][0] != '-' && path == NULL) path = argv[i];
         else usage_error(USAGE);
     }
+    const char *image_path = det.image_path;
+    const double rate = det.rate, freq = det.freq;
     if (path == NULL && image_path == NULL) usage_error("no recording file given");
     if (path != NULL && image_path != NULL) usage_error("a recording or --image, not both");
     if (image_path == NULL && (size < 1 || size > FSEA_EVENTS_MAX_WIDTH)) usage_error("--size must be in [1, 1048576]");
     if (hop == 0) hop = size;
     if (image_path == NULL && hop < 1) usage_error("--hop must be positive");
-    if (guard < 0 || guard > FSEA_CFAR_MAX_GUARD) usage_error("--guard must be in [0, 64]");
-    if (train < 1 || train > FSEA_CFAR_MAX_TRAIN) usage_error("--train must be in [1, 256]");
-    if (offset < -FSEA_CFAR_MAX_OFFSET || offset > FSEA_CFAR_MAX_OFFSET) usage_error("--offset must be in [-1048576, 1048576]");
+    tool_detector_check("fsea-events", &det);
     if (gap_cols < 0 || gap_cols > FSEA_EVENTS_MAX_GAP_COLS) usage_error("--gap-cols must be in [0, 64]");
     if (gap_rows < 0 || gap_rows > FSEA_EVENTS_MAX_GAP_ROWS) usage_error("--gap-rows must be in [0, 65536]");
     if (min_rows < 1 || min_rows > 0xffffffffll) usage_error("--min-rows must be at least 1");
     if (min_cols < 1 || min_cols > 0xffffffffll) usage_error("--min-cols must be at least 1");
     if (min_hits < 1) usage_error("--min-hits must be at least 1");
-    if ((rate != 0.0) != have_freq || rate < 0.0) usage_error("--rate HZ (positive) and --freq MHZ go together");
-    int mode = FSEA_MODE_DB5_U8_DCFIX, type = FSEA_CFAR_U8;
-    if (!strcmp(mode_name, "db10")) mode = FSEA_MODE_DB10_U8;
-    else if (!strcmp(mode_name, "db")) {
-        mode = FSEA_MODE_DB_F32;
-        type = FSEA_CFAR_F32;
-    } else if (strcmp(mode_name, "db5") != 0) usage_error("--mode must be db5, db10 or db");
+    tool_detector_check_axis("fsea-events", &det);
+    int mode = 0, type = 0;
+    if (!tool_rows_mode(mode_name, "db", &mode, &type)) usage_error("--mode must be db5, db10 or db");
 
     /* The object counts the rows of every call; the tool counts its own (`done`) and has the object start each chunk at row
      * 0, so that a chunk can be asked twice: once for the number of its runs, once for the records. */
@@ -135,14 +114,7 @@ int main(int argc, char **argv) {
     size_t done = 0;
     if (image_path != NULL) {
         int height = 0;
-        uint8_t *image = read_gray_png(image_path, &width, &height);
-        if (image == NULL) {
-            fprintf(stderr, "fsea-events: cannot read %s as an 8-bit grey PNG\n", image_path);
-            return EXIT_FAILURE;
-        }
-        if (width < 1 || width > FSEA_EVENTS_MAX_WIDTH) usage_error("the image is wider than 1048576 columns");
-        if (fsea_cfar_create(&cfar, width, 0) != FSEA_OK) die("fsea_cfar_create");
-        if (fsea_cfar_set(cfar, guard, train, offset, method) != FSEA_OK) die("fsea_cfar_set");
+        uint8_t *image = tool_detector_image("fsea-events", &det, &width, &height, &cfar);
         if (fsea_events_create(&events, width, 0) != FSEA_OK) die("fsea_events_create");
         if (fsea_events_set_gap(events, gap_cols) != FSEA_OK) die("fsea_events_set_gap");
         uint8_t *mask = (uint8_t *)malloc((size_t)width * (size_t)height + 1);
@@ -160,42 +132,17 @@ int main(int argc, char **argv) {
         free(mask);
         free(image);
     } else {
-        FILE *fp = fopen(path, "rb");
-        if (fp == NULL) {
-            fprintf(stderr, "fsea-events: cannot open recording %s\n", path);
-            return EXIT_FAILURE;
-        }
-        fsea_plan *plan = NULL;
-        if (fsea_plan_create(&plan, size, hop, mode, 0) != FSEA_OK) die("fsea_plan_create");
-        const int wrc = tool_set_named_window(plan, window, size);
-        if (wrc == TOOL_WINDOW_UNKNOWN) usage_error("--window must be rect, hann, hamming, blackman, blackmanharris or flattop");
-        if (wrc != 0) die("--window");
-        if (fsea_cfar_create(&cfar, size, 0) != FSEA_OK) die("fsea_cfar_create");
-        if (fsea_cfar_set(cfar, guard, train, offset, method) != FSEA_OK) die("fsea_cfar_set");
+        tool_row_source src;
+        tool_rows_open(&src, "fsea-events", path, size, hop, mode, window, flip);
+        cfar = tool_detector_create("fsea-events", &det, size);
         if (fsea_events_create(&events, size, 0) != FSEA_OK) die("fsea_events_create");
         if (fsea_events_set_gap(events, gap_cols) != FSEA_OK) die("fsea_events_set_gap");
-
-        /* a chunk: whole frames, at most CHUNK_SAMPLES samples and CHUNK_ROW_BYTES of rows, one frame at least */
-        const size_t n = (size_t)size, h = (size_t)hop, row_bytes = fsea_plan_row_bytes(plan);
-        size_t frames_max = CHUNK_ROW_BYTES / row_bytes;
-        if (CHUNK_SAMPLES > n && (CHUNK_SAMPLES - n) / h + 1 < frames_max) frames_max = (CHUNK_SAMPLES - n) / h + 1;
-        if (frames_max < 1 || CHUNK_SAMPLES <= n) frames_max = 1;
-        const size_t chunk = (frames_max - 1) * h + n;
-        uint8_t *iq = (uint8_t *)malloc(2 * chunk);
-        if (iq == NULL) usage_error("out of memory");
-        void *d_iq = NULL, *d_rows = NULL, *d_mask = NULL, *d_runs = NULL;
+        const size_t n = (size_t)size;
+        void *d_rows = src.d_rows, *d_mask = NULL, *d_runs = NULL;
         size_t d_runs_cap = 0;
-        if (fsea_device_alloc(0, 2 * chunk, &d_iq) != FSEA_OK) die("fsea_device_alloc");
-        if (fsea_device_alloc(0, frames_max * row_bytes, &d_rows) != FSEA_OK) die("fsea_device_alloc");
-        if (fsea_device_alloc(0, frames_max * n, &d_mask) != FSEA_OK) die("fsea_device_alloc");
+        if (fsea_device_alloc(0, src.frames_max * n, &d_mask) != FSEA_OK) die("fsea_device_alloc");
         /* rows and mask stay on the device between the plan, the detector and the runs; everything on the null stream */
-        for (long long pos = 0;;) {
-            if (fseek(fp, 2 * pos, SEEK_SET) != 0) break;
-            const size_t got = fread(iq, 2, chunk, fp);
-            if (got < n) break;
-            const size_t frames = (got - n) / h + 1;
-            if (fsea_copy_to_device(0, d_iq, iq, 2 * got) != FSEA_OK) die("fsea_copy_to_device");
-            if (fsea_exec_u8_device(plan, d_iq, frames, flip, d_rows, NULL) != FSEA_OK) die("fsea_exec_u8_device");
+        for (size_t frames; (frames = tool_rows_next(&src)) > 0; done += frames) {
             if (fsea_cfar_add_device(cfar, d_rows, type, frames, n, (uint8_t *)d_mask, NULL, NULL) != FSEA_OK) die("fsea_cfar_add_device");
             size_t found = 0;
             if (fsea_events_reset(events) != FSEA_OK) die("fsea_events_reset");
@@ -219,20 +166,14 @@ int main(int argc, char **argv) {
                 for (size_t i = 0; i < found; i++) dst[i].row += (uint32_t)done;
                 g_n_runs += found;
             }
-            done += frames;
-            pos += (long long)(frames * h);
         }
-        fclose(fp);
-        fsea_plan_destroy(plan);
-        fsea_device_free(0, d_iq);
-        fsea_device_free(0, d_rows);
+        tool_rows_close(&src);
         fsea_device_free(0, d_mask);
         if (d_runs != NULL) fsea_device_free(0, d_runs);
-        free(iq);
     }
     if (done < 1) {
         if (image_path != NULL) fprintf(stderr, "fsea-events: image %s has no rows\n", image_path);
-        else fprintf(stderr, "fsea-events: recording %s holds fewer than one frame of %d samples\n", path, size);
+        else return tool_rows_none("fsea-events", path, size);
         return EXIT_FAILURE;
     }
 
@@ -257,7 +198,7 @@ int main(int argc, char **argv) {
                e->peak_row, e->peak_col);
         if (rate > 0.0) {
             const uint32_t k[3] = {e->col_first, e->col_last, e->peak_col}, r[3] = {e->row_first, e->row_last, e->peak_row};
-            for (int i = 0; i < 3; i++) printf(" %.6f", freq + ((double)k[i] - (double)(width / 2)) * rate / (double)width / 1e6);
+            for (int i = 0; i < 3; i++) printf(" %.6f", tool_column_mhz(freq, rate, width, k[i]));
             if (image_path == NULL) {
                 for (int i = 0; i < 3; i++) printf(" %.6f", (double)r[i] * (double)hop / rate);
             }

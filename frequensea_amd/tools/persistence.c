@@ -20,9 +20,6 @@
 #include "fsea.h"
 #include "tool_common.h"
 
-#define CHUNK_SAMPLES ((size_t)1 << 22)        /* samples read at a time */
-#define CHUNK_ROW_BYTES ((size_t)256 << 20)    /* and the rows of a chunk at most */
-
 static const char *USAGE =
     "usage: fsea-persistence FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db:LO:HI] [--map sat|lin|log]\n"
     "                        [--full COUNT] [--traces FILE] -o OUT.png\n"
@@ -66,59 +63,27 @@ int main(int argc, char **argv) {
     if (size < 1 || size > FSEA_PERSIST_MAX_WIDTH) usage_error("--size must be in [1, 65536]");
     if (hop == 0) hop = size;
     if (hop < 1) usage_error("--hop must be positive");
-    int mode = FSEA_MODE_DB5_U8_DCFIX, type = FSEA_PERSIST_U8;
+    int mode = FSEA_MODE_DB_F32, type = FSEA_PERSIST_F32;
     float lo = 0.0f, hi = 0.0f;
-    if (!strcmp(mode_name, "db10")) mode = FSEA_MODE_DB10_U8;
-    else if (!strncmp(mode_name, "db:", 3)) {
-        mode = FSEA_MODE_DB_F32;
-        type = FSEA_PERSIST_F32;
+    if (!strncmp(mode_name, "db:", 3)) {
         if (sscanf(mode_name + 3, "%f:%f", &lo, &hi) != 2 || !isfinite(lo) || !isfinite(hi) || !(lo < hi)) {
             usage_error("--mode db:LO:HI needs two finite numbers with LO < HI");
         }
-    } else if (strcmp(mode_name, "db5") != 0) usage_error("--mode must be db5, db10 or db:LO:HI");
+    } else if (!tool_rows_mode(mode_name, NULL, &mode, &type)) usage_error("--mode must be db5, db10 or db:LO:HI");
 
-    FILE *fp = fopen(path, "rb");
-    if (fp == NULL) {
-        fprintf(stderr, "fsea-persistence: cannot open recording %s\n", path);
-        return EXIT_FAILURE;
-    }
-    fsea_plan *plan = NULL;
-    if (fsea_plan_create(&plan, size, hop, mode, 0) != FSEA_OK) die("fsea_plan_create");
-    const int wrc = tool_set_named_window(plan, window, size);
-    if (wrc == TOOL_WINDOW_UNKNOWN) usage_error("--window must be rect, hann, hamming, blackman, blackmanharris or flattop");
-    if (wrc != 0) die("--window");
+    tool_row_source src;
+    tool_rows_open(&src, "fsea-persistence", path, size, hop, mode, window, flip);
     fsea_persist *persist = NULL;
     if (fsea_persist_create(&persist, size, 0) != FSEA_OK) die("fsea_persist_create");
     if (type == FSEA_PERSIST_F32 && fsea_persist_set_range(persist, lo, hi) != FSEA_OK) die("fsea_persist_set_range");
-
-    /* a chunk: whole frames, at most CHUNK_SAMPLES samples and CHUNK_ROW_BYTES of rows, one frame at least */
-    const size_t n = (size_t)size, h = (size_t)hop, row_bytes = fsea_plan_row_bytes(plan);
-    size_t frames_max = CHUNK_ROW_BYTES / row_bytes;
-    if (CHUNK_SAMPLES > n && (CHUNK_SAMPLES - n) / h + 1 < frames_max) frames_max = (CHUNK_SAMPLES - n) / h + 1;
-    if (frames_max < 1 || CHUNK_SAMPLES <= n) frames_max = 1;
-    const size_t chunk = (frames_max - 1) * h + n;
-    uint8_t *iq = (uint8_t *)malloc(2 * chunk);
-    if (iq == NULL) usage_error("out of memory");
-    void *d_iq = NULL, *d_rows = NULL;
-    if (fsea_device_alloc(0, 2 * chunk, &d_iq) != FSEA_OK) die("fsea_device_alloc");
-    if (fsea_device_alloc(0, frames_max * row_bytes, &d_rows) != FSEA_OK) die("fsea_device_alloc");
-    /* the rows stay on the device between the plan and the object; everything on the null stream, in order */
-    for (long long pos = 0;;) {
-        if (fseek(fp, 2 * pos, SEEK_SET) != 0) break;
-        const size_t got = fread(iq, 2, chunk, fp);
-        if (got < n) break;
-        const size_t frames = (got - n) / h + 1;
-        if (fsea_copy_to_device(0, d_iq, iq, 2 * got) != FSEA_OK) die("fsea_copy_to_device");
-        if (fsea_exec_u8_device(plan, d_iq, frames, flip, d_rows, NULL) != FSEA_OK) die("fsea_exec_u8_device");
-        if (fsea_persist_add_device(persist, d_rows, type, frames, n, NULL) != FSEA_OK) die("fsea_persist_add_device");
-        pos += (long long)(frames * h);
+    /* the rows stay on the device between the plan and the object */
+    const size_t n = (size_t)size;
+    for (size_t frames; (frames = tool_rows_next(&src)) > 0;) {
+        if (fsea_persist_add_device(persist, src.d_rows, type, frames, n, NULL) != FSEA_OK) die("fsea_persist_add_device");
     }
-    fclose(fp);
+    tool_rows_close(&src);
     const unsigned long long rows = fsea_persist_rows(persist);
-    if (rows < 1) {
-        fprintf(stderr, "fsea-persistence: recording %s holds fewer than one frame of %d samples\n", path, size);
-        return EXIT_FAILURE;
-    }
+    if (rows < 1) return tool_rows_none("fsea-persistence", path, size);
 
     uint8_t *image = (uint8_t *)malloc((size_t)FSEA_PERSIST_LEVELS * n);
     uint32_t *counts = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)FSEA_PERSIST_LEVELS * n);
@@ -152,12 +117,8 @@ int main(int argc, char **argv) {
         }
     }
     fsea_persist_destroy(persist);
-    fsea_plan_destroy(plan);
-    fsea_device_free(0, d_iq);
-    fsea_device_free(0, d_rows);
     free(trace);
     free(counts);
     free(image);
-    free(iq);
     return 0;
 }

@@ -1,7 +1,11 @@
 /*
  * tool_common.h -- what the command-line tools share beside pipeline.h (which stays about threads and rings): the two ways a
- * tool ends with a message, the capture format's constants, the newest-first row reader of the sweep tools and the --window
- * names.  Everything is `static inline`, as in pipeline.h; a tool takes what applies to it.
+ * tool ends with a message, the capture format's constants, the newest-first row reader of the sweep tools, the --window
+ * names, and what the tools that give dB rows to a device object share (fsea-persistence, fsea-occupancy, fsea-events): the
+ * recording that becomes rows on the device chunk by chunk, the --mode names, the CFAR detector's options and the MHz of a
+ * column.  Everything is `static inline`, as in pipeline.h; a tool takes what applies to it.
+ *
+ * The --window table is the tools' own: the host library keeps one like it in its private header, which no tool includes.
  */
 #ifndef FSEA_TOOLS_TOOL_COMMON_H
 #define FSEA_TOOLS_TOOL_COMMON_H
@@ -11,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "easypng.h"
 #include "fsea.h"
 
 #define TRANSFER_BYTES 262144 /* one HackRF transfer: 131072 IQ samples, as c/rfcap.c records them */
@@ -43,6 +48,160 @@ static inline int tool_set_named_window(fsea_plan *plan, const char *name, int n
         return rc;
     }
     return TOOL_WINDOW_UNKNOWN;
+}
+
+/* --mode NAME of the tools that give rows to an object: db5 and db10 are 8-bit rows; `f32_name` ("db"; NULL: the tool has
+ * a form of its own) is f32 dB rows.  The type is FSEA_CFAR_U8 / _F32, which FSEA_PERSIST_U8 / _F32 equal.  0: no such name. */
+static inline int tool_rows_mode(const char *name, const char *f32_name, int *mode, int *type) {
+    *type = FSEA_CFAR_U8;
+    if (!strcmp(name, "db5")) *mode = FSEA_MODE_DB5_U8_DCFIX;
+    else if (!strcmp(name, "db10")) *mode = FSEA_MODE_DB10_U8;
+    else if (f32_name != NULL && !strcmp(name, f32_name)) {
+        *mode = FSEA_MODE_DB_F32;
+        *type = FSEA_CFAR_F32;
+    } else return 0;
+    return 1;
+}
+
+/* column k of `width` as MHz: the plan's rows have the centre frequency, `freq` MHz, in column width / 2 */
+static inline double tool_column_mhz(double freq, double rate, int width, long long k) {
+    return freq + (double)(k - width / 2) * rate / (double)width / 1e6;
+}
+
+/* A raw 8-bit IQ recording as dB rows on the device: every frame of n samples, one every h, through a plan with the named
+ * window, in chunks of whole frames of at most TOOL_CHUNK_SAMPLES samples and TOOL_CHUNK_ROW_BYTES of rows, one frame at
+ * least.  The rows of a chunk are in d_rows, n to a row, until the next chunk is asked for; everything on the null stream,
+ * in order. */
+#define TOOL_CHUNK_SAMPLES ((size_t)1 << 22)
+#define TOOL_CHUNK_ROW_BYTES ((size_t)256 << 20)
+typedef struct {
+    const char *tool;
+    FILE *fp;
+    fsea_plan *plan;
+    int flip;
+    size_t n, h, chunk, frames_max;   /* samples and frames of a chunk at most */
+    long long pos;                    /* the sample the next chunk begins at */
+    uint8_t *iq;
+    void *d_iq, *d_rows;
+} tool_row_source;
+
+/* "cannot open recording" comes before any device call; every failure ends the tool */
+static inline void tool_rows_open(tool_row_source *s, const char *tool, const char *path, int size, int hop, int mode,
+                                  const char *window, int flip) {
+    memset(s, 0, sizeof(*s));
+    s->tool = tool;
+    s->flip = flip;
+    s->fp = fopen(path, "rb");
+    if (s->fp == NULL) {
+        fprintf(stderr, "%s: cannot open recording %s\n", tool, path);
+        exit(EXIT_FAILURE);
+    }
+    if (fsea_plan_create(&s->plan, size, hop, mode, 0) != FSEA_OK) tool_die(tool, "fsea_plan_create");
+    const int wrc = tool_set_named_window(s->plan, window, size);
+    if (wrc == TOOL_WINDOW_UNKNOWN) tool_usage_error(tool, "--window must be rect, hann, hamming, blackman, blackmanharris or flattop");
+    if (wrc != 0) tool_die(tool, "--window");
+    const size_t n = (size_t)size, h = (size_t)hop, row_bytes = fsea_plan_row_bytes(s->plan);
+    size_t frames_max = TOOL_CHUNK_ROW_BYTES / row_bytes;
+    if (TOOL_CHUNK_SAMPLES > n && (TOOL_CHUNK_SAMPLES - n) / h + 1 < frames_max) frames_max = (TOOL_CHUNK_SAMPLES - n) / h + 1;
+    if (frames_max < 1 || TOOL_CHUNK_SAMPLES <= n) frames_max = 1;
+    s->n = n;
+    s->h = h;
+    s->frames_max = frames_max;
+    s->chunk = (frames_max - 1) * h + n;
+    s->iq = (uint8_t *)malloc(2 * s->chunk);
+    if (s->iq == NULL) tool_usage_error(tool, "out of memory");
+    if (fsea_device_alloc(0, 2 * s->chunk, &s->d_iq) != FSEA_OK) tool_die(tool, "fsea_device_alloc");
+    if (fsea_device_alloc(0, frames_max * row_bytes, &s->d_rows) != FSEA_OK) tool_die(tool, "fsea_device_alloc");
+}
+
+/* the frames of the next chunk, now in d_rows; 0: the recording holds no further frame */
+static inline size_t tool_rows_next(tool_row_source *s) {
+    if (fseek(s->fp, 2 * s->pos, SEEK_SET) != 0) return 0;
+    const size_t got = fread(s->iq, 2, s->chunk, s->fp);
+    if (got < s->n) return 0;
+    const size_t frames = (got - s->n) / s->h + 1;
+    if (fsea_copy_to_device(0, s->d_iq, s->iq, 2 * got) != FSEA_OK) tool_die(s->tool, "fsea_copy_to_device");
+    if (fsea_exec_u8_device(s->plan, s->d_iq, frames, s->flip, s->d_rows, NULL) != FSEA_OK) tool_die(s->tool, "fsea_exec_u8_device");
+    s->pos += (long long)(frames * s->h);
+    return frames;
+}
+
+static inline void tool_rows_close(tool_row_source *s) {
+    fclose(s->fp);
+    fsea_plan_destroy(s->plan);
+    fsea_device_free(0, s->d_iq);
+    fsea_device_free(0, s->d_rows);
+    free(s->iq);
+}
+
+/* what a tool says of a recording that gave no row, for its exit status */
+static inline int tool_rows_none(const char *tool, const char *path, int size) {
+    fprintf(stderr, "%s: recording %s holds fewer than one frame of %d samples\n", tool, path, size);
+    return EXIT_FAILURE;
+}
+
+/* The CFAR detector of fsea-occupancy and fsea-events: --guard --train --offset --method, the axis of --rate and --freq, and
+ * --image IN.png in place of a recording. */
+typedef struct {
+    int guard, train, offset, method, have_freq;
+    double rate, freq;
+    const char *image_path;
+} tool_detector;
+#define TOOL_DETECTOR_DEFAULTS {2, 16, 60, FSEA_CFAR_CA, 0, 0.0, 0.0, NULL}
+
+/* 1: argv[*i] was one of the detector's options and *i is on its value; 0: not one of them */
+static inline int tool_detector_option(const char *tool, tool_detector *d, int argc, char **argv, int *i) {
+    const char *arg = argv[*i];
+    if (*i + 1 >= argc) return 0;
+    if (!strcmp(arg, "--guard")) d->guard = atoi(argv[++*i]);
+    else if (!strcmp(arg, "--train")) d->train = atoi(argv[++*i]);
+    else if (!strcmp(arg, "--offset")) d->offset = atoi(argv[++*i]);
+    else if (!strcmp(arg, "--method")) {
+        const char *m = argv[++*i];
+        if (!strcmp(m, "ca")) d->method = FSEA_CFAR_CA;
+        else if (!strcmp(m, "go")) d->method = FSEA_CFAR_GO;
+        else if (!strcmp(m, "so")) d->method = FSEA_CFAR_SO;
+        else tool_usage_error(tool, "--method must be ca, go or so");
+    } else if (!strcmp(arg, "--rate")) d->rate = atof(argv[++*i]);
+    else if (!strcmp(arg, "--freq")) {
+        d->freq = atof(argv[++*i]);
+        d->have_freq = 1;
+    } else if (!strcmp(arg, "--image")) d->image_path = argv[++*i];
+    else return 0;
+    return 1;
+}
+
+/* the ranges of the detector's own three; a tool checks --rate and --freq behind its own options */
+static inline void tool_detector_check(const char *tool, const tool_detector *d) {
+    if (d->guard < 0 || d->guard > FSEA_CFAR_MAX_GUARD) tool_usage_error(tool, "--guard must be in [0, 64]");
+    if (d->train < 1 || d->train > FSEA_CFAR_MAX_TRAIN) tool_usage_error(tool, "--train must be in [1, 256]");
+    if (d->offset < -FSEA_CFAR_MAX_OFFSET || d->offset > FSEA_CFAR_MAX_OFFSET) {
+        tool_usage_error(tool, "--offset must be in [-1048576, 1048576]");
+    }
+}
+
+static inline void tool_detector_check_axis(const char *tool, const tool_detector *d) {
+    if ((d->rate != 0.0) != d->have_freq || d->rate < 0.0) tool_usage_error(tool, "--rate HZ (positive) and --freq MHZ go together");
+}
+
+/* a detector of `width` columns with the options' settings */
+static inline fsea_cfar *tool_detector_create(const char *tool, const tool_detector *d, int width) {
+    fsea_cfar *cfar = NULL;
+    if (fsea_cfar_create(&cfar, width, 0) != FSEA_OK) tool_die(tool, "fsea_cfar_create");
+    if (fsea_cfar_set(cfar, d->guard, d->train, d->offset, d->method) != FSEA_OK) tool_die(tool, "fsea_cfar_set");
+    return cfar;
+}
+
+/* --image: the rows of the PNG (the caller frees them), their size, and a detector of their width */
+static inline uint8_t *tool_detector_image(const char *tool, const tool_detector *d, int *width, int *height, fsea_cfar **cfar) {
+    uint8_t *image = read_gray_png(d->image_path, width, height);
+    if (image == NULL) {
+        fprintf(stderr, "%s: cannot read %s as an 8-bit grey PNG\n", tool, d->image_path);
+        exit(EXIT_FAILURE);
+    }
+    if (*width < 1 || *width > FSEA_CFAR_MAX_WIDTH) tool_usage_error(tool, "the image is wider than 1048576 columns");
+    *cfar = tool_detector_create(tool, d, *width);
+    return image;
 }
 
 #if defined(_POSIX_C_SOURCE) && _POSIX_C_SOURCE >= 200809L /* pread: the sweep tools are built with it */
