@@ -1,10 +1,11 @@
 // fsea_fir_stage.h -- how an input sample becomes the f32 complex value a FIR kernel stages in LDS, shared by the kernels of
-// fsea_fir.hip (fsea_fir_u8, fsea_fir_f64, fsea_shift_fir_u8), fsea_zoom.hip (fsea_shift_decim_u8) and fsea_pfb.hip
-// (fsea_pfb_frames_u8): the byte and f64 conversions, the frequency shift of fsea_fir_u8_shifted_* (include/fsea.h) with
-// every rounding spelled out, the packed tap FMA, the host side of the shift (FirRot from the caller's arguments, the
-// argument limits), and the filter state the three objects carry from call to call (FirState: the taps and two tails of a
-// length each object gives at create).  A sample's value is a function of (cycles_per_sample, phase0_cycles, stream
-// position) alone, so every kernel that stages through these helpers sees the same bits.
+// fsea_fir.hip (fsea_fir_u8, fsea_fir_f64, fsea_shift_fir_u8), fsea_zoom.hip (fsea_shift_decim_u8), fsea_extract.hip
+// (fsea_extract_u8) and fsea_pfb.hip (fsea_pfb_frames_u8): the byte and f64 conversions, the frequency shift of
+// fsea_fir_u8_shifted_* (include/fsea.h) with every rounding spelled out, the packed tap FMA, the host side of the shift
+// (FirRot from the caller's arguments, the argument limits), and the filter state the three objects carry from call to call
+// (FirState: the taps and two tails of a length each object gives at create).  A sample's value is a function of
+// (cycles_per_sample, phase0_cycles, stream position) alone, so every kernel that stages through these helpers sees the
+// same bits.
 #pragma once
 
 #include "fsea_internal.h"
@@ -163,6 +164,39 @@ __device__ __forceinline__ void stage_group(const void *in, long long s, long lo
                 const cf ph = rot_mul(o + j < 8 ? b0 : b1, rot_step(rot, (o + j) & 7));
                 if (s + j < n_in) v[j] = rot_sample(v[j], ph);
             }
+        }
+    }
+}
+
+// stage_group for a job that begins anywhere in a resident buffer (fsea_extract_u8): sample 0 of the job is element `first`
+// of `in`, the job has n samples, and the group is aligned to the buffer, not to the job: first + s is a multiple of 8, s
+// itself any number from -7 on.  The samples in front of the job are 0.0 (a zero tail) and so are those behind it; no load
+// leaves [first, first + n).  The stream position of sample s is rot.offset + s, and a sample's phasor is rot_base at
+// P & ~7 times step P & 7 as in stage_group: the same bits whatever the grouping.  o = P0 & 7 is the same for every group
+// of a job, the groups being eight samples apart, so the caller works it out once, from uniform values, and hands in the
+// steps in the group's order: turned[j] = step[(o + j) & 7], eight scalar loads at a uniform index.  (That kernel reads its
+// FirRot from device memory, not from its arguments; rot_step's selects among eight loaded values the compiler made a
+// table in scratch, indexed by the lane's o + j, or by the uniform one.)  Of rot only delta, phase0 and offset are read.
+template <int KIND>
+__device__ __forceinline__ void stage_group_at(const void *in, long long first, long long s, long long n, uint32_t flip,
+                                               const FirRot &rot, const cf turned[8], int o, cf v[8]) {
+    if (s >= 0 && s + 8 <= n) {
+        load_group<KIND>(in, first + s, flip, v);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const long long ss = s + j;
+            v[j] = ss >= 0 && ss < n ? load_sample<KIND>(in, first + ss, flip) : cf{0.0f, 0.0f};
+        }
+    }
+    if (s + 8 > 0 && s < n) {
+        const long long P0 = rot.offset + s;   // P0 & 7 == o
+        const cf b0 = rot_base(rot, P0 - o);   // in front of position 0 only for samples in front of the job: not used
+        const cf b1 = o ? rot_base(rot, P0 - o + 8) : b0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const cf ph = rot_mul(o + j < 8 ? b0 : b1, turned[j]);
+            if (s + j >= 0 && s + j < n) v[j] = rot_sample(v[j], ph);
         }
     }
 }

@@ -16,51 +16,15 @@
 // holds D (ZM_T + ceil((L - 1) / D)) samples: eight, four and two workgroups per CU.  A tile of 128 outputs keeps two
 // workgroups on a CU at D = 64, L = 512; a lane with several outputs would need an image several times that.  Workgroup 0 writes the next tail into
 // the second of two tail buffers, as the filter does.
-#include "fsea_fir_stage.h"
+#include "fsea_zoom_image.h"
 
 #include <cmath>
 
 using fsea_detail::DeviceGuard;
 using fsea_detail::fail;
-using namespace fsea_stage;
+using namespace fsea_zoom_image;   // the image, the chain and fsea_stage
 
 namespace {
-
-constexpr int ZM_WG = 256;                       // lanes per workgroup: all of them stage
-constexpr int ZM_T = FSEA_ZOOM_TILE_OUTPUTS;     // outputs per workgroup, one per lane of the first two waves
-constexpr int ZM_TAPS_ALLOC = FSEA_FIR_MAX_TAPS + 8;   // padded taps on the device (zeros past L): whole groups of eight
-constexpr int ZM_CAP_S = 2304, ZM_CAP_M = 4608, ZM_CAP_L = 8832;   // samples of the three LDS images
-constexpr size_t ZM_MAX_SAMPLES = (size_t)1 << 31;
-static_assert(ZM_T <= ZM_WG && ZM_T % 64 == 0, "whole waves own the outputs, one per lane");
-
-// columns of the phase-major image: sample m of the tile at [m % D][m / D], m < ZM_T D + L - 1; odd
-constexpr int zoom_pitch(int D, int L) { return (ZM_T + (L - 1 + D - 1) / D) | 1; }
-constexpr int zoom_lds_samples(int D, int L) { return D * zoom_pitch(D, L); }
-static_assert(zoom_lds_samples(FSEA_ZOOM_MAX_DECIMATION, FSEA_FIR_MAX_TAPS) <= ZM_CAP_L, "the largest image fits");
-static_assert(2 * ZM_CAP_L * sizeof(cf) <= 160 * 1024, "two workgroups per CU at the largest L and D");
-
-// One output: one FMA chain over the taps ascending, from +0.  col = the image at the lane's column: sample i D + k stands
-// at [k % D][i + k / D], the same byte offset from col for every lane.  Those offsets are a table in device memory (made
-// once per object: D and L are its constants), read like the taps by scalar loads -- stepping k % D and k / D in the loop
-// instead cost eight scalar instructions per tap, more than the CU's one scalar unit has time for at small D.  Eight taps
-// at a time; past L the table holds offset 0 (a staged, finite sample) for the zero taps behind the filter's own.
-__device__ __forceinline__ cf zoom_chain(const cf *col, const float *__restrict__ taps, const uint32_t *__restrict__ offs, int L) {
-    const cf *taps2 = reinterpret_cast<const cf *>(taps);   // tap pairs, one SGPR pair each
-    const char *base = reinterpret_cast<const char *>(col);
-    cf acc = cf{0.0f, 0.0f};
-    for (int k0 = 0; k0 < L; k0 += 8) {
-        cf x[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = *reinterpret_cast<const cf *>(base + offs[k0 + j]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const cf t = taps2[(k0 >> 1) + j];
-            acc = pk_tap_fma_lo(x[2 * j], t, acc);
-            acc = pk_tap_fma_hi(x[2 * j + 1], t, acc);
-        }
-    }
-    return acc;
-}
 
 template <int CAP>
 __device__ __forceinline__ void zoom_body(const void *__restrict__ in, long long n, uint32_t flip, const cf *__restrict__ tail_in,
@@ -86,18 +50,7 @@ __device__ __forceinline__ void zoom_body(const void *__restrict__ in, long long
         cf v[8];
         stage_group<FIR_IN_U8, true>(in, s, n, flip, tail_in, L, rot, v);
         const int m0 = (int)(s - s_first);      // tile position of the group's sample 0; negative in the first group only
-        int q = m0 > 0 ? m0 / D : 0, r = m0 > 0 ? m0 - q * D : 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int m = m0 + j;
-            if (m >= 0) {
-                if (m < span) lds[r * pitch + q] = v[j];
-                if (++r == D) {
-                    r = 0;
-                    ++q;
-                }
-            }
-        }
+        zoom_store_group(lds, v, m0, span, D, pitch);
     }
     __syncthreads();
 
@@ -203,10 +156,8 @@ int fsea_zoom_create(fsea_zoom **out, const double *taps, int n_taps, int decima
         z->decimation = decimation;
         int rc = fsea_plan_create(&z->plan.ptr, fft_size, hop, mode, device);   // the sizes and modes of any plan, and its statuses
         if (rc) return rc;
-        uint32_t offs[ZM_TAPS_ALLOC] = {};
-        for (int k = 0; k < n_taps; ++k) {
-            offs[k] = (uint32_t)(((k % decimation) * zoom_pitch(decimation, n_taps) + k / decimation) * (int)sizeof(cf));
-        }
+        uint32_t offs[ZM_TAPS_ALLOC];
+        zoom_fill_offsets(offs, n_taps, decimation);
         hipError_t e = z->state.create(taps, n_taps, ZM_TAPS_ALLOC, FSEA_FIR_MAX_TAPS);
         if (e == hipSuccess) e = z->d_offs.upload(offs, ZM_TAPS_ALLOC);
         if (e == hipSuccess) e = z->pairs.create(z->staging.stream);

@@ -52,6 +52,7 @@ EVENTS_RUN = np.dtype([("row", "<u4"), ("first", "<u4"), ("last", "<u4"), ("hits
 EVENTS_EVENT = np.dtype([("row_first", "<u4"), ("row_last", "<u4"), ("col_first", "<u4"), ("col_last", "<u4"), ("runs", "<u4"),
                          ("peak", "<i4"), ("peak_row", "<u4"), ("peak_col", "<u4"), ("hits", "<u8"), ("level_sum", "<i8")])   # fsea_events_event
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
+EXTRACT_MAX_JOBS = 65536        # FSEA_EXTRACT_MAX_JOBS
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
 DEMOD_MAX_CHANNELS = 256            # FSEA_DEMOD_MAX_CHANNELS
@@ -78,6 +79,12 @@ class ChainOutputs(ctypes.Structure):
     """fsea_chain_outputs (include/fsea.h)."""
     _fields_ = [("points", ctypes.c_void_p), ("lines", ctypes.c_void_p), ("size_multiplier", ctypes.c_int),
                 ("n_line_points", ctypes.c_size_t), ("pairs", ctypes.c_void_p)]
+
+
+class ExtractJob(ctypes.Structure):
+    """fsea_extract_job (include/fsea.h): one cut-out of a resident recording."""
+    _fields_ = [("first", ctypes.c_uint64), ("n_samples", ctypes.c_uint64), ("sample_offset", ctypes.c_uint64),
+                ("cycles_per_sample", ctypes.c_double), ("phase0_cycles", ctypes.c_double), ("out_first", ctypes.c_uint64)]
 
 
 class CaptureRun(ctypes.Structure):
@@ -210,6 +217,16 @@ API = {
     "fsea_events_link": (_ci, [_vp, _sz, _ci, _ci, _u32, _u32, _u64, _vp, _vp, _sz, _szp]),
     "fsea_events_paint_device": (_ci, [_vp, _vp, _vp, _sz, _u64, _sz, _vp, _sz, _vp]),
     "fsea_events_paint_host": (_ci, [_vp, _vp, _vp, _sz, _u64, _sz, _vp, _sz]),
+    "fsea_extract_create": (_ci, [_out, _vp, _ci, _ci, _ci]),
+    "fsea_extract_destroy": (_ci, [_vp]),
+    "fsea_extract_decimation": (_ci, [_vp]),
+    "fsea_extract_n_taps": (_ci, [_vp]),
+    "fsea_extract_out_pairs": (_sz, [_vp, _sz]),
+    "fsea_extract_lead": (_sz, [_ci, _ci]),
+    "fsea_extract_layout": (_ci, [_vp, _vp, _sz, _szp]),
+    "fsea_extract_run_device": (_ci, [_vp, _vp, _sz, _ci, _vp, _sz, _vp, _sz, _vp]),
+    "fsea_extract_run_host": (_ci, [_vp, _vp, _sz, _ci, _vp, _sz, _vp, _sz]),
+    "fsea_extract_jobs": (_ci, [_vp, _sz, _ci, _ci, _u64, _ci, _ci, _f64, _vp, _vp]),
     "fsea_iq_draw_create": (_ci, [_out, _ci]),
     "fsea_iq_draw_destroy": (_ci, [_vp]),
     "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
@@ -947,6 +964,73 @@ class Events(_RowsHandle):
         `pitch` bytes apart; asynchronous."""
         _check(self._L.fsea_events_paint_device(self._p, d_runs_ptr or None, d_values_ptr or None, n_runs, int(row0), n_rows,
                                                 d_image_ptr or None, self.width if pitch is None else pitch, stream or None))
+
+
+def extract_lead(n_taps, decimation):
+    """fsea_extract_lead: ceil((n_taps - 1) / decimation) * decimation, the samples a cut-out starts in front of its event."""
+    return hip_lib().fsea_extract_lead(int(n_taps), int(decimation))
+
+
+def extract_jobs(events, width, hop, n_samples, n_taps, decimation, max_fill=0.8):
+    """fsea_extract_jobs (host arithmetic): (jobs, fits) of an array of EVENTS_EVENT whose rows are the frames of `width`
+    samples, one every `hop`, of a recording of n_samples samples -- a ctypes array of ExtractJob, one per event with
+    out_first 0, and a uint8 array: 1 where the event's columns times the decimation fit max_fill * width."""
+    e = np.ascontiguousarray(events, dtype=EVENTS_EVENT)
+    if e.ndim != 1:
+        raise ValueError("events is a 1-D array")
+    jobs = (ExtractJob * e.size)()
+    fits = np.zeros(e.size, dtype=np.uint8)
+    _check(hip_lib().fsea_extract_jobs(e.ctypes.data if e.size else None, e.size, int(width), int(hop), int(n_samples), int(n_taps),
+                                       int(decimation), float(max_fill), ctypes.addressof(jobs) if e.size else None,
+                                       fits.ctypes.data if e.size else None))
+    return jobs, fits
+
+
+def _job_table(jobs):
+    """a sequence of ExtractJob as one ctypes array (a ctypes array of them passes through)"""
+    if isinstance(jobs, ctypes.Array) and jobs._type_ is ExtractJob:
+        return jobs
+    jobs = list(jobs)
+    return (ExtractJob * len(jobs))(*jobs)
+
+
+class Extract(_Handle):
+    """Event cut-outs on one device: a table of shift -> low-pass -> keep every decimation-th sample jobs over one recording
+    in one launch, stateless; thin wrapper over fsea_extract_*.  run() takes 8-bit IQ and the jobs from the host and
+    returns one complex64 array per job; run_device() works on resident memory with the jobs' own out_first."""
+    _kind = "extract"
+
+    def __init__(self, taps, decimation, device=0):
+        t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
+        self.n_taps, self.decimation, self.device = t.size, decimation, device
+        self._create("fsea_extract_create", t.ctypes.data if t.size else None, t.size, decimation, device)
+
+    def out_pairs(self, n_samples):
+        return self._L.fsea_extract_out_pairs(self._p, n_samples)
+
+    def layout(self, jobs):
+        """fsea_extract_layout: (the jobs as a ctypes array with out_first filled in, the pairs they need in all)."""
+        table = _job_table(jobs)
+        total = ctypes.c_size_t()
+        _check(self._L.fsea_extract_layout(self._p, ctypes.addressof(table) if len(table) else None, len(table), ctypes.byref(total)))
+        return table, total.value
+
+    def run(self, iq_u8, jobs, flip=False):
+        """The host form on a copy of the jobs laid out with layout(): a list of complex64 arrays, one per job."""
+        iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
+        table, total = self.layout([ExtractJob.from_buffer_copy(j) for j in jobs])
+        pairs = np.zeros(max(total, 1), dtype=np.complex64)
+        _check(self._L.fsea_extract_run_host(self._p, iq.ctypes.data, iq.size // 2, int(bool(flip)),
+                                             ctypes.addressof(table) if len(table) else None, len(table), pairs.ctypes.data, total))
+        return [pairs[j.out_first:j.out_first + j.n_samples // self.decimation].copy() for j in table]
+
+    def run_device(self, d_iq_ptr, n_iq_samples, jobs, d_pairs_ptr, pairs_capacity, flip=False, stream=0):
+        """Device pointers (ints, 16-byte aligned): 2 * n_iq_samples bytes in, pairs_capacity complex64 out, every job at its
+        own out_first; asynchronous.  The jobs are read before the call returns."""
+        table = _job_table(jobs)
+        _check(self._L.fsea_extract_run_device(self._p, d_iq_ptr or None, n_iq_samples, int(bool(flip)),
+                                               ctypes.addressof(table) if len(table) else None, len(table), d_pairs_ptr or None,
+                                               pairs_capacity, stream or None))
 
 
 class Demod(_ResettableHandle):

@@ -1,0 +1,305 @@
+/*
+ * fsea-cutouts -- from a recording to one IQ file per emission: fsea-events finds the time-frequency boxes, this tool turns
+ * each box back into its signal, mixed to the centre, low-passed and decimated by D.
+ *
+ * Pass 1 is fsea-events' for a recording: every frame of N samples (one every H) through a plan in a dB mode, the rows to a
+ * fsea_cfar object with a mask, mask and rows to a fsea_events object, all on the device chunk by chunk; the runs are kept
+ * on the host and linked once at the end.  Pass 2 turns the first --max-events surviving events into jobs with
+ * fsea_extract_jobs (include/fsea.h): a job begins fsea_extract_lead samples in front of its box, so that the filter has run
+ * in where the box begins, and ends with the last frame of the box; a job longer than --max-samples is cut short.  The jobs
+ * are grouped into batches whose samples total at most 64 MiB; the byte ranges of a batch are read from the file into one
+ * pinned buffer back to back, every job's `first` rebased to its place there (sample_offset stays the stream position), and
+ * the batch is uploaded and run in one fsea_extract_run_device call.  Cut-out j is written as DIR/cutout-%05u.cf32: raw
+ * little-endian f32 pairs at RATE / D, without the first lead / D outputs (the filter's run-in).  DIR/cutouts.txt gets one
+ * line per event:
+ *     number row_first row_last col_first col_last first_sample samples centre_mhz output_rate pairs fits cut_short
+ * (centre_mhz and output_rate are 0 without --rate and --freq).  An event whose columns times D exceed --fill of the N
+ * columns does not fit the decimated band and gets no file (fits 0); neither does one past --max-events or one with no
+ * output behind the run-in.  The tool prints
+ *     rows R runs N events E cutouts C skipped S
+ *
+ * usage: fsea-cutouts FILE --size N --decimation D --out DIR [--hop H] [--window NAME] [--flip] [--mode db5|db10|db]
+ *                     [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R]
+ *                     [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--taps L] [--cutoff HZ]
+ *                     [--fill F] [--max-events E] [--max-samples S]
+ */
+#include <errno.h>
+#include <limits.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <sys/types.h>
+
+#include "fsea.h"
+#include "tool_common.h"
+
+#define TOOL "fsea-cutouts"
+#define BATCH_SAMPLES ((size_t)32 << 20) /* 64 MiB of 8-bit IQ */
+
+static const char *USAGE =
+    "usage: fsea-cutouts FILE --size N --decimation D --out DIR [--hop H] [--window NAME] [--flip] [--mode db5|db10|db]\n"
+    "                    [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R]\n"
+    "                    [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--taps L] [--cutoff HZ]\n"
+    "                    [--fill F] [--max-events E] [--max-samples S]\n"
+    "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8).  The emissions are found as fsea-events finds them (its\n"
+    "  options, same defaults); each one whose columns times D fill at most F of the N columns is mixed to the centre,\n"
+    "  low-passed (L taps, half amplitude at --cutoff, default 0.4 RATE / D) and decimated by D on the GPU, all of a batch in\n"
+    "  one launch, and written to DIR/cutout-NNNNN.cf32 as f32 pairs; DIR/cutouts.txt lists every event.  A cut-out longer\n"
+    "  than S samples is cut short.  Prints `rows R runs N events E cutouts C skipped S`\n"
+    "  defaults: --taps 97 --fill 0.8 --max-events 1024 --max-samples 16777216";
+
+static void usage_error(const char *msg) { tool_usage_error(TOOL, msg); }
+
+static void die(const char *what) { tool_die(TOOL, what); }
+
+/* all runs of the input, in order */
+static fsea_events_run *g_runs = NULL;
+static size_t g_n_runs = 0, g_cap_runs = 0;
+
+static fsea_events_run *runs_room(size_t more) {
+    if (g_n_runs + more > g_cap_runs) {
+        size_t cap = g_cap_runs ? g_cap_runs : 1024;
+        while (cap < g_n_runs + more) cap *= 2;
+        fsea_events_run *grown = (fsea_events_run *)realloc(g_runs, cap * sizeof(fsea_events_run));
+        if (grown == NULL) usage_error("out of memory");
+        g_runs = grown;
+        g_cap_runs = cap;
+    }
+    return g_runs + g_n_runs;
+}
+
+int main(int argc, char **argv) {
+    const char *path = NULL, *out_dir = NULL, *window = "rect", *mode_name = "db5";
+    int size = 0, hop = 0, flip = 0, gap_cols = 0, gap_rows = 0, decimation = 0, n_taps = 97;
+    long long min_rows = 1, min_cols = 1, min_hits = 1, max_events = 1024, max_samples = 1ll << 24;
+    double cutoff = 0.0, fill = 0.8;
+    tool_detector det = TOOL_DETECTOR_DEFAULTS;
+    for (int i = 1; i < argc; i++) {
+        const int more = i + 1 < argc;
+        if (!strcmp(argv[i], "--help")) {
+            puts(USAGE);
+            return 0;
+        } else if (!strcmp(argv[i], "--size") && more) size = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--hop") && more) hop = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--window") && more) window = argv[++i];
+        else if (!strcmp(argv[i], "--flip")) flip = 1;
+        else if (!strcmp(argv[i], "--mode") && more) mode_name = argv[++i];
+        else if (tool_detector_option(TOOL, &det, argc, argv, &i)) continue;
+        else if (!strcmp(argv[i], "--gap-cols") && more) gap_cols = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--gap-rows") && more) gap_rows = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--min-rows") && more) min_rows = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--min-cols") && more) min_cols = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--min-hits") && more) min_hits = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--decimation") && more) decimation = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--taps") && more) n_taps = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--cutoff") && more) cutoff = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--fill") && more) fill = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--max-events") && more) max_events = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--max-samples") && more) max_samples = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--out") && more) out_dir = argv[++i];
+        else if (argv[i][0] != '-' && path == NULL) path = argv[i];
+        else usage_error(USAGE);
+    }
+    const double rate = det.rate, freq = det.freq;
+    if (det.image_path != NULL) usage_error("--image has no samples to cut out: give a recording");
+    if (path == NULL) usage_error("no recording file given");
+    if (size < 1 || size > FSEA_EVENTS_MAX_WIDTH) usage_error("--size must be in [1, 1048576]");
+    if (hop == 0) hop = size;
+    if (hop < 1) usage_error("--hop must be positive");
+    tool_detector_check(TOOL, &det);
+    if (gap_cols < 0 || gap_cols > FSEA_EVENTS_MAX_GAP_COLS) usage_error("--gap-cols must be in [0, 64]");
+    if (gap_rows < 0 || gap_rows > FSEA_EVENTS_MAX_GAP_ROWS) usage_error("--gap-rows must be in [0, 65536]");
+    if (min_rows < 1 || min_rows > 0xffffffffll) usage_error("--min-rows must be at least 1");
+    if (min_cols < 1 || min_cols > 0xffffffffll) usage_error("--min-cols must be at least 1");
+    if (min_hits < 1) usage_error("--min-hits must be at least 1");
+    tool_detector_check_axis(TOOL, &det);
+    if (decimation == 0) usage_error("--decimation D is required");
+    if (decimation < 1 || decimation > FSEA_ZOOM_MAX_DECIMATION) usage_error("--decimation must be in [1, 64]");
+    if (n_taps < 1 || n_taps > FSEA_FIR_MAX_TAPS) usage_error("--taps must be in [1, 512]");
+    if (!(fill > 0.0 && fill <= 1.0)) usage_error("--fill must be in (0, 1]");
+    if (max_events < 1 || max_events > FSEA_EXTRACT_MAX_JOBS) usage_error("--max-events must be in [1, 65536]");
+    if (max_samples < 1 || max_samples > (1ll << 24)) usage_error("--max-samples must be in [1, 16777216]");
+    if (cutoff < 0.0) usage_error("--cutoff must be positive");
+    if (out_dir == NULL) usage_error("--out DIR is required");
+    int mode = 0, type = 0;
+    if (!tool_rows_mode(mode_name, "db", &mode, &type)) usage_error("--mode must be db5, db10 or db");
+
+    /* pass 1: fsea-events' */
+    tool_row_source src;
+    tool_rows_open(&src, TOOL, path, size, hop, mode, window, flip);
+    fsea_cfar *cfar = tool_detector_create(TOOL, &det, size);
+    fsea_events *events = NULL;
+    if (fsea_events_create(&events, size, 0) != FSEA_OK) die("fsea_events_create");
+    if (fsea_events_set_gap(events, gap_cols) != FSEA_OK) die("fsea_events_set_gap");
+    const size_t n = (size_t)size;
+    void *d_rows = src.d_rows, *d_mask = NULL, *d_runs = NULL;
+    size_t d_runs_cap = 0, done = 0;
+    if (fsea_device_alloc(0, src.frames_max * n, &d_mask) != FSEA_OK) die("fsea_device_alloc");
+    for (size_t frames; (frames = tool_rows_next(&src)) > 0; done += frames) {
+        if (fsea_cfar_add_device(cfar, d_rows, type, frames, n, (uint8_t *)d_mask, NULL, NULL) != FSEA_OK) die("fsea_cfar_add_device");
+        size_t found = 0;
+        if (fsea_events_reset(events) != FSEA_OK) die("fsea_events_reset");
+        if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, NULL, 0, &found, NULL) != FSEA_OK) {
+            die("fsea_events_runs_device");
+        }
+        if (found == 0) continue;
+        if (found > d_runs_cap) {
+            if (d_runs != NULL) fsea_device_free(0, d_runs);
+            d_runs_cap = found + found / 2;
+            if (fsea_device_alloc(0, d_runs_cap * sizeof(fsea_events_run), &d_runs) != FSEA_OK) die("fsea_device_alloc");
+        }
+        if (fsea_events_reset(events) != FSEA_OK) die("fsea_events_reset");
+        if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, (fsea_events_run *)d_runs, found, &found,
+                                    NULL) != FSEA_OK) {
+            die("fsea_events_runs_device");
+        }
+        fsea_events_run *dst = runs_room(found);
+        if (fsea_copy_to_host(0, dst, d_runs, found * sizeof(fsea_events_run)) != FSEA_OK) die("fsea_copy_to_host");
+        if (done + frames > 0xffffffffull) usage_error("the recording holds more than 2^32 - 1 frames");
+        for (size_t i = 0; i < found; i++) dst[i].row += (uint32_t)done;
+        g_n_runs += found;
+    }
+    tool_rows_close(&src);
+    fsea_device_free(0, d_mask);
+    if (d_runs != NULL) fsea_device_free(0, d_runs);
+    if (done < 1) return tool_rows_none(TOOL, path, size);
+
+    size_t n_events = 0;
+    if (fsea_events_link(g_runs, g_n_runs, gap_cols, gap_rows, (uint32_t)min_rows, (uint32_t)min_cols, (uint64_t)min_hits, NULL, NULL, 0,
+                         &n_events) != FSEA_OK) {
+        die("fsea_events_link");
+    }
+    fsea_events_event *found_events = (fsea_events_event *)malloc(sizeof(fsea_events_event) * (n_events + 1));
+    if (found_events == NULL) usage_error("out of memory");
+    if (fsea_events_link(g_runs, g_n_runs, gap_cols, gap_rows, (uint32_t)min_rows, (uint32_t)min_cols, (uint64_t)min_hits, NULL,
+                         found_events, n_events, &n_events) != FSEA_OK) {
+        die("fsea_events_link");
+    }
+
+    /* pass 2: the first max_events events as jobs */
+    FILE *fp = fopen(path, "rb");
+    if (fp == NULL || fseek(fp, 0, SEEK_END) != 0) usage_error("cannot read the recording again");
+    const uint64_t n_samples = (uint64_t)ftell(fp) / 2;
+    const size_t n_jobs = n_events < (size_t)max_events ? n_events : (size_t)max_events;
+    const size_t lead_out = fsea_extract_lead(n_taps, decimation) / (size_t)decimation;
+    fsea_extract_job *jobs = (fsea_extract_job *)malloc(sizeof(fsea_extract_job) * (n_jobs + 1));
+    uint8_t *fits = (uint8_t *)calloc(n_jobs + 1, 1), *cut = (uint8_t *)calloc(n_jobs + 1, 1);
+    size_t *written = (size_t *)calloc(n_events + 1, sizeof(size_t));
+    double *taps = (double *)malloc(sizeof(double) * (size_t)n_taps);
+    if (jobs == NULL || fits == NULL || cut == NULL || written == NULL || taps == NULL) usage_error("out of memory");
+    if (fsea_extract_jobs(found_events, n_jobs, size, hop, n_samples, n_taps, decimation, fill, jobs, fits) != FSEA_OK) die("fsea_extract_jobs");
+    for (size_t j = 0; j < n_jobs; j++) {
+        if (jobs[j].n_samples > (uint64_t)max_samples) {
+            jobs[j].n_samples = (uint64_t)max_samples;
+            cut[j] = 1;
+        }
+    }
+    /* the design takes a rate and a frequency in the same unit: without --rate, 1 and cycles per sample */
+    const double design_rate = rate > 0.0 ? rate : 1.0;
+    if (cutoff == 0.0) cutoff = 0.4 * design_rate / (double)decimation;
+    if (fsea_fir_lowpass_taps(design_rate, cutoff, n_taps, taps) != FSEA_OK) die("fsea_fir_lowpass_taps");
+    fsea_extract *extract = NULL;
+    if (fsea_extract_create(&extract, taps, n_taps, decimation, 0) != FSEA_OK) die("fsea_extract_create");
+    if (mkdir(out_dir, 0777) != 0 && errno != EEXIST) {
+        fprintf(stderr, TOOL ": cannot create directory %s\n", out_dir);
+        return EXIT_FAILURE;
+    }
+
+    size_t name_len = strlen(out_dir) + 32, n_cutouts = 0;
+    char *name = (char *)malloc(name_len);
+    fsea_extract_job *batch = (fsea_extract_job *)malloc(sizeof(fsea_extract_job) * (n_jobs + 1));
+    size_t *batch_of = (size_t *)malloc(sizeof(size_t) * (n_jobs + 1));
+    void *h_iq = NULL, *d_iq = NULL, *d_pairs = NULL;
+    float *h_pairs = NULL;
+    size_t pairs_cap = 0;
+    if (name == NULL || batch == NULL || batch_of == NULL) usage_error("out of memory");
+    if (fsea_host_alloc(2 * BATCH_SAMPLES, &h_iq) != FSEA_OK) die("fsea_host_alloc");
+    if (fsea_device_alloc(0, 2 * BATCH_SAMPLES, &d_iq) != FSEA_OK) die("fsea_device_alloc");
+    for (size_t j = 0; j < n_jobs;) {
+        /* a batch: the jobs from j on whose samples fit the buffer, back to back */
+        size_t n_batch = 0, at = 0;
+        for (; j < n_jobs && at + (size_t)jobs[j].n_samples <= BATCH_SAMPLES; j++) {
+            if (jobs[j].n_samples == 0) continue;
+            if (fseek(fp, (long)(2 * jobs[j].first), SEEK_SET) != 0 ||
+                fread((uint8_t *)h_iq + 2 * at, 2, (size_t)jobs[j].n_samples, fp) != (size_t)jobs[j].n_samples) {
+                fprintf(stderr, TOOL ": short read of %s\n", path);
+                return EXIT_FAILURE;
+            }
+            batch[n_batch] = jobs[j];
+            batch[n_batch].first = at;   /* its place in the buffer; sample_offset stays the stream position */
+            batch_of[n_batch++] = j;
+            at += (size_t)jobs[j].n_samples;
+        }
+        if (n_batch == 0) continue;
+        size_t total = 0;
+        if (fsea_extract_layout(extract, batch, n_batch, &total) != FSEA_OK) die("fsea_extract_layout");
+        if (total == 0) continue;
+        if (total > pairs_cap) {
+            if (d_pairs != NULL) fsea_device_free(0, d_pairs);
+            if (h_pairs != NULL) fsea_host_free(h_pairs);
+            pairs_cap = total + total / 2;
+            void *h = NULL;
+            if (fsea_device_alloc(0, pairs_cap * 2 * sizeof(float), &d_pairs) != FSEA_OK) die("fsea_device_alloc");
+            if (fsea_host_alloc(pairs_cap * 2 * sizeof(float), &h) != FSEA_OK) die("fsea_host_alloc");
+            h_pairs = (float *)h;
+        }
+        if (fsea_copy_to_device(0, d_iq, h_iq, 2 * at) != FSEA_OK) die("fsea_copy_to_device");
+        if (fsea_extract_run_device(extract, d_iq, at, flip, batch, n_batch, d_pairs, total, NULL) != FSEA_OK) die("fsea_extract_run_device");
+        if (fsea_copy_to_host(0, h_pairs, d_pairs, total * 2 * sizeof(float)) != FSEA_OK) die("fsea_copy_to_host");
+        for (size_t b = 0; b < n_batch; b++) {
+            const size_t n_out = (size_t)batch[b].n_samples / (size_t)decimation, e = batch_of[b];
+            if (n_out <= lead_out) continue;
+            snprintf(name, name_len, "%s/cutout-%05u.cf32", out_dir, (unsigned)e);
+            FILE *out = fopen(name, "wb");
+            const size_t keep = n_out - lead_out;
+            if (out == NULL || fwrite(h_pairs + 2 * ((size_t)batch[b].out_first + lead_out), 2 * sizeof(float), keep, out) != keep ||
+                fclose(out) != 0) {
+                fprintf(stderr, TOOL ": cannot write %s\n", name);
+                return EXIT_FAILURE;
+            }
+            written[e] = keep;
+            n_cutouts++;
+        }
+    }
+
+    snprintf(name, name_len, "%s/cutouts.txt", out_dir);
+    FILE *list = fopen(name, "w");
+    if (list == NULL) {
+        fprintf(stderr, TOOL ": cannot write %s\n", name);
+        return EXIT_FAILURE;
+    }
+    for (size_t e = 0; e < n_events; e++) {
+        const fsea_events_event *ev = &found_events[e];
+        const int listed = e < n_jobs;
+        const double mhz = rate > 0.0 ? 0.5 * (tool_column_mhz(freq, rate, size, ev->col_first) + tool_column_mhz(freq, rate, size, ev->col_last)) : 0.0;
+        fprintf(list, "%u %u %u %u %u %llu %llu %.6f %.3f %zu %d %d\n", (unsigned)e, ev->row_first, ev->row_last, ev->col_first,
+                ev->col_last, listed ? (unsigned long long)jobs[e].first : 0ull, listed ? (unsigned long long)jobs[e].n_samples : 0ull, mhz,
+                rate / (double)decimation, written[e], listed ? (int)fits[e] : 0, listed ? (int)cut[e] : 0);
+    }
+    if (fclose(list) != 0) {
+        fprintf(stderr, TOOL ": cannot write %s\n", name);
+        return EXIT_FAILURE;
+    }
+    printf("rows %zu runs %zu events %zu cutouts %zu skipped %zu\n", done, g_n_runs, n_events, n_cutouts, n_events - n_cutouts);
+
+    fsea_extract_destroy(extract);
+    fsea_events_destroy(events);
+    fsea_cfar_destroy(cfar);
+    fsea_device_free(0, d_iq);
+    if (d_pairs != NULL) fsea_device_free(0, d_pairs);
+    if (h_pairs != NULL) fsea_host_free(h_pairs);
+    fsea_host_free(h_iq);
+    fclose(fp);
+    free(name);
+    free(batch);
+    free(batch_of);
+    free(jobs);
+    free(fits);
+    free(cut);
+    free(written);
+    free(taps);
+    free(found_events);
+    free(g_runs);
+    return 0;
+}

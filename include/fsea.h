@@ -35,6 +35,7 @@
  *   fsea_persist_*        a persistence spectrum (no counterpart in the reference): per-bin level histograms of resident rows
  *   fsea_cfar_*           a CFAR detector across frequency (no counterpart in the reference): occupied bins, bands and masks
  *   fsea_events_*         spectrum events (no counterpart in the reference): a detection mask as runs, time-frequency boxes
+ *   fsea_extract_*        event cut-outs (no counterpart in the reference): each box of fsea_events_link as decimated IQ
  *   fsea_detect_*         the burst detector of lua/signal-detector.lua: the two loops of nrf_signal_detector_process,
  *                         src/nrf.c:883-898, as integer sums over many blocks per launch
  *   fsea_capture_*        that scene on a resident recording: detect -> gate -> filter the bursts -> line images
@@ -69,6 +70,7 @@ typedef struct fsea_pfb fsea_pfb;
 typedef struct fsea_persist fsea_persist;
 typedef struct fsea_cfar fsea_cfar;
 typedef struct fsea_events fsea_events;
+typedef struct fsea_extract fsea_extract;
 typedef struct fsea_demod fsea_demod;
 typedef struct fsea_interp fsea_interp;
 typedef struct fsea_trace fsea_trace;
@@ -788,6 +790,74 @@ int fsea_events_paint_device(fsea_events *events, const fsea_events_run *d_runs,
                              uint64_t row0, size_t n_rows, uint8_t *d_image, size_t pitch, void *stream);
 int fsea_events_paint_host(fsea_events *events, const fsea_events_run *runs, const uint8_t *values, size_t n_runs, uint64_t row0,
                            size_t n_rows, uint8_t *image, size_t pitch);
+
+/* Event cut-outs: the signal behind each box of fsea_events_link -- the emission's IQ mixed to the centre, low-passed to its
+ * own bandwidth and decimated.  fsea_zoom does this arithmetic for one centre frequency and one contiguous stream per call;
+ * an event list is hundreds of short spans, each with its own centre and start, scattered over one resident recording.  An
+ * fsea_extract holds the taps c (L of them) and the decimation D and takes a table of jobs over one resident buffer of 8-bit
+ * IQ: every job's decimated pairs in one launch.  There is no state between calls and no reset.
+ *   job:        with x the rotated samples of fsea_fir_u8_shifted_* for the n_samples samples at d_iq + 2 first (same flip; the
+ *               stream position of sample m is sample_offset + m; cycles_per_sample and phase0_cycles the job's own) and
+ *               x_ext = (L - 1 zeros) ++ x,
+ *                 pairs[out_first + i] = sum_{k < L} c[k] x_ext[i D + k],   i < n_samples / D (rounded down):
+ *               the pairs fsea_zoom_run_device writes right after fsea_zoom_reset with the same taps, D, flip and arguments
+ *               on those samples, bit for bit, whatever other jobs share the call, whatever their order and whatever first
+ *               mod 8 is.  Jobs may overlap in the input; their output ranges must not overlap and lie inside
+ *               pairs_capacity.  A job with n_samples < D has no output and is legal.  Nothing outside the jobs' output
+ *               ranges is written, nothing outside the n_iq_samples samples is read.  `jobs` is host memory, read before
+ *               the call returns.  first and sample_offset are two fields because a caller that uploads only a window of a
+ *               recording rebases first and leaves the stream position alone.
+ *   create:     taps and decimation as fsea_zoom_create, with its limits (FSEA_FIR_MAX_TAPS, FSEA_ZOOM_MAX_DECIMATION) and
+ *               checks; FSEA_ENODEVICE without a GPU.  decimation and n_taps return 0 for NULL, out_pairs (n_samples / D) too.
+ *   lead:       ceil((L - 1) / D) D, the samples in front of an event a job starts early so that output lead / D is the first
+ *               whose taps all lie on samples; 0 for an n_taps or decimation below 1.  No object needed.
+ *   layout:     fills out_first in job order, each job at the next even pair index (a 16-byte boundary), and gives the
+ *               capacity needed in *total_pairs.  FSEA_EINVAL for a NULL object or total_pairs, n_jobs above
+ *               FSEA_EXTRACT_MAX_JOBS, a NULL table with n_jobs > 0.
+ *   run_device: d_iq (2 n_iq_samples bytes) and d_pairs (2 pairs_capacity floats) 16-byte aligned; asynchronous on `stream`.
+ *               The object owns the device table of the jobs, so calls on several streams follow one another (an event).
+ *               Kernel fsea_extract_u8 (and _s, _m: the zoom's three LDS sizes): one workgroup per tile of
+ *               FSEA_ZOOM_TILE_OUTPUTS outputs of one job, which it finds by a bisection over the jobs' first tiles.
+ *   run_host:   the same from and to host memory through pinned staging on the object's own stream; returns when `pairs` is
+ *               complete; of `pairs` only the jobs' output ranges are written.
+ * Both check, before any device work and reading nothing of the object but its decimation, in this order: a NULL object;
+ * n_jobs above FSEA_EXTRACT_MAX_JOBS; n_jobs == 0 is then a successful no-op; a NULL job table; a NULL buffer; per job in
+ * table order: first + n_samples past n_iq_samples, n_samples above 2^31, the cycles_per_sample, phase0_cycles and
+ * sample_offset + n_samples limits of fsea_fir_u8_shifted_* (each text names the job); more than 2^31 outputs in the call;
+ * per job with output in table order: an output range past pairs_capacity; two output ranges that overlap (the text names
+ * both jobs); for run_device a misaligned d_iq or d_pairs.  All FSEA_EINVAL; a refused call writes nothing.  Destroy waits
+ * for the device.  Calls on one object from several threads are serialised.
+ *   jobs:       fsea_extract_jobs, host arithmetic, no device: one job per event, in order.  With N = width, H = hop, row r of
+ *               the events beginning at sample r H of a recording of n_samples samples, and lead as above: begin =
+ *               row_first H; first = sample_offset = begin - min(begin, lead); end = min(n_samples, row_last H + N); the
+ *               job's n_samples = end - first, 0 if end <= first; cycles_per_sample = -(col_first + col_last - 2 (N / 2)) /
+ *               (2 N): the negated integer over the integer 2 N in one double division (column N / 2 is the centre; an
+ *               event centred there gets +0.0); phase0_cycles = 0; out_first = 0, the caller lays the jobs out.  fits[i] =
+ *               1 when (col_last - col_first + 1) D <= max_fill N (the product max_fill N rounded once), else 0 and the
+ *               job's n_samples 0.  FSEA_EINVAL for NULL pointers (with n_events > 0), width or hop < 1, n_taps or
+ *               decimation out of create's range, max_fill outside (0, 1]. */
+#define FSEA_EXTRACT_MAX_JOBS 65536
+typedef struct {              /* 48 bytes */
+    uint64_t first;           /* index in d_iq / iq of the job's sample 0 */
+    uint64_t n_samples;       /* samples of the job, <= 2^31; first + n_samples <= n_iq_samples */
+    uint64_t sample_offset;   /* stream position of the job's sample 0 (the phase; as fsea_fir_u8_shifted_*) */
+    double cycles_per_sample;
+    double phase0_cycles;
+    uint64_t out_first;       /* index in d_pairs / pairs of the job's output 0; it has n_samples / D outputs */
+} fsea_extract_job;
+int fsea_extract_create(fsea_extract **extract, const double *taps, int n_taps, int decimation, int device);
+int fsea_extract_destroy(fsea_extract *extract);
+int fsea_extract_decimation(const fsea_extract *extract);
+int fsea_extract_n_taps(const fsea_extract *extract);
+size_t fsea_extract_out_pairs(const fsea_extract *extract, size_t n_samples);
+size_t fsea_extract_lead(int n_taps, int decimation);
+int fsea_extract_layout(const fsea_extract *extract, fsea_extract_job *jobs, size_t n_jobs, size_t *total_pairs);
+int fsea_extract_run_device(fsea_extract *extract, const void *d_iq, size_t n_iq_samples, int flip, const fsea_extract_job *jobs,
+                            size_t n_jobs, void *d_pairs, size_t pairs_capacity, void *stream);
+int fsea_extract_run_host(fsea_extract *extract, const uint8_t *iq, size_t n_iq_samples, int flip, const fsea_extract_job *jobs,
+                          size_t n_jobs, float *pairs, size_t pairs_capacity);
+int fsea_extract_jobs(const fsea_events_event *events, size_t n_events, int width, int hop, uint64_t n_samples, int n_taps,
+                      int decimation, double max_fill, fsea_extract_job *jobs, uint8_t *fits);
 
 /* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
  * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With

@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""What a table of cut-outs in one launch (fsea_extract_*, kernel fsea_extract_u8) costs against the zoom it shares its
+arithmetic with, on a resident recording of 2^25 samples, L = 97, D = 4, 16, 64.  HIP-event times in one process, median of
+REPS calls after WARMUP:
+
+(a) one fsea_extract_run_device of 256 jobs of 65536 + D - 1 samples each, spread over the recording at firsts that are no
+    multiples of 8, every job with its own centre;
+(b) one fsea_zoom_run_device over the same total number of samples (a zoom whose plan yields a single 128-point frame, as
+    scripts/zoom_rate.py times the decimating kernel);
+(c) 256 fsea_zoom_run_device calls of one job's length each: the route before this object, without the resets it would
+    also need.
+
+(a) / (b) is what the ragged last tile of every job, the table look-up and the misaligned ends cost; (c) / (a) is what the
+one launch buys.  The traffic bound is 2 + 8 / D bytes per input sample at 8 TB/s, as in profiles/zoom_rate.txt.
+
+Without an argument every D runs as a child process under its own time limit and the lines go to profiles/extract_rate.txt
+(or the file named after --out); a part that fails ends the run.
+Usage: python scripts/extract_rate.py [--out FILE] | python scripts/extract_rate.py measure D"""
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from frequensea_amd import fsea  # noqa: E402
+
+N_SAMPLES = 1 << 25
+TAPS = 97
+DECIMATIONS = (4, 16, 64)
+N_JOBS, JOB_BASE = 256, 65536
+WARMUP, REPS = 5, 20
+HBM_BPS = 8e12
+STEP_LIMIT_S = 240
+
+HEADER = """# scripts/extract_rate.py on one MI355X: HIP-event times in one process, median (min) of %d calls after %d
+# recording: 2^25 samples resident, L = %d, taps = lowpass(10e6, 10e6 / (2 D), %d)
+# (a) one fsea_extract_run_device: %d jobs of 65536 + D - 1 samples, first = 131072 i + 3 + i mod 5, a centre per job
+# (b) one fsea_zoom_run_device over the same number of samples (its plan yields one 128-point frame)
+# (c) %d fsea_zoom_run_device calls of one job's length each, no resets
+# traffic bound = (2 + 8 / D) bytes per input sample at 8 TB/s; host time: wall time of the call (a) itself, until it returns
+""" % (REPS, WARMUP, TAPS, TAPS, N_JOBS, N_JOBS)
+
+
+def timed(fn):
+    import torch
+    times = []
+    for k in range(WARMUP + REPS):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        if k >= WARMUP:
+            times.append(e0.elapsed_time(e1) / 1e3)
+    return float(np.median(times)), min(times)
+
+
+def measure(D):
+    import torch
+    iq = np.random.default_rng(1).integers(0, 256, 2 * N_SAMPLES, dtype=np.uint8)
+    d_in = fsea.DeviceBuffer(iq.nbytes).upload(iq)
+    torch.cuda.init()
+    c = fsea.lowpass_taps(10e6, 10e6 / (2 * D), TAPS)
+    n_job = JOB_BASE + D - 1
+    total_samples = N_JOBS * n_job
+    ex = fsea.Extract(c, D)
+    jobs = [fsea.ExtractJob(131072 * i + 3 + i % 5, n_job, 131072 * i + 3 + i % 5, (i - 128) / 1024.0, 0.0, 0) for i in range(N_JOBS)]
+    table, total = ex.layout(jobs)
+    d_pairs = fsea.DeviceBuffer(8 * total)
+    zoom = fsea.Zoom(c, D, 128, 1 << 30)
+    assert zoom.out_rows(total_samples) == 1 and zoom.out_rows(n_job) == 1
+    d_row = fsea.DeviceBuffer(128 * 4)
+
+    def a():
+        ex.run_device(d_in.ptr.value, N_SAMPLES, table, d_pairs.ptr.value, total, flip=True)
+
+    def b():
+        zoom.run_device(d_in.ptr.value, total_samples, d_row.ptr.value, -0.125, flip=True)
+
+    def c_route():
+        for j in table:
+            zoom.run_device(d_in.ptr.value + 2 * (j.first & ~7), n_job, d_row.ptr.value, j.cycles_per_sample,
+                            sample_offset=j.sample_offset, flip=True)
+
+    (ta, ta_min), (tb, tb_min), (tc, tc_min) = timed(a), timed(b), timed(c_route)
+    # what the host spends inside the call before it returns (checks, 256 records with eight phasors each, two launches): a
+    # HIP-event interval on an idle stream holds it too
+    sync = fsea.Plan(128)
+    host = []
+    for _ in range(REPS):
+        sync.synchronize()
+        t0 = time.perf_counter()
+        a()
+        host.append(time.perf_counter() - t0)
+    sync.synchronize()
+    sync.close()
+    bound = (2.0 + 8.0 / D) * total_samples / HBM_BPS
+    print("D=%-2d %d samples in %d jobs   (a) extract %8.1f us (%8.1f)   (b) one zoom call %8.1f us (%8.1f)   (c) %d zoom calls %9.1f us (%9.1f)"
+          "   traffic bound %5.1f us   (a)/(b) %.3f   (c)/(a) %.1f   host time of (a) %.1f us"
+          % (D, total_samples, N_JOBS, ta * 1e6, ta_min * 1e6, tb * 1e6, tb_min * 1e6, N_JOBS, tc * 1e6, tc_min * 1e6, bound * 1e6, ta / tb,
+             tc / ta, float(np.median(host)) * 1e6))
+    for o in (ex, zoom):
+        o.close()
+    for o in (d_in, d_pairs, d_row):
+        o.free()
+
+
+def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "measure":
+        measure(int(sys.argv[2]))
+        return
+    out = sys.argv[2] if len(sys.argv) > 2 and sys.argv[1] == "--out" else os.path.join(ROOT, "profiles", "extract_rate.txt")
+    text = HEADER + "\n"
+    for D in DECIMATIONS:
+        r = subprocess.run(["timeout", "-k", "10", str(STEP_LIMIT_S), sys.executable, os.path.abspath(__file__), "measure", str(D)],
+                           capture_output=True, text=True)
+        sys.stdout.write(r.stdout)
+        sys.stderr.write(r.stderr)
+        if r.returncode != 0:
+            raise SystemExit("D = %d failed (exit status %d): stopping" % (D, r.returncode))
+        text += r.stdout
+    with open(out, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()
