@@ -8,11 +8,10 @@ the row's ends, plus the mask bytes written; the share says how far the call is 
 Beside it the ratio to the plan's own launch that produced those rows (fsea_exec_u8_device, code the detector does not
 touch), measured in the same process.
 
-One process; every GPU step runs under an alarm of its own, which ends the process where a step hangs.  What it prints also
-goes to profiles/cfar_rate.txt (--to FILE: there instead).
-Usage: python scripts/cfar_rate.py [--to FILE]"""
+The measurement is one part, `run`; without an argument it runs as a child process under its time limit, and what it prints
+also goes to profiles/cfar_rate.txt (--to FILE: there instead).
+Usage: python scripts/cfar_rate.py [run] [--to FILE]"""
 import os
-import signal
 import sys
 
 import numpy as np
@@ -20,41 +19,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea  # noqa: E402
+import ratelib  # noqa: E402
 
 N, FRAMES = 8192, 4096
 CASES = ((2, 16), (64, 256))
 WARMUP, REPS = 5, 20
 HBM_BPS = 8e12
-STEP_LIMIT_S = 120
-
-
-class step:
-    """A GPU step under its own time limit: SIGALRM's default action ends the process, also inside a library call."""
-
-    def __init__(self, what):
-        self.what = what
-
-    def __enter__(self):
-        signal.signal(signal.SIGALRM, signal.SIG_DFL)
-        signal.alarm(STEP_LIMIT_S)
-
-    def __exit__(self, *exc):
-        signal.alarm(0)
-        return False
-
-
-def event_times(call):
-    import torch
-    times = []
-    for k in range(WARMUP + REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        if k >= WARMUP:
-            times.append(e0.elapsed_time(e1) / 1e3)
-    return float(np.median(times)), min(times)
+STEP_LIMIT_S = 120      # the whole part took 13.0 s of wall time on an MI355X
 
 
 def traffic_bytes(guard, train):
@@ -64,42 +35,35 @@ def traffic_bytes(guard, train):
     return FRAMES * per_row, FRAMES * N
 
 
-def main():
-    args = sys.argv[1:]
-    to = os.path.join(ROOT, "profiles", "cfar_rate.txt")
-    if "--to" in args:
-        to = args[args.index("--to") + 1]
+def run():
     if fsea.device_count() < 1:
         raise SystemExit("cfar_rate.py needs a GPU")
     import torch
-    lines = []
 
     def say(text):
         print(text, flush=True)
-        lines.append(text)
 
-    with step("set-up"):
-        torch.cuda.init()
-        raw = np.random.default_rng(1).integers(0, 256, 2 * N * FRAMES, dtype=np.uint8)
-        d_in = fsea.DeviceBuffer(raw.nbytes).upload(raw)
-        d_rows = fsea.DeviceBuffer(FRAMES * N)
-        d_mask = fsea.DeviceBuffer(FRAMES * N)
-        plan = fsea.Plan(N, N, fsea.MODE_DB5_U8_DCFIX)
-        plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True)
-        plan.synchronize()
+    torch.cuda.init()
+    raw = np.random.default_rng(1).integers(0, 256, 2 * N * FRAMES, dtype=np.uint8)
+    d_in = fsea.DeviceBuffer(raw.nbytes).upload(raw)
+    d_rows = fsea.DeviceBuffer(FRAMES * N)
+    d_mask = fsea.DeviceBuffer(FRAMES * N)
+    plan = fsea.Plan(N, N, fsea.MODE_DB5_U8_DCFIX)
+    plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True)
+    plan.synchronize()
     say("%d rows x %d columns of DB5 rows resident; fsea_cfar_add_device with a mask, median of %d calls after %d"
         % (FRAMES, N, REPS, WARMUP))
-    with step("plan"):
-        pt, pmin = event_times(lambda: plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True))
+    pt, pmin = ratelib.median_min(ratelib.per_call(lambda: plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True),
+                                                   WARMUP, REPS))
     say("the plan's launch that produces the rows: %8.1f us (min %8.1f)" % (pt * 1e6, pmin * 1e6))
     for guard, train in CASES:
-        with step("add"):
-            c = fsea.Cfar(N)
-            c.set(guard, train, 60, fsea.CFAR_CA)
-            t, tmin = event_times(lambda: c.add_device(d_rows.ptr.value, fsea.CFAR_U8, FRAMES, N, d_mask.ptr.value))
-            detected = int(c.hits().sum())
-            rows = c.rows
-            c.close()
+        c = fsea.Cfar(N)
+        c.set(guard, train, 60, fsea.CFAR_CA)
+        t, tmin = ratelib.median_min(ratelib.per_call(
+            lambda: c.add_device(d_rows.ptr.value, fsea.CFAR_U8, FRAMES, N, d_mask.ptr.value), WARMUP, REPS))
+        detected = int(c.hits().sum())
+        rows = c.rows
+        c.close()
         read, written = traffic_bytes(guard, train)
         bound = (read + written) / HBM_BPS
         say("(G, T) = (%2d, %3d): add %8.1f us (min %8.1f)   bound %6.1f us (%d bytes read, %d written at 8 TB/s)   "
@@ -108,8 +72,11 @@ def main():
     plan.close()
     for b in (d_in, d_rows, d_mask):
         b.free()
-    with open(to, "w") as f:
-        f.write("\n".join(lines) + "\n")
+
+
+def main():
+    if ratelib.run_parts(__file__, {"run": STEP_LIMIT_S}, sys.argv[1:], to=os.path.join(ROOT, "profiles", "cfar_rate.txt")):
+        run()
 
 
 if __name__ == "__main__":

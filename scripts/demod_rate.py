@@ -11,23 +11,28 @@
    printed.  Counted FLOP per channel and input sample (FMA = 2, a divide = 1): conversion 4, rotation 6, phase
    recurrence 6, stage 1 (2 x 51 taps x 2) / rate_mul1, discriminator 20 / rate_mul1, stage 3 (41 x 2) / (rate_mul1
    rate_mul3), de-emphasis 3 / (rate_mul1 rate_mul3).
-Usage: python scripts/demod_rate.py [--device-only] [--fp64-tflops X] [--out FILE]"""
+The measurement is one part, `run`, which also writes what it prints to profiles/demod_rate.txt (--out FILE: there
+instead); without `run` on the command line it runs as a child process under its time limit.
+Usage: python scripts/demod_rate.py [run] [--device-only] [--fp64-tflops X] [--out FILE]"""
 import argparse
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea, nrf  # noqa: E402
+import ratelib  # noqa: E402
 
 PAIRS = 131072
 WARMUP, REPS, ROUNDS = 3, 20, 3
 HBM_BPS = 8e12
 CHANNELS = [1, 8, 64, 256]
+# the part's time limit: three times its wall time on an MI355X (1.9 s), rounded up to 30 s, and at least 120 s -- a first
+# import of torch on a fresh machine alone can take over a minute
+STEP_LIMIT_S = 120
 
 
 def flop_per_sample(in_rate, out_rate=48000):
@@ -45,13 +50,7 @@ def host_call(lines):
     L = nrf.nrf_lib()
     samples = np.ascontiguousarray(block() ^ 0x80)
     dec = L.nrf_decoder_new(nrf.NRF_DEMODULATE_WBFM, 5000000, 48000, 50000)
-    for _ in range(WARMUP):
-        L.nrf_decoder_process(dec, samples.ctypes.data, PAIRS)
-    walls = []
-    for _ in range(100):
-        t0 = time.perf_counter()
-        L.nrf_decoder_process(dec, samples.ctypes.data, PAIRS)
-        walls.append(time.perf_counter() - t0)
+    walls = ratelib.wall(lambda: L.nrf_decoder_process(dec, samples.ctypes.data, PAIRS), WARMUP, 100)
     L.nrf_decoder_free(dec)
     med = statistics.median(walls)
     lines.append("1. nrf_decoder_process, WBFM 5 MHz -> 48 kHz, 131072 pairs (host form), 100 calls")
@@ -78,18 +77,7 @@ def device_calls(lines, fp64_tflops):
         def call():
             d.run_device(d_iq.data_ptr(), PAIRS, out.data_ptr(), flip=True)
 
-        for _ in range(WARMUP):
-            call()
-        torch.cuda.synchronize()
-        best = 1e9
-        for _ in range(ROUNDS):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(REPS):
-                call()
-            e1.record()
-            e1.synchronize()
-            best = min(best, e0.elapsed_time(e1) / 1e3 / REPS)
+        best = min(ratelib.per_round(call, WARMUP, REPS, ROUNDS))
         d.close()
         cs = K * PAIRS / best
         t_bytes = 2 * PAIRS / HBM_BPS
@@ -102,11 +90,12 @@ def device_calls(lines, fp64_tflops):
         lines.append(line)
 
 
-def main():
+def run():
     import torch
     torch.cuda.init()     # torch's HIP runtime first, then the libraries (libfsea_hip.so loaded globally, as the tests do)
     fsea.hip_lib()
     ap = argparse.ArgumentParser()
+    ap.add_argument("run")
     ap.add_argument("--device-only", action="store_true")
     ap.add_argument("--fp64-tflops", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "demod_rate.txt"))
@@ -119,6 +108,11 @@ def main():
     print(text, end="")
     with open(a.out, "w") as fp:
         fp.write(text)
+
+
+def main():
+    if ratelib.run_parts(__file__, {"run": STEP_LIMIT_S}, sys.argv[1:]):
+        run()
 
 
 if __name__ == "__main__":

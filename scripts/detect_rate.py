@@ -10,7 +10,9 @@ takes the best of five launches per grid): the plain stream the detector is meas
 detector rate over the best read-only rate.  The stream runs in a process of its own, with its own allocation and clock
 history, and its figure is the best over three grids and three runs: the ratio compares two bests taken seconds apart on
 one card and moves with the clock state by a few per cent.  The registers of the kernels are read from the shipped code object.
-Usage: python scripts/detect_rate.py [--launch-only]   (--launch-only: the detector alone, for a trace or counters run)"""
+The measurement is one part, `run`; without it on the command line it runs as a child process under its time limit.
+Usage: python scripts/detect_rate.py [run] [--launch-only] [--to FILE]   (--launch-only: the detector alone; a trace or
+counters run names the part, `run --launch-only`, so that the profiler's child is the process that measures)"""
 import os
 import re
 import subprocess
@@ -21,28 +23,15 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea  # noqa: E402
+import ratelib  # noqa: E402
 
 WARMUP, REPS, ROUNDS = 20, 3, 5   # 20 launches of 1 GiB settle the clocks before the first timed round
+# the part's time limit: three times its wall time on an MI355X (3.3 s), rounded up to 30 s, and at least 120 s -- a first
+# import of torch on a fresh machine alone can take over a minute
+STEP_LIMIT_S = 120
 SHAPES = [(4096, 262144), (262144, 4096)]
 STREAM_SRC = os.path.join(ROOT, "scripts", "ubench", "stream_rw.hip")
 STREAM = os.path.join(ROOT, "scripts", "ubench", "bin", "stream_rw")
-
-
-def rounds(fn):
-    import torch
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(ROUNDS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(REPS):
-            fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) / 1e3 / REPS)
-    return out
 
 
 def read_only_stream():
@@ -55,7 +44,7 @@ def read_only_stream():
     return [float(m) for m in re.findall(r"read only\s+[\d.]+ ms\s+(\d+) GB/s", text)]
 
 
-def main():
+def run():
     import torch
     from tests.test_shipped_artifacts import _kernels
     if fsea.device_count() < 1:
@@ -76,7 +65,7 @@ def main():
     for _ in range(2):
         for n_blocks, block_bytes in SHAPES:
             assert n_blocks * block_bytes == nbytes
-            ts = rounds(lambda: det.sums_device(data.data_ptr(), block_bytes, n_blocks, sums.data_ptr()))
+            ts = ratelib.per_round(lambda: det.sums_device(data.data_ptr(), block_bytes, n_blocks, sums.data_ptr()), WARMUP, REPS, ROUNDS)
             print("%d blocks x %d bytes, ms: %s" % (n_blocks, block_bytes, " ".join("%.3f" % (t * 1e3) for t in ts)))
             best[(n_blocks, block_bytes)] = min(ts + [best.get((n_blocks, block_bytes), 1e9)])
         if not launch_only:
@@ -90,6 +79,11 @@ def main():
     if plain:
         print("read-only stream (scripts/ubench/stream_rw.hip, 1 GiB, best of 5 per grid), GB/s: %s; best %.0f" %
               (" ".join("%.0f" % p for p in plain), max(plain)))
+
+
+def main():
+    if ratelib.run_parts(__file__, {"run": STEP_LIMIT_S}, sys.argv[1:]):
+        run()
 
 
 if __name__ == "__main__":

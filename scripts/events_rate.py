@@ -13,11 +13,10 @@ In one process, with HIP events, the median of REPS calls after WARMUP:
 that hold a hit, the records written (the row counts, 4 bytes per row three times over, are left out).  The same for an
 all-ones mask, the worst case for the level loads: every group is loaded, and a row is one run.
 
-One process; every GPU step runs under an alarm of its own, which ends the process where a step hangs.  What it prints also
-goes to profiles/events_rate.txt (--to FILE: there instead).
-Usage: python scripts/events_rate.py [--to FILE]"""
+The measurement is one part, `run`; without an argument it runs as a child process under its time limit, and what it prints
+also goes to profiles/events_rate.txt (--to FILE: there instead).
+Usage: python scripts/events_rate.py [run] [--to FILE]"""
 import os
-import signal
 import sys
 
 import numpy as np
@@ -25,41 +24,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea  # noqa: E402
+import ratelib  # noqa: E402
 
 N, FRAMES = 8192, 4096
 WARMUP, REPS = 5, 20
 HBM_BPS = 8e12
-STEP_LIMIT_S = 120
+STEP_LIMIT_S = 120      # the whole part took 6.6 s of wall time on an MI355X
 RUN_BYTES = fsea.EVENTS_RUN.itemsize
-
-
-class step:
-    """A GPU step under its own time limit: SIGALRM's default action ends the process, also inside a library call."""
-
-    def __init__(self, what):
-        self.what = what
-
-    def __enter__(self):
-        signal.signal(signal.SIGALRM, signal.SIG_DFL)
-        signal.alarm(STEP_LIMIT_S)
-
-    def __exit__(self, *exc):
-        signal.alarm(0)
-        return False
-
-
-def event_times(call):
-    import torch
-    times = []
-    for k in range(WARMUP + REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        if k >= WARMUP:
-            times.append(e0.elapsed_time(e1) / 1e3)
-    return float(np.median(times)), min(times)
 
 
 def synth_batch(seed, n_bytes):
@@ -76,65 +47,57 @@ def synth_batch(seed, n_bytes):
     return out.view(np.uint8)
 
 
-def main():
-    args = sys.argv[1:]
-    to = os.path.join(ROOT, "profiles", "events_rate.txt")
-    if "--to" in args:
-        to = args[args.index("--to") + 1]
+def run():
     if fsea.device_count() < 1:
         raise SystemExit("events_rate.py needs a GPU")
     import torch
-    lines = []
 
     def say(text):
         print(text, flush=True)
-        lines.append(text)
 
-    with step("set-up"):
-        torch.cuda.init()
-        raw = synth_batch(3, 2 * N * FRAMES)
-        d_in = fsea.DeviceBuffer(raw.nbytes).upload(raw)
-        d_rows = fsea.DeviceBuffer(FRAMES * N)
-        d_mask = fsea.DeviceBuffer(FRAMES * N)
-        d_image = fsea.DeviceBuffer(FRAMES * N)
-        plan = fsea.Plan(N, N, fsea.MODE_DB5_U8_DCFIX)
-        plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True)
-        plan.synchronize()
-        cfar = fsea.Cfar(N)
-        cfar.set(2, 16, 60, fsea.CFAR_CA)
+    def med_min(call):
+        return ratelib.median_min(ratelib.per_call(call, WARMUP, REPS))
+
+    torch.cuda.init()
+    raw = synth_batch(3, 2 * N * FRAMES)
+    d_in = fsea.DeviceBuffer(raw.nbytes).upload(raw)
+    d_rows = fsea.DeviceBuffer(FRAMES * N)
+    d_mask = fsea.DeviceBuffer(FRAMES * N)
+    d_image = fsea.DeviceBuffer(FRAMES * N)
+    plan = fsea.Plan(N, N, fsea.MODE_DB5_U8_DCFIX)
+    plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True)
+    plan.synchronize()
+    cfar = fsea.Cfar(N)
+    cfar.set(2, 16, 60, fsea.CFAR_CA)
     say("%d rows x %d columns of DB5 rows resident (the bench's synthetic input); median of %d calls after %d, HIP events"
         % (FRAMES, N, REPS, WARMUP))
-    with step("plan"):
-        pt, pmin = event_times(lambda: plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True))
+    pt, pmin = med_min(lambda: plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True))
     say("(a) the plan's launch that produces the rows:           %8.1f us (min %8.1f)" % (pt * 1e6, pmin * 1e6))
-    with step("add"):
-        ct, cmin = event_times(lambda: cfar.add_device(d_rows.ptr.value, fsea.CFAR_U8, FRAMES, N, d_mask.ptr.value))
+    ct, cmin = med_min(lambda: cfar.add_device(d_rows.ptr.value, fsea.CFAR_U8, FRAMES, N, d_mask.ptr.value))
     say("(b) fsea_cfar_add_device at (2, 16) with a mask:        %8.1f us (min %8.1f)" % (ct * 1e6, cmin * 1e6))
 
     ev = fsea.Events(N)
 
     def measure(label, gap):
-        with step("runs"):
-            mask = d_mask.download(np.uint8, (FRAMES, N))
-            groups = int((mask.reshape(FRAMES, N // 16, 16) != 0).any(axis=2).sum())
-            chunks = int((mask.reshape(FRAMES, N // 1024, 1024) != 0).any(axis=2).sum())
-            ev.set_gap(gap)
-            found = ev.runs_device(d_mask.ptr.value, FRAMES, None, 0)
-            d_runs = fsea.DeviceBuffer(max(found, 1) * RUN_BYTES)
-            d_values = fsea.DeviceBuffer(max(found, 1)).upload(np.full(max(found, 1), 255, np.uint8))
+        mask = d_mask.download(np.uint8, (FRAMES, N))
+        groups = int((mask.reshape(FRAMES, N // 16, 16) != 0).any(axis=2).sum())
+        chunks = int((mask.reshape(FRAMES, N // 1024, 1024) != 0).any(axis=2).sum())
+        ev.set_gap(gap)
+        found = ev.runs_device(d_mask.ptr.value, FRAMES, None, 0)
+        d_runs = fsea.DeviceBuffer(max(found, 1) * RUN_BYTES)
+        d_values = fsea.DeviceBuffer(max(found, 1)).upload(np.full(max(found, 1), 255, np.uint8))
 
-            def call():
-                ev.reset()
-                ev.runs_device(d_mask.ptr.value, FRAMES, d_runs.ptr.value, found, d_levels_ptr=d_rows.ptr.value, type=fsea.CFAR_U8)
+        def call():
+            ev.reset()
+            ev.runs_device(d_mask.ptr.value, FRAMES, d_runs.ptr.value, found, d_levels_ptr=d_rows.ptr.value, type=fsea.CFAR_U8)
 
-            def count():
-                ev.reset()
-                ev.runs_device(d_mask.ptr.value, FRAMES, None, 0)
+        def count():
+            ev.reset()
+            ev.runs_device(d_mask.ptr.value, FRAMES, None, 0)
 
-            t, tmin = event_times(call)
-            t1, t1min = event_times(count)
-        with step("paint"):
-            p, p_min = event_times(lambda: ev.paint_device(d_runs.ptr.value, d_values.ptr.value, found, FRAMES, d_image.ptr.value))
+        t, tmin = med_min(call)
+        t1, t1min = med_min(count)
+        p, p_min = med_min(lambda: ev.paint_device(d_runs.ptr.value, d_values.ptr.value, found, FRAMES, d_image.ptr.value))
         read, written = 2 * FRAMES * N + 16 * groups, found * RUN_BYTES
         bound = (read + written) / HBM_BPS
         say("%s, column gap %d: %d hits in %d level groups of 16 and %d of the %d chunks of 1024, %d runs"
@@ -150,15 +113,17 @@ def main():
 
     measure("the detector's mask", 0)
     measure("the detector's mask", 3)
-    with step("dense"):
-        d_mask.upload(np.full(FRAMES * N, 255, np.uint8))
+    d_mask.upload(np.full(FRAMES * N, 255, np.uint8))
     measure("an all-ones mask", 0)
     for o in (ev, cfar, plan):
         o.close()
     for b in (d_in, d_rows, d_mask, d_image):
         b.free()
-    with open(to, "w") as f:
-        f.write("\n".join(lines) + "\n")
+
+
+def main():
+    if ratelib.run_parts(__file__, {"run": STEP_LIMIT_S}, sys.argv[1:], to=os.path.join(ROOT, "profiles", "events_rate.txt")):
+        run()
 
 
 if __name__ == "__main__":

@@ -14,10 +14,9 @@ REPS calls after WARMUP:
 one launch buys.  The traffic bound is 2 + 8 / D bytes per input sample at 8 TB/s, as in profiles/zoom_rate.txt.
 
 Without an argument every D runs as a child process under its own time limit and the lines go to profiles/extract_rate.txt
-(or the file named after --out); a part that fails ends the run.
-Usage: python scripts/extract_rate.py [--out FILE] | python scripts/extract_rate.py measure D"""
+(or the file named after --to); a part that fails ends the run.
+Usage: python scripts/extract_rate.py [--to FILE] | python scripts/extract_rate.py measure D      (D = 4, 16 or 64)"""
 import os
-import subprocess
 import sys
 import time
 
@@ -26,6 +25,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea  # noqa: E402
+import ratelib  # noqa: E402
 
 N_SAMPLES = 1 << 25
 TAPS = 97
@@ -42,20 +42,6 @@ HEADER = """# scripts/extract_rate.py on one MI355X: HIP-event times in one proc
 # (c) %d fsea_zoom_run_device calls of one job's length each, no resets
 # traffic bound = (2 + 8 / D) bytes per input sample at 8 TB/s; host time: wall time of the call (a) itself, until it returns
 """ % (REPS, WARMUP, TAPS, TAPS, N_JOBS, N_JOBS)
-
-
-def timed(fn):
-    import torch
-    times = []
-    for k in range(WARMUP + REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        if k >= WARMUP:
-            times.append(e0.elapsed_time(e1) / 1e3)
-    return float(np.median(times)), min(times)
 
 
 def measure(D):
@@ -85,9 +71,10 @@ def measure(D):
             zoom.run_device(d_in.ptr.value + 2 * (j.first & ~7), n_job, d_row.ptr.value, j.cycles_per_sample,
                             sample_offset=j.sample_offset, flip=True)
 
-    (ta, ta_min), (tb, tb_min), (tc, tc_min) = timed(a), timed(b), timed(c_route)
+    (ta, ta_min), (tb, tb_min), (tc, tc_min) = (ratelib.median_min(ratelib.per_call(fn, WARMUP, REPS)) for fn in (a, b, c_route))
     # what the host spends inside the call before it returns (checks, 256 records with eight phasors each, two launches): a
-    # HIP-event interval on an idle stream holds it too
+    # HIP-event interval on an idle stream holds it too.  Not ratelib.wall: the clock stops at the return of a call that
+    # does not wait, on a stream made idle outside the clock
     sync = fsea.Plan(128)
     host = []
     for _ in range(REPS):
@@ -109,21 +96,10 @@ def measure(D):
 
 
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "measure":
-        measure(int(sys.argv[2]))
-        return
-    out = sys.argv[2] if len(sys.argv) > 2 and sys.argv[1] == "--out" else os.path.join(ROOT, "profiles", "extract_rate.txt")
-    text = HEADER + "\n"
-    for D in DECIMATIONS:
-        r = subprocess.run(["timeout", "-k", "10", str(STEP_LIMIT_S), sys.executable, os.path.abspath(__file__), "measure", str(D)],
-                           capture_output=True, text=True)
-        sys.stdout.write(r.stdout)
-        sys.stderr.write(r.stderr)
-        if r.returncode != 0:
-            raise SystemExit("D = %d failed (exit status %d): stopping" % (D, r.returncode))
-        text += r.stdout
-    with open(out, "w") as f:
-        f.write(text)
+    part = ratelib.run_parts(__file__, {"measure %d" % D: STEP_LIMIT_S for D in DECIMATIONS}, sys.argv[1:],
+                             to=os.path.join(ROOT, "profiles", "extract_rate.txt"), header=HEADER + "\n")
+    if part:
+        measure(int(part.split()[1]))
 
 
 if __name__ == "__main__":

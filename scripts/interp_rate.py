@@ -11,7 +11,9 @@
    one-frame launch (events) and the download of the frame (wall) -- beside the reference's host loop as restated in
    tests/interp_ref.py (numpy, one CPU).
 The registers and LDS of the kernels are read from the shipped code object.
-Usage: python scripts/interp_rate.py [--image-only]   (--image-only: part 1 alone, for a counters run)"""
+The measurement is one part, `run`; without it on the command line it runs as a child process under its time limit.
+Usage: python scripts/interp_rate.py [run] [--image-only] [--to FILE]   (--image-only: 1. alone; a counters run names the
+part, `run --image-only`, so that the profiler's child is the process that measures)"""
 import ctypes
 import os
 import statistics
@@ -23,32 +25,19 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea, nrf  # noqa: E402
+import ratelib  # noqa: E402
 
 WARMUP, REPS, ROUNDS = 2, 3, 5
-
-
-def rounds(fn):
-    import torch
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(ROUNDS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(REPS):
-            fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) / 1e3 / REPS)
-    return out
+# the part's time limit: three times its wall time on an MI355X (2.2 s), rounded up to 30 s, and at least 120 s -- a first
+# import of torch on a fresh machine alone can take over a minute
+STEP_LIMIT_S = 120
 
 
 def beside(name, nbytes, kernel, plain):
     k, p = [], []
     for _ in range(2):                       # alternately
-        k += rounds(kernel)
-        p += rounds(plain)
+        k += ratelib.per_round(kernel, WARMUP, REPS, ROUNDS)
+        p += ratelib.per_round(plain, WARMUP, REPS, ROUNDS)
     fmt = lambda ts: " ".join("%.3f" % (t * 1e3) for t in ts)
     print("%s: %.1f MB written per launch" % (name, nbytes / 1e6))
     print("  kernel       ms: %s   best %.3f ms = %.0f GB/s" % (fmt(k), min(k) * 1e3, nbytes / min(k) / 1e9))
@@ -57,7 +46,7 @@ def beside(name, nbytes, kernel, plain):
           (min(k) / min(p), 100 * (max(p) - min(p)) / min(p)))
 
 
-def main():
+def run():
     import torch
     from tests.test_shipped_artifacts import _kernels
     from tests import interp_ref as R
@@ -99,13 +88,9 @@ def main():
         beside("sample form, 128 frames of %d %s" % (n, np.dtype(dtype).name), out.numel(),
                lambda: ip.frames_device(d_w.data_ptr(), 128, out.data_ptr()), plain(out))
         if dtype == np.uint8:
-            one = rounds(lambda: ip.frames_device(d_w.data_ptr(), 1, out.data_ptr()))
+            one = ratelib.per_round(lambda: ip.frames_device(d_w.data_ptr(), 1, out.data_ptr()), WARMUP, REPS, ROUNDS)
             host = np.empty(n, dtype=np.uint8)
-            dl = []
-            for _ in range(20):
-                t0 = time.perf_counter()
-                fsea._check(ip._L.fsea_copy_to_host(0, host.ctypes.data, out.data_ptr(), n))
-                dl.append(time.perf_counter() - t0)
+            dl = ratelib.wall(lambda: fsea._check(ip._L.fsea_copy_to_host(0, host.ctypes.data, out.data_ptr(), n)), 0, 20)
         del out
         ip.close()
 
@@ -117,22 +102,23 @@ def main():
         buf = L.nut_buffer_new_u8(131072, 2, blk.ctypes.data)
         L.nrf_interpolator_process(itp, buf)
         L.nut_buffer_free(buf)
-    wall = []
+    wall = []                  # not ratelib.wall: the buffer a call returns is freed outside the clock, before the next call
     for _ in range(60):
         t0 = time.perf_counter()
         got = L.nrf_interpolator_get_buffer(itp)
         wall.append(time.perf_counter() - t0)
         L.nut_buffer_free(got)
     L.nrf_interpolator_free(itp)
-    ref = []
-    for _ in range(10):
-        t0 = time.perf_counter()
-        R.blend_frames(a, b, [0.01])
-        ref.append(time.perf_counter() - t0)
+    ref = ratelib.wall(lambda: R.blend_frames(a, b, [0.01]), 0, 10)
     print("nrf_interpolator_get_buffer, 262144 U8: median wall %.1f us (min %.1f); one-frame launch %.1f us (events, best of "
           "%d rounds of %d); download of the frame %.1f us (median wall); restated host loop (numpy, one CPU) %.1f us (median)" %
           (statistics.median(wall[10:]) * 1e6, min(wall) * 1e6, min(one) * 1e6, ROUNDS, REPS, statistics.median(dl) * 1e6,
            statistics.median(ref) * 1e6))
+
+
+def main():
+    if ratelib.run_parts(__file__, {"run": STEP_LIMIT_S}, sys.argv[1:]):
+        run()
 
 
 if __name__ == "__main__":

@@ -10,18 +10,17 @@ kernel:  the shifted FIR kernel against the unshifted one at n = 2^26, L = 21, 5
          and bound (the rotation's flops are not algorithmic work).
 
 Without an argument both parts run, each as a child process under its own time limit; a part that fails ends the run.
-Usage: python scripts/iq_chain_rate.py [percall|kernel]"""
+Usage: python scripts/iq_chain_rate.py [percall|kernel] [--to FILE]   (--to: what the parts print goes there too)"""
 import ctypes
 import os
-import subprocess
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea, nrf  # noqa: E402
+import ratelib  # noqa: E402
 
 PAIRS = 131072
 WARMUP_CALLS, CALLS = 30, 300
@@ -29,17 +28,6 @@ N = 1 << 26
 WARMUP, REPS, ROUNDS = 5, 20, 5
 HBM_BPS, VALU_FLOPS = 8e12, 157.3e12
 STEP_LIMIT_S = {"percall": 240, "kernel": 240}
-
-
-def median_us(fn):
-    for _ in range(WARMUP_CALLS):
-        fn()
-    times = []
-    for _ in range(CALLS):
-        t0 = time.perf_counter()
-        fn()
-        times.append(time.perf_counter() - t0)
-    return float(np.median(times)) * 1e6, float(np.min(times)) * 1e6
 
 
 def percall():
@@ -71,7 +59,8 @@ def percall():
             L.nrf_iq_chain_process(chain, buf)
             L.nut_buffer_free(draw_chain(chain))
 
-        b, c = median_us(blocks), median_us(chained)
+        # both end in the draw's download of its image: the wall time of a call holds all of its work
+        b, c = ([t * 1e6 for t in ratelib.median_min(ratelib.wall(fn, WARMUP_CALLS, CALLS))] for fn in (blocks, chained))
         print("%-7s block sequence %8.1f us (%8.1f)   nrf_iq_chain %7.1f us (%7.1f)   ratio %.2f"
               % (name, b[0], b[1], c[0], c[1], b[0] / c[0]))
         L.nrf_iq_chain_free(chain)
@@ -106,18 +95,7 @@ def kernel():
                                                                              flip=True)))
         bound = max(10.0 * N / HBM_BPS, 4.0 * taps * N / VALU_FLOPS)
         for name, launch in launches:      # "+3": a call that starts off the 8-sample grid (two phasor bases per group)
-            for _ in range(WARMUP):
-                launch()
-            torch.cuda.synchronize()
-            best = 1e9
-            for _ in range(ROUNDS):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(REPS):
-                    launch()
-                e1.record()
-                e1.synchronize()
-                best = min(best, e0.elapsed_time(e1) / 1e3 / REPS)
+            best = min(ratelib.per_round(launch, WARMUP, REPS, ROUNDS))
             print("L=%-3d %-21s achieved %8.1f us   bound %8.1f us   fraction %.3f" % (taps, name, best * 1e6, bound * 1e6,
                                                                                      bound / best))
         fir.close()
@@ -126,14 +104,9 @@ def kernel():
 
 
 def main():
-    parts = {"percall": percall, "kernel": kernel}
-    if len(sys.argv) > 1:
-        parts[sys.argv[1]]()
-        return
-    for name in ("percall", "kernel"):
-        r = subprocess.run(["timeout", "-k", "10", str(STEP_LIMIT_S[name]), sys.executable, os.path.abspath(__file__), name])
-        if r.returncode != 0:
-            raise SystemExit("%s failed (exit status %d): stopping" % (name, r.returncode))
+    part = ratelib.run_parts(__file__, STEP_LIMIT_S, sys.argv[1:])
+    if part:
+        {"percall": percall, "kernel": kernel}[part]()
 
 
 if __name__ == "__main__":

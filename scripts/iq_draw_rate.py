@@ -10,39 +10,31 @@
    (sum over segments of max(dx, dy) + 1, counted on the host over every 64th frame and scaled by 64).  Inputs: the
    replay block, the sixteen short captures (both recorded: tests/golden/rfdata_all_golden.npz), and uniform random bytes.
 HIP events (torch.cuda.Event on the null stream, where the launches go) around REPS launches after WARMUP, best of ROUNDS.
-Usage: python scripts/iq_draw_rate.py [--batched-only] [block|captures|random ...]   (default: both parts, every input;
-a counters run per input takes one input name)"""
+The measurement is one part, `run`; without it on the command line it runs as a child process under its time limit.
+Usage: python scripts/iq_draw_rate.py [run] [--batched-only] [block|captures|random ...] [--to FILE]   (default: 1. and 2.,
+every input; a counters run per input takes one input name and names the part, `run --batched-only random`, so that the
+profiler's child is the process that measures)"""
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea, nrf  # noqa: E402
+import ratelib  # noqa: E402
 
 FRAMES, PAIRS = 512, 131072
 WARMUP, REPS, ROUNDS = 2, 5, 3
+# the part's time limit: three times its wall time on an MI355X (7.0 s), rounded up to 30 s, and at least 120 s -- a first
+# import of torch on a fresh machine alone can take over a minute
+STEP_LIMIT_S = 120
 HBM_BPS = 8e12
 
 
-def timed(fn, reps=REPS):
-    import torch
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    best = 1e9
-    for _ in range(ROUNDS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        e1.synchronize()
-        best = min(best, e0.elapsed_time(e1) / 1e3 / reps)
-    return best
+def best(fn, reps=REPS):
+    return min(ratelib.per_round(fn, WARMUP, reps, ROUNDS))
 
 
 def increments(iq_u8, m, n_points):
@@ -67,23 +59,17 @@ def per_call(L, draw, torch):
     h_in = torch.from_numpy(f64).pin_memory()
     d_in = h_in.to("cuda")
     for name, fn in calls.items():
-        for _ in range(3):
-            fn()
-        walls = []
-        for _ in range(20):
-            t0 = time.perf_counter()
-            fn()
-            walls.append(time.perf_counter() - t0)
+        walls = ratelib.wall(fn, 3, 20)
         m = 4 if name.startswith("lines") else 1
         img_bytes = (256 * m) ** 2
         d_img = torch.empty(img_bytes, dtype=torch.uint8, device="cuda")
         h_img = torch.empty(img_bytes, dtype=torch.uint8).pin_memory()
-        up = timed(lambda: d_in.copy_(h_in, non_blocking=True))
+        up = best(lambda: d_in.copy_(h_in, non_blocking=True))
         if m == 1:
-            k = timed(lambda: draw.points_device(d_in.data_ptr(), fsea.IQ_F64, n, 1, d_img.data_ptr()))
+            k = best(lambda: draw.points_device(d_in.data_ptr(), fsea.IQ_F64, n, 1, d_img.data_ptr()))
         else:
-            k = timed(lambda: draw.lines_device(d_in.data_ptr(), fsea.IQ_F64, n_points, 1, 4, d_img.data_ptr()))
-        down = timed(lambda: h_img.copy_(d_img, non_blocking=True))
+            k = best(lambda: draw.lines_device(d_in.data_ptr(), fsea.IQ_F64, n_points, 1, 4, d_img.data_ptr()))
+        down = best(lambda: h_img.copy_(d_img, non_blocking=True))
         print("  %-14s wall median %7.1f us (min %7.1f)   upload %6.1f us (%d B)   kernels %7.1f us   download %6.1f us (%d B)"
               % (name, statistics.median(walls) * 1e6, min(walls) * 1e6, up * 1e6, f64.nbytes, k * 1e6, down * 1e6,
                  img_bytes))
@@ -104,7 +90,7 @@ def batched(draw, torch, names):
         iq = make()
         d_in = torch.from_numpy(iq).to("cuda")
         d_pts = torch.empty(FRAMES * 65536, dtype=torch.uint8, device="cuda")
-        t = timed(lambda: draw.points_device(d_in.data_ptr(), fsea.IQ_U8, PAIRS, FRAMES, d_pts.data_ptr()))
+        t = best(lambda: draw.points_device(d_in.data_ptr(), fsea.IQ_U8, PAIRS, FRAMES, d_pts.data_ptr()))
         nbytes = 2.0 * PAIRS * FRAMES + 65536.0 * FRAMES
         print("  %-15s points      %8.1f us  %7.2f Gpairs/s  %7.1f GB/s  fraction of HBM roofline %.3f"
               % (name, t * 1e6, PAIRS * FRAMES / t / 1e9, nbytes / t / 1e9, nbytes / HBM_BPS / t))
@@ -113,7 +99,7 @@ def batched(draw, torch, names):
             n_points = (int(np.float32(2 * PAIRS) * np.float32(0.3)) + 1) // 2
             inc = sum(increments(iq[f * 2 * PAIRS:(f + 1) * 2 * PAIRS], m, n_points) for f in range(0, FRAMES, 64)) * 64
             d_img = torch.empty(FRAMES * (256 * m) ** 2, dtype=torch.uint8, device="cuda")
-            t = timed(lambda: draw.lines_device(d_in.data_ptr(), fsea.IQ_U8, n_points, FRAMES, m, d_img.data_ptr()),
+            t = best(lambda: draw.lines_device(d_in.data_ptr(), fsea.IQ_U8, n_points, FRAMES, m, d_img.data_ptr()),
                       reps=2)
             print("  %-15s lines m=%d   %8.1f us  %7.2f G pixel increments/s  (%.3g increments, %d points per frame)"
                   % (name, m, t * 1e6, inc / t / 1e9, inc, n_points))
@@ -122,16 +108,21 @@ def batched(draw, torch, names):
         torch.cuda.empty_cache()
 
 
-def main():
+def run():
     import torch
     torch.cuda.init()
     L = nrf.nrf_lib()
     draw = fsea.IqDraw()
-    args = sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != "run"]
     if "--batched-only" not in args:
         per_call(L, draw, torch)
     batched(draw, torch, [a for a in args if not a.startswith("--")])
     draw.close()
+
+
+def main():
+    if ratelib.run_parts(__file__, {"run": STEP_LIMIT_S}, sys.argv[1:]):
+        run()
 
 
 if __name__ == "__main__":

@@ -7,16 +7,11 @@ sys.path.insert(0, ROOT)
 from frequensea_amd import fsea
 fsea.use_tune_library()
 
-def dev_alloc(nbytes):
-    p = ctypes.c_void_p()
-    fsea._check(fsea.hip_lib().fsea_device_alloc(0, nbytes, ctypes.byref(p)))
-    return p
-
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
 TOTAL = 1 << 28     # samples: 512 MiB in, 1 GiB out
 host = np.random.default_rng(1).integers(-70, 70, 2 * (1 << 24), dtype=np.int8).view(np.uint8)
-d_in = dev_alloc(2 * TOTAL)
-d_out = dev_alloc(4 * TOTAL)
+d_in = fsea.DeviceBuffer(2 * TOTAL).ptr
+d_out = fsea.DeviceBuffer(4 * TOTAL).ptr
 L = fsea.hip_lib()
 for off in range(0, 2 * TOTAL, host.nbytes):
     fsea._check(L.fsea_copy_to_device(0, ctypes.c_void_p(d_in.value + off), host.ctypes.data, host.nbytes))

@@ -15,18 +15,13 @@ kernels: the add kernel alone, from the dispatch timestamps of a kernel trace: t
 Without an argument run and kernels run, each as a child process under its own time limit; a part that fails ends the run,
 and what they print also goes to profiles/persist_rate.txt (--to FILE: there instead).
 Usage: python scripts/persist_rate.py [run|kernels|launches] [--out DIR] [--to FILE]   (--out: keep the trace there)"""
-import csv
-import glob
 import os
-import subprocess
 import sys
-import tempfile
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea  # noqa: E402
+import ratelib  # noqa: E402
 
 N_SAMPLES = 1 << 25
 SIZES = (128, 1024, 16384)
@@ -34,24 +29,6 @@ WARMUP, REPS = 5, 20
 HBM_BPS = 8e12
 STEP_LIMIT_S = {"run": 240, "kernels": 300}
 KERNEL = "fsea_persist_u8"
-
-
-def recording():
-    return np.random.default_rng(1).integers(0, 256, 2 * N_SAMPLES, dtype=np.uint8)
-
-
-def event_times(call):
-    import torch
-    times = []
-    for k in range(WARMUP + REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        if k >= WARMUP:
-            times.append(e0.elapsed_time(e1) / 1e3)
-    return float(np.median(times)), min(times)
 
 
 def resident_rows(d_in, n):
@@ -66,15 +43,16 @@ def resident_rows(d_in, n):
 
 def run():
     import torch
-    d_in = fsea.DeviceBuffer(2 * N_SAMPLES).upload(recording())
+    d_in = fsea.DeviceBuffer(2 * N_SAMPLES).upload(ratelib.recording(N_SAMPLES))
     torch.cuda.init()
     print("n = %d samples resident; fsea_persist_add_device on the DB5 rows (hop N), median of %d calls after %d"
           % (N_SAMPLES, REPS, WARMUP))
     for n in SIZES:
         plan, d_rows, frames = resident_rows(d_in, n)
-        pt, pmin = event_times(lambda: plan.exec_device(d_in.ptr.value, frames, d_rows.ptr.value, flip=True))
+        pt, pmin = ratelib.median_min(ratelib.per_call(lambda: plan.exec_device(d_in.ptr.value, frames, d_rows.ptr.value, flip=True),
+                                                       WARMUP, REPS))
         p = fsea.Persist(n)
-        t, tmin = event_times(lambda: p.add_device(d_rows.ptr.value, fsea.PERSIST_U8, frames, n))
+        t, tmin = ratelib.median_min(ratelib.per_call(lambda: p.add_device(d_rows.ptr.value, fsea.PERSIST_U8, frames, n), WARMUP, REPS))
         levels = int((p.counts().sum(axis=1) > 0).sum())
         print("N=%-5d rows %-6d  add %8.1f us (min %8.1f) %7.1f GB/s of rows   the plan's launch %8.1f us (min %8.1f)   add / plan %.2f   levels occupied %d"
               % (n, frames, t * 1e6, tmin * 1e6, frames * n / t / 1e9, pt * 1e6, pmin * 1e6, t / pt, levels))
@@ -85,7 +63,7 @@ def run():
 
 
 def launches():
-    d_in = fsea.DeviceBuffer(2 * N_SAMPLES).upload(recording())
+    d_in = fsea.DeviceBuffer(2 * N_SAMPLES).upload(ratelib.recording(N_SAMPLES))
     for n in SIZES:
         plan, d_rows, frames = resident_rows(d_in, n)
         p = fsea.Persist(n)
@@ -98,63 +76,31 @@ def launches():
     d_in.free()
 
 
-def kernels(out_dir):
-    cmd = ["rocprofv3", "--kernel-trace", "-d", out_dir, "-o", "persist", "--output-format", "csv", "--", sys.executable,
-           os.path.abspath(__file__), "launches"]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
-    traces = glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if len(traces) != 1:
-        raise SystemExit("expected one kernel trace under %s, found %d" % (out_dir, len(traces)))
-    with open(traces[0], newline="") as f:
-        rows = [r for r in csv.DictReader(f) if r["Kernel_Name"].startswith(KERNEL)]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    per_case = WARMUP + REPS
-    if len(rows) != per_case * len(SIZES):
-        raise SystemExit("expected %d dispatches of %s, found %d" % (per_case * len(SIZES), KERNEL, len(rows)))
+def kernel_times(out_dir):
+    cases = ratelib.kernel_trace([sys.executable, os.path.abspath(__file__), "launches"], KERNEL, WARMUP + REPS, len(SIZES), out_dir)
     print("n = %d samples resident; %s alone (dispatch timestamps of a kernel trace), median of %d launches after %d"
           % (N_SAMPLES, KERNEL, REPS, WARMUP))
-    for i, n in enumerate(SIZES):
-        mine = rows[i * per_case + WARMUP:(i + 1) * per_case]
-        times = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e9 for r in mine]
-        t = float(np.median(times))
+    for n, (name, times) in zip(SIZES, cases):
+        t, tmin = ratelib.median_min(times[WARMUP:])
         frames = N_SAMPLES // n
         groups = -(-n // 64) * -(-frames // fsea.PERSIST_RUN_ROWS)
         read = frames * n / HBM_BPS
         flush_max = groups * 256 * 64 * 4 / HBM_BPS
         print("N=%-5d %s median %8.1f us (min %8.1f)   %d workgroups   bound: rows %5.1f us, rows + every counter flushed %5.1f us   fraction %.3f .. %.3f   %.1f GB/s of rows"
-              % (n, mine[0]["Kernel_Name"], t * 1e6, min(times) * 1e6, groups, read * 1e6, (read + flush_max) * 1e6, read / t,
+              % (n, name, t * 1e6, tmin * 1e6, groups, read * 1e6, (read + flush_max) * 1e6, read / t,
                  (read + flush_max) / t, frames * n / t / 1e9))
 
 
 def main():
     args = sys.argv[1:]
-    out_dir, to = None, os.path.join(ROOT, "profiles", "persist_rate.txt")
-    if "--out" in args:
-        out_dir = args[args.index("--out") + 1]
-        args = [a for a in args if a not in ("--out", out_dir)]
-    if "--to" in args:
-        to = args[args.index("--to") + 1]
-        args = [a for a in args if a not in ("--to", to)]
-    if args:
-        if args[0] == "kernels":
-            if out_dir:
-                kernels(out_dir)
-            else:
-                with tempfile.TemporaryDirectory() as tmp:
-                    kernels(tmp)
-        else:
-            {"run": run, "launches": launches}[args[0]]()
+    if "launches" in args:
+        launches()
         return
-    text = []
-    for name in ("run", "kernels"):
-        cmd = ["timeout", "-k", "10", str(STEP_LIMIT_S[name]), sys.executable, os.path.abspath(__file__), name]
-        r = subprocess.run(cmd + (["--out", out_dir] if out_dir and name == "kernels" else []), stdout=subprocess.PIPE, text=True)
-        sys.stdout.write(r.stdout)
-        if r.returncode != 0:
-            raise SystemExit("%s failed (exit status %d): stopping" % (name, r.returncode))
-        text.append(r.stdout)
-    with open(to, "w") as f:
-        f.write("\n".join(text))
+    part = ratelib.run_parts(__file__, STEP_LIMIT_S, args, to=os.path.join(ROOT, "profiles", "persist_rate.txt"))
+    if part == "run":
+        run()
+    elif part == "kernels":
+        kernel_times(args[args.index("--out") + 1] if "--out" in args else None)
 
 
 if __name__ == "__main__":

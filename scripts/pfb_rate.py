@@ -12,20 +12,15 @@ kernels: the frames kernel alone.  A call always runs the plan behind it, so its
          M / q samples).  The fraction says how far the kernel is from the memory bound, not what bounds it.
 
 Without an argument run and kernels run, each as a child process under its own time limit; a part that fails ends the run.
-Usage: python scripts/pfb_rate.py [run|kernels|launches] [--out DIR]   (--out: keep the trace there; the output of a run
-without a part is profiles/pfb_rate.txt)"""
-import csv
-import glob
+Usage: python scripts/pfb_rate.py [run|kernels|launches] [--out DIR] [--to FILE]   (--out: keep the trace there; --to: what
+the parts print goes there too -- profiles/pfb_rate.txt is the output of a run without a part)"""
 import os
-import subprocess
 import sys
-import tempfile
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea  # noqa: E402
+import ratelib  # noqa: E402
 
 N_SAMPLES = 1 << 25
 CASES = ((128, 8, 1), (1024, 8, 1), (1024, 8, 2), (16384, 4, 1))
@@ -35,27 +30,9 @@ STEP_LIMIT_S = {"run": 240, "kernels": 300}
 KERNEL = "fsea_pfb_frames_u8"
 
 
-def recording():
-    return np.random.default_rng(1).integers(0, 256, 2 * N_SAMPLES, dtype=np.uint8)
-
-
-def event_times(call):
-    import torch
-    times = []
-    for k in range(WARMUP + REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        if k >= WARMUP:
-            times.append(e0.elapsed_time(e1) / 1e3)
-    return float(np.median(times)), min(times)
-
-
 def run():
     import torch
-    d_in = fsea.DeviceBuffer(2 * N_SAMPLES).upload(recording())
+    d_in = fsea.DeviceBuffer(2 * N_SAMPLES).upload(ratelib.recording(N_SAMPLES))
     torch.cuda.init()
     print("n = %d samples resident; a whole call (frames kernel + plan), median of %d calls after %d, MAG rows"
           % (N_SAMPLES, REPS, WARMUP))
@@ -64,13 +41,15 @@ def run():
         pfb = fsea.Pfb(fsea.pfb_prototype(M, P), M, q, fsea.MODE_MAG_F32)
         F = pfb.out_frames(N_SAMPLES)
         d_rows = fsea.DeviceBuffer(F * M * 4)
-        t, tmin = event_times(lambda: pfb.run_device(d_in.ptr.value, N_SAMPLES, d_rows.ptr.value, flip=True))
+        t, tmin = ratelib.median_min(ratelib.per_call(lambda: pfb.run_device(d_in.ptr.value, N_SAMPLES, d_rows.ptr.value, flip=True),
+                                                     WARMUP, REPS))
         pfb.close()
         plan = fsea.Plan(M, D, fsea.MODE_MAG_F32)
         plan.set_window("hann")
         nf = (N_SAMPLES - M) // D + 1
         d_plain = fsea.DeviceBuffer(nf * M * 4)
-        pt, pmin = event_times(lambda: plan.exec_device(d_in.ptr.value, nf, d_plain.ptr.value, flip=True))
+        pt, pmin = ratelib.median_min(ratelib.per_call(lambda: plan.exec_device(d_in.ptr.value, nf, d_plain.ptr.value, flip=True),
+                                                       WARMUP, REPS))
         plan.close()
         print("M=%-5d P=%-2d q=%d  bank %9.1f us (min %9.1f) %6.2f Gsamples/s   Hann-windowed plan %9.1f us (min %9.1f) %6.2f Gsamples/s   ratio %.2f"
               % (M, P, q, t * 1e6, tmin * 1e6, N_SAMPLES / t / 1e9, pt * 1e6, pmin * 1e6, N_SAMPLES / pt / 1e9, t / pt))
@@ -80,7 +59,7 @@ def run():
 
 
 def launches():
-    d_in = fsea.DeviceBuffer(2 * N_SAMPLES).upload(recording())
+    d_in = fsea.DeviceBuffer(2 * N_SAMPLES).upload(ratelib.recording(N_SAMPLES))
     sync = fsea.Plan(128)
     for M, P, q in CASES:
         pfb = fsea.Pfb(fsea.pfb_prototype(M, P), M, q, fsea.MODE_MAG_F32)
@@ -94,51 +73,27 @@ def launches():
     d_in.free()
 
 
-def kernels(out_dir):
-    cmd = ["rocprofv3", "--kernel-trace", "-d", out_dir, "-o", "pfb", "--output-format", "csv", "--", sys.executable,
-           os.path.abspath(__file__), "launches"]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
-    traces = glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if len(traces) != 1:
-        raise SystemExit("expected one kernel trace under %s, found %d" % (out_dir, len(traces)))
-    with open(traces[0], newline="") as f:
-        rows = [r for r in csv.DictReader(f) if r["Kernel_Name"].startswith(KERNEL)]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    per_case = WARMUP + REPS
-    if len(rows) != per_case * len(CASES):
-        raise SystemExit("expected %d dispatches of %s, found %d" % (per_case * len(CASES), KERNEL, len(rows)))
+def kernel_times(out_dir):
+    cases = ratelib.kernel_trace([sys.executable, os.path.abspath(__file__), "launches"], KERNEL, WARMUP + REPS, len(CASES), out_dir)
     print("n = %d samples resident; %s alone (dispatch timestamps of a kernel trace), median of %d launches after %d"
           % (N_SAMPLES, KERNEL, REPS, WARMUP))
-    for i, (M, P, q) in enumerate(CASES):
-        mine = rows[i * per_case + WARMUP:(i + 1) * per_case]
-        times = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e9 for r in mine]
-        t = float(np.median(times))
+    for (M, P, q), (name, times) in zip(CASES, cases):
+        t, tmin = ratelib.median_min(times[WARMUP:])
         bound = (2.0 + 8.0 * q) * N_SAMPLES / HBM_BPS
         print("M=%-5d P=%-2d q=%d  %s median %8.1f us (min %8.1f)   traffic bound %6.1f us   fraction %.3f   %.2f Gsamples/s"
-              % (M, P, q, mine[0]["Kernel_Name"], t * 1e6, min(times) * 1e6, bound * 1e6, bound / t, N_SAMPLES / t / 1e9))
+              % (M, P, q, name, t * 1e6, tmin * 1e6, bound * 1e6, bound / t, N_SAMPLES / t / 1e9))
 
 
 def main():
     args = sys.argv[1:]
-    out_dir = None
-    if "--out" in args:
-        out_dir = args[args.index("--out") + 1]
-        args = [a for a in args if a not in ("--out", out_dir)]
-    if args:
-        if args[0] == "kernels":
-            if out_dir:
-                kernels(out_dir)
-            else:
-                with tempfile.TemporaryDirectory() as tmp:
-                    kernels(tmp)
-        else:
-            {"run": run, "launches": launches}[args[0]]()
+    if "launches" in args:
+        launches()
         return
-    for name in ("run", "kernels"):
-        cmd = ["timeout", "-k", "10", str(STEP_LIMIT_S[name]), sys.executable, os.path.abspath(__file__), name]
-        r = subprocess.run(cmd + (["--out", out_dir] if out_dir and name == "kernels" else []))
-        if r.returncode != 0:
-            raise SystemExit("%s failed (exit status %d): stopping" % (name, r.returncode))
+    part = ratelib.run_parts(__file__, STEP_LIMIT_S, args)
+    if part == "run":
+        run()
+    elif part == "kernels":
+        kernel_times(args[args.index("--out") + 1] if "--out" in args else None)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,140 @@
+"""What the scripts/*_rate.py share: three ways to time a call, the kernel-trace reader, the part runner and the seeded
+recording.  A script keeps its constants, its set-up, the bound it computes and its print lines; how a number is taken is
+here, once.
+
+Timing, all in seconds, each returning the list of its samples (the caller reduces: np.median, min, best of):
+  per_call   HIP events round every single call;
+  per_round  HIP events round `reps` back-to-back calls, `rounds` times, each divided by `reps`;
+  wall       the host clock round every single call, for calls that end in a device wait.
+
+torch is imported inside the functions: a script decides when torch's HIP runtime loads relative to libfsea_hip.so
+(tests/test_gpu_object_lifetime.py says why the order matters), and importing this module must not decide it for them."""
+import csv
+import glob
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+
+def per_call(call, warmup, reps):
+    """`reps` times of one call each: fresh events on the null stream round every call, the first `warmup` results dropped."""
+    import torch
+    times = []
+    for k in range(warmup + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        e1.synchronize()
+        if k >= warmup:
+            times.append(e0.elapsed_time(e1) / 1e3)
+    return times
+
+
+def per_round(call, warmup, reps, rounds):
+    """`rounds` per-call times: `warmup` calls and a device wait, then events round `reps` back-to-back calls per round."""
+    import torch
+    for _ in range(warmup):
+        call()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            call()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) / 1e3 / reps)
+    return out
+
+
+def wall(call, warmup, calls):
+    """`calls` host-clock times of one call each, after `warmup` untimed ones.  The call must end in a device wait (a
+    blocking copy, a synchronize, a host form that downloads its result): the clock stops when the call returns, and
+    whatever the device still has to do by then is not in the figure."""
+    for _ in range(warmup):
+        call()
+    times = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        call()
+        times.append(time.perf_counter() - t0)
+    return times
+
+
+def median_min(times):
+    return float(np.median(times)), min(times)
+
+
+def kernel_trace(argv, prefix, per_case, n_cases, out_dir=None):
+    """Run `argv` in a fresh child under `rocprofv3 --kernel-trace` (nothing else traced, no counters) and read the
+    dispatches of the kernels whose name starts with `prefix`, in start order: `per_case` of them for each of `n_cases`
+    cases.  Returns per case (kernel name, [durations in seconds]).  out_dir: keep the trace there, not in a temporary
+    directory."""
+    if out_dir is None:
+        with tempfile.TemporaryDirectory() as tmp:
+            return kernel_trace(argv, prefix, per_case, n_cases, tmp)
+    cmd = ["rocprofv3", "--kernel-trace", "-d", out_dir, "-o", prefix, "--output-format", "csv", "--"] + list(argv)
+    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
+    traces = glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True)
+    if len(traces) != 1:
+        raise SystemExit("expected one kernel trace under %s, found %d" % (out_dir, len(traces)))
+    with open(traces[0], newline="") as f:
+        rows = [r for r in csv.DictReader(f) if r["Kernel_Name"].startswith(prefix)]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    if len(rows) != per_case * n_cases:
+        raise SystemExit("expected %d dispatches of %s, found %d" % (per_case * n_cases, prefix, len(rows)))
+    cases = []
+    for i in range(n_cases):
+        mine = rows[i * per_case:(i + 1) * per_case]
+        cases.append((mine[0]["Kernel_Name"], [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e9 for r in mine]))
+    return cases
+
+
+def _option(argv, flag):
+    """(the value after `flag` or None, argv without the two)."""
+    if flag not in argv:
+        return None, argv
+    i = argv.index(flag)
+    return argv[i + 1], argv[:i] + argv[i + 2:]
+
+
+def run_parts(script, parts, argv, to=None, header=""):
+    """The GPU work of a script in parts, each a child process under a time limit of its own.
+
+    parts: {part name: limit in seconds}, in the order they run; a name may be several words ("measure 16").
+    argv:  the script's arguments.  `--to FILE` says where the text goes (instead of `to`); everything else, `--out DIR`
+           (where a part keeps its trace) included, is the parts' own and is passed on to them.
+
+    With a part name in argv: returns that name, and the script runs the part itself, in this process.  Without one: runs
+    every part as `timeout -k 10 LIMIT python script part argv...`, echoes what each prints, and stops at the first that
+    fails, starting nothing after it; after the last, writes `header` and what the parts printed to `to` (if there is
+    one) and returns None."""
+    file, argv = _option(list(argv), "--to")
+    for name in parts:
+        words = name.split()
+        if any(argv[i:i + len(words)] == words for i in range(len(argv))):
+            return name
+    text = header
+    for name, limit in parts.items():
+        r = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(script)] + name.split() + argv,
+                           stdout=subprocess.PIPE, text=True)
+        sys.stdout.write(r.stdout)
+        sys.stdout.flush()
+        if r.returncode != 0:
+            raise SystemExit("%s failed (exit status %d): stopping" % (name, r.returncode))
+        text += r.stdout
+    if file or to:
+        with open(file or to, "w") as f:
+            f.write(text)
+    return None
+
+
+def recording(n_samples, seed=1):
+    """n_samples of 8-bit IQ, two bytes each, uniform random from a seeded generator."""
+    return np.random.default_rng(seed).integers(0, 256, 2 * n_samples, dtype=np.uint8)

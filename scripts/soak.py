@@ -34,15 +34,9 @@ MAX_IN = 1 << 27                                   # bytes of IQ per launch at m
 host = rng.integers(-100, 100, MAX_IN + (1 << 16), dtype=np.int8).view(np.uint8)
 
 
-def dev_alloc(nbytes):
-    p = ctypes.c_void_p()
-    fsea._check(L.fsea_device_alloc(0, nbytes, ctypes.byref(p)))
-    return p
-
-
-d_in = dev_alloc(host.nbytes)
+d_in = fsea.DeviceBuffer(host.nbytes).ptr
 fsea._check(L.fsea_copy_to_device(0, d_in, host.ctypes.data, host.nbytes))
-d_out = [dev_alloc(4 * MAX_IN) for _ in streams]   # f32 rows of a non-overlapped launch fit; others are clipped below
+d_out = [fsea.DeviceBuffer(4 * MAX_IN).ptr for _ in streams]   # f32 rows of a non-overlapped launch fit; others are clipped below
 plans = {}
 WINDOWS = {}                                       # (name, n) -> the float32 weights handed to fsea_plan_set_window
 

@@ -10,7 +10,9 @@
 2. The tool on one 262144-byte capture at its defaults (2622 frames): wall time with --raw and as PNG files, and the time
    write_gray_png alone takes for the same frames (the share that is PNG encoding).
 The registers of the kernels are read from the shipped code object.
-Usage: python scripts/trace_rate.py [--launch-only] [--out DIR]   (--launch-only: part 1 alone, for a trace or counters run)"""
+The measurement is one part, `run`; without it on the command line it runs as a child process under its time limit.
+Usage: python scripts/trace_rate.py [run] [--launch-only] [--to FILE]   (--launch-only: 1. alone; a trace or counters run
+names the part, `run --launch-only`, so that the profiler's child is the process that measures)"""
 import ctypes
 import os
 import subprocess
@@ -23,33 +25,20 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea, nrf  # noqa: E402
+import ratelib  # noqa: E402
 
 WARMUP, REPS, ROUNDS = 2, 3, 5
+# the part's time limit: three times its wall time on an MI355X (7.7 s), rounded up to 30 s, and at least 120 s -- a first
+# import of torch on a fresh machine alone can take over a minute
+STEP_LIMIT_S = 120
 TOOL = os.path.join(ROOT, "frequensea_amd", "bin", "fsea-single-sample")
-
-
-def rounds(fn):
-    import torch
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(ROUNDS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(REPS):
-            fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) / 1e3 / REPS)
-    return out
 
 
 def beside(name, nbytes, kernel, plain):
     k, p = [], []
     for _ in range(2):                       # alternately
-        k += rounds(kernel)
-        p += rounds(plain)
+        k += ratelib.per_round(kernel, WARMUP, REPS, ROUNDS)
+        p += ratelib.per_round(plain, WARMUP, REPS, ROUNDS)
     fmt = lambda ts: " ".join("%.3f" % (t * 1e3) for t in ts)
     print("%s: %.1f MB written per launch" % (name, nbytes / 1e6))
     print("  movie launch ms: %s   best %.3f ms = %.0f GB/s" % (fmt(k), min(k) * 1e3, nbytes / min(k) / 1e9))
@@ -58,7 +47,7 @@ def beside(name, nbytes, kernel, plain):
           (min(k) / min(p), 100 * (max(p) - min(p)) / min(p)))
 
 
-def main():
+def run():
     import torch
     from tests.test_shipped_artifacts import _kernels
     if fsea.device_count() < 1:
@@ -111,6 +100,11 @@ def main():
     print("fsea-single-sample, one 262144-byte capture, %d frames: --raw %.2f s wall, PNG %.2f s wall; write_gray_png alone on "
           "these frames %.2f s (every 20th frame timed, scaled) = %.0f %% of the PNG run" %
           (n, wall["raw"], wall["png"], enc, 100 * enc / wall["png"]))
+
+
+def main():
+    if ratelib.run_parts(__file__, {"run": STEP_LIMIT_S}, sys.argv[1:]):
+        run()
 
 
 if __name__ == "__main__":

@@ -32,12 +32,6 @@ MODE = int(os.environ.get("TUNE_MODE", "0"))
 OUT_BYTES = {0: 4, 1: 1, 2: 1, 3: 8, 4: 4, 5: 4}[MODE]
 
 
-def dev_alloc(nbytes):
-    p = ctypes.c_void_p()
-    fsea._check(fsea.hip_lib().fsea_device_alloc(0, nbytes, ctypes.byref(p)))
-    return p
-
-
 def main():
     sizes = [int(a) for a in sys.argv[1:]] or [8192, 1024, 4096, 16384, 2048, 512, 256, 128]
     L = fsea.hip_lib()
@@ -46,8 +40,8 @@ def main():
     if os.environ.get("TUNE_CONST_INPUT"):  # how much of the time is data-dependent (power)?
         host[:] = 0x80
     per_set = TOTAL_SAMPLES if not os.environ.get("TUNE_FRAMES") else int(os.environ["TUNE_FRAMES"]) * max(sizes)
-    d_ins = [dev_alloc(2 * per_set) for _ in range(SETS)]
-    d_outs = [dev_alloc(max(4, OUT_BYTES) * per_set) for _ in range(SETS)]
+    d_ins = [fsea.DeviceBuffer(2 * per_set).ptr for _ in range(SETS)]
+    d_outs = [fsea.DeviceBuffer(max(4, OUT_BYTES) * per_set).ptr for _ in range(SETS)]
     for d in d_ins:
         fsea._check(L.fsea_copy_to_device(0, d, host.ctypes.data, 2 * per_set))
     d_in, d_out = d_ins[0], d_outs[0]

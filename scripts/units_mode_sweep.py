@@ -18,17 +18,11 @@ MODE = int(os.environ.get("SWEEP_MODE", "0"))
 OUT_BYTES = {0: 4, 1: 1, 2: 1}[MODE]
 
 
-def dev_alloc(nbytes):
-    p = ctypes.c_void_p()
-    fsea._check(L.fsea_device_alloc(0, nbytes, ctypes.byref(p)))
-    return p
-
-
 for n in [int(a) for a in sys.argv[1:]] or [8192]:
     max_frames = (1 << 28) // n // 2
     host = np.random.default_rng(1).integers(-70, 70, 2 * n * max_frames, dtype=np.int8).view(np.uint8)
-    d_ins = [dev_alloc(host.nbytes) for _ in range(SETS)]
-    d_outs = [dev_alloc(OUT_BYTES * n * max_frames) for _ in range(SETS)]
+    d_ins = [fsea.DeviceBuffer(host.nbytes).ptr for _ in range(SETS)]
+    d_outs = [fsea.DeviceBuffer(OUT_BYTES * n * max_frames).ptr for _ in range(SETS)]
     for d in d_ins:
         fsea._check(L.fsea_copy_to_device(0, d, host.ctypes.data, host.nbytes))
     plans = {}

@@ -11,11 +11,9 @@ fsea.use_tune_library()
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
 frames = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 L = fsea.hip_lib()
-def dev_alloc(nbytes):
-    p = ctypes.c_void_p(); fsea._check(L.fsea_device_alloc(0, nbytes, ctypes.byref(p))); return p
 sets = 8
-d_in = [dev_alloc(2 * n * frames) for _ in range(sets)]
-d_out = [dev_alloc(4 * n * frames) for _ in range(sets)]
+d_in = [fsea.DeviceBuffer(2 * n * frames).ptr for _ in range(sets)]
+d_out = [fsea.DeviceBuffer(4 * n * frames).ptr for _ in range(sets)]
 host = np.random.default_rng(1).integers(-70, 70, 2 * n * frames, dtype=np.int8).view(np.uint8)
 for d in d_in:
     fsea._check(L.fsea_copy_to_device(0, d, host.ctypes.data, host.nbytes))

@@ -22,19 +22,13 @@ OUT_BYTES = {0: 4, 1: 1, 2: 1, 3: 8, 4: 4, 5: 4}[MODE]
 ROUNDS = 11
 
 
-def dev_alloc(nbytes):
-    p = ctypes.c_void_p()
-    fsea._check(fsea.hip_lib().fsea_device_alloc(0, nbytes, ctypes.byref(p)))
-    return p
-
-
 def main():
     sizes = [int(a) for a in sys.argv[1:]] or [256, 1024, 2048, 4096, 8192, 16384]
     L = fsea.hip_lib()
     rng = np.random.default_rng(1)
     host = rng.integers(-70, 70, 2 * TOTAL_SAMPLES, dtype=np.int8).view(np.uint8)
-    d_ins = [dev_alloc(host.nbytes) for _ in range(SETS)]
-    d_outs = [dev_alloc(max(4, OUT_BYTES) * TOTAL_SAMPLES) for _ in range(SETS)]
+    d_ins = [fsea.DeviceBuffer(host.nbytes).ptr for _ in range(SETS)]
+    d_outs = [fsea.DeviceBuffer(max(4, OUT_BYTES) * TOTAL_SAMPLES).ptr for _ in range(SETS)]
     for d in d_ins:
         fsea._check(L.fsea_copy_to_device(0, d, host.ctypes.data, host.nbytes))
     for n in sizes:

@@ -16,17 +16,16 @@ counters D: four launches at one D and nothing else, for a counters run of its o
          scripts/zoom_rate.py counters 16), summarised by scripts/pmc_summary.py.
 
 Without an argument kernel and rows run, each as a child process under its own time limit; a part that fails ends the run.
-Usage: python scripts/zoom_rate.py [kernel|rows|counters D]"""
+Usage: python scripts/zoom_rate.py [kernel|rows|counters D] [--to FILE]   (--to: what the parts print goes there too)"""
 import os
-import subprocess
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea  # noqa: E402
+import ratelib  # noqa: E402
 
 N_SAMPLES = 1 << 25
 TAPS, FFT = 97, 1024
@@ -36,10 +35,6 @@ WARMUP, REPS = 5, 40
 WARMUP_CALLS, CALLS = 2, 7
 HBM_BPS = 8e12
 STEP_LIMIT_S = {"kernel": 180, "rows": 420}
-
-
-def recording():
-    return np.random.default_rng(1).integers(0, 256, 2 * N_SAMPLES, dtype=np.uint8)
 
 
 def taps_for(D):
@@ -55,20 +50,12 @@ def lone_kernel_zoom(D):
 
 def kernel():
     import torch
-    d_in, d_row = fsea.DeviceBuffer(2 * N_SAMPLES).upload(recording()), fsea.DeviceBuffer(128 * 4)
+    d_in, d_row = fsea.DeviceBuffer(2 * N_SAMPLES).upload(ratelib.recording(N_SAMPLES)), fsea.DeviceBuffer(128 * 4)
     torch.cuda.init()
     print("n = %d samples resident, L = %d; the decimating kernel alone, median of %d launches after %d" % (N_SAMPLES, TAPS, REPS, WARMUP))
     for D in DECIMATIONS:
         zoom = lone_kernel_zoom(D)
-        times = []
-        for k in range(WARMUP + REPS):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            zoom.run_device(d_in.ptr.value, N_SAMPLES, d_row.ptr.value, CPS, flip=True)
-            e1.record()
-            e1.synchronize()
-            if k >= WARMUP:
-                times.append(e0.elapsed_time(e1) / 1e3)
+        times = ratelib.per_call(lambda: zoom.run_device(d_in.ptr.value, N_SAMPLES, d_row.ptr.value, CPS, flip=True), WARMUP, REPS)
         t = float(np.median(times))
         bound = (2.0 + 8.0 / D) * N_SAMPLES / HBM_BPS
         print("D=%-2d fsea_shift_decim_u8 median %8.1f us (min %8.1f)   traffic bound %6.1f us   fraction %.3f   %.1f Gsamples/s"
@@ -79,7 +66,7 @@ def kernel():
 
 
 def rows():
-    iq = recording()
+    iq = ratelib.recording(N_SAMPLES)
     d_in = fsea.DeviceBuffer(iq.nbytes).upload(iq)
     print("n = %d samples resident, L = %d, N = %d; the same rows two ways, median (min) wall time of %d calls after %d"
           % (N_SAMPLES, TAPS, FFT, CALLS, WARMUP_CALLS))
@@ -102,17 +89,7 @@ def rows():
             return plan.exec_host_f64(kept.view(np.float32).astype(np.float64), n_rows)
 
         assert np.array_equal(new_path().view(np.uint32), parent_path().view(np.uint32)), "the two routes differ"
-        result = []
-        for fn in (new_path, parent_path):
-            for _ in range(WARMUP_CALLS):
-                fn()
-            times = []
-            for _ in range(CALLS):
-                t0 = time.perf_counter()
-                fn()
-                times.append(time.perf_counter() - t0)
-            result.append((float(np.median(times)), min(times)))
-        (zt, zmin), (pt, pmin) = result
+        (zt, zmin), (pt, pmin) = (ratelib.median_min(ratelib.wall(fn, WARMUP_CALLS, CALLS)) for fn in (new_path, parent_path))
         print("D=%-2d %5d rows   zoom %9.1f us (%9.1f)   parent route %11.1f us (%11.1f)   ratio %.1f"
               % (D, n_rows, zt * 1e6, zmin * 1e6, pt * 1e6, pmin * 1e6, pt / zt))
         for obj in (zoom, fir, plan):
@@ -123,7 +100,7 @@ def rows():
 
 
 def counters(D):
-    d_in, d_row = fsea.DeviceBuffer(2 * N_SAMPLES).upload(recording()), fsea.DeviceBuffer(128 * 4)
+    d_in, d_row = fsea.DeviceBuffer(2 * N_SAMPLES).upload(ratelib.recording(N_SAMPLES)), fsea.DeviceBuffer(128 * 4)
     sync = fsea.Plan(128)
     zoom = lone_kernel_zoom(D)
     for _ in range(4):
@@ -136,17 +113,12 @@ def counters(D):
 
 
 def main():
-    parts = {"kernel": kernel, "rows": rows}
-    if len(sys.argv) > 2 and sys.argv[1] == "counters":
+    if sys.argv[1:2] == ["counters"]:
         counters(int(sys.argv[2]))
         return
-    if len(sys.argv) > 1:
-        parts[sys.argv[1]]()
-        return
-    for name in ("kernel", "rows"):
-        r = subprocess.run(["timeout", "-k", "10", str(STEP_LIMIT_S[name]), sys.executable, os.path.abspath(__file__), name])
-        if r.returncode != 0:
-            raise SystemExit("%s failed (exit status %d): stopping" % (name, r.returncode))
+    part = ratelib.run_parts(__file__, STEP_LIMIT_S, sys.argv[1:])
+    if part:
+        {"kernel": kernel, "rows": rows}[part]()
 
 
 if __name__ == "__main__":
