@@ -53,6 +53,10 @@ EVENTS_EVENT = np.dtype([("row_first", "<u4"), ("row_last", "<u4"), ("col_first"
                          ("peak", "<i4"), ("peak_row", "<u4"), ("peak_col", "<u4"), ("hits", "<u8"), ("level_sum", "<i8")])   # fsea_events_event
 IQ_U8, IQ_F32, IQ_F64 = 0, 1, 2   # FSEA_IQ_* input types (include/fsea.h)
 EXTRACT_MAX_JOBS = 65536        # FSEA_EXTRACT_MAX_JOBS
+MEASURE_TILE_PAIRS = 4096       # FSEA_MEASURE_TILE_PAIRS: pairs per workgroup of fsea_measure_tiles
+MEASURE_MAX_JOBS = 65536        # FSEA_MEASURE_MAX_JOBS
+MEASURE_MAX_PAIRS = 1 << 24     # FSEA_MEASURE_MAX_PAIRS, per job
+MEASURE_MAX_LAG = 65536         # FSEA_MEASURE_MAX_LAG
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
 DEMOD_MAX_CHANNELS = 256            # FSEA_DEMOD_MAX_CHANNELS
@@ -85,6 +89,25 @@ class ExtractJob(ctypes.Structure):
     """fsea_extract_job (include/fsea.h): one cut-out of a resident recording."""
     _fields_ = [("first", ctypes.c_uint64), ("n_samples", ctypes.c_uint64), ("sample_offset", ctypes.c_uint64),
                 ("cycles_per_sample", ctypes.c_double), ("phase0_cycles", ctypes.c_double), ("out_first", ctypes.c_uint64)]
+
+
+class MeasureJob(ctypes.Structure):
+    """fsea_measure_job (include/fsea.h): a span of a resident buffer of pairs."""
+    _fields_ = [("first_pair", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64)]
+
+
+class MeasureSums(ctypes.Structure):
+    """fsea_measure_sums (include/fsea.h): the moment sums of one job."""
+    _fields_ = [("s_re", ctypes.c_double), ("s_im", ctypes.c_double), ("p", ctypes.c_double), ("q", ctypes.c_double),
+                ("r_re", ctypes.c_double), ("r_im", ctypes.c_double), ("peak", ctypes.c_double), ("peak_index", ctypes.c_uint64),
+                ("n_pairs", ctypes.c_uint64), ("n_lagged", ctypes.c_uint64)]
+
+
+class MeasureResult(ctypes.Structure):
+    """fsea_measure_result (include/fsea.h): what fsea_measure_finish makes of the sums."""
+    _fields_ = [("mean_power", ctypes.c_double), ("power_db", ctypes.c_double), ("dc_re", ctypes.c_double), ("dc_im", ctypes.c_double),
+                ("freq_cycles", ctypes.c_double), ("coherence", ctypes.c_double), ("width_cycles", ctypes.c_double),
+                ("kurtosis", ctypes.c_double), ("crest", ctypes.c_double), ("peak_index", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64)]
 
 
 class CaptureRun(ctypes.Structure):
@@ -227,6 +250,12 @@ API = {
     "fsea_extract_run_device": (_ci, [_vp, _vp, _sz, _ci, _vp, _sz, _vp, _sz, _vp]),
     "fsea_extract_run_host": (_ci, [_vp, _vp, _sz, _ci, _vp, _sz, _vp, _sz]),
     "fsea_extract_jobs": (_ci, [_vp, _sz, _ci, _ci, _u64, _ci, _ci, _f64, _vp, _vp]),
+    "fsea_measure_create": (_ci, [_out, _ci]),
+    "fsea_measure_destroy": (_ci, [_vp]),
+    "fsea_measure_run_device": (_ci, [_vp, _vp, _sz, _vp, _sz, _f64, _f64, _ci, _vp, _vp]),
+    "fsea_measure_run_host": (_ci, [_vp, _vp, _sz, _vp, _sz, _f64, _f64, _ci, _vp]),
+    "fsea_measure_jobs": (_ci, [_vp, _sz, _ci, _sz, _vp]),
+    "fsea_measure_finish": (_ci, [_vp, _ci, _vp]),
     "fsea_iq_draw_create": (_ci, [_out, _ci]),
     "fsea_iq_draw_destroy": (_ci, [_vp]),
     "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
@@ -1031,6 +1060,59 @@ class Extract(_Handle):
         _check(self._L.fsea_extract_run_device(self._p, d_iq_ptr or None, n_iq_samples, int(bool(flip)),
                                                ctypes.addressof(table) if len(table) else None, len(table), d_pairs_ptr or None,
                                                pairs_capacity, stream or None))
+
+
+def _table_of(kind, jobs):
+    """a sequence of `kind` records as one ctypes array (a ctypes array of them passes through)"""
+    if isinstance(jobs, ctypes.Array) and jobs._type_ is kind:
+        return jobs
+    jobs = list(jobs)
+    return (kind * len(jobs))(*jobs)
+
+
+def measure_jobs(extract_jobs_laid_out, decimation, skip_pairs=0):
+    """fsea_measure_jobs (host arithmetic): the spans of the outputs of extract jobs that Extract.layout laid out, each
+    without its first skip_pairs pairs, as a ctypes array of MeasureJob."""
+    table = _job_table(extract_jobs_laid_out)
+    jobs = (MeasureJob * len(table))()
+    _check(hip_lib().fsea_measure_jobs(ctypes.addressof(table) if len(table) else None, len(table), int(decimation), int(skip_pairs),
+                                       ctypes.addressof(jobs) if len(table) else None))
+    return jobs
+
+
+def measure_finish(sums, lag=1):
+    """fsea_measure_finish (host arithmetic, no GPU needed): a MeasureSums made with `lag` to a MeasureResult."""
+    result = MeasureResult()
+    _check(hip_lib().fsea_measure_finish(ctypes.byref(sums), int(lag), ctypes.byref(result)))
+    return result
+
+
+class Measure(_Handle):
+    """Signal measures on one device: a table of spans of one buffer of complex64 in, one record of moment sums per span out,
+    in two launches, stateless; thin wrapper over fsea_measure_*.  run() takes the pairs and the jobs from the host and
+    returns a ctypes array of MeasureSums; run_device() works on resident memory."""
+    _kind = "measure"
+
+    def __init__(self, device=0):
+        self.device = device
+        self._create("fsea_measure_create", device)
+
+    def run(self, pairs, jobs, offset=0j, lag=1):
+        z = np.ascontiguousarray(pairs, dtype=np.complex64).ravel()
+        table = _table_of(MeasureJob, jobs)
+        sums = (MeasureSums * len(table))()
+        offset = complex(offset)
+        _check(self._L.fsea_measure_run_host(self._p, z.ctypes.data, z.size, ctypes.addressof(table) if len(table) else None, len(table),
+                                             offset.real, offset.imag, int(lag), ctypes.addressof(sums) if len(table) else None))
+        return sums
+
+    def run_device(self, d_pairs_ptr, n_buffer_pairs, jobs, d_sums_ptr, offset=0j, lag=1, stream=0):
+        """Device pointers (ints): n_buffer_pairs complex64 in (8-byte aligned), one 80-byte record per job out (16-byte
+        aligned); asynchronous.  The jobs are read before the call returns."""
+        table = _table_of(MeasureJob, jobs)
+        offset = complex(offset)
+        _check(self._L.fsea_measure_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, ctypes.addressof(table) if len(table) else None,
+                                               len(table), offset.real, offset.imag, int(lag), d_sums_ptr or None, stream or None))
 
 
 class Demod(_ResettableHandle):

@@ -18,10 +18,18 @@
  * output behind the run-in.  The tool prints
  *     rows R runs N events E cutouts C skipped S
  *
+ * --measures says what is inside each cut-out.  After a batch's fsea_extract_run_device, with the pairs still resident, one
+ * fsea_measure_run_device (include/fsea.h) sums the spans the .cf32 files get -- the outputs without the run-in -- with
+ * the lag of --lag (default 1) and the offset (0.5 + 0.5j) sum(c) a cut-out rests on, c the taps as the f32 values the
+ * extract object holds.  DIR/measures.txt gets one line per cut-out written:
+ *     number pairs power_db freq_cycles freq_mhz width_cycles kurtosis crest dc_re dc_im
+ * the eight measures as %.9e (fsea_measure_finish); freq_mhz is what freq_cycles adds to the event's centre_mhz, 0 without
+ * --rate.  Without --measures nothing of this happens and no such file is written.
+ *
  * usage: fsea-cutouts FILE --size N --decimation D --out DIR [--hop H] [--window NAME] [--flip] [--mode db5|db10|db]
  *                     [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R]
  *                     [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--taps L] [--cutoff HZ]
- *                     [--fill F] [--max-events E] [--max-samples S]
+ *                     [--fill F] [--max-events E] [--max-samples S] [--measures [--lag K]]
  */
 #include <errno.h>
 #include <limits.h>
@@ -41,12 +49,14 @@ static const char *USAGE =
     "usage: fsea-cutouts FILE --size N --decimation D --out DIR [--hop H] [--window NAME] [--flip] [--mode db5|db10|db]\n"
     "                    [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R]\n"
     "                    [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--taps L] [--cutoff HZ]\n"
-    "                    [--fill F] [--max-events E] [--max-samples S]\n"
+    "                    [--fill F] [--max-events E] [--max-samples S] [--measures [--lag K]]\n"
     "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8).  The emissions are found as fsea-events finds them (its\n"
     "  options, same defaults); each one whose columns times D fill at most F of the N columns is mixed to the centre,\n"
     "  low-passed (L taps, half amplitude at --cutoff, default 0.4 RATE / D) and decimated by D on the GPU, all of a batch in\n"
     "  one launch, and written to DIR/cutout-NNNNN.cf32 as f32 pairs; DIR/cutouts.txt lists every event.  A cut-out longer\n"
-    "  than S samples is cut short.  Prints `rows R runs N events E cutouts C skipped S`\n"
+    "  than S samples is cut short.  --measures: DIR/measures.txt says of every cut-out written its power in dB, its\n"
+    "  frequency offset (lag K pairs, default 1), spectrum width, envelope kurtosis, crest factor and what is left of its DC.\n"
+    "  Prints `rows R runs N events E cutouts C skipped S`\n"
     "  defaults: --taps 97 --fill 0.8 --max-events 1024 --max-samples 16777216";
 
 static void usage_error(const char *msg) { tool_usage_error(TOOL, msg); }
@@ -71,7 +81,7 @@ static fsea_events_run *runs_room(size_t more) {
 
 int main(int argc, char **argv) {
     const char *path = NULL, *out_dir = NULL, *window = "rect", *mode_name = "db5";
-    int size = 0, hop = 0, flip = 0, gap_cols = 0, gap_rows = 0, decimation = 0, n_taps = 97;
+    int size = 0, hop = 0, flip = 0, gap_cols = 0, gap_rows = 0, decimation = 0, n_taps = 97, measures = 0, lag = 1;
     long long min_rows = 1, min_cols = 1, min_hits = 1, max_events = 1024, max_samples = 1ll << 24;
     double cutoff = 0.0, fill = 0.8;
     tool_detector det = TOOL_DETECTOR_DEFAULTS;
@@ -97,6 +107,8 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--fill") && more) fill = atof(argv[++i]);
         else if (!strcmp(argv[i], "--max-events") && more) max_events = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--max-samples") && more) max_samples = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--measures")) measures = 1;
+        else if (!strcmp(argv[i], "--lag") && more) lag = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--out") && more) out_dir = argv[++i];
         else if (argv[i][0] != '-' && path == NULL) path = argv[i];
         else usage_error(USAGE);
@@ -121,6 +133,7 @@ int main(int argc, char **argv) {
     if (max_events < 1 || max_events > FSEA_EXTRACT_MAX_JOBS) usage_error("--max-events must be in [1, 65536]");
     if (max_samples < 1 || max_samples > (1ll << 24)) usage_error("--max-samples must be in [1, 16777216]");
     if (cutoff < 0.0) usage_error("--cutoff must be positive");
+    if (lag < 1 || lag > FSEA_MEASURE_MAX_LAG) usage_error("--lag must be in [1, 65536]");
     if (out_dir == NULL) usage_error("--out DIR is required");
     int mode = 0, type = 0;
     if (!tool_rows_mode(mode_name, "db", &mode, &type)) usage_error("--mode must be db5, db10 or db");
@@ -201,6 +214,23 @@ int main(int argc, char **argv) {
     if (fsea_fir_lowpass_taps(design_rate, cutoff, n_taps, taps) != FSEA_OK) die("fsea_fir_lowpass_taps");
     fsea_extract *extract = NULL;
     if (fsea_extract_create(&extract, taps, n_taps, decimation, 0) != FSEA_OK) die("fsea_extract_create");
+    /* --measures: the object, one record per event, and the pedestal of a cut-out from the taps as the extract holds them */
+    fsea_measure *measure = NULL;
+    fsea_measure_result *measured = NULL;
+    fsea_measure_job *spans = NULL;
+    fsea_measure_sums *h_sums = NULL;
+    void *d_sums = NULL;
+    double pedestal = 0.0;
+    if (measures) {
+        if (fsea_measure_create(&measure, 0) != FSEA_OK) die("fsea_measure_create");
+        measured = (fsea_measure_result *)calloc(n_jobs + 1, sizeof(fsea_measure_result));
+        spans = (fsea_measure_job *)malloc(sizeof(fsea_measure_job) * (n_jobs + 1));
+        h_sums = (fsea_measure_sums *)malloc(sizeof(fsea_measure_sums) * (n_jobs + 1));
+        if (measured == NULL || spans == NULL || h_sums == NULL) usage_error("out of memory");
+        if (fsea_device_alloc(0, sizeof(fsea_measure_sums) * (n_jobs + 1), &d_sums) != FSEA_OK) die("fsea_device_alloc");
+        for (int k = 0; k < n_taps; k++) pedestal += (double)(float)taps[k];
+        pedestal *= 0.5;
+    }
     if (mkdir(out_dir, 0777) != 0 && errno != EEXIST) {
         fprintf(stderr, TOOL ": cannot create directory %s\n", out_dir);
         return EXIT_FAILURE;
@@ -246,6 +276,18 @@ int main(int argc, char **argv) {
         }
         if (fsea_copy_to_device(0, d_iq, h_iq, 2 * at) != FSEA_OK) die("fsea_copy_to_device");
         if (fsea_extract_run_device(extract, d_iq, at, flip, batch, n_batch, d_pairs, total, NULL) != FSEA_OK) die("fsea_extract_run_device");
+        if (measures) {
+            /* the spans the files get, on the pairs as they lie on the device */
+            if (fsea_measure_jobs(batch, n_batch, decimation, lead_out, spans) != FSEA_OK) die("fsea_measure_jobs");
+            if (fsea_measure_run_device(measure, d_pairs, total, spans, n_batch, pedestal, pedestal, lag, (fsea_measure_sums *)d_sums,
+                                        NULL) != FSEA_OK) {
+                die("fsea_measure_run_device");
+            }
+            if (fsea_copy_to_host(0, h_sums, d_sums, n_batch * sizeof(fsea_measure_sums)) != FSEA_OK) die("fsea_copy_to_host");
+            for (size_t b = 0; b < n_batch; b++) {
+                if (fsea_measure_finish(&h_sums[b], lag, &measured[batch_of[b]]) != FSEA_OK) die("fsea_measure_finish");
+            }
+        }
         if (fsea_copy_to_host(0, h_pairs, d_pairs, total * 2 * sizeof(float)) != FSEA_OK) die("fsea_copy_to_host");
         for (size_t b = 0; b < n_batch; b++) {
             const size_t n_out = (size_t)batch[b].n_samples / (size_t)decimation, e = batch_of[b];
@@ -280,6 +322,29 @@ int main(int argc, char **argv) {
     if (fclose(list) != 0) {
         fprintf(stderr, TOOL ": cannot write %s\n", name);
         return EXIT_FAILURE;
+    }
+    if (measures) {
+        snprintf(name, name_len, "%s/measures.txt", out_dir);
+        FILE *table = fopen(name, "w");
+        if (table == NULL) {
+            fprintf(stderr, TOOL ": cannot write %s\n", name);
+            return EXIT_FAILURE;
+        }
+        for (size_t e = 0; e < n_jobs; e++) {
+            const fsea_measure_result *r = &measured[e];
+            if (written[e] == 0) continue;
+            fprintf(table, "%u %zu %.9e %.9e %.9e %.9e %.9e %.9e %.9e %.9e\n", (unsigned)e, written[e], r->power_db, r->freq_cycles,
+                    r->freq_cycles * rate / (double)decimation / 1e6, r->width_cycles, r->kurtosis, r->crest, r->dc_re, r->dc_im);
+        }
+        if (fclose(table) != 0) {
+            fprintf(stderr, TOOL ": cannot write %s\n", name);
+            return EXIT_FAILURE;
+        }
+        fsea_measure_destroy(measure);
+        fsea_device_free(0, d_sums);
+        free(measured);
+        free(spans);
+        free(h_sums);
     }
     printf("rows %zu runs %zu events %zu cutouts %zu skipped %zu\n", done, g_n_runs, n_events, n_cutouts, n_events - n_cutouts);
 

@@ -36,6 +36,7 @@
  *   fsea_cfar_*           a CFAR detector across frequency (no counterpart in the reference): occupied bins, bands and masks
  *   fsea_events_*         spectrum events (no counterpart in the reference): a detection mask as runs, time-frequency boxes
  *   fsea_extract_*        event cut-outs (no counterpart in the reference): each box of fsea_events_link as decimated IQ
+ *   fsea_measure_*        signal measures (no counterpart in the reference): power, offset, width and envelope of each cut-out
  *   fsea_detect_*         the burst detector of lua/signal-detector.lua: the two loops of nrf_signal_detector_process,
  *                         src/nrf.c:883-898, as integer sums over many blocks per launch
  *   fsea_capture_*        that scene on a resident recording: detect -> gate -> filter the bursts -> line images
@@ -858,6 +859,95 @@ int fsea_extract_run_host(fsea_extract *extract, const uint8_t *iq, size_t n_iq_
                           size_t n_jobs, float *pairs, size_t pairs_capacity);
 int fsea_extract_jobs(const fsea_events_event *events, size_t n_events, int width, int hop, uint64_t n_samples, int n_taps,
                       int decimation, double max_fill, fsea_extract_job *jobs, uint8_t *fits);
+
+/* Signal measures: what is inside each cut-out -- how strong it is, how far it sits from the centre its box gave it, how wide
+ * it is, whether its envelope is constant (FM, FSK, a carrier) or noise-like (OFDM, DVB-T).  All of it follows from a few
+ * sums per cut-out, the pulse-pair moments of radar plus the envelope's second and fourth moments.  An fsea_measure takes a
+ * table of jobs over one resident buffer of f32 pairs (what fsea_extract_run_device left) and gives one record of sums per
+ * job, in one launch for the tiles and one for the fold.  There is no state between calls and no reset.
+ *   terms:      for pair i of a job, z_i = pairs[first_pair + i], in f64 with exactly the roundings written here (rn = one
+ *               IEEE rounding; nothing is contracted into an FMA):
+ *                 a_i = rn((double)re_i - offset_re),   b_i = rn((double)im_i - offset_im),
+ *                 P_i = rn(rn(a_i a_i) + rn(b_i b_i)),  Q_i = rn(P_i P_i),   and with j = i - lag, for i >= lag,
+ *                 Rre_i = rn(rn(a_i a_j) + rn(b_i b_j)),  Rim_i = rn(rn(b_i a_j) - rn(a_i b_j));
+ *               for i < lag both R terms are +0.0 and keep their place in the order.  offset is the pedestal the caller
+ *               knows: a cut-out rests on (0.5 + 0.5j) sum(c), and what is left of it shows in s_re, s_im.
+ *   order:      fold_W(x[0 .. m)): W accumulators start at +0.0; accumulator l adds x[l], x[l + W], x[l + 2 W], ... in that
+ *               order; then for k = 1, 2, 4, ..., W / 2: acc[l] = acc[l] + acc[l ^ k] for every l; the value is acc[0]; an
+ *               absent x counts as +0.0.  A job's pairs are cut into tiles of FSEA_MEASURE_TILE_PAIRS counted from the job's
+ *               own pair 0.  A tile's partial of each of the six sums (a_i, b_i, P_i, Q_i, Rre_i, Rim_i) is fold_256 over the
+ *               tile's terms; a job's sum is fold_64 over its tiles' partials in tile order.  peak is the largest P_i
+ *               (comparisons: a NaN term is never the peak), peak_index the least i that has it.  Nothing in this depends on
+ *               first_pair (at any parity), on the other jobs, on their order or on the launch geometry: a job's record is
+ *               the same bits alone or in a table of FSEA_MEASURE_MAX_JOBS.
+ *   table:      jobs may overlap and may repeat; sums[k] belongs to jobs[k]; an empty job gets zeros, peak +0.0 and
+ *               peak_index 0.  `jobs` is host memory, read before the call returns.  Only the jobs' pairs are read, only the
+ *               n_jobs records are written.
+ *   create:     FSEA_ENODEVICE without a GPU.  Destroy waits for the device.
+ *   run_device: d_pairs (n_buffer_pairs pairs of floats) 8-byte aligned, d_sums (n_jobs records) 16-byte aligned;
+ *               asynchronous on `stream`.  The object owns the device copy of the table and the tile partials and grows them
+ *               as needed, so calls on several streams follow one another (an event).  Kernel fsea_measure_tiles: one
+ *               workgroup per tile of one job, which it finds by a bisection over the jobs' first tiles; kernel
+ *               fsea_measure_fold: one wave per job.
+ *   run_host:   the same from and to host memory through pinned staging on the object's own stream; returns when `sums` is
+ *               complete.
+ * Both check, before any device work and reading nothing of the object, in this order: a NULL object; n_jobs above
+ * FSEA_MEASURE_MAX_JOBS; n_jobs == 0 is then a successful no-op; a NULL job table; a NULL buffer (pairs or sums); lag outside
+ * [1, FSEA_MEASURE_MAX_LAG]; an offset that is not finite; per job in table order: first_pair + n_pairs past n_buffer_pairs,
+ * n_pairs above FSEA_MEASURE_MAX_PAIRS (each text names the job); more than 2^31 pairs in the call; for run_device a d_pairs
+ * that is not 8-byte or a d_sums that is not 16-byte aligned.  All FSEA_EINVAL; a refused call writes nothing.  Calls on one
+ * object from several threads are serialised.
+ *   jobs:       fsea_measure_jobs, host arithmetic, no device: the spans of the outputs of extract jobs that were laid out
+ *               (fsea_extract_layout), without the first skip_pairs of each (the filter's run-in, fsea_extract_lead /
+ *               decimation).  With outs = n_samples / decimation (rounded down) and skip = min(skip_pairs, outs): job k
+ *               gets first_pair = out_first + skip, n_pairs = outs - skip.  FSEA_EINVAL for NULL tables with n_jobs > 0,
+ *               n_jobs above FSEA_MEASURE_MAX_JOBS, decimation < 1, a span longer than FSEA_MEASURE_MAX_PAIRS (the text
+ *               names the job).
+ *   finish:     fsea_measure_finish, host arithmetic, callable in a process without a GPU: one record of sums and the lag
+ *               it was made with to the measures, with n = n_pairs, m = n_lagged and |r| = hypot(r_re, r_im):
+ *                 mean_power   = p / n                       power_db = 10 log10(mean_power)
+ *                 dc_re, dc_im = s_re / n, s_im / n
+ *                 freq_cycles  = atan2(r_im, r_re) / (2 pi lag)      cycles per pair, unambiguous within +-1 / (2 lag)
+ *                 coherence    = rho = min(1, |r| n / (p m))
+ *                 width_cycles = sqrt(-2 ln rho) / (2 pi lag)        the pulse-pair width of a Gaussian spectrum
+ *                 kurtosis     = n q / p^2                   1 for a constant envelope, 2 for complex Gaussian noise
+ *                 crest        = peak n / p
+ *                 peak_index   = the sums' own
+ *               With n == 0 or p == 0 the ratios are NaN (power_db of a zero mean power is -inf) and the call still returns
+ *               FSEA_OK; freq_cycles, coherence and width_cycles are NaN when m == 0.  FSEA_EINVAL for a NULL pointer or a
+ *               lag outside [1, FSEA_MEASURE_MAX_LAG]. */
+#define FSEA_MEASURE_TILE_PAIRS 4096
+#define FSEA_MEASURE_MAX_JOBS   65536          /* = FSEA_EXTRACT_MAX_JOBS */
+#define FSEA_MEASURE_MAX_PAIRS  (1u << 24)     /* per job */
+#define FSEA_MEASURE_MAX_LAG    65536
+typedef struct { uint64_t first_pair, n_pairs; } fsea_measure_job;       /* 16 bytes */
+typedef struct {                                                        /* 80 bytes */
+    double s_re, s_im;      /* sum z                          */
+    double p;               /* sum |z|^2                      */
+    double q;               /* sum |z|^4                      */
+    double r_re, r_im;      /* sum z[i] conj(z[i - lag]), i >= lag */
+    double peak;            /* max |z|^2                      */
+    uint64_t peak_index;    /* first i that has it (0 for an empty job) */
+    uint64_t n_pairs, n_lagged;   /* n, max(n - lag, 0)       */
+} fsea_measure_sums;
+typedef struct {                                                        /* 88 bytes */
+    double mean_power, power_db;
+    double dc_re, dc_im;
+    double freq_cycles;
+    double coherence, width_cycles;
+    double kurtosis, crest;
+    uint64_t peak_index;
+    uint64_t n_pairs;
+} fsea_measure_result;
+typedef struct fsea_measure fsea_measure;
+int fsea_measure_create(fsea_measure **m, int device);
+int fsea_measure_destroy(fsea_measure *m);
+int fsea_measure_run_device(fsea_measure *m, const void *d_pairs, size_t n_buffer_pairs, const fsea_measure_job *jobs,
+                            size_t n_jobs, double offset_re, double offset_im, int lag, fsea_measure_sums *d_sums, void *stream);
+int fsea_measure_run_host(fsea_measure *m, const float *pairs, size_t n_buffer_pairs, const fsea_measure_job *jobs,
+                          size_t n_jobs, double offset_re, double offset_im, int lag, fsea_measure_sums *sums);
+int fsea_measure_jobs(const fsea_extract_job *ejobs, size_t n_jobs, int decimation, size_t skip_pairs, fsea_measure_job *jobs);
+int fsea_measure_finish(const fsea_measure_sums *sums, int lag, fsea_measure_result *result);
 
 /* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
  * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With

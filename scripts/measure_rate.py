@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""What the moment sums of a table of cut-outs (fsea_measure_*, kernels fsea_measure_tiles and fsea_measure_fold) cost against
+the extract call that made the pairs and against one call per cut-out, on a resident recording of 2^25 samples, L = 97,
+D = 4, 16, 64.  HIP-event times in one process, median of REPS calls after WARMUP:
+
+(a) one fsea_measure_run_device of 256 jobs of 65536 / D pairs each on the pairs (b) left, the jobs at even and odd firsts
+    in turn, lag 1;
+(b) the fsea_extract_run_device call that made those pairs: 256 jobs of 65536 + D samples, as scripts/extract_rate.py lays
+    them over the recording;
+(c) 256 fsea_measure_run_device calls of one job each: the route of a caller that measures cut-out by cut-out.
+
+Two bounds for (a): 8 bytes per pair at 8 TB/s, and the counted f64 instructions per pair -- 4 conversions, 4 subtractions, 3
+for P, 1 for Q, 6 for the two R terms, 6 accumulations, 1 comparison: 25, none of them fused -- against the 32.9 T f64
+instructions a second behind the 65.8 TFLOP/s that scripts/ubench/fp64_fma.hip measured (an FMA counts 2).
+
+`trace` runs TRACE_CALLS calls of (a) at D = 16 in a child of its own under a kernel trace (nothing else traced) and prints the
+median time of each of the three kernels of a call.
+
+Without an argument every D and then the trace run as child processes under their own time limits and the lines go to
+profiles/measure_rate.txt (or the file named after --to); a part that fails ends the run.
+Usage: python scripts/measure_rate.py [--to FILE] | python scripts/measure_rate.py measure D | ... trace      (D = 4, 16 or 64)"""
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from frequensea_amd import fsea  # noqa: E402
+import ratelib  # noqa: E402
+
+N_SAMPLES = 1 << 25
+TAPS = 97
+DECIMATIONS = (4, 16, 64)
+N_JOBS, JOB_BASE = 256, 65536
+WARMUP, REPS = 5, 20
+HBM_BPS = 8e12
+F64_OPS_PER_PAIR = 25
+F64_OPS_PER_S = 65.8e12 / 2
+STEP_LIMIT_S = 240
+TRACE_D, TRACE_CALLS = 16, 10
+KERNELS = ("fsea_measure_upload", "fsea_measure_tiles", "fsea_measure_fold")     # a call's three, in launch order
+
+HEADER = """# scripts/measure_rate.py on one MI355X: HIP-event times in one process, median (min) of %d calls after %d
+# recording: 2^25 samples resident, L = %d, taps = lowpass(10e6, 10e6 / (2 D), %d); lag 1, offset (0.5 + 0.5j) sum(c)
+# (a) one fsea_measure_run_device: %d jobs of 65536 / D pairs on the pairs of (b), first_pair = out_first + i mod 2
+# (b) the fsea_extract_run_device that made them: %d jobs of 65536 + D samples, first = 131072 i + 3 + i mod 5, a centre per job
+# (c) %d fsea_measure_run_device calls of one job each
+# traffic bound = 8 bytes per pair at 8 TB/s; f64 bound = %d instructions per pair at 32.9 T/s (65.8 TFLOP/s of v_fma_f64, FMA = 2)
+# host time: wall time of the call (a) itself, until it returns
+""" % (REPS, WARMUP, TAPS, TAPS, N_JOBS, N_JOBS, N_JOBS, F64_OPS_PER_PAIR)
+
+
+def setup(D):
+    """the three routes as calls, what they work on, and what to release afterwards"""
+    import torch
+    iq = ratelib.recording(N_SAMPLES)
+    d_in = fsea.DeviceBuffer(iq.nbytes).upload(iq)
+    torch.cuda.init()
+    c = fsea.lowpass_taps(10e6, 10e6 / (2 * D), TAPS)
+    n_pairs = JOB_BASE // D
+    ex, m = fsea.Extract(c, D), fsea.Measure()
+    ejobs = [fsea.ExtractJob(131072 * i + 3 + i % 5, JOB_BASE + D, 131072 * i + 3 + i % 5, (i - 128) / 1024.0, 0.0, 0) for i in range(N_JOBS)]
+    table, total = ex.layout(ejobs)
+    d_pairs = fsea.DeviceBuffer(8 * total)
+    mjobs = (fsea.MeasureJob * N_JOBS)(*[fsea.MeasureJob(j.out_first + i % 2, n_pairs) for i, j in enumerate(table)])
+    singles = [(fsea.MeasureJob * 1)(j) for j in mjobs]
+    d_sums = fsea.DeviceBuffer(80 * N_JOBS)
+    offset = 0.5 * float(np.sum(c.astype(np.float32).astype(np.float64))) * (1 + 1j)
+
+    def a():
+        m.run_device(d_pairs.ptr.value, total, mjobs, d_sums.ptr.value, offset=offset, lag=1)
+
+    def b():
+        ex.run_device(d_in.ptr.value, N_SAMPLES, table, d_pairs.ptr.value, total, flip=True)
+
+    def c_route():
+        for k, one in enumerate(singles):
+            m.run_device(d_pairs.ptr.value, total, one, d_sums.ptr.value + 80 * k, offset=offset, lag=1)
+
+    b()
+    return a, b, c_route, total, offset, (ex, m), (d_in, d_pairs, d_sums)
+
+
+def release(objects, buffers):
+    for o in objects:
+        o.close()
+    for o in buffers:
+        o.free()
+
+
+def measure(D):
+    a, b, c_route, total, offset, objects, buffers = setup(D)
+    n_pairs = JOB_BASE // D
+    (tb, tb_min), (ta, ta_min), (tc, tc_min) = (ratelib.median_min(ratelib.per_call(fn, WARMUP, REPS)) for fn in (b, a, c_route))
+    # what the host spends inside the call (a) before it returns, on a stream made idle outside the clock (as extract_rate.py)
+    sync = fsea.Plan(128)
+    host = []
+    for _ in range(REPS):
+        sync.synchronize()
+        t0 = time.perf_counter()
+        a()
+        host.append(time.perf_counter() - t0)
+    sync.synchronize()
+    sync.close()
+    pairs = N_JOBS * n_pairs
+    traffic, f64 = 8.0 * pairs / HBM_BPS, F64_OPS_PER_PAIR * pairs / F64_OPS_PER_S
+    print("D=%-2d %d pairs in %d jobs   (a) measure %8.1f us (%8.1f)   (b) the extract call %8.1f us (%8.1f)   (c) %d one-job calls %9.1f us (%9.1f)"
+          "   traffic bound %5.2f us   f64 bound %5.2f us   (a)/(b) %.3f   (c)/(a) %.1f   host time of (a) %.1f us"
+          % (D, pairs, N_JOBS, ta * 1e6, ta_min * 1e6, tb * 1e6, tb_min * 1e6, N_JOBS, tc * 1e6, tc_min * 1e6, traffic * 1e6, f64 * 1e6,
+             ta / tb, tc / ta, float(np.median(host)) * 1e6))
+    release(objects, buffers)
+
+
+def launches():
+    """what the trace sees: TRACE_CALLS calls of (a) at TRACE_D"""
+    a, b, c_route, total, offset, objects, buffers = setup(TRACE_D)
+    for _ in range(TRACE_CALLS):
+        a()
+    sync = fsea.Plan(128)
+    sync.synchronize()
+    sync.close()
+    release(objects, buffers)
+
+
+def trace():
+    name, times = ratelib.kernel_trace([sys.executable, os.path.abspath(__file__), "launches"], "fsea_measure_", 3 * TRACE_CALLS, 1)[0]
+    assert name.startswith(KERNELS[0]), name
+    print("kernel trace, D=%d, %d calls of (a): " % (TRACE_D, TRACE_CALLS) +
+          "   ".join("%s %.1f us" % (k, float(np.median(times[i::3])) * 1e6) for i, k in enumerate(KERNELS)))
+
+
+def main():
+    if sys.argv[1:] == ["launches"]:         # the traced child of `trace`, not a part of its own
+        return launches()
+    parts = {"measure %d" % D: STEP_LIMIT_S for D in DECIMATIONS}
+    parts["trace"] = STEP_LIMIT_S
+    part = ratelib.run_parts(__file__, parts, sys.argv[1:], to=os.path.join(ROOT, "profiles", "measure_rate.txt"), header=HEADER + "\n")
+    if part == "trace":
+        trace()
+    elif part:
+        measure(int(part.split()[1]))
+
+
+if __name__ == "__main__":
+    main()
