@@ -1,6 +1,7 @@
 // fsea_api.hip -- what every translation unit of libfsea_hip.so stands on, and the part of the C ABI (include/fsea.h) that
-// takes no plan: the error plumbing, the bodies of the device objects' scaffold (fsea_internal.h), device count, the
-// alloc / copy / stream wrappers and the two image compositors.  Plans are in fsea_plan.hip and fsea_plan_host.hip.
+// takes no plan: the error plumbing, the bodies of the device objects' scaffold (fsea_internal.h), the job tables' upload
+// kernel (fsea_jobs.h), device count, the alloc / copy / stream wrappers and the two image compositors.  Plans are in
+// fsea_plan.hip and fsea_plan_host.hip.
 #include "../../include/fsea.h"
 
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include <string>
 
 #include "fsea_internal.h"
+#include "fsea_jobs.h"
 
 using namespace fsea_detail;
 
@@ -76,6 +78,13 @@ __global__ void fsea_stitch_tiles_kernel(uint8_t *dst, const uint8_t *tiles, uin
 }
 
 }  // namespace
+
+// A job table from the mapped host memory a call built it in to the device, one word a lane (fsea_jobs.h: JobTable)
+extern "C" __global__ __launch_bounds__(256) void fsea_jobs_upload(const uint32_t *__restrict__ host, uint32_t *__restrict__ table,
+                                                                 uint32_t n_words) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n_words) table[i] = host[i];
+}
 
 namespace fsea_detail {
 
@@ -156,6 +165,15 @@ int SharedScratch::acquire(size_t need, hipStream_t s) {
 
 int SharedScratch::release(hipStream_t s) {
     FSEA_HIP(hipEventRecord(used, s));
+    return FSEA_OK;
+}
+
+int jobs_upload(const void *h_table, void *d_table, uint32_t n_words, hipStream_t s) {
+    void *d_host = nullptr;
+    FSEA_HIP(hipHostGetDevicePointer(&d_host, const_cast<void *>(h_table), 0));
+    hipLaunchKernelGGL(fsea_jobs_upload, dim3((n_words + 255u) / 256u), dim3(256), 0, s, static_cast<const uint32_t *>(d_host),
+                       static_cast<uint32_t *>(d_table), n_words);
+    FSEA_HIP(hipGetLastError());
     return FSEA_OK;
 }
 

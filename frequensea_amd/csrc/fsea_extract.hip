@@ -6,17 +6,20 @@
 // Kernel fsea_extract_u8 ("Event cut-outs"): one workgroup of ZM_WG = 256 lanes per tile of ZM_T = 128
 // outputs of one job; the grid is the sum of the jobs' tiles.  The host turns every job that has an output into a 128-byte
 // record (first, out_first, its first tile, its FirRot with the eight step phasors) and a column of first tiles; a
-// workgroup finds its job by a bisection over that column, `steps` = ceil(log2(records)) <= 16 loads, all of them uniform:
-// scalar loads and SGPRs, and so is the record itself.  From there on it is the zoom's tile (fsea_zoom_image.h): the
+// workgroup finds its job by a bisection over that column (fsea_jobs.h: job_of_tile), `steps` = ceil(log2(records)) <= 16
+// loads, all of them uniform: scalar loads and SGPRs, and so is the record itself.  The table's way to the device and the
+// checks of a job table are fsea_measure's too (fsea_jobs.h).  From there on it is the zoom's tile (fsea_zoom_image.h): the
 // tile's T D + L - 1 rotated samples phase-major in LDS, one FMA chain per output with taps and byte offsets from scalar
 // loads, 8-byte stores, the three static LDS sizes.  What differs is the staging: the groups of eight are aligned to the
 // buffer (first + s a multiple of 8), so that a group inside the job is one 16-byte load whatever first mod 8 is; the two
 // ends go sample by sample, and what lies in front of the job is the zero tail (fsea_fir_stage.h: stage_group_at).  No wave
 // waits for another, no atomics, every loop has its bound on entry.
+#include "fsea_jobs.h"
 #include "fsea_zoom_image.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <string>
 #include <vector>
 
@@ -45,20 +48,7 @@ __device__ __forceinline__ void extract_body(const void *__restrict__ in, uint32
     const int tid = threadIdx.x;
     const uint32_t tile = blockIdx.x;
 
-    // the last record whose first tile is not behind this one: the answer lies in [lo, lo + len), len halves every step
-    int lo = 0, len = n_rec;
-    for (int i = 0; i < steps; ++i) {
-        const int half = len >> 1;
-        if (half) {
-            if (tile0[lo + half] <= tile) {
-                lo += half;
-                len -= half;
-            } else {
-                len = half;
-            }
-        }
-    }
-    const ExtractRec *rec = recs + lo;
+    const ExtractRec *rec = recs + fsea_detail::job_of_tile(tile0, n_rec, steps, tile);
     // the record field by field: uniform, so scalar loads
     FirRot rot;   // delta, phase0 and offset: what rot_base reads
     rot.delta = rec->rot.delta;
@@ -110,56 +100,38 @@ FSEA_EXTRACT_KERNEL(fsea_extract_u8_s, ZM_CAP_S)
 FSEA_EXTRACT_KERNEL(fsea_extract_u8_m, ZM_CAP_M)
 FSEA_EXTRACT_KERNEL(fsea_extract_u8, ZM_CAP_L)
 
-// The records and the first-tile column from the mapped host memory a call built them in to the device table, one word a
-// lane: a launch on the caller's stream in front of the extract kernel, 3.6 us.  A copy engine's transfer there cost two
-// changes of queue, 6 to 10 us more a call (profiles/extract_rate.txt).
-extern "C" __global__ __launch_bounds__(256) void fsea_extract_upload(const uint32_t *__restrict__ host, uint32_t *__restrict__ table,
-                                                                    uint32_t n_words) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n_words) table[i] = host[i];
-}
-
 struct fsea_extract {
     int n_taps = 0;       // the three plain numbers first: the checks of a run read `decimation` and nothing else
     int decimation = 1;
     int device = 0;
     fsea_detail::DeviceArray<float> d_taps;       // ZM_TAPS_ALLOC floats, zeros past n_taps
     fsea_detail::DeviceArray<uint32_t> d_offs;    // ZM_TAPS_ALLOC byte offsets of the taps' samples in the LDS image
-    fsea_detail::SharedScratch table;             // the records and their first-tile column; its event orders the calls
-    fsea_detail::MappedBuffer h_table;            // where a call builds them: mapped, fsea_extract_upload reads it itself
-    fsea_detail::Event copied;                    // recorded behind fsea_extract_upload: the next call waits for it
+    fsea_detail::JobTable table;                  // the records and their first-tile column
     std::mutex mu;
     fsea_detail::HostStaging staging;             // the host form
 };
+static_assert(offsetof(fsea_extract, n_taps) == 0 && offsetof(fsea_extract, decimation) == 4 && offsetof(fsea_extract, device) == 8,
+              "the fake object of tests/test_extract_host.py");
 
 namespace {
-
-constexpr uint64_t EX_MAX_OUTPUTS = (uint64_t)1 << 31;
 
 // Everything a run checks, in the header's order, reading nothing of the object but its decimation.
 int check_run(const fsea_extract *x, const void *iq, size_t n_iq, const fsea_extract_job *jobs, size_t n_jobs, const void *pairs,
               size_t capacity) {
-    if (!x) return fail(FSEA_EINVAL, "extract is NULL");
-    if (n_jobs > FSEA_EXTRACT_MAX_JOBS) return fail(FSEA_EINVAL, "n_jobs %zu above %d", n_jobs, FSEA_EXTRACT_MAX_JOBS);
+    if (int rc = fsea_detail::check_jobs_head(x, "extract", n_jobs, jobs, iq, pairs)) return rc;
     if (n_jobs == 0) return FSEA_OK;
-    if (!jobs) return fail(FSEA_EINVAL, "NULL job table");
-    if (!iq || !pairs) return fail(FSEA_EINVAL, "NULL buffer");
     const uint64_t D = (uint64_t)x->decimation;
     uint64_t total = 0;
     for (size_t i = 0; i < n_jobs; ++i) {
         const fsea_extract_job &j = jobs[i];
-        if (j.n_samples > n_iq || j.first > n_iq - j.n_samples) {
-            return fail(FSEA_EINVAL, "job %zu: samples %llu .. %llu + %llu lie past the %zu of the input", i,
-                        (unsigned long long)j.first, (unsigned long long)j.first, (unsigned long long)j.n_samples, n_iq);
-        }
-        if (j.n_samples > ZM_MAX_SAMPLES) return fail(FSEA_EINVAL, "job %zu: n_samples %llu too large", i, (unsigned long long)j.n_samples);
+        if (int rc = fsea_detail::check_job_span(i, j.first, j.n_samples, n_iq, ZM_MAX_SAMPLES, "samples", "input")) return rc;
         if (check_shift(j.cycles_per_sample, j.phase0_cycles, j.sample_offset, (size_t)j.n_samples)) {
             const std::string why = fsea_last_error_string();
             return fail(FSEA_EINVAL, "job %zu: %s", i, why.c_str());
         }
         total += j.n_samples / D;
     }
-    if (total > EX_MAX_OUTPUTS) return fail(FSEA_EINVAL, "%llu outputs in one call: more than 2^31", (unsigned long long)total);
+    if (int rc = fsea_detail::check_jobs_total(total, "outputs")) return rc;
     std::vector<uint32_t> order;
     for (size_t i = 0; i < n_jobs; ++i) {
         const uint64_t n_out = jobs[i].n_samples / D;
@@ -183,18 +155,16 @@ int check_run(const fsea_extract *x, const void *iq, size_t n_iq, const fsea_ext
     return FSEA_OK;
 }
 
-// One call on device buffers, asynchronous on `s`: the records built in mapped host memory, fsea_extract_upload, the launch.  The caller
-// holds x->mu and is on x's device; the arguments are checked.
+// One call on device buffers, asynchronous on `s`: the records built in mapped host memory, their upload, the launch.  The
+// caller holds x->mu and is on x's device; the arguments are checked.
 int queue_call(fsea_extract *x, const void *d_iq, int flip, const fsea_extract_job *jobs, size_t n_jobs, void *d_pairs, hipStream_t s) {
     const int D = x->decimation, L = x->n_taps;
     size_t n_rec = 0;
     for (size_t i = 0; i < n_jobs; ++i) n_rec += jobs[i].n_samples / (uint64_t)D ? 1 : 0;
     if (n_rec == 0) return FSEA_OK;
     const size_t bytes = n_rec * (sizeof(ExtractRec) + sizeof(uint32_t));
-    FSEA_HIP(hipEventSynchronize(x->copied));   // the previous call's fsea_extract_upload has read the host table
-    int rc = x->h_table.grow(bytes);
-    if (rc) return rc;
-    ExtractRec *recs = static_cast<ExtractRec *>(x->h_table.ptr);
+    ExtractRec *recs = nullptr;
+    if (int rc = x->table.begin(bytes, &recs)) return rc;
     uint32_t *tile0 = reinterpret_cast<uint32_t *>(recs + n_rec);
     uint64_t tiles = 0;
     size_t r = 0;
@@ -205,30 +175,20 @@ int queue_call(fsea_extract *x, const void *d_iq, int flip, const fsea_extract_j
         ExtractRec &rec = recs[r];
         rec.first = (long long)j.first;
         rec.out_first = (long long)j.out_first;
-        rec.tile0 = tile0[r] = (uint32_t)tiles;
+        rec.tile0 = tile0[r] = fsea_detail::job_first_tile(&tiles, n_out, ZM_T);
         rec.pad[0] = rec.pad[1] = rec.pad[2] = 0;
         rec.rot = make_rot(j.cycles_per_sample, j.phase0_cycles, j.sample_offset, (size_t)j.n_samples);
-        tiles += (n_out + ZM_T - 1) / ZM_T;   // <= 2^31 / ZM_T + 65536 in all
         ++r;
     }
-    int steps = 0;
-    while (((size_t)1 << steps) < n_rec) ++steps;
-    // every call, on whatever stream, follows the previous user of the device table
-    rc = x->table.acquire(bytes, s);
-    if (rc) return rc;
-    void *d_host = nullptr;
-    FSEA_HIP(hipHostGetDevicePointer(&d_host, recs, 0));
-    const uint32_t n_words = (uint32_t)(bytes / sizeof(uint32_t));   // <= 65536 * 33
-    hipLaunchKernelGGL(fsea_extract_upload, dim3((n_words + 255u) / 256u), dim3(256), 0, s, static_cast<const uint32_t *>(d_host),
-                       static_cast<uint32_t *>(x->table.buf.ptr), n_words);
-    FSEA_HIP(hipGetLastError());
-    FSEA_HIP(hipEventRecord(x->copied, s));
-    const ExtractRec *d_recs = static_cast<const ExtractRec *>(x->table.buf.ptr);
+    uint8_t *base = nullptr;
+    if (int rc = x->table.queue(bytes, bytes, s, &base)) return rc;
+    const ExtractRec *d_recs = reinterpret_cast<const ExtractRec *>(base);
     const uint32_t *d_tile0 = reinterpret_cast<const uint32_t *>(d_recs + n_rec);
     const int need = zoom_lds_samples(D, L);
     auto kernel = need <= ZM_CAP_S ? fsea_extract_u8_s : need <= ZM_CAP_M ? fsea_extract_u8_m : fsea_extract_u8;
     hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(ZM_WG), 0, s, d_iq, flip ? 0x80808080u : 0u, d_recs, d_tile0, (int)n_rec,
-                       steps, (const float *)x->d_taps.ptr, (const uint32_t *)x->d_offs.ptr, L, D, static_cast<cf *>(d_pairs));
+                       fsea_detail::job_steps(n_rec), (const float *)x->d_taps.ptr, (const uint32_t *)x->d_offs.ptr, L, D,
+                       static_cast<cf *>(d_pairs));
     FSEA_HIP(hipGetLastError());
     return x->table.release(s);
 }
@@ -254,8 +214,6 @@ int fsea_extract_create(fsea_extract **out, const double *taps, int n_taps, int 
         hipError_t e = x->d_taps.upload(tf, ZM_TAPS_ALLOC);
         if (e == hipSuccess) e = x->d_offs.upload(offs, ZM_TAPS_ALLOC);
         if (e == hipSuccess) e = x->table.create(x->staging.stream);
-        if (e == hipSuccess) e = x->copied.create();
-        if (e == hipSuccess) e = hipEventRecord(x->copied, x->staging.stream);
         return e;
     });
 }
@@ -277,7 +235,7 @@ size_t fsea_extract_lead(int n_taps, int decimation) {
 int fsea_extract_layout(const fsea_extract *x, fsea_extract_job *jobs, size_t n_jobs, size_t *total_pairs) {
     if (!x) return fail(FSEA_EINVAL, "extract is NULL");
     if (!total_pairs) return fail(FSEA_EINVAL, "total_pairs is NULL");
-    if (n_jobs > FSEA_EXTRACT_MAX_JOBS) return fail(FSEA_EINVAL, "n_jobs %zu above %d", n_jobs, FSEA_EXTRACT_MAX_JOBS);
+    if (int rc = fsea_detail::check_jobs_count(n_jobs)) return rc;
     if (n_jobs && !jobs) return fail(FSEA_EINVAL, "NULL job table");
     uint64_t at = 0;
     for (size_t i = 0; i < n_jobs; ++i) {

@@ -6,8 +6,9 @@
 //
 // Kernel fsea_measure_tiles ("Signal measures"): one workgroup of MS_WG = 256 lanes per tile of
 // MS_TILE = 4096 pairs of one job; the grid is the sum of the jobs' tiles.  The device table is the caller's jobs as they are
-// and a column of first tiles; a workgroup finds its job by a bisection over that column, `steps` = ceil(log2(jobs)) <= 16
-// loads, uniform, so scalar loads and SGPRs, and so is the job itself.  A job without pairs has its successor's first tile
+// and a column of first tiles, brought there as fsea_extract's (fsea_jobs.h: JobTable); a workgroup finds its job by a
+// bisection over that column (job_of_tile), `steps` = ceil(log2(jobs)) <= 16 loads, uniform, so scalar loads and SGPRs, and
+// so is the job itself.  A job without pairs has its successor's first tile
 // and the bisection ends at the last job whose first tile is not behind the workgroup's: never at an empty one.  Lane l
 // takes pairs l, l + 256, ... of the tile: sixteen 8-byte loads, a wave's 64 of them 512 contiguous bytes at any parity of
 // first_pair, and sixteen more for the lagged partners (the same lines `lag` pairs earlier, cache hits), all issued in
@@ -17,7 +18,7 @@
 // last two stages (k = 64, 128) over the four waves' values in LDS; lanes 0 .. 7 store the tile's partial, 8 bytes each.
 // Kernel fsea_measure_fold: one wave per job runs fold_64 over the job's partials and stores the 80-byte record.  No float
 // atomics, no wave waits for another, every loop has its bound on entry.
-#include "fsea_internal.h"
+#include "fsea_jobs.h"
 
 #include <algorithm>
 #include <cmath>
@@ -139,19 +140,7 @@ extern "C" __global__ __launch_bounds__(MS_WG, 4) void fsea_measure_tiles(const 
     const unsigned tid = threadIdx.x;
     const uint32_t tile = blockIdx.x;
 
-    // the last job whose first tile is not behind this one: the answer lies in [lo, lo + len), len halves every step
-    int lo = 0, len = n_jobs;
-    for (int i = 0; i < steps; ++i) {
-        const int half = len >> 1;
-        if (half) {
-            if (tile0[lo + half] <= tile) {
-                lo += half;
-                len -= half;
-            } else {
-                len = half;
-            }
-        }
-    }
+    const int lo = fsea_detail::job_of_tile(tile0, n_jobs, steps, tile);
     const unsigned long long first = jobs[lo].first_pair, n = jobs[lo].n_pairs;
     const unsigned i0 = (tile - tile0[lo]) * (unsigned)MS_TILE;    // the tile's first pair, counted from the job's: below 2^24
     const unsigned left = (unsigned)n - i0;                         // pairs from there on: at least 1
@@ -212,93 +201,59 @@ extern "C" __global__ __launch_bounds__(64) void fsea_measure_fold(const fsea_me
     }
 }
 
-// The jobs and the first-tile column from the mapped host memory a call built them in to the device table, one word a lane,
-// on the caller's stream in front of the two kernels (as fsea_extract_upload: profiles/extract_rate.txt).
-extern "C" __global__ __launch_bounds__(256) void fsea_measure_upload(const uint32_t *__restrict__ host, uint32_t *__restrict__ table,
-                                                                    uint32_t n_words) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n_words) table[i] = host[i];
-}
-
 struct fsea_measure {
     int device = 0;
-    fsea_detail::SharedScratch scratch;   // the jobs, their first-tile column, the tile partials; its event orders the calls
-    fsea_detail::MappedBuffer h_table;    // where a call builds the first two: mapped, fsea_measure_upload reads it itself
-    fsea_detail::Event copied;            // recorded behind fsea_measure_upload: the next call waits for it
+    fsea_detail::JobTable table;          // the jobs and their first-tile column; behind them in its scratch, the tile partials
     std::mutex mu;
     fsea_detail::HostStaging staging;     // the host form
 };
 
 namespace {
 
-constexpr uint64_t MS_MAX_CALL_PAIRS = (uint64_t)1 << 31;
-
 // Everything a run checks, in the header's order, reading nothing of the object.
 int check_run(const fsea_measure *m, const void *pairs, size_t n_buffer_pairs, const fsea_measure_job *jobs, size_t n_jobs,
               double offset_re, double offset_im, int lag, const void *sums) {
-    if (!m) return fail(FSEA_EINVAL, "measure is NULL");
-    if (n_jobs > FSEA_MEASURE_MAX_JOBS) return fail(FSEA_EINVAL, "n_jobs %zu above %d", n_jobs, FSEA_MEASURE_MAX_JOBS);
+    if (int rc = fsea_detail::check_jobs_head(m, "measure", n_jobs, jobs, pairs, sums)) return rc;
     if (n_jobs == 0) return FSEA_OK;
-    if (!jobs) return fail(FSEA_EINVAL, "NULL job table");
-    if (!pairs || !sums) return fail(FSEA_EINVAL, "NULL buffer");
     if (lag < 1 || lag > FSEA_MEASURE_MAX_LAG) return fail(FSEA_EINVAL, "lag must be in [1, %d], got %d", FSEA_MEASURE_MAX_LAG, lag);
     if (!std::isfinite(offset_re) || !std::isfinite(offset_im)) return fail(FSEA_EINVAL, "the offset is not finite");
     uint64_t total = 0;
     for (size_t i = 0; i < n_jobs; ++i) {
         const fsea_measure_job &j = jobs[i];
-        if (j.n_pairs > n_buffer_pairs || j.first_pair > n_buffer_pairs - j.n_pairs) {
-            return fail(FSEA_EINVAL, "job %zu: pairs %llu .. %llu + %llu lie past the %zu of the buffer", i,
-                        (unsigned long long)j.first_pair, (unsigned long long)j.first_pair, (unsigned long long)j.n_pairs, n_buffer_pairs);
-        }
-        if (j.n_pairs > FSEA_MEASURE_MAX_PAIRS) return fail(FSEA_EINVAL, "job %zu: n_pairs %llu too large", i, (unsigned long long)j.n_pairs);
+        if (int rc = fsea_detail::check_job_span(i, j.first_pair, j.n_pairs, n_buffer_pairs, FSEA_MEASURE_MAX_PAIRS, "pairs", "buffer")) return rc;
         total += j.n_pairs;
     }
-    if (total > MS_MAX_CALL_PAIRS) return fail(FSEA_EINVAL, "%llu pairs in one call: more than 2^31", (unsigned long long)total);
-    return FSEA_OK;
+    return fsea_detail::check_jobs_total(total, "pairs");
 }
 
-// One call on device buffers, asynchronous on `s`: the table built in mapped host memory, fsea_measure_upload, the tiles, the
-// fold.  The caller holds m->mu and is on m's device; the arguments are checked and n_jobs is at least 1.
+// One call on device buffers, asynchronous on `s`: the table built in mapped host memory, its upload, the tiles, the fold.
+// The caller holds m->mu and is on m's device; the arguments are checked and n_jobs is at least 1.
 int queue_call(fsea_measure *m, const void *d_pairs, const fsea_measure_job *jobs, size_t n_jobs, double offset_re, double offset_im,
                int lag, fsea_measure_sums *d_sums, hipStream_t s) {
     const size_t table_bytes = n_jobs * (sizeof(fsea_measure_job) + sizeof(uint32_t));
     const size_t partials_at = (table_bytes + 63) & ~(size_t)63;
-    FSEA_HIP(hipEventSynchronize(m->copied));   // the previous call's fsea_measure_upload has read the host table
-    int rc = m->h_table.grow(table_bytes);
-    if (rc) return rc;
-    fsea_measure_job *h_jobs = static_cast<fsea_measure_job *>(m->h_table.ptr);
+    fsea_measure_job *h_jobs = nullptr;
+    if (int rc = m->table.begin(table_bytes, &h_jobs)) return rc;
     uint32_t *h_tile0 = reinterpret_cast<uint32_t *>(h_jobs + n_jobs);
     uint64_t tiles = 0;
     for (size_t i = 0; i < n_jobs; ++i) {
         h_jobs[i] = jobs[i];
-        h_tile0[i] = (uint32_t)tiles;
-        tiles += (jobs[i].n_pairs + MS_TILE - 1) / MS_TILE;   // <= 2^31 / MS_TILE + 65536 in all
+        h_tile0[i] = fsea_detail::job_first_tile(&tiles, jobs[i].n_pairs, MS_TILE);
     }
-    int steps = 0;
-    while (((size_t)1 << steps) < n_jobs) ++steps;
-    // every call, on whatever stream, follows the previous user of the device table and the partials
-    rc = m->scratch.acquire(partials_at + (size_t)tiles * sizeof(Partial), s);
-    if (rc) return rc;
-    void *d_host = nullptr;
-    FSEA_HIP(hipHostGetDevicePointer(&d_host, h_jobs, 0));
-    const uint32_t n_words = (uint32_t)(table_bytes / sizeof(uint32_t));   // <= 65536 * 5
-    uint8_t *base = static_cast<uint8_t *>(m->scratch.buf.ptr);
-    hipLaunchKernelGGL(fsea_measure_upload, dim3((n_words + 255u) / 256u), dim3(256), 0, s, static_cast<const uint32_t *>(d_host),
-                       reinterpret_cast<uint32_t *>(base), n_words);
-    FSEA_HIP(hipGetLastError());
-    FSEA_HIP(hipEventRecord(m->copied, s));
+    uint8_t *base = nullptr;
+    if (int rc = m->table.queue(table_bytes, partials_at + (size_t)tiles * sizeof(Partial), s, &base)) return rc;
     const fsea_measure_job *d_jobs = reinterpret_cast<const fsea_measure_job *>(base);
     const uint32_t *d_tile0 = reinterpret_cast<const uint32_t *>(d_jobs + n_jobs);
     Partial *d_partials = reinterpret_cast<Partial *>(base + partials_at);
     if (tiles) {
         hipLaunchKernelGGL(fsea_measure_tiles, dim3((unsigned)tiles), dim3(MS_WG), 0, s, static_cast<const float2 *>(d_pairs), d_jobs,
-                           d_tile0, (int)n_jobs, steps, offset_re, offset_im, lag, d_partials);
+                           d_tile0, (int)n_jobs, fsea_detail::job_steps(n_jobs), offset_re, offset_im, lag, d_partials);
         FSEA_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(fsea_measure_fold, dim3((unsigned)n_jobs), dim3(64), 0, s, d_jobs, d_tile0, static_cast<const Partial *>(d_partials),
                        lag, d_sums);
     FSEA_HIP(hipGetLastError());
-    return m->scratch.release(s);
+    return m->table.release(s);
 }
 
 }  // namespace
@@ -308,12 +263,8 @@ extern "C" {
 int fsea_measure_create(fsea_measure **out, int device) {
     if (!out) return fail(FSEA_EINVAL, "measure out-pointer is NULL");
     *out = nullptr;
-    return fsea_detail::create_object(out, device, "fsea_measure_create", [&](fsea_measure *m) -> hipError_t {
-        hipError_t e = m->scratch.create(m->staging.stream);
-        if (e == hipSuccess) e = m->copied.create();
-        if (e == hipSuccess) e = hipEventRecord(m->copied, m->staging.stream);
-        return e;
-    });
+    return fsea_detail::create_object(out, device, "fsea_measure_create",
+                                      [&](fsea_measure *m) -> hipError_t { return m->table.create(m->staging.stream); });
 }
 
 int fsea_measure_destroy(fsea_measure *m) { return fsea_detail::destroy_object(m); }
@@ -348,7 +299,7 @@ int fsea_measure_run_host(fsea_measure *m, const float *pairs, size_t n_buffer_p
 }
 
 int fsea_measure_jobs(const fsea_extract_job *ejobs, size_t n_jobs, int decimation, size_t skip_pairs, fsea_measure_job *jobs) {
-    if (n_jobs > FSEA_MEASURE_MAX_JOBS) return fail(FSEA_EINVAL, "n_jobs %zu above %d", n_jobs, FSEA_MEASURE_MAX_JOBS);
+    if (int rc = fsea_detail::check_jobs_count(n_jobs)) return rc;
     if (n_jobs && (!ejobs || !jobs)) return fail(FSEA_EINVAL, "NULL job table");
     if (decimation < 1) return fail(FSEA_EINVAL, "decimation must be at least 1, got %d", decimation);
     for (size_t i = 0; i < n_jobs; ++i) {

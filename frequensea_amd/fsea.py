@@ -1010,17 +1010,21 @@ def extract_jobs(events, width, hop, n_samples, n_taps, decimation, max_fill=0.8
     jobs = (ExtractJob * e.size)()
     fits = np.zeros(e.size, dtype=np.uint8)
     _check(hip_lib().fsea_extract_jobs(e.ctypes.data if e.size else None, e.size, int(width), int(hop), int(n_samples), int(n_taps),
-                                       int(decimation), float(max_fill), ctypes.addressof(jobs) if e.size else None,
-                                       fits.ctypes.data if e.size else None))
+                                       int(decimation), float(max_fill), _address(jobs), fits.ctypes.data if e.size else None))
     return jobs, fits
 
 
-def _job_table(jobs):
-    """a sequence of ExtractJob as one ctypes array (a ctypes array of them passes through)"""
-    if isinstance(jobs, ctypes.Array) and jobs._type_ is ExtractJob:
+def _table_of(kind, jobs):
+    """a sequence of `kind` records as one ctypes array (a ctypes array of them passes through)"""
+    if isinstance(jobs, ctypes.Array) and jobs._type_ is kind:
         return jobs
     jobs = list(jobs)
-    return (ExtractJob * len(jobs))(*jobs)
+    return (kind * len(jobs))(*jobs)
+
+
+def _address(array):
+    """the address of a ctypes array, None for an empty one"""
+    return ctypes.addressof(array) if len(array) else None
 
 
 class Extract(_Handle):
@@ -1039,9 +1043,9 @@ class Extract(_Handle):
 
     def layout(self, jobs):
         """fsea_extract_layout: (the jobs as a ctypes array with out_first filled in, the pairs they need in all)."""
-        table = _job_table(jobs)
+        table = _table_of(ExtractJob, jobs)
         total = ctypes.c_size_t()
-        _check(self._L.fsea_extract_layout(self._p, ctypes.addressof(table) if len(table) else None, len(table), ctypes.byref(total)))
+        _check(self._L.fsea_extract_layout(self._p, _address(table), len(table), ctypes.byref(total)))
         return table, total.value
 
     def run(self, iq_u8, jobs, flip=False):
@@ -1049,34 +1053,24 @@ class Extract(_Handle):
         iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
         table, total = self.layout([ExtractJob.from_buffer_copy(j) for j in jobs])
         pairs = np.zeros(max(total, 1), dtype=np.complex64)
-        _check(self._L.fsea_extract_run_host(self._p, iq.ctypes.data, iq.size // 2, int(bool(flip)),
-                                             ctypes.addressof(table) if len(table) else None, len(table), pairs.ctypes.data, total))
+        _check(self._L.fsea_extract_run_host(self._p, iq.ctypes.data, iq.size // 2, int(bool(flip)), _address(table), len(table),
+                                             pairs.ctypes.data, total))
         return [pairs[j.out_first:j.out_first + j.n_samples // self.decimation].copy() for j in table]
 
     def run_device(self, d_iq_ptr, n_iq_samples, jobs, d_pairs_ptr, pairs_capacity, flip=False, stream=0):
         """Device pointers (ints, 16-byte aligned): 2 * n_iq_samples bytes in, pairs_capacity complex64 out, every job at its
         own out_first; asynchronous.  The jobs are read before the call returns."""
-        table = _job_table(jobs)
-        _check(self._L.fsea_extract_run_device(self._p, d_iq_ptr or None, n_iq_samples, int(bool(flip)),
-                                               ctypes.addressof(table) if len(table) else None, len(table), d_pairs_ptr or None,
-                                               pairs_capacity, stream or None))
-
-
-def _table_of(kind, jobs):
-    """a sequence of `kind` records as one ctypes array (a ctypes array of them passes through)"""
-    if isinstance(jobs, ctypes.Array) and jobs._type_ is kind:
-        return jobs
-    jobs = list(jobs)
-    return (kind * len(jobs))(*jobs)
+        table = _table_of(ExtractJob, jobs)
+        _check(self._L.fsea_extract_run_device(self._p, d_iq_ptr or None, n_iq_samples, int(bool(flip)), _address(table), len(table),
+                                               d_pairs_ptr or None, pairs_capacity, stream or None))
 
 
 def measure_jobs(extract_jobs_laid_out, decimation, skip_pairs=0):
     """fsea_measure_jobs (host arithmetic): the spans of the outputs of extract jobs that Extract.layout laid out, each
     without its first skip_pairs pairs, as a ctypes array of MeasureJob."""
-    table = _job_table(extract_jobs_laid_out)
+    table = _table_of(ExtractJob, extract_jobs_laid_out)
     jobs = (MeasureJob * len(table))()
-    _check(hip_lib().fsea_measure_jobs(ctypes.addressof(table) if len(table) else None, len(table), int(decimation), int(skip_pairs),
-                                       ctypes.addressof(jobs) if len(table) else None))
+    _check(hip_lib().fsea_measure_jobs(_address(table), len(table), int(decimation), int(skip_pairs), _address(jobs)))
     return jobs
 
 
@@ -1102,8 +1096,8 @@ class Measure(_Handle):
         table = _table_of(MeasureJob, jobs)
         sums = (MeasureSums * len(table))()
         offset = complex(offset)
-        _check(self._L.fsea_measure_run_host(self._p, z.ctypes.data, z.size, ctypes.addressof(table) if len(table) else None, len(table),
-                                             offset.real, offset.imag, int(lag), ctypes.addressof(sums) if len(table) else None))
+        _check(self._L.fsea_measure_run_host(self._p, z.ctypes.data, z.size, _address(table), len(table), offset.real, offset.imag,
+                                             int(lag), _address(sums)))
         return sums
 
     def run_device(self, d_pairs_ptr, n_buffer_pairs, jobs, d_sums_ptr, offset=0j, lag=1, stream=0):
@@ -1111,8 +1105,8 @@ class Measure(_Handle):
         aligned); asynchronous.  The jobs are read before the call returns."""
         table = _table_of(MeasureJob, jobs)
         offset = complex(offset)
-        _check(self._L.fsea_measure_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, ctypes.addressof(table) if len(table) else None,
-                                               len(table), offset.real, offset.imag, int(lag), d_sums_ptr or None, stream or None))
+        _check(self._L.fsea_measure_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, _address(table), len(table), offset.real,
+                                               offset.imag, int(lag), d_sums_ptr or None, stream or None))
 
 
 class Demod(_ResettableHandle):

@@ -4,7 +4,7 @@
  *
  * Pass 1 is fsea-events' for a recording: every frame of N samples (one every H) through a plan in a dB mode, the rows to a
  * fsea_cfar object with a mask, mask and rows to a fsea_events object, all on the device chunk by chunk; the runs are kept
- * on the host and linked once at the end.  Pass 2 turns the first --max-events surviving events into jobs with
+ * on the host and linked once at the end (tool_common.h).  Pass 2 turns the first --max-events surviving events into jobs with
  * fsea_extract_jobs (include/fsea.h): a job begins fsea_extract_lead samples in front of its box, so that the filter has run
  * in where the box begins, and ends with the last frame of the box; a job longer than --max-samples is cut short.  The jobs
  * are grouped into batches whose samples total at most 64 MiB; the byte ranges of a batch are read from the file into one
@@ -63,20 +63,10 @@ static void usage_error(const char *msg) { tool_usage_error(TOOL, msg); }
 
 static void die(const char *what) { tool_die(TOOL, what); }
 
-/* all runs of the input, in order */
-static fsea_events_run *g_runs = NULL;
-static size_t g_n_runs = 0, g_cap_runs = 0;
-
-static fsea_events_run *runs_room(size_t more) {
-    if (g_n_runs + more > g_cap_runs) {
-        size_t cap = g_cap_runs ? g_cap_runs : 1024;
-        while (cap < g_n_runs + more) cap *= 2;
-        fsea_events_run *grown = (fsea_events_run *)realloc(g_runs, cap * sizeof(fsea_events_run));
-        if (grown == NULL) usage_error("out of memory");
-        g_runs = grown;
-        g_cap_runs = cap;
-    }
-    return g_runs + g_n_runs;
+/* a file of the output that could not be written, for main's exit status */
+static int cannot_write(const char *name) {
+    fprintf(stderr, TOOL ": cannot write %s\n", name);
+    return EXIT_FAILURE;
 }
 
 int main(int argc, char **argv) {
@@ -145,50 +135,12 @@ int main(int argc, char **argv) {
     fsea_events *events = NULL;
     if (fsea_events_create(&events, size, 0) != FSEA_OK) die("fsea_events_create");
     if (fsea_events_set_gap(events, gap_cols) != FSEA_OK) die("fsea_events_set_gap");
-    const size_t n = (size_t)size;
-    void *d_rows = src.d_rows, *d_mask = NULL, *d_runs = NULL;
-    size_t d_runs_cap = 0, done = 0;
-    if (fsea_device_alloc(0, src.frames_max * n, &d_mask) != FSEA_OK) die("fsea_device_alloc");
-    for (size_t frames; (frames = tool_rows_next(&src)) > 0; done += frames) {
-        if (fsea_cfar_add_device(cfar, d_rows, type, frames, n, (uint8_t *)d_mask, NULL, NULL) != FSEA_OK) die("fsea_cfar_add_device");
-        size_t found = 0;
-        if (fsea_events_reset(events) != FSEA_OK) die("fsea_events_reset");
-        if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, NULL, 0, &found, NULL) != FSEA_OK) {
-            die("fsea_events_runs_device");
-        }
-        if (found == 0) continue;
-        if (found > d_runs_cap) {
-            if (d_runs != NULL) fsea_device_free(0, d_runs);
-            d_runs_cap = found + found / 2;
-            if (fsea_device_alloc(0, d_runs_cap * sizeof(fsea_events_run), &d_runs) != FSEA_OK) die("fsea_device_alloc");
-        }
-        if (fsea_events_reset(events) != FSEA_OK) die("fsea_events_reset");
-        if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, (fsea_events_run *)d_runs, found, &found,
-                                    NULL) != FSEA_OK) {
-            die("fsea_events_runs_device");
-        }
-        fsea_events_run *dst = runs_room(found);
-        if (fsea_copy_to_host(0, dst, d_runs, found * sizeof(fsea_events_run)) != FSEA_OK) die("fsea_copy_to_host");
-        if (done + frames > 0xffffffffull) usage_error("the recording holds more than 2^32 - 1 frames");
-        for (size_t i = 0; i < found; i++) dst[i].row += (uint32_t)done;
-        g_n_runs += found;
-    }
+    tool_run_list runs = {NULL, 0, 0};
+    const size_t done = tool_recording_runs(TOOL, &src, cfar, events, type, &runs);
     tool_rows_close(&src);
-    fsea_device_free(0, d_mask);
-    if (d_runs != NULL) fsea_device_free(0, d_runs);
     if (done < 1) return tool_rows_none(TOOL, path, size);
-
     size_t n_events = 0;
-    if (fsea_events_link(g_runs, g_n_runs, gap_cols, gap_rows, (uint32_t)min_rows, (uint32_t)min_cols, (uint64_t)min_hits, NULL, NULL, 0,
-                         &n_events) != FSEA_OK) {
-        die("fsea_events_link");
-    }
-    fsea_events_event *found_events = (fsea_events_event *)malloc(sizeof(fsea_events_event) * (n_events + 1));
-    if (found_events == NULL) usage_error("out of memory");
-    if (fsea_events_link(g_runs, g_n_runs, gap_cols, gap_rows, (uint32_t)min_rows, (uint32_t)min_cols, (uint64_t)min_hits, NULL,
-                         found_events, n_events, &n_events) != FSEA_OK) {
-        die("fsea_events_link");
-    }
+    fsea_events_event *found_events = tool_link(TOOL, &runs, gap_cols, gap_rows, min_rows, min_cols, min_hits, NULL, &n_events);
 
     /* pass 2: the first max_events events as jobs */
     FILE *fp = fopen(path, "rb");
@@ -297,8 +249,7 @@ int main(int argc, char **argv) {
             const size_t keep = n_out - lead_out;
             if (out == NULL || fwrite(h_pairs + 2 * ((size_t)batch[b].out_first + lead_out), 2 * sizeof(float), keep, out) != keep ||
                 fclose(out) != 0) {
-                fprintf(stderr, TOOL ": cannot write %s\n", name);
-                return EXIT_FAILURE;
+                return cannot_write(name);
             }
             written[e] = keep;
             n_cutouts++;
@@ -307,10 +258,7 @@ int main(int argc, char **argv) {
 
     snprintf(name, name_len, "%s/cutouts.txt", out_dir);
     FILE *list = fopen(name, "w");
-    if (list == NULL) {
-        fprintf(stderr, TOOL ": cannot write %s\n", name);
-        return EXIT_FAILURE;
-    }
+    if (list == NULL) return cannot_write(name);
     for (size_t e = 0; e < n_events; e++) {
         const fsea_events_event *ev = &found_events[e];
         const int listed = e < n_jobs;
@@ -319,34 +267,25 @@ int main(int argc, char **argv) {
                 ev->col_last, listed ? (unsigned long long)jobs[e].first : 0ull, listed ? (unsigned long long)jobs[e].n_samples : 0ull, mhz,
                 rate / (double)decimation, written[e], listed ? (int)fits[e] : 0, listed ? (int)cut[e] : 0);
     }
-    if (fclose(list) != 0) {
-        fprintf(stderr, TOOL ": cannot write %s\n", name);
-        return EXIT_FAILURE;
-    }
+    if (fclose(list) != 0) return cannot_write(name);
     if (measures) {
         snprintf(name, name_len, "%s/measures.txt", out_dir);
         FILE *table = fopen(name, "w");
-        if (table == NULL) {
-            fprintf(stderr, TOOL ": cannot write %s\n", name);
-            return EXIT_FAILURE;
-        }
+        if (table == NULL) return cannot_write(name);
         for (size_t e = 0; e < n_jobs; e++) {
             const fsea_measure_result *r = &measured[e];
             if (written[e] == 0) continue;
             fprintf(table, "%u %zu %.9e %.9e %.9e %.9e %.9e %.9e %.9e %.9e\n", (unsigned)e, written[e], r->power_db, r->freq_cycles,
                     r->freq_cycles * rate / (double)decimation / 1e6, r->width_cycles, r->kurtosis, r->crest, r->dc_re, r->dc_im);
         }
-        if (fclose(table) != 0) {
-            fprintf(stderr, TOOL ": cannot write %s\n", name);
-            return EXIT_FAILURE;
-        }
+        if (fclose(table) != 0) return cannot_write(name);
         fsea_measure_destroy(measure);
         fsea_device_free(0, d_sums);
         free(measured);
         free(spans);
         free(h_sums);
     }
-    printf("rows %zu runs %zu events %zu cutouts %zu skipped %zu\n", done, g_n_runs, n_events, n_cutouts, n_events - n_cutouts);
+    printf("rows %zu runs %zu events %zu cutouts %zu skipped %zu\n", done, runs.n, n_events, n_cutouts, n_events - n_cutouts);
 
     fsea_extract_destroy(extract);
     fsea_events_destroy(events);
@@ -365,6 +304,6 @@ int main(int argc, char **argv) {
     free(written);
     free(taps);
     free(found_events);
-    free(g_runs);
+    free(runs.runs);
     return 0;
 }

@@ -48,22 +48,6 @@ static void usage_error(const char *msg) { tool_usage_error("fsea-events", msg);
 
 static void die(const char *what) { tool_die("fsea-events", what); }
 
-/* all runs of the input, in order */
-static fsea_events_run *g_runs = NULL;
-static size_t g_n_runs = 0, g_cap_runs = 0;
-
-static fsea_events_run *runs_room(size_t more) {
-    if (g_n_runs + more > g_cap_runs) {
-        size_t cap = g_cap_runs ? g_cap_runs : 1024;
-        while (cap < g_n_runs + more) cap *= 2;
-        fsea_events_run *grown = (fsea_events_run *)realloc(g_runs, cap * sizeof(fsea_events_run));
-        if (grown == NULL) usage_error("out of memory");
-        g_runs = grown;
-        g_cap_runs = cap;
-    }
-    return g_runs + g_n_runs;
-}
-
 int main(int argc, char **argv) {
     const char *path = NULL, *paint_path = NULL, *window = "rect", *mode_name = "db5";
     int size = 0, hop = 0, flip = 0, gap_cols = 0, gap_rows = 0;
@@ -106,10 +90,9 @@ int main(int argc, char **argv) {
     int mode = 0, type = 0;
     if (!tool_rows_mode(mode_name, "db", &mode, &type)) usage_error("--mode must be db5, db10 or db");
 
-    /* The object counts the rows of every call; the tool counts its own (`done`) and has the object start each chunk at row
-     * 0, so that a chunk can be asked twice: once for the number of its runs, once for the records. */
     fsea_cfar *cfar = NULL;
     fsea_events *events = NULL;
+    tool_run_list list = {NULL, 0, 0};   /* all runs of the input, in order */
     int width = size;
     size_t done = 0;
     if (image_path != NULL) {
@@ -124,10 +107,9 @@ int main(int argc, char **argv) {
         size_t found = 0;
         if (fsea_events_runs_host(events, mask, w, image, FSEA_CFAR_U8, w, h, NULL, 0, &found) != FSEA_OK) die("fsea_events_runs_host");
         if (fsea_events_reset(events) != FSEA_OK) die("fsea_events_reset");
-        if (fsea_events_runs_host(events, mask, w, image, FSEA_CFAR_U8, w, h, runs_room(found), found, &found) != FSEA_OK) {
-            die("fsea_events_runs_host");
-        }
-        g_n_runs = found;
+        fsea_events_run *dst = tool_runs_room("fsea-events", &list, found);
+        if (fsea_events_runs_host(events, mask, w, image, FSEA_CFAR_U8, w, h, dst, found, &found) != FSEA_OK) die("fsea_events_runs_host");
+        list.n = found;
         done = h;
         free(mask);
         free(image);
@@ -137,39 +119,8 @@ int main(int argc, char **argv) {
         cfar = tool_detector_create("fsea-events", &det, size);
         if (fsea_events_create(&events, size, 0) != FSEA_OK) die("fsea_events_create");
         if (fsea_events_set_gap(events, gap_cols) != FSEA_OK) die("fsea_events_set_gap");
-        const size_t n = (size_t)size;
-        void *d_rows = src.d_rows, *d_mask = NULL, *d_runs = NULL;
-        size_t d_runs_cap = 0;
-        if (fsea_device_alloc(0, src.frames_max * n, &d_mask) != FSEA_OK) die("fsea_device_alloc");
-        /* rows and mask stay on the device between the plan, the detector and the runs; everything on the null stream */
-        for (size_t frames; (frames = tool_rows_next(&src)) > 0; done += frames) {
-            if (fsea_cfar_add_device(cfar, d_rows, type, frames, n, (uint8_t *)d_mask, NULL, NULL) != FSEA_OK) die("fsea_cfar_add_device");
-            size_t found = 0;
-            if (fsea_events_reset(events) != FSEA_OK) die("fsea_events_reset");
-            if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, NULL, 0, &found, NULL) != FSEA_OK) {
-                die("fsea_events_runs_device");
-            }
-            if (found > 0) {
-                if (found > d_runs_cap) {
-                    if (d_runs != NULL) fsea_device_free(0, d_runs);
-                    d_runs_cap = found + found / 2;
-                    if (fsea_device_alloc(0, d_runs_cap * sizeof(fsea_events_run), &d_runs) != FSEA_OK) die("fsea_device_alloc");
-                }
-                if (fsea_events_reset(events) != FSEA_OK) die("fsea_events_reset");
-                if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, (fsea_events_run *)d_runs, found,
-                                            &found, NULL) != FSEA_OK) {
-                    die("fsea_events_runs_device");
-                }
-                fsea_events_run *dst = runs_room(found);
-                if (fsea_copy_to_host(0, dst, d_runs, found * sizeof(fsea_events_run)) != FSEA_OK) die("fsea_copy_to_host");
-                if (done + frames > 0xffffffffull) usage_error("the recording holds more than 2^32 - 1 frames");
-                for (size_t i = 0; i < found; i++) dst[i].row += (uint32_t)done;
-                g_n_runs += found;
-            }
-        }
+        done = tool_recording_runs("fsea-events", &src, cfar, events, type, &list);
         tool_rows_close(&src);
-        fsea_device_free(0, d_mask);
-        if (d_runs != NULL) fsea_device_free(0, d_runs);
     }
     if (done < 1) {
         if (image_path != NULL) fprintf(stderr, "fsea-events: image %s has no rows\n", image_path);
@@ -178,20 +129,11 @@ int main(int argc, char **argv) {
     }
 
     /* one link over all runs of the input */
-    uint32_t *event_of_run = (uint32_t *)malloc(sizeof(uint32_t) * (g_n_runs + 1));
+    uint32_t *event_of_run = (uint32_t *)malloc(sizeof(uint32_t) * (list.n + 1));
     if (event_of_run == NULL) usage_error("out of memory");
     size_t n_events = 0;
-    if (fsea_events_link(g_runs, g_n_runs, gap_cols, gap_rows, (uint32_t)min_rows, (uint32_t)min_cols, (uint64_t)min_hits, NULL, NULL, 0,
-                         &n_events) != FSEA_OK) {
-        die("fsea_events_link");
-    }
-    fsea_events_event *found_events = (fsea_events_event *)malloc(sizeof(fsea_events_event) * (n_events + 1));
-    if (found_events == NULL) usage_error("out of memory");
-    if (fsea_events_link(g_runs, g_n_runs, gap_cols, gap_rows, (uint32_t)min_rows, (uint32_t)min_cols, (uint64_t)min_hits, event_of_run,
-                         found_events, n_events, &n_events) != FSEA_OK) {
-        die("fsea_events_link");
-    }
-    printf("rows %zu runs %zu events %zu\n", done, g_n_runs, n_events);
+    fsea_events_event *found_events = tool_link("fsea-events", &list, gap_cols, gap_rows, min_rows, min_cols, min_hits, event_of_run, &n_events);
+    printf("rows %zu runs %zu events %zu\n", done, list.n, n_events);
     for (size_t j = 0; j < n_events; j++) {
         const fsea_events_event *e = &found_events[j];
         printf("%u %u %u %u %llu %d %u %u", e->row_first, e->row_last, e->col_first, e->col_last, (unsigned long long)e->hits, e->peak,
@@ -207,10 +149,10 @@ int main(int argc, char **argv) {
     }
     if (paint_path != NULL) {
         if (done > (size_t)INT_MAX) usage_error("too many rows for a PNG");
-        uint8_t *values = (uint8_t *)malloc(g_n_runs + 1), *image = (uint8_t *)malloc(done * (size_t)width + 1);
+        uint8_t *values = (uint8_t *)malloc(list.n + 1), *image = (uint8_t *)malloc(done * (size_t)width + 1);
         if (values == NULL || image == NULL) usage_error("out of memory");
-        for (size_t i = 0; i < g_n_runs; i++) values[i] = event_of_run[i] != FSEA_EVENTS_NO_EVENT ? 255 : 0;
-        if (fsea_events_paint_host(events, g_runs, values, g_n_runs, 0, done, image, (size_t)width) != FSEA_OK) die("fsea_events_paint_host");
+        for (size_t i = 0; i < list.n; i++) values[i] = event_of_run[i] != FSEA_EVENTS_NO_EVENT ? 255 : 0;
+        if (fsea_events_paint_host(events, list.runs, values, list.n, 0, done, image, (size_t)width) != FSEA_OK) die("fsea_events_paint_host");
         if (write_gray_png(paint_path, width, (int)done, image) != 0) {
             fprintf(stderr, "fsea-events: cannot write %s\n", paint_path);
             return EXIT_FAILURE;
@@ -222,6 +164,6 @@ int main(int argc, char **argv) {
     fsea_cfar_destroy(cfar);
     free(found_events);
     free(event_of_run);
-    free(g_runs);
+    free(list.runs);
     return 0;
 }

@@ -3,7 +3,8 @@
  * tool ends with a message, the capture format's constants, the newest-first row reader of the sweep tools, the --window
  * names, and what the tools that give dB rows to a device object share (fsea-persistence, fsea-occupancy, fsea-events): the
  * recording that becomes rows on the device chunk by chunk, the --mode names, the CFAR detector's options and the MHz of a
- * column.  Everything is `static inline`, as in pipeline.h; a tool takes what applies to it.
+ * column; and for fsea-events and fsea-cutouts the list of an input's runs, its filling from a recording and the link into
+ * events.  Everything is `static inline`, as in pipeline.h; a tool takes what applies to it.
  *
  * The --window table is the tools' own: the host library keeps one like it in its private header, which no tool includes.
  */
@@ -202,6 +203,77 @@ static inline uint8_t *tool_detector_image(const char *tool, const tool_detector
     if (*width < 1 || *width > FSEA_CFAR_MAX_WIDTH) tool_usage_error(tool, "the image is wider than 1048576 columns");
     *cfar = tool_detector_create(tool, d, *width);
     return image;
+}
+
+/* All runs of an input, in order (fsea-events, fsea-cutouts): a growing array, zeroed to begin with; the tool frees `runs`. */
+typedef struct {
+    fsea_events_run *runs;
+    size_t n, cap;
+} tool_run_list;
+
+/* where `more` runs behind the list's own go; the caller adds what it put there to `n` */
+static inline fsea_events_run *tool_runs_room(const char *tool, tool_run_list *list, size_t more) {
+    if (list->n + more > list->cap) {
+        size_t cap = list->cap ? list->cap : 1024;
+        while (cap < list->n + more) cap *= 2;
+        fsea_events_run *grown = (fsea_events_run *)realloc(list->runs, cap * sizeof(fsea_events_run));
+        if (grown == NULL) tool_usage_error(tool, "out of memory");
+        list->runs = grown;
+        list->cap = cap;
+    }
+    return list->runs + list->n;
+}
+
+/* The runs of a recording, to the list: every chunk of the opened `src` to the detector with a mask, mask and rows (of `type`)
+ * to the events object, on the device and the null stream.  The object starts each chunk at row 0, so that a chunk can be
+ * asked twice: for the number of its runs, then for the records, whose rows this rebases.  Returns the rows done. */
+static inline size_t tool_recording_runs(const char *tool, tool_row_source *src, fsea_cfar *cfar, fsea_events *events, int type,
+                                         tool_run_list *list) {
+    const size_t n = src->n;
+    void *d_rows = src->d_rows, *d_mask = NULL, *d_runs = NULL;
+    size_t d_runs_cap = 0, done = 0;
+    if (fsea_device_alloc(0, src->frames_max * n, &d_mask) != FSEA_OK) tool_die(tool, "fsea_device_alloc");
+    for (size_t frames; (frames = tool_rows_next(src)) > 0; done += frames) {
+        if (fsea_cfar_add_device(cfar, d_rows, type, frames, n, (uint8_t *)d_mask, NULL, NULL) != FSEA_OK) tool_die(tool, "fsea_cfar_add_device");
+        size_t found = 0;
+        if (fsea_events_reset(events) != FSEA_OK) tool_die(tool, "fsea_events_reset");
+        if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, NULL, 0, &found, NULL) != FSEA_OK) {
+            tool_die(tool, "fsea_events_runs_device");
+        }
+        if (found == 0) continue;
+        if (found > d_runs_cap) {
+            if (d_runs != NULL) fsea_device_free(0, d_runs);
+            d_runs_cap = found + found / 2;
+            if (fsea_device_alloc(0, d_runs_cap * sizeof(fsea_events_run), &d_runs) != FSEA_OK) tool_die(tool, "fsea_device_alloc");
+        }
+        if (fsea_events_reset(events) != FSEA_OK) tool_die(tool, "fsea_events_reset");
+        if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, (fsea_events_run *)d_runs, found, &found,
+                                    NULL) != FSEA_OK) {
+            tool_die(tool, "fsea_events_runs_device");
+        }
+        fsea_events_run *dst = tool_runs_room(tool, list, found);
+        if (fsea_copy_to_host(0, dst, d_runs, found * sizeof(fsea_events_run)) != FSEA_OK) tool_die(tool, "fsea_copy_to_host");
+        if (done + frames > 0xffffffffull) tool_usage_error(tool, "the recording holds more than 2^32 - 1 frames");
+        for (size_t i = 0; i < found; i++) dst[i].row += (uint32_t)done;
+        list->n += found;
+    }
+    fsea_device_free(0, d_mask);
+    if (d_runs != NULL) fsea_device_free(0, d_runs);
+    return done;
+}
+
+/* One link over all runs of the input with the tool's checked --gap-cols, --gap-rows, --min-rows, --min-cols and --min-hits:
+ * the number of events, then the events themselves (the caller frees them).  event_of_run: NULL, or room for an entry per run. */
+static inline fsea_events_event *tool_link(const char *tool, const tool_run_list *list, int gap_cols, int gap_rows, long long min_rows,
+                                           long long min_cols, long long min_hits, uint32_t *event_of_run, size_t *n_events) {
+    const uint32_t rows = (uint32_t)min_rows, cols = (uint32_t)min_cols;
+    int rc = fsea_events_link(list->runs, list->n, gap_cols, gap_rows, rows, cols, (uint64_t)min_hits, NULL, NULL, 0, n_events);
+    if (rc != FSEA_OK) tool_die(tool, "fsea_events_link");
+    fsea_events_event *found = (fsea_events_event *)malloc(sizeof(fsea_events_event) * (*n_events + 1));
+    if (found == NULL) tool_usage_error(tool, "out of memory");
+    rc = fsea_events_link(list->runs, list->n, gap_cols, gap_rows, rows, cols, (uint64_t)min_hits, event_of_run, found, *n_events, n_events);
+    if (rc != FSEA_OK) tool_die(tool, "fsea_events_link");
+    return found;
 }
 
 #if defined(_POSIX_C_SOURCE) && _POSIX_C_SOURCE >= 200809L /* pread: the sweep tools are built with it */

@@ -18,7 +18,6 @@ Without an argument every D runs as a child process under its own time limit and
 Usage: python scripts/extract_rate.py [--to FILE] | python scripts/extract_rate.py measure D      (D = 4, 16 or 64)"""
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -72,17 +71,9 @@ def measure(D):
                             sample_offset=j.sample_offset, flip=True)
 
     (ta, ta_min), (tb, tb_min), (tc, tc_min) = (ratelib.median_min(ratelib.per_call(fn, WARMUP, REPS)) for fn in (a, b, c_route))
-    # what the host spends inside the call before it returns (checks, 256 records with eight phasors each, two launches): a
-    # HIP-event interval on an idle stream holds it too.  Not ratelib.wall: the clock stops at the return of a call that
-    # does not wait, on a stream made idle outside the clock
+    # what the host spends inside the call before it returns: checks, 256 records with eight phasors each, two launches
     sync = fsea.Plan(128)
-    host = []
-    for _ in range(REPS):
-        sync.synchronize()
-        t0 = time.perf_counter()
-        a()
-        host.append(time.perf_counter() - t0)
-    sync.synchronize()
+    host = ratelib.host_time(a, sync.synchronize, REPS)
     sync.close()
     bound = (2.0 + 8.0 / D) * total_samples / HBM_BPS
     print("D=%-2d %d samples in %d jobs   (a) extract %8.1f us (%8.1f)   (b) one zoom call %8.1f us (%8.1f)   (c) %d zoom calls %9.1f us (%9.1f)"

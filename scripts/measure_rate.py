@@ -21,7 +21,6 @@ profiles/measure_rate.txt (or the file named after --to); a part that fails ends
 Usage: python scripts/measure_rate.py [--to FILE] | python scripts/measure_rate.py measure D | ... trace      (D = 4, 16 or 64)"""
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -40,7 +39,7 @@ F64_OPS_PER_PAIR = 25
 F64_OPS_PER_S = 65.8e12 / 2
 STEP_LIMIT_S = 240
 TRACE_D, TRACE_CALLS = 16, 10
-KERNELS = ("fsea_measure_upload", "fsea_measure_tiles", "fsea_measure_fold")     # a call's three, in launch order
+KERNELS = ("fsea_jobs_upload", "fsea_measure_tiles", "fsea_measure_fold")     # a call's three, in launch order
 
 HEADER = """# scripts/measure_rate.py on one MI355X: HIP-event times in one process, median (min) of %d calls after %d
 # recording: 2^25 samples resident, L = %d, taps = lowpass(10e6, 10e6 / (2 D), %d); lag 1, offset (0.5 + 0.5j) sum(c)
@@ -94,15 +93,9 @@ def measure(D):
     a, b, c_route, total, offset, objects, buffers = setup(D)
     n_pairs = JOB_BASE // D
     (tb, tb_min), (ta, ta_min), (tc, tc_min) = (ratelib.median_min(ratelib.per_call(fn, WARMUP, REPS)) for fn in (b, a, c_route))
-    # what the host spends inside the call (a) before it returns, on a stream made idle outside the clock (as extract_rate.py)
+    # what the host spends inside the call (a) before it returns: checks, the table of 256 jobs, three launches
     sync = fsea.Plan(128)
-    host = []
-    for _ in range(REPS):
-        sync.synchronize()
-        t0 = time.perf_counter()
-        a()
-        host.append(time.perf_counter() - t0)
-    sync.synchronize()
+    host = ratelib.host_time(a, sync.synchronize, REPS)
     sync.close()
     pairs = N_JOBS * n_pairs
     traffic, f64 = 8.0 * pairs / HBM_BPS, F64_OPS_PER_PAIR * pairs / F64_OPS_PER_S
@@ -125,10 +118,12 @@ def launches():
 
 
 def trace():
-    name, times = ratelib.kernel_trace([sys.executable, os.path.abspath(__file__), "launches"], "fsea_measure_", 3 * TRACE_CALLS, 1)[0]
+    # the upload is every job table's, so the extract call that makes the pairs has one too: the first dispatch of all
+    argv = [sys.executable, os.path.abspath(__file__), "launches"]
+    name, times = ratelib.kernel_trace(argv, (KERNELS[0], "fsea_measure_"), 1 + 3 * TRACE_CALLS, 1)[0]
     assert name.startswith(KERNELS[0]), name
     print("kernel trace, D=%d, %d calls of (a): " % (TRACE_D, TRACE_CALLS) +
-          "   ".join("%s %.1f us" % (k, float(np.median(times[i::3])) * 1e6) for i, k in enumerate(KERNELS)))
+          "   ".join("%s %.1f us" % (k, float(np.median(times[1 + i::3])) * 1e6) for i, k in enumerate(KERNELS)))
 
 
 def main():

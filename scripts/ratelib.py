@@ -1,11 +1,12 @@
-"""What the scripts/*_rate.py share: three ways to time a call, the kernel-trace reader, the part runner and the seeded
+"""What the scripts/*_rate.py share: four ways to time a call, the kernel-trace reader, the part runner and the seeded
 recording.  A script keeps its constants, its set-up, the bound it computes and its print lines; how a number is taken is
 here, once.
 
 Timing, all in seconds, each returning the list of its samples (the caller reduces: np.median, min, best of):
   per_call   HIP events round every single call;
   per_round  HIP events round `reps` back-to-back calls, `rounds` times, each divided by `reps`;
-  wall       the host clock round every single call, for calls that end in a device wait.
+  wall       the host clock round every single call, for calls that end in a device wait;
+  host_time  the host clock round every single call that does not wait, on a stream made idle outside the clock.
 
 torch is imported inside the functions: a script decides when torch's HIP runtime loads relative to libfsea_hip.so
 (tests/test_gpu_object_lifetime.py says why the order matters), and importing this module must not decide it for them."""
@@ -67,19 +68,34 @@ def wall(call, warmup, calls):
     return times
 
 
+def host_time(call, idle, calls):
+    """`calls` host-clock times of what the host spends inside a call that does not wait, before it returns: idle() brings
+    the call's stream to rest outside the clock, and once more behind the last call.  Not `wall`: that clock stops when a
+    call that ends in a device wait returns, this one when a call that left its work queued on an idle stream does."""
+    times = []
+    for _ in range(calls):
+        idle()
+        t0 = time.perf_counter()
+        call()
+        times.append(time.perf_counter() - t0)
+    idle()
+    return times
+
+
 def median_min(times):
     return float(np.median(times)), min(times)
 
 
 def kernel_trace(argv, prefix, per_case, n_cases, out_dir=None):
     """Run `argv` in a fresh child under `rocprofv3 --kernel-trace` (nothing else traced, no counters) and read the
-    dispatches of the kernels whose name starts with `prefix`, in start order: `per_case` of them for each of `n_cases`
-    cases.  Returns per case (kernel name, [durations in seconds]).  out_dir: keep the trace there, not in a temporary
-    directory."""
+    dispatches of the kernels whose name starts with `prefix` (or with one of a tuple of them; the first names the trace),
+    in start order: `per_case` of them for each of `n_cases` cases.  Returns per case (the first kernel's name, [durations
+    in seconds]).  out_dir: keep the trace there, not in a temporary directory."""
     if out_dir is None:
         with tempfile.TemporaryDirectory() as tmp:
             return kernel_trace(argv, prefix, per_case, n_cases, tmp)
-    cmd = ["rocprofv3", "--kernel-trace", "-d", out_dir, "-o", prefix, "--output-format", "csv", "--"] + list(argv)
+    prefix = (prefix,) if isinstance(prefix, str) else tuple(prefix)
+    cmd = ["rocprofv3", "--kernel-trace", "-d", out_dir, "-o", prefix[0], "--output-format", "csv", "--"] + list(argv)
     subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
     traces = glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True)
     if len(traces) != 1:
@@ -88,7 +104,7 @@ def kernel_trace(argv, prefix, per_case, n_cases, out_dir=None):
         rows = [r for r in csv.DictReader(f) if r["Kernel_Name"].startswith(prefix)]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     if len(rows) != per_case * n_cases:
-        raise SystemExit("expected %d dispatches of %s, found %d" % (per_case * n_cases, prefix, len(rows)))
+        raise SystemExit("expected %d dispatches of %s, found %d" % (per_case * n_cases, " / ".join(prefix), len(rows)))
     cases = []
     for i in range(n_cases):
         mine = rows[i * per_case:(i + 1) * per_case]

@@ -97,6 +97,47 @@ def test_kernel_trace_refuses_no_trace_and_two(ratelib, tmp_path, monkeypatch, n
     assert str(e.value) == "expected one kernel trace under %s, found %d" % (out, n_files)
 
 
+def test_kernel_trace_takes_several_prefixes(ratelib, tmp_path, monkeypatch):
+    """a call whose kernels share no prefix (measure_rate.py: the job tables' upload and fsea_measure_*): one case of all
+    that start with any of them, in start order; the first prefix names the trace"""
+    stub_rocprofv3(tmp_path, monkeypatch, TRACE)
+    kept = tmp_path / "kept"
+    cases = ratelib.kernel_trace(["the-program", "launches"], ("oth", "mine_b"), 6, 1, out_dir=str(kept))
+    assert [(name, [round(t * 1e9) for t in times]) for name, times in cases] == [("other", [5, 5, 40, 50, 60, 5])]
+    assert (kept / "host0" / "oth_kernel_trace.csv").exists()
+    with pytest.raises(SystemExit) as e:
+        ratelib.kernel_trace(["the-program", "launches"], ("oth", "mine_b"), 5, 1)
+    assert str(e.value) == "expected 5 dispatches of oth / mine_b, found 6"
+
+
+# ---- the host time of a call that does not wait
+
+def test_host_time_stops_the_clock_round_the_call_alone(ratelib, monkeypatch):
+    """a stub clock that every look at it advances by 1, a call that advances it by 10 and an idle() that advances it by 100:
+    each sample is the call's 10 and the one step of the first look, and idle() runs in front of every call and once behind
+    the last, never inside the clock"""
+    now, log = [0.0], []
+
+    def clock():
+        now[0] += 1.0
+        log.append("clock")
+        return now[0]
+
+    def call():
+        now[0] += 10.0
+        log.append("call")
+
+    def idle():
+        now[0] += 100.0
+        log.append("idle")
+
+    monkeypatch.setattr(ratelib.time, "perf_counter", clock)
+    assert ratelib.host_time(call, idle, 3) == [11.0, 11.0, 11.0]
+    assert log == ["idle", "clock", "call", "clock"] * 3 + ["idle"]
+    del log[:]
+    assert ratelib.host_time(call, idle, 0) == [] and log == ["idle"]
+
+
 # ---- the part runner
 
 STUB_SCRIPT = """import sys, time
