@@ -1,9 +1,28 @@
 """A numpy restatement of fsea_extract_jobs and fsea_extract_layout, written from the contract in include/fsea.h, not from
-the C, and the recording of the end-to-end tests (three tone bursts in noise) with the check they make of a cut-out."""
+the C, the reference of one job's pairs (tests/shift_ref.py's exact phase on the job's slice), and the recording of the
+end-to-end tests (three tone bursts in noise) with the check they make of a cut-out."""
 import numpy as np
+
+from tests import shift_ref
 
 JOB = np.dtype([("first", "<u8"), ("n_samples", "<u8"), ("sample_offset", "<u8"), ("cycles_per_sample", "<f8"),
                 ("phase0_cycles", "<f8"), ("out_first", "<u8")])      # fsea_extract_job
+
+
+def cutout_reference(iq, job, taps, D, flip):
+    """The pairs of one job in f64: a job is a freshly reset zoom on its own samples (include/fsea.h), so this is
+    shift_ref.zoom_reference on iq[2 first : 2 (first + n)] with the job's cycles_per_sample and phase0_cycles, its
+    sample_offset as the stream position of sample 0 and a zero tail in front -- the phase exact, nothing of how the kernel
+    groups or aligns its loads.  `job` is an fsea.ExtractJob or a JOB record; out_first is not looked at.  n_samples // D
+    pairs; an empty job gives an empty array."""
+    first, n, offset, cps, phase0 = (job[k] if isinstance(job, np.void) else getattr(job, k)
+                                     for k in ("first", "n_samples", "sample_offset", "cycles_per_sample", "phase0_cycles"))
+    first, n = int(first), int(n)
+    if n == 0:
+        return np.zeros(0, dtype=np.complex128)
+    part = np.asarray(iq, dtype=np.uint8)[2 * first:2 * (first + n)]
+    assert part.size == 2 * n, (first, n, "the job leaves the recording")
+    return shift_ref.zoom_reference(part, flip, float(cps), float(phase0), taps, D, offset=int(offset))[0]
 
 
 def lead(n_taps, decimation):

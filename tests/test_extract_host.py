@@ -1,8 +1,11 @@
 """CPU tier: event cut-outs without a GPU -- the argument checks of fsea_extract_* (before any device work, against a fake
 object where a check must not look into the object beyond its decimation), their order, the no-op cases; fsea_extract_jobs
 and fsea_extract_layout against the restatement of tests/extract_ref.py, field for field; the shipped fsea_extract_u8
-kernels' resource usage; the restatement's own end-to-end check on the CPU; fsea-cutouts' usage errors."""
+kernels' resource usage; the restatement's own end-to-end check on the CPU; the job grid of tests/test_gpu_extract_domain.py
+(domain_jobs: what it holds, asserted here) and the teeth of the reference that tier compares with; fsea-cutouts' usage
+errors."""
 import ctypes
+import itertools
 import os
 import re
 import struct
@@ -14,11 +17,20 @@ import pytest
 from frequensea_amd import fsea
 from tests import extract_ref as R
 from tests.conftest import ROOT
+from tests.test_fir_host import fir_reference
+from tests.test_gpu_fir import check
+from tests.test_gpu_shift_domain import ABOVE, CPS, EVERYWHERE, PHASE0
+from tests.test_gpu_zoom import lowpass_like_taps
+from tests.test_iq_chain_host import shifted_samples as product_samples
+from tests.test_shift_ref_host import GRID_CYCLES, GRID_PHASES, LIMIT, grid_positions
 from tests.test_shipped_artifacts import LIB, _kernels
 from tests.test_zoom_host import zoom_reference
 
 FSEA_EINVAL = -1
 TOOL = os.path.join(ROOT, "frequensea_amd", "bin", "fsea-cutouts")
+ZT = fsea.ZOOM_TILE_OUTPUTS
+DOMAIN_CASES = [(3, 21, 0), (25, 97, 1), (64, 512, 0)]          # (D, L, flip): one per LDS size, _s, _m, _l
+RESIDUE_GROUPS = ("residues, high", "residues, low")
 
 
 def job(first=0, n=64, offset=0, cps=0.01, phase0=0.0, out_first=0):
@@ -282,6 +294,136 @@ def test_the_restatement_alone_finds_each_burst_at_the_centre_of_its_cutout():
     first, n = int(j["first"]), int(j["n_samples"])
     y, _ = zoom_reference(raw[2 * first:2 * (first + n)], 1, float(j["cycles_per_sample"]) + 8.0 / R.N, 0.0, c, R.D, offset=first)
     assert abs(R.peak_bin_inside_the_burst(y[R.lead(R.TAPS, R.D) // R.D:], first, R.BURSTS[0], rest=(0.5 + 0.5j) * c.sum())) > 100
+
+
+# ---- the job grid of tests/test_gpu_extract_domain.py: what it is for, and the teeth of its reference ------------------
+
+def domain_lengths(D):
+    """(n_long, n_tile, n_short): five outputs more than a tile and one sample over; one output more than a tile (two tiles)
+    and two samples over; three outputs and seventeen samples over, so that a whole 16-byte group lies inside at any first."""
+    return D * (ZT + 5) + 1, D * (ZT + 1) + 2, 3 * D + 17
+
+
+def domain_jobs(D, L):
+    """The jobs of one case over the argument domain check_shift admits per job -> ({group: [fsea.ExtractJob]}, n_iq).
+      positions         n_long samples at every grid position with the three cycles and two phases of EVERYWHERE, and one job
+                        with 2^32 in the middle of its second tile;
+      grid across 2^31  n_tile samples, every GRID_CYCLES x GRID_PHASES;
+      grid, last call   the same where sample_offset + n_samples == 2^52;
+      residues, high    n_short samples, first = a + 8 k, sample_offset = 2^40 + r for all (a, r) in 0 .. 7 x 0 .. 7;
+      residues, low     the same at sample_offset = r: the first group's base lies in front of stream position 0.
+    Outside the residue groups `first` walks 0 .. 15, so the jobs overlap in a recording of n_long + 21 samples.  The grid does
+    not depend on L; the argument is the case's."""
+    n_long, n_tile, n_short = domain_lengths(D)
+    walk = itertools.count()
+
+    def job(n, offset, cps, phase0, first=None):
+        return fsea.ExtractJob(next(walk) % 16 if first is None else first, n, offset, cps, phase0, 0)
+
+    groups = {"positions": [job(n_long, p, c, ph) for p in grid_positions(n_long) for c, ph in EVERYWHERE]}
+    groups["positions"].append(job(n_long, (1 << 32) - (ZT * D + (n_long - ZT * D) // 2), CPS, PHASE0))
+    at = grid_positions(n_tile)
+    for name, p in (("grid across 2^31", at[2]), ("grid, last call", at[5])):
+        groups[name] = [job(n_tile, p, c, ph) for c in GRID_CYCLES for ph in GRID_PHASES]
+    for name, base in zip(RESIDUE_GROUPS, (ABOVE, 0)):
+        groups[name] = [job(n_short, base + r, CPS, PHASE0, first=a + 8 * ((a + r) & 1)) for a in range(8) for r in range(8)]
+    return groups, n_long + 21
+
+
+def domain_calls(groups):
+    """The grid as three calls.  The call-wide relative bound of tests/test_gpu_fir.py rests on rms(y) >= ~0.3, which a call
+    of residue jobs alone (three to eight outputs each on a fresh tail, most of them run-in) does not have: the residue groups
+    share a call with long jobs."""
+    return [groups["positions"] + groups["residues, high"], groups["grid across 2^31"] + groups["residues, low"],
+            groups["grid, last call"]]
+
+
+def phase_key(j):
+    """what shift_ref.exact_turns is cached on"""
+    return (j.cycles_per_sample, j.phase0_cycles, j.sample_offset, j.n_samples)
+
+
+@pytest.mark.parametrize("D,L,flip", DOMAIN_CASES)
+def test_the_domain_grid_holds_what_it_is_for(D, L, flip):
+    groups, n_iq = domain_jobs(D, L)
+    n_long, n_tile, n_short = domain_lengths(D)
+    jobs = [j for g in groups.values() for j in g]
+    assert all(j.first + j.n_samples <= n_iq and j.sample_offset + j.n_samples <= LIMIT and j.n_samples // D >= 3 for j in jobs)
+    assert sorted(map(id, jobs)) == sorted(id(j) for call in domain_calls(groups) for j in call)      # every job is in one call
+    assert {j.first for j in jobs if j.n_samples != n_short} == set(range(16))
+    assert n_long // D == ZT + 5 and n_tile // D == ZT + 1 and n_long % D and n_tile % D
+    # both residue groups: all 64 pairs; every job holds a whole group of eight of the buffer (one 16-byte load) and begins
+    # inside a group, but for first = 0 and 8, which end inside one
+    for name in RESIDUE_GROUPS:
+        g = groups[name]
+        assert {(j.first % 8, j.sample_offset % 8) for j in g} == set(itertools.product(range(8), range(8))) and len(g) == 64
+        assert all(j.sample_offset < 8 for j in g) == (name == "residues, low") and all(j.first < 16 for j in g)
+        for j in g:
+            end = j.first + j.n_samples
+            assert -(-j.first // 8) * 8 + 8 <= end, (name, j.first, "no whole group")
+            assert j.first % 8 or end % 8, (name, j.first, "neither end is ragged")
+    assert all(j.sample_offset >= (1 << 40) for j in groups["residues, high"])
+    # 2^32 strictly inside a job, inside a tile of it: the added job has it in the middle of its second tile
+    j = groups["positions"][-1]
+    k = (1 << 32) - j.sample_offset
+    assert ZT * D < k < j.n_samples == n_long and k % (ZT * D) == (n_long - ZT * D) // 2 != 0
+    assert sum(1 for j in jobs if j.sample_offset < (1 << 32) < j.sample_offset + j.n_samples) >= 1
+    assert sum(1 for j in jobs if j.sample_offset < (1 << 31) < j.sample_offset + j.n_samples) >= 60
+    # the last admissible job, in both lengths
+    assert {j.n_samples for j in jobs if j.sample_offset + j.n_samples == LIMIT} == {n_long, n_tile}
+    for name in ("grid across 2^31", "grid, last call"):
+        assert {(j.cycles_per_sample, j.phase0_cycles) for j in groups[name]} >= set(itertools.product(GRID_CYCLES, GRID_PHASES))
+        assert len(groups[name]) == len(GRID_CYCLES) * len(GRID_PHASES) == 60
+    assert {(j.cycles_per_sample, j.phase0_cycles) for j in groups["positions"]} == set(EVERYWHERE)
+    assert {j.sample_offset for j in groups["positions"][:-1]} == set(grid_positions(n_long))
+    # The exact phase is a Python loop per sample, cached on phase_key: no two jobs share a key but the eight firsts of a
+    # residue, which must (the residue is the offset's), and then the second costs nothing
+    long_keys = [phase_key(j) for name, g in groups.items() if name not in RESIDUE_GROUPS for j in g]
+    assert len(set(long_keys)) == len(long_keys)
+    for name in RESIDUE_GROUPS:
+        assert len({phase_key(j) for j in groups[name]}) == 8
+    steps = sum(k[3] for k in {phase_key(j) for j in jobs})
+    print("D = %d: %d jobs, %d samples of exact phase" % (D, len(jobs), steps))
+    assert steps == 37 * n_long + 120 * n_tile + 16 * n_short
+
+
+def product_cutout(iq, job, taps, D, flip):
+    """cutout_reference with the phase as ONE rounded double product (tests/test_iq_chain_host.py: shifted_samples): the
+    error a kernel has whose phase reduction is a plain multiplication"""
+    part = iq[2 * job.first:2 * (job.first + job.n_samples)]
+    x = product_samples(part, flip, job.cycles_per_sample, job.phase0_cycles, job.sample_offset)
+    y = fir_reference(x, taps)[0]
+    return y[::D][:job.n_samples // D]
+
+
+def test_the_cutout_reference_has_teeth_through_the_bounds_of_the_gpu_tier():
+    """Reference against reference through tests/test_gpu_fir.py's check, the comparison of the GPU tier: a two-tile job at
+    cycles -0.12 and position 2^44 against the same job one stream position on (a slip of o, of a group base or of the step
+    table is at least that), and against the single rounded product (1.2e-4 cycles there,
+    test_the_product_restatement_is_no_judge_at_2_to_the_44).  Both fail; if either passed, the comparison of
+    tests/test_gpu_extract_domain.py would judge nothing."""
+    D, L, flip = 3, 21, 0
+    c = lowpass_like_taps(L, 5)
+    n = domain_lengths(D)[1]
+    iq = np.random.default_rng(44).integers(0, 256, 2 * (n + 5), dtype=np.uint8)
+    j = fsea.ExtractJob(5, n, 1 << 44, CPS, PHASE0, 0)
+    assert CPS == -0.12 and n // D == ZT + 1
+    want = R.cutout_reference(iq, j, c, D, flip)
+    assert want.size == ZT + 1 and want.dtype == np.complex128
+    check(want.astype(np.complex64), want, "the reference rounded to f32 passes")
+    check(product_cutout(iq, fsea.ExtractJob(5, n, 0, CPS, PHASE0, 0), c, D, flip),
+          R.cutout_reference(iq, fsea.ExtractJob(5, n, 0, CPS, PHASE0, 0), c, D, flip), "at position 0 the product is good")
+    one_on = fsea.ExtractJob(5, n, (1 << 44) + 1, CPS, PHASE0, 0)
+    for name, other in (("sample_offset + 1", R.cutout_reference(iq, one_on, c, D, flip)), ("one rounded product", product_cutout(iq, j, c, D, flip))):
+        print(name, "max |delta| %.3e, relative L2 %.3e" % (np.abs(other - want).max(), np.linalg.norm(other - want) / np.linalg.norm(want)))
+        with pytest.raises(AssertionError):
+            check(other, want, name)
+    # the reference of a job is the job's own: an empty job, one shorter than D, a record of the restatement's dtype
+    assert R.cutout_reference(iq, fsea.ExtractJob(3, 0, 7, CPS, 0.0, 0), c, D, flip).size == 0
+    assert R.cutout_reference(iq, fsea.ExtractJob(3, D - 1, 7, CPS, 0.0, 0), c, D, flip).size == 0
+    rec = np.zeros((), R.JOB)
+    rec["first"], rec["n_samples"], rec["sample_offset"], rec["cycles_per_sample"], rec["phase0_cycles"] = 5, n, 1 << 44, CPS, PHASE0
+    assert np.array_equal(R.cutout_reference(iq, rec[()], c, D, flip), want)
 
 
 def test_tool_usage_errors():

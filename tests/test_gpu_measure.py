@@ -4,7 +4,13 @@ Bit identity, no tolerance: a job's record is tests/measure_ref.py's for the job
 roundings, fold_256 inside a tile and fold_64 over the tiles -- whatever first_pair is, whatever other jobs share the call
 and in whatever order.  The shapes are the smallest at which the kernels can still go wrong: lengths round the lag, a wave,
 a workgroup's 256 lanes, one and two tiles, the 64 tiles of the fold's first round; odd and even firsts; jobs that overlap;
-one that ends with the buffer; a table long enough for the bisection to take every turn.  Inputs and outputs are guarded."""
+one that ends with the buffer; a table long enough for the bisection to take every turn.  Inputs and outputs are guarded.
+
+Special values, where the header promises something (a NaN term is never the peak, an accumulator is never -0.0, the terms are
+f64 conversions of the f32 values): one NaN or infinity per buffer at every place a kernel treats differently -- the stand-ins
+of a missing partner and of pairs past the end, both bodies, the lane's chain, the combine's and the fold's peak merges --,
+a buffer of -0.0, and one of subnormals and FLT_MAX.  Records that hold NaNs are compared through same_record; every other
+test keeps same_bits."""
 import ctypes
 import os
 import subprocess
@@ -17,6 +23,7 @@ from tests import extract_ref as R
 from tests import measure_ref as M
 from tests.conftest import ROOT
 from tests.guarded import FILL, Guarded
+from tests.test_measure_host import extremes_buffer, pairs_f32, special_sums
 
 pytestmark = pytest.mark.gpu
 
@@ -223,6 +230,145 @@ def test_two_streams_and_an_odd_pair_base(resident):
         g.free()
     for o in (s1, s2, sync, m):
         o.close()
+
+
+# ---- special values: a NaN, an infinity, -0.0 and the ends of the f32 range, where the header promises something --------
+
+N_SPECIAL = 3 * T + 300
+SPECIAL_LENGTHS = (1, 257, 2 * T, 2 * T + 1)     # the second tile of the longer two takes the body without tests
+SPECIAL_FIRSTS = (4, 7)
+SPECIAL_LAGS = (1, 7)
+LOUD = np.complex64(40.5 - 29.5j)                # |z - OFFSET|^2 = 2500: far above any of the Gaussian pairs
+
+
+def same_record(got, want):
+    """The comparison rule for records that hold NaNs: peak, peak_index, n_pairs and n_lagged by their bits; each of the six
+    sums by its bits where the reference is not a NaN and "is a NaN" where it is -- neither include/fsea.h nor IEEE 754 fixes
+    the sign and the payload of a generated NaN, and x86 and the GPU differ."""
+    ok = all(same_bits(got[name], want[name]) for name in ("peak", "peak_index", "n_pairs", "n_lagged"))
+    for name in M.NAMES:
+        ok = ok and (bool(np.isnan(got[name])) if np.isnan(want[name]) else same_bits(got[name], want[name]))
+    return ok
+
+
+def placements(n):
+    """{name: (index of the special pair, index of a planted maximum or None)} inside a job of n pairs"""
+    out = {"a: pair 0, the stand-in for a missing partner": (0, None)}
+    if n == 1:
+        return out
+    if n % T:
+        out["b: the last pair of a ragged tile, the stand-in for pairs past the end"] = (n - 1, None)
+    out["c: a middle lane of tile 0"] = (100 if n < 1000 else 868, None)
+    if n >= 2 * T:
+        out["d: inside the whole second tile"] = (T + 1500, None)
+        for base, body in ((0, "tile 0"), (T, "the whole second tile")):
+            out["e: 256 pairs in front of the maximum, in its lane's column, %s" % body] = (base + 1068, base + 1324)
+            out["e: 256 pairs behind the maximum, in its lane's column, %s" % body] = (base + 1580, base + 1324)
+        out["f: in another wave than the maximum"] = (200, 70)
+        out["f: in the tile behind the maximum's"] = (T + 10, 70)
+        out["f: in the tile in front of the maximum's"] = (70, T + 10)
+    else:
+        out["e: 256 pairs in front of the maximum, in its lane's column"] = (0, 256)
+        out["e: 256 pairs behind the maximum, in its lane's column"] = (256, 0)
+        out["f: in another wave than the maximum"] = (200, 70)
+    return out
+
+
+def neighbours(first, n, at):
+    """the jobs inside (first, n) that end just in front of pair `at` of it or begin just behind it"""
+    return [(a, m) for a, m in ((first, at), (first + at + 1, n - at - 1)) if m > 0]
+
+
+@pytest.fixture(scope="module")
+def special():
+    """(the Gaussian buffer the special pairs are planted in, a guarded device buffer of its size, a Measure)"""
+    z = pairs_of(21, N_SPECIAL)
+    d = Guarded(z.nbytes)
+    m = fsea.Measure()
+    yield z, d, m
+    d.check("the input is read, not written")
+    d.free()
+    m.close()
+
+
+@pytest.mark.parametrize("n", SPECIAL_LENGTHS)
+@pytest.mark.parametrize("kind", ["nan", "inf"])
+def test_a_nan_or_an_infinity_at_every_place_a_kernel_treats_differently(special, kind, n):
+    """One special pair per buffer (a NaN in re, +inf in im) at each place of `placements`, in a job at an even and at an odd
+    first_pair, with lags 1 and 7: the record is measure_ref.sums' by same_record; the peak is that of the other pairs (the
+    NaN) or the special pair's (the infinity); the jobs on either side of the special pair are finite and bit-identical."""
+    base, d_pairs, m = special
+    for first in SPECIAL_FIRSTS:
+        for name, (at, loud) in placements(n).items():
+            z = base.copy()
+            if loud is not None:
+                z[first + loud] = LOUD
+            if kind == "nan":
+                z.real[first + at] = np.nan
+            else:
+                z.imag[first + at] = np.inf
+            d_pairs.upload(z)
+            jobs = [(first, n)] + neighbours(first, n, at)
+            for lag in SPECIAL_LAGS:
+                what = (kind, n, first, lag, name)
+                got = run_device(m, d_pairs, N_SPECIAL, jobs, lag)
+                want = [special_sums(z[a:a + k], OFFSET, lag) for a, k in jobs]
+                assert same_record(got[0], want[0]), what + (got[0], want[0])
+                if kind == "nan":
+                    assert np.isnan(got[0]["s_re"]) and np.isnan(got[0]["p"]) and np.isnan(got[0]["q"]), what
+                    assert np.isfinite(got[0]["s_im"]) and np.isfinite(got[0]["peak"]), what
+                    others = np.delete(z[first:first + n], at).astype(np.complex128) - OFFSET
+                    power = others.real * others.real + others.imag * others.imag
+                    if n > 1:
+                        k = int(np.argmax(power))
+                        assert (got[0]["peak"], got[0]["peak_index"]) == (power[k], k + (k >= at)), what
+                    else:
+                        assert got[0]["peak"].tobytes() == bytes(8) and got[0]["peak_index"] == 0, what     # all NaN: +0.0 at 0
+                    if loud is not None:
+                        assert (got[0]["peak"], got[0]["peak_index"]) == (2500.0, loud), what
+                else:
+                    assert (got[0]["p"], got[0]["q"], got[0]["peak"], got[0]["peak_index"]) == (np.inf, np.inf, np.inf, at), what
+                for k in range(1, len(jobs)):
+                    assert same_bits(got[k], want[k]), what + (jobs[k],)
+                    assert all(np.isfinite(got[k][f]) for f in M.NAMES + ("peak",)), what + (jobs[k],)
+                host = np.frombuffer(m.run(z, table(jobs), OFFSET, lag), dtype=M.SUMS)
+                assert all(same_record(host[k], want[k]) for k in range(len(jobs))), what + ("host form",)
+
+
+def test_minus_zero_pairs_give_plus_zero_records(special):
+    """Every pair -0.0 - 0.0j with offset +0.0: the terms of s_re and s_im are -0.0, an absent one is +0.0, and every sum and
+    the peak are +0.0 by their bits at all four lengths -- "an accumulator is never -0.0"."""
+    _, d_pairs, m = special
+    z = pairs_f32([-0.0] * N_SPECIAL, [-0.0] * N_SPECIAL)
+    d_pairs.upload(z)
+    jobs = [(first, n) for first in SPECIAL_FIRSTS for n in SPECIAL_LENGTHS]
+    for lag in SPECIAL_LAGS:
+        got = run_device(m, d_pairs, N_SPECIAL, jobs, lag, offset=0j)
+        for k, (a, n) in enumerate(jobs):
+            assert same_bits(got[k], special_sums(z[a:a + n], 0j, lag)), (lag, a, n, got[k])
+            assert got[k].tobytes()[:64] == bytes(64) and (got[k]["n_pairs"], got[k]["n_lagged"]) == (n, max(n - lag, 0)), (lag, a, n, got[k])
+
+
+def test_subnormals_and_flt_max_every_field_by_its_bits(special):
+    """The buffer of tests/test_measure_host.py: multiples of the smallest f32 subnormal in front of pair 2 T + 150, +-FLT_MAX
+    behind.  The terms are f64 conversions of the f32 values: a flushed subnormal gives a zero where the reference has 2^-149,
+    an f32 product an infinity where it has 2^256."""
+    _, d_pairs, m = special
+    at = 2 * T + 150
+    z = extremes_buffer(N_SPECIAL, at)
+    d_pairs.upload(z)
+    jobs = [(first, n) for first in SPECIAL_FIRSTS for n in SPECIAL_LENGTHS]
+    jobs += [(at - 100, 257), (at + 1, T + 100), (at, 1), (at - 1, 2), (at - 1, 1), (3, N_SPECIAL - 3)]
+    for lag in SPECIAL_LAGS:
+        got = run_device(m, d_pairs, N_SPECIAL, jobs, lag, offset=0j)
+        for k, (a, n) in enumerate(jobs):
+            want = special_sums(z[a:a + n], 0j, lag)
+            assert same_record(got[k], want) and same_bits(got[k], want), (lag, a, n, got[k], want)
+            assert all(np.isfinite(got[k][f]) for f in M.NAMES + ("peak",)), (lag, a, n, got[k])
+            if a + n <= at:
+                assert got[k]["p"] > 0.0 and got[k]["q"] > 0.0 and got[k]["peak"] >= 2.0 ** -298, (lag, a, n, got[k])
+        host = np.frombuffer(m.run(z, table(jobs), 0j, lag), dtype=M.SUMS)
+        assert same_bits(host, got), lag
 
 
 # ---- end to end: a recording with a constant-envelope burst and a noise-like one

@@ -1,5 +1,6 @@
 """CPU tier: signal measures without a GPU -- the restatement tests/measure_ref.py against exact arithmetic, inside the bound
-the depth of its addition tree gives; fsea_measure_finish on a tone, on noise and on the NaN cases; fsea_measure_jobs against
+the depth of its addition tree gives, and on hand-made special values (a NaN, an infinity, -0.0, the smallest subnormal and
+FLT_MAX) against expectations written out by hand; fsea_measure_finish on a tone, on noise and on the NaN cases; fsea_measure_jobs against
 its formula; the argument checks of fsea_measure_run_* in the header's order, against a fake object (they read nothing of
 it); the shipped kernels' resource usage; fsea-cutouts' new usage error."""
 import ctypes
@@ -102,6 +103,111 @@ def test_fold_is_the_tree_the_header_describes():
     assert (M.sums(ties)["peak"], M.sums(ties)["peak_index"]) == (4.0, 77)
     empty = M.sums(np.zeros(0, np.complex64), 0.5 + 0.5j, 3)
     assert empty.tobytes() == bytes(80)
+
+
+# ---- special values: what include/fsea.h promises of a NaN, of -0.0 and of the ends of the f32 range ------------------
+
+TINY, FMAX = 2.0 ** -149, float(np.finfo(np.float32).max)       # the smallest f32 subnormal, FLT_MAX: both exact as doubles
+NAMES_AND_PEAK = M.NAMES + ("peak",)
+
+
+def pairs_f32(re, im):
+    """complex64 from two lists through float32 arrays: no complex128 arithmetic between the values and the buffer"""
+    z = np.empty(len(re), np.complex64)
+    z.real, z.imag = np.asarray(re, np.float32), np.asarray(im, np.float32)
+    return z
+
+
+def special_sums(z, offset=0j, lag=1):
+    """measure_ref.sums where inf - inf and inf * 0 are meant"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        return M.sums(z, offset, lag)
+
+
+def bits_of(x):
+    return int(np.float64(x).view(np.uint64))
+
+
+def extremes_buffer(n, at):
+    """n pairs: in front of `at` small whole multiples of the smallest f32 subnormal (every sum of them is exact in f64 and
+    is 0 if a conversion flushes), from `at` on +-FLT_MAX (|z|^4 = 2^514 a pair: finite in f64 over any job)."""
+    k = np.arange(n)
+    re, im = ((k % 3) + 1) * TINY * (1 - 2 * (k % 2)), ((k % 5) - 2) * TINY
+    re[at:], im[at:] = FMAX * (1 - 2 * (k[at:] % 2)), FMAX * (1 - 2 * ((k[at:] // 2) % 2))
+    return pairs_f32(re, im)
+
+
+@pytest.mark.parametrize("n", [1, 257, 2 * M.TILE + 1])
+def test_minus_zero_pairs_give_plus_zero_sums(n):
+    """a = -0.0 - +0.0 = -0.0 in every term of s_re and s_im; an accumulator that starts at +0.0 stays +0.0 under it, "so an
+    absent term may be added as +0.0 or left out"."""
+    z = pairs_f32([-0.0] * n, [-0.0] * n)
+    assert np.all(np.signbit(z.real)) and np.all(np.signbit(z.imag))
+    a, b = M.terms(z, 0j, 1)[:2]
+    assert np.all(np.signbit(a)) and np.all(np.signbit(b))                         # the terms are -0.0 ...
+    for lag in (1, 7):
+        s = special_sums(z, 0j, lag)
+        for name in NAMES_AND_PEAK:
+            assert bits_of(s[name]) == 0, (n, lag, name)                           # ... and every sum +0.0 by its bits
+        assert (s["peak_index"], s["n_pairs"], s["n_lagged"]) == (0, n, max(n - lag, 0))
+
+
+def test_a_nan_term_poisons_its_sums_and_is_never_the_peak():
+    z = pairs_f32([1.0, np.nan, 3.0, 0.5], [1.0, 2.0, -2.0, 0.0])
+    clean = pairs_f32([1.0, 0.0, 3.0, 0.5], [1.0, 2.0, -2.0, 0.0])
+    s, c = special_sums(z), special_sums(clean)
+    assert s["s_im"] == 1.0 and bits_of(s["s_im"]) == bits_of(c["s_im"])           # 1 + 2 - 2 + 0
+    for name in ("s_re", "p", "q", "r_re", "r_im"):
+        assert np.isnan(s[name]) and np.isfinite(c[name]), name
+    assert (s["peak"], s["peak_index"]) == (13.0, 2) == (c["peak"], c["peak_index"])      # 3^2 + 2^2, the other pairs' largest
+    # the NaN in front of the largest, behind it, first and last: the same peak; in its place: the next largest
+    for k in range(4):
+        z = pairs_f32([1.0, 2.0, 3.0, 0.5], [1.0, 2.0, -2.0, 0.0])
+        z.real[k] = np.nan
+        want = (13.0, 2) if k != 2 else (8.0, 1)
+        assert (special_sums(z)["peak"], special_sums(z)["peak_index"]) == want, k
+    # lag 2: the partner's NaN reaches r two pairs on, nothing else changes
+    s = special_sums(pairs_f32([1.0, np.nan, 3.0, 0.5], [1.0, 2.0, -2.0, 0.0]), 0j, 2)
+    assert np.isnan(s["r_re"]) and np.isnan(s["r_im"]) and s["s_im"] == 1.0 and s["n_lagged"] == 2
+    # all NaN: peak +0.0 at index 0, as an empty or a silent job
+    s = special_sums(pairs_f32([np.nan] * 5, [np.nan] * 5))
+    assert bits_of(s["peak"]) == 0 and s["peak_index"] == 0 and all(np.isnan(s[name]) for name in M.NAMES)
+
+
+def test_an_infinity_is_the_peak_at_its_index():
+    s = special_sums(pairs_f32([1.0, 2.0, 3.0], [1.0, np.inf, 0.5]))
+    assert s["p"] == np.inf and s["q"] == np.inf and (s["peak"], s["peak_index"]) == (np.inf, 1)
+    assert s["s_re"] == 6.0 and s["s_im"] == np.inf
+    assert s["r_re"] == np.inf and np.isnan(s["r_im"])        # r_re: 2 * 1 + inf * 1, 3 * 2 + 0.5 * inf; r_im of pair 1 and 2: inf, -inf
+
+
+def test_the_ends_of_the_f32_range_give_finite_sums_computed_by_hand():
+    """The smallest subnormal and FLT_MAX are exact doubles and so are their products here; the folds of two and three terms
+    are (x0 + x1) and (x0 + x1) + (x2 + 0), everything else of the tree adds +0.0."""
+    t, F = TINY, FMAX
+    s = special_sums(pairs_f32([t, 3 * t], [-t, t]))
+    want = {"s_re": t + 3 * t, "s_im": -t + t, "p": (t * t + t * t) + (9 * t * t + t * t), "q": (2 * t * t) ** 2 + (10 * t * t) ** 2,
+            "r_re": 0.0 + (3 * t * t + t * -t), "r_im": 0.0 + (t * t - 3 * t * -t), "peak": 10 * t * t}
+    for name in NAMES_AND_PEAK:
+        assert bits_of(s[name]) == bits_of(want[name]) and np.isfinite(s[name]), (name, s[name], want[name])
+    assert s["p"] == 12 * 2.0 ** -298 > 0.0 and s["s_re"] == 2.0 ** -147 and s["peak_index"] == 1
+    s = special_sums(pairs_f32([F, -F, t], [F, F, F]))
+    want = {"s_re": (F + -F) + (t + 0.0), "s_im": (F + F) + (F + 0.0), "p": (2 * F * F + 2 * F * F) + ((t * t + F * F) + 0.0),
+            "q": ((2 * F * F) ** 2 + (2 * F * F) ** 2) + ((t * t + F * F) ** 2 + 0.0),
+            "r_re": (0.0 + (-F * F + F * F)) + ((t * -F + F * F) + 0.0), "r_im": (0.0 + (F * F - -F * F)) + ((F * -F - t * F) + 0.0),
+            "peak": 2 * F * F}
+    for name in NAMES_AND_PEAK:
+        assert bits_of(s[name]) == bits_of(want[name]) and np.isfinite(s[name]), (name, s[name], want[name])
+    assert s["s_re"] == t and s["peak_index"] == 0 and s["q"] > 2.0 ** 515
+    # the buffer of the GPU tier: subnormals alone in front (exact sums, none of them zero), FLT_MAX behind, all finite
+    z = extremes_buffer(700, 400)
+    assert np.all(np.abs(z[:400].real) >= TINY) and np.all(np.abs(z[:400].real) <= 3 * TINY) and np.all(np.abs(z[400:].real) == FMAX)
+    s = special_sums(z[:257], 0j, 7)
+    k = np.arange(257)
+    assert s["s_re"] == float(np.sum(((k % 3) + 1) * (1 - 2 * (k % 2)))) * t != 0.0 and s["p"] > 0.0 and s["q"] > 0.0 and s["r_re"] != 0.0
+    for a, n in ((0, 700), (300, 257), (400, 300), (399, 2)):
+        s = special_sums(z[a:a + n], 0j, 1)
+        assert all(np.isfinite(s[name]) for name in NAMES_AND_PEAK), (a, n, s)
 
 
 @pytest.mark.parametrize("lag", [1, 3])
