@@ -13,7 +13,7 @@
 // in one copy and one wait.  The filter state of fsea_fir, fsea_zoom and fsea_pfb is FirState (fsea_fir_stage.h), whose
 // tail length each object gives at create: FSEA_FIR_MAX_TAPS samples, or the bank's L - 1.  What fsea_persist, fsea_cfar
 // and fsea_events share as consumers of rows of levels -- the head of their structs, the row checks, the packing of host
-// rows, the zeroed accumulator -- is fsea_rows.h; what fsea_extract and fsea_measure share as runners of a table of jobs
+// rows, the zeroed accumulator -- is fsea_rows.h; what fsea_extract, fsea_measure and fsea_audio share as runners of a table of jobs
 // -- the look-up on the device, the table's way there, the checks of a table -- is fsea_jobs.h.  What stays written out:
 // fsea_plan_reset (it clears the counter slots too), fsea_interp_reset (nothing to zero and no second wait without
 // elements), and the two device-wide waits of fsea_demod (before an evicted index table is released and before the

@@ -1,6 +1,7 @@
-// fsea_jobs.h -- what the objects that run a table of jobs over one resident buffer share: fsea_extract (fsea_extract.hip)
-// and fsea_measure (fsea_measure.hip).  The look-up of a workgroup's job on the device, the table's way from the caller to
-// the device (JobTable: built in mapped host memory, copied by the one kernel fsea_jobs_upload, ordered by two events), the
+// fsea_jobs.h -- what the objects that run a table of jobs over one resident buffer share: fsea_extract (fsea_extract.hip),
+// fsea_measure (fsea_measure.hip) and fsea_audio (fsea_audio.hip).  The look-up of a workgroup's job on the device, the
+// table's way from the caller to the device (JobTable: built in mapped host memory, copied by the one kernel
+// fsea_jobs_upload, ordered by two events), the
 // two numbers a table needs beside its entries, and the checks of a job table with the one text each has.  What a job is,
 // what a kernel does with it and what lies behind the table in the scratch are each file's own.  Everything has internal
 // linkage but jobs_upload, whose body stands beside its kernel in fsea_api.hip: the library is built without relocatable
@@ -11,7 +12,7 @@
 
 namespace fsea_detail {
 
-static_assert(FSEA_MEASURE_MAX_JOBS == FSEA_EXTRACT_MAX_JOBS, "one cap of a job table");
+static_assert(FSEA_MEASURE_MAX_JOBS == FSEA_EXTRACT_MAX_JOBS && FSEA_AUDIO_MAX_JOBS == FSEA_EXTRACT_MAX_JOBS, "one cap of a job table");
 
 // fsea_jobs_upload on `s`: n_words 32-bit words from mapped host memory (its host address) to device memory, one a lane
 int jobs_upload(const void *h_table, void *d_table, uint32_t n_words, hipStream_t s);
@@ -90,7 +91,7 @@ int check_jobs_count(size_t n_jobs) {
     return FSEA_OK;
 }
 
-// object (`name`: "extract" or "measure"), count, table and the two buffers of a run; no jobs: a no-op, nothing more is looked at
+// object (`name`: "extract", "measure" or "audio"), count, table and the two buffers of a run; no jobs: a no-op, nothing more is looked at
 int check_jobs_head(const void *obj, const char *name, size_t n_jobs, const void *jobs, const void *in, const void *out) {
     if (!obj) return fail(FSEA_EINVAL, "%s is NULL", name);
     if (int rc = check_jobs_count(n_jobs)) return rc;

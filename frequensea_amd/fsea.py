@@ -57,6 +57,10 @@ MEASURE_TILE_PAIRS = 4096       # FSEA_MEASURE_TILE_PAIRS: pairs per workgroup o
 MEASURE_MAX_JOBS = 65536        # FSEA_MEASURE_MAX_JOBS
 MEASURE_MAX_PAIRS = 1 << 24     # FSEA_MEASURE_MAX_PAIRS, per job
 MEASURE_MAX_LAG = 65536         # FSEA_MEASURE_MAX_LAG
+AUDIO_FM, AUDIO_AM = 0, 1       # FSEA_AUDIO_*: kind
+AUDIO_MAX_DECIMATION = 64       # FSEA_AUDIO_MAX_DECIMATION
+AUDIO_MAX_JOBS = 65536          # FSEA_AUDIO_MAX_JOBS
+AUDIO_MAX_PAIRS = 1 << 24       # FSEA_AUDIO_MAX_PAIRS, per job
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
 DEMOD_MAX_CHANNELS = 256            # FSEA_DEMOD_MAX_CHANNELS
@@ -108,6 +112,11 @@ class MeasureResult(ctypes.Structure):
     _fields_ = [("mean_power", ctypes.c_double), ("power_db", ctypes.c_double), ("dc_re", ctypes.c_double), ("dc_im", ctypes.c_double),
                 ("freq_cycles", ctypes.c_double), ("coherence", ctypes.c_double), ("width_cycles", ctypes.c_double),
                 ("kurtosis", ctypes.c_double), ("crest", ctypes.c_double), ("peak_index", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64)]
+
+
+class AudioJob(ctypes.Structure):
+    """fsea_audio_job (include/fsea.h): a span of a resident buffer of pairs and the place of its audio."""
+    _fields_ = [("first_pair", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64), ("out_first", ctypes.c_uint64)]
 
 
 class CaptureRun(ctypes.Structure):
@@ -256,6 +265,14 @@ API = {
     "fsea_measure_run_host": (_ci, [_vp, _vp, _sz, _vp, _sz, _f64, _f64, _ci, _vp]),
     "fsea_measure_jobs": (_ci, [_vp, _sz, _ci, _sz, _vp]),
     "fsea_measure_finish": (_ci, [_vp, _ci, _vp]),
+    "fsea_audio_create": (_ci, [_out, _ci, _vp, _ci, _ci, _ci]),
+    "fsea_audio_destroy": (_ci, [_vp]),
+    "fsea_audio_kind": (_ci, [_vp]),
+    "fsea_audio_decimation": (_ci, [_vp]),
+    "fsea_audio_n_taps": (_ci, [_vp]),
+    "fsea_audio_layout": (_ci, [_vp, _vp, _sz, _szp]),
+    "fsea_audio_run_device": (_ci, [_vp, _vp, _sz, _vp, _sz, _f64, _f64, _f64, _vp, _sz, _vp]),
+    "fsea_audio_run_host": (_ci, [_vp, _vp, _sz, _vp, _sz, _f64, _f64, _f64, _vp, _sz]),
     "fsea_iq_draw_create": (_ci, [_out, _ci]),
     "fsea_iq_draw_destroy": (_ci, [_vp]),
     "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
@@ -1107,6 +1124,56 @@ class Measure(_Handle):
         offset = complex(offset)
         _check(self._L.fsea_measure_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, _address(table), len(table), offset.real,
                                                offset.imag, int(lag), d_sums_ptr or None, stream or None))
+
+
+def audio_layout(jobs, decimation):
+    """What fsea_audio_layout does, without an object: (the jobs as a ctypes array of AudioJob with out_first filled in back
+    to back in table order, the floats they need in all); a job of n pairs has n // decimation outputs."""
+    table = _table_of(AudioJob, jobs)
+    at = 0
+    for j in table:
+        j.out_first = at
+        at += j.n_pairs // int(decimation)
+    return table, at
+
+
+class Audio(_Handle):
+    """Cut-out audio on one device: a table of spans of one buffer of complex64 in, every span's FM-discriminated
+    (kind "fm") or envelope-detected ("am"), low-passed and decimated float32 audio out, in one launch, stateless; thin
+    wrapper over fsea_audio_*.  run() takes the pairs and the jobs from the host and returns one float32 array per job;
+    run_device() works on resident memory with the jobs' own out_first."""
+    _kind = "audio"
+
+    def __init__(self, kind, taps, decimation, device=0):
+        t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
+        self.kind = {"fm": AUDIO_FM, "am": AUDIO_AM}.get(kind, kind)
+        self.n_taps, self.decimation, self.device = t.size, decimation, device
+        self._create("fsea_audio_create", self.kind, t.ctypes.data if t.size else None, t.size, decimation, device)
+
+    def layout(self, jobs):
+        """fsea_audio_layout: (the jobs as a ctypes array with out_first filled in, the floats they need in all)."""
+        table = _table_of(AudioJob, jobs)
+        total = ctypes.c_size_t()
+        _check(self._L.fsea_audio_layout(self._p, _address(table), len(table), ctypes.byref(total)))
+        return table, total.value
+
+    def run(self, pairs, jobs, offset=0j, gain=1.0):
+        """The host form on a copy of the jobs laid out with layout(): a list of float32 arrays, one per job."""
+        z = np.ascontiguousarray(pairs, dtype=np.complex64).ravel()
+        table, total = self.layout([AudioJob.from_buffer_copy(j) for j in jobs])
+        audio = np.zeros(max(total, 1), dtype=np.float32)
+        offset = complex(offset)
+        _check(self._L.fsea_audio_run_host(self._p, z.ctypes.data, z.size, _address(table), len(table), offset.real, offset.imag,
+                                           float(gain), audio.ctypes.data, total))
+        return [audio[j.out_first:j.out_first + j.n_pairs // self.decimation].copy() for j in table]
+
+    def run_device(self, d_pairs_ptr, n_buffer_pairs, jobs, d_audio_ptr, n_audio, offset=0j, gain=1.0, stream=0):
+        """Device pointers (ints): n_buffer_pairs complex64 in (8-byte aligned), n_audio float32 out (4-byte aligned), every
+        job at its own out_first; asynchronous.  The jobs are read before the call returns."""
+        table = _table_of(AudioJob, jobs)
+        offset = complex(offset)
+        _check(self._L.fsea_audio_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, _address(table), len(table), offset.real,
+                                             offset.imag, float(gain), d_audio_ptr or None, n_audio, stream or None))
 
 
 class Demod(_ResettableHandle):

@@ -26,10 +26,23 @@
  * the eight measures as %.9e (fsea_measure_finish); freq_mhz is what freq_cycles adds to the event's centre_mhz, 0 without
  * --rate.  Without --measures nothing of this happens and no such file is written.
  *
+ * --audio fm|am says what each cut-out carries.  After a batch's fsea_extract_run_device (and the measures), with the pairs
+ * still resident, one fsea_audio_run_device (include/fsea.h) demodulates the spans the .cf32 files get: the FM discriminator
+ * or the AM envelope, an --audio-taps low-pass (default 41 taps, half amplitude at --audio-cutoff, default 0.4 of the audio
+ * rate) and a decimation by D2 = RATE / D over --audio-rate (default 48000), rounded, in [1, 64]; the same offset as the
+ * measures.  FM: gain = (RATE / D) / (2 pi --deviation), so a deviation of --deviation Hz (default 75000) is an amplitude of
+ * 1; AM: gain 1 and the cut-out's mean taken off on the host.  DIR/cutout-%05u.wav is mono 16-bit PCM at RATE / D / D2 (the
+ * header's rate rounded to a whole number), sample = (int16_t)(audio * 32000) as nrf_player's, saturated; DIR/audio.txt gets
+ * one line per file:
+ *     number rate samples peak
+ * (peak: the largest |audio| written, before the scale), and the summary line gains ` audio A`, the files written.  Without
+ * --audio nothing of this happens.
+ *
  * usage: fsea-cutouts FILE --size N --decimation D --out DIR [--hop H] [--window NAME] [--flip] [--mode db5|db10|db]
  *                     [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R]
  *                     [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--taps L] [--cutoff HZ]
  *                     [--fill F] [--max-events E] [--max-samples S] [--measures [--lag K]]
+ *                     [--audio fm|am [--audio-rate HZ] [--audio-taps N] [--audio-cutoff HZ] [--deviation HZ]]
  */
 #include <errno.h>
 #include <limits.h>
@@ -50,18 +63,53 @@ static const char *USAGE =
     "                    [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R]\n"
     "                    [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--taps L] [--cutoff HZ]\n"
     "                    [--fill F] [--max-events E] [--max-samples S] [--measures [--lag K]]\n"
+    "                    [--audio fm|am [--audio-rate HZ] [--audio-taps N] [--audio-cutoff HZ] [--deviation HZ]]\n"
     "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8).  The emissions are found as fsea-events finds them (its\n"
     "  options, same defaults); each one whose columns times D fill at most F of the N columns is mixed to the centre,\n"
     "  low-passed (L taps, half amplitude at --cutoff, default 0.4 RATE / D) and decimated by D on the GPU, all of a batch in\n"
     "  one launch, and written to DIR/cutout-NNNNN.cf32 as f32 pairs; DIR/cutouts.txt lists every event.  A cut-out longer\n"
     "  than S samples is cut short.  --measures: DIR/measures.txt says of every cut-out written its power in dB, its\n"
     "  frequency offset (lag K pairs, default 1), spectrum width, envelope kurtosis, crest factor and what is left of its DC.\n"
-    "  Prints `rows R runs N events E cutouts C skipped S`\n"
-    "  defaults: --taps 97 --fill 0.8 --max-events 1024 --max-samples 16777216";
+    "  --audio: every cut-out written is FM- or AM-demodulated on the GPU, low-passed (N taps, half amplitude at\n"
+    "  --audio-cutoff, default 0.4 of the audio rate) and decimated to about --audio-rate; DIR/cutout-NNNNN.wav is mono 16-bit\n"
+    "  PCM, full scale at --deviation for FM, and DIR/audio.txt lists number, rate, samples and peak of every file.  Needs --rate.\n"
+    "  Prints `rows R runs N events E cutouts C skipped S`, with --audio followed by ` audio A`\n"
+    "  defaults: --taps 97 --fill 0.8 --max-events 1024 --max-samples 16777216 --audio-rate 48000 --audio-taps 41 --deviation 75000";
 
 static void usage_error(const char *msg) { tool_usage_error(TOOL, msg); }
 
 static void die(const char *what) { tool_die(TOOL, what); }
+
+/* 16 and 32 bits, little-endian */
+static void put_le(uint8_t *at, uint32_t value, int bytes) {
+    for (int i = 0; i < bytes; i++) at[i] = (uint8_t)(value >> (8 * i));
+}
+
+/* DIR/cutout-NNNNN.wav: the 44-byte header of mono 16-bit PCM and n samples; 0 when everything was written */
+static int write_wav(const char *name, uint32_t rate, const int16_t *pcm, size_t n) {
+    uint8_t head[44];
+    memcpy(head, "RIFF", 4);
+    put_le(head + 4, (uint32_t)(36 + 2 * n), 4);
+    memcpy(head + 8, "WAVEfmt ", 8);
+    put_le(head + 16, 16, 4);
+    put_le(head + 20, 1, 2);        /* PCM */
+    put_le(head + 22, 1, 2);        /* one channel */
+    put_le(head + 24, rate, 4);
+    put_le(head + 28, 2 * rate, 4); /* bytes a second */
+    put_le(head + 32, 2, 2);        /* bytes a sample */
+    put_le(head + 34, 16, 2);
+    memcpy(head + 36, "data", 4);
+    put_le(head + 40, (uint32_t)(2 * n), 4);
+    FILE *out = fopen(name, "wb");
+    if (out == NULL) return 1;
+    int bad = fwrite(head, 1, sizeof(head), out) != sizeof(head);
+    for (size_t i = 0; i < n && !bad; i++) {
+        uint8_t two[2];
+        put_le(two, (uint16_t)pcm[i], 2);
+        bad = fwrite(two, 1, 2, out) != 2;
+    }
+    return (fclose(out) != 0) | bad;
+}
 
 /* a file of the output that could not be written, for main's exit status */
 static int cannot_write(const char *name) {
@@ -73,7 +121,9 @@ int main(int argc, char **argv) {
     const char *path = NULL, *out_dir = NULL, *window = "rect", *mode_name = "db5";
     int size = 0, hop = 0, flip = 0, gap_cols = 0, gap_rows = 0, decimation = 0, n_taps = 97, measures = 0, lag = 1;
     long long min_rows = 1, min_cols = 1, min_hits = 1, max_events = 1024, max_samples = 1ll << 24;
-    double cutoff = 0.0, fill = 0.8;
+    double cutoff = 0.0, fill = 0.8, audio_rate = 48000.0, audio_cutoff = 0.0, deviation = 75000.0;
+    const char *audio_name = NULL;
+    int audio_taps = 41;
     tool_detector det = TOOL_DETECTOR_DEFAULTS;
     for (int i = 1; i < argc; i++) {
         const int more = i + 1 < argc;
@@ -99,6 +149,11 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--max-samples") && more) max_samples = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--measures")) measures = 1;
         else if (!strcmp(argv[i], "--lag") && more) lag = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--audio") && more) audio_name = argv[++i];
+        else if (!strcmp(argv[i], "--audio-rate") && more) audio_rate = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--audio-taps") && more) audio_taps = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--audio-cutoff") && more) audio_cutoff = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--deviation") && more) deviation = atof(argv[++i]);
         else if (!strcmp(argv[i], "--out") && more) out_dir = argv[++i];
         else if (argv[i][0] != '-' && path == NULL) path = argv[i];
         else usage_error(USAGE);
@@ -124,6 +179,22 @@ int main(int argc, char **argv) {
     if (max_samples < 1 || max_samples > (1ll << 24)) usage_error("--max-samples must be in [1, 16777216]");
     if (cutoff < 0.0) usage_error("--cutoff must be positive");
     if (lag < 1 || lag > FSEA_MEASURE_MAX_LAG) usage_error("--lag must be in [1, 65536]");
+    int audio_kind = -1, audio_decimation = 1;
+    if (audio_name != NULL) {
+        audio_kind = !strcmp(audio_name, "fm") ? FSEA_AUDIO_FM : !strcmp(audio_name, "am") ? FSEA_AUDIO_AM : -1;
+        if (audio_kind < 0) usage_error("--audio must be fm or am");
+        if (!(rate > 0.0)) usage_error("--audio needs --rate: the audio rate is in Hz");
+        if (decimation >= 1 && decimation <= FSEA_ZOOM_MAX_DECIMATION) {
+            const double ratio = rate / (double)decimation / audio_rate;
+            if (!(audio_rate > 0.0) || !(ratio >= 0.5) || !(ratio < FSEA_AUDIO_MAX_DECIMATION + 0.5)) {
+                usage_error("--audio-rate must be RATE / D over a whole number in [1, 64], rounded");
+            }
+            audio_decimation = (int)(ratio + 0.5);
+        }
+        if (audio_taps < 1 || audio_taps > FSEA_FIR_MAX_TAPS) usage_error("--audio-taps must be in [1, 512]");
+        if (audio_cutoff < 0.0) usage_error("--audio-cutoff must be positive");
+        if (!(deviation > 0.0)) usage_error("--deviation must be positive");
+    }
     if (out_dir == NULL) usage_error("--out DIR is required");
     int mode = 0, type = 0;
     if (!tool_rows_mode(mode_name, "db", &mode, &type)) usage_error("--mode must be db5, db10 or db");
@@ -173,6 +244,33 @@ int main(int argc, char **argv) {
     fsea_measure_sums *h_sums = NULL;
     void *d_sums = NULL;
     double pedestal = 0.0;
+    if (measures || audio_kind >= 0) {
+        for (int k = 0; k < n_taps; k++) pedestal += (double)(float)taps[k];
+        pedestal *= 0.5;
+    }
+    /* --audio: the object, the spans and their audio jobs, the audio of a batch on the device and on the host */
+    fsea_audio *audio = NULL;
+    fsea_measure_job *audio_spans = NULL;
+    fsea_audio_job *audio_jobs = NULL;
+    void *d_audio = NULL;
+    float *h_audio = NULL;
+    int16_t *pcm = NULL;
+    size_t audio_cap = 0, pcm_cap = 0, n_audio_files = 0;
+    double out_rate = 0.0, audio_gain = 1.0;
+    FILE *audio_list = NULL;
+    if (audio_kind >= 0) {
+        const double pair_rate = rate / (double)decimation;
+        out_rate = pair_rate / (double)audio_decimation;
+        if (audio_cutoff == 0.0) audio_cutoff = 0.4 * out_rate;
+        double *audio_c = (double *)malloc(sizeof(double) * (size_t)audio_taps);
+        audio_spans = (fsea_measure_job *)malloc(sizeof(fsea_measure_job) * (n_jobs + 1));
+        audio_jobs = (fsea_audio_job *)malloc(sizeof(fsea_audio_job) * (n_jobs + 1));
+        if (audio_c == NULL || audio_spans == NULL || audio_jobs == NULL) usage_error("out of memory");
+        if (fsea_fir_lowpass_taps(pair_rate, audio_cutoff, audio_taps, audio_c) != FSEA_OK) die("fsea_fir_lowpass_taps");
+        if (fsea_audio_create(&audio, audio_kind, audio_c, audio_taps, audio_decimation, 0) != FSEA_OK) die("fsea_audio_create");
+        free(audio_c);
+        if (audio_kind == FSEA_AUDIO_FM) audio_gain = pair_rate / (2.0 * 3.14159265358979323846 * deviation);
+    }
     if (measures) {
         if (fsea_measure_create(&measure, 0) != FSEA_OK) die("fsea_measure_create");
         measured = (fsea_measure_result *)calloc(n_jobs + 1, sizeof(fsea_measure_result));
@@ -180,8 +278,6 @@ int main(int argc, char **argv) {
         h_sums = (fsea_measure_sums *)malloc(sizeof(fsea_measure_sums) * (n_jobs + 1));
         if (measured == NULL || spans == NULL || h_sums == NULL) usage_error("out of memory");
         if (fsea_device_alloc(0, sizeof(fsea_measure_sums) * (n_jobs + 1), &d_sums) != FSEA_OK) die("fsea_device_alloc");
-        for (int k = 0; k < n_taps; k++) pedestal += (double)(float)taps[k];
-        pedestal *= 0.5;
     }
     if (mkdir(out_dir, 0777) != 0 && errno != EEXIST) {
         fprintf(stderr, TOOL ": cannot create directory %s\n", out_dir);
@@ -190,6 +286,11 @@ int main(int argc, char **argv) {
 
     size_t name_len = strlen(out_dir) + 32, n_cutouts = 0;
     char *name = (char *)malloc(name_len);
+    if (audio_kind >= 0 && name != NULL) {
+        snprintf(name, name_len, "%s/audio.txt", out_dir);
+        audio_list = fopen(name, "w");
+        if (audio_list == NULL) return cannot_write(name);
+    }
     fsea_extract_job *batch = (fsea_extract_job *)malloc(sizeof(fsea_extract_job) * (n_jobs + 1));
     size_t *batch_of = (size_t *)malloc(sizeof(size_t) * (n_jobs + 1));
     void *h_iq = NULL, *d_iq = NULL, *d_pairs = NULL;
@@ -240,6 +341,33 @@ int main(int argc, char **argv) {
                 if (fsea_measure_finish(&h_sums[b], lag, &measured[batch_of[b]]) != FSEA_OK) die("fsea_measure_finish");
             }
         }
+        size_t total_audio = 0;
+        if (audio_kind >= 0) {
+            /* the spans the files get, as the measures'; every span's audio back to back */
+            if (fsea_measure_jobs(batch, n_batch, decimation, lead_out, audio_spans) != FSEA_OK) die("fsea_measure_jobs");
+            for (size_t b = 0; b < n_batch; b++) {
+                audio_jobs[b].first_pair = audio_spans[b].first_pair;
+                audio_jobs[b].n_pairs = audio_spans[b].n_pairs;
+                audio_jobs[b].out_first = 0;
+            }
+            if (fsea_audio_layout(audio, audio_jobs, n_batch, &total_audio) != FSEA_OK) die("fsea_audio_layout");
+            if (total_audio > audio_cap) {
+                if (d_audio != NULL) fsea_device_free(0, d_audio);
+                if (h_audio != NULL) fsea_host_free(h_audio);
+                audio_cap = total_audio + total_audio / 2;
+                void *h = NULL;
+                if (fsea_device_alloc(0, audio_cap * sizeof(float), &d_audio) != FSEA_OK) die("fsea_device_alloc");
+                if (fsea_host_alloc(audio_cap * sizeof(float), &h) != FSEA_OK) die("fsea_host_alloc");
+                h_audio = (float *)h;
+            }
+            if (total_audio > 0) {
+                if (fsea_audio_run_device(audio, d_pairs, total, audio_jobs, n_batch, pedestal, pedestal, audio_gain, (float *)d_audio,
+                                          total_audio, NULL) != FSEA_OK) {
+                    die("fsea_audio_run_device");
+                }
+                if (fsea_copy_to_host(0, h_audio, d_audio, total_audio * sizeof(float)) != FSEA_OK) die("fsea_copy_to_host");
+            }
+        }
         if (fsea_copy_to_host(0, h_pairs, d_pairs, total * 2 * sizeof(float)) != FSEA_OK) die("fsea_copy_to_host");
         for (size_t b = 0; b < n_batch; b++) {
             const size_t n_out = (size_t)batch[b].n_samples / (size_t)decimation, e = batch_of[b];
@@ -253,6 +381,31 @@ int main(int argc, char **argv) {
             }
             written[e] = keep;
             n_cutouts++;
+            if (audio_kind >= 0) {
+                const size_t n_audio = (size_t)audio_jobs[b].n_pairs / (size_t)audio_decimation;
+                const float *a = h_audio + audio_jobs[b].out_first;
+                if (n_audio == 0) continue;
+                if (n_audio > pcm_cap) {
+                    free(pcm);
+                    pcm_cap = n_audio + n_audio / 2;
+                    pcm = (int16_t *)malloc(sizeof(int16_t) * pcm_cap);
+                    if (pcm == NULL) usage_error("out of memory");
+                }
+                double mean = 0.0, peak = 0.0;
+                if (audio_kind == FSEA_AUDIO_AM) {   /* the carrier's level: the sum in order, over the count */
+                    for (size_t i = 0; i < n_audio; i++) mean += (double)a[i];
+                    mean /= (double)n_audio;
+                }
+                for (size_t i = 0; i < n_audio; i++) {
+                    const double v = (double)a[i] - mean, s = v * 32000.0, mag = v < 0.0 ? -v : v;
+                    if (mag > peak) peak = mag;
+                    pcm[i] = s >= 32767.0 ? 32767 : s <= -32768.0 ? -32768 : s == s ? (int16_t)s : 0;
+                }
+                snprintf(name, name_len, "%s/cutout-%05u.wav", out_dir, (unsigned)e);
+                if (write_wav(name, (uint32_t)(out_rate + 0.5), pcm, n_audio)) return cannot_write(name);
+                fprintf(audio_list, "%u %.3f %zu %.6f\n", (unsigned)e, out_rate, n_audio, peak);
+                n_audio_files++;
+            }
         }
     }
 
@@ -285,7 +438,20 @@ int main(int argc, char **argv) {
         free(spans);
         free(h_sums);
     }
-    printf("rows %zu runs %zu events %zu cutouts %zu skipped %zu\n", done, runs.n, n_events, n_cutouts, n_events - n_cutouts);
+    if (audio_kind >= 0) {
+        snprintf(name, name_len, "%s/audio.txt", out_dir);
+        if (fclose(audio_list) != 0) return cannot_write(name);
+        fsea_audio_destroy(audio);
+        if (d_audio != NULL) fsea_device_free(0, d_audio);
+        if (h_audio != NULL) fsea_host_free(h_audio);
+        free(pcm);
+        free(audio_spans);
+        free(audio_jobs);
+        printf("rows %zu runs %zu events %zu cutouts %zu skipped %zu audio %zu\n", done, runs.n, n_events, n_cutouts, n_events - n_cutouts,
+               n_audio_files);
+    } else {
+        printf("rows %zu runs %zu events %zu cutouts %zu skipped %zu\n", done, runs.n, n_events, n_cutouts, n_events - n_cutouts);
+    }
 
     fsea_extract_destroy(extract);
     fsea_events_destroy(events);

@@ -37,6 +37,8 @@
  *   fsea_events_*         spectrum events (no counterpart in the reference): a detection mask as runs, time-frequency boxes
  *   fsea_extract_*        event cut-outs (no counterpart in the reference): each box of fsea_events_link as decimated IQ
  *   fsea_measure_*        signal measures (no counterpart in the reference): power, offset, width and envelope of each cut-out
+ *   fsea_audio_*          cut-out audio: the FM discriminator of nrf_demodulate's WBFM branch, src/nrf.c:969-993, or the AM
+ *                         envelope, low-passed and decimated, for every cut-out of a table at once
  *   fsea_detect_*         the burst detector of lua/signal-detector.lua: the two loops of nrf_signal_detector_process,
  *                         src/nrf.c:883-898, as integer sums over many blocks per launch
  *   fsea_capture_*        that scene on a resident recording: detect -> gate -> filter the bursts -> line images
@@ -948,6 +950,81 @@ int fsea_measure_run_host(fsea_measure *m, const float *pairs, size_t n_buffer_p
                           size_t n_jobs, double offset_re, double offset_im, int lag, fsea_measure_sums *sums);
 int fsea_measure_jobs(const fsea_extract_job *ejobs, size_t n_jobs, int decimation, size_t skip_pairs, fsea_measure_job *jobs);
 int fsea_measure_finish(const fsea_measure_sums *sums, int lag, fsea_measure_result *result);
+
+/* Cut-out audio: what each cut-out carries -- the FM discriminator of the reference's WBFM chain or the AM envelope, then a
+ * real low-pass that keeps every D-th value.  fsea_demod does this for one continuous 8-bit stream at the reference's fixed
+ * rates, with state from call to call; an event list is hundreds of short cut-outs that already lie resident as centred,
+ * band-limited f32 pairs (what fsea_extract_run_device left).  An fsea_audio holds the kind, L real f64 taps c and the
+ * decimation D, takes a table of jobs over that buffer and gives every job's audio in one launch.  There is no state between
+ * calls and no reset.
+ *   terms:      for pair i of a job, z_i = pairs[first_pair + i], in f64 with exactly the roundings written here (rn = one
+ *               IEEE rounding, round to nearest even; nothing is contracted into an FMA; / and sqrt are correctly rounded):
+ *                 a_i = rn((double)re_i - offset_re),   b_i = rn((double)im_i - offset_im);
+ *               offset is the pedestal the caller knows, (0.5 + 0.5j) sum(c) of the extract's taps, as for the measures.
+ *   FM:         d_0 = +0.0: the first pair has none before it.  For i >= 1, with (a', b') = (a_(i-1), b_(i-1)):
+ *                 real = rn(rn(a' a) + rn(b' b)),   imag = rn(rn(a' b) - rn(a b')),
+ *               then the reference's arctangent (src/nrf.c:971-991) without its ampl_conv factor: sgn = +1; if imag < 0:
+ *               sgn = -1, imag = -imag.  If real == imag: ang = 0, div = 1; else if real > imag: ang = 0, div = rn(imag /
+ *               real); else: ang = -pi / 2 (the double nearest to it), div = rn(real / imag), sgn = -sgn.
+ *                 d_i = sgn rn(ang + rn(div / rn(0.98419158358617365 + rn(div rn(0.093485702629671305 +
+ *                                                                              rn(div 0.19556307900617517))))))
+ *               One deviation from the reference: where real and imag are both zero (either sign) d_i = +0.0; the reference's
+ *               real == imag branch gives 0.785 for a silent pair.  A NaN or an infinity in a pair gives what these
+ *               expressions and comparisons give: with a NaN no comparison holds, the third branch divides and d_i is NaN.
+ *               d is in radians per pair.  The expression is the reference's and so is its error: within 9.4e-4 of
+ *               atan2(imag, real) for a phase step of at most a quarter turn (real >= 0); behind that it falls away from
+ *               the angle, 0.14 off at three eighths of a turn and pi / 2 off at half a turn.  An emission belongs in the
+ *               inner half of the cut-out's band: offset plus deviation below a quarter of the pair rate.
+ *   AM:         d_i = sqrt(rn(rn(a_i a_i) + rn(b_i b_i))) for every i.
+ *   filter:     with d_ext = (L - 1 values of +0.0) ++ d, output j of a job of n pairs, j < n / D (rounded down):
+ *                 acc = +0.0;  for k = 0 .. L - 1 ascending: acc = rn(acc + rn(c[k] d_ext[j D + k]));
+ *                 audio[out_first + j] = (float) rn(gain acc)      (the conversion rounds to nearest even).
+ *               An accumulator is never -0.0: it starts at +0.0, and a sum in round-to-nearest is -0.0 only when both of its
+ *               operands are -0.0.  So a term rn(c[k] (+0.0)) = +-0.0 of the zero prefix leaves it as it is and may be added
+ *               or left out: the same bits.
+ *               An output depends on the job's pairs alone: not on first_pair (at any parity), on the other jobs, on their
+ *               order, on the tile size or on the launch geometry.
+ *   table:      jobs may overlap and may repeat in the input; their output ranges must not overlap and lie inside n_audio.
+ *               A job with n_pairs < D (an empty one too) has no output, writes nothing and is legal.  Only the jobs' pairs
+ *               are read, only the jobs' outputs are written.  `jobs` is host memory, read before the call returns.
+ *   create:     kind FSEA_AUDIO_FM or FSEA_AUDIO_AM; 1 .. FSEA_FIR_MAX_TAPS finite taps, kept as f64 on the device;
+ *               decimation in [1, FSEA_AUDIO_MAX_DECIMATION].  FSEA_EINVAL, in this order, for a NULL out-pointer, another
+ *               kind, NULL taps, n_taps out of range, a tap that is not finite, decimation out of range; only then
+ *               FSEA_ENODEVICE without a GPU.  kind returns -1 for NULL, decimation and n_taps 0.  Destroy waits for the device.
+ *   layout:     fills out_first back to back in table order (job k's n_pairs / D outputs behind job k - 1's) and gives the
+ *               floats needed in *total_outputs.  FSEA_EINVAL for a NULL object or total_outputs, n_jobs above
+ *               FSEA_AUDIO_MAX_JOBS, a NULL table with n_jobs > 0.
+ *   run_device: d_pairs (n_buffer_pairs pairs of floats) 8-byte aligned, d_audio (n_audio floats) 4-byte aligned;
+ *               asynchronous on `stream`.  The object owns the device copy of the table, so calls on several streams follow
+ *               one another (an event).  A call is one upload of the table and one launch of fsea_audio_tiles: one workgroup
+ *               per tile of T outputs of one job, which it finds by a bisection over the jobs' first tiles; T is the largest
+ *               count up to 256 for which T D + L - 1 <= 4096, a constant of the object that no output depends on.
+ *   run_host:   the same from and to host memory through pinned staging on the object's own stream; returns when `audio` is
+ *               complete; of `audio` only the jobs' output ranges are written.
+ * Both check, before any device work and reading nothing of the object but its decimation, in this order: a NULL object;
+ * n_jobs above FSEA_AUDIO_MAX_JOBS; n_jobs == 0 is then a successful no-op; a NULL job table; a NULL buffer (pairs or audio);
+ * an offset that is not finite; a gain that is not finite; per job in table order: first_pair + n_pairs past n_buffer_pairs,
+ * n_pairs above FSEA_AUDIO_MAX_PAIRS, for a job with output out_first + n_pairs / D past n_audio (each text names the job);
+ * two output ranges that overlap (the text names both jobs); more than 2^31 outputs in the call; for run_device a d_pairs
+ * that is not 8-byte or a d_audio that is not 4-byte aligned.  All FSEA_EINVAL; a refused call writes nothing.  Calls on one
+ * object from several threads are serialised. */
+#define FSEA_AUDIO_FM 0
+#define FSEA_AUDIO_AM 1
+#define FSEA_AUDIO_MAX_DECIMATION 64
+#define FSEA_AUDIO_MAX_JOBS  65536        /* = FSEA_EXTRACT_MAX_JOBS */
+#define FSEA_AUDIO_MAX_PAIRS (1u << 24)   /* per job */
+typedef struct { uint64_t first_pair, n_pairs, out_first; } fsea_audio_job;   /* 24 bytes */
+typedef struct fsea_audio fsea_audio;
+int fsea_audio_create(fsea_audio **audio, int kind, const double *taps, int n_taps, int decimation, int device);
+int fsea_audio_destroy(fsea_audio *audio);
+int fsea_audio_kind(const fsea_audio *audio);
+int fsea_audio_decimation(const fsea_audio *audio);
+int fsea_audio_n_taps(const fsea_audio *audio);
+int fsea_audio_layout(const fsea_audio *audio, fsea_audio_job *jobs, size_t n_jobs, size_t *total_outputs);
+int fsea_audio_run_device(fsea_audio *audio, const void *d_pairs, size_t n_buffer_pairs, const fsea_audio_job *jobs, size_t n_jobs,
+                          double offset_re, double offset_im, double gain, float *d_audio, size_t n_audio, void *stream);
+int fsea_audio_run_host(fsea_audio *audio, const float *pairs, size_t n_buffer_pairs, const fsea_audio_job *jobs, size_t n_jobs,
+                        double offset_re, double offset_im, double gain, float *audio_out, size_t n_audio);
 
 /* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
  * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With
