@@ -49,6 +49,30 @@ def check_db(got, want_db, want_mag_nodc):
     assert err.max(initial=0.0) <= 8.69 * PER_BIN_TOL / 1e-5 + 1e-3
 
 
+def check_db_bins(got, want_db, want_mag_nodc):
+    """dB rows (mode 5) bin by bin, for rows without numerically empty bins (tests/flat_ref.py).  check_db allows 1.7 dB
+    because it is written for rows with a dynamic range of 1e5; here every bin gets check_float's per-bin allowance on its
+    magnitude, 2e-6 * max + 1e-6, carried through the logarithm, plus the logarithm's own error L:
+        |got - want| <= 20 log10(1 + (2e-6 * max + 1e-6) / mag[k]) + L[k].
+    L: the kernels form (10 log10 2) * v_log_f32(p + 1e-20).  v_log_f32 (base 2) is stated as "1ULP accuracy, denormals are
+    flushed" in AMD's "Graphics Core Next Architecture, Generation 3" ISA reference (chapter 13, VOP1 opcodes, V_LOG_F32;
+    the later ISA guides list the opcode without a figure): 2^-23 of |log2 p|.  The product with the f32 constant adds one
+    rounding and the constant's own, 2^-24 each: together 2^-22 of |dB|.  Near p = 1 the result vanishes and nothing
+    promises an error relative to it, so the level is taken as at least one octave (3.01 dB).  p = re^2 + im^2 + 1e-20
+    carries three f32 roundings (one under contraction), 3 * 2^-24 relative, 10 log10(e) times that in dB.
+    Returns the worst excess over the first term alone, in dB (negative: inside it without L): what L has to cover."""
+    want_db = np.asarray(want_db, dtype=np.float64)
+    mag = np.asarray(want_mag_nodc, dtype=np.float64)
+    assert mag.min(initial=1.0) > 0.0, "check_db_bins is for rows without empty bins"
+    err = np.abs(np.asarray(got, dtype=np.float64) - want_db)
+    through_log = 20.0 * np.log10(1.0 + (PER_BIN_TOL * float(np.max(mag)) + 1e-6) / mag)
+    octave = 10.0 * 0.30102999566398120
+    bound = through_log + 2.0 ** -22 * np.maximum(np.abs(want_db), octave) + 10.0 * np.log10(np.e) * 3.0 * 2.0 ** -24
+    k = int(np.argmax(err - bound))
+    assert np.all(err <= bound), "dB error %.3e > %.3e at bin %d" % (err.flat[k], bound.flat[k], k)
+    return float(np.max(err - through_log))
+
+
 def check_mode(got, iq, n, n_frames, hop, flip, mode):
     want = O.rows(iq, n_frames, n, hop=hop, flip=flip, mode=ORACLE_MODE[mode])
     if mode in (1, 2):
