@@ -7,10 +7,11 @@
 // Kernel fsea_audio_tiles ("Cut-out audio"): one workgroup of AU_WG = 256 lanes per tile of T outputs of
 // one job; the grid is the sum of the jobs' tiles.  T is the object's: the largest count up to 256 whose T D + L - 1
 // discriminator values fit 4096 (audio_tile), as fsea_demod's stage 1 picks its own.  The device table is the caller's jobs
-// as they are and a column of first tiles, brought there as the other two bring theirs (fsea_jobs.h: JobTable); a workgroup
-// finds its job by job_of_tile, scalar loads.  Staging: the lanes stride over the tile's span of d_ext; each loads its pair
-// and the pair before it (the neighbour lane's line: a cache hit), converts, subtracts and computes d once; what lies in
-// front of the job is +0.0; an address in front of the job is the job's pair 0 and a select drops what it gave.  The values
+// as they are and a column of first tiles, built and brought there as the other two's (fsea_jobs.h: JobTable); a workgroup
+// finds its job by job_of_tile, scalar loads; the placement check, the layout and the host form are fsea_extract's too.
+// Staging: the lanes stride over the tile's span of d_ext; each loads its pair and the pair before it (the neighbour
+// lane's line: a cache hit), converts, subtracts and computes d once; what lies in front of the job is +0.0; an address
+// in front of the job is the job's pair 0 and a select drops what it gave.  The values
 // stand phase-major in LDS, value m of the span at [m mod D][m / D] with an odd pitch (the zoom's image, in doubles), so the
 // 64 ds_read_b64 of a wave's tap k touch 64 consecutive doubles: no bank conflict at any D.  The staging's writes go down a
 // column, rows `pitch` doubles apart: odd, so 16 lanes meet 16 different double-wide banks for D >= 16 and a 16 / D-way
@@ -23,7 +24,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
-#include <vector>
 
 // every product and sum below is rounded on its own: a'a + b'b, c[k] d + acc and the like must not become one FMA
 #pragma clang fp contract(off)
@@ -161,28 +161,13 @@ int check_run(const fsea_audio *a, const void *pairs, size_t n_buffer_pairs, con
     if (!std::isfinite(gain)) return fail(FSEA_EINVAL, "the gain is not finite");
     const uint64_t D = (uint64_t)a->decimation;
     uint64_t total = 0;
-    std::vector<uint32_t> order;
-    for (size_t i = 0; i < n_jobs; ++i) {
+    const int rc = fsea_detail::check_jobs_placement(n_jobs, n_audio, "", " of the audio", [&](size_t i, uint64_t *first, uint64_t *n) {
         const fsea_audio_job &j = jobs[i];
-        if (int rc = fsea_detail::check_job_span(i, j.first_pair, j.n_pairs, n_buffer_pairs, FSEA_AUDIO_MAX_PAIRS, "pairs", "buffer")) return rc;
-        const uint64_t n_out = j.n_pairs / D;
-        if (n_out == 0) continue;
-        if (n_out > n_audio || j.out_first > n_audio - n_out) {
-            return fail(FSEA_EINVAL, "job %zu: outputs %llu .. %llu + %llu lie past the %zu of the audio", i, (unsigned long long)j.out_first,
-                        (unsigned long long)j.out_first, (unsigned long long)n_out, n_audio);
-        }
-        total += n_out;
-        order.push_back((uint32_t)i);
-    }
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        return jobs[x].out_first != jobs[y].out_first ? jobs[x].out_first < jobs[y].out_first : x < y;
+        *first = j.out_first;
+        total += *n = j.n_pairs / D;
+        return fsea_detail::check_job_span(i, j.first_pair, j.n_pairs, n_buffer_pairs, FSEA_AUDIO_MAX_PAIRS, "pairs", "buffer");
     });
-    for (size_t k = 1; k < order.size(); ++k) {
-        const fsea_audio_job &x = jobs[order[k - 1]], &y = jobs[order[k]];
-        if (x.out_first + x.n_pairs / D > y.out_first) {
-            return fail(FSEA_EINVAL, "the outputs of jobs %u and %u overlap", std::min(order[k - 1], order[k]), std::max(order[k - 1], order[k]));
-        }
-    }
+    if (rc) return rc;
     return fsea_detail::check_jobs_total(total, "outputs");
 }
 
@@ -194,20 +179,13 @@ int queue_call(fsea_audio *a, const void *d_pairs, const fsea_audio_job *jobs, s
     uint64_t tiles = 0;
     for (size_t i = 0; i < n_jobs; ++i) tiles += (jobs[i].n_pairs / D + (unsigned)a->tile - 1) / (unsigned)a->tile;
     if (tiles == 0) return FSEA_OK;
-    const size_t table_bytes = n_jobs * (sizeof(fsea_audio_job) + sizeof(uint32_t));
-    fsea_audio_job *h_jobs = nullptr;
-    if (int rc = a->table.begin(table_bytes, &h_jobs)) return rc;
-    uint32_t *h_tile0 = reinterpret_cast<uint32_t *>(h_jobs + n_jobs);
-    tiles = 0;
-    for (size_t i = 0; i < n_jobs; ++i) {
-        h_jobs[i] = jobs[i];
-        h_tile0[i] = fsea_detail::job_first_tile(&tiles, jobs[i].n_pairs / D, (unsigned)a->tile);   // a job without output: its successor's
-    }
-    uint8_t *base = nullptr;
-    if (int rc = a->table.queue(table_bytes, table_bytes, s, &base)) return rc;
-    const fsea_audio_job *d_jobs = reinterpret_cast<const fsea_audio_job *>(base);
-    const uint32_t *d_tile0 = reinterpret_cast<const uint32_t *>(d_jobs + n_jobs);
-    hipLaunchKernelGGL(fsea_audio_tiles, dim3((unsigned)tiles), dim3(AU_WG), 0, s, static_cast<const float2 *>(d_pairs), d_jobs, d_tile0,
+    fsea_detail::JobTable::Built<fsea_audio_job> t;
+    const int rc = a->table.build<fsea_audio_job>(n_jobs, (unsigned)a->tile, 0, s, [&](size_t i, fsea_audio_job &rec, uint32_t) {
+        rec = jobs[i];
+        return jobs[i].n_pairs / D;
+    }, &t);
+    if (rc) return rc;
+    hipLaunchKernelGGL(fsea_audio_tiles, dim3((unsigned)t.tiles), dim3(AU_WG), 0, s, static_cast<const float2 *>(d_pairs), t.recs, t.tile0,
                        (int)n_jobs, fsea_detail::job_steps(n_jobs), a->kind, (const double *)a->d_taps.ptr, (const uint32_t *)a->d_offs.ptr,
                        a->n_taps, a->decimation, a->tile, a->pitch, offset_re, offset_im, gain, d_audio);
     FSEA_HIP(hipGetLastError());
@@ -250,17 +228,8 @@ int fsea_audio_decimation(const fsea_audio *a) { return a ? a->decimation : 0; }
 int fsea_audio_n_taps(const fsea_audio *a) { return a ? a->n_taps : 0; }
 
 int fsea_audio_layout(const fsea_audio *a, fsea_audio_job *jobs, size_t n_jobs, size_t *total_outputs) {
-    if (!a) return fail(FSEA_EINVAL, "audio is NULL");
-    if (!total_outputs) return fail(FSEA_EINVAL, "total_outputs is NULL");
-    if (int rc = fsea_detail::check_jobs_count(n_jobs)) return rc;
-    if (n_jobs && !jobs) return fail(FSEA_EINVAL, "NULL job table");
-    uint64_t at = 0;
-    for (size_t i = 0; i < n_jobs; ++i) {
-        jobs[i].out_first = at;
-        at += jobs[i].n_pairs / (uint64_t)a->decimation;
-    }
-    *total_outputs = (size_t)at;
-    return FSEA_OK;
+    return fsea_detail::layout_jobs(a, "audio", jobs, n_jobs, total_outputs, "total_outputs", 1,
+                                    [&](const fsea_audio_job &j) { return j.n_pairs / (uint64_t)a->decimation; });
 }
 
 int fsea_audio_run_device(fsea_audio *a, const void *d_pairs, size_t n_buffer_pairs, const fsea_audio_job *jobs, size_t n_jobs,
@@ -280,30 +249,17 @@ int fsea_audio_run_host(fsea_audio *a, const float *pairs, size_t n_buffer_pairs
     const int rc = check_run(a, pairs, n_buffer_pairs, jobs, n_jobs, offset_re, offset_im, gain, audio, n_audio);
     if (rc || n_jobs == 0) return rc;
     const uint64_t D = (uint64_t)a->decimation;
-    size_t end_in = 0, end_out = 0;   // the pairs in front of end_in are staged; only the jobs' own outputs go to the caller
+    size_t end_in = 0;   // the pairs in front of end_in are staged
     for (size_t i = 0; i < n_jobs; ++i) {
-        const uint64_t n_out = jobs[i].n_pairs / D;
-        if (n_out) {
-            end_in = std::max(end_in, (size_t)(jobs[i].first_pair + jobs[i].n_pairs));
-            end_out = std::max(end_out, (size_t)(jobs[i].out_first + n_out));
-        }
+        if (jobs[i].n_pairs / D) end_in = std::max(end_in, (size_t)(jobs[i].first_pair + jobs[i].n_pairs));
     }
-    if (end_out == 0) return FSEA_OK;
-    std::lock_guard<std::mutex> lock(a->mu);
-    FSEA_ON_DEVICE(a->device);
-    fsea_detail::HostStaging &st = a->staging;
-    if (int rc2 = st.reserve(end_in * sizeof(float2), end_out * sizeof(float))) return rc2;
-    std::memcpy(st.h_in.ptr, pairs, end_in * sizeof(float2));
-    FSEA_HIP(hipMemcpyAsync(st.d_in.ptr, st.h_in.ptr, end_in * sizeof(float2), hipMemcpyHostToDevice, st.stream));
-    if (int rc2 = queue_call(a, st.d_in.ptr, jobs, n_jobs, offset_re, offset_im, gain, static_cast<float *>(st.d_out.ptr), st.stream)) return rc2;
-    FSEA_HIP(hipMemcpyAsync(st.h_out.ptr, st.d_out.ptr, end_out * sizeof(float), hipMemcpyDeviceToHost, st.stream));
-    FSEA_HIP(hipStreamSynchronize(st.stream));
-    const float *h = static_cast<const float *>(st.h_out.ptr);
-    for (size_t i = 0; i < n_jobs; ++i) {
-        const uint64_t n_out = jobs[i].n_pairs / D;
-        if (n_out) std::memcpy(audio + jobs[i].out_first, h + jobs[i].out_first, (size_t)n_out * sizeof(float));
-    }
-    return FSEA_OK;
+    return fsea_detail::run_host_placed(
+        a, end_in * sizeof(float2), n_jobs, audio, [&](void *h_in) { std::memcpy(h_in, pairs, end_in * sizeof(float2)); },
+        [&](void *d_in, float *d_out, hipStream_t s) { return queue_call(a, d_in, jobs, n_jobs, offset_re, offset_im, gain, d_out, s); },
+        [&](size_t i, uint64_t *first, uint64_t *n) {
+            *first = jobs[i].out_first;
+            *n = jobs[i].n_pairs / D;
+        });
 }
 
 }  // extern "C"

@@ -7,21 +7,20 @@
 // outputs of one job; the grid is the sum of the jobs' tiles.  The host turns every job that has an output into a 128-byte
 // record (first, out_first, its first tile, its FirRot with the eight step phasors) and a column of first tiles; a
 // workgroup finds its job by a bisection over that column (fsea_jobs.h: job_of_tile), `steps` = ceil(log2(records)) <= 16
-// loads, all of them uniform: scalar loads and SGPRs, and so is the record itself.  The table's way to the device and the
-// checks of a job table are fsea_measure's too (fsea_jobs.h).  From there on it is the zoom's tile (fsea_zoom_image.h): the
-// tile's T D + L - 1 rotated samples phase-major in LDS, one FMA chain per output with taps and byte offsets from scalar
-// loads, 8-byte stores, the three static LDS sizes.  What differs is the staging: the groups of eight are aligned to the
+// loads, all of them uniform: scalar loads and SGPRs, and so is the record itself.  The table's build and way to the device
+// and the checks of a job table are fsea_measure's and fsea_audio's too, the placement of the outputs, the layout and the
+// host form fsea_audio's (fsea_jobs.h).  From there on it is the zoom's tile (fsea_zoom_image.h): the tile's T D + L - 1
+// rotated samples phase-major in LDS, one FMA chain per output with taps and byte offsets from scalar loads, 8-byte
+// stores, the three static LDS sizes.  What differs is the staging: the groups of eight are aligned to the
 // buffer (first + s a multiple of 8), so that a group inside the job is one 16-byte load whatever first mod 8 is; the two
 // ends go sample by sample, and what lies in front of the job is the zero tail (fsea_fir_stage.h: stage_group_at).  No wave
 // waits for another, no atomics, every loop has its bound on entry.
 #include "fsea_jobs.h"
 #include "fsea_zoom_image.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <string>
-#include <vector>
 
 using fsea_detail::DeviceGuard;
 using fsea_detail::fail;
@@ -132,27 +131,11 @@ int check_run(const fsea_extract *x, const void *iq, size_t n_iq, const fsea_ext
         total += j.n_samples / D;
     }
     if (int rc = fsea_detail::check_jobs_total(total, "outputs")) return rc;
-    std::vector<uint32_t> order;
-    for (size_t i = 0; i < n_jobs; ++i) {
-        const uint64_t n_out = jobs[i].n_samples / D;
-        if (n_out == 0) continue;
-        if (n_out > capacity || jobs[i].out_first > capacity - n_out) {
-            return fail(FSEA_EINVAL, "job %zu: outputs %llu .. %llu + %llu lie past the capacity of %zu pairs", i,
-                        (unsigned long long)jobs[i].out_first, (unsigned long long)jobs[i].out_first, (unsigned long long)n_out, capacity);
-        }
-        order.push_back((uint32_t)i);
-    }
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        return jobs[a].out_first != jobs[b].out_first ? jobs[a].out_first < jobs[b].out_first : a < b;
+    return fsea_detail::check_jobs_placement(n_jobs, capacity, "capacity of ", " pairs", [&](size_t i, uint64_t *first, uint64_t *n) {
+        *first = jobs[i].out_first;
+        *n = jobs[i].n_samples / D;
+        return FSEA_OK;
     });
-    for (size_t k = 1; k < order.size(); ++k) {
-        const fsea_extract_job &a = jobs[order[k - 1]], &b = jobs[order[k]];
-        if (a.out_first + a.n_samples / D > b.out_first) {
-            return fail(FSEA_EINVAL, "the outputs of jobs %u and %u overlap", std::min(order[k - 1], order[k]),
-                        std::max(order[k - 1], order[k]));
-        }
-    }
-    return FSEA_OK;
 }
 
 // One call on device buffers, asynchronous on `s`: the records built in mapped host memory, their upload, the launch.  The
@@ -162,31 +145,22 @@ int queue_call(fsea_extract *x, const void *d_iq, int flip, const fsea_extract_j
     size_t n_rec = 0;
     for (size_t i = 0; i < n_jobs; ++i) n_rec += jobs[i].n_samples / (uint64_t)D ? 1 : 0;
     if (n_rec == 0) return FSEA_OK;
-    const size_t bytes = n_rec * (sizeof(ExtractRec) + sizeof(uint32_t));
-    ExtractRec *recs = nullptr;
-    if (int rc = x->table.begin(bytes, &recs)) return rc;
-    uint32_t *tile0 = reinterpret_cast<uint32_t *>(recs + n_rec);
-    uint64_t tiles = 0;
-    size_t r = 0;
-    for (size_t i = 0; i < n_jobs; ++i) {
-        const fsea_extract_job &j = jobs[i];
-        const uint64_t n_out = j.n_samples / (uint64_t)D;
-        if (!n_out) continue;
-        ExtractRec &rec = recs[r];
+    size_t i = 0;   // the job of the next record: jobs without output have none
+    fsea_detail::JobTable::Built<ExtractRec> t;
+    const int rc = x->table.build<ExtractRec>(n_rec, ZM_T, 0, s, [&](size_t, ExtractRec &rec, uint32_t tile0) {
+        while (jobs[i].n_samples / (uint64_t)D == 0) ++i;
+        const fsea_extract_job &j = jobs[i++];
         rec.first = (long long)j.first;
         rec.out_first = (long long)j.out_first;
-        rec.tile0 = tile0[r] = fsea_detail::job_first_tile(&tiles, n_out, ZM_T);
+        rec.tile0 = tile0;
         rec.pad[0] = rec.pad[1] = rec.pad[2] = 0;
         rec.rot = make_rot(j.cycles_per_sample, j.phase0_cycles, j.sample_offset, (size_t)j.n_samples);
-        ++r;
-    }
-    uint8_t *base = nullptr;
-    if (int rc = x->table.queue(bytes, bytes, s, &base)) return rc;
-    const ExtractRec *d_recs = reinterpret_cast<const ExtractRec *>(base);
-    const uint32_t *d_tile0 = reinterpret_cast<const uint32_t *>(d_recs + n_rec);
+        return j.n_samples / (uint64_t)D;
+    }, &t);
+    if (rc) return rc;
     const int need = zoom_lds_samples(D, L);
     auto kernel = need <= ZM_CAP_S ? fsea_extract_u8_s : need <= ZM_CAP_M ? fsea_extract_u8_m : fsea_extract_u8;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(ZM_WG), 0, s, d_iq, flip ? 0x80808080u : 0u, d_recs, d_tile0, (int)n_rec,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)t.tiles), dim3(ZM_WG), 0, s, d_iq, flip ? 0x80808080u : 0u, t.recs, t.tile0, (int)n_rec,
                        fsea_detail::job_steps(n_rec), (const float *)x->d_taps.ptr, (const uint32_t *)x->d_offs.ptr, L, D,
                        static_cast<cf *>(d_pairs));
     FSEA_HIP(hipGetLastError());
@@ -233,18 +207,8 @@ size_t fsea_extract_lead(int n_taps, int decimation) {
 }
 
 int fsea_extract_layout(const fsea_extract *x, fsea_extract_job *jobs, size_t n_jobs, size_t *total_pairs) {
-    if (!x) return fail(FSEA_EINVAL, "extract is NULL");
-    if (!total_pairs) return fail(FSEA_EINVAL, "total_pairs is NULL");
-    if (int rc = fsea_detail::check_jobs_count(n_jobs)) return rc;
-    if (n_jobs && !jobs) return fail(FSEA_EINVAL, "NULL job table");
-    uint64_t at = 0;
-    for (size_t i = 0; i < n_jobs; ++i) {
-        at = (at + 1) & ~(uint64_t)1;
-        jobs[i].out_first = at;
-        at += jobs[i].n_samples / (uint64_t)x->decimation;
-    }
-    *total_pairs = (size_t)at;
-    return FSEA_OK;
+    return fsea_detail::layout_jobs(x, "extract", jobs, n_jobs, total_pairs, "total_pairs", 2,
+                                    [&](const fsea_extract_job &j) { return j.n_samples / (uint64_t)x->decimation; });
 }
 
 int fsea_extract_run_device(fsea_extract *x, const void *d_iq, size_t n_iq_samples, int flip, const fsea_extract_job *jobs,
@@ -261,28 +225,13 @@ int fsea_extract_run_host(fsea_extract *x, const uint8_t *iq, size_t n_iq_sample
                           size_t n_jobs, float *pairs, size_t pairs_capacity) {
     const int rc = check_run(x, iq, n_iq_samples, jobs, n_jobs, pairs, pairs_capacity);
     if (rc || n_jobs == 0) return rc;
-    const uint64_t D = (uint64_t)x->decimation;
-    size_t end = 0;   // the pairs in front of `end` are staged; only the jobs' own go to the caller
-    for (size_t i = 0; i < n_jobs; ++i) {
-        const uint64_t n_out = jobs[i].n_samples / D;
-        if (n_out) end = std::max(end, (size_t)(jobs[i].out_first + n_out));
-    }
-    if (end == 0) return FSEA_OK;
-    std::lock_guard<std::mutex> lock(x->mu);
-    FSEA_ON_DEVICE(x->device);
-    fsea_detail::HostStaging &st = x->staging;
-    if (int rc2 = st.reserve(2 * n_iq_samples, end * sizeof(cf))) return rc2;
-    std::memcpy(st.h_in.ptr, iq, 2 * n_iq_samples);
-    FSEA_HIP(hipMemcpyAsync(st.d_in.ptr, st.h_in.ptr, 2 * n_iq_samples, hipMemcpyHostToDevice, st.stream));
-    if (int rc2 = queue_call(x, st.d_in.ptr, flip, jobs, n_jobs, st.d_out.ptr, st.stream)) return rc2;
-    FSEA_HIP(hipMemcpyAsync(st.h_out.ptr, st.d_out.ptr, end * sizeof(cf), hipMemcpyDeviceToHost, st.stream));
-    FSEA_HIP(hipStreamSynchronize(st.stream));
-    const cf *h = static_cast<const cf *>(st.h_out.ptr);
-    for (size_t i = 0; i < n_jobs; ++i) {
-        const uint64_t n_out = jobs[i].n_samples / D;
-        if (n_out) std::memcpy(pairs + 2 * jobs[i].out_first, h + jobs[i].out_first, (size_t)n_out * sizeof(cf));
-    }
-    return FSEA_OK;
+    return fsea_detail::run_host_placed(
+        x, 2 * n_iq_samples, n_jobs, reinterpret_cast<cf *>(pairs), [&](void *h_in) { std::memcpy(h_in, iq, 2 * n_iq_samples); },
+        [&](void *d_in, cf *d_out, hipStream_t s) { return queue_call(x, d_in, flip, jobs, n_jobs, d_out, s); },
+        [&](size_t i, uint64_t *first, uint64_t *n) {
+            *first = jobs[i].out_first;
+            *n = jobs[i].n_samples / (uint64_t)x->decimation;
+        });
 }
 
 int fsea_extract_jobs(const fsea_events_event *events, size_t n_events, int width, int hop, uint64_t n_samples, int n_taps,

@@ -245,9 +245,10 @@ struct HostStaging {
     // queues the object's work, copy out, wait, every part to its host pointer.  The parts lie behind d_out / h_out in
     // their order, each at a 16-byte boundary; d_parts[i] is the device address of part i.  A launch may put memory of
     // the object's own there instead: that part comes back in a copy of its own, queued behind the one copy of all that
-    // is staged.  Zero-byte copies are skipped.  The caller holds the object's mutex and is on its device.
-    template <size_t N, class Fill, class Launch>
-    int run(size_t in_bytes, const Part (&parts)[N], Fill &&fill, Launch &&launch) {
+    // is staged.  Zero-byte copies are skipped.  The caller holds the object's mutex and is on its device.  With a
+    // `deliver`, deliver(i, h) takes part i from pinned memory in place of the copy of the whole part to its host pointer.
+    template <size_t N, class Fill, class Launch, class Deliver>
+    int run(size_t in_bytes, const Part (&parts)[N], Fill &&fill, Launch &&launch, Deliver &&deliver) {
         size_t at[N], bytes[N], end = 0;
         for (size_t i = 0; i < N; ++i) {
             bytes[i] = parts[i].host ? parts[i].bytes : 0;
@@ -277,9 +278,13 @@ struct HostStaging {
         }
         FSEA_HIP(hipStreamSynchronize(stream));
         for (size_t i = 0; i < N; ++i) {
-            if (bytes[i]) std::memcpy(parts[i].host, h + at[i], bytes[i]);
+            if (bytes[i]) deliver(i, static_cast<const uint8_t *>(h + at[i]));
         }
         return FSEA_OK;
+    }
+    template <size_t N, class Fill, class Launch>
+    int run(size_t in_bytes, const Part (&parts)[N], Fill &&fill, Launch &&launch) {
+        return run(in_bytes, parts, fill, launch, [&](size_t i, const uint8_t *h) { std::memcpy(parts[i].host, h, parts[i].bytes); });
     }
 
     // the same with one output: launch(d_in, d_out, stream)

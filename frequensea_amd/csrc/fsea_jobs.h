@@ -1,14 +1,18 @@
 // fsea_jobs.h -- what the objects that run a table of jobs over one resident buffer share: fsea_extract (fsea_extract.hip),
-// fsea_measure (fsea_measure.hip) and fsea_audio (fsea_audio.hip).  The look-up of a workgroup's job on the device, the
-// table's way from the caller to the device (JobTable: built in mapped host memory, copied by the one kernel
-// fsea_jobs_upload, ordered by two events), the
-// two numbers a table needs beside its entries, and the checks of a job table with the one text each has.  What a job is,
-// what a kernel does with it and what lies behind the table in the scratch are each file's own.  Everything has internal
-// linkage but jobs_upload, whose body stands beside its kernel in fsea_api.hip: the library is built without relocatable
-// device code, so a kernel has one translation unit.
+// fsea_measure (fsea_measure.hip) and fsea_audio (fsea_audio.hip).  The look-up of a workgroup's job on the device; the
+// table's way from the caller to the device (JobTable: records and first-tile column built in mapped host memory by the
+// one routine `build`, copied by the one kernel fsea_jobs_upload, ordered by two events); the checks of a job table with
+// the one text each has, the placement of the outputs among them; and, for the two objects that place their outputs
+// (extract, audio), the layout and the host form that hands back only the jobs' own ranges.  What a job is, what a kernel
+// does with it and what lies behind the table in the scratch are each file's own.  Everything has internal linkage but
+// jobs_upload, whose body stands beside its kernel in fsea_api.hip: the library is built without relocatable device code,
+// so a kernel has one translation unit.
 #pragma once
 
 #include "fsea_internal.h"
+
+#include <algorithm>
+#include <vector>
 
 namespace fsea_detail {
 
@@ -44,13 +48,6 @@ int job_steps(size_t n) {
     return steps;
 }
 
-// the first tile of an entry of `count` elements in tiles of `tile`, *tiles the running total: <= 2^31 / tile + 65536 in all
-uint32_t job_first_tile(uint64_t *tiles, uint64_t count, unsigned tile) {
-    const uint32_t first = (uint32_t)*tiles;
-    *tiles += (count + tile - 1) / tile;
-    return first;
-}
-
 // The table of a call on its way to the device.  A call builds it in mapped host memory and fsea_jobs_upload copies it on the
 // caller's stream in front of the object's kernels (3.6 us; a copy engine's transfer there cost two changes of queue, 6 to
 // 10 us more a call: profiles/extract_rate.txt).  `copied` keeps the next call's fill behind this call's upload, the
@@ -65,27 +62,47 @@ struct JobTable {
         if (e == hipSuccess) e = copied.create();
         return e == hipSuccess ? hipEventRecord(copied, first) : e;
     }
-    // a call begins: the previous call's upload has read the host table; table_bytes of it behind *host, to be filled
-    template <class T>
-    int begin(size_t table_bytes, T **host) {
+    // What a call's kernels get: the records, the column of their first tiles, the tiles of all, and the room behind the
+    // table, which is there only for a call with behind_per_tile: otherwise `behind` may lie past the scratch
+    template <class Rec>
+    struct Built {
+        const Rec *recs;
+        const uint32_t *tile0;
+        uint8_t *behind;
+        uint64_t tiles;    // <= 2^31 / tile + 65536
+    };
+    // One call's table on `s`: n records, record r filled by fill(r, rec, first), which gets the entry's first tile and
+    // returns its elements, in tiles of `tile`; fill is called exactly once for each r, in ascending order (extract's walks
+    // its jobs alongside and skips those without output); the column of first tiles behind the records (an entry without
+    // a tile has its successor's).  First the previous call's upload has read the host table; then the fill, the scratch, the upload.
+    // behind_per_tile: bytes an object keeps behind the table for every tile, from a 64-byte boundary (measure's partials).
+    template <class Rec, class Fill>
+    int build(size_t n, unsigned tile, size_t behind_per_tile, hipStream_t s, Fill &&fill, Built<Rec> *built) {
+        const size_t bytes = n * (sizeof(Rec) + sizeof(uint32_t)), behind_at = (bytes + 63) & ~(size_t)63;   // <= 65536 * 33 words
         FSEA_HIP(hipEventSynchronize(copied));
-        const int rc = h_table.grow(table_bytes);
-        *host = static_cast<T *>(h_table.ptr);
-        return rc;
-    }
-    // the filled table to the head of total_bytes >= table_bytes of scratch, on `s`; *base is the scratch
-    int queue(size_t table_bytes, size_t total_bytes, hipStream_t s, uint8_t **base) {
-        if (int rc = scratch.acquire(total_bytes, s)) return rc;
-        if (int rc = jobs_upload(h_table.ptr, scratch.buf.ptr, (uint32_t)(table_bytes / sizeof(uint32_t)), s)) return rc;   // <= 65536 * 33 words
+        if (int rc = h_table.grow(bytes)) return rc;
+        Rec *recs = static_cast<Rec *>(h_table.ptr);
+        uint32_t *tile0 = reinterpret_cast<uint32_t *>(recs + n);
+        uint64_t tiles = 0;
+        for (size_t r = 0; r < n; ++r) {
+            tile0[r] = (uint32_t)tiles;
+            tiles += ((uint64_t)fill(r, recs[r], tile0[r]) + tile - 1) / tile;
+        }
+        if (int rc = scratch.acquire(behind_per_tile ? behind_at + (size_t)tiles * behind_per_tile : bytes, s)) return rc;
+        if (int rc = jobs_upload(h_table.ptr, scratch.buf.ptr, (uint32_t)(bytes / sizeof(uint32_t)), s)) return rc;
         FSEA_HIP(hipEventRecord(copied, s));
-        *base = static_cast<uint8_t *>(scratch.buf.ptr);
+        uint8_t *base = static_cast<uint8_t *>(scratch.buf.ptr);
+        built->recs = reinterpret_cast<const Rec *>(base);
+        built->tile0 = reinterpret_cast<const uint32_t *>(built->recs + n);
+        built->behind = base + behind_at;
+        built->tiles = tiles;
         return FSEA_OK;
     }
     // behind the object's last launch of the call
     int release(hipStream_t s) { return scratch.release(s); }
 };
 
-// The checks of a job table, in the order both objects have them: the count
+// The checks of a job table, in the order the three objects have them: the count
 int check_jobs_count(size_t n_jobs) {
     if (n_jobs > FSEA_EXTRACT_MAX_JOBS) return fail(FSEA_EINVAL, "n_jobs %zu above %d", n_jobs, FSEA_EXTRACT_MAX_JOBS);
     return FSEA_OK;
@@ -116,6 +133,81 @@ int check_job_span(size_t i, uint64_t first, uint64_t n, size_t n_buffer, uint64
 int check_jobs_total(uint64_t total, const char *elems) {
     if (total > (uint64_t)1 << 31) return fail(FSEA_EINVAL, "%llu %s in one call: more than 2^31", (unsigned long long)total, elems);
     return FSEA_OK;
+}
+
+// Where the outputs of the jobs go, for the objects that place them: every job with an output inside the caller's
+// `capacity`, in table order, then no two of them on top of one another.  at(i, &out_first, &n_out) says where job i's
+// outputs lie; it may refuse the job for a reason of its own first (audio: the job's span), and that code is returned.  The
+// text ends "lie past the <before><capacity><after>".
+template <class At>
+int check_jobs_placement(size_t n_jobs, size_t capacity, const char *before, const char *after, At &&at) {
+    struct Placed {
+        uint64_t first, n;
+        uint32_t job;
+    };
+    std::vector<Placed> placed;
+    for (size_t i = 0; i < n_jobs; ++i) {
+        Placed p = {0, 0, (uint32_t)i};
+        if (int rc = at(i, &p.first, &p.n)) return rc;
+        if (p.n == 0) continue;
+        if (p.n > capacity || p.first > capacity - p.n) {
+            return fail(FSEA_EINVAL, "job %zu: outputs %llu .. %llu + %llu lie past the %s%zu%s", i, (unsigned long long)p.first,
+                        (unsigned long long)p.first, (unsigned long long)p.n, before, capacity, after);
+        }
+        placed.push_back(p);
+    }
+    std::sort(placed.begin(), placed.end(), [](const Placed &a, const Placed &b) { return a.first != b.first ? a.first < b.first : a.job < b.job; });
+    for (size_t k = 1; k < placed.size(); ++k) {
+        const Placed &a = placed[k - 1], &b = placed[k];
+        if (a.first + a.n > b.first) {
+            return fail(FSEA_EINVAL, "the outputs of jobs %u and %u overlap", std::min(a.job, b.job), std::max(a.job, b.job));
+        }
+    }
+    return FSEA_OK;
+}
+
+// fsea_X_layout: out_first of every job, back to back in table order, each at a multiple of `align` (a power of two);
+// outputs(job) is a job's count.  `name` as in check_jobs_head, `total_name` the out-parameter's.
+template <class Job, class Outputs>
+int layout_jobs(const void *obj, const char *name, Job *jobs, size_t n_jobs, size_t *total, const char *total_name, uint64_t align,
+                Outputs &&outputs) {
+    if (!obj) return fail(FSEA_EINVAL, "%s is NULL", name);
+    if (!total) return fail(FSEA_EINVAL, "%s is NULL", total_name);
+    if (int rc = check_jobs_count(n_jobs)) return rc;
+    if (n_jobs && !jobs) return fail(FSEA_EINVAL, "NULL job table");
+    uint64_t at = 0;
+    for (size_t i = 0; i < n_jobs; ++i) {
+        at = (at + align - 1) & ~(align - 1);
+        jobs[i].out_first = at;
+        at += outputs(jobs[i]);
+    }
+    *total = (size_t)at;
+    return FSEA_OK;
+}
+
+// The host form of an object that places its outputs (`obj`: mu, device, staging), the arguments checked: in_bytes of
+// input staged by fill(h_in), queue(d_in, d_out, stream), the elements in front of the end of the last placed job brought
+// back, and of those only every job's own range to `out`; at(i, &out_first, &n_out) as above.  No output: nothing is done.
+template <class T, class Out, class Fill, class Queue, class At>
+int run_host_placed(T *obj, size_t in_bytes, size_t n_jobs, Out *out, Fill &&fill, Queue &&queue, At &&at) {
+    uint64_t first = 0, n = 0;
+    size_t end = 0;
+    for (size_t i = 0; i < n_jobs; ++i) {
+        at(i, &first, &n);
+        if (n) end = std::max(end, (size_t)(first + n));
+    }
+    if (end == 0) return FSEA_OK;
+    std::lock_guard<std::mutex> lock(obj->mu);
+    FSEA_ON_DEVICE(obj->device);
+    const HostStaging::Part part[1] = {{out, end * sizeof(Out)}};
+    return obj->staging.run(
+        in_bytes, part, fill, [&](void *d_in, void **d_parts, hipStream_t s) { return queue(d_in, static_cast<Out *>(d_parts[0]), s); },
+        [&](size_t, const uint8_t *h) {
+            for (size_t i = 0; i < n_jobs; ++i) {
+                at(i, &first, &n);
+                if (n) std::memcpy(out + first, reinterpret_cast<const Out *>(h) + first, (size_t)n * sizeof(Out));
+            }
+        });
 }
 
 }  // namespace

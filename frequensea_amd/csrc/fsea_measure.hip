@@ -6,13 +6,13 @@
 //
 // Kernel fsea_measure_tiles ("Signal measures"): one workgroup of MS_WG = 256 lanes per tile of
 // MS_TILE = 4096 pairs of one job; the grid is the sum of the jobs' tiles.  The device table is the caller's jobs as they are
-// and a column of first tiles, brought there as fsea_extract's (fsea_jobs.h: JobTable); a workgroup finds its job by a
-// bisection over that column (job_of_tile), `steps` = ceil(log2(jobs)) <= 16 loads, uniform, so scalar loads and SGPRs, and
-// so is the job itself.  A job without pairs has its successor's first tile
-// and the bisection ends at the last job whose first tile is not behind the workgroup's: never at an empty one.  Lane l
-// takes pairs l, l + 256, ... of the tile: sixteen 8-byte loads, a wave's 64 of them 512 contiguous bytes at any parity of
-// first_pair, and sixteen more for the lagged partners (the same lines `lag` pairs earlier, cache hits), all issued in
-// front of the arithmetic.  A tile that is whole and has a partner for every pair takes a body without bounds tests; the
+// and a column of first tiles, built and brought there as fsea_extract's and fsea_audio's (fsea_jobs.h: JobTable::build),
+// the tile partials behind it; a workgroup finds its job by a bisection over that column (job_of_tile), `steps` =
+// ceil(log2(jobs)) <= 16 loads, uniform, so scalar loads and SGPRs, and so is the job itself.  A job without pairs has
+// its successor's first tile and the bisection ends at the last job whose first tile is not behind the workgroup's:
+// never at an empty one.  Lane l takes pairs l, l + 256, ... of the tile: sixteen 8-byte loads, a wave's 64 of them
+// 512 contiguous bytes at any parity of first_pair, and sixteen more for the lagged partners (the same lines `lag` pairs
+// earlier, cache hits), all issued in front of the arithmetic.  A tile that is whole and has a partner for every pair takes a body without bounds tests; the
 // other body tests every pair and does the same operations in the same order.  Six f64 accumulators, the running maximum
 // and its index stay in registers; the 256-lane combine is the xor butterfly across a wave's lanes (k = 1 .. 32) and the
 // last two stages (k = 64, 128) over the four waves' values in LDS; lanes 0 .. 7 store the tile's partial, 8 bytes each.
@@ -230,27 +230,19 @@ int check_run(const fsea_measure *m, const void *pairs, size_t n_buffer_pairs, c
 // The caller holds m->mu and is on m's device; the arguments are checked and n_jobs is at least 1.
 int queue_call(fsea_measure *m, const void *d_pairs, const fsea_measure_job *jobs, size_t n_jobs, double offset_re, double offset_im,
                int lag, fsea_measure_sums *d_sums, hipStream_t s) {
-    const size_t table_bytes = n_jobs * (sizeof(fsea_measure_job) + sizeof(uint32_t));
-    const size_t partials_at = (table_bytes + 63) & ~(size_t)63;
-    fsea_measure_job *h_jobs = nullptr;
-    if (int rc = m->table.begin(table_bytes, &h_jobs)) return rc;
-    uint32_t *h_tile0 = reinterpret_cast<uint32_t *>(h_jobs + n_jobs);
-    uint64_t tiles = 0;
-    for (size_t i = 0; i < n_jobs; ++i) {
-        h_jobs[i] = jobs[i];
-        h_tile0[i] = fsea_detail::job_first_tile(&tiles, jobs[i].n_pairs, MS_TILE);
-    }
-    uint8_t *base = nullptr;
-    if (int rc = m->table.queue(table_bytes, partials_at + (size_t)tiles * sizeof(Partial), s, &base)) return rc;
-    const fsea_measure_job *d_jobs = reinterpret_cast<const fsea_measure_job *>(base);
-    const uint32_t *d_tile0 = reinterpret_cast<const uint32_t *>(d_jobs + n_jobs);
-    Partial *d_partials = reinterpret_cast<Partial *>(base + partials_at);
-    if (tiles) {
-        hipLaunchKernelGGL(fsea_measure_tiles, dim3((unsigned)tiles), dim3(MS_WG), 0, s, static_cast<const float2 *>(d_pairs), d_jobs,
-                           d_tile0, (int)n_jobs, fsea_detail::job_steps(n_jobs), offset_re, offset_im, lag, d_partials);
+    fsea_detail::JobTable::Built<fsea_measure_job> t;
+    const int rc = m->table.build<fsea_measure_job>(n_jobs, MS_TILE, sizeof(Partial), s, [&](size_t i, fsea_measure_job &rec, uint32_t) {
+        rec = jobs[i];
+        return jobs[i].n_pairs;
+    }, &t);
+    if (rc) return rc;
+    Partial *d_partials = reinterpret_cast<Partial *>(t.behind);
+    if (t.tiles) {
+        hipLaunchKernelGGL(fsea_measure_tiles, dim3((unsigned)t.tiles), dim3(MS_WG), 0, s, static_cast<const float2 *>(d_pairs), t.recs,
+                           t.tile0, (int)n_jobs, fsea_detail::job_steps(n_jobs), offset_re, offset_im, lag, d_partials);
         FSEA_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(fsea_measure_fold, dim3((unsigned)n_jobs), dim3(64), 0, s, d_jobs, d_tile0, static_cast<const Partial *>(d_partials),
+    hipLaunchKernelGGL(fsea_measure_fold, dim3((unsigned)n_jobs), dim3(64), 0, s, t.recs, t.tile0, static_cast<const Partial *>(d_partials),
                        lag, d_sums);
     FSEA_HIP(hipGetLastError());
     return m->table.release(s);

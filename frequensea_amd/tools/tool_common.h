@@ -4,7 +4,7 @@
  * names, and what the tools that give dB rows to a device object share (fsea-persistence, fsea-occupancy, fsea-events): the
  * recording that becomes rows on the device chunk by chunk, the --mode names, the CFAR detector's options and the MHz of a
  * column; and for fsea-events and fsea-cutouts the list of an input's runs, its filling from a recording and the link into
- * events.  Everything is `static inline`, as in pipeline.h; a tool takes what applies to it.
+ * events; a device buffer with its pinned twin, regrown by half.  All `static inline`, as in pipeline.h; a tool takes its part.
  *
  * The --window table is the tools' own: the host library keeps one like it in its private header, which no tool includes.
  */
@@ -32,6 +32,27 @@ static inline void tool_die(const char *tool, const char *what) {
 static inline void tool_usage_error(const char *tool, const char *msg) {
     fprintf(stderr, "%s: %s\n", tool, msg);
     exit(EXIT_FAILURE);
+}
+
+/* A device buffer and, where asked for, its pinned twin on the host, regrown by half when a call needs more; zeroed to begin
+ * with.  What they held is gone after a regrowth. */
+typedef struct {
+    void *d, *h;
+    size_t cap; /* elements */
+} tool_grown;
+
+static inline void tool_grown_free(tool_grown *g) {
+    if (g->d != NULL) fsea_device_free(0, g->d);
+    if (g->h != NULL) fsea_host_free(g->h);
+    memset(g, 0, sizeof(*g));
+}
+
+static inline void tool_grown_need(const char *tool, tool_grown *g, size_t count, size_t elem_bytes, int pinned) {
+    if (count <= g->cap) return;
+    tool_grown_free(g);
+    g->cap = count + count / 2;
+    if (fsea_device_alloc(0, g->cap * elem_bytes, &g->d) != FSEA_OK) tool_die(tool, "fsea_device_alloc");
+    if (pinned && fsea_host_alloc(g->cap * elem_bytes, &g->h) != FSEA_OK) tool_die(tool, "fsea_host_alloc");
 }
 
 /* --window NAME: the periodic cosine-sum taper of that name on the plan (include/fsea.h: fsea_window_fill; the position in
@@ -230,8 +251,9 @@ static inline fsea_events_run *tool_runs_room(const char *tool, tool_run_list *l
 static inline size_t tool_recording_runs(const char *tool, tool_row_source *src, fsea_cfar *cfar, fsea_events *events, int type,
                                          tool_run_list *list) {
     const size_t n = src->n;
-    void *d_rows = src->d_rows, *d_mask = NULL, *d_runs = NULL;
-    size_t d_runs_cap = 0, done = 0;
+    void *d_rows = src->d_rows, *d_mask = NULL;
+    tool_grown d_runs = {NULL, NULL, 0};
+    size_t done = 0;
     if (fsea_device_alloc(0, src->frames_max * n, &d_mask) != FSEA_OK) tool_die(tool, "fsea_device_alloc");
     for (size_t frames; (frames = tool_rows_next(src)) > 0; done += frames) {
         if (fsea_cfar_add_device(cfar, d_rows, type, frames, n, (uint8_t *)d_mask, NULL, NULL) != FSEA_OK) tool_die(tool, "fsea_cfar_add_device");
@@ -241,24 +263,20 @@ static inline size_t tool_recording_runs(const char *tool, tool_row_source *src,
             tool_die(tool, "fsea_events_runs_device");
         }
         if (found == 0) continue;
-        if (found > d_runs_cap) {
-            if (d_runs != NULL) fsea_device_free(0, d_runs);
-            d_runs_cap = found + found / 2;
-            if (fsea_device_alloc(0, d_runs_cap * sizeof(fsea_events_run), &d_runs) != FSEA_OK) tool_die(tool, "fsea_device_alloc");
-        }
+        tool_grown_need(tool, &d_runs, found, sizeof(fsea_events_run), 0);
         if (fsea_events_reset(events) != FSEA_OK) tool_die(tool, "fsea_events_reset");
-        if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, (fsea_events_run *)d_runs, found, &found,
+        if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, (fsea_events_run *)d_runs.d, found, &found,
                                     NULL) != FSEA_OK) {
             tool_die(tool, "fsea_events_runs_device");
         }
         fsea_events_run *dst = tool_runs_room(tool, list, found);
-        if (fsea_copy_to_host(0, dst, d_runs, found * sizeof(fsea_events_run)) != FSEA_OK) tool_die(tool, "fsea_copy_to_host");
+        if (fsea_copy_to_host(0, dst, d_runs.d, found * sizeof(fsea_events_run)) != FSEA_OK) tool_die(tool, "fsea_copy_to_host");
         if (done + frames > 0xffffffffull) tool_usage_error(tool, "the recording holds more than 2^32 - 1 frames");
         for (size_t i = 0; i < found; i++) dst[i].row += (uint32_t)done;
         list->n += found;
     }
     fsea_device_free(0, d_mask);
-    if (d_runs != NULL) fsea_device_free(0, d_runs);
+    tool_grown_free(&d_runs);
     return done;
 }
 

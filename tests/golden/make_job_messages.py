@@ -1,8 +1,9 @@
 """Writes tests/golden/job_messages.json: code and fsea_last_error_string() of every case of tests/test_job_messages.py.
 
-The table is a record of the library BEFORE fsea_extract and fsea_measure got their shared checks (csrc/fsea_jobs.h): run
-this against a libfsea_hip.so built from that commit's csrc/, never to bless what a changed check says.  From the
-repository root:  python -m tests.golden.make_job_messages
+The table is a record of the library BEFORE the objects' checks were shared (csrc/fsea_jobs.h): the fsea_extract_* and
+fsea_measure_* entries from before the two got their shared checks, the fsea_audio_* entries from the commit that added the
+object, before its placement check and host form moved there.  Run this against a libfsea_hip.so built from such a commit's
+csrc/, never to bless what a changed check says.  From the repository root:  python -m tests.golden.make_job_messages
 """
 import json
 
