@@ -42,6 +42,8 @@ CFAR_TILE_COLUMNS = 1024    # FSEA_CFAR_TILE_COLUMNS: columns per workgroup of f
 CFAR_RUN_ROWS = 64          # FSEA_CFAR_RUN_ROWS: rows per workgroup
 CFAR_U8, CFAR_F32 = 0, 1                # FSEA_CFAR_*: element type of a row
 CFAR_CA, CFAR_GO, CFAR_SO = 0, 1, 2     # FSEA_CFAR_*: method
+OSCFAR_TILE_COLUMNS = 1024  # FSEA_OSCFAR_TILE_COLUMNS: columns per workgroup of fsea_oscfar_u8 / fsea_oscfar_f32
+OSCFAR_RUN_ROWS = 64        # FSEA_OSCFAR_RUN_ROWS: rows per workgroup
 CFAR_BAND = np.dtype([("first", "<i4"), ("last", "<i4"), ("peak", "<i4"), ("peak_hits", "<u4"), ("hits_sum", "<u8")])   # fsea_cfar_band
 EVENTS_MAX_WIDTH = 1 << 20      # FSEA_EVENTS_MAX_WIDTH
 EVENTS_MAX_GAP_COLS = 64        # FSEA_EVENTS_MAX_GAP_COLS
@@ -238,6 +240,16 @@ API = {
     "fsea_cfar_add_host": (_ci, [_vp, _vp, _ci, _sz, _sz, _vp, _vp]),
     "fsea_cfar_hits_host": (_ci, [_vp, _vp]),
     "fsea_cfar_bands": (_ci, [_vp, _ci, _u64, _f64, _ci, _ci, _vp, _sz, _szp]),
+    "fsea_oscfar_create": (_ci, [_out, _ci, _ci]),
+    "fsea_oscfar_destroy": (_ci, [_vp]),
+    "fsea_oscfar_reset": (_ci, [_vp]),
+    "fsea_oscfar_set": (_ci, [_vp, _ci, _ci, _ci, _ci]),
+    "fsea_oscfar_width": (_ci, [_vp]),
+    "fsea_oscfar_rows": (_u64, [_vp]),
+    "fsea_oscfar_rank": (_ci, [_vp]),
+    "fsea_oscfar_add_device": (_ci, [_vp, _vp, _ci, _sz, _sz, _vp, _vp, _vp]),
+    "fsea_oscfar_add_host": (_ci, [_vp, _vp, _ci, _sz, _sz, _vp, _vp]),
+    "fsea_oscfar_hits_host": (_ci, [_vp, _vp]),
     "fsea_events_create": (_ci, [_out, _ci, _ci]),
     "fsea_events_destroy": (_ci, [_vp]),
     "fsea_events_reset": (_ci, [_vp]),
@@ -820,7 +832,7 @@ def _rows_2d(a, dtypes, what):
 
 
 class _RowsHandle(_ResettableHandle):
-    """What consumes rows of `width` levels (Persist, Cfar, Events): the width and the rows offered so far."""
+    """What consumes rows of `width` levels (Persist, Cfar, OsCfar, Events): the width and the rows offered so far."""
 
     def __init__(self, width, device=0):
         self.device = device
@@ -933,6 +945,40 @@ class Cfar(_RowsHandle):
     def hits(self):
         out = np.empty(self.width, dtype=np.uint32)
         _check(self._L.fsea_cfar_hits_host(self._p, out.ctypes.data))
+        return out
+
+
+class OsCfar(_RowsHandle):
+    """An ordered-statistic CFAR detector across frequency on one device: which cells of a dB row stand above the rank-th
+    smallest level of their training cells -- the weaker of two close emissions keeps its hit -- and hits[column] over all
+    the rows offered; thin wrapper over fsea_oscfar_*.  add(), add_device() and hits() are Cfar's; cfar_bands() takes the hits."""
+    _kind = "oscfar"
+
+    def set(self, guard=2, train=16, offset=60, rank=24):
+        _check(self._L.fsea_oscfar_set(self._p, int(guard), int(train), int(offset), int(rank)))
+
+    @property
+    def rank(self):
+        return self._L.fsea_oscfar_rank(self._p)
+
+    def add(self, rows, mask=False, row_hits=False):
+        """None, the (n_rows, width) uint8 mask, the (n_rows,) uint32 row hits, or (mask, row_hits)."""
+        a, pitch, type = self._host_rows(rows)
+        m = np.empty(a.shape, dtype=np.uint8) if mask else None
+        h = np.empty(a.shape[0], dtype=np.uint32) if row_hits else None
+        _check(self._L.fsea_oscfar_add_host(self._p, a.ctypes.data, type, a.shape[0], pitch,
+                                            m.ctypes.data if mask else None, h.ctypes.data if row_hits else None))
+        return (m, h) if mask and row_hits else m if mask else h
+
+    def add_device(self, d_rows_ptr, type, n_rows, pitch=None, d_mask_ptr=None, d_row_hits_ptr=None, stream=0):
+        """d_rows_ptr (an int, 16-byte aligned): n_rows rows of `width` elements, `pitch` elements apart; d_mask_ptr
+        (n_rows * width bytes) and d_row_hits_ptr (n_rows uint32) are optional; asynchronous."""
+        _check(self._L.fsea_oscfar_add_device(self._p, d_rows_ptr, int(type), n_rows, self.width if pitch is None else pitch,
+                                              d_mask_ptr or None, d_row_hits_ptr or None, stream or None))
+
+    def hits(self):
+        out = np.empty(self.width, dtype=np.uint32)
+        _check(self._L.fsea_oscfar_hits_host(self._p, out.ctypes.data))
         return out
 
 

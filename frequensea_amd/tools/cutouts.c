@@ -35,8 +35,8 @@
 
 static const char *USAGE =
     "usage: fsea-cutouts FILE --size N --decimation D --out DIR [--hop H] [--window NAME] [--flip] [--mode db5|db10|db]\n"
-    "                    [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R]\n"
-    "                    [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--taps L] [--cutoff HZ]\n"
+    "                    [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--rank R] [--gap-cols B]\n"
+    "                    [--gap-rows R] [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--taps L] [--cutoff HZ]\n"
     "                    [--fill F] [--max-events E] [--max-samples S] [--measures [--lag K]]\n"
     "                    [--audio fm|am [--audio-rate HZ] [--audio-taps N] [--audio-cutoff HZ] [--deviation HZ]]\n"
     "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8).  The emissions are found as fsea-events finds them (its\n"
@@ -321,12 +321,12 @@ int main(int argc, char **argv) {
     /* pass 1: fsea-events' */
     tool_row_source src;
     tool_rows_open(&src, TOOL, o.path, size, hop, o.mode, o.window, o.flip);
-    fsea_cfar *cfar = tool_detector_create(TOOL, &o.det, size);
+    tool_detector_object detector = tool_detector_create(TOOL, &o.det, size);
     fsea_events *events = NULL;
     if (fsea_events_create(&events, size, 0) != FSEA_OK) die("fsea_events_create");
     if (fsea_events_set_gap(events, o.gap_cols) != FSEA_OK) die("fsea_events_set_gap");
     tool_run_list runs = {NULL, 0, 0};
-    const size_t done = tool_recording_runs(TOOL, &src, cfar, events, o.type, &runs);
+    const size_t done = tool_recording_runs(TOOL, &src, &detector, events, o.type, &runs);
     tool_rows_close(&src);
     if (done < 1) return tool_rows_none(TOOL, o.path, size);
     size_t n_events = 0;
@@ -437,7 +437,7 @@ int main(int argc, char **argv) {
 
     fsea_extract_destroy(extract);
     fsea_events_destroy(events);
-    fsea_cfar_destroy(cfar);
+    tool_detector_destroy(&detector);
     fsea_device_free(0, d_iq);
     tool_grown_free(&b.pairs);
     fsea_host_free(h_iq);

@@ -15,7 +15,7 @@
  * events, closed gaps included, as a mask of one row per frame: 255 inside, 0 elsewhere.
  *
  * usage: fsea-events FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db] [--guard G] [--train T]
- *                    [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R] [--min-rows R] [--min-cols B]
+ *                    [--offset LEVELS] [--method ca|go|so | --rank R] [--gap-cols B] [--gap-rows R] [--min-rows R] [--min-cols B]
  *                    [--min-hits K] [--rate HZ --freq MHZ] [--paint OUT.png]
  *        fsea-events --image IN.png [the detector's and the events' options]
  */
@@ -30,11 +30,12 @@
 
 static const char *USAGE =
     "usage: fsea-events FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db] [--guard G] [--train T]\n"
-    "                   [--offset LEVELS] [--method ca|go|so] [--gap-cols B] [--gap-rows R] [--min-rows R] [--min-cols B]\n"
-    "                   [--min-hits K] [--rate HZ --freq MHZ] [--paint OUT.png]\n"
+    "                   [--offset LEVELS] [--method ca|go|so] [--rank R] [--gap-cols B] [--gap-rows R] [--min-rows R]\n"
+    "                   [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--paint OUT.png]\n"
     "       fsea-events --image IN.png [--guard G] ... [--paint OUT.png]\n"
     "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8); every frame of N samples, one every H, becomes a dB row on the\n"
-    "  GPU and fsea-occupancy's CFAR detector (--guard, --train, --offset, --method; --mode db: f32 dB rows, LEVELS in 1/64 dB)\n"
+    "  GPU and fsea-occupancy's CFAR detector (--guard, --train, --offset, --method; --mode db: f32 dB rows, LEVELS in 1/64 dB;\n"
+    "  --rank R in place of --method: its ordered-statistic detector, the R-th smallest of the 2 T bins in place of their mean)\n"
     "  marks the bins that hold a signal; --image IN.png scans the rows of an 8-bit grey PNG instead.  Detections of a row\n"
     "  with at most --gap-cols free bins between them are a run; runs at most --gap-rows free rows apart that overlap, give\n"
     "  or take --gap-cols bins, belong to one event.  Events lower than --min-rows rows, narrower than --min-cols bins or of\n"
@@ -90,20 +91,20 @@ int main(int argc, char **argv) {
     int mode = 0, type = 0;
     if (!tool_rows_mode(mode_name, "db", &mode, &type)) usage_error("--mode must be db5, db10 or db");
 
-    fsea_cfar *cfar = NULL;
+    tool_detector_object detector = {NULL, NULL};
     fsea_events *events = NULL;
     tool_run_list list = {NULL, 0, 0};   /* all runs of the input, in order */
     int width = size;
     size_t done = 0;
     if (image_path != NULL) {
         int height = 0;
-        uint8_t *image = tool_detector_image("fsea-events", &det, &width, &height, &cfar);
+        uint8_t *image = tool_detector_image("fsea-events", &det, &width, &height, &detector);
         if (fsea_events_create(&events, width, 0) != FSEA_OK) die("fsea_events_create");
         if (fsea_events_set_gap(events, gap_cols) != FSEA_OK) die("fsea_events_set_gap");
         uint8_t *mask = (uint8_t *)malloc((size_t)width * (size_t)height + 1);
         if (mask == NULL) usage_error("out of memory");
         const size_t h = (size_t)height, w = (size_t)width;
-        if (fsea_cfar_add_host(cfar, image, FSEA_CFAR_U8, h, w, mask, NULL) != FSEA_OK) die("fsea_cfar_add_host");
+        tool_detector_add_host("fsea-events", &detector, image, FSEA_CFAR_U8, h, w, mask);
         size_t found = 0;
         if (fsea_events_runs_host(events, mask, w, image, FSEA_CFAR_U8, w, h, NULL, 0, &found) != FSEA_OK) die("fsea_events_runs_host");
         if (fsea_events_reset(events) != FSEA_OK) die("fsea_events_reset");
@@ -116,10 +117,10 @@ int main(int argc, char **argv) {
     } else {
         tool_row_source src;
         tool_rows_open(&src, "fsea-events", path, size, hop, mode, window, flip);
-        cfar = tool_detector_create("fsea-events", &det, size);
+        detector = tool_detector_create("fsea-events", &det, size);
         if (fsea_events_create(&events, size, 0) != FSEA_OK) die("fsea_events_create");
         if (fsea_events_set_gap(events, gap_cols) != FSEA_OK) die("fsea_events_set_gap");
-        done = tool_recording_runs("fsea-events", &src, cfar, events, type, &list);
+        done = tool_recording_runs("fsea-events", &src, &detector, events, type, &list);
         tool_rows_close(&src);
     }
     if (done < 1) {
@@ -161,7 +162,7 @@ int main(int argc, char **argv) {
         free(image);
     }
     fsea_events_destroy(events);
-    fsea_cfar_destroy(cfar);
+    tool_detector_destroy(&detector);
     free(found_events);
     free(event_of_run);
     free(list.runs);

@@ -11,7 +11,7 @@
  * writes the detections, one row per frame, 255 for a hit; --bands FILE writes the band lines.
  *
  * usage: fsea-occupancy FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db] [--guard G] [--train T]
- *                       [--offset LEVELS] [--method ca|go|so] [--min-duty F] [--max-gap B] [--min-width B]
+ *                       [--offset LEVELS] [--method ca|go|so | --rank R] [--min-duty F] [--max-gap B] [--min-width B]
  *                       [--rate HZ --freq MHZ] [--mask OUT.png] [--bands FILE]
  *        fsea-occupancy --image IN.png [the detector's and the bands' options]
  */
@@ -26,13 +26,15 @@
 
 static const char *USAGE =
     "usage: fsea-occupancy FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db] [--guard G] [--train T]\n"
-    "                      [--offset LEVELS] [--method ca|go|so] [--min-duty F] [--max-gap B] [--min-width B]\n"
+    "                      [--offset LEVELS] [--method ca|go|so] [--rank R] [--min-duty F] [--max-gap B] [--min-width B]\n"
     "                      [--rate HZ --freq MHZ] [--mask OUT.png] [--bands FILE]\n"
     "       fsea-occupancy --image IN.png [--guard G] ... [--bands FILE]\n"
     "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8); every frame of N samples, one every H, becomes a dB row on the\n"
     "  GPU and a CFAR detector compares each bin with the mean level of T bins on either side, G guard bins left out:\n"
     "  a bin is detected when its level is more than LEVELS above that mean (--mode db: f32 dB rows, LEVELS in 1/64 dB);\n"
-    "  --method go asks that of each side (steps do not fire), so of either side; --image IN.png scans the rows of an 8-bit\n"
+    "  --method go asks that of each side (steps do not fire), so of either side; --rank R, in place of --method, compares\n"
+    "  with the R-th smallest of the 2 T bins (R in [1, 2 T]; 24 of 32: the weaker of two close signals keeps its bins)\n"
+    "  in place of the mean; --image IN.png scans the rows of an 8-bit\n"
     "  grey PNG instead; a bin detected in at least F of the rows is occupied, bands bridge up to --max-gap free bins and are\n"
     "  at least --min-width wide; prints `rows R` and `first last peak duty` per band, with --rate and --freq also as MHz\n"
     "  defaults: --hop N --window rect --mode db5 --guard 2 --train 16 --offset 60 --method ca --min-duty 0.5 --max-gap 0\n"
@@ -92,29 +94,29 @@ int main(int argc, char **argv) {
     int mode = 0, type = 0;
     if (!tool_rows_mode(mode_name, "db", &mode, &type)) usage_error("--mode must be db5, db10 or db");
 
-    fsea_cfar *cfar = NULL;
+    tool_detector_object detector = {NULL, NULL};
     uint8_t *mask = NULL;          /* rows x width, grown chunk by chunk; only with --mask */
     int width = size;
     if (image_path != NULL) {
         int height = 0;
-        uint8_t *image = tool_detector_image("fsea-occupancy", &det, &width, &height, &cfar);
+        uint8_t *image = tool_detector_image("fsea-occupancy", &det, &width, &height, &detector);
         if (mask_path != NULL) {
             mask = (uint8_t *)malloc((size_t)width * (size_t)height + 1);
             if (mask == NULL) usage_error("out of memory");
         }
-        if (fsea_cfar_add_host(cfar, image, FSEA_CFAR_U8, (size_t)height, (size_t)width, mask, NULL) != FSEA_OK) die("fsea_cfar_add_host");
+        tool_detector_add_host("fsea-occupancy", &detector, image, FSEA_CFAR_U8, (size_t)height, (size_t)width, mask);
         free(image);
     } else {
         tool_row_source src;
         tool_rows_open(&src, "fsea-occupancy", path, size, hop, mode, window, flip);
-        cfar = tool_detector_create("fsea-occupancy", &det, size);
+        detector = tool_detector_create("fsea-occupancy", &det, size);
         const size_t n = (size_t)size;
         void *d_mask = NULL;
         if (mask_path != NULL && fsea_device_alloc(0, src.frames_max * n, &d_mask) != FSEA_OK) die("fsea_device_alloc");
         /* the rows stay on the device between the plan and the object */
         size_t done = 0;
         for (size_t frames; (frames = tool_rows_next(&src)) > 0; done += frames) {
-            if (fsea_cfar_add_device(cfar, src.d_rows, type, frames, n, (uint8_t *)d_mask, NULL, NULL) != FSEA_OK) die("fsea_cfar_add_device");
+            tool_detector_add_device("fsea-occupancy", &detector, src.d_rows, type, frames, n, (uint8_t *)d_mask);
             if (mask_path != NULL) {
                 uint8_t *grown = (uint8_t *)realloc(mask, (done + frames) * n);
                 if (grown == NULL) usage_error("out of memory");
@@ -125,7 +127,7 @@ int main(int argc, char **argv) {
         tool_rows_close(&src);
         if (d_mask != NULL) fsea_device_free(0, d_mask);
     }
-    const unsigned long long rows = fsea_cfar_rows(cfar);
+    const unsigned long long rows = tool_detector_rows(&detector);
     if (rows < 1) {
         if (image_path != NULL) fprintf(stderr, "fsea-occupancy: image %s has no rows\n", image_path);
         else return tool_rows_none("fsea-occupancy", path, size);
@@ -134,7 +136,7 @@ int main(int argc, char **argv) {
 
     uint32_t *hits = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)width);
     if (hits == NULL) usage_error("out of memory");
-    if (fsea_cfar_hits_host(cfar, hits) != FSEA_OK) die("fsea_cfar_hits_host");
+    tool_detector_hits_host("fsea-occupancy", &detector, hits);
     size_t n_bands = 0;
     if (fsea_cfar_bands(hits, width, rows, min_duty, max_gap, min_width, NULL, 0, &n_bands) != FSEA_OK) die("fsea_cfar_bands");
     fsea_cfar_band *bands = (fsea_cfar_band *)malloc(sizeof(fsea_cfar_band) * (n_bands + 1));
@@ -158,7 +160,7 @@ int main(int argc, char **argv) {
             return EXIT_FAILURE;
         }
     }
-    fsea_cfar_destroy(cfar);
+    tool_detector_destroy(&detector);
     free(bands);
     free(hits);
     free(mask);

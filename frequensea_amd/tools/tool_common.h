@@ -162,14 +162,16 @@ static inline int tool_rows_none(const char *tool, const char *path, int size) {
     return EXIT_FAILURE;
 }
 
-/* The CFAR detector of fsea-occupancy and fsea-events: --guard --train --offset --method, the axis of --rate and --freq, and
- * --image IN.png in place of a recording. */
+/* The CFAR detector of fsea-occupancy, fsea-events and fsea-cutouts: --guard --train --offset --method, or --rank R in place
+ * of --method for the ordered-statistic detector (fsea_oscfar); the axis of --rate and --freq, and --image IN.png in place of
+ * a recording. */
 typedef struct {
     int guard, train, offset, method, have_freq;
     double rate, freq;
     const char *image_path;
+    int rank, have_rank, have_method;
 } tool_detector;
-#define TOOL_DETECTOR_DEFAULTS {2, 16, 60, FSEA_CFAR_CA, 0, 0.0, 0.0, NULL}
+#define TOOL_DETECTOR_DEFAULTS {2, 16, 60, FSEA_CFAR_CA, 0, 0.0, 0.0, NULL, 0, 0, 0}
 
 /* 1: argv[*i] was one of the detector's options and *i is on its value; 0: not one of them */
 static inline int tool_detector_option(const char *tool, tool_detector *d, int argc, char **argv, int *i) {
@@ -184,6 +186,10 @@ static inline int tool_detector_option(const char *tool, tool_detector *d, int a
         else if (!strcmp(m, "go")) d->method = FSEA_CFAR_GO;
         else if (!strcmp(m, "so")) d->method = FSEA_CFAR_SO;
         else tool_usage_error(tool, "--method must be ca, go or so");
+        d->have_method = 1;
+    } else if (!strcmp(arg, "--rank")) {
+        d->rank = atoi(argv[++*i]);
+        d->have_rank = 1;
     } else if (!strcmp(arg, "--rate")) d->rate = atof(argv[++*i]);
     else if (!strcmp(arg, "--freq")) {
         d->freq = atof(argv[++*i]);
@@ -193,36 +199,81 @@ static inline int tool_detector_option(const char *tool, tool_detector *d, int a
     return 1;
 }
 
-/* the ranges of the detector's own three; a tool checks --rate and --freq behind its own options */
+/* the ranges of the detector's own; a tool checks --rate and --freq behind its own options */
 static inline void tool_detector_check(const char *tool, const tool_detector *d) {
     if (d->guard < 0 || d->guard > FSEA_CFAR_MAX_GUARD) tool_usage_error(tool, "--guard must be in [0, 64]");
     if (d->train < 1 || d->train > FSEA_CFAR_MAX_TRAIN) tool_usage_error(tool, "--train must be in [1, 256]");
     if (d->offset < -FSEA_CFAR_MAX_OFFSET || d->offset > FSEA_CFAR_MAX_OFFSET) {
         tool_usage_error(tool, "--offset must be in [-1048576, 1048576]");
     }
+    if (d->have_rank && d->have_method) tool_usage_error(tool, "--rank R is a detector of its own: not together with --method");
+    if (d->have_rank && (d->rank < 1 || d->rank > 2 * d->train)) tool_usage_error(tool, "--rank must be in [1, 2 * --train]");
 }
 
 static inline void tool_detector_check_axis(const char *tool, const tool_detector *d) {
     if ((d->rate != 0.0) != d->have_freq || d->rate < 0.0) tool_usage_error(tool, "--rate HZ (positive) and --freq MHZ go together");
 }
 
+/* The tool's detector: a fsea_cfar, or with --rank a fsea_oscfar; one of the two is not NULL.  Their add, rows and hits forms
+ * have the same arguments, so a tool names the pair and these pass the call on, with the entry point's name for tool_die. */
+typedef struct {
+    fsea_cfar *cfar;
+    fsea_oscfar *oscfar;
+} tool_detector_object;
+
 /* a detector of `width` columns with the options' settings */
-static inline fsea_cfar *tool_detector_create(const char *tool, const tool_detector *d, int width) {
-    fsea_cfar *cfar = NULL;
-    if (fsea_cfar_create(&cfar, width, 0) != FSEA_OK) tool_die(tool, "fsea_cfar_create");
-    if (fsea_cfar_set(cfar, d->guard, d->train, d->offset, d->method) != FSEA_OK) tool_die(tool, "fsea_cfar_set");
-    return cfar;
+static inline tool_detector_object tool_detector_create(const char *tool, const tool_detector *d, int width) {
+    tool_detector_object o = {NULL, NULL};
+    if (d->have_rank) {
+        if (fsea_oscfar_create(&o.oscfar, width, 0) != FSEA_OK) tool_die(tool, "fsea_oscfar_create");
+        if (fsea_oscfar_set(o.oscfar, d->guard, d->train, d->offset, d->rank) != FSEA_OK) tool_die(tool, "fsea_oscfar_set");
+        return o;
+    }
+    if (fsea_cfar_create(&o.cfar, width, 0) != FSEA_OK) tool_die(tool, "fsea_cfar_create");
+    if (fsea_cfar_set(o.cfar, d->guard, d->train, d->offset, d->method) != FSEA_OK) tool_die(tool, "fsea_cfar_set");
+    return o;
+}
+
+static inline void tool_detector_add_device(const char *tool, const tool_detector_object *o, const void *d_rows, int type, size_t n_rows,
+                                            size_t pitch, uint8_t *d_mask) {
+    if (o->oscfar != NULL) {
+        if (fsea_oscfar_add_device(o->oscfar, d_rows, type, n_rows, pitch, d_mask, NULL, NULL) != FSEA_OK) tool_die(tool, "fsea_oscfar_add_device");
+    } else if (fsea_cfar_add_device(o->cfar, d_rows, type, n_rows, pitch, d_mask, NULL, NULL) != FSEA_OK) tool_die(tool, "fsea_cfar_add_device");
+}
+
+static inline void tool_detector_add_host(const char *tool, const tool_detector_object *o, const void *rows, int type, size_t n_rows,
+                                          size_t pitch, uint8_t *mask) {
+    if (o->oscfar != NULL) {
+        if (fsea_oscfar_add_host(o->oscfar, rows, type, n_rows, pitch, mask, NULL) != FSEA_OK) tool_die(tool, "fsea_oscfar_add_host");
+    } else if (fsea_cfar_add_host(o->cfar, rows, type, n_rows, pitch, mask, NULL) != FSEA_OK) tool_die(tool, "fsea_cfar_add_host");
+}
+
+static inline unsigned long long tool_detector_rows(const tool_detector_object *o) {
+    return o->oscfar != NULL ? fsea_oscfar_rows(o->oscfar) : fsea_cfar_rows(o->cfar);
+}
+
+static inline void tool_detector_hits_host(const char *tool, const tool_detector_object *o, uint32_t *hits) {
+    if (o->oscfar != NULL) {
+        if (fsea_oscfar_hits_host(o->oscfar, hits) != FSEA_OK) tool_die(tool, "fsea_oscfar_hits_host");
+    } else if (fsea_cfar_hits_host(o->cfar, hits) != FSEA_OK) tool_die(tool, "fsea_cfar_hits_host");
+}
+
+static inline void tool_detector_destroy(tool_detector_object *o) {
+    fsea_oscfar_destroy(o->oscfar);
+    fsea_cfar_destroy(o->cfar);
+    o->oscfar = NULL;
+    o->cfar = NULL;
 }
 
 /* --image: the rows of the PNG (the caller frees them), their size, and a detector of their width */
-static inline uint8_t *tool_detector_image(const char *tool, const tool_detector *d, int *width, int *height, fsea_cfar **cfar) {
+static inline uint8_t *tool_detector_image(const char *tool, const tool_detector *d, int *width, int *height, tool_detector_object *det) {
     uint8_t *image = read_gray_png(d->image_path, width, height);
     if (image == NULL) {
         fprintf(stderr, "%s: cannot read %s as an 8-bit grey PNG\n", tool, d->image_path);
         exit(EXIT_FAILURE);
     }
     if (*width < 1 || *width > FSEA_CFAR_MAX_WIDTH) tool_usage_error(tool, "the image is wider than 1048576 columns");
-    *cfar = tool_detector_create(tool, d, *width);
+    *det = tool_detector_create(tool, d, *width);
     return image;
 }
 
@@ -248,15 +299,15 @@ static inline fsea_events_run *tool_runs_room(const char *tool, tool_run_list *l
 /* The runs of a recording, to the list: every chunk of the opened `src` to the detector with a mask, mask and rows (of `type`)
  * to the events object, on the device and the null stream.  The object starts each chunk at row 0, so that a chunk can be
  * asked twice: for the number of its runs, then for the records, whose rows this rebases.  Returns the rows done. */
-static inline size_t tool_recording_runs(const char *tool, tool_row_source *src, fsea_cfar *cfar, fsea_events *events, int type,
-                                         tool_run_list *list) {
+static inline size_t tool_recording_runs(const char *tool, tool_row_source *src, const tool_detector_object *det, fsea_events *events,
+                                         int type, tool_run_list *list) {
     const size_t n = src->n;
     void *d_rows = src->d_rows, *d_mask = NULL;
     tool_grown d_runs = {NULL, NULL, 0};
     size_t done = 0;
     if (fsea_device_alloc(0, src->frames_max * n, &d_mask) != FSEA_OK) tool_die(tool, "fsea_device_alloc");
     for (size_t frames; (frames = tool_rows_next(src)) > 0; done += frames) {
-        if (fsea_cfar_add_device(cfar, d_rows, type, frames, n, (uint8_t *)d_mask, NULL, NULL) != FSEA_OK) tool_die(tool, "fsea_cfar_add_device");
+        tool_detector_add_device(tool, det, d_rows, type, frames, n, (uint8_t *)d_mask);
         size_t found = 0;
         if (fsea_events_reset(events) != FSEA_OK) tool_die(tool, "fsea_events_reset");
         if (fsea_events_runs_device(events, (const uint8_t *)d_mask, n, d_rows, type, n, frames, NULL, 0, &found, NULL) != FSEA_OK) {

@@ -34,6 +34,7 @@
  *   fsea_pfb_*            a polyphase filter bank (no counterpart in the reference): all M channels of the band at once
  *   fsea_persist_*        a persistence spectrum (no counterpart in the reference): per-bin level histograms of resident rows
  *   fsea_cfar_*           a CFAR detector across frequency (no counterpart in the reference): occupied bins, bands and masks
+ *   fsea_oscfar_*         an ordered-statistic CFAR detector (no counterpart in the reference): the weaker of two close emissions
  *   fsea_events_*         spectrum events (no counterpart in the reference): a detection mask as runs, time-frequency boxes
  *   fsea_extract_*        event cut-outs (no counterpart in the reference): each box of fsea_events_link as decimated IQ
  *   fsea_measure_*        signal measures (no counterpart in the reference): power, offset, width and envelope of each cut-out
@@ -72,6 +73,7 @@ typedef struct fsea_zoom fsea_zoom;
 typedef struct fsea_pfb fsea_pfb;
 typedef struct fsea_persist fsea_persist;
 typedef struct fsea_cfar fsea_cfar;
+typedef struct fsea_oscfar fsea_oscfar;
 typedef struct fsea_events fsea_events;
 typedef struct fsea_extract fsea_extract;
 typedef struct fsea_demod fsea_demod;
@@ -706,6 +708,52 @@ int fsea_cfar_add_host(fsea_cfar *cfar, const void *rows, int type, size_t n_row
 int fsea_cfar_hits_host(fsea_cfar *cfar, uint32_t *hits);
 int fsea_cfar_bands(const uint32_t *hits, int width, uint64_t rows, double min_fraction, int max_gap, int min_width,
                     fsea_cfar_band *bands, size_t capacity, size_t *n_bands);
+
+/* The ordered-statistic CFAR detector: fsea_cfar's question answered against a rank of the training cells in place of their
+ * mean.  A mean is pulled up by any strong neighbour, so under fsea_cfar the weaker of two close emissions gets no hit; the
+ * R-th smallest level of the window is not moved by a few strong cells.  A u8 row of 128 cells at level 100 with a carrier of
+ * 200 on columns 40 .. 47 and one of 130 on column 60, G = 2, T = 16, offset 20: CA hits 40 .. 47 only (column 60 sees a mean
+ * of 118.75), rank 24 of 32 hits 40 .. 47 and 60.  The object is fsea_cfar's in every other respect: it owns hits[k], width
+ * uint32_t, zero after create and reset; `rows`, the rows offered so far; and the settings (guard G, train T, offset, rank R),
+ * (2, 16, 60, 24) after create -- three quarters of the window, Rohling's choice.  Integer and order-free.
+ *   level, windows: fsea_cfar's, above: the same levels of u8 and f32 elements (FSEA_CFAR_U8 / FSEA_CFAR_F32), left training
+ *           cells k-G-T .. k-G-1 and right training cells k+G+1 .. k+G+T, each side clipped to [0, width-1], no wrap-around;
+ *           n = nL + nR is the number of training cells inside the row.
+ *   decision: for the cell's level x, all in 32-bit integers.  r = (R*n + 2T - 1) / (2T) rounded down, that is
+ *           ceil(R*n / 2T): at least 1, and R for a window that is not clipped.  z is the r-th smallest level of the n
+ *           training cells, counted from 1, ties counted as often as they occur.  hit: n > 0 and x > z + offset.
+ *           The counting identity: hit exactly when n > 0 and the number of training cells with level + offset < x is at
+ *           least r (r such cells put the r-th smallest among them, and the r-th smallest below x - offset puts the r - 1
+ *           before it there too).  This is what the kernels evaluate; nothing is sorted.
+ *   set:    checks guard, train, offset, rank in this order; R is in [1, 2T].  rank returns R (0 for NULL).
+ *   add, hits_host: fsea_cfar_add_* and fsea_cfar_hits_host word for word: pitch and sub-bands, the tight optional d_mask
+ *           (255 / 0), the optional d_row_hits (set, not added to), hits[k] += and rows += with the 2^32 - 1 guard, the
+ *           n_rows == 0 no-op, the alignment of the device form's three pointers, the order of calls on different streams, the
+ *           16-byte and element-wise reads and mask writes, the staging of the host form.
+ *           Kernels fsea_oscfar_u8 / fsea_oscfar_f32: a workgroup of 256 lanes takes a tile of FSEA_OSCFAR_TILE_COLUMNS columns
+ *           over a run of FSEA_OSCFAR_RUN_ROWS rows; a row segment's levels in LDS are compared 2T to a cell, the cost grows
+ *           with T.
+ *   bands:  fsea_cfar_bands on the fetched hits.
+ * Every check runs before any device work, in fsea_cfar's order with the rank behind the offset: FSEA_EINVAL for a NULL object
+ * or input buffer, a width outside [1, FSEA_CFAR_MAX_WIDTH], a guard outside [0, FSEA_CFAR_MAX_GUARD], a train outside
+ * [1, FSEA_CFAR_MAX_TRAIN], |offset| above FSEA_CFAR_MAX_OFFSET, a rank outside [1, 2 * train], an unknown type, pitch < width,
+ * n_rows > 2^31, a misaligned device pointer.  Create: FSEA_ENODEVICE without a GPU.  width, rows and rank return 0 for NULL.
+ * Destroy and reset wait for the device; reset zeroes hits and rows and keeps the settings.  Calls on one object from several
+ * threads are serialised. */
+#define FSEA_OSCFAR_TILE_COLUMNS 1024   /* columns of a workgroup of the add kernels */
+#define FSEA_OSCFAR_RUN_ROWS 64         /* rows a workgroup of the add kernels takes before it adds its column hits to hits */
+int fsea_oscfar_create(fsea_oscfar **oscfar, int width, int device);
+int fsea_oscfar_destroy(fsea_oscfar *oscfar);
+int fsea_oscfar_reset(fsea_oscfar *oscfar);
+int fsea_oscfar_set(fsea_oscfar *oscfar, int guard, int train, int offset, int rank);
+int fsea_oscfar_width(const fsea_oscfar *oscfar);
+uint64_t fsea_oscfar_rows(const fsea_oscfar *oscfar);
+int fsea_oscfar_rank(const fsea_oscfar *oscfar);
+int fsea_oscfar_add_device(fsea_oscfar *oscfar, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask,
+                           uint32_t *d_row_hits, void *stream);
+int fsea_oscfar_add_host(fsea_oscfar *oscfar, const void *rows, int type, size_t n_rows, size_t pitch, uint8_t *mask,
+                         uint32_t *row_hits);
+int fsea_oscfar_hits_host(fsea_oscfar *oscfar, uint32_t *hits);
 
 /* Spectrum events: which emissions a detection mask holds -- this burst, from row 812 to row 860, columns 3011 .. 3042, peak
  * 171 at (830, 3027).  A device pass reduces a resident mask (fsea_cfar's, n_rows x width bytes) and optionally the level rows
