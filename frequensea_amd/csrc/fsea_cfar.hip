@@ -25,6 +25,10 @@
 // level arrays are a wave's own, so the four waves meet only at the kernel's first and last barrier, and a wave loads the
 // 16-byte groups of its next row before it decides the current one.
 //
+// fsea_cfar_shared.h has what this file shares with fsea_oscfar.hip as code: the geometry's constants, level_at, spread4,
+// wave_sync, the kernels' one signature, the object, its launch and the entry points.  Step 3 and the end of the run stand
+// in both files as text: moved into functions they compile to other registers here ("What the detectors share").
+//
 // The prefix sums are u32 and wrap: an f32 level is in [-2^20, 2^20], so a prefix value may be "negative" (two's complement)
 // or, over a long row, pass 2^32.  A side sum has at most 256 terms, |S| <= 2^28, and the difference of two u32 prefix values
 // is that sum modulo 2^32, hence exact once read as an int32_t.  (Here the prefix restarts at every segment of at most 1680
@@ -33,40 +37,32 @@
 // The _narrow kernels are the same code with every cell loaded on its own (any pitch and base).  In the 16-byte kernels a
 // group that would end past the row's width is loaded cell by cell too, so no load passes the width; the mask is written 16
 // bytes per lane where the width is a multiple of 16 and byte by byte otherwise.
-#include "fsea_rows.h"
+#include "fsea_cfar_shared.h"
 
 #include <cmath>
 #include <type_traits>
 
-using fsea_detail::DeviceGuard;
 using fsea_detail::cfar_level_f32;
 using fsea_detail::fail;
+using fsea_detail::level_at;
 using fsea_detail::run_of_workgroup;
+using fsea_detail::spread4;
+using fsea_detail::wave_sync;
 
 namespace {
 
-constexpr int CF_WG = 256;                        // lanes per workgroup
-constexpr int CF_WAVES = CF_WG / 64;
-constexpr int CF_C = FSEA_CFAR_TILE_COLUMNS;      // columns per tile
-constexpr int CF_RUN = FSEA_CFAR_RUN_ROWS;        // rows per workgroup
+constexpr int CF_WAVES = fsea_detail::DET_WAVES;
+constexpr int CF_C = fsea_detail::DET_C;          // columns per tile
 constexpr int CF_HALO = FSEA_CFAR_MAX_GUARD + FSEA_CFAR_MAX_TRAIN;
 constexpr int CF_SEG = CF_C + 2 * CF_HALO + 16;   // cells of a staged segment at most (a0 is rounded down by up to 15)
 constexpr int CF_FRONT = (CF_HALO + 1 + 15) & ~15;   // zero dwords in front of a wave's prefix array: the cells before the row
 constexpr int CF_Q = CF_FRONT + CF_SEG;           // dwords of a wave's prefix array
 static_assert(CF_SEG % 16 == 0, "whole 16-byte groups");
-static_assert(CF_C == 16 * 64, "a wave decides a row of the tile in 16 steps; a lane stores 16 mask bytes");
-static_assert(CF_RUN % CF_WAVES == 0 && CF_RUN / CF_WAVES <= 255, "a run is whole iterations of the four waves; a lane counts a column in a byte");
 static_assert((CF_WAVES * (CF_Q + CF_C) + CF_C) * 4 <= 80 * 1024, "two workgroups per CU");
 
 struct Settings {
-    int guard, train, offset, method;
+    int guard = 2, train = 16, offset = 60, method = FSEA_CFAR_CA;
 };
-
-template <bool F32>
-__device__ __forceinline__ int level_at(const void *__restrict__ rows, size_t i) {
-    if (F32) return cfar_level_f32(static_cast<const float *>(rows)[i]);
-    return (int)static_cast<const uint8_t *>(rows)[i];
-}
 
 // Whether the group that starts at `cell` is read with one 16-byte load: the kernel may (VEC), the group starts inside the
 // segment and ends inside the width.
@@ -93,9 +89,6 @@ __device__ __forceinline__ void levels_of(const void *__restrict__ rows, size_t 
     for (int e = 0; e < EPG; ++e) lv[e] = live && cell + e < end ? level_at<F32>(rows, at + cell + e) : 0;
 }
 
-// bits 0..3 of n to the bytes of a word, 255 for a set bit: the four shifted copies of n do not overlap
-__device__ __forceinline__ uint32_t spread4(uint32_t n) { return (((n & 15u) * 0x00204081u) & 0x01010101u) * 255u; }
-
 template <bool F32, bool VEC>
 __device__ __forceinline__ void cfar_body(const void *__restrict__ rows, size_t n_rows, size_t pitch, int width, Settings st,
                                           uint8_t *__restrict__ mask, int mask_vec, uint32_t *__restrict__ row_hits,
@@ -115,11 +108,11 @@ __device__ __forceinline__ void cfar_body(const void *__restrict__ rows, size_t 
     const int ngrp = (c0 + CF_C + G + T - a0 + EPG - 1) / EPG; // ... and the groups up to the last cell a window may name
     const bool inner = c0 - G - T >= 0 && c0 + CF_C + G + T <= width;
     size_t row0;
-    const int run = run_of_workgroup<CF_RUN>(n_rows, &row0);
+    const int run = run_of_workgroup<fsea_detail::DET_RUN>(n_rows, &row0);
 
-    for (int i = tid; i < CF_C; i += CF_WG) total[i] = 0u;
+    for (int i = tid; i < CF_C; i += fsea_detail::DET_WG) total[i] = 0u;
     for (int i = lane; i < CF_FRONT; i += 64) q[i] = 0u;       // the cells before the row and before the segment
-    uint32_t cnt[4] = {0u, 0u, 0u, 0u};                        // the lane's 16 columns, a byte each: at most CF_RUN / 4 hits
+    uint32_t cnt[4] = {0u, 0u, 0u, 0u};                        // the lane's 16 columns, a byte each: at most DET_RUN / 4 hits
     __syncthreads();
 
     // the 16-byte groups of a row are loaded one row ahead: raw[c] is the lane's group of chunk c (zero where there is none)
@@ -137,13 +130,6 @@ __device__ __forceinline__ void cfar_body(const void *__restrict__ rows, size_t 
         }
     };
     fetch(wave, 0);
-
-    // The waves do not wait for one another: q and x are a wave's own, an LDS instruction of a wave is carried out after the
-    // ones it issued before, and wave_sync() keeps the compiler from moving an access across it.
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
 
     for (int it = 0; it < (run + CF_WAVES - 1) / CF_WAVES; ++it) {
         const int rr = it * CF_WAVES + wave;
@@ -244,7 +230,7 @@ __device__ __forceinline__ void cfar_body(const void *__restrict__ rows, size_t 
         if (n) atomicAdd(&total[64 * j + lane], n);
     }
     __syncthreads();
-    for (int i = tid; i < CF_C; i += CF_WG) {
+    for (int i = tid; i < CF_C; i += fsea_detail::DET_WG) {
         const uint32_t v = total[i];
         if (v && c0 + i < width) atomicAdd(&hits[c0 + i], v);
     }
@@ -252,81 +238,26 @@ __device__ __forceinline__ void cfar_body(const void *__restrict__ rows, size_t 
 
 }  // namespace
 
-#define FSEA_CFAR_KERNEL(name, F32, VEC)                                                                                       \
-    extern "C" __global__ __launch_bounds__(CF_WG, 3) void name(const void *__restrict__ rows, size_t n_rows, size_t pitch,      \
-                                                              int width, int guard, int train, int offset, int method,        \
-                                                              uint8_t *__restrict__ mask, int mask_vec,                        \
-                                                              uint32_t *__restrict__ row_hits, uint32_t *__restrict__ hits) { \
-        cfar_body<F32, VEC>(rows, n_rows, pitch, width, Settings{guard, train, offset, method}, mask, mask_vec, row_hits,     \
-                            hits);                                                                                             \
-    }
-FSEA_CFAR_KERNEL(fsea_cfar_u8, false, true)
-FSEA_CFAR_KERNEL(fsea_cfar_f32, true, true)
-FSEA_CFAR_KERNEL(fsea_cfar_u8_narrow, false, false)
-FSEA_CFAR_KERNEL(fsea_cfar_f32_narrow, true, false)
-#undef FSEA_CFAR_KERNEL
+FSEA_DETECTOR_KERNEL(fsea_cfar_u8, cfar_body, 3, false, true)
+FSEA_DETECTOR_KERNEL(fsea_cfar_f32, cfar_body, 3, true, true)
+FSEA_DETECTOR_KERNEL(fsea_cfar_u8_narrow, cfar_body, 3, false, false)
+FSEA_DETECTOR_KERNEL(fsea_cfar_f32_narrow, cfar_body, 3, true, false)
 
-struct fsea_cfar : fsea_detail::RowObject {
-    Settings set{2, 16, 60, FSEA_CFAR_CA};
-    fsea_detail::ZeroedScratch hits;              // width u32; its event orders the calls
-    std::mutex mu;
-    fsea_detail::HostStaging staging;             // the host forms
-};
-
-namespace {
-
-// One add on device rows, asynchronous on `s`.  The caller holds c->mu, is on c's device and has checked the arguments.
-int add_launch(fsea_cfar *c, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask, uint32_t *d_row_hits,
-               hipStream_t s) {
-    int rc = c->hits.acquire(s);
-    if (rc) return rc;
-    uint32_t *hits = static_cast<uint32_t *>(c->hits.buf.ptr);
-    const int width = c->width;
-    if (d_row_hits) FSEA_HIP(hipMemsetAsync(d_row_hits, 0, n_rows * sizeof(uint32_t), s));   // set, not added to
-    const dim3 grid((unsigned)((n_rows + CF_RUN - 1) / CF_RUN), (unsigned)((width + CF_C - 1) / CF_C));
-    const bool vec = fsea_detail::rows_vec16(d_rows, pitch * fsea_detail::row_elem_bytes(type));
-    const int mask_vec = width % 16 == 0;
-    const Settings st = c->set;
-    auto kernel = type == FSEA_CFAR_U8 ? (vec ? fsea_cfar_u8 : fsea_cfar_u8_narrow) : (vec ? fsea_cfar_f32 : fsea_cfar_f32_narrow);
-    hipLaunchKernelGGL(kernel, grid, dim3(CF_WG), 0, s, d_rows, n_rows, pitch, width, st.guard, st.train, st.offset, st.method,
-                       d_mask, mask_vec, d_row_hits, hits);
-    FSEA_HIP(hipGetLastError());
-    c->rows += n_rows;
-    return c->hits.release(s);
-}
-
-}  // namespace
+// object, launch and entry points: fsea_cfar_shared.h
+struct fsea_cfar : fsea_detail::Detector<Settings, fsea_cfar_u8, fsea_cfar_f32, fsea_cfar_u8_narrow, fsea_cfar_f32_narrow> {};
 
 extern "C" {
 
 int fsea_cfar_create(fsea_cfar **out, int width, int device) {
-    if (!out) return fail(FSEA_EINVAL, "cfar out-pointer is NULL");
-    *out = nullptr;
-    if (width < 1 || width > FSEA_CFAR_MAX_WIDTH) {
-        return fail(FSEA_EINVAL, "width must be in [1, %d], got %d", FSEA_CFAR_MAX_WIDTH, width);
-    }
-    return fsea_detail::create_object(out, device, "fsea_cfar_create", [&](fsea_cfar *c) -> int {
-        c->width = width;
-        return c->hits.create_zeroed("fsea_cfar_create", (size_t)width * sizeof(uint32_t), c->staging.stream);
-    });
+    return fsea_detail::detector_create(out, width, device, "cfar", "fsea_cfar_create");
 }
 
 int fsea_cfar_destroy(fsea_cfar *c) { return fsea_detail::destroy_object(c); }
 
-int fsea_cfar_reset(fsea_cfar *c) {
-    return fsea_detail::reset_object(c, "cfar is NULL", [&] {
-        c->rows = 0;
-        return c->hits.zero();
-    });
-}
+int fsea_cfar_reset(fsea_cfar *c) { return fsea_detail::detector_reset(c, "cfar is NULL"); }
 
 int fsea_cfar_set(fsea_cfar *c, int guard, int train, int offset, int method) {
-    if (!c) return fail(FSEA_EINVAL, "cfar is NULL");
-    if (guard < 0 || guard > FSEA_CFAR_MAX_GUARD) return fail(FSEA_EINVAL, "guard must be in [0, %d], got %d", FSEA_CFAR_MAX_GUARD, guard);
-    if (train < 1 || train > FSEA_CFAR_MAX_TRAIN) return fail(FSEA_EINVAL, "train must be in [1, %d], got %d", FSEA_CFAR_MAX_TRAIN, train);
-    if (offset < -FSEA_CFAR_MAX_OFFSET || offset > FSEA_CFAR_MAX_OFFSET) {
-        return fail(FSEA_EINVAL, "offset must be in [-%d, %d], got %d", FSEA_CFAR_MAX_OFFSET, FSEA_CFAR_MAX_OFFSET, offset);
-    }
+    if (int rc = fsea_detail::detector_check_set(c, "cfar", guard, train, offset)) return rc;
     if (method != FSEA_CFAR_CA && method != FSEA_CFAR_GO && method != FSEA_CFAR_SO) return fail(FSEA_EINVAL, "unknown method %d", method);
     std::lock_guard<std::mutex> lock(c->mu);
     c->set = Settings{guard, train, offset, method};
@@ -339,45 +270,14 @@ uint64_t fsea_cfar_rows(const fsea_cfar *c) { return c ? c->rows : 0; }
 
 int fsea_cfar_add_device(fsea_cfar *c, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask,
                          uint32_t *d_row_hits, void *stream) {
-    int rc = fsea_detail::check_rows_add(c, "cfar", d_rows, type, n_rows, pitch);
-    if (!rc && n_rows) rc = fsea_detail::check_aligned16("d_rows, d_mask and d_row_hits", d_rows, d_mask, d_row_hits);
-    if (rc) return rc;
-    if (n_rows == 0) return FSEA_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if ((rc = fsea_detail::check_rows_room(c, n_rows))) return rc;
-    FSEA_ON_DEVICE(c->device);
-    return add_launch(c, d_rows, type, n_rows, pitch, d_mask, d_row_hits, static_cast<hipStream_t>(stream));
+    return fsea_detail::detector_add_device(c, "cfar", d_rows, type, n_rows, pitch, d_mask, d_row_hits, stream);
 }
 
 int fsea_cfar_add_host(fsea_cfar *c, const void *rows, int type, size_t n_rows, size_t pitch, uint8_t *mask, uint32_t *row_hits) {
-    int rc = fsea_detail::check_rows_add(c, "cfar", rows, type, n_rows, pitch);
-    if (rc) return rc;
-    if (n_rows == 0) return FSEA_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if ((rc = fsea_detail::check_rows_room(c, n_rows))) return rc;
-    FSEA_ON_DEVICE(c->device);
-    // the rows go up packed, in chunks; mask and row hits of a chunk come back behind it
-    const size_t width = (size_t)c->width, esz = fsea_detail::row_elem_bytes(type);
-    const fsea_detail::PackedPlane in(rows, pitch * esz, width * esz);
-    return fsea_detail::for_row_chunks(n_rows, in.packed, [&](size_t r0, size_t nr) {
-        const fsea_detail::HostStaging::Part parts[2] = {{mask ? mask + r0 * width : nullptr, nr * width},
-                                                         {row_hits ? row_hits + r0 : nullptr, nr * sizeof(uint32_t)}};
-        return c->staging.run(
-            nr * in.packed, parts, [&](void *h_in) { in.pack(h_in, r0, nr); },
-            [&](void *d_in, void **d_parts, hipStream_t s) {
-                return add_launch(c, d_in, type, nr, in.packed / esz, static_cast<uint8_t *>(d_parts[0]),
-                                  static_cast<uint32_t *>(d_parts[1]), s);
-            });
-    });
+    return fsea_detail::detector_add_host(c, "cfar", rows, type, n_rows, pitch, mask, row_hits);
 }
 
-int fsea_cfar_hits_host(fsea_cfar *c, uint32_t *hits) {
-    if (!c) return fail(FSEA_EINVAL, "cfar is NULL");
-    if (!hits) return fail(FSEA_EINVAL, "hits is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    FSEA_ON_DEVICE(c->device);
-    return c->hits.fetch(c->staging, hits);
-}
+int fsea_cfar_hits_host(fsea_cfar *c, uint32_t *hits) { return fsea_detail::detector_hits_host(c, "cfar", hits); }
 
 int fsea_cfar_bands(const uint32_t *hits, int width, uint64_t rows, double min_fraction, int max_gap, int min_width,
                     fsea_cfar_band *bands, size_t capacity, size_t *n_bands) {

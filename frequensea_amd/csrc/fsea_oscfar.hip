@@ -31,40 +31,36 @@
 // array is a wave's own, so the four waves meet only at the kernel's first and last barrier, and a wave loads the 16-byte
 // groups of its next row before it decides the current one.
 //
+// fsea_cfar_shared.h has what this file shares with fsea_cfar.hip as code: the geometry's constants, level_at, spread4,
+// wave_sync, the kernels' one signature, the object, its launch and the entry points.  Step 3 and the end of the run are
+// fsea_cfar's as text: moved into functions they compile to other registers there ("What the detectors share").
+//
 // The _narrow kernels are the same code with every cell loaded on its own (any pitch and base).  In the 16-byte kernels a
 // group that would begin before the row or end past its width is loaded cell by cell too, so no load leaves the row; the
 // mask is written 16 bytes per lane where the width is a multiple of 16 and byte by byte otherwise.
-#include "fsea_rows.h"
+#include "fsea_cfar_shared.h"
 
-using fsea_detail::DeviceGuard;
 using fsea_detail::cfar_level_f32;
 using fsea_detail::fail;
+using fsea_detail::level_at;
 using fsea_detail::run_of_workgroup;
+using fsea_detail::spread4;
+using fsea_detail::wave_sync;
 
 namespace {
 
-constexpr int OS_WG = 256;                        // lanes per workgroup
-constexpr int OS_WAVES = OS_WG / 64;
-constexpr int OS_C = FSEA_OSCFAR_TILE_COLUMNS;    // columns per tile
-constexpr int OS_RUN = FSEA_OSCFAR_RUN_ROWS;      // rows per workgroup
+constexpr int OS_WAVES = fsea_detail::DET_WAVES;
+constexpr int OS_C = fsea_detail::DET_C;          // columns per tile
 constexpr int OS_PAD = (FSEA_CFAR_MAX_GUARD + FSEA_CFAR_MAX_TRAIN + 15) & ~15;   // cells of a halo at most, whole groups
 constexpr int OS_SEG = OS_C + 2 * OS_PAD;         // dwords of a wave's level array
 constexpr int OS_OUTSIDE = 1 << 29;               // the level of a cell outside the row: below no threshold
-static_assert(OS_C == 16 * 64, "a wave decides a row of the tile in 16 steps; a lane stores 16 mask bytes");
-static_assert(OS_RUN % OS_WAVES == 0 && OS_RUN / OS_WAVES <= 255, "a run is whole iterations of the four waves; a lane counts a column in a byte");
 static_assert((OS_WAVES * OS_SEG + OS_C) * 4 <= 80 * 1024, "two workgroups per CU");
 static_assert(OS_OUTSIDE > 2 * fsea_detail::CFAR_LEVEL_LIMIT + 255 && FSEA_CFAR_MAX_OFFSET == fsea_detail::CFAR_LEVEL_LIMIT,
               "x - offset stays below OUTSIDE, and OUTSIDE - (x - offset) inside an int");
 
 struct Settings {
-    int guard, train, offset, rank;
+    int guard = 2, train = 16, offset = 60, rank = 24;
 };
-
-template <bool F32>
-__device__ __forceinline__ int level_at(const void *__restrict__ rows, size_t i) {
-    if (F32) return cfar_level_f32(static_cast<const float *>(rows)[i]);
-    return (int)static_cast<const uint8_t *>(rows)[i];
-}
 
 // Whether the group that starts at `cell` is read with one 16-byte load: the kernel may (VEC) and the group lies inside the row.
 template <bool VEC, int EPG>
@@ -99,9 +95,6 @@ __device__ __forceinline__ int med3(int a, int lo, int hi) {
     return r;
 }
 
-// bits 0..3 of n to the bytes of a word, 255 for a set bit: the four shifted copies of n do not overlap
-__device__ __forceinline__ uint32_t spread4(uint32_t n) { return (((n & 15u) * 0x00204081u) & 0x01010101u) * 255u; }
-
 template <bool F32, bool VEC>
 __device__ __forceinline__ void oscfar_body(const void *__restrict__ rows, size_t n_rows, size_t pitch, int width, Settings st,
                                             uint8_t *__restrict__ mask, int mask_vec, uint32_t *__restrict__ row_hits,
@@ -119,10 +112,10 @@ __device__ __forceinline__ void oscfar_body(const void *__restrict__ rows, size_
     const int ngrp = (OS_C + 2 * halo) / EPG;     // the groups of the staged cells [g0, c0 + C + halo)
     int32_t *seg = lv + (OS_PAD - halo);          // seg[i]: the level of cell g0 + i
     size_t row0;
-    const int run = run_of_workgroup<OS_RUN>(n_rows, &row0);
+    const int run = run_of_workgroup<fsea_detail::DET_RUN>(n_rows, &row0);
 
-    for (int i = tid; i < OS_C; i += OS_WG) total[i] = 0u;
-    uint32_t cnt[4] = {0u, 0u, 0u, 0u};           // the lane's 16 columns, a byte each: at most OS_RUN / 4 hits
+    for (int i = tid; i < OS_C; i += fsea_detail::DET_WG) total[i] = 0u;
+    uint32_t cnt[4] = {0u, 0u, 0u, 0u};           // the lane's 16 columns, a byte each: at most DET_RUN / 4 hits
     __syncthreads();
 
     // the 16-byte groups of a row are loaded one row ahead: raw[c] is the lane's group of chunk c (zero where there is none)
@@ -140,13 +133,6 @@ __device__ __forceinline__ void oscfar_body(const void *__restrict__ rows, size_
         }
     };
     fetch(wave);
-
-    // The waves do not wait for one another: lv is a wave's own, an LDS instruction of a wave is carried out after the ones
-    // it issued before, and wave_sync() keeps the compiler from moving an access across it.
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
 
     const int two_t = 2 * T;
     for (int rr = wave; rr < run; rr += OS_WAVES) {            // the same for all lanes of a wave
@@ -218,7 +204,7 @@ __device__ __forceinline__ void oscfar_body(const void *__restrict__ rows, size_
         if (n) atomicAdd(&total[64 * j + lane], n);
     }
     __syncthreads();
-    for (int i = tid; i < OS_C; i += OS_WG) {
+    for (int i = tid; i < OS_C; i += fsea_detail::DET_WG) {
         const uint32_t v = total[i];
         if (v && c0 + i < width) atomicAdd(&hits[c0 + i], v);
     }
@@ -226,81 +212,26 @@ __device__ __forceinline__ void oscfar_body(const void *__restrict__ rows, size_
 
 }  // namespace
 
-#define FSEA_OSCFAR_KERNEL(name, F32, VEC)                                                                                     \
-    extern "C" __global__ __launch_bounds__(OS_WG, 4) void name(const void *__restrict__ rows, size_t n_rows, size_t pitch,      \
-                                                              int width, int guard, int train, int offset, int rank,          \
-                                                              uint8_t *__restrict__ mask, int mask_vec,                        \
-                                                              uint32_t *__restrict__ row_hits, uint32_t *__restrict__ hits) { \
-        oscfar_body<F32, VEC>(rows, n_rows, pitch, width, Settings{guard, train, offset, rank}, mask, mask_vec, row_hits,     \
-                              hits);                                                                                           \
-    }
-FSEA_OSCFAR_KERNEL(fsea_oscfar_u8, false, true)
-FSEA_OSCFAR_KERNEL(fsea_oscfar_f32, true, true)
-FSEA_OSCFAR_KERNEL(fsea_oscfar_u8_narrow, false, false)
-FSEA_OSCFAR_KERNEL(fsea_oscfar_f32_narrow, true, false)
-#undef FSEA_OSCFAR_KERNEL
+FSEA_DETECTOR_KERNEL(fsea_oscfar_u8, oscfar_body, 4, false, true)
+FSEA_DETECTOR_KERNEL(fsea_oscfar_f32, oscfar_body, 4, true, true)
+FSEA_DETECTOR_KERNEL(fsea_oscfar_u8_narrow, oscfar_body, 4, false, false)
+FSEA_DETECTOR_KERNEL(fsea_oscfar_f32_narrow, oscfar_body, 4, true, false)
 
-struct fsea_oscfar : fsea_detail::RowObject {
-    Settings set{2, 16, 60, 24};
-    fsea_detail::ZeroedScratch hits;              // width u32; its event orders the calls
-    std::mutex mu;
-    fsea_detail::HostStaging staging;             // the host forms
-};
-
-namespace {
-
-// One add on device rows, asynchronous on `s`.  The caller holds c->mu, is on c's device and has checked the arguments.
-int add_launch(fsea_oscfar *c, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask, uint32_t *d_row_hits,
-               hipStream_t s) {
-    int rc = c->hits.acquire(s);
-    if (rc) return rc;
-    uint32_t *hits = static_cast<uint32_t *>(c->hits.buf.ptr);
-    const int width = c->width;
-    if (d_row_hits) FSEA_HIP(hipMemsetAsync(d_row_hits, 0, n_rows * sizeof(uint32_t), s));   // set, not added to
-    const dim3 grid((unsigned)((n_rows + OS_RUN - 1) / OS_RUN), (unsigned)((width + OS_C - 1) / OS_C));
-    const bool vec = fsea_detail::rows_vec16(d_rows, pitch * fsea_detail::row_elem_bytes(type));
-    const int mask_vec = width % 16 == 0;
-    const Settings st = c->set;
-    auto kernel = type == FSEA_CFAR_U8 ? (vec ? fsea_oscfar_u8 : fsea_oscfar_u8_narrow) : (vec ? fsea_oscfar_f32 : fsea_oscfar_f32_narrow);
-    hipLaunchKernelGGL(kernel, grid, dim3(OS_WG), 0, s, d_rows, n_rows, pitch, width, st.guard, st.train, st.offset, st.rank,
-                       d_mask, mask_vec, d_row_hits, hits);
-    FSEA_HIP(hipGetLastError());
-    c->rows += n_rows;
-    return c->hits.release(s);
-}
-
-}  // namespace
+// object, launch and entry points: fsea_cfar_shared.h
+struct fsea_oscfar : fsea_detail::Detector<Settings, fsea_oscfar_u8, fsea_oscfar_f32, fsea_oscfar_u8_narrow, fsea_oscfar_f32_narrow> {};
 
 extern "C" {
 
 int fsea_oscfar_create(fsea_oscfar **out, int width, int device) {
-    if (!out) return fail(FSEA_EINVAL, "oscfar out-pointer is NULL");
-    *out = nullptr;
-    if (width < 1 || width > FSEA_CFAR_MAX_WIDTH) {
-        return fail(FSEA_EINVAL, "width must be in [1, %d], got %d", FSEA_CFAR_MAX_WIDTH, width);
-    }
-    return fsea_detail::create_object(out, device, "fsea_oscfar_create", [&](fsea_oscfar *c) -> int {
-        c->width = width;
-        return c->hits.create_zeroed("fsea_oscfar_create", (size_t)width * sizeof(uint32_t), c->staging.stream);
-    });
+    return fsea_detail::detector_create(out, width, device, "oscfar", "fsea_oscfar_create");
 }
 
 int fsea_oscfar_destroy(fsea_oscfar *c) { return fsea_detail::destroy_object(c); }
 
-int fsea_oscfar_reset(fsea_oscfar *c) {
-    return fsea_detail::reset_object(c, "oscfar is NULL", [&] {
-        c->rows = 0;
-        return c->hits.zero();
-    });
-}
+int fsea_oscfar_reset(fsea_oscfar *c) { return fsea_detail::detector_reset(c, "oscfar is NULL"); }
 
 int fsea_oscfar_set(fsea_oscfar *c, int guard, int train, int offset, int rank) {
-    if (!c) return fail(FSEA_EINVAL, "oscfar is NULL");
-    if (guard < 0 || guard > FSEA_CFAR_MAX_GUARD) return fail(FSEA_EINVAL, "guard must be in [0, %d], got %d", FSEA_CFAR_MAX_GUARD, guard);
-    if (train < 1 || train > FSEA_CFAR_MAX_TRAIN) return fail(FSEA_EINVAL, "train must be in [1, %d], got %d", FSEA_CFAR_MAX_TRAIN, train);
-    if (offset < -FSEA_CFAR_MAX_OFFSET || offset > FSEA_CFAR_MAX_OFFSET) {
-        return fail(FSEA_EINVAL, "offset must be in [-%d, %d], got %d", FSEA_CFAR_MAX_OFFSET, FSEA_CFAR_MAX_OFFSET, offset);
-    }
+    if (int rc = fsea_detail::detector_check_set(c, "oscfar", guard, train, offset)) return rc;
     if (rank < 1 || rank > 2 * train) return fail(FSEA_EINVAL, "rank must be in [1, 2 * train = %d], got %d", 2 * train, rank);
     std::lock_guard<std::mutex> lock(c->mu);
     c->set = Settings{guard, train, offset, rank};
@@ -315,44 +246,13 @@ int fsea_oscfar_rank(const fsea_oscfar *c) { return c ? c->set.rank : 0; }
 
 int fsea_oscfar_add_device(fsea_oscfar *c, const void *d_rows, int type, size_t n_rows, size_t pitch, uint8_t *d_mask,
                            uint32_t *d_row_hits, void *stream) {
-    int rc = fsea_detail::check_rows_add(c, "oscfar", d_rows, type, n_rows, pitch);
-    if (!rc && n_rows) rc = fsea_detail::check_aligned16("d_rows, d_mask and d_row_hits", d_rows, d_mask, d_row_hits);
-    if (rc) return rc;
-    if (n_rows == 0) return FSEA_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if ((rc = fsea_detail::check_rows_room(c, n_rows))) return rc;
-    FSEA_ON_DEVICE(c->device);
-    return add_launch(c, d_rows, type, n_rows, pitch, d_mask, d_row_hits, static_cast<hipStream_t>(stream));
+    return fsea_detail::detector_add_device(c, "oscfar", d_rows, type, n_rows, pitch, d_mask, d_row_hits, stream);
 }
 
 int fsea_oscfar_add_host(fsea_oscfar *c, const void *rows, int type, size_t n_rows, size_t pitch, uint8_t *mask, uint32_t *row_hits) {
-    int rc = fsea_detail::check_rows_add(c, "oscfar", rows, type, n_rows, pitch);
-    if (rc) return rc;
-    if (n_rows == 0) return FSEA_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if ((rc = fsea_detail::check_rows_room(c, n_rows))) return rc;
-    FSEA_ON_DEVICE(c->device);
-    // the rows go up packed, in chunks; mask and row hits of a chunk come back behind it
-    const size_t width = (size_t)c->width, esz = fsea_detail::row_elem_bytes(type);
-    const fsea_detail::PackedPlane in(rows, pitch * esz, width * esz);
-    return fsea_detail::for_row_chunks(n_rows, in.packed, [&](size_t r0, size_t nr) {
-        const fsea_detail::HostStaging::Part parts[2] = {{mask ? mask + r0 * width : nullptr, nr * width},
-                                                         {row_hits ? row_hits + r0 : nullptr, nr * sizeof(uint32_t)}};
-        return c->staging.run(
-            nr * in.packed, parts, [&](void *h_in) { in.pack(h_in, r0, nr); },
-            [&](void *d_in, void **d_parts, hipStream_t s) {
-                return add_launch(c, d_in, type, nr, in.packed / esz, static_cast<uint8_t *>(d_parts[0]),
-                                  static_cast<uint32_t *>(d_parts[1]), s);
-            });
-    });
+    return fsea_detail::detector_add_host(c, "oscfar", rows, type, n_rows, pitch, mask, row_hits);
 }
 
-int fsea_oscfar_hits_host(fsea_oscfar *c, uint32_t *hits) {
-    if (!c) return fail(FSEA_EINVAL, "oscfar is NULL");
-    if (!hits) return fail(FSEA_EINVAL, "hits is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    FSEA_ON_DEVICE(c->device);
-    return c->hits.fetch(c->staging, hits);
-}
+int fsea_oscfar_hits_host(fsea_oscfar *c, uint32_t *hits) { return fsea_detail::detector_hits_host(c, "oscfar", hits); }
 
 }  // extern "C"

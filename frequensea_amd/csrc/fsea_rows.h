@@ -3,7 +3,8 @@
 // the row arguments with the one text each has, the 16-byte-load predicate, the packing of host rows into the staging and
 // the walk over its chunks, the zeroed accumulator of persist's counts and cfar's hits, and the two pieces of device code
 // that the kernels have in common.  The group loaders of the three kernels are not here: their shapes differ for the
-// reasons each file's head gives.
+// reasons each file's head gives.  What only the two CFAR detectors share (fsea_cfar.hip and fsea_oscfar.hip: the object, its
+// launch, the entry points, the kernels' geometry and signature) is in fsea_cfar_shared.h, on top of this header.
 //
 // Everything has internal linkage: the libraries export what they did before this header.
 #pragma once

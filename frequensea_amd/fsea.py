@@ -918,40 +918,46 @@ def cfar_bands(hits, rows, min_fraction, max_gap=0, min_width=1):
     return out
 
 
-class Cfar(_RowsHandle):
-    """A CFAR detector across frequency on one device: which cells of a dB row stand above the mean level of their
-    neighbours, and hits[column] over all the rows offered; thin wrapper over fsea_cfar_*.  add() takes a 2-D uint8 or
-    float32 array from the host (any row stride) and returns what was asked for; add_device() takes resident rows."""
-    _kind = "cfar"
-
-    def set(self, guard=2, train=16, offset=60, method=CFAR_CA):
-        _check(self._L.fsea_cfar_set(self._p, int(guard), int(train), int(offset), int(method)))
+class _Detector(_RowsHandle):
+    """What Cfar and OsCfar have in common, fsea_<kind>_add_host, _add_device and _hits_host: add() takes a 2-D uint8 or
+    float32 array from the host (any row stride) and returns what was asked for; add_device() takes resident rows; hits()
+    fetches hits[column] over all the rows offered."""
 
     def add(self, rows, mask=False, row_hits=False):
         """None, the (n_rows, width) uint8 mask, the (n_rows,) uint32 row hits, or (mask, row_hits)."""
         a, pitch, type = self._host_rows(rows)
         m = np.empty(a.shape, dtype=np.uint8) if mask else None
         h = np.empty(a.shape[0], dtype=np.uint32) if row_hits else None
-        _check(self._L.fsea_cfar_add_host(self._p, a.ctypes.data, type, a.shape[0], pitch,
-                                          m.ctypes.data if mask else None, h.ctypes.data if row_hits else None))
+        _check(getattr(self._L, "fsea_%s_add_host" % self._kind)(self._p, a.ctypes.data, type, a.shape[0], pitch,
+                                                                 m.ctypes.data if mask else None, h.ctypes.data if row_hits else None))
         return (m, h) if mask and row_hits else m if mask else h
 
     def add_device(self, d_rows_ptr, type, n_rows, pitch=None, d_mask_ptr=None, d_row_hits_ptr=None, stream=0):
         """d_rows_ptr (an int, 16-byte aligned): n_rows rows of `width` elements, `pitch` elements apart; d_mask_ptr
         (n_rows * width bytes) and d_row_hits_ptr (n_rows uint32) are optional; asynchronous."""
-        _check(self._L.fsea_cfar_add_device(self._p, d_rows_ptr, int(type), n_rows, self.width if pitch is None else pitch,
-                                            d_mask_ptr or None, d_row_hits_ptr or None, stream or None))
+        _check(getattr(self._L, "fsea_%s_add_device" % self._kind)(
+            self._p, d_rows_ptr, int(type), n_rows, self.width if pitch is None else pitch, d_mask_ptr or None,
+            d_row_hits_ptr or None, stream or None))
 
     def hits(self):
         out = np.empty(self.width, dtype=np.uint32)
-        _check(self._L.fsea_cfar_hits_host(self._p, out.ctypes.data))
+        _check(getattr(self._L, "fsea_%s_hits_host" % self._kind)(self._p, out.ctypes.data))
         return out
 
 
-class OsCfar(_RowsHandle):
+class Cfar(_Detector):
+    """A CFAR detector across frequency on one device: which cells of a dB row stand above the mean level of their
+    neighbours, and hits[column] over all the rows offered; thin wrapper over fsea_cfar_*."""
+    _kind = "cfar"
+
+    def set(self, guard=2, train=16, offset=60, method=CFAR_CA):
+        _check(self._L.fsea_cfar_set(self._p, int(guard), int(train), int(offset), int(method)))
+
+
+class OsCfar(_Detector):
     """An ordered-statistic CFAR detector across frequency on one device: which cells of a dB row stand above the rank-th
     smallest level of their training cells -- the weaker of two close emissions keeps its hit -- and hits[column] over all
-    the rows offered; thin wrapper over fsea_oscfar_*.  add(), add_device() and hits() are Cfar's; cfar_bands() takes the hits."""
+    the rows offered; thin wrapper over fsea_oscfar_*.  cfar_bands() takes the hits."""
     _kind = "oscfar"
 
     def set(self, guard=2, train=16, offset=60, rank=24):
@@ -960,26 +966,6 @@ class OsCfar(_RowsHandle):
     @property
     def rank(self):
         return self._L.fsea_oscfar_rank(self._p)
-
-    def add(self, rows, mask=False, row_hits=False):
-        """None, the (n_rows, width) uint8 mask, the (n_rows,) uint32 row hits, or (mask, row_hits)."""
-        a, pitch, type = self._host_rows(rows)
-        m = np.empty(a.shape, dtype=np.uint8) if mask else None
-        h = np.empty(a.shape[0], dtype=np.uint32) if row_hits else None
-        _check(self._L.fsea_oscfar_add_host(self._p, a.ctypes.data, type, a.shape[0], pitch,
-                                            m.ctypes.data if mask else None, h.ctypes.data if row_hits else None))
-        return (m, h) if mask and row_hits else m if mask else h
-
-    def add_device(self, d_rows_ptr, type, n_rows, pitch=None, d_mask_ptr=None, d_row_hits_ptr=None, stream=0):
-        """d_rows_ptr (an int, 16-byte aligned): n_rows rows of `width` elements, `pitch` elements apart; d_mask_ptr
-        (n_rows * width bytes) and d_row_hits_ptr (n_rows uint32) are optional; asynchronous."""
-        _check(self._L.fsea_oscfar_add_device(self._p, d_rows_ptr, int(type), n_rows, self.width if pitch is None else pitch,
-                                              d_mask_ptr or None, d_row_hits_ptr or None, stream or None))
-
-    def hits(self):
-        out = np.empty(self.width, dtype=np.uint32)
-        _check(self._L.fsea_oscfar_hits_host(self._p, out.ctypes.data))
-        return out
 
 
 class Events(_RowsHandle):

@@ -14,8 +14,6 @@ Usage: python scripts/cfar_rate.py [run] [--to FILE]"""
 import os
 import sys
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea  # noqa: E402
@@ -30,9 +28,7 @@ STEP_LIMIT_S = 120      # the whole part took 13.0 s of wall time on an MI355X
 
 def traffic_bytes(guard, train):
     """(read, written) of one add with mask: per row, every tile's segment clipped at the row's ends; the mask."""
-    halo, tile = guard + train, fsea.CFAR_TILE_COLUMNS
-    per_row = sum(min(N, c0 + tile + halo) - max(0, c0 - halo) for c0 in range(0, N, tile))
-    return FRAMES * per_row, FRAMES * N
+    return ratelib.detector_traffic(N, FRAMES, fsea.CFAR_TILE_COLUMNS, guard + train)
 
 
 def run():
@@ -44,13 +40,8 @@ def run():
         print(text, flush=True)
 
     torch.cuda.init()
-    raw = np.random.default_rng(1).integers(0, 256, 2 * N * FRAMES, dtype=np.uint8)
-    d_in = fsea.DeviceBuffer(raw.nbytes).upload(raw)
-    d_rows = fsea.DeviceBuffer(FRAMES * N)
+    plan, d_in, d_rows = ratelib.db5_rows(fsea, N, FRAMES)
     d_mask = fsea.DeviceBuffer(FRAMES * N)
-    plan = fsea.Plan(N, N, fsea.MODE_DB5_U8_DCFIX)
-    plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True)
-    plan.synchronize()
     say("%d rows x %d columns of DB5 rows resident; fsea_cfar_add_device with a mask, median of %d calls after %d"
         % (FRAMES, N, REPS, WARMUP))
     pt, pmin = ratelib.median_min(ratelib.per_call(lambda: plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True),

@@ -21,8 +21,6 @@ Usage: python scripts/oscfar_rate.py [run | counters small|wide] [--to FILE]"""
 import os
 import sys
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from frequensea_amd import fsea  # noqa: E402
@@ -42,18 +40,11 @@ STEP_LIMIT_S = 180
 
 def traffic_bytes(guard, train):
     """(read, written) of one add with mask: per row, every tile's staged cells clipped at the row's ends; the mask."""
-    halo, tile = (guard + train + 15) // 16 * 16, fsea.OSCFAR_TILE_COLUMNS
-    per_row = sum(min(N, c0 + tile + halo) - max(0, c0 - halo) for c0 in range(0, N, tile))
-    return FRAMES * per_row, FRAMES * N
+    return ratelib.detector_traffic(N, FRAMES, fsea.OSCFAR_TILE_COLUMNS, (guard + train + 15) // 16 * 16)
 
 
 def resident_rows():
-    raw = np.random.default_rng(1).integers(0, 256, 2 * N * FRAMES, dtype=np.uint8)
-    d_in = fsea.DeviceBuffer(raw.nbytes).upload(raw)
-    d_rows = fsea.DeviceBuffer(FRAMES * N)
-    plan = fsea.Plan(N, N, fsea.MODE_DB5_U8_DCFIX)
-    plan.exec_device(d_in.ptr.value, FRAMES, d_rows.ptr.value, flip=True)
-    plan.synchronize()
+    plan, d_in, d_rows = ratelib.db5_rows(fsea, N, FRAMES)
     plan.close()
     d_in.free()
     return d_rows

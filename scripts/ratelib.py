@@ -1,5 +1,5 @@
-"""What the scripts/*_rate.py share: four ways to time a call, the kernel-trace reader, the part runner and the seeded
-recording.  A script keeps its constants, its set-up, the bound it computes and its print lines; how a number is taken is
+"""What the scripts/*_rate.py share: four ways to time a call, the kernel-trace reader, the part runner, the seeded
+recording and, for the two detectors' scripts, the resident rows and the traffic count.  A script keeps its constants, its set-up, the bound it computes and its print lines; how a number is taken is
 here, once.
 
 Timing, all in seconds, each returning the list of its samples (the caller reduces: np.median, min, best of):
@@ -154,3 +154,24 @@ def run_parts(script, parts, argv, to=None, header=""):
 def recording(n_samples, seed=1):
     """n_samples of 8-bit IQ, two bytes each, uniform random from a seeded generator."""
     return np.random.default_rng(seed).integers(0, 256, 2 * n_samples, dtype=np.uint8)
+
+
+def db5_rows(fsea, n, frames):
+    """What the detectors' scripts measure on: the DB5 rows of `frames` frames of size n of the seeded recording, produced
+    by the plan and left on the device.  Returns (plan, input buffer, rows buffer); the caller closes and frees them.
+    `fsea` is the caller's frequensea_amd.fsea: this module imports no library."""
+    raw = recording(n * frames)
+    d_in = fsea.DeviceBuffer(raw.nbytes).upload(raw)
+    d_rows = fsea.DeviceBuffer(frames * n)
+    plan = fsea.Plan(n, n, fsea.MODE_DB5_U8_DCFIX)
+    plan.exec_device(d_in.ptr.value, frames, d_rows.ptr.value, flip=True)
+    plan.synchronize()
+    return plan, d_in, d_rows
+
+
+def detector_traffic(n, frames, tile, halo):
+    """(bytes read, bytes written) of one detector add with mask on `frames` u8 rows of n cells: per row, every tile of
+    `tile` columns with `halo` cells more each side, clipped at the row's ends; the mask.  How a kernel rounds its halo is
+    the caller's."""
+    per_row = sum(min(n, c0 + tile + halo) - max(0, c0 - halo) for c0 in range(0, n, tile))
+    return frames * per_row, frames * n

@@ -2,7 +2,9 @@
 
 The table is a record of the library BEFORE fsea_persist, fsea_cfar and fsea_events got their shared checks
 (csrc/fsea_rows.h): run this against a libfsea_hip.so built from that commit's csrc/, never to bless what a changed check
-says.  From the repository root:  python -m tests.golden.make_row_messages
+says.  The fsea_oscfar_* entries are a record of commit 510f74d, the last one before fsea_cfar and fsea_oscfar got their
+shared scaffold (csrc/fsea_cfar_shared.h); they were added with that commit's csrc/ built, and the other entries came out
+byte for byte as they were.  From the repository root:  python -m tests.golden.make_row_messages
 """
 import json
 

@@ -1,8 +1,10 @@
-"""CPU tier: the argument checks of fsea_persist_*, fsea_cfar_* and fsea_events_* that run before any device work, each
-with its error code and the whole text of fsea_last_error_string(), against tests/golden/row_messages.json.  The table was
-recorded (tests/golden/make_row_messages.py) from the library as it was before the three objects got their shared checks
-(csrc/fsea_rows.h), so it pins what a caller saw then: the codes, the texts and, through the cases that break two rules
-at once, the order of the checks.  The substring asserts of test_persist_host.py, test_cfar_host.py and
+"""CPU tier: the argument checks of fsea_persist_*, fsea_cfar_*, fsea_oscfar_* and fsea_events_* that run before any device
+work, each with its error code and the whole text of fsea_last_error_string(), against tests/golden/row_messages.json.  The
+table was recorded (tests/golden/make_row_messages.py) from the library as it was before the three objects got their shared
+checks (csrc/fsea_rows.h), so it pins what a caller saw then: the codes, the texts and, through the cases that break two
+rules at once, the order of the checks.  The fsea_oscfar_* entries were recorded from commit 510f74d, which added that
+detector as a copy of fsea_cfar's host side: the last one before the two detectors got their shared scaffold
+(csrc/fsea_cfar_shared.h).  The substring asserts of test_persist_host.py, test_cfar_host.py, test_oscfar_host.py and
 test_events_host.py stay; this is the byte-for-byte layer under them."""
 import ctypes
 import json
@@ -152,6 +154,33 @@ CASES = (
        ("fsea_cfar_bands: gap -1", "fsea_cfar_bands", (P, 64, 1, 0.5, -1, 1, P, 4, N)),
        ("fsea_cfar_bands: min_width 0", "fsea_cfar_bands", (P, 64, 1, 0.5, 0, 0, P, 4, N)),
        ("fsea_cfar_bands: no rows", "fsea_cfar_bands", (P, 64, 0, 0.5, 0, 1, None, 0, N))]
+    # the ordered-statistic CFAR detector
+    + [("fsea_oscfar_create: %s" % label, "fsea_oscfar_create", args) for label, args in (
+        ("NULL out", (None, 64, 0)), ("width 0", ("OUT", 0, 0)), ("width above the maximum", ("OUT", (1 << 20) + 1, 0)),
+        ("width -1 before the device", ("OUT", -1, 99)))]
+    + _both("fsea_oscfar_add", (("_device", (None, None, None)), ("_host", (None, None))), _ADD)
+    + [("fsea_oscfar_add_device: rows off 16 bytes", "fsea_oscfar_add_device", (F, OFF, 0, 1, 64, None, None, None)),
+       ("fsea_oscfar_add_device: mask off 16 bytes", "fsea_oscfar_add_device", (F, P, 0, 1, 64, OFF, None, None)),
+       ("fsea_oscfar_add_device: row hits off 16 bytes", "fsea_oscfar_add_device", (F, P, 1, 1, 64, P, OFF, None)),
+       ("fsea_oscfar_add_device: pitch before alignment", "fsea_oscfar_add_device", (F, OFF, 0, 1, 63, None, None, None)),
+       ("fsea_oscfar_add_device: alignment before rows past 2^32 - 1", "fsea_oscfar_add_device", (FULL, P, 0, 2, 64, OFF, None, None)),
+       ("fsea_oscfar_add_device: no rows, off 16 bytes", "fsea_oscfar_add_device", (F, OFF, 0, 0, 64, OFF, OFF, None)),
+       ("fsea_oscfar_reset: NULL object", "fsea_oscfar_reset", (None,)),
+       ("fsea_oscfar_destroy: NULL object", "fsea_oscfar_destroy", (None,)),
+       ("fsea_oscfar_set: NULL object", "fsea_oscfar_set", (None, 2, 16, 60, 24)),
+       ("fsea_oscfar_set: guard -1", "fsea_oscfar_set", (F, -1, 16, 60, 24)),
+       ("fsea_oscfar_set: guard 65 before train", "fsea_oscfar_set", (F, 65, 0, 60, 24)),
+       ("fsea_oscfar_set: train 0", "fsea_oscfar_set", (F, 2, 0, 60, 24)),
+       ("fsea_oscfar_set: train 257", "fsea_oscfar_set", (F, 2, 257, 60, 24)),
+       ("fsea_oscfar_set: train 0 before rank", "fsea_oscfar_set", (F, 2, 0, 60, 0)),
+       ("fsea_oscfar_set: offset above", "fsea_oscfar_set", (F, 2, 16, (1 << 20) + 1, 24)),
+       ("fsea_oscfar_set: offset below", "fsea_oscfar_set", (F, 2, 16, -(1 << 20) - 1, 24)),
+       ("fsea_oscfar_set: offset before rank", "fsea_oscfar_set", (F, 2, 16, (1 << 20) + 1, 33)),
+       ("fsea_oscfar_set: rank 0", "fsea_oscfar_set", (F, 2, 16, 60, 0)),
+       ("fsea_oscfar_set: rank 2 * train + 1", "fsea_oscfar_set", (F, 2, 16, 60, 33)),
+       ("fsea_oscfar_set: fine", "fsea_oscfar_set", (F, 0, 1, -5, 2)),
+       ("fsea_oscfar_hits_host: NULL object", "fsea_oscfar_hits_host", (None, P)),
+       ("fsea_oscfar_hits_host: NULL hits", "fsea_oscfar_hits_host", (F, None))]
     # spectrum events
     + [("fsea_events_create: %s" % label, "fsea_events_create", args) for label, args in (
         ("NULL out", (None, 64, 0)), ("width 0", ("OUT", 0, 0)), ("width above the maximum", ("OUT", (1 << 20) + 1, 0)),
@@ -216,7 +245,7 @@ def table():
 def test_the_table_is_the_cases(table):
     assert sorted(table) == sorted(IDS)
     # every entry point that takes rows, device and host form, sees each of the shared checks' texts
-    for name in ("fsea_persist_add", "fsea_cfar_add", "fsea_events_runs", "fsea_events_paint"):
+    for name in ("fsea_persist_add", "fsea_cfar_add", "fsea_oscfar_add", "fsea_events_runs", "fsea_events_paint"):
         for form in ("_device", "_host"):
             texts = " | ".join(t for k, (_, t) in table.items() if k.startswith(name + form + ":") and t)
             for part in ("is NULL", "is more than 2^31", "NULL buffer for the", "is below the width 64", "is too large"):
