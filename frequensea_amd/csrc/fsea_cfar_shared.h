@@ -1,5 +1,8 @@
-// fsea_cfar_shared.h -- what the two CFAR detectors share: fsea_cfar (fsea_cfar.hip, cell averaging on prefix sums) and
-// fsea_oscfar (fsea_oscfar.hip, a rank of the training cells).  Included by those two files only.  On the device: the
+// fsea_cfar_shared.h -- what the two CFAR detectors across frequency share: fsea_cfar (fsea_cfar.hip, cell averaging on
+// prefix sums) and fsea_oscfar (fsea_oscfar.hip, a rank of the training cells).  A third user, fsea_tcfar (fsea_tcfar.hip,
+// cell averaging down the time axis), takes level_at, spread4 and the entry points that need nothing but the object's head
+// -- create, reset, the checks of set, hits_host -- and has a geometry, a kernel signature, an object and adds of its own
+// (context rows, a fifth setting).  Included by those three files only.  On the device: the
 // geometry of a workgroup, the level of a cell, the spreading of mask bits into bytes, the wave-local fence and the
 // kernels' one signature.  On the host: the object, its one launch and the entry points that differ in nothing but the
 // object's name and the kernels.  What is not here differs for the reasons each file's head gives: the group loaders, the

@@ -4,7 +4,8 @@
 // the walk over its chunks, the zeroed accumulator of persist's counts and cfar's hits, and the two pieces of device code
 // that the kernels have in common.  The group loaders of the three kernels are not here: their shapes differ for the
 // reasons each file's head gives.  What only the two CFAR detectors share (fsea_cfar.hip and fsea_oscfar.hip: the object, its
-// launch, the entry points, the kernels' geometry and signature) is in fsea_cfar_shared.h, on top of this header.
+// launch, the entry points, the kernels' geometry and signature) is in fsea_cfar_shared.h, on top of this header; the
+// detector down the time axis (fsea_tcfar.hip) takes its part of both.
 //
 // Everything has internal linkage: the libraries export what they did before this header.
 #pragma once

@@ -44,6 +44,9 @@ CFAR_U8, CFAR_F32 = 0, 1                # FSEA_CFAR_*: element type of a row
 CFAR_CA, CFAR_GO, CFAR_SO = 0, 1, 2     # FSEA_CFAR_*: method
 OSCFAR_TILE_COLUMNS = 1024  # FSEA_OSCFAR_TILE_COLUMNS: columns per workgroup of fsea_oscfar_u8 / fsea_oscfar_f32
 OSCFAR_RUN_ROWS = 64        # FSEA_OSCFAR_RUN_ROWS: rows per workgroup
+TCFAR_TILE_COLUMNS = 1024   # FSEA_TCFAR_TILE_COLUMNS: columns per workgroup of fsea_tcfar_u8 / fsea_tcfar_f32
+TCFAR_RUN_ROWS = 32         # FSEA_TCFAR_RUN_ROWS: rows a workgroup decides
+TCFAR_MASK_SET, TCFAR_MASK_OR, TCFAR_MASK_AND = 0, 1, 2   # FSEA_TCFAR_MASK_*: what an add does with the mask already there
 CFAR_BAND = np.dtype([("first", "<i4"), ("last", "<i4"), ("peak", "<i4"), ("peak_hits", "<u4"), ("hits_sum", "<u8")])   # fsea_cfar_band
 EVENTS_MAX_WIDTH = 1 << 20      # FSEA_EVENTS_MAX_WIDTH
 EVENTS_MAX_GAP_COLS = 64        # FSEA_EVENTS_MAX_GAP_COLS
@@ -250,6 +253,16 @@ API = {
     "fsea_oscfar_add_device": (_ci, [_vp, _vp, _ci, _sz, _sz, _vp, _vp, _vp]),
     "fsea_oscfar_add_host": (_ci, [_vp, _vp, _ci, _sz, _sz, _vp, _vp]),
     "fsea_oscfar_hits_host": (_ci, [_vp, _vp]),
+    "fsea_tcfar_create": (_ci, [_out, _ci, _ci]),
+    "fsea_tcfar_destroy": (_ci, [_vp]),
+    "fsea_tcfar_reset": (_ci, [_vp]),
+    "fsea_tcfar_set": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci]),
+    "fsea_tcfar_width": (_ci, [_vp]),
+    "fsea_tcfar_rows": (_u64, [_vp]),
+    "fsea_tcfar_run_rows": (_ci, [_vp]),
+    "fsea_tcfar_add_device": (_ci, [_vp, _vp, _ci, _sz, _sz, _sz, _sz, _vp, _vp, _vp]),
+    "fsea_tcfar_add_host": (_ci, [_vp, _vp, _ci, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "fsea_tcfar_hits_host": (_ci, [_vp, _vp]),
     "fsea_events_create": (_ci, [_out, _ci, _ci]),
     "fsea_events_destroy": (_ci, [_vp]),
     "fsea_events_reset": (_ci, [_vp]),
@@ -832,7 +845,7 @@ def _rows_2d(a, dtypes, what):
 
 
 class _RowsHandle(_ResettableHandle):
-    """What consumes rows of `width` levels (Persist, Cfar, OsCfar, Events): the width and the rows offered so far."""
+    """What consumes rows of `width` levels (Persist, Cfar, OsCfar, Tcfar, Events): the width and the rows offered so far."""
 
     def __init__(self, width, device=0):
         self.device = device
@@ -919,7 +932,8 @@ def cfar_bands(hits, rows, min_fraction, max_gap=0, min_width=1):
 
 
 class _Detector(_RowsHandle):
-    """What Cfar and OsCfar have in common, fsea_<kind>_add_host, _add_device and _hits_host: add() takes a 2-D uint8 or
+    """What Cfar and OsCfar have in common, fsea_<kind>_add_host, _add_device and _hits_host (Tcfar keeps hits() and has
+    adds of its own, with context rows): add() takes a 2-D uint8 or
     float32 array from the host (any row stride) and returns what was asked for; add_device() takes resident rows; hits()
     fetches hits[column] over all the rows offered."""
 
@@ -966,6 +980,47 @@ class OsCfar(_Detector):
     @property
     def rank(self):
         return self._L.fsea_oscfar_rank(self._p)
+
+
+class Tcfar(_Detector):
+    """A CFAR detector down the time axis on one device: which cells stand above the mean level of the cells of their own
+    column in the rows before and after them -- a burst wider than any frequency window -- and hits[column] over all the
+    rows decided; thin wrapper over fsea_tcfar_*.  cfar_bands() takes the hits."""
+    _kind = "tcfar"
+
+    def set(self, guard=2, train=16, offset=60, method=CFAR_CA, mask_op=TCFAR_MASK_SET):
+        _check(self._L.fsea_tcfar_set(self._p, int(guard), int(train), int(offset), int(method), int(mask_op)))
+
+    @property
+    def run_rows(self):
+        """The rows a workgroup decides under the current settings: where the seams of a call lie."""
+        return self._L.fsea_tcfar_run_rows(self._p)
+
+    def add(self, rows, before=0, after=0, mask=False, row_hits=False):
+        """`rows` is the whole array, context included: its first `before` and last `after` rows are context, the rows
+        between are decided.  `mask`: True for a new (n_rows, width) uint8 mask, or a C-contiguous uint8 array of that
+        shape, which TCFAR_MASK_OR and TCFAR_MASK_AND combine with and every operation writes.  Returns None, the mask,
+        the (n_rows,) uint32 row hits, or (mask, row_hits)."""
+        a, pitch, type = self._host_rows(rows)
+        n = a.shape[0] - int(before) - int(after)
+        if before < 0 or after < 0 or n < 0:
+            raise ValueError("before and after are row counts within the array")
+        want_mask = mask is not False and mask is not None
+        m = np.empty((n, a.shape[1]), dtype=np.uint8) if mask is True else mask if want_mask else None
+        if want_mask and (not isinstance(m, np.ndarray) or m.dtype != np.uint8 or m.shape != (n, a.shape[1])
+                          or not m.flags.c_contiguous or not m.flags.writeable):
+            raise ValueError("mask is True or a writeable C-contiguous uint8 array of shape (n_rows, width)")
+        h = np.empty(n, dtype=np.uint32) if row_hits else None
+        _check(self._L.fsea_tcfar_add_host(self._p, a.ctypes.data + int(before) * pitch * a.itemsize, type, n, pitch, int(before),
+                                           int(after), m.ctypes.data if want_mask else None, h.ctypes.data if row_hits else None))
+        return (m, h) if want_mask and row_hits else m if want_mask else h
+
+    def add_device(self, d_rows_ptr, type, n_rows, pitch=None, before=0, after=0, d_mask_ptr=None, d_row_hits_ptr=None, stream=0):
+        """d_rows_ptr (an int, 16-byte aligned): the first of n_rows decided rows of `width` elements, `pitch` elements
+        apart, `before` context rows in front of it and `after` behind the last; d_mask_ptr (n_rows * width bytes, read
+        as well under TCFAR_MASK_OR and TCFAR_MASK_AND) and d_row_hits_ptr (n_rows uint32) are optional; asynchronous."""
+        _check(self._L.fsea_tcfar_add_device(self._p, d_rows_ptr, int(type), n_rows, self.width if pitch is None else pitch,
+                                             int(before), int(after), d_mask_ptr or None, d_row_hits_ptr or None, stream or None))
 
 
 class Events(_RowsHandle):

@@ -4,7 +4,8 @@
  *
  * Pass 1 is fsea-events' for a recording: every frame of N samples (one every H) through a plan in a dB mode, the rows to a
  * fsea_cfar object with a mask, mask and rows to a fsea_events object, all on the device chunk by chunk; the runs are kept
- * on the host and linked once at the end (tool_common.h).  Pass 2 turns the first --max-events surviving events into jobs with
+ * on the host and linked once at the end (tool_common.h); --axis time|either: fsea-events', the detector down the time axis
+ * alone or OR-ed into that mask.  Pass 2 turns the first --max-events surviving events into jobs with
  * fsea_extract_jobs (include/fsea.h): a job begins fsea_extract_lead samples in front of its box, so that the filter has run
  * in where the box begins, and ends with the last frame of the box; a job longer than --max-samples is cut short.  The jobs
  * are grouped into batches whose samples total at most 64 MiB; the byte ranges of a batch are read from the file into one
@@ -35,8 +36,9 @@
 
 static const char *USAGE =
     "usage: fsea-cutouts FILE --size N --decimation D --out DIR [--hop H] [--window NAME] [--flip] [--mode db5|db10|db]\n"
-    "                    [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--rank R] [--gap-cols B]\n"
-    "                    [--gap-rows R] [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--taps L] [--cutoff HZ]\n"
+    "                    [--guard G] [--train T] [--offset LEVELS] [--method ca|go|so] [--rank R] [--axis freq|time|either]\n"
+    "                    [--gap-cols B] [--gap-rows R] [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ]\n"
+    "                    [--taps L] [--cutoff HZ]\n"
     "                    [--fill F] [--max-events E] [--max-samples S] [--measures [--lag K]]\n"
     "                    [--audio fm|am [--audio-rate HZ] [--audio-taps N] [--audio-cutoff HZ] [--deviation HZ]]\n"
     "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8).  The emissions are found as fsea-events finds them (its\n"
@@ -320,7 +322,9 @@ int main(int argc, char **argv) {
 
     /* pass 1: fsea-events' */
     tool_row_source src;
+    tool_detector_check_chunk(TOOL, &o.det, size, hop, o.type);
     tool_rows_open(&src, TOOL, o.path, size, hop, o.mode, o.window, o.flip);
+    tool_rows_keep(&src, tool_detector_keep(&o.det, size, o.type));
     tool_detector_object detector = tool_detector_create(TOOL, &o.det, size);
     fsea_events *events = NULL;
     if (fsea_events_create(&events, size, 0) != FSEA_OK) die("fsea_events_create");

@@ -12,11 +12,12 @@
  * and one line per event: row_first row_last col_first col_last hits peak peak_row peak_col.  With --rate and --freq the three
  * columns follow as MHz by fsea-occupancy's formula, column k of N being FREQ + (k - N / 2) * RATE / N; for a recording the
  * three rows then follow as seconds, row r beginning r * H / RATE into it.  --paint OUT.png writes the runs of the surviving
- * events, closed gaps included, as a mask of one row per frame: 255 inside, 0 elsewhere.
+ * events, closed gaps included, as a mask of one row per frame: 255 inside, 0 elsewhere.  --axis time and --axis either are
+ * fsea-occupancy's: the detector down the time axis (fsea_tcfar), alone or OR-ed into the frequency detector's mask.
  *
  * usage: fsea-events FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db] [--guard G] [--train T]
- *                    [--offset LEVELS] [--method ca|go|so | --rank R] [--gap-cols B] [--gap-rows R] [--min-rows R] [--min-cols B]
- *                    [--min-hits K] [--rate HZ --freq MHZ] [--paint OUT.png]
+ *                    [--offset LEVELS] [--method ca|go|so | --rank R] [--axis freq|time|either] [--gap-cols B] [--gap-rows R]
+ *                    [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--paint OUT.png]
  *        fsea-events --image IN.png [the detector's and the events' options]
  */
 #include <limits.h>
@@ -30,19 +31,20 @@
 
 static const char *USAGE =
     "usage: fsea-events FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db] [--guard G] [--train T]\n"
-    "                   [--offset LEVELS] [--method ca|go|so] [--rank R] [--gap-cols B] [--gap-rows R] [--min-rows R]\n"
-    "                   [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--paint OUT.png]\n"
+    "                   [--offset LEVELS] [--method ca|go|so] [--rank R] [--axis freq|time|either] [--gap-cols B]\n"
+    "                   [--gap-rows R] [--min-rows R] [--min-cols B] [--min-hits K] [--rate HZ --freq MHZ] [--paint OUT.png]\n"
     "       fsea-events --image IN.png [--guard G] ... [--paint OUT.png]\n"
     "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8); every frame of N samples, one every H, becomes a dB row on the\n"
     "  GPU and fsea-occupancy's CFAR detector (--guard, --train, --offset, --method; --mode db: f32 dB rows, LEVELS in 1/64 dB;\n"
-    "  --rank R in place of --method: its ordered-statistic detector, the R-th smallest of the 2 T bins in place of their mean)\n"
+    "  --rank R in place of --method: its ordered-statistic detector, the R-th smallest of the 2 T bins in place of their mean;\n"
+    "  --axis time: a bin against the same bin of the T frames before and after it; --axis either: both, OR-ed)\n"
     "  marks the bins that hold a signal; --image IN.png scans the rows of an 8-bit grey PNG instead.  Detections of a row\n"
     "  with at most --gap-cols free bins between them are a run; runs at most --gap-rows free rows apart that overlap, give\n"
     "  or take --gap-cols bins, belong to one event.  Events lower than --min-rows rows, narrower than --min-cols bins or of\n"
     "  fewer than --min-hits detections are dropped.  Prints `rows R runs N events E` and per event\n"
     "  `row_first row_last col_first col_last hits peak peak_row peak_col`, with --rate and --freq also the columns as MHz\n"
     "  and, for a recording, the rows as seconds; --paint OUT.png writes the surviving events as a mask\n"
-    "  defaults: --hop N --window rect --mode db5 --guard 2 --train 16 --offset 60 --method ca --gap-cols 0 --gap-rows 0\n"
+    "  defaults: --hop N --window rect --mode db5 --guard 2 --train 16 --offset 60 --method ca --axis freq --gap-cols 0 --gap-rows 0\n"
     "  --min-rows 1 --min-cols 1 --min-hits 1";
 
 static void usage_error(const char *msg) { tool_usage_error("fsea-events", msg); }
@@ -91,7 +93,7 @@ int main(int argc, char **argv) {
     int mode = 0, type = 0;
     if (!tool_rows_mode(mode_name, "db", &mode, &type)) usage_error("--mode must be db5, db10 or db");
 
-    tool_detector_object detector = {NULL, NULL};
+    tool_detector_object detector = {NULL, NULL, NULL};
     fsea_events *events = NULL;
     tool_run_list list = {NULL, 0, 0};   /* all runs of the input, in order */
     int width = size;
@@ -116,7 +118,9 @@ int main(int argc, char **argv) {
         free(image);
     } else {
         tool_row_source src;
+        tool_detector_check_chunk("fsea-events", &det, size, hop, type);
         tool_rows_open(&src, "fsea-events", path, size, hop, mode, window, flip);
+        tool_rows_keep(&src, tool_detector_keep(&det, size, type));
         detector = tool_detector_create("fsea-events", &det, size);
         if (fsea_events_create(&events, size, 0) != FSEA_OK) die("fsea_events_create");
         if (fsea_events_set_gap(events, gap_cols) != FSEA_OK) die("fsea_events_set_gap");

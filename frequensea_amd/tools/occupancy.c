@@ -8,11 +8,13 @@
  * example.  It prints the rows decided and one line per band of occupied columns: first last peak duty, the duty being the
  * share of the rows in which the band's peak column was detected; with --rate and --freq the three columns follow as MHz:
  * column k of N is FREQ + (k - N / 2) * RATE / N, the plan's rows having the centre frequency in column N / 2.  --mask OUT.png
- * writes the detections, one row per frame, 255 for a hit; --bands FILE writes the band lines.
+ * writes the detections, one row per frame, 255 for a hit; --bands FILE writes the band lines.  --axis time puts the
+ * detector's question down each column instead (fsea_tcfar: a bin against the same bin in the frames before and after it,
+ * --guard and --train counted in frames), --axis either detects across frequency as given and ORs the time axis in.
  *
  * usage: fsea-occupancy FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db] [--guard G] [--train T]
- *                       [--offset LEVELS] [--method ca|go|so | --rank R] [--min-duty F] [--max-gap B] [--min-width B]
- *                       [--rate HZ --freq MHZ] [--mask OUT.png] [--bands FILE]
+ *                       [--offset LEVELS] [--method ca|go|so | --rank R] [--axis freq|time|either] [--min-duty F] [--max-gap B]
+ *                       [--min-width B] [--rate HZ --freq MHZ] [--mask OUT.png] [--bands FILE]
  *        fsea-occupancy --image IN.png [the detector's and the bands' options]
  */
 #include <math.h>
@@ -26,18 +28,20 @@
 
 static const char *USAGE =
     "usage: fsea-occupancy FILE --size N [--hop H] [--window NAME] [--flip] [--mode db5|db10|db] [--guard G] [--train T]\n"
-    "                      [--offset LEVELS] [--method ca|go|so] [--rank R] [--min-duty F] [--max-gap B] [--min-width B]\n"
-    "                      [--rate HZ --freq MHZ] [--mask OUT.png] [--bands FILE]\n"
+    "                      [--offset LEVELS] [--method ca|go|so] [--rank R] [--axis freq|time|either] [--min-duty F]\n"
+    "                      [--max-gap B] [--min-width B] [--rate HZ --freq MHZ] [--mask OUT.png] [--bands FILE]\n"
     "       fsea-occupancy --image IN.png [--guard G] ... [--bands FILE]\n"
     "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8); every frame of N samples, one every H, becomes a dB row on the\n"
     "  GPU and a CFAR detector compares each bin with the mean level of T bins on either side, G guard bins left out:\n"
     "  a bin is detected when its level is more than LEVELS above that mean (--mode db: f32 dB rows, LEVELS in 1/64 dB);\n"
     "  --method go asks that of each side (steps do not fire), so of either side; --rank R, in place of --method, compares\n"
     "  with the R-th smallest of the 2 T bins (R in [1, 2 T]; 24 of 32: the weaker of two close signals keeps its bins)\n"
-    "  in place of the mean; --image IN.png scans the rows of an 8-bit\n"
+    "  in place of the mean; --axis time compares a bin with the same bin of the T frames before and after it instead, G\n"
+    "  frames left out (a burst wider than any window; not with --rank), --axis either detects across frequency as given\n"
+    "  and adds what --axis time finds with the same G, T, LEVELS and method; --image IN.png scans the rows of an 8-bit\n"
     "  grey PNG instead; a bin detected in at least F of the rows is occupied, bands bridge up to --max-gap free bins and are\n"
     "  at least --min-width wide; prints `rows R` and `first last peak duty` per band, with --rate and --freq also as MHz\n"
-    "  defaults: --hop N --window rect --mode db5 --guard 2 --train 16 --offset 60 --method ca --min-duty 0.5 --max-gap 0\n"
+    "  defaults: --hop N --window rect --mode db5 --guard 2 --train 16 --offset 60 --method ca --axis freq --min-duty 0.5 --max-gap 0\n"
     "  --min-width 1";
 
 static void usage_error(const char *msg) { tool_usage_error("fsea-occupancy", msg); }
@@ -94,13 +98,14 @@ int main(int argc, char **argv) {
     int mode = 0, type = 0;
     if (!tool_rows_mode(mode_name, "db", &mode, &type)) usage_error("--mode must be db5, db10 or db");
 
-    tool_detector_object detector = {NULL, NULL};
+    tool_detector_object detector = {NULL, NULL, NULL};
     uint8_t *mask = NULL;          /* rows x width, grown chunk by chunk; only with --mask */
+    const int with_mask = mask_path != NULL || det.axis == TOOL_AXIS_EITHER;   /* either: the second detector reads the first's */
     int width = size;
     if (image_path != NULL) {
         int height = 0;
         uint8_t *image = tool_detector_image("fsea-occupancy", &det, &width, &height, &detector);
-        if (mask_path != NULL) {
+        if (with_mask) {
             mask = (uint8_t *)malloc((size_t)width * (size_t)height + 1);
             if (mask == NULL) usage_error("out of memory");
         }
@@ -108,15 +113,18 @@ int main(int argc, char **argv) {
         free(image);
     } else {
         tool_row_source src;
+        tool_detector_check_chunk("fsea-occupancy", &det, size, hop, type);
         tool_rows_open(&src, "fsea-occupancy", path, size, hop, mode, window, flip);
+        tool_rows_keep(&src, tool_detector_keep(&det, size, type));
         detector = tool_detector_create("fsea-occupancy", &det, size);
         const size_t n = (size_t)size;
         void *d_mask = NULL;
-        if (mask_path != NULL && fsea_device_alloc(0, src.frames_max * n, &d_mask) != FSEA_OK) die("fsea_device_alloc");
+        if (with_mask && fsea_device_alloc(0, src.frames_max * n, &d_mask) != FSEA_OK) die("fsea_device_alloc");
         /* the rows stay on the device between the plan and the object */
         size_t done = 0;
-        for (size_t frames; (frames = tool_rows_next(&src)) > 0; done += frames) {
-            tool_detector_add_device("fsea-occupancy", &detector, src.d_rows, type, frames, n, (uint8_t *)d_mask);
+        for (size_t chunk, frames = 0; (chunk = tool_rows_next(&src)) > 0; done += frames) {
+            tool_detector_add_chunk("fsea-occupancy", &detector, &src, chunk, type, (uint8_t *)d_mask);
+            frames = src.hi - src.lo;          /* the chunk's own rows */
             if (mask_path != NULL) {
                 uint8_t *grown = (uint8_t *)realloc(mask, (done + frames) * n);
                 if (grown == NULL) usage_error("out of memory");

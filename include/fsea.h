@@ -35,6 +35,7 @@
  *   fsea_persist_*        a persistence spectrum (no counterpart in the reference): per-bin level histograms of resident rows
  *   fsea_cfar_*           a CFAR detector across frequency (no counterpart in the reference): occupied bins, bands and masks
  *   fsea_oscfar_*         an ordered-statistic CFAR detector (no counterpart in the reference): the weaker of two close emissions
+ *   fsea_tcfar_*          a CFAR detector down the time axis (no counterpart in the reference): bursts wider than a window
  *   fsea_events_*         spectrum events (no counterpart in the reference): a detection mask as runs, time-frequency boxes
  *   fsea_extract_*        event cut-outs (no counterpart in the reference): each box of fsea_events_link as decimated IQ
  *   fsea_measure_*        signal measures (no counterpart in the reference): power, offset, width and envelope of each cut-out
@@ -74,6 +75,7 @@ typedef struct fsea_pfb fsea_pfb;
 typedef struct fsea_persist fsea_persist;
 typedef struct fsea_cfar fsea_cfar;
 typedef struct fsea_oscfar fsea_oscfar;
+typedef struct fsea_tcfar fsea_tcfar;
 typedef struct fsea_events fsea_events;
 typedef struct fsea_extract fsea_extract;
 typedef struct fsea_demod fsea_demod;
@@ -754,6 +756,68 @@ int fsea_oscfar_add_device(fsea_oscfar *oscfar, const void *d_rows, int type, si
 int fsea_oscfar_add_host(fsea_oscfar *oscfar, const void *rows, int type, size_t n_rows, size_t pitch, uint8_t *mask,
                          uint32_t *row_hits);
 int fsea_oscfar_hits_host(fsea_oscfar *oscfar, uint32_t *hits);
+
+/* The time-axis CFAR detector: fsea_cfar's question put down each column.  fsea_cfar and fsea_oscfar compare a cell with its
+ * neighbours in the same row, so a cell inside a flat-topped emission wider than the window sees only the emission and gets no
+ * hit: 64 u8 rows of 256 cells at level 100, a burst of 160 on rows 30 .. 35 and columns 40 .. 199, a carrier of 200 on column
+ * 220, G = 2, T = 16, offset 20, CA: fsea_cfar hits the burst's two edges (columns 40 .. 47 and 192 .. 199) and the carrier in
+ * all 64 rows; fsea_tcfar hits all 960 cells of the burst and no cell of the carrier.  Here a cell is compared with the cells
+ * of the same column in the rows before and after it.  The object is fsea_cfar's in every other respect: it owns hits[k],
+ * width uint32_t, zero after create and reset; `rows`, the rows decided so far; and the settings (guard G, train T, offset,
+ * method, mask operation), (2, 16, 60, FSEA_CFAR_CA, FSEA_TCFAR_MASK_SET) after create.  Integer and order-free.  It carries no
+ * state from call to call other than hits and rows.
+ *   level:  of an element: fsea_cfar's, above (FSEA_CFAR_U8 and FSEA_CFAR_F32).
+ *   rows:   of a call.  A call decides n_rows rows; d_rows points at the first decided row.  rows_before further rows lie in
+ *           memory in front of it, at the same pitch, and rows_after rows behind the last decided row: the context.  The rows
+ *           of the call are numbered -rows_before .. n_rows + rows_after - 1.
+ *   windows: of cell (r, k).  Earlier training cells: rows r-G-T .. r-G-1 of column k; later training cells: rows r+G+1 ..
+ *           r+G+T; each side clipped to the rows of the call, no wrap-around; nL, nR are the counts of cells and SL, SR the
+ *           sums of levels.  G and T are counted in rows.  Context beyond G + T rows on a side is never read.
+ *   decision: fsea_cfar's ok(n, S) and its three methods with nL, SL, nR, SR as above, in 32-bit integers (|S| <= 256 * 2^20).
+ *           In time, GO holds at a level step (a retune); SO finds the onset and the end of a long emission.
+ *           In one sentence: the mask of a call is fsea_cfar's mask of the transposed block of rows_before + n_rows +
+ *           rows_after rows, transposed back, rows 0 .. n_rows - 1 kept.
+ *   cuts:   a recording decided in any number of calls gives the same bits as one call over all of it when every call gets
+ *           min(G + T, the rows that exist) rows of context on each side.
+ *   mask operation: FSEA_TCFAR_MASK_SET: the mask byte becomes 255 for a hit and 0 otherwise.  FSEA_TCFAR_MASK_OR and
+ *           FSEA_TCFAR_MASK_AND combine the decision with what d_mask already holds, any non-zero byte counting as set; the
+ *           result is written as 255 or 0.  hits, d_row_hits and the mask all describe the written value.  fsea_cfar or
+ *           fsea_oscfar writes a mask, then fsea_tcfar with OR gives "either axis" and with AND "stands out on both".
+ *   set:    checks guard, train, offset (fsea_cfar's ranges), method, mask operation in this order.
+ *   run_rows: the rows a workgroup of the add kernels decides under the current settings, FSEA_TCFAR_RUN_ROWS whatever they
+ *           are (0 for NULL): where the seams of a call lie.
+ *   add, hits_host: fsea_cfar_add_* and fsea_cfar_hits_host with the context rows: pitch and sub-bands, the tight d_mask of
+ *           n_rows * width bytes (optional under SET, read and written under OR and AND), the optional d_row_hits (set, not
+ *           added to), hits[k] += and rows += n_rows with the 2^32 - 1 guard, the n_rows == 0 no-op, the alignment of the
+ *           device form's three pointers, the order of calls on different streams, the 16-byte and element-wise reads and
+ *           mask accesses.  add_host: `rows` points at the first decided row of the caller's array, the context rows around
+ *           it; the rows go up in chunks, each with its context rows and, where the operation reads it, its mask, so the
+ *           host form equals the device form bit for bit.  A row so long that 2 (G + T) + 1 packed rows do not fit the
+ *           staging of 64 MiB is refused: use add_device.
+ *           Kernels fsea_tcfar_u8 / fsea_tcfar_f32: a workgroup of one wave takes a tile of FSEA_TCFAR_TILE_COLUMNS columns
+ *           over a run of FSEA_TCFAR_RUN_ROWS rows; a lane keeps the window sums of its 16 columns in registers and moves
+ *           them on with five row reads per row, the cost per cell independent of T.
+ *   bands:  fsea_cfar_bands on the fetched hits.
+ * Every check runs before any device work, in this order: FSEA_EINVAL for a NULL object, an unknown type, n_rows > 2^31, a
+ * NULL input buffer, pitch < width, (rows_before + n_rows + rows_after) x pitch above 2^40, a misaligned device pointer, OR or
+ * AND without a mask, rows past 2^32 - 1.  Create: FSEA_ENODEVICE without a GPU.  width, rows and run_rows return 0 for NULL.
+ * Destroy and reset wait for the device; reset zeroes hits and rows and keeps the settings.  Calls on one object from several
+ * threads are serialised. */
+#define FSEA_TCFAR_TILE_COLUMNS 1024    /* columns of a workgroup of the add kernels */
+#define FSEA_TCFAR_RUN_ROWS 32          /* rows a workgroup of the add kernels decides before it adds its column hits to hits */
+enum { FSEA_TCFAR_MASK_SET = 0, FSEA_TCFAR_MASK_OR = 1, FSEA_TCFAR_MASK_AND = 2 };   /* mask operation */
+int fsea_tcfar_create(fsea_tcfar **tcfar, int width, int device);
+int fsea_tcfar_destroy(fsea_tcfar *tcfar);
+int fsea_tcfar_reset(fsea_tcfar *tcfar);
+int fsea_tcfar_set(fsea_tcfar *tcfar, int guard, int train, int offset, int method, int mask_op);
+int fsea_tcfar_width(const fsea_tcfar *tcfar);
+uint64_t fsea_tcfar_rows(const fsea_tcfar *tcfar);
+int fsea_tcfar_run_rows(const fsea_tcfar *tcfar);
+int fsea_tcfar_add_device(fsea_tcfar *tcfar, const void *d_rows, int type, size_t n_rows, size_t pitch, size_t rows_before,
+                          size_t rows_after, uint8_t *d_mask, uint32_t *d_row_hits, void *stream);
+int fsea_tcfar_add_host(fsea_tcfar *tcfar, const void *rows, int type, size_t n_rows, size_t pitch, size_t rows_before,
+                        size_t rows_after, uint8_t *mask, uint32_t *row_hits);
+int fsea_tcfar_hits_host(fsea_tcfar *tcfar, uint32_t *hits);
 
 /* Spectrum events: which emissions a detection mask holds -- this burst, from row 812 to row 860, columns 3011 .. 3042, peak
  * 171 at (830, 3027).  A device pass reduces a resident mask (fsea_cfar's, n_rows x width bytes) and optionally the level rows
