@@ -1,9 +1,9 @@
 // fsea_jobs.h -- what the objects that run a table of jobs over one resident buffer share: fsea_extract (fsea_extract.hip),
-// fsea_measure (fsea_measure.hip) and fsea_audio (fsea_audio.hip).  The look-up of a workgroup's job on the device; the
+// fsea_measure (fsea_measure.hip), fsea_audio (fsea_audio.hip) and fsea_spectra (fsea_spectra.hip).  The look-up of a workgroup's job on the device; the
 // table's way from the caller to the device (JobTable: records and first-tile column built in mapped host memory by the
 // one routine `build`, copied by the one kernel fsea_jobs_upload, ordered by two events); the checks of a job table with
-// the one text each has, the placement of the outputs among them; and, for the two objects that place their outputs
-// (extract, audio), the layout and the host form that hands back only the jobs' own ranges.  What a job is, what a kernel
+// the one text each has, the placement of the outputs among them; and, for the three objects that place their outputs
+// (extract, audio, spectra), the layout and the host form that hands back only the jobs' own ranges.  What a job is, what a kernel
 // does with it and what lies behind the table in the scratch are each file's own.  Everything has internal linkage but
 // jobs_upload, whose body stands beside its kernel in fsea_api.hip: the library is built without relocatable device code,
 // so a kernel has one translation unit.
@@ -75,7 +75,7 @@ struct JobTable {
     // returns its elements, in tiles of `tile`; fill is called exactly once for each r, in ascending order (extract's walks
     // its jobs alongside and skips those without output); the column of first tiles behind the records (an entry without
     // a tile has its successor's).  First the previous call's upload has read the host table; then the fill, the scratch, the upload.
-    // behind_per_tile: bytes an object keeps behind the table for every tile, from a 64-byte boundary (measure's partials).
+    // behind_per_tile: bytes an object keeps behind the table for every tile, from a 64-byte boundary (measure's and spectra's partials).
     template <class Rec, class Fill>
     int build(size_t n, unsigned tile, size_t behind_per_tile, hipStream_t s, Fill &&fill, Built<Rec> *built) {
         const size_t bytes = n * (sizeof(Rec) + sizeof(uint32_t)), behind_at = (bytes + 63) & ~(size_t)63;   // <= 65536 * 33 words
@@ -108,7 +108,7 @@ int check_jobs_count(size_t n_jobs) {
     return FSEA_OK;
 }
 
-// object (`name`: "extract", "measure" or "audio"), count, table and the two buffers of a run; no jobs: a no-op, nothing more is looked at
+// object (`name`: "extract", "measure", "audio" or "spectra"), count, table and the two buffers of a run; no jobs: a no-op, nothing more is looked at
 int check_jobs_head(const void *obj, const char *name, size_t n_jobs, const void *jobs, const void *in, const void *out) {
     if (!obj) return fail(FSEA_EINVAL, "%s is NULL", name);
     if (int rc = check_jobs_count(n_jobs)) return rc;
@@ -129,7 +129,7 @@ int check_job_span(size_t i, uint64_t first, uint64_t n, size_t n_buffer, uint64
     return FSEA_OK;
 }
 
-// the elements of one call; `elems`: "outputs" or "pairs"
+// the elements of one call; `elems`: "outputs", "pairs" or "points"
 int check_jobs_total(uint64_t total, const char *elems) {
     if (total > (uint64_t)1 << 31) return fail(FSEA_EINVAL, "%llu %s in one call: more than 2^31", (unsigned long long)total, elems);
     return FSEA_OK;

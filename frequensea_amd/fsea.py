@@ -66,6 +66,12 @@ AUDIO_FM, AUDIO_AM = 0, 1       # FSEA_AUDIO_*: kind
 AUDIO_MAX_DECIMATION = 64       # FSEA_AUDIO_MAX_DECIMATION
 AUDIO_MAX_JOBS = 65536          # FSEA_AUDIO_MAX_JOBS
 AUDIO_MAX_PAIRS = 1 << 24       # FSEA_AUDIO_MAX_PAIRS, per job
+SPECTRA_Z, SPECTRA_ENVELOPE, SPECTRA_SQUARE, SPECTRA_FOURTH = 0, 1, 2, 3   # FSEA_SPECTRA_*: kind
+SPECTRA_KINDS = {"z": 0, "env": 1, "sq": 2, "fourth": 3}
+SPECTRA_MIN_N, SPECTRA_MAX_N = 64, 4096   # FSEA_SPECTRA_MIN_N, FSEA_SPECTRA_MAX_N
+SPECTRA_TILE_SEGMENTS = 32      # FSEA_SPECTRA_TILE_SEGMENTS: segments per workgroup of fsea_spectra_tiles_<n>
+SPECTRA_MAX_JOBS = 65536        # FSEA_SPECTRA_MAX_JOBS
+SPECTRA_MAX_PAIRS = 1 << 24     # FSEA_SPECTRA_MAX_PAIRS, per job
 IQ_MAX_MULTIPLIER = 16      # FSEA_IQ_MAX_MULTIPLIER
 DEMOD_RAW, DEMOD_WBFM = 0, 1        # FSEA_DEMOD_* (= nrf_demodulate_type)
 DEMOD_MAX_CHANNELS = 256            # FSEA_DEMOD_MAX_CHANNELS
@@ -122,6 +128,18 @@ class MeasureResult(ctypes.Structure):
 class AudioJob(ctypes.Structure):
     """fsea_audio_job (include/fsea.h): a span of a resident buffer of pairs and the place of its audio."""
     _fields_ = [("first_pair", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64), ("out_first", ctypes.c_uint64)]
+
+
+class SpectraJob(ctypes.Structure):
+    """fsea_spectra_job (include/fsea.h): a span of a resident buffer of pairs and the place of its n powers."""
+    _fields_ = [("first_pair", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64), ("out_first", ctypes.c_uint64)]
+
+
+class SpectraResult(ctypes.Structure):
+    """fsea_spectra_result (include/fsea.h): what fsea_spectra_finish makes of one row of powers."""
+    _fields_ = [("total", ctypes.c_double), ("centroid_cycles", ctypes.c_double), ("obw_centre_cycles", ctypes.c_double),
+                ("peak_power", ctypes.c_double), ("peak_cycles", ctypes.c_double), ("floor", ctypes.c_double), ("line_db", ctypes.c_double),
+                ("obw_lo", ctypes.c_int32), ("obw_hi", ctypes.c_int32), ("obw_bins", ctypes.c_int32), ("peak_bin", ctypes.c_int32)]
 
 
 class CaptureRun(ctypes.Structure):
@@ -298,6 +316,17 @@ API = {
     "fsea_audio_layout": (_ci, [_vp, _vp, _sz, _szp]),
     "fsea_audio_run_device": (_ci, [_vp, _vp, _sz, _vp, _sz, _f64, _f64, _f64, _vp, _sz, _vp]),
     "fsea_audio_run_host": (_ci, [_vp, _vp, _sz, _vp, _sz, _f64, _f64, _f64, _vp, _sz]),
+    "fsea_spectra_create": (_ci, [_out, _ci, _ci, _ci, _vp, _ci]),
+    "fsea_spectra_destroy": (_ci, [_vp]),
+    "fsea_spectra_n": (_ci, [_vp]),
+    "fsea_spectra_hop": (_ci, [_vp]),
+    "fsea_spectra_kind": (_ci, [_vp]),
+    "fsea_spectra_segments": (_sz, [_vp, _sz]),
+    "fsea_spectra_layout": (_ci, [_vp, _vp, _sz, _szp]),
+    "fsea_spectra_run_device": (_ci, [_vp, _vp, _sz, _vp, _sz, _f64, _f64, _vp, _sz, _vp]),
+    "fsea_spectra_run_host": (_ci, [_vp, _vp, _sz, _vp, _sz, _f64, _f64, _vp, _sz]),
+    "fsea_spectra_jobs": (_ci, [_vp, _sz, _ci, _sz, _vp]),
+    "fsea_spectra_finish": (_ci, [_vp, _ci, _ci, _f64, _vp]),
     "fsea_iq_draw_create": (_ci, [_out, _ci]),
     "fsea_iq_draw_destroy": (_ci, [_vp]),
     "fsea_iq_points_device": (_ci, [_vp, _vp, _ci, _ci, _sz, _ci, _vp, _vp]),
@@ -1261,6 +1290,67 @@ class Audio(_Handle):
         offset = complex(offset)
         _check(self._L.fsea_audio_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, _address(table), len(table), offset.real,
                                              offset.imag, float(gain), d_audio_ptr or None, n_audio, stream or None))
+
+
+def spectra_jobs(extract_jobs_laid_out, decimation, skip_pairs=0):
+    """fsea_spectra_jobs (host arithmetic): the spans of the outputs of extract jobs that Extract.layout laid out, each
+    without its first skip_pairs pairs, as a ctypes array of SpectraJob (out_first 0: Spectra.layout places them)."""
+    table = _table_of(ExtractJob, extract_jobs_laid_out)
+    jobs = (SpectraJob * len(table))()
+    _check(hip_lib().fsea_spectra_jobs(_address(table), len(table), int(decimation), int(skip_pairs), _address(jobs)))
+    return jobs
+
+
+def spectra_finish(power, guard_bins=0, fraction=0.99):
+    """fsea_spectra_finish (host arithmetic, no GPU needed): one row of n float32 powers to a SpectraResult."""
+    p = np.ascontiguousarray(power, dtype=np.float32).ravel()
+    result = SpectraResult()
+    _check(hip_lib().fsea_spectra_finish(p.ctypes.data, p.size, int(guard_bins), float(fraction), ctypes.byref(result)))
+    return result
+
+
+class Spectra(_Handle):
+    """Cut-out spectra on one device: a table of spans of one buffer of complex64 in, every span's averaged periodogram of n
+    bins out -- of the span itself (kind "z"), of |z|^2 ("env"), z^2 ("sq") or z^4 ("fourth") -- in two launches, stateless;
+    thin wrapper over fsea_spectra_*.  run() takes the pairs and the jobs from the host and returns one float32 array per
+    job (empty for a span shorter than n); run_device() works on resident memory with the jobs' own out_first."""
+    _kind = "spectra"
+
+    def __init__(self, n, hop=None, kind="z", window=None, device=0):
+        self.n, self.hop, self.device = int(n), int(n) // 2 if hop is None else int(hop), device
+        self.kind = SPECTRA_KINDS.get(kind, kind)
+        w = None if window is None else np.ascontiguousarray(window, dtype=np.float32).ravel()
+        if w is not None and w.size != self.n:
+            raise FseaError("the window must have n weights")
+        self._create("fsea_spectra_create", self.n, self.hop, self.kind, w.ctypes.data if w is not None else None, device)
+
+    def segments(self, n_pairs):
+        return self._L.fsea_spectra_segments(self._p, n_pairs)
+
+    def layout(self, jobs):
+        """fsea_spectra_layout: (the jobs as a ctypes array with out_first filled in, the floats they need in all)."""
+        table = _table_of(SpectraJob, jobs)
+        total = ctypes.c_size_t()
+        _check(self._L.fsea_spectra_layout(self._p, _address(table), len(table), ctypes.byref(total)))
+        return table, total.value
+
+    def run(self, pairs, jobs, offset=0j):
+        """The host form on a copy of the jobs laid out with layout(): a list of float32 arrays, one per job."""
+        z = np.ascontiguousarray(pairs, dtype=np.complex64).ravel()
+        table, total = self.layout([SpectraJob.from_buffer_copy(j) for j in jobs])
+        power = np.zeros(max(total, 1), dtype=np.float32)
+        offset = complex(offset)
+        _check(self._L.fsea_spectra_run_host(self._p, z.ctypes.data, z.size, _address(table), len(table), offset.real, offset.imag,
+                                             power.ctypes.data, total))
+        return [power[j.out_first:j.out_first + (self.n if self.segments(j.n_pairs) else 0)].copy() for j in table]
+
+    def run_device(self, d_pairs_ptr, n_buffer_pairs, jobs, d_power_ptr, n_power, offset=0j, stream=0):
+        """Device pointers (ints): n_buffer_pairs complex64 in (8-byte aligned), n_power float32 out (4-byte aligned), every
+        job with a segment at its own out_first; asynchronous.  The jobs are read before the call returns."""
+        table = _table_of(SpectraJob, jobs)
+        offset = complex(offset)
+        _check(self._L.fsea_spectra_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, _address(table), len(table), offset.real,
+                                               offset.imag, d_power_ptr or None, n_power, stream or None))
 
 
 class Demod(_ResettableHandle):

@@ -19,7 +19,8 @@
  * output behind the run-in.  The tool prints
  *     rows R runs N events E cutouts C skipped S
  *
- * --measures and --audio fm|am: the two stages below, each on a batch's pairs while they are resident.  The options: USAGE.
+ * --measures, --audio fm|am and --spectra N: the three stages below, each on a batch's pairs while they are resident.  The
+ * options: USAGE.
  */
 #include <errno.h>
 #include <stdio.h>
@@ -41,6 +42,8 @@ static const char *USAGE =
     "                    [--taps L] [--cutoff HZ]\n"
     "                    [--fill F] [--max-events E] [--max-samples S] [--measures [--lag K]]\n"
     "                    [--audio fm|am [--audio-rate HZ] [--audio-taps N] [--audio-cutoff HZ] [--deviation HZ]]\n"
+    "                    [--spectra N [--spectra-hop H] [--spectra-kind z|env|sq|fourth] [--spectra-window NAME]\n"
+    "                     [--spectra-guard G] [--spectra-fraction F]]\n"
     "  FILE is a raw 8-bit IQ recording (--flip: HackRF int8).  The emissions are found as fsea-events finds them (its\n"
     "  options, same defaults); each one whose columns times D fill at most F of the N columns is mixed to the centre,\n"
     "  low-passed (L taps, half amplitude at --cutoff, default 0.4 RATE / D) and decimated by D on the GPU, all of a batch in\n"
@@ -50,7 +53,13 @@ static const char *USAGE =
     "  --audio: every cut-out written is FM- or AM-demodulated on the GPU, low-passed (N taps, half amplitude at\n"
     "  --audio-cutoff, default 0.4 of the audio rate) and decimated to about --audio-rate; DIR/cutout-NNNNN.wav is mono 16-bit\n"
     "  PCM, full scale at --deviation for FM, and DIR/audio.txt lists number, rate, samples and peak of every file.  Needs --rate.\n"
-    "  Prints `rows R runs N events E cutouts C skipped S`, with --audio followed by ` audio A`\n"
+    "  --spectra: the averaged periodogram of every cut-out written, N bins (a power of two in [64, 4096]) every H pairs\n"
+    "  (default N / 2) under the taper NAME (--window's names, default hann), on the GPU: of the cut-out itself (z), of its\n"
+    "  envelope |z|^2 (env: a line at the symbol rate), of z^2 (sq: a line at twice a BPSK carrier's offset) or of z^4\n"
+    "  (fourth: four times a QPSK carrier's).  DIR/spectra.txt lists number, segments, the bandwidth that holds F of the\n"
+    "  power (default 0.99), the centroid and the strongest line outside G bins round the centre (default 0 for z, 2\n"
+    "  otherwise; -1: none) -- in Hz with --rate, in cycles per pair without -- and the line's height over the median in dB.\n"
+    "  Prints `rows R runs N events E cutouts C skipped S`, with --audio followed by ` audio A`, with --spectra by ` spectra P`\n"
     "  defaults: --taps 97 --fill 0.8 --max-events 1024 --max-samples 16777216 --audio-rate 48000 --audio-taps 41 --deviation 75000";
 
 static void usage_error(const char *msg) { tool_usage_error(TOOL, msg); }
@@ -99,12 +108,14 @@ static void cannot_write(const char *name) {
 }
 
 typedef struct {
-    const char *path, *out_dir, *window, *mode_name, *audio_name;
+    const char *path, *out_dir, *window, *mode_name, *audio_name, *spectra_kind_name, *spectra_window;
     int size, hop, flip, gap_cols, gap_rows, decimation, n_taps, measures, lag, audio_taps;
+    int spectra, spectra_hop, spectra_guard, spectra_guard_given, spectra_sub; /* spectra 0: no --spectra; _sub: a --spectra-* was given */
     long long min_rows, min_cols, min_hits, max_events, max_samples;
-    double cutoff, fill, audio_rate, audio_cutoff, deviation;
+    double cutoff, fill, audio_rate, audio_cutoff, deviation, spectra_fraction;
     tool_detector det;
     int mode, type, audio_kind, audio_decimation; /* what the checks make of the names and rates; audio_kind -1: no --audio */
+    int spectra_kind, spectra_window_kind;
     char *name;                                   /* room for DIR/<any name of the output>, name_len bytes: main's, after the checks */
     size_t name_len;
 } options;
@@ -140,7 +151,20 @@ static void parse_options(int argc, char **argv, options *o) {
         else if (!strcmp(argv[i], "--audio-taps") && more) o->audio_taps = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--audio-cutoff") && more) o->audio_cutoff = atof(argv[++i]);
         else if (!strcmp(argv[i], "--deviation") && more) o->deviation = atof(argv[++i]);
-        else if (!strcmp(argv[i], "--out") && more) o->out_dir = argv[++i];
+        else if (!strcmp(argv[i], "--spectra") && more) o->spectra = atoi(argv[++i]);
+        else if (!strncmp(argv[i], "--spectra-", 10) && more) {
+            const char *sub = argv[i] + 10, *value = argv[++i];
+            o->spectra_sub = 1;
+            if (!strcmp(sub, "hop")) o->spectra_hop = atoi(value);
+            else if (!strcmp(sub, "kind")) o->spectra_kind_name = value;
+            else if (!strcmp(sub, "window")) o->spectra_window = value;
+            else if (!strcmp(sub, "guard")) {
+                o->spectra_guard = atoi(value);
+                o->spectra_guard_given = 1;
+            }
+            else if (!strcmp(sub, "fraction")) o->spectra_fraction = atof(value);
+            else usage_error(USAGE);
+        } else if (!strcmp(argv[i], "--out") && more) o->out_dir = argv[++i];
         else if (argv[i][0] != '-' && o->path == NULL) o->path = argv[i];
         else usage_error(USAGE);
     }
@@ -176,6 +200,27 @@ static void parse_options(int argc, char **argv, options *o) {
         if (o->audio_taps < 1 || o->audio_taps > FSEA_FIR_MAX_TAPS) usage_error("--audio-taps must be in [1, 512]");
         if (o->audio_cutoff < 0.0) usage_error("--audio-cutoff must be positive");
         if (!(o->deviation > 0.0)) usage_error("--deviation must be positive");
+    }
+    if (o->spectra != 0) {
+        const int n = o->spectra;
+        if (n < FSEA_SPECTRA_MIN_N || n > FSEA_SPECTRA_MAX_N || (n & (n - 1)) != 0) usage_error("--spectra must be a power of two in [64, 4096]");
+        if (o->spectra_hop == 0) o->spectra_hop = n / 2;
+        if (o->spectra_hop < 1 || o->spectra_hop > n) usage_error("--spectra-hop must be in [1, N]");
+        const char *kinds[] = {"z", "env", "sq", "fourth"};
+        o->spectra_kind = -1;
+        for (int k = 0; k < 4; k++) {
+            if (!strcmp(o->spectra_kind_name, kinds[k])) o->spectra_kind = k;
+        }
+        if (o->spectra_kind < 0) usage_error("--spectra-kind must be z, env, sq or fourth");
+        o->spectra_window_kind = tool_window_kind(o->spectra_window);
+        if (o->spectra_window_kind == TOOL_WINDOW_UNKNOWN) {
+            usage_error("--spectra-window must be rect, hann, hamming, blackman, blackmanharris or flattop");
+        }
+        if (!o->spectra_guard_given) o->spectra_guard = o->spectra_kind == FSEA_SPECTRA_Z ? 0 : 2;
+        if (o->spectra_guard < -1 || o->spectra_guard > n / 2 - 1) usage_error("--spectra-guard must be in [-1, N / 2 - 1]");
+        if (!(o->spectra_fraction > 0.0 && o->spectra_fraction <= 1.0)) usage_error("--spectra-fraction must be in (0, 1]");
+    } else if (o->spectra_sub) {
+        usage_error("--spectra-hop, -kind, -window, -guard and -fraction need --spectra N");
     }
     if (o->out_dir == NULL) usage_error("--out DIR is required");
     if (!tool_rows_mode(o->mode_name, "db", &o->mode, &o->type)) usage_error("--mode must be db5, db10 or db");
@@ -312,10 +357,81 @@ static void audio_close(audio_stage *a, const options *o) {
     free(a->jobs);
 }
 
+/* --spectra N says what each cut-out looks like in frequency.  After a batch's fsea_extract_run_device (and the other stages),
+ * with the pairs still resident, one fsea_spectra_run_device (include/fsea.h) averages the periodograms of the spans the
+ * .cf32 files get: N bins every --spectra-hop pairs (default N / 2) under --spectra-window (default hann), of the kind
+ * --spectra-kind (default z); the same offset as the measures.  fsea_spectra_finish makes the figures of each row with
+ * --spectra-guard (default 0 for z, 2 otherwise) and --spectra-fraction (default 0.99).  DIR/spectra.txt gets one line per
+ * cut-out written:
+ *     number segments obw centroid line line_db
+ * obw, centroid and line as %.9e in Hz with --rate (obw_bins / N, centroid_cycles and peak_cycles times RATE / D), in
+ * cycles per pair without; a cut-out shorter than N pairs gets `number 0 short: P pairs, fewer than N`.  The summary line
+ * gains ` spectra P`, the cut-outs that have a spectrum.  Without --spectra nothing of this happens. */
+typedef struct {
+    fsea_spectra *object;
+    fsea_spectra_job *jobs; /* a batch's */
+    tool_grown power;       /* and their rows, on the device and on the host */
+    size_t n_rows;
+    FILE *list;             /* DIR/spectra.txt: main opens it once DIR is there */
+} spectra_stage;
+
+static void spectra_open(spectra_stage *s, const options *o, size_t n_jobs) {
+    float *w = (float *)malloc(sizeof(float) * (size_t)o->spectra);
+    s->jobs = (fsea_spectra_job *)malloc(sizeof(fsea_spectra_job) * (n_jobs + 1));
+    if (w == NULL || s->jobs == NULL) usage_error("out of memory");
+    if (fsea_window_fill(o->spectra_window_kind, o->spectra, w) != FSEA_OK) die("fsea_window_fill");
+    if (fsea_spectra_create(&s->object, o->spectra, o->spectra_hop, o->spectra_kind, o->spectra_window_kind == FSEA_WINDOW_RECT ? NULL : w,
+                            0) != FSEA_OK) {
+        die("fsea_spectra_create");
+    }
+    free(w);
+}
+
+/* every span's row back to back, averaged and brought to the host; then the line of every cut-out written */
+static void spectra_batch(spectra_stage *s, const batch *b, const options *o) {
+    size_t total = 0;
+    const double unit = o->det.rate > 0.0 ? o->det.rate / (double)o->decimation : 1.0;
+    for (size_t k = 0; k < b->n; k++) s->jobs[k] = (fsea_spectra_job){b->spans[k].first_pair, b->spans[k].n_pairs, 0};
+    if (fsea_spectra_layout(s->object, s->jobs, b->n, &total) != FSEA_OK) die("fsea_spectra_layout");
+    if (total != 0) {
+        tool_grown_need(TOOL, &s->power, total, sizeof(float), 1);
+        if (fsea_spectra_run_device(s->object, b->pairs.d, b->total, s->jobs, b->n, b->pedestal, b->pedestal, (float *)s->power.d, total,
+                                    NULL) != FSEA_OK) {
+            die("fsea_spectra_run_device");
+        }
+        if (fsea_copy_to_host(0, s->power.h, s->power.d, total * sizeof(float)) != FSEA_OK) die("fsea_copy_to_host");
+    }
+    for (size_t k = 0; k < b->n; k++) {
+        const size_t n_pairs = (size_t)s->jobs[k].n_pairs, segments = fsea_spectra_segments(s->object, n_pairs);
+        const unsigned e = (unsigned)b->event[k];
+        fsea_spectra_result r;
+        if (n_pairs == 0) continue; /* no cut-out is written */
+        if (segments == 0) {
+            fprintf(s->list, "%u 0 short: %zu pairs, fewer than %d\n", e, n_pairs, o->spectra);
+            continue;
+        }
+        if (fsea_spectra_finish((const float *)s->power.h + s->jobs[k].out_first, o->spectra, o->spectra_guard, o->spectra_fraction, &r) != FSEA_OK) {
+            die("fsea_spectra_finish");
+        }
+        fprintf(s->list, "%u %zu %.9e %.9e %.9e %.9e\n", e, segments, (double)r.obw_bins / (double)o->spectra * unit, r.centroid_cycles * unit,
+                r.peak_cycles * unit, r.line_db);
+        s->n_rows++;
+    }
+}
+
+static void spectra_close(spectra_stage *s, const options *o) {
+    snprintf(o->name, o->name_len, "%s/spectra.txt", o->out_dir);
+    if (fclose(s->list) != 0) cannot_write(o->name);
+    fsea_spectra_destroy(s->object);
+    tool_grown_free(&s->power);
+    free(s->jobs);
+}
+
 int main(int argc, char **argv) {
     options o = {.window = "rect", .mode_name = "db5", .n_taps = 97, .lag = 1, .audio_taps = 41, .min_rows = 1, .min_cols = 1,
                  .min_hits = 1, .max_events = 1024, .max_samples = 1ll << 24, .fill = 0.8, .audio_rate = 48000.0, .deviation = 75000.0,
-                 .det = TOOL_DETECTOR_DEFAULTS, .audio_kind = -1, .audio_decimation = 1};
+                 .det = TOOL_DETECTOR_DEFAULTS, .audio_kind = -1, .audio_decimation = 1, .spectra_kind_name = "z", .spectra_window = "hann",
+                 .spectra_fraction = 0.99};
     parse_options(argc, argv, &o);
     const int size = o.size, hop = o.hop, decimation = o.decimation, n_taps = o.n_taps;
     const double rate = o.det.rate, freq = o.det.freq;
@@ -363,7 +479,9 @@ int main(int argc, char **argv) {
     /* what can fail before anything is written: the stages' objects, audio's first, then DIR and audio's list in it */
     measure_stage measure = {0};
     audio_stage audio = {0};
+    spectra_stage spectra = {0};
     if (o.audio_kind >= 0) audio_open(&audio, &o, n_jobs);
+    if (o.spectra) spectra_open(&spectra, &o, n_jobs);
     if (o.measures) measure_open(&measure, n_jobs);
     if (mkdir(o.out_dir, 0777) != 0 && errno != EEXIST) {
         fprintf(stderr, TOOL ": cannot create directory %s\n", o.out_dir);
@@ -376,6 +494,8 @@ int main(int argc, char **argv) {
     if (o.name == NULL || b.jobs == NULL || b.event == NULL || b.spans == NULL) usage_error("out of memory");
     snprintf(o.name, o.name_len, "%s/audio.txt", o.out_dir);
     if (o.audio_kind >= 0 && (audio.list = fopen(o.name, "w")) == NULL) cannot_write(o.name);
+    snprintf(o.name, o.name_len, "%s/spectra.txt", o.out_dir);
+    if (o.spectra && (spectra.list = fopen(o.name, "w")) == NULL) cannot_write(o.name);
     for (int k = 0; k < n_taps; k++) b.pedestal += (double)(float)taps[k];
     b.pedestal *= 0.5; /* of the taps as the f32 values the extract holds */
     void *h_iq = NULL, *d_iq = NULL;
@@ -408,6 +528,7 @@ int main(int argc, char **argv) {
         if (fsea_extract_run_device(extract, d_iq, at, o.flip, b.jobs, b.n, b.pairs.d, b.total, NULL) != FSEA_OK) die("fsea_extract_run_device");
         if (o.measures) measure_batch(&measure, &b, o.lag);
         if (o.audio_kind >= 0) audio_batch(&audio, &b, &o);
+        if (o.spectra) spectra_batch(&spectra, &b, &o);
         if (fsea_copy_to_host(0, b.pairs.h, b.pairs.d, b.total * 2 * sizeof(float)) != FSEA_OK) die("fsea_copy_to_host");
         for (size_t k = 0; k < b.n; k++) {
             const size_t keep = (size_t)b.spans[k].n_pairs, e = b.event[k];
@@ -435,8 +556,10 @@ int main(int argc, char **argv) {
     if (fclose(list) != 0) cannot_write(o.name);
     if (o.measures) measure_close(&measure, &o, n_jobs, written);
     if (o.audio_kind >= 0) audio_close(&audio, &o);
+    if (o.spectra) spectra_close(&spectra, &o);
     printf("rows %zu runs %zu events %zu cutouts %zu skipped %zu", done, runs.n, n_events, n_cutouts, n_events - n_cutouts);
     if (o.audio_kind >= 0) printf(" audio %zu", audio.n_files);
+    if (o.spectra) printf(" spectra %zu", spectra.n_rows);
     putchar('\n');
 
     fsea_extract_destroy(extract);

@@ -58,18 +58,24 @@ static inline void tool_grown_need(const char *tool, tool_grown *g, size_t count
 /* --window NAME: the periodic cosine-sum taper of that name on the plan (include/fsea.h: fsea_window_fill; the position in
  * the table is the kind).  0, a failure of the library (or of malloc), or TOOL_WINDOW_UNKNOWN: the caller words that one. */
 #define TOOL_WINDOW_UNKNOWN (-2)
-static inline int tool_set_named_window(fsea_plan *plan, const char *name, int n) {
+/* the kind of a --window name (FSEA_WINDOW_*), or TOOL_WINDOW_UNKNOWN */
+static inline int tool_window_kind(const char *name) {
     static const char *names[] = {"rect", "hann", "hamming", "blackman", "blackmanharris", "flattop"};
     for (int k = 0; k < 6; k++) {
-        if (strcmp(name, names[k]) != 0) continue;
-        float *w = (float *)malloc(sizeof(float) * (size_t)n);
-        if (!w) return -1;
-        int rc = fsea_window_fill(k, n, w);
-        if (rc == 0 && k != 0) rc = fsea_plan_set_window(plan, w);
-        free(w);
-        return rc;
+        if (strcmp(name, names[k]) == 0) return k;
     }
     return TOOL_WINDOW_UNKNOWN;
+}
+
+static inline int tool_set_named_window(fsea_plan *plan, const char *name, int n) {
+    const int k = tool_window_kind(name);
+    if (k == TOOL_WINDOW_UNKNOWN) return k;
+    float *w = (float *)malloc(sizeof(float) * (size_t)n);
+    if (!w) return -1;
+    int rc = fsea_window_fill(k, n, w);
+    if (rc == 0 && k != 0) rc = fsea_plan_set_window(plan, w);
+    free(w);
+    return rc;
 }
 
 /* --mode NAME of the tools that give rows to an object: db5 and db10 are 8-bit rows; `f32_name` ("db"; NULL: the tool has

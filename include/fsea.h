@@ -1138,6 +1138,110 @@ int fsea_audio_run_device(fsea_audio *audio, const void *d_pairs, size_t n_buffe
 int fsea_audio_run_host(fsea_audio *audio, const float *pairs, size_t n_buffer_pairs, const fsea_audio_job *jobs, size_t n_jobs,
                         double offset_re, double offset_im, double gain, float *audio_out, size_t n_audio);
 
+/* Cut-out spectra: what each cut-out looks like in frequency -- the averaged periodogram of the cut-out itself, or of one of
+ * the three nonlinear forms that tell emissions apart: |z|^2, whose line sits at the symbol rate; z^2, whose line sits at
+ * twice the carrier offset for BPSK; z^4, the same at four times for QPSK.  fsea_plan transforms one contiguous buffer at one
+ * hop and writes a row per frame; an event list is hundreds of scattered spans of different lengths that each want one
+ * averaged row.  An fsea_spectra holds the transform size n (a power of two in [FSEA_SPECTRA_MIN_N, FSEA_SPECTRA_MAX_N]),
+ * the hop in [1, n], the kind and an optional taper w of n finite f32 weights (NULL: rectangular), takes a table of jobs
+ * over one resident buffer of f32 pairs and writes n f32 powers per job at power + out_first.  There is no state between
+ * calls and no reset.
+ *   terms:      for pair i of a job, z_i = pairs[first_pair + i] (rn = one IEEE rounding, round to nearest even; nothing is
+ *               contracted into an FMA):
+ *                 a_i = (float) rn((double)re_i - offset_re),   b_i = (float) rn((double)im_i - offset_im)
+ *               (the subtraction in f64, then the conversion's rounding); offset is the pedestal the caller knows,
+ *               (0.5 + 0.5j) sum(c) of the extract's taps, as for the measures.  From there on everything is f32.
+ *   kinds:      FSEA_SPECTRA_Z:        (u, v) = (a, b)
+ *               FSEA_SPECTRA_ENVELOPE: u = rn(rn(a a) + rn(b b)),  v = +0.0
+ *               FSEA_SPECTRA_SQUARE:   u = rn(rn(a a) - rn(b b)),  v = rn(2 rn(a b))
+ *               FSEA_SPECTRA_FOURTH:   SQUARE applied to SQUARE's (u, v)
+ *   segments:   S = n_pairs < n ? 0 : (n_pairs - n) / hop + 1 (rounded down).  Segment s covers pairs s hop .. s hop + n - 1
+ *               of the job; its input is x_j = (-1)^j (rn(w_j u), rn(w_j v)), j = 0 .. n - 1.  Without a taper there is no
+ *               multiplication; a taper of all 1.0f gives the bits of NULL.
+ *   transform:  X_s[k] = sum over j of x_j e^(-2 pi i j k / n) in f32: a radix-4 Stockham transform (a last radix-2 pass where
+ *               log2 n is odd) with twiddles rounded to f32 from f64; its roundings are the implementation's.  With the sign
+ *               (-1)^j bin k is the frequency (k - n / 2) / n cycles per pair: the cut-out's centre is bin n / 2, as
+ *               everywhere in this library.  p_s[k] = rn(rn(re^2) + rn(im^2)) in f32.
+ *   average:    the f32 p_s[k] are widened to f64 and added in segment order: a job's segments are cut into tiles of
+ *               FSEA_SPECTRA_TILE_SEGMENTS counted from the job's own segment 0; a tile's partial starts at +0.0 and adds
+ *               its segments ascending; a job's sum adds the tiles' partials ascending;
+ *                 power[out_first + k] = (float) rn(sum / (double)S).
+ *               Nothing in this depends on first_pair (at any parity), on the other jobs, on their order or on the launch
+ *               geometry: a job's n floats are the same bits alone or in a table of FSEA_SPECTRA_MAX_JOBS.  A NaN or an
+ *               infinity in one job's pairs shows in that job's output alone.
+ *   table:      jobs may overlap and may repeat in the input; their output ranges must not overlap and lie inside n_power.
+ *               A job with S = 0 (an empty one too) has no output, writes nothing and is legal.  Only the jobs' pairs are
+ *               read, only the jobs' outputs are written.  `jobs` is host memory, read before the call returns.
+ *   create:     FSEA_EINVAL, in this order, for a NULL out-pointer, an n that is not a power of two in [64, 4096], a hop
+ *               outside [1, n], an unknown kind, a window weight that is not finite; only then FSEA_ENODEVICE without a
+ *               GPU.  The window is copied.  n and hop return 0 for NULL, kind -1.  Destroy waits for the device.
+ *   segments:   S for a span of n_pairs; 0 for a NULL object.
+ *   layout:     fills out_first back to back in table order -- every job with S > 0 gets n floats, a job with S = 0 the
+ *               running position and none -- and gives the floats needed in *total_floats.  FSEA_EINVAL for a NULL object or
+ *               total_floats, n_jobs above FSEA_SPECTRA_MAX_JOBS, a NULL table with n_jobs > 0.
+ *   run_device: d_pairs (n_buffer_pairs pairs of floats) 8-byte aligned, d_power (n_power floats) 4-byte aligned;
+ *               asynchronous on `stream`.  The object owns the device copy of the table and the tiles' partials and grows
+ *               them as needed, so calls on several streams follow one another (an event).  Kernel fsea_spectra_tiles_<n>:
+ *               one workgroup per tile of one job, which it finds by a bisection over the jobs' first tiles; kernel
+ *               fsea_spectra_fold: the tiles' partials in order, the division, the store.
+ *   run_host:   the same from and to host memory through pinned staging on the object's own stream; returns when `power` is
+ *               complete; of `power` only the jobs' output ranges are written.
+ * Both check, before any device work and reading nothing of the object but n and hop, in this order: a NULL object; n_jobs
+ * above FSEA_SPECTRA_MAX_JOBS; n_jobs == 0 is then a successful no-op; a NULL job table; a NULL buffer (pairs or power); an
+ * offset that is not finite; per job in table order: first_pair + n_pairs past n_buffer_pairs, n_pairs above
+ * FSEA_SPECTRA_MAX_PAIRS, for a job with output out_first + n past n_power (each text names the job); two output ranges that
+ * overlap (the text names both jobs); more than 2^31 transformed points (the sum of S n) in the call; for run_device a
+ * d_pairs that is not 8-byte or a d_power that is not 4-byte aligned.  All FSEA_EINVAL; a refused call writes nothing.  Calls
+ * on one object from several threads are serialised.
+ *   jobs:       fsea_spectra_jobs, host arithmetic, no device: the twin of fsea_measure_jobs -- the spans of the outputs of
+ *               extract jobs that were laid out, without the first skip_pairs of each; out_first is set to 0
+ *               (fsea_spectra_layout places them).  The same refusals, the cap FSEA_SPECTRA_MAX_PAIRS.
+ *   finish:     fsea_spectra_finish, host arithmetic, callable in a process without a GPU: one row P of n powers to its
+ *               figures, all in f64, every sum over k ascending:
+ *                 total             = sum P[k]
+ *                 centroid_cycles   = sum (k - n/2) P[k] / total / n
+ *                 the occupied band at `fraction` (0.99, say): t = total (1 - fraction) / 2, c[k] the running sum;
+ *                 obw_lo            = the least k with c[k] > t;   obw_hi = the least k with c[k] >= total - t
+ *                 obw_bins          = obw_hi - obw_lo + 1;   obw_centre_cycles = ((obw_lo + obw_hi) / 2 - n/2) / n
+ *                 the strongest line, among the bins outside |k - n/2| <= guard_bins (guard_bins = -1 guards nothing):
+ *                 peak_bin          = the lowest k with the maximum;  peak_power = P[peak_bin];
+ *                 peak_cycles       = (peak_bin - n/2) / n
+ *                 floor             = the lower median of the same bins (element (m - 1) / 2 of the m, ascending)
+ *                 line_db           = 10 log10(peak_power / floor)
+ *               With total == 0 the ratios are NaN, there is no band (obw_lo = obw_hi = -1, obw_bins = 0, obw_centre_cycles
+ *               NaN) and the call still returns FSEA_OK; so with a NaN among the powers.  FSEA_EINVAL, in this order, for a
+ *               NULL pointer, an n that is not a power of two in [64, 4096], guard_bins outside [-1, n/2 - 1], fraction
+ *               outside (0, 1]. */
+#define FSEA_SPECTRA_Z        0
+#define FSEA_SPECTRA_ENVELOPE 1
+#define FSEA_SPECTRA_SQUARE   2
+#define FSEA_SPECTRA_FOURTH   3
+#define FSEA_SPECTRA_MIN_N    64
+#define FSEA_SPECTRA_MAX_N    4096
+#define FSEA_SPECTRA_TILE_SEGMENTS 32
+#define FSEA_SPECTRA_MAX_JOBS  65536        /* = FSEA_EXTRACT_MAX_JOBS */
+#define FSEA_SPECTRA_MAX_PAIRS (1u << 24)   /* per job */
+typedef struct { uint64_t first_pair, n_pairs, out_first; } fsea_spectra_job;   /* 24 bytes */
+typedef struct {                                                                 /* 72 bytes */
+    double total, centroid_cycles, obw_centre_cycles;
+    double peak_power, peak_cycles, floor, line_db;
+    int32_t obw_lo, obw_hi, obw_bins, peak_bin;
+} fsea_spectra_result;
+typedef struct fsea_spectra fsea_spectra;
+int fsea_spectra_create(fsea_spectra **spectra, int n, int hop, int kind, const float *window, int device);
+int fsea_spectra_destroy(fsea_spectra *spectra);
+int fsea_spectra_n(const fsea_spectra *spectra);
+int fsea_spectra_hop(const fsea_spectra *spectra);
+int fsea_spectra_kind(const fsea_spectra *spectra);
+size_t fsea_spectra_segments(const fsea_spectra *spectra, size_t n_pairs);
+int fsea_spectra_layout(const fsea_spectra *spectra, fsea_spectra_job *jobs, size_t n_jobs, size_t *total_floats);
+int fsea_spectra_run_device(fsea_spectra *spectra, const void *d_pairs, size_t n_buffer_pairs, const fsea_spectra_job *jobs,
+                            size_t n_jobs, double offset_re, double offset_im, float *d_power, size_t n_power, void *stream);
+int fsea_spectra_run_host(fsea_spectra *spectra, const float *pairs, size_t n_buffer_pairs, const fsea_spectra_job *jobs,
+                          size_t n_jobs, double offset_re, double offset_im, float *power, size_t n_power);
+int fsea_spectra_jobs(const fsea_extract_job *ejobs, size_t n_jobs, int decimation, size_t skip_pairs, fsea_spectra_job *jobs);
+int fsea_spectra_finish(const float *power, int n, int guard_bins, double fraction, fsea_spectra_result *result);
+
 /* The burst detector of the reference's signal scene (lua/signal-detector.lua:93-96): nrf_signal_detector_process
  * (src/nrf.c:883-898) on n_blocks consecutive blocks of block_bytes 8-bit samples behind one pointer.  With
  * x_i = byte_i / 256.0 and n = block_bytes the reference computes
