@@ -7,7 +7,7 @@
 // Kernel fsea_audio_tiles ("Cut-out audio"): one workgroup of AU_WG = 256 lanes per tile of T outputs of
 // one job; the grid is the sum of the jobs' tiles.  T is the object's: the largest count up to 256 whose T D + L - 1
 // discriminator values fit 4096 (audio_tile), as fsea_demod's stage 1 picks its own.  The device table is the caller's jobs
-// as they are and a column of first tiles, built and brought there as the other two's (fsea_jobs.h: JobTable); a workgroup
+// as they are and a column of first tiles, built and brought there as the others' (fsea_jobs.h: JobTable); a workgroup
 // finds its job by job_of_tile, scalar loads; the placement check, the layout and the host form are fsea_extract's too.
 // Staging: the lanes stride over the tile's span of d_ext; each loads its pair and the pair before it (the neighbour
 // lane's line: a cache hit), converts, subtracts and computes d once; what lies in front of the job is +0.0; an address
@@ -152,19 +152,26 @@ static_assert(offsetof(fsea_audio, kind) == 0 && offsetof(fsea_audio, n_taps) ==
 
 namespace {
 
+// where job i's audio lies, (out_first, count): the placement check's, the layout's and the host form's
+auto placed(const fsea_audio *a, const fsea_audio_job *jobs) {
+    return [a, jobs](size_t i, uint64_t *first, uint64_t *n) {
+        *first = jobs[i].out_first;
+        *n = jobs[i].n_pairs / (uint64_t)a->decimation;
+    };
+}
+
 // Everything a run checks but the alignment, in the header's order, reading nothing of the object but its decimation.
 int check_run(const fsea_audio *a, const void *pairs, size_t n_buffer_pairs, const fsea_audio_job *jobs, size_t n_jobs,
               double offset_re, double offset_im, double gain, const void *audio, size_t n_audio) {
     if (int rc = fsea_detail::check_jobs_head(a, "audio", n_jobs, jobs, pairs, audio)) return rc;
     if (n_jobs == 0) return FSEA_OK;
-    if (!std::isfinite(offset_re) || !std::isfinite(offset_im)) return fail(FSEA_EINVAL, "the offset is not finite");
+    if (int rc = fsea_detail::check_offset(offset_re, offset_im)) return rc;
     if (!std::isfinite(gain)) return fail(FSEA_EINVAL, "the gain is not finite");
-    const uint64_t D = (uint64_t)a->decimation;
     uint64_t total = 0;
     const int rc = fsea_detail::check_jobs_placement(n_jobs, n_audio, "", " of the audio", [&](size_t i, uint64_t *first, uint64_t *n) {
         const fsea_audio_job &j = jobs[i];
-        *first = j.out_first;
-        total += *n = j.n_pairs / D;
+        placed(a, jobs)(i, first, n);
+        total += *n;
         return fsea_detail::check_job_span(i, j.first_pair, j.n_pairs, n_buffer_pairs, FSEA_AUDIO_MAX_PAIRS, "pairs", "buffer");
     });
     if (rc) return rc;
@@ -228,20 +235,16 @@ int fsea_audio_decimation(const fsea_audio *a) { return a ? a->decimation : 0; }
 int fsea_audio_n_taps(const fsea_audio *a) { return a ? a->n_taps : 0; }
 
 int fsea_audio_layout(const fsea_audio *a, fsea_audio_job *jobs, size_t n_jobs, size_t *total_outputs) {
-    return fsea_detail::layout_jobs(a, "audio", jobs, n_jobs, total_outputs, "total_outputs", 1,
-                                    [&](const fsea_audio_job &j) { return j.n_pairs / (uint64_t)a->decimation; });
+    return fsea_detail::layout_jobs(a, "audio", jobs, n_jobs, total_outputs, "total_outputs", 1, placed(a, jobs));
 }
 
 int fsea_audio_run_device(fsea_audio *a, const void *d_pairs, size_t n_buffer_pairs, const fsea_audio_job *jobs, size_t n_jobs,
                           double offset_re, double offset_im, double gain, float *d_audio, size_t n_audio, void *stream) {
     const int rc = check_run(a, d_pairs, n_buffer_pairs, jobs, n_jobs, offset_re, offset_im, gain, d_audio, n_audio);
     if (rc || n_jobs == 0) return rc;
-    if (((uintptr_t)d_pairs & 7) || ((uintptr_t)d_audio & 3)) {
-        return fail(FSEA_EINVAL, "d_pairs must be 8-byte and d_audio 4-byte aligned");
-    }
-    std::lock_guard<std::mutex> lock(a->mu);
-    FSEA_ON_DEVICE(a->device);
-    return queue_call(a, d_pairs, jobs, n_jobs, offset_re, offset_im, gain, d_audio, static_cast<hipStream_t>(stream));
+    return fsea_detail::run_device_pairs(a, d_pairs, d_audio, "d_audio", 4, stream, [&](hipStream_t s) {
+        return queue_call(a, d_pairs, jobs, n_jobs, offset_re, offset_im, gain, d_audio, s);
+    });
 }
 
 int fsea_audio_run_host(fsea_audio *a, const float *pairs, size_t n_buffer_pairs, const fsea_audio_job *jobs, size_t n_jobs,
@@ -249,17 +252,11 @@ int fsea_audio_run_host(fsea_audio *a, const float *pairs, size_t n_buffer_pairs
     const int rc = check_run(a, pairs, n_buffer_pairs, jobs, n_jobs, offset_re, offset_im, gain, audio, n_audio);
     if (rc || n_jobs == 0) return rc;
     const uint64_t D = (uint64_t)a->decimation;
-    size_t end_in = 0;   // the pairs in front of end_in are staged
-    for (size_t i = 0; i < n_jobs; ++i) {
-        if (jobs[i].n_pairs / D) end_in = std::max(end_in, (size_t)(jobs[i].first_pair + jobs[i].n_pairs));
-    }
+    const size_t end_in = fsea_detail::staged_pairs(jobs, n_jobs, [D](const fsea_audio_job &j) { return j.n_pairs / D != 0; });
     return fsea_detail::run_host_placed(
         a, end_in * sizeof(float2), n_jobs, audio, [&](void *h_in) { std::memcpy(h_in, pairs, end_in * sizeof(float2)); },
         [&](void *d_in, float *d_out, hipStream_t s) { return queue_call(a, d_in, jobs, n_jobs, offset_re, offset_im, gain, d_out, s); },
-        [&](size_t i, uint64_t *first, uint64_t *n) {
-            *first = jobs[i].out_first;
-            *n = jobs[i].n_pairs / D;
-        });
+        placed(a, jobs));
 }
 
 }  // extern "C"

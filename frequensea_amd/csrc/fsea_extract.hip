@@ -114,6 +114,14 @@ static_assert(offsetof(fsea_extract, n_taps) == 0 && offsetof(fsea_extract, deci
 
 namespace {
 
+// where job i's pairs lie, (out_first, count): the placement check's, the layout's and the host form's
+auto placed(const fsea_extract *x, const fsea_extract_job *jobs) {
+    return [x, jobs](size_t i, uint64_t *first, uint64_t *n) {
+        *first = jobs[i].out_first;
+        *n = jobs[i].n_samples / (uint64_t)x->decimation;
+    };
+}
+
 // Everything a run checks, in the header's order, reading nothing of the object but its decimation.
 int check_run(const fsea_extract *x, const void *iq, size_t n_iq, const fsea_extract_job *jobs, size_t n_jobs, const void *pairs,
               size_t capacity) {
@@ -132,8 +140,7 @@ int check_run(const fsea_extract *x, const void *iq, size_t n_iq, const fsea_ext
     }
     if (int rc = fsea_detail::check_jobs_total(total, "outputs")) return rc;
     return fsea_detail::check_jobs_placement(n_jobs, capacity, "capacity of ", " pairs", [&](size_t i, uint64_t *first, uint64_t *n) {
-        *first = jobs[i].out_first;
-        *n = jobs[i].n_samples / D;
+        placed(x, jobs)(i, first, n);
         return FSEA_OK;
     });
 }
@@ -207,8 +214,7 @@ size_t fsea_extract_lead(int n_taps, int decimation) {
 }
 
 int fsea_extract_layout(const fsea_extract *x, fsea_extract_job *jobs, size_t n_jobs, size_t *total_pairs) {
-    return fsea_detail::layout_jobs(x, "extract", jobs, n_jobs, total_pairs, "total_pairs", 2,
-                                    [&](const fsea_extract_job &j) { return j.n_samples / (uint64_t)x->decimation; });
+    return fsea_detail::layout_jobs(x, "extract", jobs, n_jobs, total_pairs, "total_pairs", 2, placed(x, jobs));
 }
 
 int fsea_extract_run_device(fsea_extract *x, const void *d_iq, size_t n_iq_samples, int flip, const fsea_extract_job *jobs,
@@ -228,10 +234,7 @@ int fsea_extract_run_host(fsea_extract *x, const uint8_t *iq, size_t n_iq_sample
     return fsea_detail::run_host_placed(
         x, 2 * n_iq_samples, n_jobs, reinterpret_cast<cf *>(pairs), [&](void *h_in) { std::memcpy(h_in, iq, 2 * n_iq_samples); },
         [&](void *d_in, cf *d_out, hipStream_t s) { return queue_call(x, d_in, flip, jobs, n_jobs, d_out, s); },
-        [&](size_t i, uint64_t *first, uint64_t *n) {
-            *first = jobs[i].out_first;
-            *n = jobs[i].n_samples / (uint64_t)x->decimation;
-        });
+        placed(x, jobs));
 }
 
 int fsea_extract_jobs(const fsea_events_event *events, size_t n_events, int width, int hop, uint64_t n_samples, int n_taps,

@@ -2,9 +2,11 @@
 // fsea_measure (fsea_measure.hip), fsea_audio (fsea_audio.hip) and fsea_spectra (fsea_spectra.hip).  The look-up of a workgroup's job on the device; the
 // table's way from the caller to the device (JobTable: records and first-tile column built in mapped host memory by the
 // one routine `build`, copied by the one kernel fsea_jobs_upload, ordered by two events); the checks of a job table with
-// the one text each has, the placement of the outputs among them; and, for the three objects that place their outputs
-// (extract, audio, spectra), the layout and the host form that hands back only the jobs' own ranges.  What a job is, what a kernel
-// does with it and what lies behind the table in the scratch are each file's own.  Everything has internal linkage but
+// the one text each has, the placement of the outputs among them; for the three objects that place their outputs
+// (extract, audio, spectra), the layout and the host form that hands back only the jobs' own ranges; and, for the three that
+// read pairs (measure, audio, spectra), the spans of laid-out extract jobs, the end of the staged input and the tail of
+// run_device.  What a job is, what a kernel does with it, where its outputs lie and what lies behind the table in the
+// scratch are each file's own.  Everything has internal linkage but
 // jobs_upload, whose body stands beside its kernel in fsea_api.hip: the library is built without relocatable device code,
 // so a kernel has one translation unit.
 #pragma once
@@ -12,11 +14,14 @@
 #include "fsea_internal.h"
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 namespace fsea_detail {
 
-static_assert(FSEA_MEASURE_MAX_JOBS == FSEA_EXTRACT_MAX_JOBS && FSEA_AUDIO_MAX_JOBS == FSEA_EXTRACT_MAX_JOBS, "one cap of a job table");
+static_assert(FSEA_MEASURE_MAX_JOBS == FSEA_EXTRACT_MAX_JOBS && FSEA_AUDIO_MAX_JOBS == FSEA_EXTRACT_MAX_JOBS &&
+                  FSEA_SPECTRA_MAX_JOBS == FSEA_EXTRACT_MAX_JOBS,
+              "one cap of a job table");
 
 // fsea_jobs_upload on `s`: n_words 32-bit words from mapped host memory (its host address) to device memory, one a lane
 int jobs_upload(const void *h_table, void *d_table, uint32_t n_words, hipStream_t s);
@@ -102,7 +107,7 @@ struct JobTable {
     int release(hipStream_t s) { return scratch.release(s); }
 };
 
-// The checks of a job table, in the order the three objects have them: the count
+// The checks of a job table, in the order the four objects have them: the count
 int check_jobs_count(size_t n_jobs) {
     if (n_jobs > FSEA_EXTRACT_MAX_JOBS) return fail(FSEA_EINVAL, "n_jobs %zu above %d", n_jobs, FSEA_EXTRACT_MAX_JOBS);
     return FSEA_OK;
@@ -126,6 +131,12 @@ int check_job_span(size_t i, uint64_t first, uint64_t n, size_t n_buffer, uint64
                     (unsigned long long)first, (unsigned long long)n, n_buffer, buffer);
     }
     if (n > most) return fail(FSEA_EINVAL, "job %zu: n_%s %llu too large", i, elems, (unsigned long long)n);
+    return FSEA_OK;
+}
+
+// the offset of a pair stage
+int check_offset(double offset_re, double offset_im) {
+    if (!std::isfinite(offset_re) || !std::isfinite(offset_im)) return fail(FSEA_EINVAL, "the offset is not finite");
     return FSEA_OK;
 }
 
@@ -167,21 +178,23 @@ int check_jobs_placement(size_t n_jobs, size_t capacity, const char *before, con
 }
 
 // fsea_X_layout: out_first of every job, back to back in table order, each at a multiple of `align` (a power of two);
-// outputs(job) is a job's count.  `name` as in check_jobs_head, `total_name` the out-parameter's.
-template <class Job, class Outputs>
-int layout_jobs(const void *obj, const char *name, Job *jobs, size_t n_jobs, size_t *total, const char *total_name, uint64_t align,
-                Outputs &&outputs) {
+// at(i, &out_first, &n_out) as above, of which only the count is taken: the out_first it reports is the one about to be
+// overwritten, which a caller may have left unset, and is dropped.  `name` as in check_jobs_head, `total_name` the
+// out-parameter's.
+template <class Job, class At>
+int layout_jobs(const void *obj, const char *name, Job *jobs, size_t n_jobs, size_t *total, const char *total_name, uint64_t align, At &&at) {
     if (!obj) return fail(FSEA_EINVAL, "%s is NULL", name);
     if (!total) return fail(FSEA_EINVAL, "%s is NULL", total_name);
     if (int rc = check_jobs_count(n_jobs)) return rc;
     if (n_jobs && !jobs) return fail(FSEA_EINVAL, "NULL job table");
-    uint64_t at = 0;
+    uint64_t end = 0, unused, n;
     for (size_t i = 0; i < n_jobs; ++i) {
-        at = (at + align - 1) & ~(align - 1);
-        jobs[i].out_first = at;
-        at += outputs(jobs[i]);
+        end = (end + align - 1) & ~(align - 1);
+        at(i, &unused, &n);
+        jobs[i].out_first = end;
+        end += n;
     }
-    *total = (size_t)at;
+    *total = (size_t)end;
     return FSEA_OK;
 }
 
@@ -208,6 +221,46 @@ int run_host_placed(T *obj, size_t in_bytes, size_t n_jobs, Out *out, Fill &&fil
                 if (n) std::memcpy(out + first, reinterpret_cast<const Out *>(h) + first, (size_t)n * sizeof(Out));
             }
         });
+}
+
+// fsea_X_jobs of a pair stage: the spans of the outputs of extract jobs that fsea_extract_layout laid out, each without its
+// first skip_pairs pairs and of `most` pairs at the most; rest(job) fills what else the record has.
+template <class Job, class Rest>
+int jobs_of_extract(const fsea_extract_job *ejobs, size_t n_jobs, int decimation, size_t skip_pairs, unsigned most, Job *jobs, Rest &&rest) {
+    if (int rc = check_jobs_count(n_jobs)) return rc;
+    if (n_jobs && (!ejobs || !jobs)) return fail(FSEA_EINVAL, "NULL job table");
+    if (decimation < 1) return fail(FSEA_EINVAL, "decimation must be at least 1, got %d", decimation);
+    for (size_t i = 0; i < n_jobs; ++i) {
+        const uint64_t outs = ejobs[i].n_samples / (uint64_t)decimation;
+        const uint64_t skip = std::min<uint64_t>(skip_pairs, outs);
+        if (outs - skip > most) return fail(FSEA_EINVAL, "job %zu: %llu pairs, more than %u", i, (unsigned long long)(outs - skip), most);
+        jobs[i].first_pair = ejobs[i].out_first + skip;
+        jobs[i].n_pairs = outs - skip;
+        rest(jobs[i]);
+    }
+    return FSEA_OK;
+}
+
+// The host form of a pair stage stages the pairs in front of this: the end of the last job that has_output(job)
+template <class Job, class Has>
+size_t staged_pairs(const Job *jobs, size_t n_jobs, Has &&has_output) {
+    size_t end = 0;
+    for (size_t i = 0; i < n_jobs; ++i) {
+        if (has_output(jobs[i])) end = std::max(end, (size_t)(jobs[i].first_pair + jobs[i].n_pairs));
+    }
+    return end;
+}
+
+// The tail of a pair stage's run_device, the arguments checked and n_jobs at least 1: the alignment of the two buffers
+// (`out_name` has to be `align`-byte aligned), then queue(stream) under the object's mutex and on its device.
+template <class T, class Queue>
+int run_device_pairs(T *obj, const void *d_pairs, const void *d_out, const char *out_name, unsigned align, void *stream, Queue &&queue) {
+    if (((uintptr_t)d_pairs & 7) || ((uintptr_t)d_out & (align - 1))) {
+        return fail(FSEA_EINVAL, "d_pairs must be 8-byte and %s %u-byte aligned", out_name, align);
+    }
+    std::lock_guard<std::mutex> lock(obj->mu);
+    FSEA_ON_DEVICE(obj->device);
+    return queue(static_cast<hipStream_t>(stream));
 }
 
 }  // namespace

@@ -216,7 +216,7 @@ int check_run(const fsea_measure *m, const void *pairs, size_t n_buffer_pairs, c
     if (int rc = fsea_detail::check_jobs_head(m, "measure", n_jobs, jobs, pairs, sums)) return rc;
     if (n_jobs == 0) return FSEA_OK;
     if (lag < 1 || lag > FSEA_MEASURE_MAX_LAG) return fail(FSEA_EINVAL, "lag must be in [1, %d], got %d", FSEA_MEASURE_MAX_LAG, lag);
-    if (!std::isfinite(offset_re) || !std::isfinite(offset_im)) return fail(FSEA_EINVAL, "the offset is not finite");
+    if (int rc = fsea_detail::check_offset(offset_re, offset_im)) return rc;
     uint64_t total = 0;
     for (size_t i = 0; i < n_jobs; ++i) {
         const fsea_measure_job &j = jobs[i];
@@ -265,22 +265,16 @@ int fsea_measure_run_device(fsea_measure *m, const void *d_pairs, size_t n_buffe
                             double offset_re, double offset_im, int lag, fsea_measure_sums *d_sums, void *stream) {
     const int rc = check_run(m, d_pairs, n_buffer_pairs, jobs, n_jobs, offset_re, offset_im, lag, d_sums);
     if (rc || n_jobs == 0) return rc;
-    if (((uintptr_t)d_pairs & 7) || ((uintptr_t)d_sums & 15)) {
-        return fail(FSEA_EINVAL, "d_pairs must be 8-byte and d_sums 16-byte aligned");
-    }
-    std::lock_guard<std::mutex> lock(m->mu);
-    FSEA_ON_DEVICE(m->device);
-    return queue_call(m, d_pairs, jobs, n_jobs, offset_re, offset_im, lag, d_sums, static_cast<hipStream_t>(stream));
+    return fsea_detail::run_device_pairs(m, d_pairs, d_sums, "d_sums", 16, stream, [&](hipStream_t s) {
+        return queue_call(m, d_pairs, jobs, n_jobs, offset_re, offset_im, lag, d_sums, s);
+    });
 }
 
 int fsea_measure_run_host(fsea_measure *m, const float *pairs, size_t n_buffer_pairs, const fsea_measure_job *jobs, size_t n_jobs,
                           double offset_re, double offset_im, int lag, fsea_measure_sums *sums) {
     const int rc = check_run(m, pairs, n_buffer_pairs, jobs, n_jobs, offset_re, offset_im, lag, sums);
     if (rc || n_jobs == 0) return rc;
-    size_t end = 0;   // the pairs in front of `end` are staged
-    for (size_t i = 0; i < n_jobs; ++i) {
-        if (jobs[i].n_pairs) end = std::max(end, (size_t)(jobs[i].first_pair + jobs[i].n_pairs));
-    }
+    const size_t end = fsea_detail::staged_pairs(jobs, n_jobs, [](const fsea_measure_job &j) { return j.n_pairs != 0; });
     std::lock_guard<std::mutex> lock(m->mu);
     FSEA_ON_DEVICE(m->device);
     return m->staging.run(
@@ -291,19 +285,7 @@ int fsea_measure_run_host(fsea_measure *m, const float *pairs, size_t n_buffer_p
 }
 
 int fsea_measure_jobs(const fsea_extract_job *ejobs, size_t n_jobs, int decimation, size_t skip_pairs, fsea_measure_job *jobs) {
-    if (int rc = fsea_detail::check_jobs_count(n_jobs)) return rc;
-    if (n_jobs && (!ejobs || !jobs)) return fail(FSEA_EINVAL, "NULL job table");
-    if (decimation < 1) return fail(FSEA_EINVAL, "decimation must be at least 1, got %d", decimation);
-    for (size_t i = 0; i < n_jobs; ++i) {
-        const uint64_t outs = ejobs[i].n_samples / (uint64_t)decimation;
-        const uint64_t skip = std::min<uint64_t>(skip_pairs, outs);
-        if (outs - skip > FSEA_MEASURE_MAX_PAIRS) {
-            return fail(FSEA_EINVAL, "job %zu: %llu pairs, more than %u", i, (unsigned long long)(outs - skip), FSEA_MEASURE_MAX_PAIRS);
-        }
-        jobs[i].first_pair = ejobs[i].out_first + skip;
-        jobs[i].n_pairs = outs - skip;
-    }
-    return FSEA_OK;
+    return fsea_detail::jobs_of_extract(ejobs, n_jobs, decimation, skip_pairs, FSEA_MEASURE_MAX_PAIRS, jobs, [](fsea_measure_job &) {});
 }
 
 // Host arithmetic; no device is touched.  Each line is the header's formula; 0 / 0 gives the NaN of an empty or silent job.

@@ -8,7 +8,7 @@
 //
 // Kernel fsea_spectra_tiles_<n> ("Cut-out spectra"): one workgroup of SP_WG = 256 lanes per tile of
 // FSEA_SPECTRA_TILE_SEGMENTS segments of one job; the grid is the sum of the jobs' tiles.  The device table is the caller's
-// jobs as they are and a column of first tiles, built and brought there as the other three's (fsea_jobs.h: JobTable), the
+// jobs as they are and a column of first tiles, built and brought there as the others' (fsea_jobs.h: JobTable), the
 // tiles' partials behind it; a workgroup finds its job by job_of_tile, scalar loads.  A round transforms G = max(1, 1024 / n)
 // segments at once, P = G n = max(n, 1024) points, so that all 256 lanes have a radix-4 butterfly in every pass at any n.
 // The transform is Stockham's autosort, radix 4 with a final radix 2 where log2 n is odd, from one template on log2 n: pass 0
@@ -39,7 +39,6 @@ constexpr int SP_WG = 256;
 constexpr int SP_TILE = FSEA_SPECTRA_TILE_SEGMENTS;
 constexpr int SP_ROUND = 1024;                                // points a round transforms at the least: four a lane
 static_assert(sizeof(fsea_spectra_job) == 24, "the record of include/fsea.h");
-static_assert(FSEA_SPECTRA_MAX_JOBS == FSEA_EXTRACT_MAX_JOBS, "one cap of a job table");
 static_assert(FSEA_SPECTRA_MIN_N == 64 && FSEA_SPECTRA_MAX_N == 4096 && FSEA_SPECTRA_MIN_N / 4 >= 2, "(-1)^j is one sign for a lane's four inputs");
 
 // the geometry of one size
@@ -266,19 +265,26 @@ bool size_ok(int n) { return n >= FSEA_SPECTRA_MIN_N && n <= FSEA_SPECTRA_MAX_N 
 // S of the header
 uint64_t segments_of(uint64_t n_pairs, int n, int hop) { return n_pairs < (uint64_t)n ? 0 : (n_pairs - (uint64_t)n) / (uint64_t)hop + 1; }
 
+// where job i's powers lie: (out_first, count): the placement check's, the layout's and the host form's
+auto placed(const fsea_spectra *sp, const fsea_spectra_job *jobs) {
+    return [sp, jobs](size_t i, uint64_t *first, uint64_t *count) {
+        *first = jobs[i].out_first;
+        *count = segments_of(jobs[i].n_pairs, sp->n, sp->hop) ? (uint64_t)sp->n : 0;
+    };
+}
+
 // Everything a run checks but the alignment, in the header's order, reading nothing of the object but n and hop.
 int check_run(const fsea_spectra *sp, const void *pairs, size_t n_buffer_pairs, const fsea_spectra_job *jobs, size_t n_jobs,
               double offset_re, double offset_im, const void *power, size_t n_power) {
     if (int rc = fsea_detail::check_jobs_head(sp, "spectra", n_jobs, jobs, pairs, power)) return rc;
     if (n_jobs == 0) return FSEA_OK;
-    if (!std::isfinite(offset_re) || !std::isfinite(offset_im)) return fail(FSEA_EINVAL, "the offset is not finite");
+    if (int rc = fsea_detail::check_offset(offset_re, offset_im)) return rc;
     const int n = sp->n, hop = sp->hop;
     uint64_t total = 0;
     const int rc = fsea_detail::check_jobs_placement(n_jobs, n_power, "", " of the power", [&](size_t i, uint64_t *first, uint64_t *count) {
         const fsea_spectra_job &j = jobs[i];
         const uint64_t S = segments_of(j.n_pairs, n, hop);
-        *first = j.out_first;
-        *count = S ? (uint64_t)n : 0;
+        placed(sp, jobs)(i, first, count);
         total += S <= ((uint64_t)1 << 32) ? S * (uint64_t)n : (uint64_t)1 << 44;   // a span that is refused anyway
         return fsea_detail::check_job_span(i, j.first_pair, j.n_pairs, n_buffer_pairs, FSEA_SPECTRA_MAX_PAIRS, "pairs", "buffer");
     });
@@ -326,14 +332,6 @@ int queue_call(fsea_spectra *sp, const void *d_pairs, const fsea_spectra_job *jo
                        static_cast<const double *>(partials), n_i, hop_i, chunks, d_power);
     FSEA_HIP(hipGetLastError());
     return sp->table.release(s);
-}
-
-// where job i's powers lie: run_host_placed's and the placement check's
-auto placed(const fsea_spectra *sp, const fsea_spectra_job *jobs) {
-    return [sp, jobs](size_t i, uint64_t *first, uint64_t *count) {
-        *first = jobs[i].out_first;
-        *count = segments_of(jobs[i].n_pairs, sp->n, sp->hop) ? (uint64_t)sp->n : 0;
-    };
 }
 
 }  // namespace
@@ -384,31 +382,24 @@ int fsea_spectra_kind(const fsea_spectra *sp) { return sp ? sp->kind : -1; }
 size_t fsea_spectra_segments(const fsea_spectra *sp, size_t n_pairs) { return sp ? (size_t)segments_of(n_pairs, sp->n, sp->hop) : 0; }
 
 int fsea_spectra_layout(const fsea_spectra *sp, fsea_spectra_job *jobs, size_t n_jobs, size_t *total_floats) {
-    return fsea_detail::layout_jobs(sp, "spectra", jobs, n_jobs, total_floats, "total_floats", 1, [&](const fsea_spectra_job &j) {
-        return segments_of(j.n_pairs, sp->n, sp->hop) ? (uint64_t)sp->n : (uint64_t)0;
-    });
+    return fsea_detail::layout_jobs(sp, "spectra", jobs, n_jobs, total_floats, "total_floats", 1, placed(sp, jobs));
 }
 
 int fsea_spectra_run_device(fsea_spectra *sp, const void *d_pairs, size_t n_buffer_pairs, const fsea_spectra_job *jobs, size_t n_jobs,
                             double offset_re, double offset_im, float *d_power, size_t n_power, void *stream) {
     const int rc = check_run(sp, d_pairs, n_buffer_pairs, jobs, n_jobs, offset_re, offset_im, d_power, n_power);
     if (rc || n_jobs == 0) return rc;
-    if (((uintptr_t)d_pairs & 7) || ((uintptr_t)d_power & 3)) {
-        return fail(FSEA_EINVAL, "d_pairs must be 8-byte and d_power 4-byte aligned");
-    }
-    std::lock_guard<std::mutex> lock(sp->mu);
-    FSEA_ON_DEVICE(sp->device);
-    return queue_call(sp, d_pairs, jobs, n_jobs, offset_re, offset_im, d_power, static_cast<hipStream_t>(stream));
+    return fsea_detail::run_device_pairs(sp, d_pairs, d_power, "d_power", 4, stream, [&](hipStream_t s) {
+        return queue_call(sp, d_pairs, jobs, n_jobs, offset_re, offset_im, d_power, s);
+    });
 }
 
 int fsea_spectra_run_host(fsea_spectra *sp, const float *pairs, size_t n_buffer_pairs, const fsea_spectra_job *jobs, size_t n_jobs,
                           double offset_re, double offset_im, float *power, size_t n_power) {
     const int rc = check_run(sp, pairs, n_buffer_pairs, jobs, n_jobs, offset_re, offset_im, power, n_power);
     if (rc || n_jobs == 0) return rc;
-    size_t end_in = 0;   // the pairs in front of end_in are staged
-    for (size_t i = 0; i < n_jobs; ++i) {
-        if (segments_of(jobs[i].n_pairs, sp->n, sp->hop)) end_in = std::max(end_in, (size_t)(jobs[i].first_pair + jobs[i].n_pairs));
-    }
+    const size_t end_in = fsea_detail::staged_pairs(
+        jobs, n_jobs, [sp](const fsea_spectra_job &j) { return segments_of(j.n_pairs, sp->n, sp->hop) != 0; });
     return fsea_detail::run_host_placed(
         sp, end_in * sizeof(float2), n_jobs, power, [&](void *h_in) { std::memcpy(h_in, pairs, end_in * sizeof(float2)); },
         [&](void *d_in, float *d_out, hipStream_t s) { return queue_call(sp, d_in, jobs, n_jobs, offset_re, offset_im, d_out, s); },
@@ -416,20 +407,8 @@ int fsea_spectra_run_host(fsea_spectra *sp, const float *pairs, size_t n_buffer_
 }
 
 int fsea_spectra_jobs(const fsea_extract_job *ejobs, size_t n_jobs, int decimation, size_t skip_pairs, fsea_spectra_job *jobs) {
-    if (int rc = fsea_detail::check_jobs_count(n_jobs)) return rc;
-    if (n_jobs && (!ejobs || !jobs)) return fail(FSEA_EINVAL, "NULL job table");
-    if (decimation < 1) return fail(FSEA_EINVAL, "decimation must be at least 1, got %d", decimation);
-    for (size_t i = 0; i < n_jobs; ++i) {
-        const uint64_t outs = ejobs[i].n_samples / (uint64_t)decimation;
-        const uint64_t skip = std::min<uint64_t>(skip_pairs, outs);
-        if (outs - skip > FSEA_SPECTRA_MAX_PAIRS) {
-            return fail(FSEA_EINVAL, "job %zu: %llu pairs, more than %u", i, (unsigned long long)(outs - skip), FSEA_SPECTRA_MAX_PAIRS);
-        }
-        jobs[i].first_pair = ejobs[i].out_first + skip;
-        jobs[i].n_pairs = outs - skip;
-        jobs[i].out_first = 0;
-    }
-    return FSEA_OK;
+    return fsea_detail::jobs_of_extract(ejobs, n_jobs, decimation, skip_pairs, FSEA_SPECTRA_MAX_PAIRS, jobs,
+                                        [](fsea_spectra_job &j) { j.out_first = 0; });   // fsea_spectra_layout places them
 }
 
 // Host arithmetic; no device is touched.  Each line is the header's formula; 0 / 0 gives the NaN of a silent row.

@@ -1160,11 +1160,46 @@ def _address(array):
     return ctypes.addressof(array) if len(array) else None
 
 
-class Extract(_Handle):
+class _JobRunner(_Handle):
+    """What Extract, Measure, Audio and Spectra have in common, the objects that run a table of `_job` records over one
+    resident buffer: _table() makes the jobs the (array, address, length) a call takes.  A run_device names its function
+    and takes the offset apart itself: what it spends before the call is the host time the rate scripts print, and a
+    call forwarded through a method of this class took 2.4 us where it takes 1.6 (profiles/jobs_scaffold.txt)."""
+    _job = None    # the record of the table
+
+    def _table(self, jobs):
+        """(the jobs as one ctypes array, its address or None for an empty one, its length)"""
+        table = _table_of(self._job, jobs)
+        return table, _address(table), len(table)
+
+
+class _PlacingJobRunner(_JobRunner):
+    """The three that place their outputs, Extract, Audio and Spectra (Measure writes one record per job): layout() is
+    fsea_<kind>_layout, _run_placed() their host form: a copy of the jobs laid out, one call, one array per job."""
+
+    def layout(self, jobs):
+        """fsea_<kind>_layout: (the jobs as a ctypes array with out_first filled in, the outputs they need in all: pairs
+        for Extract, floats for Audio and Spectra)."""
+        table, at, n = self._table(jobs)
+        total = ctypes.c_size_t()
+        _check(getattr(self._L, "fsea_%s_layout" % self._kind)(self._p, at, n, ctypes.byref(total)))
+        return table, total.value
+
+    def _run_placed(self, before, jobs, dtype, count, *between):
+        """fsea_<kind>_run_host(object, *before, table, n_jobs, *between, out, total) on a copy of the jobs laid out with
+        layout(): a list of `dtype` arrays, count(job) long, one per job."""
+        table, total = self.layout([self._job.from_buffer_copy(j) for j in jobs])
+        out = np.zeros(max(total, 1), dtype=dtype)
+        _check(getattr(self._L, "fsea_%s_run_host" % self._kind)(self._p, *before, _address(table), len(table), *between,
+                                                                 out.ctypes.data, total))
+        return [out[j.out_first:j.out_first + count(j)].copy() for j in table]
+
+
+class Extract(_PlacingJobRunner):
     """Event cut-outs on one device: a table of shift -> low-pass -> keep every decimation-th sample jobs over one recording
     in one launch, stateless; thin wrapper over fsea_extract_*.  run() takes 8-bit IQ and the jobs from the host and
     returns one complex64 array per job; run_device() works on resident memory with the jobs' own out_first."""
-    _kind = "extract"
+    _kind, _job = "extract", ExtractJob
 
     def __init__(self, taps, decimation, device=0):
         t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
@@ -1174,37 +1209,32 @@ class Extract(_Handle):
     def out_pairs(self, n_samples):
         return self._L.fsea_extract_out_pairs(self._p, n_samples)
 
-    def layout(self, jobs):
-        """fsea_extract_layout: (the jobs as a ctypes array with out_first filled in, the pairs they need in all)."""
-        table = _table_of(ExtractJob, jobs)
-        total = ctypes.c_size_t()
-        _check(self._L.fsea_extract_layout(self._p, _address(table), len(table), ctypes.byref(total)))
-        return table, total.value
-
     def run(self, iq_u8, jobs, flip=False):
         """The host form on a copy of the jobs laid out with layout(): a list of complex64 arrays, one per job."""
         iq = np.ascontiguousarray(iq_u8, dtype=np.uint8).ravel()
-        table, total = self.layout([ExtractJob.from_buffer_copy(j) for j in jobs])
-        pairs = np.zeros(max(total, 1), dtype=np.complex64)
-        _check(self._L.fsea_extract_run_host(self._p, iq.ctypes.data, iq.size // 2, int(bool(flip)), _address(table), len(table),
-                                             pairs.ctypes.data, total))
-        return [pairs[j.out_first:j.out_first + j.n_samples // self.decimation].copy() for j in table]
+        return self._run_placed((iq.ctypes.data, iq.size // 2, int(bool(flip))), jobs, np.complex64,
+                                lambda j: j.n_samples // self.decimation)
 
     def run_device(self, d_iq_ptr, n_iq_samples, jobs, d_pairs_ptr, pairs_capacity, flip=False, stream=0):
         """Device pointers (ints, 16-byte aligned): 2 * n_iq_samples bytes in, pairs_capacity complex64 out, every job at its
         own out_first; asynchronous.  The jobs are read before the call returns."""
-        table = _table_of(ExtractJob, jobs)
-        _check(self._L.fsea_extract_run_device(self._p, d_iq_ptr or None, n_iq_samples, int(bool(flip)), _address(table), len(table),
-                                               d_pairs_ptr or None, pairs_capacity, stream or None))
+        table, at, n = self._table(jobs)
+        _check(self._L.fsea_extract_run_device(self._p, d_iq_ptr or None, n_iq_samples, int(bool(flip)), at, n, d_pairs_ptr or None,
+                                               pairs_capacity, stream or None))
+
+
+def _jobs_of_extract(kind, record, extract_jobs_laid_out, decimation, skip_pairs):
+    """fsea_<kind>_jobs: a ctypes array of `record`, one per extract job"""
+    table = _table_of(ExtractJob, extract_jobs_laid_out)
+    jobs = (record * len(table))()
+    _check(getattr(hip_lib(), "fsea_%s_jobs" % kind)(_address(table), len(table), int(decimation), int(skip_pairs), _address(jobs)))
+    return jobs
 
 
 def measure_jobs(extract_jobs_laid_out, decimation, skip_pairs=0):
     """fsea_measure_jobs (host arithmetic): the spans of the outputs of extract jobs that Extract.layout laid out, each
     without its first skip_pairs pairs, as a ctypes array of MeasureJob."""
-    table = _table_of(ExtractJob, extract_jobs_laid_out)
-    jobs = (MeasureJob * len(table))()
-    _check(hip_lib().fsea_measure_jobs(_address(table), len(table), int(decimation), int(skip_pairs), _address(jobs)))
-    return jobs
+    return _jobs_of_extract("measure", MeasureJob, extract_jobs_laid_out, decimation, skip_pairs)
 
 
 def measure_finish(sums, lag=1):
@@ -1214,11 +1244,11 @@ def measure_finish(sums, lag=1):
     return result
 
 
-class Measure(_Handle):
+class Measure(_JobRunner):
     """Signal measures on one device: a table of spans of one buffer of complex64 in, one record of moment sums per span out,
     in two launches, stateless; thin wrapper over fsea_measure_*.  run() takes the pairs and the jobs from the host and
     returns a ctypes array of MeasureSums; run_device() works on resident memory."""
-    _kind = "measure"
+    _kind, _job = "measure", MeasureJob
 
     def __init__(self, device=0):
         self.device = device
@@ -1226,20 +1256,19 @@ class Measure(_Handle):
 
     def run(self, pairs, jobs, offset=0j, lag=1):
         z = np.ascontiguousarray(pairs, dtype=np.complex64).ravel()
-        table = _table_of(MeasureJob, jobs)
-        sums = (MeasureSums * len(table))()
+        table, at, n = self._table(jobs)
+        sums = (MeasureSums * n)()
         offset = complex(offset)
-        _check(self._L.fsea_measure_run_host(self._p, z.ctypes.data, z.size, _address(table), len(table), offset.real, offset.imag,
-                                             int(lag), _address(sums)))
+        _check(self._L.fsea_measure_run_host(self._p, z.ctypes.data, z.size, at, n, offset.real, offset.imag, int(lag), _address(sums)))
         return sums
 
     def run_device(self, d_pairs_ptr, n_buffer_pairs, jobs, d_sums_ptr, offset=0j, lag=1, stream=0):
         """Device pointers (ints): n_buffer_pairs complex64 in (8-byte aligned), one 80-byte record per job out (16-byte
         aligned); asynchronous.  The jobs are read before the call returns."""
-        table = _table_of(MeasureJob, jobs)
+        table, at, n = self._table(jobs)
         offset = complex(offset)
-        _check(self._L.fsea_measure_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, _address(table), len(table), offset.real,
-                                               offset.imag, int(lag), d_sums_ptr or None, stream or None))
+        _check(self._L.fsea_measure_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, at, n, offset.real, offset.imag, int(lag),
+                                               d_sums_ptr or None, stream or None))
 
 
 def audio_layout(jobs, decimation):
@@ -1253,12 +1282,12 @@ def audio_layout(jobs, decimation):
     return table, at
 
 
-class Audio(_Handle):
+class Audio(_PlacingJobRunner):
     """Cut-out audio on one device: a table of spans of one buffer of complex64 in, every span's FM-discriminated
     (kind "fm") or envelope-detected ("am"), low-passed and decimated float32 audio out, in one launch, stateless; thin
     wrapper over fsea_audio_*.  run() takes the pairs and the jobs from the host and returns one float32 array per job;
     run_device() works on resident memory with the jobs' own out_first."""
-    _kind = "audio"
+    _kind, _job = "audio", AudioJob
 
     def __init__(self, kind, taps, decimation, device=0):
         t = np.ascontiguousarray(taps, dtype=np.float64).ravel()
@@ -1266,39 +1295,26 @@ class Audio(_Handle):
         self.n_taps, self.decimation, self.device = t.size, decimation, device
         self._create("fsea_audio_create", self.kind, t.ctypes.data if t.size else None, t.size, decimation, device)
 
-    def layout(self, jobs):
-        """fsea_audio_layout: (the jobs as a ctypes array with out_first filled in, the floats they need in all)."""
-        table = _table_of(AudioJob, jobs)
-        total = ctypes.c_size_t()
-        _check(self._L.fsea_audio_layout(self._p, _address(table), len(table), ctypes.byref(total)))
-        return table, total.value
-
     def run(self, pairs, jobs, offset=0j, gain=1.0):
         """The host form on a copy of the jobs laid out with layout(): a list of float32 arrays, one per job."""
         z = np.ascontiguousarray(pairs, dtype=np.complex64).ravel()
-        table, total = self.layout([AudioJob.from_buffer_copy(j) for j in jobs])
-        audio = np.zeros(max(total, 1), dtype=np.float32)
         offset = complex(offset)
-        _check(self._L.fsea_audio_run_host(self._p, z.ctypes.data, z.size, _address(table), len(table), offset.real, offset.imag,
-                                           float(gain), audio.ctypes.data, total))
-        return [audio[j.out_first:j.out_first + j.n_pairs // self.decimation].copy() for j in table]
+        return self._run_placed((z.ctypes.data, z.size), jobs, np.float32, lambda j: j.n_pairs // self.decimation,
+                                offset.real, offset.imag, float(gain))
 
     def run_device(self, d_pairs_ptr, n_buffer_pairs, jobs, d_audio_ptr, n_audio, offset=0j, gain=1.0, stream=0):
         """Device pointers (ints): n_buffer_pairs complex64 in (8-byte aligned), n_audio float32 out (4-byte aligned), every
         job at its own out_first; asynchronous.  The jobs are read before the call returns."""
-        table = _table_of(AudioJob, jobs)
+        table, at, n = self._table(jobs)
         offset = complex(offset)
-        _check(self._L.fsea_audio_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, _address(table), len(table), offset.real,
-                                             offset.imag, float(gain), d_audio_ptr or None, n_audio, stream or None))
+        _check(self._L.fsea_audio_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, at, n, offset.real, offset.imag,
+                                             float(gain), d_audio_ptr or None, n_audio, stream or None))
 
 
 def spectra_jobs(extract_jobs_laid_out, decimation, skip_pairs=0):
     """fsea_spectra_jobs (host arithmetic): the spans of the outputs of extract jobs that Extract.layout laid out, each
     without its first skip_pairs pairs, as a ctypes array of SpectraJob (out_first 0: Spectra.layout places them)."""
-    table = _table_of(ExtractJob, extract_jobs_laid_out)
-    jobs = (SpectraJob * len(table))()
-    _check(hip_lib().fsea_spectra_jobs(_address(table), len(table), int(decimation), int(skip_pairs), _address(jobs)))
-    return jobs
+    return _jobs_of_extract("spectra", SpectraJob, extract_jobs_laid_out, decimation, skip_pairs)
 
 
 def spectra_finish(power, guard_bins=0, fraction=0.99):
@@ -1309,12 +1325,12 @@ def spectra_finish(power, guard_bins=0, fraction=0.99):
     return result
 
 
-class Spectra(_Handle):
+class Spectra(_PlacingJobRunner):
     """Cut-out spectra on one device: a table of spans of one buffer of complex64 in, every span's averaged periodogram of n
     bins out -- of the span itself (kind "z"), of |z|^2 ("env"), z^2 ("sq") or z^4 ("fourth") -- in two launches, stateless;
     thin wrapper over fsea_spectra_*.  run() takes the pairs and the jobs from the host and returns one float32 array per
     job (empty for a span shorter than n); run_device() works on resident memory with the jobs' own out_first."""
-    _kind = "spectra"
+    _kind, _job = "spectra", SpectraJob
 
     def __init__(self, n, hop=None, kind="z", window=None, device=0):
         self.n, self.hop, self.device = int(n), int(n) // 2 if hop is None else int(hop), device
@@ -1327,30 +1343,20 @@ class Spectra(_Handle):
     def segments(self, n_pairs):
         return self._L.fsea_spectra_segments(self._p, n_pairs)
 
-    def layout(self, jobs):
-        """fsea_spectra_layout: (the jobs as a ctypes array with out_first filled in, the floats they need in all)."""
-        table = _table_of(SpectraJob, jobs)
-        total = ctypes.c_size_t()
-        _check(self._L.fsea_spectra_layout(self._p, _address(table), len(table), ctypes.byref(total)))
-        return table, total.value
-
     def run(self, pairs, jobs, offset=0j):
         """The host form on a copy of the jobs laid out with layout(): a list of float32 arrays, one per job."""
         z = np.ascontiguousarray(pairs, dtype=np.complex64).ravel()
-        table, total = self.layout([SpectraJob.from_buffer_copy(j) for j in jobs])
-        power = np.zeros(max(total, 1), dtype=np.float32)
         offset = complex(offset)
-        _check(self._L.fsea_spectra_run_host(self._p, z.ctypes.data, z.size, _address(table), len(table), offset.real, offset.imag,
-                                             power.ctypes.data, total))
-        return [power[j.out_first:j.out_first + (self.n if self.segments(j.n_pairs) else 0)].copy() for j in table]
+        return self._run_placed((z.ctypes.data, z.size), jobs, np.float32, lambda j: self.n if self.segments(j.n_pairs) else 0,
+                                offset.real, offset.imag)
 
     def run_device(self, d_pairs_ptr, n_buffer_pairs, jobs, d_power_ptr, n_power, offset=0j, stream=0):
         """Device pointers (ints): n_buffer_pairs complex64 in (8-byte aligned), n_power float32 out (4-byte aligned), every
         job with a segment at its own out_first; asynchronous.  The jobs are read before the call returns."""
-        table = _table_of(SpectraJob, jobs)
+        table, at, n = self._table(jobs)
         offset = complex(offset)
-        _check(self._L.fsea_spectra_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, _address(table), len(table), offset.real,
-                                               offset.imag, d_power_ptr or None, n_power, stream or None))
+        _check(self._L.fsea_spectra_run_device(self._p, d_pairs_ptr or None, n_buffer_pairs, at, n, offset.real, offset.imag,
+                                               d_power_ptr or None, n_power, stream or None))
 
 
 class Demod(_ResettableHandle):

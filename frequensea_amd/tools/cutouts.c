@@ -72,7 +72,7 @@ static void put_le(uint8_t *at, uint32_t value, int bytes) {
 }
 
 /* DIR/cutout-NNNNN.wav: the 44-byte header of mono 16-bit PCM, n samples of audio - mean, *peak their largest; 0: written */
-static int write_wav(const char *name, uint32_t rate, const float *audio, double mean, size_t n, double *peak) {
+static int write_wav(FILE *out, uint32_t rate, const float *audio, double mean, size_t n, double *peak) {
     uint8_t head[44];
     memcpy(head, "RIFF", 4);
     put_le(head + 4, (uint32_t)(36 + 2 * n), 4);
@@ -86,8 +86,6 @@ static int write_wav(const char *name, uint32_t rate, const float *audio, double
     put_le(head + 34, 16, 2);
     memcpy(head + 36, "data", 4);
     put_le(head + 40, (uint32_t)(2 * n), 4);
-    FILE *out = fopen(name, "wb");
-    if (out == NULL) return 1;
     int bad = fwrite(head, 1, sizeof(head), out) != sizeof(head);
     *peak = 0.0;
     for (size_t i = 0; i < n && !bad; i++) {
@@ -98,13 +96,31 @@ static int write_wav(const char *name, uint32_t rate, const float *audio, double
         put_le(two, (uint16_t)pcm, 2);
         bad = fwrite(two, 1, 2, out) != 2;
     }
-    return (fclose(out) != 0) | bad;
+    return bad;
 }
 
-/* a file of the output that could not be written */
-static void cannot_write(const char *name) {
-    fprintf(stderr, TOOL ": cannot write %s\n", name);
+/* Room for DIR/<any name of the output>: main's, after the checks.  Below, `format` makes the name of DIR and a number. */
+static char *out_name;
+static size_t out_name_len;
+
+/* a file of the output that could not be written: the one named last */
+static void cannot_write(void) {
+    fprintf(stderr, TOOL ": cannot write %s\n", out_name);
     exit(EXIT_FAILURE);
+}
+
+/* DIR/<name> open for writing, or the tool ends */
+static FILE *open_in(const char *dir, const char *format, unsigned number, const char *mode) {
+    snprintf(out_name, out_name_len, format, dir, number);
+    FILE *f = fopen(out_name, mode);
+    if (f == NULL) cannot_write();
+    return f;
+}
+
+/* DIR/<name> closed and, with `bad` 0, written whole, or the tool ends */
+static void close_in(FILE *f, int bad, const char *dir, const char *format, unsigned number) {
+    snprintf(out_name, out_name_len, format, dir, number);
+    if ((fclose(f) != 0) | bad) cannot_write();
 }
 
 typedef struct {
@@ -116,8 +132,6 @@ typedef struct {
     tool_detector det;
     int mode, type, audio_kind, audio_decimation; /* what the checks make of the names and rates; audio_kind -1: no --audio */
     int spectra_kind, spectra_window_kind;
-    char *name;                                   /* room for DIR/<any name of the output>, name_len bytes: main's, after the checks */
-    size_t name_len;
 } options;
 
 /* the command line into *o (the defaults are the caller's), every value checked: a wrong one ends the tool */
@@ -271,16 +285,14 @@ static void measure_batch(measure_stage *m, const batch *b, int lag) {
 }
 
 static void measure_close(measure_stage *m, const options *o, size_t n_jobs, const size_t *written) {
-    snprintf(o->name, o->name_len, "%s/measures.txt", o->out_dir);
-    FILE *table = fopen(o->name, "w");
-    if (table == NULL) cannot_write(o->name);
+    FILE *table = open_in(o->out_dir, "%s/measures.txt", 0, "w");
     for (size_t e = 0; e < n_jobs; e++) {
         const fsea_measure_result *r = &m->results[e];
         if (written[e] == 0) continue;
         fprintf(table, "%u %zu %.9e %.9e %.9e %.9e %.9e %.9e %.9e %.9e\n", (unsigned)e, written[e], r->power_db, r->freq_cycles,
                 r->freq_cycles * o->det.rate / (double)o->decimation / 1e6, r->width_cycles, r->kurtosis, r->crest, r->dc_re, r->dc_im);
     }
-    if (fclose(table) != 0) cannot_write(o->name);
+    close_in(table, 0, o->out_dir, "%s/measures.txt", 0);
     fsea_measure_destroy(m->object);
     fsea_device_free(0, m->d_sums);
     free(m->results);
@@ -342,16 +354,15 @@ static void audio_batch(audio_stage *a, const batch *b, const options *o) {
             for (size_t i = 0; i < n_audio; i++) mean += (double)x[i];
             mean /= (double)n_audio;
         }
-        snprintf(o->name, o->name_len, "%s/cutout-%05u.wav", o->out_dir, e);
-        if (write_wav(o->name, (uint32_t)(a->out_rate + 0.5), x, mean, n_audio, &peak)) cannot_write(o->name);
+        FILE *wav = open_in(o->out_dir, "%s/cutout-%05u.wav", e, "wb");
+        close_in(wav, write_wav(wav, (uint32_t)(a->out_rate + 0.5), x, mean, n_audio, &peak), o->out_dir, "%s/cutout-%05u.wav", e);
         fprintf(a->list, "%u %.3f %zu %.6f\n", e, a->out_rate, n_audio, peak);
         a->n_files++;
     }
 }
 
 static void audio_close(audio_stage *a, const options *o) {
-    snprintf(o->name, o->name_len, "%s/audio.txt", o->out_dir);
-    if (fclose(a->list) != 0) cannot_write(o->name);
+    close_in(a->list, 0, o->out_dir, "%s/audio.txt", 0);
     fsea_audio_destroy(a->object);
     tool_grown_free(&a->audio);
     free(a->jobs);
@@ -420,8 +431,7 @@ static void spectra_batch(spectra_stage *s, const batch *b, const options *o) {
 }
 
 static void spectra_close(spectra_stage *s, const options *o) {
-    snprintf(o->name, o->name_len, "%s/spectra.txt", o->out_dir);
-    if (fclose(s->list) != 0) cannot_write(o->name);
+    close_in(s->list, 0, o->out_dir, "%s/spectra.txt", 0);
     fsea_spectra_destroy(s->object);
     tool_grown_free(&s->power);
     free(s->jobs);
@@ -489,13 +499,11 @@ int main(int argc, char **argv) {
     }
     batch b = {(fsea_extract_job *)malloc(sizeof(fsea_extract_job) * (n_jobs + 1)), (size_t *)malloc(sizeof(size_t) * (n_jobs + 1)),
                (fsea_measure_job *)malloc(sizeof(fsea_measure_job) * (n_jobs + 1)), 0, 0, {NULL, NULL, 0}, 0.0};
-    o.name_len = strlen(o.out_dir) + 32;
-    o.name = (char *)malloc(o.name_len);
-    if (o.name == NULL || b.jobs == NULL || b.event == NULL || b.spans == NULL) usage_error("out of memory");
-    snprintf(o.name, o.name_len, "%s/audio.txt", o.out_dir);
-    if (o.audio_kind >= 0 && (audio.list = fopen(o.name, "w")) == NULL) cannot_write(o.name);
-    snprintf(o.name, o.name_len, "%s/spectra.txt", o.out_dir);
-    if (o.spectra && (spectra.list = fopen(o.name, "w")) == NULL) cannot_write(o.name);
+    out_name_len = strlen(o.out_dir) + 32;
+    out_name = (char *)malloc(out_name_len);
+    if (out_name == NULL || b.jobs == NULL || b.event == NULL || b.spans == NULL) usage_error("out of memory");
+    if (o.audio_kind >= 0) audio.list = open_in(o.out_dir, "%s/audio.txt", 0, "w");
+    if (o.spectra) spectra.list = open_in(o.out_dir, "%s/spectra.txt", 0, "w");
     for (int k = 0; k < n_taps; k++) b.pedestal += (double)(float)taps[k];
     b.pedestal *= 0.5; /* of the taps as the f32 values the extract holds */
     void *h_iq = NULL, *d_iq = NULL;
@@ -533,18 +541,15 @@ int main(int argc, char **argv) {
         for (size_t k = 0; k < b.n; k++) {
             const size_t keep = (size_t)b.spans[k].n_pairs, e = b.event[k];
             if (keep == 0) continue;
-            snprintf(o.name, o.name_len, "%s/cutout-%05u.cf32", o.out_dir, (unsigned)e);
             const float *from = (const float *)b.pairs.h + 2 * (size_t)b.spans[k].first_pair;
-            FILE *out = fopen(o.name, "wb");
-            if (out == NULL || fwrite(from, 2 * sizeof(float), keep, out) != keep || fclose(out) != 0) cannot_write(o.name);
+            FILE *out = open_in(o.out_dir, "%s/cutout-%05u.cf32", (unsigned)e, "wb");
+            close_in(out, fwrite(from, 2 * sizeof(float), keep, out) != keep, o.out_dir, "%s/cutout-%05u.cf32", (unsigned)e);
             written[e] = keep;
             n_cutouts++;
         }
     }
 
-    snprintf(o.name, o.name_len, "%s/cutouts.txt", o.out_dir);
-    FILE *list = fopen(o.name, "w");
-    if (list == NULL) cannot_write(o.name);
+    FILE *list = open_in(o.out_dir, "%s/cutouts.txt", 0, "w");
     for (size_t e = 0; e < n_events; e++) {
         const fsea_events_event *ev = &found_events[e];
         const int listed = e < n_jobs;
@@ -553,7 +558,7 @@ int main(int argc, char **argv) {
                 ev->col_last, listed ? (unsigned long long)jobs[e].first : 0ull, listed ? (unsigned long long)jobs[e].n_samples : 0ull, mhz,
                 rate / (double)decimation, written[e], listed ? (int)fits[e] : 0, listed ? (int)cut[e] : 0);
     }
-    if (fclose(list) != 0) cannot_write(o.name);
+    close_in(list, 0, o.out_dir, "%s/cutouts.txt", 0);
     if (o.measures) measure_close(&measure, &o, n_jobs, written);
     if (o.audio_kind >= 0) audio_close(&audio, &o);
     if (o.spectra) spectra_close(&spectra, &o);
@@ -569,7 +574,7 @@ int main(int argc, char **argv) {
     tool_grown_free(&b.pairs);
     fsea_host_free(h_iq);
     fclose(fp);
-    free(o.name);
+    free(out_name);
     free(b.jobs);
     free(b.event);
     free(b.spans);

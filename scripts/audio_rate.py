@@ -55,43 +55,23 @@ HEADER = """# scripts/audio_rate.py on one MI355X: HIP-event times in one proces
 
 def setup(D):
     """the three routes as calls, and what to release afterwards"""
-    import torch
-    iq = ratelib.recording(N_SAMPLES)
-    d_in = fsea.DeviceBuffer(iq.nbytes).upload(iq)
-    torch.cuda.init()
-    c = fsea.lowpass_taps(10e6, 10e6 / (2 * D), TAPS)
+    x = ratelib.cutouts(fsea, D, JOB_BASE + D, N_SAMPLES, TAPS, N_JOBS)
     pair_rate = 10e6 / D
-    n_pairs = JOB_BASE // D
-    ex = fsea.Extract(c, D)
     au = fsea.Audio("fm", fsea.lowpass_taps(pair_rate, 0.4 * pair_rate / AUDIO_D, AUDIO_TAPS), AUDIO_D)
-    ejobs = [fsea.ExtractJob(131072 * i + 3 + i % 5, JOB_BASE + D, 131072 * i + 3 + i % 5, (i - 128) / 1024.0, 0.0, 0) for i in range(N_JOBS)]
-    table, total = ex.layout(ejobs)
-    d_pairs = fsea.DeviceBuffer(8 * total)
-    ajobs, n_audio = au.layout([fsea.AudioJob(j.out_first + i % 2, n_pairs, 0) for i, j in enumerate(table)])
+    ajobs, n_audio = au.layout([fsea.AudioJob(j.out_first + i % 2, JOB_BASE // D, 0) for i, j in enumerate(x.table)])
     singles = [(fsea.AudioJob * 1)(j) for j in ajobs]
     d_audio = fsea.DeviceBuffer(4 * n_audio)
-    offset = 0.5 * float(np.sum(c.astype(np.float32).astype(np.float64))) * (1 + 1j)
     gain = pair_rate / (2 * np.pi * 75000.0)
 
     def a():
-        au.run_device(d_pairs.ptr.value, total, ajobs, d_audio.ptr.value, n_audio, offset=offset, gain=gain)
+        au.run_device(x.d_pairs.ptr.value, x.total, ajobs, d_audio.ptr.value, n_audio, offset=x.offset, gain=gain)
 
     def b():
         for one in singles:
-            au.run_device(d_pairs.ptr.value, total, one, d_audio.ptr.value, n_audio, offset=offset, gain=gain)
+            au.run_device(x.d_pairs.ptr.value, x.total, one, d_audio.ptr.value, n_audio, offset=x.offset, gain=gain)
 
-    def c_route():
-        ex.run_device(d_in.ptr.value, N_SAMPLES, table, d_pairs.ptr.value, total, flip=True)
-
-    c_route()
-    return a, b, c_route, (ex, au), (d_in, d_pairs, d_audio)
-
-
-def release(objects, buffers):
-    for o in objects:
-        o.close()
-    for o in buffers:
-        o.free()
+    x.extract()
+    return a, b, x.extract, (x.ex, au), (x.d_in, x.d_pairs, d_audio)
 
 
 def measure(D):
@@ -108,27 +88,20 @@ def measure(D):
           "   traffic bound %5.2f us   f64 bound %5.2f us   (a)/(c) %.3f   (b)/(a) %.1f   host time of (a) %.1f us"
           % (D, pairs, N_JOBS, ta * 1e6, ta_min * 1e6, N_JOBS, tb * 1e6, tb_min * 1e6, tc * 1e6, tc_min * 1e6, traffic * 1e6, f64 * 1e6,
              ta / tc, tb / ta, float(np.median(host)) * 1e6))
-    release(objects, buffers)
+    ratelib.release(objects, buffers)
 
 
 def launches():
     """what the trace sees: TRACE_CALLS calls of (a) at TRACE_D"""
     a, b, c_route, objects, buffers = setup(TRACE_D)
-    for _ in range(TRACE_CALLS):
-        a()
-    sync = fsea.Plan(128)
-    sync.synchronize()
-    sync.close()
-    release(objects, buffers)
+    ratelib.traced_calls(fsea, a, TRACE_CALLS)
+    ratelib.release(objects, buffers)
 
 
 def trace():
-    # the upload is every job table's, so the extract call that makes the pairs has one too: the first dispatch of all
-    argv = [sys.executable, os.path.abspath(__file__), "launches"]
-    name, times = ratelib.kernel_trace(argv, (KERNELS[0], "fsea_audio_"), 1 + 2 * TRACE_CALLS, 1)[0]
-    assert name.startswith(KERNELS[0]), name
+    times = ratelib.call_kernel_times(__file__, KERNELS, "fsea_audio_", TRACE_CALLS)
     print("kernel trace, D=%d, %d calls of (a): " % (TRACE_D, TRACE_CALLS) +
-          "   ".join("%s %.1f us" % (k, float(np.median(times[1 + i::2])) * 1e6) for i, k in enumerate(KERNELS)))
+          "   ".join("%s %.1f us" % (k, t * 1e6) for k, t in zip(KERNELS, times)))
 
 
 def main():

@@ -44,29 +44,19 @@ HEADER = """# scripts/extract_rate.py on one MI355X: HIP-event times in one proc
 
 
 def measure(D):
-    import torch
-    iq = np.random.default_rng(1).integers(0, 256, 2 * N_SAMPLES, dtype=np.uint8)
-    d_in = fsea.DeviceBuffer(iq.nbytes).upload(iq)
-    torch.cuda.init()
-    c = fsea.lowpass_taps(10e6, 10e6 / (2 * D), TAPS)
     n_job = JOB_BASE + D - 1
     total_samples = N_JOBS * n_job
-    ex = fsea.Extract(c, D)
-    jobs = [fsea.ExtractJob(131072 * i + 3 + i % 5, n_job, 131072 * i + 3 + i % 5, (i - 128) / 1024.0, 0.0, 0) for i in range(N_JOBS)]
-    table, total = ex.layout(jobs)
-    d_pairs = fsea.DeviceBuffer(8 * total)
-    zoom = fsea.Zoom(c, D, 128, 1 << 30)
+    x = ratelib.cutouts(fsea, D, n_job, N_SAMPLES, TAPS, N_JOBS)
+    a, d_in = x.extract, x.d_in
+    zoom = fsea.Zoom(x.c, D, 128, 1 << 30)
     assert zoom.out_rows(total_samples) == 1 and zoom.out_rows(n_job) == 1
     d_row = fsea.DeviceBuffer(128 * 4)
-
-    def a():
-        ex.run_device(d_in.ptr.value, N_SAMPLES, table, d_pairs.ptr.value, total, flip=True)
 
     def b():
         zoom.run_device(d_in.ptr.value, total_samples, d_row.ptr.value, -0.125, flip=True)
 
     def c_route():
-        for j in table:
+        for j in x.table:
             zoom.run_device(d_in.ptr.value + 2 * (j.first & ~7), n_job, d_row.ptr.value, j.cycles_per_sample,
                             sample_offset=j.sample_offset, flip=True)
 
@@ -80,10 +70,7 @@ def measure(D):
           "   traffic bound %5.1f us   (a)/(b) %.3f   (c)/(a) %.1f   host time of (a) %.1f us"
           % (D, total_samples, N_JOBS, ta * 1e6, ta_min * 1e6, tb * 1e6, tb_min * 1e6, N_JOBS, tc * 1e6, tc_min * 1e6, bound * 1e6, ta / tb,
              tc / ta, float(np.median(host)) * 1e6))
-    for o in (ex, zoom):
-        o.close()
-    for o in (d_in, d_pairs, d_row):
-        o.free()
+    ratelib.release((x.ex, zoom), (d_in, x.d_pairs, d_row))
 
 
 def main():

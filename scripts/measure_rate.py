@@ -52,45 +52,26 @@ HEADER = """# scripts/measure_rate.py on one MI355X: HIP-event times in one proc
 
 
 def setup(D):
-    """the three routes as calls, what they work on, and what to release afterwards"""
-    import torch
-    iq = ratelib.recording(N_SAMPLES)
-    d_in = fsea.DeviceBuffer(iq.nbytes).upload(iq)
-    torch.cuda.init()
-    c = fsea.lowpass_taps(10e6, 10e6 / (2 * D), TAPS)
-    n_pairs = JOB_BASE // D
-    ex, m = fsea.Extract(c, D), fsea.Measure()
-    ejobs = [fsea.ExtractJob(131072 * i + 3 + i % 5, JOB_BASE + D, 131072 * i + 3 + i % 5, (i - 128) / 1024.0, 0.0, 0) for i in range(N_JOBS)]
-    table, total = ex.layout(ejobs)
-    d_pairs = fsea.DeviceBuffer(8 * total)
-    mjobs = (fsea.MeasureJob * N_JOBS)(*[fsea.MeasureJob(j.out_first + i % 2, n_pairs) for i, j in enumerate(table)])
+    """the three routes as calls, and what to release afterwards"""
+    x = ratelib.cutouts(fsea, D, JOB_BASE + D, N_SAMPLES, TAPS, N_JOBS)
+    m = fsea.Measure()
+    mjobs = (fsea.MeasureJob * N_JOBS)(*[fsea.MeasureJob(j.out_first + i % 2, JOB_BASE // D) for i, j in enumerate(x.table)])
     singles = [(fsea.MeasureJob * 1)(j) for j in mjobs]
     d_sums = fsea.DeviceBuffer(80 * N_JOBS)
-    offset = 0.5 * float(np.sum(c.astype(np.float32).astype(np.float64))) * (1 + 1j)
 
     def a():
-        m.run_device(d_pairs.ptr.value, total, mjobs, d_sums.ptr.value, offset=offset, lag=1)
-
-    def b():
-        ex.run_device(d_in.ptr.value, N_SAMPLES, table, d_pairs.ptr.value, total, flip=True)
+        m.run_device(x.d_pairs.ptr.value, x.total, mjobs, d_sums.ptr.value, offset=x.offset, lag=1)
 
     def c_route():
         for k, one in enumerate(singles):
-            m.run_device(d_pairs.ptr.value, total, one, d_sums.ptr.value + 80 * k, offset=offset, lag=1)
+            m.run_device(x.d_pairs.ptr.value, x.total, one, d_sums.ptr.value + 80 * k, offset=x.offset, lag=1)
 
-    b()
-    return a, b, c_route, total, offset, (ex, m), (d_in, d_pairs, d_sums)
-
-
-def release(objects, buffers):
-    for o in objects:
-        o.close()
-    for o in buffers:
-        o.free()
+    x.extract()
+    return a, x.extract, c_route, (x.ex, m), (x.d_in, x.d_pairs, d_sums)
 
 
 def measure(D):
-    a, b, c_route, total, offset, objects, buffers = setup(D)
+    a, b, c_route, objects, buffers = setup(D)
     n_pairs = JOB_BASE // D
     (tb, tb_min), (ta, ta_min), (tc, tc_min) = (ratelib.median_min(ratelib.per_call(fn, WARMUP, REPS)) for fn in (b, a, c_route))
     # what the host spends inside the call (a) before it returns: checks, the table of 256 jobs, three launches
@@ -103,27 +84,20 @@ def measure(D):
           "   traffic bound %5.2f us   f64 bound %5.2f us   (a)/(b) %.3f   (c)/(a) %.1f   host time of (a) %.1f us"
           % (D, pairs, N_JOBS, ta * 1e6, ta_min * 1e6, tb * 1e6, tb_min * 1e6, N_JOBS, tc * 1e6, tc_min * 1e6, traffic * 1e6, f64 * 1e6,
              ta / tb, tc / ta, float(np.median(host)) * 1e6))
-    release(objects, buffers)
+    ratelib.release(objects, buffers)
 
 
 def launches():
     """what the trace sees: TRACE_CALLS calls of (a) at TRACE_D"""
-    a, b, c_route, total, offset, objects, buffers = setup(TRACE_D)
-    for _ in range(TRACE_CALLS):
-        a()
-    sync = fsea.Plan(128)
-    sync.synchronize()
-    sync.close()
-    release(objects, buffers)
+    a, b, c_route, objects, buffers = setup(TRACE_D)
+    ratelib.traced_calls(fsea, a, TRACE_CALLS)
+    ratelib.release(objects, buffers)
 
 
 def trace():
-    # the upload is every job table's, so the extract call that makes the pairs has one too: the first dispatch of all
-    argv = [sys.executable, os.path.abspath(__file__), "launches"]
-    name, times = ratelib.kernel_trace(argv, (KERNELS[0], "fsea_measure_"), 1 + 3 * TRACE_CALLS, 1)[0]
-    assert name.startswith(KERNELS[0]), name
+    times = ratelib.call_kernel_times(__file__, KERNELS, "fsea_measure_", TRACE_CALLS)
     print("kernel trace, D=%d, %d calls of (a): " % (TRACE_D, TRACE_CALLS) +
-          "   ".join("%s %.1f us" % (k, float(np.median(times[1 + i::3])) * 1e6) for i, k in enumerate(KERNELS)))
+          "   ".join("%s %.1f us" % (k, t * 1e6) for k, t in zip(KERNELS, times)))
 
 
 def main():

@@ -1,6 +1,7 @@
 """What the scripts/*_rate.py share: four ways to time a call, the kernel-trace reader, the part runner, the seeded
-recording and, for the two detectors' scripts, the resident rows and the traffic count.  A script keeps its constants, its set-up, the bound it computes and its print lines; how a number is taken is
-here, once.
+recording, for the two detectors' scripts the resident rows and the traffic count, and for the cut-out stages' scripts
+the resident cut-outs and the per-kernel times of a call.  A script keeps its constants, its header text, the bound it
+computes and its print lines; how a number is taken, and what more than one script measures on, is here, once.
 
 Timing, all in seconds, each returning the list of its samples (the caller reduces: np.median, min, best of):
   per_call   HIP events round every single call;
@@ -17,6 +18,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import types
 
 import numpy as np
 
@@ -175,3 +177,55 @@ def detector_traffic(n, frames, tile, halo):
     the caller's."""
     per_row = sum(min(n, c0 + tile + halo) - max(0, c0 - halo) for c0 in range(0, n, tile))
     return frames * per_row, frames * n
+
+
+def cutout_jobs(fsea, n_jobs, n_job):
+    """The cut-out scripts' jobs: job i takes n_job samples from first = 131072 i + 3 + i mod 5, centre (i - 128) / 1024."""
+    return [fsea.ExtractJob(131072 * i + 3 + i % 5, n_job, 131072 * i + 3 + i % 5, (i - 128) / 1024.0, 0.0, 0) for i in range(n_jobs)]
+
+
+def cutouts(fsea, D, n_job, n_samples, n_taps, n_jobs):
+    """What the cut-out stages' scripts measure on: the seeded recording of n_samples uploaded (d_in), the taps (c) of the
+    low-pass for D, the Extract (ex), cutout_jobs laid out (table, total), the pairs buffer (d_pairs), the pedestal the
+    pairs rest on (offset) and the extract call as a closure (extract); the caller runs it, and releases ex, d_in and
+    d_pairs.  torch's HIP runtime is initialised between the upload, which loads the library, and everything else."""
+    import torch
+    iq = recording(n_samples)
+    d_in = fsea.DeviceBuffer(iq.nbytes).upload(iq)
+    torch.cuda.init()
+    c = fsea.lowpass_taps(10e6, 10e6 / (2 * D), n_taps)
+    ex = fsea.Extract(c, D)
+    table, total = ex.layout(cutout_jobs(fsea, n_jobs, n_job))
+    d_pairs = fsea.DeviceBuffer(8 * total)
+    offset = 0.5 * float(np.sum(c.astype(np.float32).astype(np.float64))) * (1 + 1j)
+
+    def extract():
+        ex.run_device(d_in.ptr.value, n_samples, table, d_pairs.ptr.value, total, flip=True)
+
+    return types.SimpleNamespace(d_in=d_in, c=c, ex=ex, table=table, total=total, d_pairs=d_pairs, offset=offset, extract=extract)
+
+
+def release(objects, buffers):
+    for o in objects:
+        o.close()
+    for o in buffers:
+        o.free()
+
+
+def traced_calls(fsea, call, n):
+    """The traced child of call_kernel_times: n calls, then the device at rest."""
+    for _ in range(n):
+        call()
+    sync = fsea.Plan(128)
+    sync.synchronize()
+    sync.close()
+
+
+def call_kernel_times(script, kernels, family, calls):
+    """The median seconds of each of `kernels`, a call's dispatches in launch order (the first is the table's upload, the
+    others start with `family`), over the `calls` calls that `script launches` makes behind the one extract call -- which
+    uploads a table too: the first dispatch of all, left out."""
+    argv = [sys.executable, os.path.abspath(script), "launches"]
+    name, times = kernel_trace(argv, (kernels[0], family), 1 + len(kernels) * calls, 1)[0]
+    assert name.startswith(kernels[0]), name
+    return [float(np.median(times[1 + i::len(kernels)])) for i in range(len(kernels))]

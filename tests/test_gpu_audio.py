@@ -7,7 +7,6 @@ can still go wrong: decimations 1, 3, 8 and the largest, one tap, a usual filter
 round one tile of T outputs (T is the object's own: 256 down to 56) and round two, one job of five tiles; odd and even
 firsts; jobs that overlap in the input; one that ends with the buffer.  A single tap at D = 1 lays d itself open, so a
 division or a square root that is not correctly rounded on the device shows there at once.  Inputs and outputs are guarded."""
-import ctypes
 import math
 import os
 import subprocess
@@ -21,6 +20,8 @@ from tests import demod_ref
 from tests import extract_ref as X
 from tests.conftest import ROOT
 from tests.guarded import FILL, Guarded
+from tests.jobs_common import address, pairs_of, pedestal, same_float_bits
+from tests.jobs_common import run_device as run_placed
 from tests.test_audio_host import (AUDIO_CUTOFF, CARRIER_BIN, D, D2, DEVIATION, L, L2, RATE, audio_taps, tone_check, tone_recording)
 
 pytestmark = pytest.mark.gpu
@@ -57,11 +58,6 @@ def taps_of(n_taps, seed=3):
     return rng.uniform(0.5, 1.5, n_taps) * rng.choice([-1.0, 1.0], n_taps) / n_taps
 
 
-def pairs_of(seed, n):
-    rng = np.random.default_rng(seed)
-    return (rng.normal(0.0, 1.0, n) + 1j * rng.normal(0.0, 1.0, n) + OFFSET).astype(np.complex64)
-
-
 def laid_out(jobs, d, gap=3):
     """the jobs as a table with their outputs in table order, `gap` floats of fill between them; the floats in all"""
     at, rows = gap, []
@@ -73,26 +69,8 @@ def laid_out(jobs, d, gap=3):
 
 def run_device(obj, d_pairs, n_buffer, table, n_audio, offset=OFFSET, gain=GAIN, stream=0, wait=None):
     """one call into a guarded output pre-filled with FILL -> (one float32 array per job, the mask of floats no job owns)"""
-    g = Guarded(4 * n_audio)
-    obj.run_device(d_pairs.addr, n_buffer, table, g.addr, n_audio, offset=offset, gain=gain, stream=stream)
-    if wait is not None:
-        wait()
-    back = g.payload(np.float32, (n_audio,))
-    g.check("the audio of %d jobs" % len(table))
-    g.free()
-    owned = np.zeros(n_audio, bool)
-    out = []
-    for j in table:
-        k = j.n_pairs // obj.decimation
-        owned[j.out_first:j.out_first + k] = True
-        out.append(back[j.out_first:j.out_first + k].copy())
-    assert np.all(back[~owned].view(np.uint8) == FILL), "a float that no job owns was written"
-    return out
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    return run_placed(obj, d_pairs, n_buffer, table, n_audio, lambda j: j.n_pairs // obj.decimation, "audio", stream, wait,
+                      offset=offset, gain=gain)
 
 
 @pytest.fixture(scope="module")
@@ -123,10 +101,10 @@ def test_every_output_equals_the_restatement_bit_for_bit(resident, kind, d, n_ta
     assert differ == 0
     if n_taps == 1 and d == 1:       # d itself: every output is (float)(gain c[0] d_i)
         dd = A.discriminator(z[jobs[-1][0]:], kind, OFFSET)
-        assert same_bits(got[-1], (np.float64(GAIN) * (0.0 + c[0] * dd)).astype(np.float32))
+        assert same_float_bits(got[-1], (np.float64(GAIN) * (0.0 + c[0] * dd)).astype(np.float32))
     # the host form: the same bits, and only the jobs' own floats
     host = obj.run(z, table, OFFSET, GAIN)
-    assert all(same_bits(h, g) for h, g in zip(host, got))
+    assert all(same_float_bits(h, g) for h, g in zip(host, got))
     obj.close()
 
 
@@ -144,10 +122,10 @@ def test_the_table_does_not_change_a_bit(resident, kind):
     t2, n2 = laid_out([jobs[k] for k in order], d, gap=1)
     permuted = run_device(obj, d_pairs, N_BUFFER, t2, n2)
     for at, k in enumerate(order):
-        assert same_bits(permuted[at], together[k]), k
+        assert same_float_bits(permuted[at], together[k]), k
     for k, j in enumerate(jobs):
         t1, n1 = laid_out([j], d, gap=0)
-        assert same_bits(run_device(obj, d_pairs, N_BUFFER, t1, max(n1, 1))[0], together[k]), k
+        assert same_float_bits(run_device(obj, d_pairs, N_BUFFER, t1, max(n1, 1))[0], together[k]), k
     small = [(11 * i + i % 2, 0 if i % 9 == 4 else 2 + (i * 131) % 900) for i in range(700)]
     big, where = list(small), {}
     for k, j in enumerate(jobs):
@@ -157,11 +135,11 @@ def test_the_table_does_not_change_a_bit(resident, kind):
     t3, n3 = laid_out(big, d, gap=2)
     among = run_device(obj, d_pairs, N_BUFFER, t3, n3)
     for k, at in where.items():
-        assert same_bits(among[at], together[k]), k
+        assert same_float_bits(among[at], together[k]), k
     placed = set(where.values())
     for at, (a, n) in enumerate(big):
         if at not in placed and at % 7 == 0:                      # and the small ones are right too
-            assert same_bits(among[at], A.audio(z[a:a + n], kind, c, d, OFFSET, GAIN)), (at, a, n)
+            assert same_float_bits(among[at], A.audio(z[a:a + n], kind, c, d, OFFSET, GAIN)), (at, a, n)
     obj.close()
 
 
@@ -181,7 +159,7 @@ def test_a_nan_pair_reaches_exactly_the_outputs_the_restatement_names(kind):
     for first in (6, 9):
         table, n_audio = laid_out([(first, n)], d)
         clean = run_device(obj, g.upload(base), base.size, table, n_audio)[0]
-        assert same_bits(clean, A.audio(base[first:first + n], kind, c, d, OFFSET, GAIN)) and np.all(np.isfinite(clean))
+        assert same_float_bits(clean, A.audio(base[first:first + n], kind, c, d, OFFSET, GAIN)) and np.all(np.isfinite(clean))
         # tile 1's span begins at d_ext[T D], i.e. pair T D - (L - 1); its last value is pair 2 T D - 1
         places = {"pair 0": 0, "the last pair": n - 1, "a tile's first d": t * d - (n_taps - 1), "a tile's last d": 2 * t * d - 1,
                   "the last d of tile 0": t * d - 1, "in front of the job": -1, "behind the job": n}
@@ -195,16 +173,12 @@ def test_a_nan_pair_reaches_exactly_the_outputs_the_restatement_names(kind):
             assert np.flatnonzero(np.isnan(got)).tolist() == named, (kind, name, first)
             keep = np.ones(got.size, bool)
             keep[named] = False
-            assert same_bits(got[keep], clean[keep]), (kind, name, first)
+            assert same_float_bits(got[keep], clean[keep]), (kind, name, first)
             if not 0 <= at < n:
-                assert named == [] and same_bits(got, clean), (kind, name, first)
+                assert named == [] and same_float_bits(got, clean), (kind, name, first)
     g.check("the input is read, not written")
     g.free()
     obj.close()
-
-
-def address(tab):
-    return ctypes.addressof(tab) if tab is not None and len(tab) else None
 
 
 def test_refusals_name_the_job_and_write_nothing(resident):
@@ -238,7 +212,7 @@ def test_refusals_name_the_job_and_write_nothing(resident):
     # and the same object still works, at the edge of what is accepted: a job that ends with the buffer, outputs that end with n_audio
     tab = (fsea.AudioJob * 2)(fsea.AudioJob(N_BUFFER - 80, 80, 0), fsea.AudioJob(N_BUFFER, 0, 20))
     got = run_device(obj, d_pairs, N_BUFFER, tab, 20, gain=1.0)
-    assert same_bits(got[0], A.audio(z[N_BUFFER - 80:], A.FM, taps_of(41), 4, OFFSET, 1.0)) and got[1].size == 0
+    assert same_float_bits(got[0], A.audio(z[N_BUFFER - 80:], A.FM, taps_of(41), 4, OFFSET, 1.0)) and got[1].size == 0
     obj.close()
 
 
@@ -264,7 +238,7 @@ def test_two_streams_and_an_odd_pair_base(resident):
     for jobs, shift, table, n_audio, g in runs:
         back = g.payload(np.float32, (max(n_audio, 1),))
         for j, (a, n) in zip(table, jobs):
-            assert same_bits(back[j.out_first:j.out_first + n // 8], A.audio(z[shift + a:shift + a + n], A.AM, c, 8, OFFSET, GAIN)), (a, n)
+            assert same_float_bits(back[j.out_first:j.out_first + n // 8], A.audio(z[shift + a:shift + a + n], A.AM, c, 8, OFFSET, GAIN)), (a, n)
         g.check("two streams")
         g.free()
     for o in (s1, s2, sync, obj):
@@ -290,13 +264,6 @@ def bursts_recording():
     raw = np.empty(2 * N * ROWS)
     raw[0::2], raw[1::2] = x.real, x.imag
     return np.clip(np.rint(raw), -128, 127).astype(np.int8).view(np.uint8)
-
-
-def pedestal(c):
-    total = 0.0
-    for v in np.asarray(c, dtype=np.float64).astype(np.float32).astype(np.float64):
-        total += float(v)
-    return 0.5 * total
 
 
 def test_end_to_end_a_tone_comes_out_of_its_burst():
@@ -334,7 +301,7 @@ def test_end_to_end_a_tone_comes_out_of_its_burst():
         if pairs is None:
             pairs = g_pairs.payload(np.complex64, (total,))
         for k, j in enumerate(table):
-            assert same_bits(got[k], A.audio(pairs[j.first_pair:j.first_pair + j.n_pairs], kind, c2, D2, off, gain)), (kind, k)
+            assert same_float_bits(got[k], A.audio(pairs[j.first_pair:j.first_pair + j.n_pairs], kind, c2, D2, off, gain)), (kind, k)
         # the burst of this kind: the event at its bin; the outputs whose taps lie inside the burst
         burst = FM_BURST if kind == A.FM else AM_BURST
         mine = [i for i, e in enumerate(events) if fits[i] and e["col_first"] <= N // 2 + burst[2] <= e["col_last"] and

@@ -10,8 +10,7 @@ Special values, where the header promises something (a NaN term is never the pea
 f64 conversions of the f32 values): one NaN or infinity per buffer at every place a kernel treats differently -- the stand-ins
 of a missing partner and of pairs past the end, both bodies, the lane's chain, the combine's and the fold's peak merges --,
 a buffer of -0.0, and one of subnormals and FLT_MAX.  Records that hold NaNs are compared through same_record; every other
-test keeps same_bits."""
-import ctypes
+test keeps same_record_bits."""
 import os
 import subprocess
 
@@ -23,6 +22,7 @@ from tests import extract_ref as R
 from tests import measure_ref as M
 from tests.conftest import ROOT
 from tests.guarded import FILL, Guarded
+from tests.jobs_common import address, pairs_of, pedestal, same_record_bits
 from tests.test_measure_host import extremes_buffer, pairs_f32, special_sums
 
 pytestmark = pytest.mark.gpu
@@ -50,11 +50,6 @@ def sweep(lag):
     return jobs, n_buffer
 
 
-def pairs_of(seed, n):
-    rng = np.random.default_rng(seed)
-    return (rng.normal(0.0, 1.0, n) + 1j * rng.normal(0.0, 1.0, n) + OFFSET).astype(np.complex64)
-
-
 def table(jobs):
     return (fsea.MeasureJob * len(jobs))(*[fsea.MeasureJob(a, n) for a, n in jobs])
 
@@ -69,10 +64,6 @@ def run_device(m, d_pairs, n_buffer, jobs, lag, offset=OFFSET, stream=0, wait=No
     g.check("the records of %d jobs" % len(jobs))
     g.free()
     return got
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
 
 
 @pytest.fixture(scope="module")
@@ -95,11 +86,11 @@ def test_every_record_equals_the_restatement_bit_for_bit(resident, lag):
     got = run_device(m, d_pairs, n_buffer, jobs, lag)
     for k, (a, n) in enumerate(jobs):
         want = M.sums(z[a:a + n], OFFSET, lag)
-        assert same_bits(got[k], want), (lag, k, a, n, got[k], want)
+        assert same_record_bits(got[k], want), (lag, k, a, n, got[k], want)
     assert got["n_pairs"].tolist() == [n for _, n in jobs] and got["n_lagged"].tolist() == [max(n - lag, 0) for _, n in jobs]
     # the host form: the same bytes
     host = np.frombuffer(m.run(z, table(jobs), OFFSET, lag), dtype=M.SUMS)
-    assert same_bits(host, got), lag
+    assert same_record_bits(host, got), lag
     m.close()
 
 
@@ -113,10 +104,10 @@ def test_the_table_does_not_change_a_bit(resident):
     order = list(np.random.default_rng(6).permutation(len(jobs)))
     permuted = run_device(m, d_pairs, n_buffer, [jobs[k] for k in order], lag)
     for at, k in enumerate(order):
-        assert same_bits(permuted[at], together[k]), k
+        assert same_record_bits(permuted[at], together[k]), k
     for k, j in enumerate(jobs):
         alone = run_device(m, d_pairs, n_buffer, [j], lag)
-        assert same_bits(alone[0], together[k]), k
+        assert same_record_bits(alone[0], together[k]), k
     # 700 jobs of one tile each (every ninth one empty), the sweep's jobs between them every 27th place
     small = [(11 * i + i % 2, 0 if i % 9 == 4 else 40 + (i * 131) % 4000) for i in range(700)]
     big, where = list(small), {}
@@ -127,11 +118,11 @@ def test_the_table_does_not_change_a_bit(resident):
     assert all(big[at] == jobs[k] for k, at in where.items()) and len(big) == 700 + len(jobs)
     among = run_device(m, d_pairs, n_buffer, big, lag)
     for k, at in where.items():
-        assert same_bits(among[at], together[k]), k
+        assert same_record_bits(among[at], together[k]), k
     placed = set(where.values())
     for at, (a, n) in enumerate(big):                       # and the small ones are right too
         if at not in placed:
-            assert same_bits(among[at], M.sums(z[a:a + n], OFFSET, lag)), (at, a, n)
+            assert same_record_bits(among[at], M.sums(z[a:a + n], OFFSET, lag)), (at, a, n)
     m.close()
 
 
@@ -147,7 +138,7 @@ def test_the_first_of_equal_peaks_wins():
         got = run_device(m, d, z.size, [(a, n), (a, 30), (0, 0)], 1, offset=0j)
         ref = M.sums(z[a:a + n], 0j, 1)
         assert got[0]["peak"] == 13.0 and got[0]["peak_index"] == min(i0, i1) == ref["peak_index"], (name, got[0])
-        assert same_bits(got[0], ref), name
+        assert same_record_bits(got[0], ref), name
         assert (got[1]["peak"], got[1]["peak_index"]) == (0.125, 0), name           # all equal: the first
         assert got[2].tobytes() == bytes(80), name                                   # empty: zeros, peak +0.0
         d.check(name)
@@ -170,12 +161,12 @@ def test_refusals_name_the_job_and_write_nothing(resident):
 
     def refused(word, jobs, pairs=d_pairs.addr, n=n_buffer, off=(0.5, 0.5), lag=1, out=g.addr, obj=None, n_jobs=None):
         tab = table(jobs) if jobs is not None else None
-        rc = L.fsea_measure_run_device(m._p if obj is None else obj, pairs, n, ctypes_address(tab), len(jobs) if n_jobs is None else n_jobs,
+        rc = L.fsea_measure_run_device(m._p if obj is None else obj, pairs, n, address(tab), len(jobs) if n_jobs is None else n_jobs,
                                        off[0], off[1], lag, out, None)
         assert rc == FSEA_EINVAL and word in err(), (word, rc, err())
 
     ok = [(0, 10), (5, 20)]
-    assert L.fsea_measure_run_device(None, d_pairs.addr, n_buffer, ctypes_address(table(ok)), 2, 0.5, 0.5, 1, g.addr, None) == FSEA_EINVAL
+    assert L.fsea_measure_run_device(None, d_pairs.addr, n_buffer, address(table(ok)), 2, 0.5, 0.5, 1, g.addr, None) == FSEA_EINVAL
     assert b"measure is NULL" in err()
     refused(b"n_jobs", ok, n_jobs=fsea.MEASURE_MAX_JOBS + 1)
     refused(b"NULL job table", None, n_jobs=2)
@@ -196,13 +187,9 @@ def test_refusals_name_the_job_and_write_nothing(resident):
     g.check("refused calls")
     # and the same object still works, at the edge of what is accepted: a job that ends with the buffer, the largest lag
     got = run_device(m, d_pairs, n_buffer, [(n_buffer - 20, 20), (n_buffer, 0)], fsea.MEASURE_MAX_LAG)
-    assert same_bits(got[0], M.sums(z[n_buffer - 20:], OFFSET, fsea.MEASURE_MAX_LAG)) and got[1].tobytes() == bytes(80)
+    assert same_record_bits(got[0], M.sums(z[n_buffer - 20:], OFFSET, fsea.MEASURE_MAX_LAG)) and got[1].tobytes() == bytes(80)
     g.free()
     m.close()
-
-
-def ctypes_address(tab):
-    return ctypes.addressof(tab) if tab is not None and len(tab) else None
 
 
 def test_two_streams_and_an_odd_pair_base(resident):
@@ -222,9 +209,9 @@ def test_two_streams_and_an_odd_pair_base(resident):
     sync.synchronize(s2)
     got_a, got_b = g_a.payload(M.SUMS, (len(jobs_a),)), g_b.payload(M.SUMS, (len(jobs_b),))
     for k, (a, n) in enumerate(jobs_a):
-        assert same_bits(got_a[k], M.sums(z[a:a + n], OFFSET, 3)), k
+        assert same_record_bits(got_a[k], M.sums(z[a:a + n], OFFSET, 3)), k
     for k, (a, n) in enumerate(jobs_b):
-        assert same_bits(got_b[k], M.sums(z[1 + a:1 + a + n], OFFSET, 2)), k
+        assert same_record_bits(got_b[k], M.sums(z[1 + a:1 + a + n], OFFSET, 2)), k
     for g in (g_a, g_b):
         g.check("two streams")
         g.free()
@@ -245,9 +232,9 @@ def same_record(got, want):
     """The comparison rule for records that hold NaNs: peak, peak_index, n_pairs and n_lagged by their bits; each of the six
     sums by its bits where the reference is not a NaN and "is a NaN" where it is -- neither include/fsea.h nor IEEE 754 fixes
     the sign and the payload of a generated NaN, and x86 and the GPU differ."""
-    ok = all(same_bits(got[name], want[name]) for name in ("peak", "peak_index", "n_pairs", "n_lagged"))
+    ok = all(same_record_bits(got[name], want[name]) for name in ("peak", "peak_index", "n_pairs", "n_lagged"))
     for name in M.NAMES:
-        ok = ok and (bool(np.isnan(got[name])) if np.isnan(want[name]) else same_bits(got[name], want[name]))
+        ok = ok and (bool(np.isnan(got[name])) if np.isnan(want[name]) else same_record_bits(got[name], want[name]))
     return ok
 
 
@@ -329,7 +316,7 @@ def test_a_nan_or_an_infinity_at_every_place_a_kernel_treats_differently(special
                 else:
                     assert (got[0]["p"], got[0]["q"], got[0]["peak"], got[0]["peak_index"]) == (np.inf, np.inf, np.inf, at), what
                 for k in range(1, len(jobs)):
-                    assert same_bits(got[k], want[k]), what + (jobs[k],)
+                    assert same_record_bits(got[k], want[k]), what + (jobs[k],)
                     assert all(np.isfinite(got[k][f]) for f in M.NAMES + ("peak",)), what + (jobs[k],)
                 host = np.frombuffer(m.run(z, table(jobs), OFFSET, lag), dtype=M.SUMS)
                 assert all(same_record(host[k], want[k]) for k in range(len(jobs))), what + ("host form",)
@@ -345,7 +332,7 @@ def test_minus_zero_pairs_give_plus_zero_records(special):
     for lag in SPECIAL_LAGS:
         got = run_device(m, d_pairs, N_SPECIAL, jobs, lag, offset=0j)
         for k, (a, n) in enumerate(jobs):
-            assert same_bits(got[k], special_sums(z[a:a + n], 0j, lag)), (lag, a, n, got[k])
+            assert same_record_bits(got[k], special_sums(z[a:a + n], 0j, lag)), (lag, a, n, got[k])
             assert got[k].tobytes()[:64] == bytes(64) and (got[k]["n_pairs"], got[k]["n_lagged"]) == (n, max(n - lag, 0)), (lag, a, n, got[k])
 
 
@@ -363,12 +350,12 @@ def test_subnormals_and_flt_max_every_field_by_its_bits(special):
         got = run_device(m, d_pairs, N_SPECIAL, jobs, lag, offset=0j)
         for k, (a, n) in enumerate(jobs):
             want = special_sums(z[a:a + n], 0j, lag)
-            assert same_record(got[k], want) and same_bits(got[k], want), (lag, a, n, got[k], want)
+            assert same_record(got[k], want) and same_record_bits(got[k], want), (lag, a, n, got[k], want)
             assert all(np.isfinite(got[k][f]) for f in M.NAMES + ("peak",)), (lag, a, n, got[k])
             if a + n <= at:
                 assert got[k]["p"] > 0.0 and got[k]["q"] > 0.0 and got[k]["peak"] >= 2.0 ** -298, (lag, a, n, got[k])
         host = np.frombuffer(m.run(z, table(jobs), 0j, lag), dtype=M.SUMS)
-        assert same_bits(host, got), lag
+        assert same_record_bits(host, got), lag
 
 
 # ---- end to end: a recording with a constant-envelope burst and a noise-like one
@@ -397,14 +384,6 @@ def bursts_recording():
     return np.clip(np.rint(raw), -128, 127).astype(np.int8).view(np.uint8)
 
 
-def pedestal(c):
-    """0.5 sum(c) over the taps as f32 values, added in order in f64: what a cut-out rests on, as fsea-cutouts computes it"""
-    total = 0.0
-    for v in np.asarray(c, dtype=np.float64).astype(np.float32).astype(np.float64):
-        total += float(v)
-    return 0.5 * total
-
-
 def test_end_to_end_a_constant_envelope_and_a_noise_like_burst():
     raw = bursts_recording()
     c = fsea.lowpass_taps(RATE, 0.4 * RATE / D, TAPS)
@@ -426,7 +405,7 @@ def test_end_to_end_a_constant_envelope_and_a_noise_like_burst():
     g_pairs.check("the extract's output")
     results = []
     for k, j in enumerate(mjobs):
-        assert same_bits(got[k], M.sums(pairs[j.first_pair:j.first_pair + j.n_pairs], off, lag)), k
+        assert same_record_bits(got[k], M.sums(pairs[j.first_pair:j.first_pair + j.n_pairs], off, lag)), k
         results.append(fsea.measure_finish(fsea.MeasureSums.from_buffer_copy(got[k].tobytes()), lag))
     fm, noise = results
     for name, r in (("fm", fm), ("noise", noise)):

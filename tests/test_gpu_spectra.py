@@ -19,6 +19,8 @@ from tests import extract_ref as X
 from tests import spectra_ref as R
 from tests.conftest import ROOT
 from tests.guarded import FILL, Guarded
+from tests.jobs_common import address, same_float_bits
+from tests.jobs_common import run_device as run_placed
 from tests.parity import PER_BIN_TOL
 
 pytestmark = pytest.mark.gpu
@@ -51,26 +53,8 @@ def laid_out(obj, jobs, gap=3):
 
 def run_device(obj, d_pairs, n_buffer, table, n_power, offset=OFFSET, stream=0, wait=None):
     """one call into a guarded output pre-filled with FILL -> one float32 array per job; no float outside the jobs' is written"""
-    g = Guarded(4 * n_power)
-    obj.run_device(d_pairs.addr, n_buffer, table, g.addr, n_power, offset=offset, stream=stream)
-    if wait is not None:
-        wait()
-    back = g.payload(np.float32, (n_power,))
-    g.check("the powers of %d jobs" % len(table))
-    g.free()
-    owned = np.zeros(n_power, bool)
-    out = []
-    for j in table:
-        k = obj.n if R.segments(j.n_pairs, obj.n, obj.hop) else 0
-        owned[j.out_first:j.out_first + k] = True
-        out.append(back[j.out_first:j.out_first + k].copy())
-    assert np.all(back[~owned].view(np.uint8) == FILL), "a float that no job owns was written"
-    return out
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    return run_placed(obj, d_pairs, n_buffer, table, n_power, lambda j: obj.n if R.segments(j.n_pairs, obj.n, obj.hop) else 0,
+                      "powers", stream, wait, offset=offset)
 
 
 def worst_over_bound(got, pairs, obj, window):
@@ -136,7 +120,7 @@ def test_the_table_does_not_change_a_bit(cutouts):
         for first in (0, 3001):
             table, n_power = laid_out(obj, [(first, m)], gap=0)
             alone[(first, m)] = run_device(obj, d, buf.size, table, n_power)[0]
-        assert same_bits(alone[(0, m)], alone[(3001, m)]), m        # either parity
+        assert same_float_bits(alone[(0, m)], alone[(3001, m)]), m        # either parity
         assert worst_over_bound(alone[(0, m)], data[:m], obj, fsea.window("hann", n)) <= 1.0
     rng = np.random.default_rng(12)
     jobs = [(int(rng.integers(0, 3000)), int(rng.integers(0, 2900))) for _ in range(300)]
@@ -151,7 +135,7 @@ def test_the_table_does_not_change_a_bit(cutouts):
     for at, k in enumerate(order):
         a, m = jobs[k]
         if (a, m) in alone:
-            assert same_bits(got[at], alone[(a, m)]), (a, m)
+            assert same_float_bits(got[at], alone[(a, m)]), (a, m)
             seen += 1
         elif at % 10 == 0:                                          # and the others are right too
             assert got[at].size == (n if m >= n else 0)
@@ -171,10 +155,10 @@ def test_the_lengths_round_one_segment(cutouts, n, hop):
     table, n_power = laid_out(obj, [(3, m) for m in ns])
     got = run_device(obj, d_pairs, z.size, table, n_power)          # run_device: the floats of no job keep their fill
     assert [g.size for g in got] == [0, 0, n, n, n]
-    assert same_bits(got[2], got[3])                                # the pairs behind the last whole segment are not read
+    assert same_float_bits(got[2], got[3])                                # the pairs behind the last whole segment are not read
     for m, g in zip(ns, got):
         assert worst_over_bound(g, z[3:3 + m], obj, None) <= 1.0
-    assert not same_bits(got[3], got[4])
+    assert not same_float_bits(got[3], got[4])
     obj.close()
 
 
@@ -198,7 +182,7 @@ def test_the_tile_seam(n, hop):
         got = run_device(obj, d, z.size, table, n_power)
         assert worst_over_bound(got[0], z[:n], obj, w) <= 1.0 and np.all(got[0] >= 0)
         for S, g in zip(counts, got):
-            assert same_bits(g, got[0]), (kind, S)
+            assert same_float_bits(g, got[0]), (kind, S)
         # and on pairs that do differ from segment to segment the seam keeps the bound
         obj.close()
     d.check("the input is read, not written")
@@ -226,7 +210,7 @@ def test_a_window_of_ones_gives_the_bits_of_none(cutouts, n):
         jobs = [(1, 3 * n), (4, n)]
         a = run_device(plain, d_pairs, z.size, *laid_out(plain, jobs))
         b = run_device(ones, d_pairs, z.size, *laid_out(ones, jobs))
-        assert all(same_bits(x, y) for x, y in zip(a, b)), kind
+        assert all(same_float_bits(x, y) for x, y in zip(a, b)), kind
         plain.close()
         ones.close()
 
@@ -255,9 +239,9 @@ def test_a_nan_pair_reaches_its_own_job_alone():
         assert np.flatnonzero(np.isnan(want)).tolist() == named, name
         assert np.flatnonzero(np.isnan(got[1])).tolist() == named, name
         if not named:
-            assert same_bits(got[1], clean[1]), name
+            assert same_float_bits(got[1], clean[1]), name
         if first + at >= n:                                         # the neighbour in front does not hold the pair
-            assert same_bits(got[0], clean[0]), name
+            assert same_float_bits(got[0], clean[0]), name
         assert got[2].size == 0
     g.check("the input is read, not written")
     g.free()
@@ -278,10 +262,10 @@ def test_the_host_form_gives_the_bits_of_the_device_form(cutouts):
         assert rc == 0, L_.fsea_last_error_string()
         owned = np.zeros(n_power, bool)
         for j, dev in zip(table, device):
-            assert same_bits(power[j.out_first:j.out_first + dev.size], dev)
+            assert same_float_bits(power[j.out_first:j.out_first + dev.size], dev)
             owned[j.out_first:j.out_first + dev.size] = True
         assert np.all(power[~owned].view(np.uint8) == FILL)         # only the jobs' ranges
-        assert all(same_bits(h, dev) for h, dev in zip(obj.run(z, table, OFFSET), device))
+        assert all(same_float_bits(h, dev) for h, dev in zip(obj.run(z, table, OFFSET), device))
         obj.close()
 
 
@@ -311,15 +295,11 @@ def test_two_streams_and_an_odd_pair_base(cutouts):
     for shift, table, n_power, g in runs:
         back = g.payload(np.float32, (max(n_power, 1),))
         for j, want in zip(table, ref[shift]):
-            assert same_bits(back[j.out_first:j.out_first + want.size], want), (shift, j.first_pair)
+            assert same_float_bits(back[j.out_first:j.out_first + want.size], want), (shift, j.first_pair)
         g.check("two streams")
         g.free()
     for o in (s1, s2, sync, obj):
         o.close()
-
-
-def address(tab):
-    return ctypes.addressof(tab) if tab is not None and len(tab) else None
 
 
 def test_refusals_name_the_job_and_write_nothing(cutouts):

@@ -14,7 +14,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPTS = os.path.join(ROOT, "scripts")
 MOVED = ["cfar_rate", "demod_rate", "detect_rate", "events_rate", "extract_rate", "interp_rate", "iq_chain_rate",
-         "iq_draw_rate", "persist_rate", "pfb_rate", "trace_rate", "zoom_rate", "fir_roofline"]
+         "iq_draw_rate", "persist_rate", "pfb_rate", "trace_rate", "zoom_rate", "fir_roofline", "measure_rate", "audio_rate"]
+CUTOUT_SCRIPTS = ["extract_rate", "measure_rate", "audio_rate"]     # they measure on ratelib.cutouts
 
 
 def load(name, monkeypatch):
@@ -230,8 +231,23 @@ def test_a_moved_script_imports_and_kept_no_copy(name, monkeypatch):
     module = load(name, monkeypatch)
     assert callable(module.main)
     assert module.ratelib.__file__ == os.path.join(SCRIPTS, "ratelib.py")
-    for gone in ("event_times", "timed", "rounds", "median_us", "step", "kernels"):
+    for gone in ("event_times", "timed", "rounds", "median_us", "step", "kernels", "release"):
         assert not hasattr(module, gone), "%s.py still has its own %s" % (name, gone)
+    if name in CUTOUT_SCRIPTS:
+        with open(os.path.join(SCRIPTS, name + ".py")) as f:
+            text = f.read()
+        for gone in ("ExtractJob(", "lowpass_taps(10e6", "torch"):
+            assert gone not in text, "%s.py still builds its own cut-outs: %s" % (name, gone)
+
+
+def test_cutout_jobs_are_the_scripts_jobs(ratelib):
+    from frequensea_amd import fsea
+    jobs = ratelib.cutout_jobs(fsea, 256, 65540)
+    assert len(jobs) == 256
+    for i, j in enumerate(jobs):
+        first = 131072 * i + 3 + i % 5
+        assert (j.first, j.n_samples, j.sample_offset, j.out_first) == (first, 65540, first, 0)
+        assert (j.cycles_per_sample, j.phase0_cycles) == ((i - 128) / 1024, 0.0)
 
 
 # ---- GPU tier: the plumbing of the three timing functions on the smallest launch of a real kernel
