@@ -166,6 +166,39 @@ def noise_cutout(n, seed=8, pedestal=0.5 + 0.5j):
     return (rng.normal(0.0, 1.0, n) + 1j * rng.normal(0.0, 1.0, n) + pedestal).astype(np.complex64)
 
 
+# ---- inputs whose spectra have a closed form that f32 gives exactly ---------------------------------------------------------------
+
+CONSTANT, IMPULSE = 2.0 - 0.25j, 4.0 - 2.0j       # halves and quarters: every term, square and fourth power is exact in f32
+
+
+def constant_pairs(m, offset=0j):
+    """m pairs that are all offset + CONSTANT"""
+    return np.full(m, complex(offset) + CONSTANT, np.complex64)
+
+
+def impulse_pairs(n, offset=0j):
+    """one segment: pair 0 is offset + IMPULSE, every other pair the offset alone"""
+    z = np.full(n, complex(offset), np.complex64)
+    z[0] = complex(offset) + IMPULSE
+    return z
+
+
+def constant_spectrum(n, kind, dtype=np.float32):
+    """The n powers of constant_pairs without a taper, any S and hop: x_j = (-1)^j (u, v), so X is n (u, v) in bin n / 2 and
+    +0 in every other.  (u, v) is kind_of in f32; with dtype float32 the power is n^2 (u u + v v) as f32 arithmetic rounds
+    it, which is what a transform that multiplies by no twiddle but 1 gives; with float64 it is the exact value."""
+    u, v = kind_of(np.float32([CONSTANT.real]), np.float32([CONSTANT.imag]), kind)
+    u, v = dtype(u[0]), dtype(v[0])
+    want = np.zeros(n, dtype)
+    want[n // 2] = dtype(n) * dtype(n) * (u * u + v * v)
+    return want
+
+
+def impulse_spectrum(n, dtype=np.float32):
+    """The n powers of impulse_pairs, kind Z, no taper: X[k] = IMPULSE for every k, |4 - 2i|^2 = 20"""
+    return np.full(n, IMPULSE.real ** 2 + IMPULSE.imag ** 2, dtype)
+
+
 def nan_bins(n_pairs, n, hop, at):
     """The bins of a job's output that a NaN in its pair `at` reaches: all n where a segment covers the pair, none otherwise."""
     S = segments(n_pairs, n, hop)

@@ -6,7 +6,9 @@ FFT paths' per-bin bound carried through the square.  A correct f32 transform us
 alone would hide a small mistake; the structural tests are where a kernel goes wrong: a job's bits alone, repeated, among
 hundreds of others and at either parity of first_pair; the lengths round one segment; the tile seam on inputs whose
 segments are all the same, where any S must give the bits of S = 1; a taper of ones; a NaN pair; the host form; two
-streams; refusals.  Small shapes only: n in {64, 256, 4096}.  Inputs and outputs are guarded."""
+streams; refusals.  Every one of the seven sizes runs in the parity, in both seam tests and in the closed forms: the radix-2
+pass is the only path of n = 128, 512, 2048, and 1024 is where a round becomes one segment.  Small shapes, but for the one
+job of FSEA_SPECTRA_MAX_PAIRS.  Inputs and outputs are guarded."""
 import ctypes
 import os
 import subprocess
@@ -28,7 +30,7 @@ pytestmark = pytest.mark.gpu
 OFFSET = 0.5 + 0.5j
 BIN = os.path.join(ROOT, "frequensea_amd", "bin")
 FSEA_EINVAL = -1
-SIZES = (64, 256, 4096)
+SIZES = (64, 128, 256, 512, 1024, 2048, 4096)
 SEGMENTS = 7                      # of a parity job
 SIGNAL_PAIRS = 4096 + (SEGMENTS - 1) * 4096 + 2
 POWER_TOL = 2.0 * PER_BIN_TOL * (1.0 + 1e-6)      # 4.000004e-6: if each segment's magnitude is within PER_BIN_TOL of its largest ...
@@ -39,7 +41,7 @@ def bound(scale):
 
 
 def hops(n):
-    return [n, n // 2, n // 4 + 3] + ([1] if n == 64 else [])
+    return [n, n // 2, n // 4 + 3] + ([1] if n in (64, 128) else [])      # 128: the smallest size with the radix-2 pass
 
 
 def laid_out(obj, jobs, gap=3):
@@ -100,16 +102,17 @@ def test_every_bin_lies_within_the_bound_of_the_restatement(cutouts, n, window):
                 print("n", n, window, "kind", kind, "hop", hop, "first", a, "worst error over the bound: %.4f" % over)
                 worst = max(worst, over)
             obj.close()
+    print("n", n, window, "worst of all kinds and hops: %.4f" % worst)
     assert worst <= 1.0
 
 
 # ---- structure ----------------------------------------------------------------------------------------------------------------
 
-def test_the_table_does_not_change_a_bit(cutouts):
+@pytest.mark.parametrize("n,hop", [(256, 77), (128, 45)])
+def test_the_table_does_not_change_a_bit(cutouts, n, hop):
     """The same spans alone, twice in one table, among 300 mixed-length jobs in a shuffled order, and the same pairs at an odd
-    and at an even first_pair: identical bits per job."""
+    and at an even first_pair: identical bits per job.  At 128 a round is eight segments and ends in the radix-2 pass."""
     z, _ = cutouts
-    n, hop = 256, 77
     data = z[5:5 + 3000]
     buf = np.concatenate([data, z[:1], data])                      # the same pairs from pair 0 and from pair 3001
     d = Guarded(buf.nbytes).upload(buf)
@@ -146,7 +149,7 @@ def test_the_table_does_not_change_a_bit(cutouts):
     obj.close()
 
 
-@pytest.mark.parametrize("n,hop", [(64, 1), (64, 37), (256, 128), (4096, 4096), (4096, 1001)])
+@pytest.mark.parametrize("n,hop", [(64, 1), (64, 37), (256, 128), (4096, 4096), (4096, 1001), (128, 1), (512, 511), (1024, 1024), (2048, 3)])
 def test_the_lengths_round_one_segment(cutouts, n, hop):
     z, d_pairs = cutouts
     obj = fsea.Spectra(n, hop, "sq")
@@ -162,7 +165,7 @@ def test_the_lengths_round_one_segment(cutouts, n, hop):
     obj.close()
 
 
-@pytest.mark.parametrize("n,hop", [(64, 16), (256, 3), (4096, 2048)])
+@pytest.mark.parametrize("n,hop", [(64, 16), (256, 3), (4096, 2048), (128, 24), (512, 7), (1024, 512), (2048, 100)])
 def test_the_tile_seam(n, hop):
     """Pairs with the period of the hop: every segment is the same, its power p an f32, and S p is exact in f64 for any S
     here -- so the average is p itself, bit for bit, for every S: one short of a tile, a tile, one more, two tiles and one.
@@ -189,17 +192,93 @@ def test_the_tile_seam(n, hop):
     d.free()
 
 
-def test_the_tile_seam_on_segments_that_differ(cutouts):
+@pytest.mark.parametrize("n", SIZES)
+def test_the_tile_seam_on_segments_that_differ(cutouts, n):
+    """A round is G = max(1, 1024 / n) segments, a tile T = 32 of them: 2, 4, 8, 16 or 32 rounds.  Jobs that end one short of
+    a round, with it, one behind it, behind the second, and the same round a tile, in one table at an odd first_pair, on
+    segments that differ: a segment dropped, doubled or read from a neighbour's place in the LDS image moves a bin by
+    percent of the scale, and the bound is 4e-6 of it."""
     z, d_pairs = cutouts
     T = fsea.SPECTRA_TILE_SEGMENTS
-    n, hop = 64, 5
-    obj = fsea.Spectra(n, hop, "env")
-    jobs = [(2, n + (S - 1) * hop) for S in (T - 1, T, T + 1)]
+    G = max(1, 1024 // n)
+    counts = sorted({S for S in (1, G - 1, G, G + 1, 2 * G + 1, T - 1, T, T + 1) if S > 0})
+    hop = 5 if n <= 512 else 37
+    obj = fsea.Spectra(n, hop, "fourth" if (n.bit_length() - 1) % 2 else "env")
+    jobs = [(3, n + (S - 1) * hop) for S in counts]
+    assert [obj.segments(m) for _, m in jobs] == counts and 3 + n + T * hop <= SIGNAL_PAIRS
     table, n_power = laid_out(obj, jobs)
     got = run_device(obj, d_pairs, z.size, table, n_power)
-    for (a, m), g in zip(jobs, got):
-        assert worst_over_bound(g, z[a:a + m], obj, None) <= 1.0
+    for S, (a, m), g in zip(counts, jobs, got):
+        over = worst_over_bound(g, z[a:a + m], obj, None)
+        print("n", n, "G", G, "S", S, "worst error over the bound: %.4f" % over)
+        assert over <= 1.0, (n, S)
     obj.close()
+
+
+def test_the_longest_job_the_checks_accept():
+    """One buffer of FSEA_SPECTRA_MAX_PAIRS pairs with the period of the hop, so every segment has the same f32 power p and
+    S p is exact in f64 (S < 2^29): the one-segment job, the job of all 2^24 pairs and the one that begins a hop later and
+    ends with the buffer have the same bits -- at (64, 16) through 1,048,573 segments in 32,768 tiles, sixteen segments a
+    round; at (2048, 2048) through 8,192 segments in 256 tiles, a segment a round and the radix-2 pass.  The segment and
+    tile arithmetic of the kernel and the fold's loop run at the largest counts the checks let through; one pair more is
+    refused."""
+    M = fsea.SPECTRA_MAX_PAIRS
+    assert M == 1 << 24
+    d = Guarded(8 * M)
+    L_ = fsea.hip_lib()
+    for n, hop, segments, tiles in ((64, 16, 1048573, 32768), (2048, 2048, 8192, 256)):
+        z = np.tile(R.noise_cutout(hop, seed=60 + n), M // hop)
+        assert z.size == M
+        d.upload(z)
+        w = fsea.window("hann", n)
+        obj = fsea.Spectra(n, hop, "z", w)
+        assert obj.segments(M) == R.segments(M, n, hop) == segments and -(-segments // fsea.SPECTRA_TILE_SEGMENTS) == tiles
+        jobs = [(0, n), (0, M), (hop, M - hop)]
+        assert obj.segments(M - hop) == R.segments(M - hop, n, hop) == segments - 1
+        table, n_power = laid_out(obj, jobs)
+        got = run_device(obj, d, M, table, n_power)
+        over = worst_over_bound(got[0], z[:n], obj, w)
+        print("n", n, "hop", hop, "S = 1, worst error over the bound: %.4f" % over)
+        assert over <= 1.0 and np.all(got[0] >= 0)
+        assert same_float_bits(got[1], got[0]), (n, "all of the buffer")
+        assert same_float_bits(got[2], got[0]), (n, "to the end of the buffer")
+        # one pair more than the longest: refused by name, in a buffer that is too short for it and in one that is not (the
+        # pair behind the payload is the guard band's, allocated), and no float is written
+        g = Guarded(4 * n_power)
+        for n_buffer, word in ((M, b"job 1: pairs 0 .. 0 + 16777217 lie past"), (M + 1, b"job 1: n_pairs 16777217 too large")):
+            tab = (fsea.SpectraJob * 2)(fsea.SpectraJob(0, n, 0), fsea.SpectraJob(0, M + 1, n))
+            rc = L_.fsea_spectra_run_device(obj._p, d.addr, n_buffer, address(tab), 2, OFFSET.real, OFFSET.imag, g.addr, n_power, None)
+            assert rc == FSEA_EINVAL and word in L_.fsea_last_error_string(), (rc, L_.fsea_last_error_string())
+        assert np.all(g.payload(np.uint8, (4 * n_power,)) == FILL)
+        g.check("a refused call")
+        g.free()
+        obj.close()
+    d.check("the input is read, not written")
+    d.free()
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_constant_pairs_and_an_impulse_give_their_closed_forms_bit_for_bit(n):
+    """Constant pairs: (-1)^j puts all of a segment in bin n / 2; pass 0 adds four equal values and from there on every
+    non-zero value meets the twiddle 1 alone, so bin n / 2 is n^2 (u u + v v) in f32 and every other bin +0, for each kind.
+    One impulse in pair 0: pass 0 copies it to four places, every later butterfly adds zeros to it, and each of the n bins is
+    |4 - 2i|^2 = 20.  A bin that is not written, a twiddle where none belongs or a value from another place shows in the bits."""
+    hop, S = 5, 4
+    m = n + (S - 1) * hop
+    z = np.concatenate([R.constant_pairs(m, OFFSET), R.impulse_pairs(n, OFFSET)])
+    d = Guarded(z.nbytes).upload(z)
+    for kind in R.KINDS:
+        obj = fsea.Spectra(n, hop, kind)
+        jobs = [(0, m)] + ([(m, n)] if kind == R.Z else [])
+        assert obj.segments(m) == S
+        got = run_device(obj, d, z.size, *laid_out(obj, jobs))
+        want = R.constant_spectrum(n, kind)
+        assert same_float_bits(got[0], want), (n, kind, got[0][n // 2], want[n // 2], np.flatnonzero(got[0].view(np.uint32) != want.view(np.uint32))[:8])
+        if kind == R.Z:
+            assert same_float_bits(got[1], R.impulse_spectrum(n)), (n, np.flatnonzero(got[1] != 20.0)[:8])
+        obj.close()
+    d.check("the input is read, not written")
+    d.free()
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -251,7 +330,7 @@ def test_a_nan_pair_reaches_its_own_job_alone():
 def test_the_host_form_gives_the_bits_of_the_device_form(cutouts):
     z, d_pairs = cutouts
     L_ = fsea.hip_lib()
-    for n, hop, kind in ((64, 32, "env"), (4096, 4000, "z")):
+    for n, hop, kind in ((64, 32, "env"), (4096, 4000, "z"), (512, 300, "sq"), (2048, 2048, "fourth")):
         obj = fsea.Spectra(n, hop, kind, fsea.window("hann", n))
         jobs = [(1, 3 * n + 5), (0, n - 1), (z.size - 2 * n, 2 * n), (7, 0), (2, n)]
         table, n_power = laid_out(obj, jobs, gap=5)
@@ -395,3 +474,19 @@ def test_tool_finds_the_fourth_power_line_of_a_qpsk_burst(tmp_path):
     want, _ = R.spectrum(y, 256, 128, R.FOURTH, fsea.window("hann", 256), complex(pedestal, pedestal))
     f = R.finish(want.astype(np.float32), 2, 0.99)
     assert int(fields[1]) == R.segments(y.size, 256, 128) and abs(f["peak_cycles"] * pair_rate - line_hz) <= 1e-3 * pair_rate / 256
+    # once more at 512 bins, the plain kind: the radix-2 pass from the command line; the guard of z is 0
+    out = tmp_path / "z512"
+    r = subprocess.run(common + ["--out", str(out), "--spectra", "512", "--spectra-kind", "z"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    print(r.stdout, open(out / "spectra.txt").read())
+    assert r.stdout == plain.stdout.rstrip("\n") + " spectra 1\n" and r.stderr == plain.stderr
+    assert sorted(os.listdir(out)) == after
+    for f in before:
+        assert open(tmp_path / "plain" / f, "rb").read() == open(out / f, "rb").read(), f
+    lines = open(out / "spectra.txt").read().splitlines()
+    assert len(lines) == 1
+    fields = lines[0].split()
+    assert int(fields[0]) == number and len(fields) == 6 and int(fields[1]) == R.segments(y.size, 512, 256) >= 1
+    want, _ = R.spectrum(y, 512, 256, R.Z, fsea.window("hann", 512), complex(pedestal, pedestal))
+    f = R.finish(want.astype(np.float32), 0, 0.99)
+    assert abs(f["peak_cycles"] * pair_rate - float(fields[4])) <= 1e-3 * pair_rate / 512

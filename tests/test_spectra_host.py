@@ -143,6 +143,26 @@ def test_the_nonlinear_lines_of_psk_stand_where_the_theory_puts_them():
     assert abs(plain["centroid_cycles"] - f) < 0.01 and abs(plain["obw_centre_cycles"] - f) < 0.02 and 1 / 8 < plain["obw_bins"] / n < 0.6
 
 
+@pytest.mark.parametrize("n", [64, 128, 256, 512, 1024, 2048, 4096])
+def test_the_closed_forms_the_gpu_tier_expects_are_the_restatements(n):
+    """tests/test_gpu_spectra.py holds the device to constant_spectrum and impulse_spectrum bit for bit.  Here, without a GPU:
+    the restatement gives the exact (float64) forms within 1e-12 of the peak in every bin, and the float32 forms are those
+    rounded once -- for z^4, u u + v v = 17850625 / 65536 needs 25 bits, so its f32 form stands 2^-25 off the exact value."""
+    offset, hop, S = 0.5 + 0.5j, 5, 4
+    for kind in R.KINDS:
+        got, scale = R.spectrum(R.constant_pairs(n + (S - 1) * hop, offset), n, hop, kind, None, offset)
+        exact, want = R.constant_spectrum(n, kind, np.float64), R.constant_spectrum(n, kind)
+        u, v = R.kind_of(np.float32([2.0]), np.float32([-0.25]), kind)
+        assert want.dtype == np.float32 and want[n // 2] == np.float32(n) ** 2 * (u[0] * u[0] + v[0] * v[0])
+        assert exact[n // 2] == float(n) ** 2 * (float(u[0]) ** 2 + float(v[0]) ** 2) and np.count_nonzero(exact) == np.count_nonzero(want) == 1
+        assert got.shape == (n,) and np.max(np.abs(got - exact)) <= 1e-12 * exact[n // 2] and abs(scale / exact[n // 2] - 1.0) <= 1e-12
+        assert np.array_equal(exact.astype(np.float32), want) and not np.any(np.signbit(want))
+        assert (exact[n // 2] == want[n // 2]) == (kind != R.FOURTH)
+    got, _ = R.spectrum(R.impulse_pairs(n, offset), n, hop, R.Z, None, offset)
+    assert np.max(np.abs(got - 20.0)) <= 20.0 * 1e-12
+    assert np.array_equal(R.impulse_spectrum(n), np.full(n, 20.0, np.float32)) and np.all(R.impulse_spectrum(n, np.float64) == 20.0)
+
+
 # ---- fsea_spectra_finish -----------------------------------------------------------------------------------------------------
 
 def same(a, b):
